@@ -17,12 +17,24 @@ of every kernel), 8 groups in flight on separate streams.  Every result is that 
 bit for bit (tests/test_gpu_group.py).  --mode streams is round 1's form of the same work: pl_ransac_run from 16 host
 threads with one HIP stream each (about 15 % slower: ~15 small launches per problem compete on 16 hardware queues).
 A hypothesis = one minimal-solver model scored against all N correspondences (ransac_impl.h:112-113).
-The same K steps are then run for the metric's second half and the other BASELINE configs (config.secondary:
-relpose_5000 = configs[2], fund_10000 / hom_10000 = configs[3]), each with its own value / roofline / parity / CPU
-baseline.  Multi-GPU: independent image pairs, one set per rank (weak scaling, no data-path collective); RCCL is used
-for the barrier and the final gather only.
+Multi-GPU: independent image pairs, one set per rank (weak scaling, no data-path collective); RCCL is used for the
+barrier and the final gather only.
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps of the primary workload and prints the line (value, ms_per_step and
+the workload's configuration); nothing else runs.
+
+    --dump-outputs DIR   after the timed steps, what the last timed step returned to its caller, as float64 .npy files
+                         (model, inliers as 0 / 1 in float32, the per-problem RANSAC statistics; a fixed sample of the
+                         problems where the masks would exceed 64 MB, problem_index.npy says which).  The inputs are
+                         seeded: the same arguments give the same problems in every run, so two builds compare output
+                         for output.
+    --full               everything else the benchmark measures and checks: the same K steps for the metric's second
+                         half and the other BASELINE configs (relpose_5000 = configs[2], fund_10000 / hom_10000 =
+                         configs[3], the undistortion stage, p3p_200 at default options, the focal estimators, the mixed
+                         batch of configs[4]), each with its own value / roofline / parity / CPU baseline, and the
+                         blocks below.  --no-secondary / --no-parity / --no-cpu-baseline trim a --full run.
+
+The JSON line of a --full run also carries
   parity       : the GPU results of RANSAC seeds 0..7 of the first timed step against the CPU oracle's runs of the same
                  seeds (the runs that also give cpu_baseline): iterations, refinements, hypotheses, inlier count and
                  mask must be identical, models within 1e-6.  A mismatch makes the exit code non-zero.
@@ -303,6 +315,8 @@ def run_workload(name, args, ranks, P, synth, pool_factory, primary):
         for sd in [1000 + w for w in range(args.warmup)] + list(range(args.steps)):
             batches[sd] = P.RansacBatch([prob_of(j) for j in range(PPS)], [options(sd * PPS + j) for j in range(PPS)])
 
+    last_results = []  # --mode streams: what the most recent step returned, (model, info) per problem
+
     def step(seed):
         """a batch of PPS independent problems (RANSAC seeds seed * PPS + j).  Grouped: see above; --mode streams: worked
         through by S host threads / HIP streams, i.e. S problems in flight on this GPU at any time.
@@ -310,28 +324,31 @@ def run_workload(name, args, ranks, P, synth, pool_factory, primary):
         if grouped:
             batches[seed].run(T, G)
             return batches[seed].stats()
-        return [info for _, info in pool.map(run_one, [(prob_of(j), seed * PPS + j) for j in range(PPS)])]
+        last_results[:] = pool.map(run_one, [(prob_of(j), seed * PPS + j) for j in range(PPS)])
+        return [info for _, info in last_results]
 
     def field(st, name):
         return st[name] if isinstance(st, dict) else getattr(st, name)
 
     for w in range(args.warmup):
         step(1000 + w)
-    # the dominant kernel with the device to itself (4 problems one after the other, outside the timed region)
-    ranks.barrier()
     solo_ms, solo_launches, solo_hyp = 0.0, 0, 0
-    # (ONE worker thread for all twelve: every host thread has a context of its own, and a context's first launch runs on freshly
-    # allocated buffers - 250 instead of 125 us for k_score_mfma<10>, scripts/exp/solo_launch_probe.py; taken from the pool's S
-    # threads as they came, the four measured launches were first launches of some threads: 0.17 - 0.23 ms in round 6's first line)
-    solo_pool = pool_factory(1)
-    for j in range(12):  # the first eight only bring the clocks up (an idle device starts these launches ~10 % slower)
-        _, info = solo_pool.submit(run_one, (probs[0], 7000 + j)).result()
-        if j < 8:
-            continue
-        solo_ms += info["score_kernel_ms"]
-        solo_launches += info["score_kernel_launches"]
-        solo_hyp += info["hypotheses"]
-    solo_pool.shutdown()
+    if args.full:
+        # the dominant kernel with the device to itself (4 problems one after the other, outside the timed region): the
+        # roofline's runs of their own
+        ranks.barrier()
+        # (ONE worker thread for all twelve: every host thread has a context of its own, and a context's first launch runs on freshly
+        # allocated buffers - 250 instead of 125 us for k_score_mfma<10>, scripts/exp/solo_launch_probe.py; taken from the pool's S
+        # threads as they came, the four measured launches were first launches of some threads: 0.17 - 0.23 ms in round 6's first line)
+        solo_pool = pool_factory(1)
+        for j in range(12):  # the first eight only bring the clocks up (an idle device starts these launches ~10 % slower)
+            _, info = solo_pool.submit(run_one, (probs[0], 7000 + j)).result()
+            if j < 8:
+                continue
+            solo_ms += info["score_kernel_ms"]
+            solo_launches += info["score_kernel_launches"]
+            solo_hyp += info["hypotheses"]
+        solo_pool.shutdown()
     ranks.barrier()
     t0 = time.perf_counter()
     hyp = nan_hyp = launches = 0
@@ -350,11 +367,17 @@ def run_workload(name, args, ranks, P, synth, pool_factory, primary):
         last_inliers = field(res[-1], "num_inliers")
     ranks.barrier()
     elapsed = time.perf_counter() - t0
+    # what the last timed step returned to its caller (--dump-outputs; rank 0 writes it)
+    outputs = None
+    if args.dump_outputs and primary and ranks.rank == 0 and args.steps > 0:
+        outputs = batches[args.steps - 1].results() if grouped else list(last_results)
     # RANSAC seeds 0..7 of the first timed step: the ones the oracle runs below
-    if grouped:
-        first = batches[0].results(PARITY_SEEDS)
-    else:
-        first = [pool.submit(run_one, (prob_of(j), j)).result() for j in range(PARITY_SEEDS)] if first_streams is not None else None
+    first = None
+    if not args.no_parity:
+        if grouped:
+            first = batches[0].results(PARITY_SEEDS)
+        else:
+            first = [pool.submit(run_one, (prob_of(j), j)).result() for j in range(PARITY_SEEDS)] if first_streams is not None else None
     batches.clear()
     for pr in probs:
         pr.close()
@@ -363,7 +386,7 @@ def run_workload(name, args, ranks, P, synth, pool_factory, primary):
            float(solo_launches), float(solo_hyp)]
     ctx = {"A": A, "B": Bpts, "parity_scenes": [scenes[j % NS] for j in range(PARITY_SEEDS)], "thr": thr, "first": first, "PPS": PPS, "S": S, "kind": KIND, "n": N_POINTS,
            "bytes_per_corr": BYTES_PER_CORR, "descr": DESCR, "outliers": OUTLIER_RATIO, "max_error_px": MAX_ERROR_PX,
-           "shard_problem": shard_problem, "grouped": grouped, "G": G, "T": T, "scenes": NS}
+           "shard_problem": shard_problem, "grouped": grouped, "G": G, "T": T, "scenes": NS, "outputs": outputs}
     return rec, ctx
 
 
@@ -417,6 +440,29 @@ def parity_block(kind, gpu_first, cpu_out):
     for k, v in worst.items():
         out["max_" + k] = v
     return out
+
+
+DUMP_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+DUMP_STATS = ("iterations", "refinements", "num_inliers", "inlier_ratio", "model_score", "hypotheses")
+
+
+def dump_outputs(directory, kind, results):
+    """--dump-outputs: what the last timed step returned to its caller, one row per problem - model.npy (poses: q, t;
+    F / H: row-major), inliers.npy (0 / 1, float32), one float64 file per RANSAC statistic in DUMP_STATS.  Where that
+    would exceed DUMP_BYTES a fixed, seeded sample of the problems is written; problem_index.npy says which."""
+    n = len(results)
+    n_points = len(results[0][1]["inliers"]) if n else 0
+    row_bytes = 4 * n_points + 8 * (len(model_vec(kind, results[0][0])) + len(DUMP_STATS) + 1) if n else 1
+    keep = max(1, (DUMP_BYTES - (1 << 16)) // row_bytes)
+    idx = np.arange(n) if n <= keep else np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+    arrays = {"problem_index": idx.astype(np.float64),
+              "model": np.array([model_vec(kind, results[i][0]) for i in idx], dtype=np.float64),
+              "inliers": np.array([results[i][1]["inliers"] for i in idx], dtype=np.float32)}
+    for f in DUMP_STATS:
+        arrays[f] = np.array([results[i][1][f] for i in idx], dtype=np.float64)
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def report_workload(name, table, ctx, args, world):
@@ -487,6 +533,8 @@ def report_workload(name, table, ctx, args, world):
     roof["note"] = ("the correspondences are register/LDS-resident: physical HBM traffic per launch (traffic, PMC) is "
                     "orders of magnitude below the SURVEY 8d 'as if every hypothesis streamed the set' count "
                     "(algorithmic_bytes_per_launch), so the binding roof is vector-ALU issue, not HBM")
+    if not args.full:  # the roofline is priced on the solo launches, which only a --full run makes
+        roof = None
     out = {"value": value, "unit": "hypotheses/s", "ms_per_step": 1e3 * t_max / args.steps,
            "problem": ctx["descr"], "correspondences": n_points, "outlier_ratio": ctx["outliers"],
            "max_iterations": ITERATIONS, "min_iterations": ITERATIONS, "max_error_px": ctx["max_error_px"],
@@ -977,7 +1025,14 @@ def main():
     ap.add_argument("--detail-file", default="", help="complete per-workload reports (default gpurun_out/bench_detail.json)")
     ap.add_argument("--rehearse-distributed", action="store_true",
                     help="launch / rendezvous / gather path only, no GPU work, prints no measurement (CPU test)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary workloads, the roofline's solo launches, parity against the oracle and the CPU "
+                         "baselines (a plain run times the primary workload only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step of the primary workload returned as DIR/<name>.npy")
     args = ap.parse_args()
+    if not args.full:  # a plain run: only what the headline figure needs
+        args.no_secondary = args.no_parity = args.no_cpu_baseline = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
@@ -1004,6 +1059,8 @@ def main():
         rec, ctx = run_workload(name, args, ranks, P, synth, pool_factory, primary=(i == 0))
         table = ranks.gather(rec)  # final gather over RCCL
         if ranks.rank == 0:
+            if ctx["outputs"] is not None:
+                dump_outputs(args.dump_outputs, ctx["kind"], ctx["outputs"])
             reports[name], ok = report_workload(name, table, ctx, args, ranks.world)
             all_ok = all_ok and ok
 
@@ -1116,7 +1173,7 @@ def main():
             "dtype": "f64",
             "data": "synthetic",
             "config": cfg,
-            "roofline": short(prim["roofline"], ("peak_basis", "frac_basis", "note", "traffic_source")),
+            "roofline": short(prim["roofline"], ("peak_basis", "frac_basis", "note", "traffic_source")) if prim["roofline"] else None,
             "parity": short(prim["parity"], ("against",)) if prim.get("parity") else None,
         }
         if "cpu_baseline" in prim:

@@ -1,10 +1,14 @@
 """The coefficient / elimination-template tables of the two focal-length solvers (poselib_amd/csrc/pl_focal_templates.h,
 oracle/src/focal_templates.inc) are GENERATED from the solvers' equations by scripts/gen_focal_templates.py.  CPU tests:
   * the committed tables are what the generator writes (nobody edited them by hand, product and oracle hold the same data);
-  * where the reference's sources are present (this container): every one of the reference's 235 + 280 coefficient formulas
-    (solvers/p35pf.cc:89-520, solvers/relpose_6pt_focal.cc:58-1030) is, term for term and in the written order, what the generator
-    derived from the equations, and the reference's index tables place the same coefficients at the same matrix positions - the
-    restatement is the reference's template, not merely a solver with the same roots."""
+  * every one of the reference's 235 + 280 coefficient formulas (solvers/p35pf.cc:89-520, solvers/relpose_6pt_focal.cc:58-1030)
+    is, term for term and in the written order, what the generator derived from the equations, and the reference's index tables
+    place the same coefficients at the same matrix positions - the restatement is the reference's template, not merely a solver
+    with the same roots.  Where the reference's sources are present they are parsed and compared directly; everywhere the
+    generator's terms and positions are checked against digests recorded from those sources
+    (tests/golden/focal_templates_ref_v1.json, written by tests/golden/make_focal_template_digests.py)."""
+import hashlib
+import json
 import os
 import re
 import sys
@@ -16,6 +20,7 @@ sys.path.insert(0, os.path.join(ROOT, "scripts"))
 import gen_focal_templates as G  # noqa: E402
 
 REF = "/root/reference/PoseLib/solvers"
+GOLDEN = os.path.join(ROOT, "tests", "golden", "focal_templates_ref_v1.json")
 
 
 def test_committed_tables_are_the_generators_output(tmp_path):
@@ -64,24 +69,54 @@ def _table(src, name):
     return [int(x) for x in m.group(1).replace("\n", " ").split(",")]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="/root/reference absent")
-@pytest.mark.parametrize("which", ["p35pf", "six"])
-def test_generated_templates_are_the_references(which):
+def _digest(obj):
+    """SHA-256 (first 16 hex digits) of a term list / position list in a canonical JSON form"""
+    return hashlib.sha256(json.dumps(obj, separators=(",", ":")).encode()).hexdigest()[:16]
+
+
+def _canonical(formulas, entries):
+    """{"coeffs": {k: digest of [[multiplier, [indices ...]], ...]}, "entries": digest of the sorted (row, col, coefficient)}"""
+    return {"n_coeffs": len(formulas),
+            "coeffs": {str(k): _digest([[m, list(idx)] for m, idx in terms]) for k, terms in sorted(formulas.items())},
+            "n_entries": len(entries), "entries": _digest(sorted(list(e) for e in entries))}
+
+
+def _reference_form(which):
+    """the reference's coefficient formulas {k: terms} and template positions {(row, col, coefficient)}, parsed from its sources"""
     if which == "p35pf":
         src = open(os.path.join(REF, "p35pf.cc")).read()
-        tb, rows = G.p35_tables(), 25
+        rows = 25
         formulas = _formulas(src, "double coeffs[235];", "static const int coeffs0_ind")
     else:
         src = open(os.path.join(REF, "relpose_6pt_focal.cc")).read()
-        tb, rows = G.six_tables(), 31
+        rows = 31
         formulas = _formulas(src, "Eigen::VectorXd coeffs(280);", "static const int coeffs0_ind")
-    assert len(formulas) == len(tb["coeffs"])
-    for k, expr in formulas.items():
-        mine = [(tb["coeffs"][k][t], t) for t in sorted(tb["coeffs"][k], key=G.term_key)]
-        assert _terms(expr) == mine, (which, k)
     ref_entries = set()
     for ci, pos in zip(_table(src, "coeffs0_ind"), _table(src, "C0_ind")):
         ref_entries.add((pos % rows, pos // rows, ci))
     for ci, pos in zip(_table(src, "coeffs1_ind"), _table(src, "C1_ind")):
         ref_entries.add((pos % rows, rows + pos // rows, ci))
-    assert ref_entries == set(tb["entries"])
+    return {k: _terms(expr) for k, expr in formulas.items()}, ref_entries
+
+
+def _generated_form(which):
+    tb = G.p35_tables() if which == "p35pf" else G.six_tables()
+    formulas = {k: [(tb["coeffs"][k][t], t) for t in sorted(tb["coeffs"][k], key=G.term_key)] for k in range(len(tb["coeffs"]))}
+    return formulas, set(tb["entries"])
+
+
+@pytest.mark.parametrize("which", ["p35pf", "six"])
+def test_generated_templates_are_the_references(which):
+    mine, entries = _generated_form(which)
+    if os.path.isdir(REF):  # the reference's sources themselves
+        formulas, ref_entries = _reference_form(which)
+        assert len(formulas) == len(mine)
+        for k, terms in formulas.items():
+            assert terms == mine[k], (which, k)
+        assert ref_entries == entries
+    rec = json.load(open(GOLDEN))[which]  # what those sources held when the digests were recorded
+    got = _canonical(mine, entries)
+    assert got["n_coeffs"] == rec["n_coeffs"] and got["n_entries"] == rec["n_entries"]
+    for k, d in rec["coeffs"].items():
+        assert got["coeffs"][k] == d, (which, k)
+    assert got["entries"] == rec["entries"]
