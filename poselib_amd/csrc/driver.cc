@@ -125,8 +125,6 @@ struct Context {
     const double *raw_src_a = nullptr, *raw_src_b = nullptr; // where the raw correspondences of the last make_problem_prepared live (device-visible)
     HostBuf h_absmax, h_positions, h_num_models, h_count, h_score, h_tasks, h_gather_idx, h_gather_out, h_mask,
         h_small, h_models;
-    HostBuf h_flag;        // completion flag of wait_stream(): the stream writes a sequence number, the host spins on it
-    uint32_t flag_seq = 0;
 };
 
 constexpr uint32_t kIotaEntries = 4097;
@@ -189,10 +187,6 @@ int get_context(Context **out) {
         HIP_TRY(c->iota.ensure(sizeof(uint32_t) * kIotaEntries));
         HIP_TRY(hipMemcpy(c->iota.p, iota.data(), sizeof(uint32_t) * kIotaEntries, hipMemcpyHostToDevice));
     }
-    if (c->h_flag.ensure(64) == hipSuccess)
-        *c->h_flag.as<uint32_t>() = 0;
-    else
-        (void)hipGetLastError(); // (wait_stream falls back to hipStreamSynchronize)
     guard.c = nullptr;
     g_ctx = c;
     *out = c;
@@ -209,21 +203,14 @@ int get_context(Context **out) {
 
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-// Wait for everything enqueued on the context's stream.  Default: hipStreamSynchronize.  POSELIB_AMD_SPIN_SYNC=1: the
-// stream itself writes a sequence number into pinned host memory behind the work (hipStreamWriteValue32: ordered like a
-// kernel) and the host spins on that word (after 2 ms without progress it yields between polls, after 5 s it falls back
-// to hipStreamSynchronize, which also reports a device fault instead of spinning for ever).  Measured on MI355X: one
-// problem at a time 0.768 -> 0.743 ms per 100000-iteration P3P problem (three synchronisations each), but -13 % on the
-// grouped batch (8 host threads) and -1 % with 16 problems in flight - the runtime's own wait already polls - so it is
-// opt-in for latency-bound single-problem use.
 // POSELIB_AMD_GROUP_TIMING=1 (diagnostic): pl_estimate_batch reports where its workers' time went - waiting for the device,
 // in the per-item preparation, in fallback items - on stderr
 std::atomic<uint64_t> g_t_wait_ns{0}, g_t_group_ns{0}, g_t_prep_ns{0}, g_t_fallback_ns{0}, g_n_waits{0}, g_n_fallback{0};
 const bool g_group_timing = std::getenv("POSELIB_AMD_GROUP_TIMING") != nullptr;
-hipError_t wait_stream_impl(Context *c);
 // host work a worker of pl_estimate_batch does INSTEAD of idling at its next wait (staging the next group's inputs); one shot
 thread_local std::function<void()> g_wait_hook;
 thread_local std::vector<double> g_wait_marks; // (diagnostic) end of every wait of this worker's current job, seconds
+// Wait for everything enqueued on the context's stream.
 hipError_t wait_stream(Context *c) {
     if (g_wait_hook) {
         std::function<void()> h;
@@ -231,44 +218,15 @@ hipError_t wait_stream(Context *c) {
         h();
     }
     if (!g_group_timing)
-        return wait_stream_impl(c);
+        return hipStreamSynchronize(c->stream);
     const double t0 = now_s();
-    const hipError_t e = wait_stream_impl(c);
+    const hipError_t e = hipStreamSynchronize(c->stream);
     const double t1 = now_s();
     g_t_wait_ns += (uint64_t)((t1 - t0) * 1e9);
     ++g_n_waits;
     g_wait_marks.push_back(t0);
     g_wait_marks.push_back(t1);
     return e;
-}
-hipError_t wait_stream_impl(Context *c) {
-    static const bool spin = std::getenv("POSELIB_AMD_SPIN_SYNC") != nullptr;
-    if (!spin || !c->h_flag.p)
-        return hipStreamSynchronize(c->stream);
-    const uint32_t seq = ++c->flag_seq;
-    hipError_t e = hipStreamWriteValue32(c->stream, c->h_flag.dp, seq, 0);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return hipStreamSynchronize(c->stream);
-    }
-    volatile uint32_t *flag = c->h_flag.as<volatile uint32_t>();
-    const double t0 = now_s();
-    for (uint64_t spins = 0;; ++spins) {
-        if (*flag == seq) {
-            std::atomic_thread_fence(std::memory_order_acquire); // (what the kernels wrote to pinned memory is read after this)
-            return hipSuccess;
-        }
-        if ((spins & 0xfff) == 0xfff) {
-            const double dt = now_s() - t0;
-            if (dt > 5.0)
-                return hipStreamSynchronize(c->stream);
-            if (dt > 2e-3)
-                std::this_thread::yield();
-        }
-#if defined(__x86_64__)
-        __builtin_ia32_pause();
-#endif
-    }
 }
 
 } // namespace
@@ -788,9 +746,8 @@ struct RansacRun {
     static constexpr double kSignTieGap = 2e-15; // (9 ulps of the score: the tree order moves a converged model's score by an ulp or two)
     static constexpr uint32_t kSignTieMaxPoints = 4096;
     int resolve_sign_tie(RefineJob &job) {
-        static const bool off = std::getenv("POSELIB_AMD_NO_SIGN_TIE") != nullptr; // (diagnostic: A/B of what the extra refinements cost)
         // (a sharded run: every rank holds the whole problem and replays the same decisions - each repeats the two refinements itself)
-        if (off || kind != EST_HOM || N <= (uint32_t)kLMSeqPoints || N > kSignTieMaxPoints || lm_sums_ordered(EST_HOM) || job.skipped ||
+        if (kind != EST_HOM || N <= (uint32_t)kLMSeqPoints || N > kSignTieMaxPoints || lm_sums_ordered(EST_HOM) || job.skipped ||
             !(st->model_score < std::numeric_limits<double>::max()) ||
             !(std::fabs(job.score - st->model_score) <= kSignTieGap * std::fabs(st->model_score)))
             return PL_OK;

@@ -69,20 +69,17 @@ inline size_t raise_hw(std::atomic<size_t> &hw, size_t v) {
     }
     return std::max(cur, v);
 }
-// worker threads of the batch pools, per device: they are persistent and keep their arenas for the life of the process, so the
-// arena budget of a thread is its share of what ALL of them may hold (several pl_*_batch calls can be in flight - four pools per
-// device - and their workers' budgets must not add up to more than the device has: ADVICE r5)
 // Batch sizes of a group's members (pl_estimate_batch).  A single problem's run doubles its batches (1024, 2048, 4096, ...: the waste
 // of a speculative batch stays below 2 x); in a group a STEP costs ~1 ms of dependent launches whatever its members' batch sizes, and
 // a call of a few hundred problems is as long as its longest member's chain of steps.  So from the second step on a member asks for
 // what its loop is known to need (the stop rule's bound after the first local optimisations, RansacRun::needed_now) up to this
 // capacity: the 5-point problems with 60 - 70 % outliers (~4 - 10 k iterations) finish in two steps instead of five.  Measured
 // (profiles/r06_batch_sizes.md): 512 problems per call 48.8 -> 59.8 k problems/s, 4096 per call unchanged (82 k).  The outcome does
-// not depend on how the iterations are cut into batches (the replay is exact).  POSELIB_AMD_GROUP_JUMP=<iterations> (0: doubling)
-const uint32_t g_group_jump = [] {
-    const char *e = std::getenv("POSELIB_AMD_GROUP_JUMP");
-    return e ? (uint32_t)std::min<long>(std::max<long>(std::atol(e), 0), 32768) : 8192u;
-}();
+// not depend on how the iterations are cut into batches (the replay is exact).
+constexpr uint32_t kGroupJump = 8192;
+// worker threads of the batch pools, per device: they are persistent and keep their arenas for the life of the process, so the
+// arena budget of a thread is its share of what ALL of them may hold (several pl_*_batch calls can be in flight - four pools per
+// device - and their workers' budgets must not add up to more than the device has: ADVICE r5)
 constexpr int kMaxDevices = 64;
 std::atomic<int> g_pool_threads[kMaxDevices];
 // POSELIB_AMD_GROUP_TIMING: host phases of run_group (ns, summed over the workers of a call)
@@ -411,7 +408,7 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
         // the batches of a run double in size; in a group they stop growing at the slot's capacity (the outcome does not
         // depend on how the iterations are cut into batches: the replay is exact)
         // (resident groups: long fixed-length runs are welcome - up to the whole run in one batch, arena permitting)
-        max_B = std::max<uint32_t>(max_B, (uint32_t)std::min<uint64_t>(std::max<uint64_t>(grow, g_group_jump && !resident ? g_group_jump : 2048), resident ? 131072 : (resume ? 32768 : std::max<uint32_t>(4096, g_group_jump))));
+        max_B = std::max<uint32_t>(max_B, (uint32_t)std::min<uint64_t>(std::max<uint64_t>(grow, resident ? 2048 : kGroupJump), resident ? 131072 : (resume ? 32768 : kGroupJump)));
         if (!resident) {
             g.raw_a_off = raw_doubles;
             raw_doubles += 2 * (size_t)g.n;
@@ -822,9 +819,9 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
             if (resume) // a regrouped long run: everything the loop is known to need at least, in one batch (plan_batch's doubling
                         // bounds the waste of a single problem's run; here the step overhead of the group is what counts)
                 g.b.B = g.b.hi_g = g.b.Bl = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(g.b.B, r.needed_now()), 32768);
-            else if (step > 0 && g_group_jump) // round 6: from the second step on a member asks for what its loop is known to need
-                                               // (the stop rule's bound after the first local optimisations) instead of doubling - a
-                                               // step of the group is ~1 ms of chain whatever its members' batch sizes
+            else if (step > 0) // round 6: from the second step on a member asks for what its loop is known to need (the stop
+                               // rule's bound after the first local optimisations) instead of doubling - a step of the group is
+                               // ~1 ms of chain whatever its members' batch sizes
                 g.b.B = g.b.hi_g = g.b.Bl = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(g.b.B, r.needed_now()), max_B);
             if (g.b.B > max_B) // (a shorter batch, the rest comes with the next step)
                 g.b.B = g.b.hi_g = g.b.Bl = max_B;

@@ -29,9 +29,6 @@
 // Exact arithmetic (fp64, reference association order) never runs on the matrix cores; only the filters' linear and
 // quadratic forms do.
 #include "pl_kernels.h"
-#ifndef PL_XCD_MAP
-#define PL_XCD_MAP 1
-#endif
 #include "pl_lm_chain.inc"
 #include "pl_device.h"
 #include <atomic>
@@ -349,11 +346,6 @@ __device__ __forceinline__ bool eval_point(const double *M, const double *pt, do
         return homography_inlier(M, pt[0], pt[1], pt[2], pt[3], thr2, r2);
 }
 
-#ifdef PL_SCALAR_ABS_FILTER
-constexpr bool kPackedAbsFilter = false;
-#else
-constexpr bool kPackedAbsFilter = true; // v_pk_fma_f32 pairs in the absolute-pose filter
-#endif
 typedef float v2f __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ v2f pk_fma(v2f a, v2f b, v2f c) { return __builtin_elementwise_fma(a, b, c); }
 __device__ __forceinline__ v2f bc(float s) { return v2f{s, s}; }
@@ -546,7 +538,7 @@ __device__ __forceinline__ void score_queue_body(const PointSet &pts, const floa
 #pragma unroll
                 for (int p = 0; p < P; ++p)
                     m[p] = vmask[p], any |= m[p];
-            } else if constexpr (EST == EST_ABS && kPackedAbsFilter) {
+            } else if constexpr (EST == EST_ABS) {
                 const float gt = pf_up(pf.gx * r[12]);
                 // two points per packed fp32 instruction; the comparisons feed the ballots directly
 #pragma unroll
@@ -572,15 +564,6 @@ __device__ __forceinline__ void score_queue_body(const PointSet &pts, const floa
                 }
                 if constexpr (P & 1) {
                     constexpr int p = P - 1;
-                    const bool out = pf_abs_outlier(r, gt, pf.thr, pf32[p][0], pf32[p][1], pf32[p][2], pf32[p][3],
-                                                    pf32[p][4], bnd[p][0]);
-                    m[p] = vmask[p] & ~__builtin_amdgcn_ballot_w64(out);
-                    any |= m[p];
-                }
-            } else if constexpr (EST == EST_ABS) {
-                const float gt = pf_up(pf.gx * r[12]);
-#pragma unroll
-                for (int p = 0; p < P; ++p) {
                     const bool out = pf_abs_outlier(r, gt, pf.thr, pf32[p][0], pf32[p][1], pf32[p][2], pf32[p][3],
                                                     pf32[p][4], bnd[p][0]);
                     m[p] = vmask[p] & ~__builtin_amdgcn_ballot_w64(out);
@@ -713,24 +696,7 @@ template <int EST, int P> __global__ __launch_bounds__(kQueueThreads) void k_sco
 typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
 typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
 typedef float float16_t __attribute__((ext_vector_type(16)));
-#ifndef PL_MFMA_THREADS
-#define PL_MFMA_THREADS 512
-#endif
-#ifndef PL_ABS_TILE_UNROLL
-#define PL_ABS_TILE_UNROLL 16 // k_score_mfma's loop over the point groups of a tile: unrolled completely (PG - 1 <= 9 iterations) - the LDS
-                             // addresses of the operands become immediate offsets (3 of 35 vector instructions per group): 131.0 -> 126.5 us
-                             // per launch (unrolled 3 times: 125.9 / 129.1; profiles/r06_score_phases.md)
-#endif
-#ifndef PL_ABS_SCHED
-#define PL_ABS_SCHED 1 // k_score_mfma: the products of the next point group interleaved with the vector instructions of this one
-#endif
-#ifndef PL_ABS_EXP
-#define PL_ABS_EXP 0 // experiment builds of k_score_mfma (scripts/exp): 1 = no exact pass, 2 = no expansion either
-#endif
-#ifndef PL_ABS_WAVES
-#define PL_ABS_WAVES 4 // wavefronts per SIMD k_score_mfma's register allocation aims at (48 accumulators + 16 bit fields + operands)
-#endif
-constexpr int kMfmaThreads = PL_MFMA_THREADS; // 8 wavefronts share one chunk of correspondences (LDS: 20 KB shared + 2.8 KB per wave)
+constexpr int kMfmaThreads = 512; // 8 wavefronts share one chunk of correspondences (LDS: 20 KB shared + 2.8 KB per wave)
 
 // Workgroup -> (hypothesis slice, chunk of correspondences) of the matrix-core scorers.  The operands of a hypothesis slice are
 // streamed by the workgroups of ALL chunks of correspondences, and the hardware deals workgroups to the 8 XCDs - each with an L2
@@ -738,14 +704,10 @@ constexpr int kMfmaThreads = PL_MFMA_THREADS; // 8 wavefronts share one chunk of
 // L2, once per chunk (k_score_mfma2<2, 12>, 10 000 correspondences: 27 x 18 MB, FETCH_SIZE 285 MB per launch).  Here the
 // (slice, chunk) pairs are numbered slice-major and XCD x (= linear workgroup index mod 8) takes the x-th eighth of them: an XCD
 // sees 2 - 3 slices per launch (1 MB each, resident in its 4 MB L2 while their chunks' workgroups stream them).  Measured on one
-// box, same build otherwise (PL_XCD_MAP = 0 / 1): FETCH_SIZE of the 7-point scorer 285 -> 61 MB per launch, of k_score_mfma<10>
-// 20.9 -> 16.4 MB; grouped throughput 7-point 3.18 -> 3.41e8, P3P 7.38 -> 7.56e8, 5-point 1.61 -> 1.64e8 hypotheses/s,
+// box, same build otherwise (linear / slice-major placement): FETCH_SIZE of the 7-point scorer 285 -> 61 MB per launch, of
+// k_score_mfma<10> 20.9 -> 16.4 MB; grouped throughput 7-point 3.18 -> 3.41e8, P3P 7.38 -> 7.56e8, 5-point 1.61 -> 1.64e8 hypotheses/s,
 // homography unchanged; a single problem's launch (all workgroups resident at once, not bandwidth bound) is unchanged.
 __device__ __forceinline__ bool slice_chunk_of_workgroup(uint32_t slices, uint32_t chunks, uint32_t &slice, uint32_t &chunk) {
-#if PL_XCD_MAP == 0
-    slice = blockIdx.x, chunk = blockIdx.y;
-    return slice < slices && chunk < chunks;
-#else
     const uint32_t T = slices * chunks, L = blockIdx.x + gridDim.x * blockIdx.y;
     if (L >= T)
         return false;
@@ -753,7 +715,6 @@ __device__ __forceinline__ bool slice_chunk_of_workgroup(uint32_t slices, uint32
     slice = p / chunks;
     chunk = p - slice * chunks;
     return true;
-#endif
 }
 
 // The exact pass of k_score_mfma and k_score_mfmah (k_score_queue's arithmetic).  A drain is a dependency chain - queue entry, the lane
@@ -790,11 +751,7 @@ __device__ __forceinline__ void mfma_drain(const uint16_t *queue, uint32_t first
         // models is needed on this path.  The unit's slot numbers were fetched when the unit began - one lane per
         // hypothesis -, so the record's address costs a lane permutation here, not a second dependent trip to memory.
         const uint32_t slot_g = (uint32_t)__shfl((int)unit_slots, (int)(b.act ? b.g : 0u), 64);
-#if PL_ABS_EXP == 4 // (experiment: every pair against the unit's first model - no scattered loads; timing only)
-        const double *Mp = models + (size_t)__builtin_amdgcn_readfirstlane((int)unit_slots) * kModelStride + (slot_g & 0u);
-#else
         const double *Mp = models + (size_t)slot_g * kModelStride;
-#endif
 #pragma unroll
         for (int i = 0; i < kModelDoubles; ++i)
             b.M[i] = Mp[i];
@@ -905,15 +862,11 @@ __device__ __forceinline__ void score_mfma_body(const PointSet &pts, const uint4
 
         // The exact pass: mfma_drain above, two batches of 64 pairs at a time
         auto drain_pair = [&](uint32_t n2) { // 64 + n2 waiting pairs (0 < n2 <= 64)
-#if PL_ABS_EXP != 1
             mfma_drain<EST_ABS>(queue, qhead, 64u, n2, &s_pts[0][0], NPW, models, unit_slots, thr2, acc_s, acc_c);
-#endif
             qhead += 64u + n2;
         };
         auto drain = [&](uint32_t n) { // n <= 64 waiting pairs
-#if PL_ABS_EXP != 1
             mfma_drain<EST_ABS>(queue, qhead, n, 0u, &s_pts[0][0], NPW, models, unit_slots, thr2, acc_s, acc_c);
-#endif
             qhead += n;
         };
 
@@ -951,22 +904,16 @@ __device__ __forceinline__ void score_mfma_body(const PointSet &pts, const uint4
                     const uint4 braw = s_b[half ? 1 + d : 0][g][col];
                     __builtin_memcpy(&Bop[d], &braw, 16);
                 }
-#if PL_ABS_EXP == 5 // (experiment: no matrix products - timing only, with PL_ABS_EXP == 2's missing expansion)
-#pragma unroll
-                for (int v = 0; v < 16; ++v) {
-                    D0[v] = (float)Bop[0][v & 7] + (float)Aop[0][v & 7];
-                    D1[v] = (float)Bop[1][v & 7] + (float)Aop[1][v & 7];
-                    D2[v] = (float)Bop[2][v & 7] + (float)Aop[2][v & 7];
-                }
-#else
                 D0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(Aop[0], Bop[0], kZero, 0, 0, 0);
                 D1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(Aop[1], Bop[1], kZero, 0, 0, 0);
                 D2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(Aop[2], Bop[2], kZero, 0, 0, 0);
-#endif
             };
             float16_t D0, D1, D2;
             products(0, D0, D1, D2);
-#pragma unroll PL_ABS_TILE_UNROLL
+            // unrolled completely (PG - 1 <= 9 iterations): the LDS addresses of the operands become immediate offsets (3 of 35
+            // vector instructions per group): 131.0 -> 126.5 us per launch (unrolled 3 times: 125.9 / 129.1;
+            // profiles/r06_score_phases.md)
+#pragma unroll 16
             for (int g = 1; g < PG; ++g) {
                 uint32_t T[16];
 #pragma unroll
@@ -976,8 +923,7 @@ __device__ __forceinline__ void score_mfma_body(const PointSet &pts, const uint4
 #pragma unroll
                 for (int v = 0; v < 16; ++v)
                     out[v] = __builtin_amdgcn_alignbit(out[v], T[v], 31);
-#if PL_ABS_SCHED
-#if PL_ABS_SCHED == 1
+                // the products of the next point group interleaved with the vector instructions of this one
                 __builtin_amdgcn_sched_group_barrier(0x002, 16, 0); // the v_or3
                 __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);  // the operands of the next group from LDS
                 __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
@@ -987,19 +933,6 @@ __device__ __forceinline__ void score_mfma_body(const PointSet &pts, const uint4
                 __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
                 __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
-#else
-                // the four v_or3 that free the registers the operands are loaded into, the loads, the other v_or3 under the loads' latency
-                __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
-                __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
-                __builtin_amdgcn_sched_group_barrier(0x002, 14, 0);
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x002, 5, 0);
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x002, 5, 0);
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
-#endif
-#endif
             }
 #pragma unroll
             for (int v = 0; v < 16; ++v) {
@@ -1011,11 +944,6 @@ __device__ __forceinline__ void score_mfma_body(const PointSet &pts, const uint4
             // vector instructions per round - runs behind a SCALAR branch for that group only; round 5)
             const bool partial_group = hg * 32u + 32u > gn;
             auto expand_round = [&](int v, bool check_slot) {
-#if PL_ABS_EXP == 2 || PL_ABS_EXP == 5 // (experiment: no expansion, no exact pass - timing only, results are wrong)
-                if (out[v] == 0x12345u)
-                    qtail += 1;
-                return;
-#endif
                 const uint32_t slot = hg * 32u + 8u * (uint32_t)(v >> 2) + 4u * (uint32_t)half + (uint32_t)(v & 3); // hypothesis index inside the unit
                 uint32_t bits = ~out[v] & validbits;
                 if (check_slot && slot >= gn)
@@ -1075,8 +1003,9 @@ __device__ __forceinline__ void score_mfma_body(const PointSet &pts, const uint4
     }
 }
 
+// amdgpu_waves_per_eu(4, 8): wavefronts per SIMD the register allocation aims at (48 accumulators + 16 bit fields + operands)
 template <int PG>
-__global__ __launch_bounds__(kMfmaThreads) __attribute__((amdgpu_waves_per_eu(PL_ABS_WAVES, 8))) void k_score_mfma(PointSet pts, const uint4 *__restrict__ shadow16,
+__global__ __launch_bounds__(kMfmaThreads) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_score_mfma(PointSet pts, const uint4 *__restrict__ shadow16,
                                                                const double *__restrict__ models,
                                                                const uint32_t *__restrict__ slots,
                                                                const uint32_t *__restrict__ num_hyp_ptr,
@@ -1091,7 +1020,7 @@ __global__ __launch_bounds__(kMfmaThreads) __attribute__((amdgpu_waves_per_eu(PL
                         gridDim.x);
 }
 template <int PG>
-__global__ __launch_bounds__(kMfmaThreads) __attribute__((amdgpu_waves_per_eu(PL_ABS_WAVES, 8))) void k_score_mfma_g(const GroupArgs *ga) {
+__global__ __launch_bounds__(kMfmaThreads) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_score_mfma_g(const GroupArgs *ga) {
     const GroupArgs &g = ga[blockIdx.z];
     uint32_t slice, chunk;
     if (!g.active || !g.use_mfma || !slice_chunk_of_workgroup(g.slices, g.chunks, slice, chunk))
@@ -2357,14 +2286,6 @@ template <int EST> __global__ __launch_bounds__(kLMThreads) void k_lm(LMTask *ta
         const unsigned long long pt3 = __builtin_readcyclecounter();
         PL_PROF_ADD(2, pt2); // waiting for the slowest wavefront of the sweep
 #endif
-#ifdef PL_LM_OLD_REDUCE // experiment builds: round 4's reductions (A/B on one box)
-        if (res) {
-            double v[1] = {racc};
-            BlockReduce<1>::run(v, cnt, reinterpret_cast<double(*)[2]>(&scratch[0][0]), s_racc, &s_count);
-        }
-        if (jac)
-            BlockReduce<NT>::run(acc, cntj, scratch, out, &s_count_j);
-#else
         if (res && jac) { // the fused sweep: the NT sums of the normal equations and the cost through one reduction
             BlockReduceT<NT + 1>::run(acc, racc, cntj, cnt, tr_stage, tr_counts, out, &s_racc[0], &s_count_j, &s_count);
         } else if (res) {
@@ -2374,7 +2295,6 @@ template <int EST> __global__ __launch_bounds__(kLMThreads) void k_lm(LMTask *ta
             uint32_t unused;
             BlockReduceT<NT>::run(acc, 0.0, cntj, 0u, tr_stage, tr_counts, out, nullptr, &s_count_j, &unused);
         }
-#endif
 #ifdef PL_LM_PROFILE
         PL_PROF_ADD(3, pt3); // block reductions
         if (threadIdx.x == 0)
@@ -2479,10 +2399,8 @@ template <int EST> __global__ __launch_bounds__(kLMThreads) void k_lm(LMTask *ta
 // POSELIB_AMD_LM_ORDERED=1) routes every task through it.  Cost and floor (measured, DESIGN 4 "Ordered sums at every n"): a
 // sequential fp64 sum is a chain of dependent additions, 9.3 cycles each on gfx950; the consumer below reaches 11.7 cycles per row in
 // isolation and ~21 inside the kernel, i.e. 44 us per LM iteration at n = 5000 against 22 us for the tree form.
-#ifndef PL_LM_WAVES
-#define PL_LM_WAVES 2 // wavefronts per SIMD the register allocation of k_lm aims at (2: one workgroup per CU, no spills)
-#endif
-template <int EST> __global__ __launch_bounds__(kLMThreads, (EST == EST_HOM ? 2 : PL_LM_WAVES)) void k_lm_ordered(LMTask *tasks, uint32_t lds_bytes) {
+// __launch_bounds__(kLMThreads, 2): wavefronts per SIMD the register allocation aims at (2: one workgroup per CU, no spills)
+template <int EST> __global__ __launch_bounds__(kLMThreads, 2) void k_lm_ordered(LMTask *tasks, uint32_t lds_bytes) {
     using R = Refiner<EST>;
     constexpr int K = R::K;
     constexpr int NT = NormalSize<K>::kTotal;
@@ -3102,35 +3020,21 @@ hipError_t launch_solve_batch(int est, const double *in, uint32_t np, double *mo
     return hipGetLastError();
 }
 
-// points per lane of the scorers (POSELIB_AMD_PF_P overrides, 1..6)
-static int max_points_per_lane_pf() {
-    static const int v = [] {
-        const char *e = std::getenv("POSELIB_AMD_PF_P");
-        const int x = e ? std::atoi(e) : 5;
-        return x < 1 ? 1 : (x > 6 ? 6 : x);
-    }();
-    return v;
-}
 // `streaming`: launches of the batched main loop (k_score_queue: 64 * P correspondences per chunk, every wave of a
 // workgroup sees the same chunk); otherwise the non-streaming kernels (256 * P correspondences per chunk).
 // For the Sampson scores P is chosen to minimise  chunks(P) * (VALU issue slots of the pre-filter for P points + a
 // per-hypothesis overhead): pairs of points share packed instructions, an odd point costs as much as a pair.
 static void score_shape(int est, uint32_t n, bool streaming, bool mfma, uint32_t &chunks, int &P) {
     const uint32_t lanes = streaming ? 64u : (uint32_t)kScoreThreads;
-    const int pmax = max_points_per_lane_pf();
     if (streaming && mfma && (est == EST_REL || est == EST_FUND)) {
         // k_score_mfma2: PG = 2 P groups of 32 correspondences per chunk; relative pose keeps the bearings in LDS as
         // well and stops at 320 correspondences per workgroup (two workgroups per CU)
-        static const uint32_t m2p = [] { // POSELIB_AMD_M2_P (experiment): point groups of 64 per chunk of the Sampson matrix-core scorer
-            const char *e = std::getenv("POSELIB_AMD_M2_P");
-            return e ? (uint32_t)std::max(1, std::min(6, std::atoi(e))) : 0u;
-        }();
-        const uint32_t per_chunk_max = lanes * (m2p ? std::min<uint32_t>(m2p, est == EST_REL ? 5u : 6u) : (est == EST_REL ? 5u : 6u));
+        const uint32_t per_chunk_max = lanes * (est == EST_REL ? 5u : 6u);
         chunks = std::max<uint32_t>(1u, (n + per_chunk_max - 1) / per_chunk_max);
         P = std::max<int>(1, (int)((n + lanes * chunks - 1) / (lanes * chunks)));
         return;
     }
-    if (streaming && (est == EST_REL || est == EST_FUND) && std::getenv("POSELIB_AMD_PF_P") == nullptr) {
+    if (streaming && (est == EST_REL || est == EST_FUND)) {
         // Sampson filter: 27 issue slots per pair of points, 29 for an odd one, ~30 per hypothesis around them
         // (measured on MI355X: P = 6 beats P = 5 by 25 % at N = 10000; for the cheaper reprojection and
         // homography filters the smaller register footprint of P = 5 wins)
@@ -3146,8 +3050,9 @@ static void score_shape(int est, uint32_t n, bool streaming, bool mfma, uint32_t
             chunks = 1;
         return;
     }
-    // (absolute pose on the matrix-core form: at most 10 groups of 32 correspondences per chunk, see launch_score_est)
-    const uint32_t per_chunk_max = lanes * (uint32_t)((streaming && mfma && (est == EST_ABS || est == EST_HOM)) ? std::min(pmax, 5) : pmax);
+    // up to 5 points per lane (absolute pose on the matrix-core form: at most 10 groups of 32 correspondences per chunk, see
+    // launch_score_est)
+    const uint32_t per_chunk_max = lanes * 5u;
     chunks = (n + per_chunk_max - 1) / per_chunk_max;
     if (chunks == 0)
         chunks = 1;
@@ -3157,15 +3062,13 @@ static void score_shape(int est, uint32_t n, bool streaming, bool mfma, uint32_t
 }
 bool score_uses_mfma(int est, uint32_t n_points, const PrefilterArgs &pf) {
     static const bool off = std::getenv("POSELIB_AMD_NO_MFMA") != nullptr;
-    static const bool off2 = std::getenv("POSELIB_AMD_NO_MFMA2") != nullptr;
     if (off || !pf.enabled || n_points < 1024u)
         return false;
     if (est == EST_ABS)
         return pf.g16 > 0.f && pf.thr <= 1.0f;
     if (est == EST_REL || est == EST_FUND)
-        return !off2 && pf.t16 > 0.f; // (coordinates bounded by 8, threshold in range: make_prefilter_args)
-    static const bool offh = std::getenv("POSELIB_AMD_NO_MFMAH") != nullptr;
-    return !offh && pf.h16 > 0.f; // homography: the same conditions
+        return pf.t16 > 0.f; // (coordinates bounded by 8, threshold in range: make_prefilter_args)
+    return pf.h16 > 0.f;     // homography: the same conditions
 }
 uint32_t score_chunks(int est, uint32_t n, bool streaming, bool mfma) {
     uint32_t c;
@@ -3381,8 +3284,7 @@ hipError_t launch_lm_tasks(int est, LMTask *tasks, uint32_t num_tasks, uint32_t 
         dyn_limit[ordered][est].store(limit, std::memory_order_release);
     }
     const size_t want = sizeof(double) * point_doubles(est) * (size_t)max_points;
-    const bool lds = std::getenv("POSELIB_AMD_LM_NO_LDS") == nullptr;
-    const size_t bytes = (lds && want <= (size_t)limit) ? want : 0;
+    const size_t bytes = want <= (size_t)limit ? want : 0;
     if (ordered) {
         PL_DISPATCH_EST(est, k_lm_ordered<E><<<dim3(num_tasks), dim3(kLMThreads), bytes, stream>>>(tasks, (uint32_t)bytes));
     } else {

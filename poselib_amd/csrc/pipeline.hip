@@ -22,7 +22,6 @@
 #include "pl_refine.h"
 #include "pl_sampler.h"
 #include <algorithm>
-#include <cstdlib>
 
 namespace pl {
 
@@ -392,8 +391,7 @@ template <bool SMALL> __global__ __launch_bounds__(1024) void k_sample_orbit_g(c
 }
 // expected number of flagged positions among M: a position is flagged when the K draws starting there repeat an index
 static bool orbit_small_build(uint32_t M, uint64_t N, int K) {
-    static const bool off = std::getenv("POSELIB_AMD_ORBIT_LARGE") != nullptr;
-    if (off || N == 0)
+    if (N == 0)
         return false;
     double distinct = 1.0;
     for (int i = 1; i < K; ++i)

@@ -287,13 +287,6 @@ template <int n> PL_HD void danilevsky_charpoly(double *A, double *p) {
 
 #ifdef __HIPCC__
 // ===================================================================================================== wave forms (device)
-#ifndef PL_WAVE_SYNC
-#define PL_WAVE_SYNC()                                                                                                 \
-    do {                                                                                                               \
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");                                                         \
-        __builtin_amdgcn_wave_barrier();                                                                               \
-    } while (0)
-#endif
 
 // The coefficients of a sample by its wavefront: lane l evaluates coefficients l, l + 64, ...  d: the data (LDS), out: LDS.
 template <bool POWERS, int NCOEF>

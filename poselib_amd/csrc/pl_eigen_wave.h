@@ -18,14 +18,6 @@ namespace pl {
 
 constexpr int eig_wave_doubles(int n) { return n * n + 3 * n; }
 
-// orders the LDS accesses of the lanes of one wavefront (the hardware executes a wavefront's LDS instructions in order; this keeps the
-// compiler from moving or caching accesses across the phases of the algorithm)
-#define PL_WAVE_SYNC()                                                                                                 \
-    do {                                                                                                               \
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");                                                         \
-        __builtin_amdgcn_wave_barrier();                                                                               \
-    } while (0)
-
 // a / b, c / d, e / f ... at once: the divisions of a reflector are independent of one another, and an fp64 division is ~35
 // instructions that every lane would issue alike - lane i forms quotient i, the others read it (v_readlane).  The same IEEE
 // operation on the same operands in another lane: the same bits.

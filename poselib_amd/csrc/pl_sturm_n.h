@@ -225,13 +225,6 @@ template <int N> PL_HD int sturm_n_roots(const double *coef, double *roots, doub
 }
 
 #ifdef __HIPCC__
-#ifndef PL_WAVE_SYNC
-#define PL_WAVE_SYNC()                                                                                                 \
-    do {                                                                                                               \
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");                                                         \
-        __builtin_amdgcn_wave_barrier();                                                                               \
-    } while (0)
-#endif
 // sturm_n_isolate by ONE WAVEFRONT.  Lane 0 builds the chain (serial: ~700 dependent operations); the bisection then runs LEVEL BY LEVEL
 // with one lane per live interval: a visit of the recursion depends on its interval alone (narrow -> leaf; more than one sign
 // variation -> bisect, the left half always, the right half when it holds a sign variation or is narrow; exactly one -> leaf; none ->

@@ -143,23 +143,10 @@ __device__ __forceinline__ void sfocal_solve_body(const SFocalGenArgs &g, uint32
         base[kLdsX + lane] = st[(size_t)(kStX + lane) * B];
     PL_WAVE_SYNC();
     // ---- coefficients, template, the last eight rows of C0^-1 C1 (relpose_6pt_focal.cc:54-1043)
-#ifndef PL_SFOCAL_STOP
-#define PL_SFOCAL_STOP 99 // (experiment builds: the kernel returns after phase n - profiles/r06_sfocal_phases.md)
-#endif
-#define PL_SFOCAL_PHASE(n)                                                                                             \
-    if (PL_SFOCAL_STOP <= (n)) {                                                                                       \
-        if (lane == 0)                                                                                                 \
-            g.num_models[it] = 0;                                                                                      \
-        return;                                                                                                        \
-    }
-    PL_SFOCAL_PHASE(0)
     template_coefficients_wave<true, kSixCoeffs>(nb, kSixTermStart, kSixTermPacked, coef, lane);
     PL_WAVE_SYNC();
-    PL_SFOCAL_PHASE(1)
     template_fill_wave<31, kSixCols, kSixS>(coef, kSixColStart, kSixEntryRow, kSixEntryCoeff, C, lane);
-    PL_SFOCAL_PHASE(2)
     lu_solve_tail_wave<31, kSixCols, kSixS, 8>(C, lane);
-    PL_SFOCAL_PHASE(3)
     // ---- the action matrix (:1045-1053): kept in the coefficients' place for the roots, a working copy for the polynomial
     double amv[4];
     {
@@ -180,9 +167,7 @@ __device__ __forceinline__ void sfocal_solve_body(const SFocalGenArgs &g, uint32
     }
     PL_WAVE_SYNC();
     // ---- characteristic polynomial, its real roots (:1069-1076)
-    PL_SFOCAL_PHASE(4)
     danilevsky_charpoly_wave<15>(amp, C + kLdsWs, poly, lane);
-    PL_SFOCAL_PHASE(5)
     // the real roots: lane 0 builds the Sturm chain (its arrays in LDS: as private arrays they are scratch memory), the bisection
     // runs level by level with one lane per live interval (sturm_n_isolate_wave), then ONE LANE PER LEAF polishes (Ridders +
     // Newton) - the roots in leaf order, at most 15, as the serial routine emits them
@@ -206,7 +191,6 @@ __device__ __forceinline__ void sfocal_solve_body(const SFocalGenArgs &g, uint32
     int nroots = (int)__popcll(rmask);
     nroots = nroots < 15 ? nroots : 15;
     PL_WAVE_SYNC();
-    PL_SFOCAL_PHASE(6)
     // ---- lane s = root s: x and w (:11-52); w < 1e-8 dropped (:1105); the solutions in the order of the roots
     bool keep = false;
     double x = 0, w = 1;
@@ -222,7 +206,6 @@ __device__ __forceinline__ void sfocal_solve_body(const SFocalGenArgs &g, uint32
         sols[pos] = x, sols[kMaxRoots + pos] = y, sols[2 * kMaxRoots + pos] = w;
     }
     PL_WAVE_SYNC();
-    PL_SFOCAL_PHASE(7)
     // ---- lane s = solution s: essential matrix, poses (:1107-1141)
     uint32_t m = 0;
     if (ns > 0) { // (uniform)

@@ -17,13 +17,12 @@ if [ "$PART" = "a" ]; then
   timeout 300 python bench.py --mode streams --streams 1 --no-secondary --no-cpu-baseline --steps 10 --detail-file $O/detail_s1.json > $O/bench_s1.json 2> $O/bench_s1.err
   timeout 300 python scripts/batch_sweep.py 4096 8:0:3 10:0:3 12:0:3 > $O/batch_sweep.log 2>&1
   for n in 256 512 1024 2048; do timeout 200 python scripts/batch_sweep.py $n 9:0:3 2>&1 | grep threads >> $O/batch_sizes.log; done
-  POSELIB_AMD_GROUP_JUMP=0 timeout 200 python scripts/batch_sweep.py 512 9:0:3 2>&1 | grep threads > $O/batch_512_doubling.log
   timeout 300 python scripts/batch_overlap.py 512 10 > $O/batch_overlap.log 2>&1
   POSELIB_AMD_GROUP_TIMING=1 timeout 200 python scripts/batch_sweep.py 512 9:0:3 2>&1 | tail -13 > $O/batch_timing_512.log
   timeout 400 python scripts/batch_cameras.py 1024 > $O/batch_cameras.md 2> $O/batch_cameras.err
   timeout 200 python scripts/time_focal_estimators.py 5 > $O/focal_timing.log 2>&1
   timeout 600 python scripts/focal_batch_bench.py 1024 2000 > $O/focal_batch.md 2> $O/focal_batch.err
-  cat $O/pytest_gpu.log; tail -c 1200 $O/bench_default.json; tail -3 $O/bench_default.err; cat $O/batch_sizes.log $O/batch_512_doubling.log; cat $O/batch_cameras.md; tail -8 $O/focal_batch.md
+  cat $O/pytest_gpu.log; tail -c 1200 $O/bench_default.json; tail -3 $O/bench_default.err; cat $O/batch_sizes.log; cat $O/batch_cameras.md; tail -8 $O/focal_batch.md
 elif [ "$PART" = "p" ]; then
   # PMC passes of the four scorers (one problem at a time); python scripts/make_profiles_r06.py pmc turns them into profiles/pmc_traffic.json,
   # which the bench of part a prices its roofline with: run p, refresh, then a

@@ -99,8 +99,7 @@ def main():
     wr("r06_batch_sizes.md",
        "# r06 - configs[4] as BASELINE words it: 4096 problems sharded over 8 ranks = 512 per call.  pl_estimate_batch at 256 ... 4096 problems per call "
        "(scripts/batch_sweep.py, 9 workers)\n\n```\n" + "".join(f"{n:5d} problems per call: {ln.strip()}\n" for n, ln in zip((256, 512, 1024, 2048), sizes))
-       + rd("batch_sweep.log") + "```\n\n512 per call with the batches of a group's members DOUBLING as in round 5 (POSELIB_AMD_GROUP_JUMP=0):\n\n```\n"
-       + rd("batch_512_doubling.log") + "```\n\nSeveral calls in flight from as many host threads (scripts/batch_overlap.py):\n\n```\n" + rd("batch_overlap.log")
+       + rd("batch_sweep.log") + "```\n\nSeveral calls in flight from as many host threads (scripts/batch_overlap.py):\n\n```\n" + rd("batch_overlap.log")
        + "```\n\nWhere the workers' time goes in a 512-problem call (POSELIB_AMD_GROUP_TIMING=1):\n\n```\n" + rd("batch_timing_512.log") + "```\n\n"
        f"bench.py (N = 1 line of the same build): batch_mixed_problems_per_s {c['batch_mixed_problems_per_s']:.0f} at 4096 per call, batch_mixed_512_problems_per_s "
        f"{c.get('batch_mixed_512_problems_per_s', float('nan')):.0f} (calls one after the other), batch_mixed_512_x4_in_flight_problems_per_s "
