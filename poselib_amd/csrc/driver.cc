@@ -1639,6 +1639,29 @@ void free_problem(pl_problem *p) {
     p->d_pts = nullptr;
 }
 
+// The bound of max(|x|, |y|) of the prepared points that keeps the scorers' fp32 / fp16 pre-filters conservative (pl_prefilter.h).
+// Absolute pose through a linear camera and two-view problems from 1024 correspondences on (the matrix-core Sampson form; the O(N)
+// host pass is not worth it below) get it from the raw points on the host; absolute pose through OPENCV reads k_prepare's atomic
+// max back (the un-projection is iterative); smaller two-view problems get none (+inf).  make_problem_prepared and the groups'
+// stage A both decide it here.
+
+// upper bound of max(|x|, |y|) of the un-projected 2-D points of a linear camera (the un-projected coordinate is (px - c) / f up to
+// one rounding)
+float host_xy_absmax(const CameraParams &cam, const double *a, size_t n) {
+    double cx = 0, cy = 0, fx = 1, fy = 1;
+    if (cam.model_id == CAM_SIMPLE_PINHOLE)
+        fx = fy = cam.p[0], cx = cam.p[1], cy = cam.p[2];
+    else if (cam.model_id == CAM_PINHOLE)
+        fx = cam.p[0], fy = cam.p[1], cx = cam.p[2], cy = cam.p[3];
+    double m = 0.0;
+    for (size_t i = 0; i < n; ++i) {
+        const double u = std::fabs((a[2 * i] - cx) / fx), v = std::fabs((a[2 * i + 1] - cy) / fy);
+        m = (u > m || u != u) ? u : m; // NaN propagates (and disables the pre-filter)
+        m = (v > m || v != v) ? v : m;
+    }
+    m = m * (1.0 + 1e-12);
+    return std::nextafter((float)m, std::numeric_limits<float>::infinity());
+}
 // Upper bound of the largest |coordinate| the prepared two-view points will have (pl_prefilter.h, fp16 Sampson form), from
 // the raw points on the host: linear cameras / the normalisation (x - c) / scale round at most once per operation.
 // +inf when it cannot be told without the device (OPENCV un-projection) or a coordinate is NaN.
@@ -1680,6 +1703,17 @@ float host_two_view_absmax(const PrepareArgs &pa, const double *a, const double 
     m = m * (1.0 + 1e-12);
     return std::nextafter((float)m, inf);
 }
+bool prefilter_bound_on_device(int kind, const PrepareArgs &pa) {
+    return kind == EST_ABS && !(pa.mode == 0 && pa.cam1.model_id != CAM_OPENCV);
+}
+// the bound when it comes from the host (prefilter_bound_on_device false)
+float host_prefilter_bound(int kind, const PrepareArgs &pa, const double *a, const double *b, size_t n) {
+    if (kind == EST_ABS)
+        return host_xy_absmax(pa.cam1, a, n);
+    if (n >= 1024 && a && b)
+        return host_two_view_absmax(pa, a, b, n);
+    return std::numeric_limits<float>::infinity();
+}
 
 // One-shot front-ends: the user's AoS buffers go to the device as they are and k_prepare (pipeline.hip) writes the SoA
 // block into the context's arena - per-point un-projection / normalisation on the GPU, no
@@ -1706,9 +1740,9 @@ int make_problem_prepared(Context *c, int kind, const double *a, const double *b
     HIP_TRY(c->pts_arena.ensure(sizeof(double) * nd * n));
     HIP_TRY(c->absmax.ensure(sizeof(unsigned long long)));
     HIP_TRY(c->h_absmax.ensure(sizeof(unsigned long long)));
-    // max|x| of the prepared points is read back only for absolute-pose problems of non-linear cameras (below): no fill dispatch
-    // in front of the others (k_prepare's atomic max then lands on a word nobody reads)
-    const bool reads_absmax = !(lm_only || kind != EST_ABS) && !(pa.mode == 0 && pa.cam1.model_id != CAM_OPENCV);
+    // max|x| of the prepared points is read back only for absolute-pose problems of non-linear cameras (prefilter_bound_on_device): no
+    // fill dispatch in front of the others (k_prepare's atomic max then lands on a word nobody reads)
+    const bool reads_absmax = !lm_only && prefilter_bound_on_device(kind, pa);
     if (reads_absmax)
         HIP_TRY(hipMemsetAsync(c->absmax.p, 0, sizeof(unsigned long long), c->stream));
     if (!resident) {
@@ -1738,31 +1772,8 @@ int make_problem_prepared(Context *c, int kind, const double *a, const double *b
     p->d_pts = c->pts_arena.as<double>();
     for (int d = 0; d < nd; ++d)
         p->ps.a[d] = p->d_pts + (size_t)d * n;
-    if (lm_only || kind != EST_ABS) { // (stream order puts the next kernels behind k_prepare)
-        // two-view: the coordinate bound that admits the matrix-core form of the Sampson filter (large problems only: the
-        // O(N) host pass is not worth it below the size that form starts at)
-        p->ps.xy_absmax = std::numeric_limits<float>::infinity();
-        if (!lm_only && n >= 1024 && a && b) // (relative pose, fundamental matrix, homography)
-            p->ps.xy_absmax = host_two_view_absmax(pa, a, b, n);
-        return PL_OK;
-    }
-    if (pa.mode == 0 && pa.cam1.model_id != CAM_OPENCV) {
-        // linear cameras: an upper bound of max(|x|, |y|) after un-projection from the raw pixels on the host - no
-        // read-back, no synchronisation (the un-projected coordinate is (px - c) / f up to one rounding)
-        const CameraParams &cam = pa.cam1;
-        double cx = 0, cy = 0, fx = 1, fy = 1;
-        if (cam.model_id == CAM_SIMPLE_PINHOLE)
-            fx = fy = cam.p[0], cx = cam.p[1], cy = cam.p[2];
-        else if (cam.model_id == CAM_PINHOLE)
-            fx = cam.p[0], fy = cam.p[1], cx = cam.p[2], cy = cam.p[3];
-        double m = 0.0;
-        for (size_t i = 0; i < n; ++i) {
-            const double u = std::fabs((a[2 * i] - cx) / fx), v = std::fabs((a[2 * i + 1] - cy) / fy);
-            m = (u > m || u != u) ? u : m; // NaN propagates (and disables the pre-filter)
-            m = (v > m || v != v) ? v : m;
-        }
-        m = m * (1.0 + 1e-12);
-        p->ps.xy_absmax = std::nextafter((float)m, std::numeric_limits<float>::infinity());
+    if (!reads_absmax) { // (stream order puts the next kernels behind k_prepare)
+        p->ps.xy_absmax = lm_only ? std::numeric_limits<float>::infinity() : host_prefilter_bound(kind, pa, a, b, n);
         return PL_OK;
     }
     HIP_TRY(hipMemcpyAsync(c->h_absmax.p, c->absmax.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
@@ -1824,22 +1835,15 @@ void normalize_frobenius(Mat3 &A) {
         A.m[i] /= n;
 }
 
-int run_with_model(Context *c, pl_problem *p, const pl_robust_options *o, void *model, uint8_t *inliers,
-                   pl_ransac_stats *st, double *record_out = nullptr) {
-    double rec[kModelStride];
-    const bool pose_kind = (p->kind == EST_ABS || p->kind == EST_REL);
-    if (o->ransac.score_initial_model) {
-        if (pose_kind)
-            record_from_pose(static_cast<const pl_camera_pose *>(model), p->kind == EST_REL, rec);
-        else
-            store_matrix_model(rec, mat_from_colmajor(static_cast<const double *>(model)));
-    } else {
-        identity_record(p->kind, rec);
-    }
-    int rc = ransac_core(c, p, o, rec, inliers, st);
-    if (rc != PL_OK)
-        return rc;
-    if (pose_kind) {
+// the caller's model (pl_camera_pose for absolute / relative pose, column-major 3 x 3 for F / H) <-> record
+void record_from_model(int kind, const void *model, double *rec) {
+    if (kind == EST_ABS || kind == EST_REL)
+        record_from_pose(static_cast<const pl_camera_pose *>(model), kind == EST_REL, rec);
+    else
+        store_matrix_model(rec, mat_from_colmajor(static_cast<const double *>(model)));
+}
+void model_from_record(int kind, const double *rec, void *model) {
+    if (kind == EST_ABS || kind == EST_REL) {
         pose_from_record(rec, static_cast<pl_camera_pose *>(model));
     } else {
         Mat3 M;
@@ -1847,8 +1851,19 @@ int run_with_model(Context *c, pl_problem *p, const pl_robust_options *o, void *
             M.m[i] = rec[kMatOff + i];
         mat_to_colmajor(M, static_cast<double *>(model));
     }
-    if (record_out)
-        std::memcpy(record_out, rec, sizeof(rec));
+}
+
+int run_with_model(Context *c, pl_problem *p, const pl_robust_options *o, void *model, uint8_t *inliers,
+                   pl_ransac_stats *st) {
+    double rec[kModelStride];
+    if (o->ransac.score_initial_model)
+        record_from_model(p->kind, model, rec);
+    else
+        identity_record(p->kind, rec);
+    int rc = ransac_core(c, p, o, rec, inliers, st);
+    if (rc != PL_OK)
+        return rc;
+    model_from_record(p->kind, rec, model);
     return PL_OK;
 }
 
@@ -1914,6 +1929,200 @@ double normalization_of(const double *x1, const double *x2, size_t n, bool centr
     pa.c1x = c1x, pa.c1y = c1y, pa.c2x = c2x, pa.c2y = c2y;
     pa.scale = scale;
     return scale;
+}
+
+// ---------------------------------------------------------------------------- front-ends (robust.cc)
+// What a front-end of robust.cc does around its ransac_* call: the loop's options and point preparation, the warm start in the
+// loop's coordinates, the inlier gate and set-up of the final bundle, the result in the caller's representation.  Written once,
+// for the single-problem entry points (pl_estimate_*) and pl_estimate_batch's groups alike.
+struct FrontEnd {
+    int kind = 0;
+    pl_robust_options scaled; // options of the ransac_* part (thresholds rescaled the way the front-end does)
+    double scale = 1.0;       // abs: 1 / focal; rel: mean inverse focal; hom / fund: normalisation scale
+    Mat3 T1, T2;              // hom / fund normalisation
+    PrepareArgs prep{};       // un-projection / normalisation of the points (k_prepare)
+    CameraParams cam{};       // abs: the caller's camera
+    int cam_flags = 0;        // abs: CamRefineFlags of the final bundle (bundle.refine_*), 0 = pose alone
+};
+
+// abs: the final bundle's options - bundle.refine_focal_length forced when the focal length was estimated (robust.cc:53)
+pl_bundle_options front_bundle_options(const pl_robust_options &opt) {
+    pl_bundle_options bundle = opt.bundle;
+    if (opt.estimate_focal_length)
+        bundle.refine_focal_length = 1; // "force refinement of focal in this case"
+    return bundle;
+}
+
+// robust.cc:40-46 (abs), 249-253 / 286-292 (rel), 552-562 (fund), 720-726 (hom)
+void front_begin(FrontEnd &fe, int kind, const double *a, const double *b, size_t n, const pl_robust_options &opt,
+                 const pl_camera *camera1, const pl_camera *camera2) {
+    fe.kind = kind;
+    fe.scaled = opt;
+    std::memset(&fe.prep, 0, sizeof(fe.prep));
+    std::memset(&fe.cam, 0, sizeof(fe.cam));
+    fe.cam_flags = 0;
+    switch (kind) {
+    case EST_ABS:
+        fe.cam = to_cam(camera1);
+        fe.scale = 1.0 / camera_focal(camera1);
+        fe.scaled.max_error *= fe.scale;
+        fe.prep = prepare_unproject(fe.cam, nullptr);
+        fe.cam_flags = active_cam_flags(fe.cam.model_id, front_bundle_options(opt));
+        break;
+    case EST_REL: {
+        fe.scale = 0.5 * (1.0 / camera_focal(camera1) + 1.0 / camera_focal(camera2));
+        fe.scaled.max_error *= fe.scale;
+        fe.scaled.bundle.loss_scale *= fe.scale;
+        const CameraParams c1 = to_cam(camera1), c2 = to_cam(camera2);
+        fe.prep = prepare_unproject(c1, &c2);
+        break;
+    }
+    default:
+        fe.scale = normalization_of(a, b, n, kind == EST_HOM || !opt.real_focal_check, fe.T1, fe.T2, fe.prep);
+        fe.scaled.max_error /= fe.scale;
+        fe.scaled.bundle.loss_scale /= fe.scale;
+        break;
+    }
+}
+
+// the record the loop starts from: the identity, or with ransac.score_initial_model the caller's model - poses as they are, F and H
+// in the normalised coordinates of the problem (robust.cc:566-569, 729-732)
+void front_initial_record(const FrontEnd &fe, const void *model, double *rec) {
+    if (!fe.scaled.ransac.score_initial_model) {
+        identity_record(fe.kind, rec);
+        return;
+    }
+    if (fe.kind == EST_ABS || fe.kind == EST_REL) {
+        record_from_model(fe.kind, model, rec);
+        return;
+    }
+    Mat3 M = mat_from_colmajor(static_cast<const double *>(model));
+    if (fe.kind == EST_FUND)
+        M = mul(mul(inverse3(transpose3(fe.T2)), M), inverse3(fe.T1));
+    else
+        M = mul(mul(fe.T2, M), inverse3(fe.T1));
+    normalize_frobenius(M);
+    store_matrix_model(rec, M);
+}
+
+// the final bundle runs when the loop's model has MORE inliers than this (robust.cc:103, 296, 573, 736; shared focal :401)
+constexpr int kFrontSharedFocal = 4; // (pl_batch_item.kind of the shared-focal relative pose)
+uint64_t front_min_inliers(int kind) {
+    switch (kind) {
+    case EST_ABS:
+        return 3;
+    case EST_REL:
+        return 5;
+    case EST_FUND:
+        return 7;
+    case EST_HOM:
+        return 4;
+    default: // kFrontSharedFocal
+        return 6;
+    }
+}
+
+// the final bundle over the inliers (robust.cc:103-123: abs in focal-normalised pixels, bundle.refine_* intrinsics with the pose;
+// 296-311, 573-588, 736-751: the others in the loop's coordinates)
+struct FrontBundle {
+    LMOptions opt;
+    CameraParams cam;
+    int cam_flags;
+    double point_scale;
+};
+FrontBundle front_bundle(const FrontEnd &fe) {
+    FrontBundle fb;
+    std::memset(&fb.cam, 0, sizeof(fb.cam));
+    if (fe.kind == EST_ABS) {
+        pl_bundle_options b = front_bundle_options(fe.scaled);
+        b.loss_scale = fe.scaled.bundle.loss_scale * fe.scale;
+        fb.cam = fe.cam;
+        camera_rescale(fb.cam, fe.scale);
+        fb.opt = to_lm(b);
+        fb.cam_flags = fe.cam_flags;
+        fb.point_scale = fe.scale;
+    } else {
+        fb.opt = to_lm(fe.scaled.bundle);
+        fb.cam.model_id = CAM_NULL;
+        fb.cam_flags = 0;
+        fb.point_scale = 1.0;
+    }
+    return fb;
+}
+// abs with the focal length estimated (robust.cc:52): the camera takes the loop's focal length, the bundle's scale follows it
+void front_set_focal(FrontEnd &fe, pl_camera *camera, double focal) {
+    camera_set_focal(camera, focal / fe.scale);
+    fe.cam = to_cam(camera);
+    fe.scale = 1.0 / camera_focal(camera);
+}
+
+// the result in the caller's representation.  abs: when the bundle ran (camera not null), the camera through the reference's
+// camera.rescale(scale) ... rescale(1 / scale) round trip (robust.cc:119-121), with the intrinsics the bundle moved (cam_refined);
+// fund / hom: back to pixels (robust.cc:590-591, 753-754)
+void front_finish(const FrontEnd &fe, const double *rec, const CameraParams *cam_refined, void *model, pl_camera *camera) {
+    if (fe.kind == EST_ABS || fe.kind == EST_REL) {
+        model_from_record(fe.kind, rec, model);
+        if (!camera)
+            return;
+        CameraParams back = fe.cam;
+        camera_rescale(back, fe.scale);
+        if (fe.cam_flags)
+            back = *cam_refined;
+        camera_rescale(back, 1.0 / fe.scale);
+        for (int i = 0; i < camera->num_params && i < 12; ++i)
+            camera->params[i] = back.p[i];
+        return;
+    }
+    Mat3 M;
+    for (int i = 0; i < 9; ++i)
+        M.m[i] = rec[kMatOff + i];
+    if (fe.kind == EST_FUND)
+        M = mul(mul(transpose3(fe.T2), M), fe.T1);
+    else
+        M = mul(mul(inverse3(fe.T2), M), fe.T1);
+    normalize_frobenius(M);
+    mat_to_colmajor(M, static_cast<double *>(model));
+}
+
+// ---------------------------------------------------------------------------- the focal-length loops (pl_focal.h)
+// the loop's options from the (rescaled) robust options; max_focal: absolute_pose.h:78 (-1: none)
+FocalLoopOptions focal_loop_options(const pl_robust_options &o, double max_focal) {
+    FocalLoopOptions lo;
+    lo.max_iterations = o.ransac.max_iterations;
+    lo.min_iterations = o.ransac.min_iterations;
+    lo.seed = o.ransac.seed;
+    lo.dyn_num_trials_mult = o.ransac.dyn_num_trials_mult;
+    lo.success_prob = o.ransac.success_prob;
+    lo.score_initial_model = o.ransac.score_initial_model != 0;
+    lo.max_error = o.max_error;
+    lo.progressive_sampling = o.ransac.progressive_sampling != 0; // sampling.cc:85-136, host-drawn (absolute_pose.h:80 / relative_pose.h:155: sampler(num_data, sample_sz, opt.ransac))
+    lo.max_prosac_iterations = o.ransac.max_prosac_iterations;
+    lo.max_focal = max_focal;
+    return lo;
+}
+void stats_from_focal_loop(const FocalLoopStats &fs, pl_ransac_stats *st) {
+    st->refinements = fs.refinements;
+    st->iterations = fs.iterations;
+    st->num_inliers = fs.num_inliers;
+    st->inlier_ratio = fs.inlier_ratio;
+    st->model_score = fs.model_score;
+    st->hypotheses = fs.hypotheses;
+    st->iterations_evaluated = fs.iterations_evaluated;
+}
+// compute_max_focal_length (absolute_pose.cc:159-177) over the caller's image points (n x 2), un-projected on the host with the same
+// camera_unproject as k_prepare (same operations, same bits; cam null: the points as they stand); -1 without a minimum field of view
+double compute_max_focal_length(const double *xy, size_t n, const CameraParams *cam, double min_fov) {
+    if (!(min_fov > 0))
+        return -1.0;
+    double max_coord = 0.0;
+    for (size_t i = 0; i < n; ++i) {
+        double x = xy[2 * i], y = xy[2 * i + 1];
+        if (cam)
+            camera_unproject(*cam, x, y, x, y);
+        max_coord = std::max(max_coord, std::fabs(x));
+        max_coord = std::max(max_coord, std::fabs(y));
+    }
+    return max_coord / std::tan((min_fov * M_PI / 180.0) / 2.0); // (focal_max_focal_length's expression)
 }
 
 #include "driver_focal.inc"
@@ -2374,6 +2583,17 @@ int pl_ransac_homography(const double *x1, const double *x2, size_t n, const pl_
 }
 
 // ---------------------------------------------------------------------------- front-ends (robust.cc)
+// the final bundle of a front-end over the inliers of the loop's model (the device mask ransac_core / run_focal left in c->mask)
+int front_final_refine(Context *c, pl_problem *p, const FrontEnd &fe, double *rec, CameraParams *cam_refined) {
+    const FrontBundle fb = front_bundle(fe);
+    double out[kModelStride];
+    *cam_refined = fb.cam;
+    int rc = final_refine(c, p, rec, fb.opt, fb.cam, fb.point_scale, out, nullptr, fb.cam_flags, cam_refined);
+    if (rc == PL_OK)
+        std::memcpy(rec, out, sizeof(out));
+    return rc;
+}
+
 int pl_estimate_absolute_pose(const double *points2D, const double *points3D, size_t n, const pl_robust_options *opt,
                               pl_camera *camera, pl_camera_pose *pose, uint8_t *inliers, pl_ransac_stats *stats) {
     int rc = validate_options(opt, /*focal_entry=*/true);
@@ -2385,66 +2605,74 @@ int pl_estimate_absolute_pose(const double *points2D, const double *points3D, si
     rc = get_context(&c);
     if (rc != PL_OK)
         return rc;
-    // robust.cc:40-46 : un-project, rescale the threshold by 1/focal
-    CameraParams cam = to_cam(camera);
-    pl_robust_options scaled = *opt;
-    double scale = 1.0 / camera_focal(camera);
-    scaled.max_error *= scale;
-
+    FrontEnd fe;
+    front_begin(fe, EST_ABS, points2D, points3D, n, *opt, camera, nullptr);
     pl_problem p;
-    rc = make_problem_prepared(c, EST_ABS, points2D, points3D, n, prepare_unproject(cam, nullptr), &p);
+    rc = make_problem_prepared(c, EST_ABS, points2D, points3D, n, fe.prep, &p);
     if (rc != PL_OK)
         return rc;
     pl_ransac_stats local;
     pl_ransac_stats *st = stats ? stats : &local;
     double rec[kModelStride];
-    pl_bundle_options bundle = opt->bundle;
     if (opt->estimate_focal_length) { // robust.cc:47-54: ransac_pnpf on the un-projected points, the camera takes its focal length
         double focal = 1.0;
-        rc = run_focal(c, &p, &scaled, pose, &focal, inliers, st, points2D, &cam);
-        free_problem(&p);
-        if (rc != PL_OK)
-            return rc;
-        camera_set_focal(camera, focal / scale);
-        cam = to_cam(camera);
-        bundle.refine_focal_length = 1; // "force refinement of focal in this case"
-        record_from_pose(pose, false, rec);
+        rc = run_focal(c, &p, &fe.scaled, pose, &focal, inliers, st, points2D, &fe.cam);
+        if (rc == PL_OK) {
+            front_set_focal(fe, camera, focal);
+            record_from_pose(pose, false, rec);
+        }
     } else {
-        rc = run_with_model(c, &p, &scaled, pose, inliers, st, rec);
-        free_problem(&p);
-        if (rc != PL_OK)
-            return rc;
+        front_initial_record(fe, pose, rec);
+        rc = ransac_core(c, &p, &fe.scaled, rec, inliers, st);
     }
+    free_problem(&p);
+    if (rc != PL_OK)
+        return rc;
+    if (st->num_inliers <= front_min_inliers(EST_ABS)) {
+        front_finish(fe, rec, nullptr, pose, nullptr);
+        return PL_OK;
+    }
+    // the bundle sees the pixels as they are (scaled by 1 / focal: front_bundle)
+    CameraParams raw_cam;
+    std::memset(&raw_cam, 0, sizeof(raw_cam));
+    raw_cam.model_id = CAM_NULL;
+    rc = make_problem_prepared(c, EST_ABS, points2D, points3D, n, prepare_unproject(raw_cam, nullptr), &p,
+                               /*resident=*/true, /*lm_only=*/true);
+    if (rc != PL_OK)
+        return rc;
+    CameraParams refined;
+    rc = front_final_refine(c, &p, fe, rec, &refined);
+    free_problem(&p);
+    if (rc != PL_OK)
+        return rc;
+    front_finish(fe, rec, &refined, pose, camera);
+    return PL_OK;
+}
 
-    if (st->num_inliers > 3) { // robust.cc:103-123 : bundle over the inliers in focal-normalised pixels
-        pl_problem pp;
-        CameraParams raw_cam;
-        std::memset(&raw_cam, 0, sizeof(raw_cam));
-        raw_cam.model_id = CAM_NULL; // pixels as they are
-        rc = make_problem_prepared(c, EST_ABS, points2D, points3D, n, prepare_unproject(raw_cam, nullptr), &pp,
-                                   /*resident=*/true, /*lm_only=*/true);
-        if (rc != PL_OK)
-            return rc;
-        scale = 1.0 / camera_focal(camera);
-        pl_bundle_options b = bundle;
-        b.loss_scale = opt->bundle.loss_scale * scale;
-        CameraParams cs = cam;
-        camera_rescale(cs, scale);
-        double out[kModelStride];
-        // bundle.refine_*: the intrinsics the model has among them move with the pose (bundle.cc:93-118)
-        const int cam_flags = active_cam_flags(cs.model_id, bundle);
-        CameraParams refined = cs;
-        rc = final_refine(c, &pp, rec, to_lm(b), cs, scale, out, nullptr, cam_flags, &refined);
-        free_problem(&pp);
-        if (rc != PL_OK)
-            return rc;
-        pose_from_record(out, pose);
-        // camera.rescale(scale) ... rescale(1/scale) round trip of the reference (robust.cc:119-121)
-        CameraParams back = cam_flags ? refined : cs;
-        camera_rescale(back, 1.0 / scale);
-        for (int i = 0; i < camera->num_params && i < 12; ++i)
-            camera->params[i] = back.p[i];
+// relative pose, fundamental matrix, homography: validate, front_begin, the loop, the gated bundle, front_finish
+int estimate_two_view(int kind, const double *x1, const double *x2, size_t n, const pl_camera *camera1, const pl_camera *camera2,
+                      const pl_robust_options *opt, void *model, uint8_t *inliers, pl_ransac_stats *st) {
+    Context *c;
+    int rc = get_context(&c);
+    if (rc != PL_OK)
+        return rc;
+    FrontEnd fe;
+    front_begin(fe, kind, x1, x2, n, *opt, camera1, camera2);
+    double rec[kModelStride];
+    front_initial_record(fe, model, rec);
+    pl_problem p;
+    rc = make_problem_prepared(c, kind, x1, x2, n, fe.prep, &p);
+    if (rc != PL_OK)
+        return rc;
+    rc = ransac_core(c, &p, &fe.scaled, rec, inliers, st);
+    if (rc == PL_OK && st->num_inliers > front_min_inliers(kind)) {
+        CameraParams refined;
+        rc = front_final_refine(c, &p, fe, rec, &refined);
     }
+    free_problem(&p);
+    if (rc != PL_OK)
+        return rc;
+    front_finish(fe, rec, nullptr, model, nullptr);
     return PL_OK;
 }
 
@@ -2456,35 +2684,8 @@ int pl_estimate_relative_pose(const double *x1, const double *x2, size_t n, cons
         return rc;
     if (!camera1 || !camera2 || !camera_supported(camera1) || !camera_supported(camera2))
         return fail(PL_ERR_UNSUPPORTED, "camera model not supported (NULL, SIMPLE_PINHOLE, PINHOLE, OPENCV)");
-    Context *c;
-    rc = get_context(&c);
-    if (rc != PL_OK)
-        return rc;
-    // robust.cc:249-253, 286-292
-    const double scale = 0.5 * (1.0 / camera_focal(camera1) + 1.0 / camera_focal(camera2));
-    pl_robust_options scaled = *opt;
-    scaled.max_error *= scale;
-    scaled.bundle.loss_scale *= scale;
-    const CameraParams c1 = to_cam(camera1), c2 = to_cam(camera2);
-    pl_problem p;
-    rc = make_problem_prepared(c, EST_REL, x1, x2, n, prepare_unproject(c1, &c2), &p);
-    if (rc != PL_OK)
-        return rc;
     pl_ransac_stats local;
-    pl_ransac_stats *st = stats ? stats : &local;
-    double rec[kModelStride];
-    rc = run_with_model(c, &p, &scaled, pose, inliers, st, rec);
-    if (rc == PL_OK && st->num_inliers > 5) { // robust.cc:296-311
-        CameraParams nc;
-        std::memset(&nc, 0, sizeof(nc));
-        nc.model_id = CAM_NULL;
-        double out[kModelStride];
-        rc = final_refine(c, &p, rec, to_lm(scaled.bundle), nc, 1.0, out, nullptr);
-        if (rc == PL_OK)
-            pose_from_record(out, pose);
-    }
-    free_problem(&p);
-    return rc;
+    return estimate_two_view(EST_REL, x1, x2, n, camera1, camera2, opt, pose, inliers, stats ? stats : &local);
 }
 
 int pl_estimate_shared_focal_relative_pose(const double *x1, const double *x2, size_t n, const double *pp, const pl_robust_options *opt,
@@ -2514,7 +2715,7 @@ int pl_estimate_shared_focal_relative_pose(const double *x1, const double *x2, s
     if (rc != PL_OK)
         return rc;
     rc = run_shared_focal(c, &p, &scaled, pose, &f, inliers, st);
-    if (rc == PL_OK && st->num_inliers > 6) // :401-415: refine_shared_focal_relpose over the inliers (c->mask: the device mask)
+    if (rc == PL_OK && st->num_inliers > front_min_inliers(kFrontSharedFocal)) // :401-415: refine_shared_focal_relpose over the inliers (c->mask: the device mask)
         rc = refine_shared_focal(c, &p, to_lm(scaled.bundle), c->mask.as<uint8_t>(), pose, &f, nullptr);
     free_problem(&p);
     if (rc != PL_OK)
@@ -2535,47 +2736,7 @@ int pl_estimate_fundamental(const double *x1, const double *x2, size_t n, const 
         st->model_score = std::numeric_limits<double>::max();
         return PL_OK;
     }
-    Context *c;
-    rc = get_context(&c);
-    if (rc != PL_OK)
-        return rc;
-    Mat3 T1, T2;
-    PrepareArgs prep;
-    const double scale = normalization_of(x1, x2, n, !opt->real_focal_check, T1, T2, prep);
-    pl_robust_options scaled = *opt;
-    scaled.max_error /= scale;
-    scaled.bundle.loss_scale /= scale;
-    Mat3 Fm = mat_from_colmajor(F);
-    if (opt->ransac.score_initial_model) { // robust.cc:566-569
-        Fm = mul(mul(inverse3(transpose3(T2)), Fm), inverse3(T1));
-        normalize_frobenius(Fm);
-    }
-    double Fcm[9];
-    mat_to_colmajor(Fm, Fcm);
-    pl_problem p;
-    rc = make_problem_prepared(c, EST_FUND, x1, x2, n, prep, &p);
-    if (rc != PL_OK)
-        return rc;
-    double rec[kModelStride];
-    rc = run_with_model(c, &p, &scaled, Fcm, inliers, st, rec);
-    if (rc == PL_OK && st->num_inliers > 7) { // robust.cc:573-588
-        CameraParams nc;
-        std::memset(&nc, 0, sizeof(nc));
-        nc.model_id = CAM_NULL;
-        double out[kModelStride];
-        rc = final_refine(c, &p, rec, to_lm(scaled.bundle), nc, 1.0, out, nullptr);
-        if (rc == PL_OK)
-            std::memcpy(rec, out, sizeof(rec));
-    }
-    free_problem(&p);
-    if (rc != PL_OK)
-        return rc;
-    for (int i = 0; i < 9; ++i)
-        Fm.m[i] = rec[kMatOff + i];
-    Fm = mul(mul(transpose3(T2), Fm), T1); // robust.cc:590-591
-    normalize_frobenius(Fm);
-    mat_to_colmajor(Fm, F);
-    return PL_OK;
+    return estimate_two_view(EST_FUND, x1, x2, n, nullptr, nullptr, opt, F, inliers, st);
 }
 
 int pl_estimate_homography(const double *x1, const double *x2, size_t n, const pl_robust_options *opt, double *H,
@@ -2590,47 +2751,7 @@ int pl_estimate_homography(const double *x1, const double *x2, size_t n, const p
         st->model_score = std::numeric_limits<double>::max();
         return PL_OK;
     }
-    Context *c;
-    rc = get_context(&c);
-    if (rc != PL_OK)
-        return rc;
-    Mat3 T1, T2;
-    PrepareArgs prep;
-    const double scale = normalization_of(x1, x2, n, true, T1, T2, prep);
-    pl_robust_options scaled = *opt;
-    scaled.max_error /= scale;
-    scaled.bundle.loss_scale /= scale;
-    Mat3 Hm = mat_from_colmajor(H);
-    if (opt->ransac.score_initial_model) { // robust.cc:729-732
-        Hm = mul(mul(T2, Hm), inverse3(T1));
-        normalize_frobenius(Hm);
-    }
-    double Hcm[9];
-    mat_to_colmajor(Hm, Hcm);
-    pl_problem p;
-    rc = make_problem_prepared(c, EST_HOM, x1, x2, n, prep, &p);
-    if (rc != PL_OK)
-        return rc;
-    double rec[kModelStride];
-    rc = run_with_model(c, &p, &scaled, Hcm, inliers, st, rec);
-    if (rc == PL_OK && st->num_inliers > 4) { // robust.cc:736-751
-        CameraParams nc;
-        std::memset(&nc, 0, sizeof(nc));
-        nc.model_id = CAM_NULL;
-        double out[kModelStride];
-        rc = final_refine(c, &p, rec, to_lm(scaled.bundle), nc, 1.0, out, nullptr);
-        if (rc == PL_OK)
-            std::memcpy(rec, out, sizeof(rec));
-    }
-    free_problem(&p);
-    if (rc != PL_OK)
-        return rc;
-    for (int i = 0; i < 9; ++i)
-        Hm.m[i] = rec[kMatOff + i];
-    Hm = mul(mul(inverse3(T2), Hm), T1); // robust.cc:753-754
-    normalize_frobenius(Hm);
-    mat_to_colmajor(Hm, H);
-    return PL_OK;
+    return estimate_two_view(EST_HOM, x1, x2, n, nullptr, nullptr, opt, H, inliers, st);
 }
 
 // ---------------------------------------------------------------------------- un-distortion stage

@@ -200,66 +200,25 @@ struct DeviceFocalBackend {
 // ransac_pnpf on a resident absolute-pose problem (normalised image points, principal point at the origin).  The device mask of
 // the returned model stays in c->mask (the front-end's final bundle reads it).
 // host_xy: the caller's image points (n x 2, as it passed them) and host_cam, the camera they are un-projected with (nullptr: they
-// are the problem's points as they stand) - compute_max_focal_length walks the image points, and the host evaluates the same
-// camera_unproject as k_prepare (same operations, same bits) instead of reading two arrays back from the device.
+// are the problem's points as they stand) - compute_max_focal_length walks the image points on the host.
 int run_focal(Context *c, const pl_problem *p, const pl_robust_options *o, pl_camera_pose *pose, double *focal, uint8_t *inliers,
-              pl_ransac_stats *st, const double *host_xy = nullptr, const CameraParams *host_cam = nullptr) {
+              pl_ransac_stats *st, const double *host_xy, const CameraParams *host_cam) {
     if (p->kind != EST_ABS)
         return fail(PL_ERR_INVALID, "the focal-length estimator works on absolute-pose problems");
     const double t_start = now_s();
     std::memset(st, 0, sizeof(*st));
     const uint32_t n = p->n;
-    // compute_max_focal_length (absolute_pose.cc:159-177) walks the image points
-    double max_focal_length = -1.0;
-    if (o->min_fov > 0) {
-        if (host_xy || n == 0) {
-            double max_coord = 0.0;
-            for (uint32_t i = 0; i < n; ++i) {
-                double x = host_xy[2 * (size_t)i], y = host_xy[2 * (size_t)i + 1];
-                if (host_cam)
-                    camera_unproject(*host_cam, x, y, x, y);
-                max_coord = std::max(max_coord, std::fabs(x));
-                max_coord = std::max(max_coord, std::fabs(y));
-            }
-            max_focal_length = max_coord / std::tan((o->min_fov * M_PI / 180.0) / 2.0); // (focal_max_focal_length's expression)
-        } else { // two arrays back from the device (into pinned memory: a copy to pageable memory pins and unpins its target under the process's memory-map lock)
-            HIP_TRY(c->h_focal.ensure(sizeof(double) * 2 * n));
-            HIP_TRY(hipMemcpyAsync(c->h_focal.p, p->ps.a[0], sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipMemcpyAsync(c->h_focal.as<double>() + n, p->ps.a[1], sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            max_focal_length = focal_max_focal_length(c->h_focal.as<double>(), c->h_focal.as<double>() + n, n, o->min_fov);
-        }
-    }
-    FocalLoopOptions lo;
-    lo.max_iterations = o->ransac.max_iterations;
-    lo.min_iterations = o->ransac.min_iterations;
-    lo.seed = o->ransac.seed;
-    lo.dyn_num_trials_mult = o->ransac.dyn_num_trials_mult;
-    lo.success_prob = o->ransac.success_prob;
-    lo.score_initial_model = false; // ransac.cc:61-66 resets the model before the loop: an initial model cannot be passed in
-    lo.max_error = o->max_error;
-    lo.progressive_sampling = o->ransac.progressive_sampling != 0; // sampling.cc:85-136, host-drawn (absolute_pose.h:80 / relative_pose.h:155: sampler(num_data, sample_sz, opt.ransac))
-    lo.max_prosac_iterations = o->ransac.max_prosac_iterations;
-    lo.max_focal = max_focal_length; /* absolute_pose.h:78 */
+    const FocalLoopOptions lo = focal_loop_options(*o, compute_max_focal_length(host_xy, n, host_cam, o->min_fov));
     DeviceFocalBackend be{c, p, o->ransac.seed, o->max_error * o->max_error, o->max_error, lo.max_focal, lo_options(o->max_error)};
     FocalModel best;
     std::memset(&best, 0, sizeof(best));
     best.q[0] = 1.0;
     best.f = 1.0;
-    FocalLoopStats fs;
-    if (o->ransac.score_initial_model) { // (the reference scores the identity pose it has just written)
-        lo.score_initial_model = true;
-    }
+    FocalLoopStats fs; // (score_initial_model: the reference scores the identity pose it has just written, ransac.cc:61-66)
     int rc = focal_lo_ransac(be, n, lo, &best, &fs);
     if (rc != PL_OK)
         return rc;
-    st->refinements = fs.refinements;
-    st->iterations = fs.iterations;
-    st->num_inliers = fs.num_inliers;
-    st->inlier_ratio = fs.inlier_ratio;
-    st->model_score = fs.model_score;
-    st->hypotheses = fs.hypotheses;
-    st->iterations_evaluated = fs.iterations_evaluated;
+    stats_from_focal_loop(fs, st);
     for (int i = 0; i < 4; ++i)
         pose->q[i] = best.q[i];
     for (int i = 0; i < 3; ++i)

@@ -5,7 +5,7 @@
 // chain of ~11 dispatches and ~8 synchronisations on its own stream (driver_focal.inc, driver_sfocal.inc): 16 hardware queues bounded
 // the throughput at 5.4 k / 4.2 k problems per second.  Here up to kFocalGroupMax problems of one estimator advance in lock-step:
 //
-//   stage A  front-end arithmetic per item on the host (the same expressions as the single-problem entry points), the raw
+//   stage A  front-end arithmetic per item on the host (front_begin, like the single-problem entry points), the raw
 //            correspondences of all members -> one pinned block -> one upload; k_prepare_g (un-projection / normalisation)
 //   rounds   every member's loop (pl_focal.h FocalLoop - the code the single-problem path runs) is advanced to its next request;
 //            the requests of all members are evaluated together - a batch of iterations for the members that ask for one
@@ -26,10 +26,7 @@ struct FocalGroupItem {
     int est = 0; // 0: absolute pose with unknown focal length, 1: shared-focal relative pose
     uint32_t n = 0;
     bool fallback = false;
-    // front-end (stage A)
-    pl_robust_options scaled;
-    double scale = 1.0;
-    PrepareArgs prep;
+    FrontEnd fe;            // front-end (stage A; est 1: scaled, scale and prep of robust.cc:373-390)
     CameraParams cam{};     // est 0: the caller's camera as it came in (snapshot taken when the item is created)
     bool cam_saved = false; // cam holds the caller's camera: a failed group may restore it before the item is retried on its own
     double max_focal = -1.0; // est 0: compute_max_focal_length (absolute_pose.cc:159-177)
@@ -202,56 +199,28 @@ struct SFocalGroupPolicy {
     }
 };
 
-// compute_max_focal_length (absolute_pose.cc:159-177) over the caller's image points, un-projected on the host with the same
-// camera_unproject as k_prepare (same operations, same bits)
-double focal_host_max_focal(const double *host_xy, size_t n, const CameraParams *host_cam, double min_fov) {
-    double max_coord = 0.0;
-    for (size_t i = 0; i < n; ++i) {
-        double x = host_xy[2 * i], y = host_xy[2 * i + 1];
-        if (host_cam)
-            camera_unproject(*host_cam, x, y, x, y);
-        max_coord = std::max(max_coord, std::fabs(x));
-        max_coord = std::max(max_coord, std::fabs(y));
-    }
-    return max_coord / std::tan((min_fov * M_PI / 180.0) / 2.0); // (focal_max_focal_length's expression)
-}
-
 // stage A, host half: what pl_estimate_absolute_pose / pl_estimate_shared_focal_relative_pose compute before the loop
 void focal_group_prepare_item(FocalGroupItem &g) {
     pl_batch_item &it = *g.item;
     g.n = (uint32_t)it.n;
     g.st = it.stats ? it.stats : &g.local_st;
-    g.scaled = *it.opt;
-    std::memset(&g.prep, 0, sizeof(g.prep));
-    std::memset(&g.cam, 0, sizeof(g.cam));
-    FocalLoopOptions &lo = g.lo;
+    FrontEnd &fe = g.fe;
     if (g.est == 0) { // robust.cc:40-54
-        g.cam = to_cam(it.camera1);
-        g.scale = 1.0 / camera_focal(it.camera1);
-        g.scaled.max_error *= g.scale;
-        g.prep = prepare_unproject(g.cam, nullptr);
-        g.max_focal = g.scaled.min_fov > 0 ? focal_host_max_focal(it.a, it.n, &g.cam, g.scaled.min_fov) : -1.0;
-        lo.score_initial_model = false; // ransac.cc:61-66 resets the model before the loop
-        lo.max_focal = g.max_focal;      // absolute_pose.h:78
+        front_begin(fe, EST_ABS, it.a, it.b, it.n, *it.opt, it.camera1, nullptr);
+        g.max_focal = compute_max_focal_length(it.a, it.n, &fe.cam, fe.scaled.min_fov);
     } else { // robust.cc:373-390
+        fe = FrontEnd();
+        fe.kind = kFrontSharedFocal;
+        fe.scaled = *it.opt;
         const double *pp = it.camera1->params + 1;
-        g.scale = normalization_about(it.a, it.b, it.n, pp[0], pp[1], g.prep);
-        g.scaled.max_error /= g.scale;
-        g.scaled.bundle.loss_scale /= g.scale;
-        lo.score_initial_model = false;
-        lo.max_focal = -1.0;
+        fe.scale = normalization_about(it.a, it.b, it.n, pp[0], pp[1], fe.prep);
+        fe.scaled.max_error /= fe.scale;
+        fe.scaled.bundle.loss_scale /= fe.scale;
+        g.max_focal = -1.0;
     }
-    const pl_robust_options &o = g.scaled;
-    lo.max_iterations = o.ransac.max_iterations;
-    lo.min_iterations = o.ransac.min_iterations;
-    lo.seed = o.ransac.seed;
-    lo.dyn_num_trials_mult = o.ransac.dyn_num_trials_mult;
-    lo.success_prob = o.ransac.success_prob;
-    lo.max_error = o.max_error;
-    lo.progressive_sampling = o.ransac.progressive_sampling != 0; // sampling.cc:85-136: FocalLoop draws the batch's samples on the host
-    lo.max_prosac_iterations = o.ransac.max_prosac_iterations;
-    g.thr2 = o.max_error * o.max_error;
-    g.lm_lo = lo_options(o.max_error);
+    g.lo = focal_loop_options(fe.scaled, g.max_focal); // (no warm starts among the members: score_initial_model is 0)
+    g.thr2 = fe.scaled.max_error * fe.scaled.max_error;
+    g.lm_lo = lo_options(fe.scaled.max_error);
     std::memset(&g.best, 0, sizeof(g.best)); // ransac.cc:61-66 / 185-190
     g.best.q[0] = 1.0;
     g.best.f = 1.0;
@@ -265,47 +234,35 @@ void focal_group_loop_result(FocalGroupItem &g) {
     for (int i = 0; i < 3; ++i)
         pose->t[i] = g.best.t[i];
     if (g.est == 0)
-        camera_set_focal(g.item->camera1, g.best.f / g.scale); // robust.cc:52 (the camera takes the focal length)
+        front_set_focal(g.fe, g.item->camera1, g.best.f); // robust.cc:52 (the camera takes the focal length)
 }
 // robust.cc:103-123 with bundle.refine_focal_length forced (:53): the inliers in focal-normalised pixels, pose and focal length free
-void focal_group_bundle_task(LMTask &t, FocalGroupItem &g, double &scale, CameraParams &cs) {
-    const pl_robust_options &opt = *g.item->opt;
-    pl_bundle_options bundle = opt.bundle;
-    bundle.refine_focal_length = 1; // "force refinement of focal in this case"
-    scale = 1.0 / camera_focal(g.item->camera1);
-    pl_bundle_options b = bundle;
-    b.loss_scale = opt.bundle.loss_scale * scale;
-    cs = to_cam(g.item->camera1);
-    camera_rescale(cs, scale);
+void focal_group_bundle_task(LMTask &t, FocalGroupItem &g) {
+    const FrontBundle fb = front_bundle(g.fe); // (cam_flags never 0: every model the path takes has a focal length)
     double rec[kModelStride];
     record_from_pose(static_cast<const pl_camera_pose *>(g.item->model), false, rec);
     std::memset(&t, 0, sizeof(t));
     t.pts = g.prob_raw.ps;
     lm_params_from_record(EST_ABS, rec, t.params);
-    t.opt = to_lm(b);
-    t.cam = cs;
-    t.point_scale = scale;
-    t.cam_flags = active_cam_flags(cs.model_id, bundle); // (never 0: every model the path takes has a focal length)
+    t.opt = fb.opt;
+    t.cam = fb.cam;
+    t.point_scale = fb.point_scale;
+    t.cam_flags = fb.cam_flags;
     t.mask = g.d_mask;
 }
-void focal_group_finish_item(FocalGroupItem &g, const LMTask *t, double scale, const CameraParams &cs) {
+void focal_group_finish_item(FocalGroupItem &g, const LMTask *t) {
     if (!t)
         return;
     pl_camera_pose *pose = static_cast<pl_camera_pose *>(g.item->model);
-    if (!t->skipped) {
-        double out[kModelStride];
-        record_from_lm_params(EST_ABS, t->params, out); // (same inline function as the device)
-        pose_from_record(out, pose);
-    }
-    // camera.rescale(scale) ... rescale(1/scale) round trip of the reference (robust.cc:119-121)
-    CameraParams back = t->cam_flags ? t->cam : cs;
-    camera_rescale(back, 1.0 / scale);
-    pl_camera *camera = g.item->camera1;
-    for (int i = 0; i < camera->num_params && i < 12; ++i)
-        camera->params[i] = back.p[i];
+    double rec[kModelStride];
+    if (t->skipped)
+        record_from_pose(pose, false, rec);
+    else
+        record_from_lm_params(EST_ABS, t->params, rec); // (same inline function as the device)
+    front_finish(g.fe, rec, &t->cam, pose, g.item->camera1);
 }
 // robust.cc:401-417: refine_shared_focal_relpose over the inliers, the focal length back in pixels
-void focal_group_bundle_task(SFocalLMTask &t, FocalGroupItem &g, double &, CameraParams &) {
+void focal_group_bundle_task(SFocalLMTask &t, FocalGroupItem &g) {
     std::memset(&t, 0, sizeof(t));
     for (int i = 0; i < 4; ++i)
         t.a[i] = g.prob.ps.a[i];
@@ -315,12 +272,12 @@ void focal_group_bundle_task(SFocalLMTask &t, FocalGroupItem &g, double &, Camer
     for (int i = 0; i < 3; ++i)
         t.params[4 + i] = g.best.t[i];
     t.params[kSFocalFocalSlot] = g.best.f;
-    t.opt = to_lm(g.scaled.bundle);
+    t.opt = to_lm(g.fe.scaled.bundle);
     t.prefilter_thr2 = 0.0;
     t.mask = g.d_mask;
     t.scratch = nullptr;
 }
-void focal_group_finish_item(FocalGroupItem &g, const SFocalLMTask *t, double, const CameraParams &) {
+void focal_group_finish_item(FocalGroupItem &g, const SFocalLMTask *t) {
     double f = g.best.f;
     if (t && !t->skipped) {
         pl_camera_pose *pose = static_cast<pl_camera_pose *>(g.item->model);
@@ -330,7 +287,7 @@ void focal_group_finish_item(FocalGroupItem &g, const SFocalLMTask *t, double, c
             pose->t[i] = t->params[4 + i];
         f = t->params[kSFocalFocalSlot];
     }
-    g.item->camera1->params[0] = f * g.scale; // :417
+    g.item->camera1->params[0] = f * g.fe.scale; // :417
 }
 
 template <class P> int run_focal_group(Context *c, FocalGroupItem *const *pit, uint32_t count) {
@@ -419,7 +376,7 @@ template <class P> int run_focal_group(Context *c, FocalGroupItem *const *pit, u
                 e.absmax_bits = nullptr;
             };
             problem_at(g.prob, pts_off[i]);
-            entry(hp[i], g.prep, g.prob);
+            entry(hp[i], g.fe.prep, g.prob);
             if (P::kEst == 0) {
                 problem_at(g.prob_raw, raw_pts_off[i]);
                 entry(hp[count + i], prepare_unproject(raw_cam, nullptr), g.prob_raw);
@@ -626,14 +583,7 @@ template <class P> int run_focal_group(Context *c, FocalGroupItem *const *pit, u
         const size_t mask_stride = align_up(max_n);
         for (uint32_t i = 0; i < count; ++i) {
             FocalGroupItem &g = *pit[i];
-            pl_ransac_stats *st = g.st;
-            st->refinements = g.fs.refinements;
-            st->iterations = g.fs.iterations;
-            st->num_inliers = g.fs.num_inliers;
-            st->inlier_ratio = g.fs.inlier_ratio;
-            st->model_score = g.fs.model_score;
-            st->hypotheses = g.fs.hypotheses;
-            st->iterations_evaluated = g.fs.iterations_evaluated;
+            stats_from_focal_loop(g.fs, g.st);
             focal_group_loop_result(g);
             FocalMaskArgs &ma = hm[i];
             std::memset(&ma, 0, sizeof(ma));
@@ -651,10 +601,8 @@ template <class P> int run_focal_group(Context *c, FocalGroupItem *const *pit, u
         std::vector<int> task_of(count, -1);
         uint32_t nb = 0;
         for (uint32_t i = 0; i < count; ++i)
-            if (pit[i]->st->num_inliers > (P::kEst == 0 ? 3u : 6u))
+            if (pit[i]->st->num_inliers > front_min_inliers(P::kEst == 0 ? EST_ABS : kFrontSharedFocal))
                 task_of[i] = (int)nb++;
-        std::vector<double> bundle_scale(count, 1.0);
-        std::vector<CameraParams> bundle_cam(count);
         if (nb) {
             HIP_TRY(gc.h_tasks.ensure(sizeof(Task) * nb));
             Task *ht = gc.h_tasks.as<Task>();
@@ -662,7 +610,7 @@ template <class P> int run_focal_group(Context *c, FocalGroupItem *const *pit, u
                 if (task_of[i] < 0)
                     continue;
                 FocalGroupItem &g = *pit[i];
-                focal_group_bundle_task(ht[task_of[i]], g, bundle_scale[i], bundle_cam[i]);
+                focal_group_bundle_task(ht[task_of[i]], g);
             }
             HIP_TRY(P::lm(gc.h_tasks.dev<Task>(), nb, c->stream));
         }
@@ -672,7 +620,7 @@ template <class P> int run_focal_group(Context *c, FocalGroupItem *const *pit, u
             FocalGroupItem &g = *pit[i];
             if (g.item->inliers && g.n)
                 std::memcpy(g.item->inliers, gc.h_mask.as<uint8_t>() + mask_stride * i, g.n);
-            focal_group_finish_item(g, task_of[i] >= 0 ? &ht[task_of[i]] : nullptr, bundle_scale[i], bundle_cam[i]);
+            focal_group_finish_item(g, task_of[i] >= 0 ? &ht[task_of[i]] : nullptr);
             g.st->seconds = now_s() - g.t_start;
             g.item->status = PL_OK;
         }

@@ -130,13 +130,8 @@ struct GroupItem {
     pl_ransac_item *ritem = nullptr; // device-resident problem (pl_ransac_batch) instead of `item`
     int kind = 0;
     uint32_t n = 0;
-    pl_robust_options scaled;   // options of the ransac_* part (thresholds rescaled the way the front-end does)
-    double scale = 1.0;         // abs: 1 / focal; rel: mean inverse focal; hom / fund: normalisation scale
-    Mat3 T1, T2;                // hom / fund normalisation
-    PrepareArgs prep;
-    CameraParams cam1;          // abs: the camera (final bundle)
-    int cam_flags = 0;          // abs: CamRefineFlags of the final bundle (opt->bundle.refine_*), 0 = pose alone
-    CameraParams cam_refined;   // abs, cam_flags != 0: the rescaled camera after the bundle
+    FrontEnd fe;                // the front-end's options, normalisation and final bundle (resident problems: the options alone)
+    CameraParams cam_refined;   // abs, fe.cam_flags != 0: the rescaled camera after the bundle
     pl_problem prob;            // borrowed SoA block in the arena
     double rec[kModelStride];   // best model record
     pl_ransac_stats local_st;
@@ -245,33 +240,7 @@ int group_prepare_item(GroupItem &g) {
     g.kind = it.kind;
     g.n = (uint32_t)it.n;
     g.st = it.stats ? it.stats : &g.local_st;
-    g.scaled = *it.opt;
-    std::memset(&g.prep, 0, sizeof(g.prep));
-    std::memset(&g.cam1, 0, sizeof(g.cam1));
-    switch (it.kind) {
-    case EST_ABS: { // robust.cc:40-46
-        g.cam1 = to_cam(it.camera1);
-        g.scale = 1.0 / camera_focal(it.camera1);
-        g.scaled.max_error *= g.scale;
-        g.prep = prepare_unproject(g.cam1, nullptr);
-        break;
-    }
-    case EST_REL: { // robust.cc:249-253, 286-292
-        g.scale = 0.5 * (1.0 / camera_focal(it.camera1) + 1.0 / camera_focal(it.camera2));
-        g.scaled.max_error *= g.scale;
-        g.scaled.bundle.loss_scale *= g.scale;
-        const CameraParams c1 = to_cam(it.camera1), c2 = to_cam(it.camera2);
-        g.prep = prepare_unproject(c1, &c2);
-        break;
-    }
-    default: { // robust.cc:552-562, 720-726
-        const bool centroid = it.kind == EST_HOM ? true : !it.opt->real_focal_check;
-        g.scale = normalization_of(it.a, it.b, it.n, centroid, g.T1, g.T2, g.prep);
-        g.scaled.max_error /= g.scale;
-        g.scaled.bundle.loss_scale /= g.scale;
-        break;
-    }
-    }
+    front_begin(g.fe, it.kind, it.a, it.b, it.n, *it.opt, it.camera1, it.camera2);
     return PL_OK;
 }
 
@@ -280,61 +249,17 @@ int group_prepare_resident(GroupItem &g) {
     g.kind = it.problem->kind;
     g.n = it.problem->n;
     g.st = it.stats ? it.stats : &g.local_st;
-    g.scaled = *it.opt;
-    g.scale = 1.0;
-    std::memset(&g.prep, 0, sizeof(g.prep));
-    std::memset(&g.cam1, 0, sizeof(g.cam1));
+    g.fe = FrontEnd();
+    g.fe.kind = g.kind;
+    g.fe.scaled = *it.opt;
     return PL_OK;
 }
 
-// upper bound of max(|x|, |y|) of the un-projected 2-D points (linear cameras; make_problem_prepared does the same)
-float host_xy_absmax(const CameraParams &cam, const double *a, size_t n) {
-    double cx = 0, cy = 0, fx = 1, fy = 1;
-    if (cam.model_id == CAM_SIMPLE_PINHOLE)
-        fx = fy = cam.p[0], cx = cam.p[1], cy = cam.p[2];
-    else if (cam.model_id == CAM_PINHOLE)
-        fx = cam.p[0], fy = cam.p[1], cx = cam.p[2], cy = cam.p[3];
-    double m = 0.0;
-    for (size_t i = 0; i < n; ++i) {
-        const double u = std::fabs((a[2 * i] - cx) / fx), v = std::fabs((a[2 * i + 1] - cy) / fy);
-        m = (u > m || u != u) ? u : m; // NaN propagates (and disables the pre-filter)
-        m = (v > m || v != v) ? v : m;
-    }
-    m = m * (1.0 + 1e-12);
-    return std::nextafter((float)m, std::numeric_limits<float>::infinity());
-}
-
-// One group: `count` items of the same kind.  Items the path cannot finish get fallback = true.
-// bound of max(|x|, |y|) of an item's un-projected points, as the scorers' pre-filters take it (same expressions as before round 4)
-// the caller's initial model (ransac.score_initial_model) as the record the loop starts from - what the front-ends hand to
-// run_with_model: poses as they are, F and H in the normalised coordinates of the problem (robust.cc:566-569, 729-732)
-void group_initial_record(const GroupItem &g, double *rec) {
-    const void *model = g.item ? g.item->model : g.ritem->model;
-    if (g.kind == EST_ABS || g.kind == EST_REL) {
-        record_from_pose(static_cast<const pl_camera_pose *>(model), g.kind == EST_REL, rec);
-        return;
-    }
-    Mat3 M = mat_from_colmajor(static_cast<const double *>(model));
-    if (g.item) { // (a front-end item: pixels; a resident problem's model is in the problem's coordinates already)
-        M = g.kind == EST_FUND ? mul(mul(inverse3(transpose3(g.T2)), M), inverse3(g.T1)) : mul(mul(g.T2, M), inverse3(g.T1));
-        normalize_frobenius(M);
-        // (through column-major and back like the front-ends: the same doubles)
-        double cm[9];
-        mat_to_colmajor(M, cm);
-        M = mat_from_colmajor(cm);
-    }
-    store_matrix_model(rec, M);
-}
-
-bool group_absmax_on_device(const GroupItem &g) { return g.kind == EST_ABS && g.cam1.model_id == CAM_OPENCV; }
+// the bound of max(|x|, |y|) of an item's prepared points (+inf while stage A has still to read it back from the device)
 float group_item_absmax(const GroupItem &g) {
-    if (group_absmax_on_device(g)) // (the iterative un-projection runs on the device: stage A reads the bound back)
+    if (prefilter_bound_on_device(g.kind, g.fe.prep))
         return std::numeric_limits<float>::infinity();
-    if (g.kind == EST_ABS)
-        return host_xy_absmax(g.cam1, g.item->a, g.n);
-    if (g.n >= 1024)
-        return host_two_view_absmax(g.prep, g.item->a, g.item->b, g.n);
-    return std::numeric_limits<float>::infinity();
+    return host_prefilter_bound(g.kind, g.fe.prep, g.item->a, g.item->b, g.n);
 }
 
 // The host half of stage A for a group this worker will run NEXT, done while it waits for the device with the current group: the
@@ -370,6 +295,7 @@ void group_stage_in(GroupItem *const *pit, uint32_t count) {
     gc.staged_first = pit[0];
 }
 
+// One group: `count` items of the same kind.  Items the path cannot finish get fallback = true.
 // `max_steps` > 0: at most so many batch steps; problems that are still running then are DEFERRED (g.deferred: their RansacRun is
 // kept, stages D / E skip them) - pl_estimate_batch regroups the deferred problems of all groups and calls again with `resume`
 // (stage A uploads their points again, stage B keeps the runs), now with batches of up to 32768 iterations: the few long runs of a
@@ -401,7 +327,7 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
     for (uint32_t i = 0; i < count; ++i) {
         GroupItem &g = (*pit[i]);
         max_n = std::max(max_n, g.n);
-        uint64_t grow = std::max<uint64_t>(g.scaled.ransac.min_iterations + 2, 512);
+        uint64_t grow = std::max<uint64_t>(g.fe.scaled.ransac.min_iterations + 2, 512);
         if (resume && g.run)
             grow = std::max<uint64_t>(grow, g.run->needed_now());
         grow = (grow + 63) / 64 * 64;
@@ -533,10 +459,10 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
             hp[i].b_raw = gc.raw.as<double>() + g.raw_b_off;
             hp[i].n = g.n;
             hp[i].pad = 0;
-            hp[i].args = g.prep;
+            hp[i].args = g.fe.prep;
             hp[i].soa = reinterpret_cast<double *>(slot(i, L.pts));
             // (the bound of max|x| comes from the host for the linear cameras; OPENCV: k_prepare_g leaves it in the slot)
-            hp[i].absmax_bits = group_absmax_on_device(g) ? reinterpret_cast<unsigned long long *>(slot(i, L.absmax)) : nullptr;
+            hp[i].absmax_bits = prefilter_bound_on_device(kind, g.fe.prep) ? reinterpret_cast<unsigned long long *>(slot(i, L.absmax)) : nullptr;
             if (hp[i].absmax_bits) {
                 HIP_TRY(hipMemsetAsync(hp[i].absmax_bits, 0, sizeof(unsigned long long), c->stream));
                 ++n_dev_absmax;
@@ -597,12 +523,14 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
             continue;
         }
         g.t_start = now_s();
-        const bool warm = g.scaled.ransac.score_initial_model != 0;
-        if (warm)
-            group_initial_record(g, g.rec); // the caller's model in the loop's coordinates (robust.cc:566-569, 729-732)
+        const bool warm = g.fe.scaled.ransac.score_initial_model != 0;
+        if (!resident)
+            front_initial_record(g.fe, g.item->model, g.rec);
+        else if (warm) // (a resident problem's model is in the problem's coordinates already)
+            record_from_model(kind, g.ritem->model, g.rec);
         else
             identity_record(kind, g.rec);
-        g.run = new RansacRun(c, &g.prob, &g.scaled, g.rec, nullptr, g.st);
+        g.run = new RansacRun(c, &g.prob, &g.fe.scaled, g.rec, nullptr, g.st);
         g.run->MAXM = (int)maxm;
         std::memset(g.st, 0, sizeof(*g.st));
         g.st->model_score = std::numeric_limits<double>::max();
@@ -870,7 +798,7 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
             ga.ctl = d_ctl;
             ga.models = reinterpret_cast<double *>(slot(i, L.models));
             ga.num_models = reinterpret_cast<uint32_t *>(slot(i, L.num_models));
-            ga.real_focal_check = g.scaled.real_focal_check;
+            ga.real_focal_check = g.fe.scaled.real_focal_check;
             ga.blk_tot = blk_tot;
             ga.blk_nan = blk_tot + nblk;
             ga.stage = generate_stage_bytes(kind, B) ? slot(i, L.gen_stage) : nullptr;
@@ -1063,29 +991,21 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
     // start_record / gate_count) - everything else they need is known to the host before stage D.  One wait per group less (of ~6).
     // Not for the fundamental matrix (its starting parameters are an SVD of F on the host) and not for resident problems (no stage E).
     const bool merged_tail = !resident && kind != EST_FUND;
-    const uint64_t min_inl = kind == EST_ABS ? 3 : kind == EST_REL ? 5 : kind == EST_FUND ? 7 : 4;
+    const uint64_t min_inl = front_min_inliers(kind);
     uint32_t ne = 0, ne_cam = 0; // merged tail: stage E's tasks / those with camera intrinsics
-    auto fill_bundle_task = [&](uint32_t i, GroupItem &g, LMTask &T) { // robust.cc:103-123, 296-311, 736-751
+    auto fill_bundle_task = [&](uint32_t i, GroupItem &g, LMTask &T) { // front_bundle over the inliers; abs: on the raw pixels
+        const FrontBundle fb = front_bundle(g.fe);
         std::memset(&T, 0, sizeof(T));
         T.pts = g.prob.ps;
         if (kind == EST_ABS) {
             double *soa2 = reinterpret_cast<double *>(slot(i, L.pts2));
             for (int d = 0; d < nd; ++d)
                 T.pts.a[d] = soa2 + (size_t)d * g.n;
-            pl_bundle_options b = g.item->opt->bundle;
-            b.loss_scale = g.item->opt->bundle.loss_scale * g.scale;
-            CameraParams cs = g.cam1;
-            camera_rescale(cs, g.scale);
-            T.opt = to_lm(b);
-            T.cam = cs;
-            T.cam_flags = g.cam_flags;
-            T.point_scale = g.scale;
-        } else {
-            T.opt = to_lm(g.scaled.bundle);
-            std::memset(&T.cam, 0, sizeof(T.cam));
-            T.cam.model_id = CAM_NULL;
-            T.point_scale = 1.0;
         }
+        T.opt = fb.opt;
+        T.cam = fb.cam;
+        T.cam_flags = fb.cam_flags;
+        T.point_scale = fb.point_scale;
         T.prefilter_thr2 = 0.0;
         T.mask = reinterpret_cast<uint8_t *>(slot(i, L.mask));
         T.scratch = nullptr;
@@ -1205,9 +1125,8 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
                     GroupItem &g = (*pit[i]);
                     if (g.fallback || g.deferred || !g.looped)
                         continue;
-                    g.cam_flags = (kind == EST_ABS) ? active_cam_flags(g.cam1.model_id, g.item->opt->bundle) : 0;
                     ne++;
-                    ne_cam += g.cam_flags ? 1u : 0u;
+                    ne_cam += g.fe.cam_flags ? 1u : 0u;
                 }
                 HIP_TRY(gc.h_tail.ensure(sizeof(LMTask) * std::max<uint32_t>(ne, 1u)));
                 LMTask *he = gc.h_tail.as<LMTask>();
@@ -1229,7 +1148,7 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
                     GroupItem &g = (*pit[i]);
                     if (g.fallback || g.deferred || !g.looped)
                         continue;
-                    g.job_e = g.cam_flags ? next_cam++ : next_plain++;
+                    g.job_e = g.fe.cam_flags ? next_cam++ : next_plain++;
                     LMTask &T = he[g.job_e];
                     fill_bundle_task(i, g, T);
                     T.start_record = reinterpret_cast<const double *>(slot(i, L.tmp_model));
@@ -1268,14 +1187,7 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
             GroupItem &g = (*pit[i]);
             if (g.fallback || g.deferred)
                 continue;
-            if (kind == EST_ABS || kind == EST_REL) {
-                pose_from_record(g.rec, static_cast<pl_camera_pose *>(g.ritem->model));
-            } else {
-                Mat3 M;
-                for (int k = 0; k < 9; ++k)
-                    M.m[k] = g.rec[kMatOff + k];
-                mat_to_colmajor(M, static_cast<double *>(g.ritem->model));
-            }
+            model_from_record(kind, g.rec, g.ritem->model);
             g.ritem->status = PL_OK;
         }
         return PL_OK;
@@ -1295,118 +1207,45 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
             if (!want)
                 continue;
             record_from_lm_params(kind, he[g.job_e].params, g.rec);
-            if (g.cam_flags)
+            if (g.fe.cam_flags)
                 g.cam_refined = he[g.job_e].cam;
         }
-    } else {
-        uint32_t nt = 0, ncam = 0; // tasks; those of them that refine intrinsics with the pose (k_lm_cam): the list's tail
-        PrepareGroupArgs *hp2 = gc.h_args.as<PrepareGroupArgs>();
-        for (uint32_t i = 0; i < count; ++i) {
-            GroupItem &g = (*pit[i]);
-            std::memset(&hp2[i], 0, sizeof(PrepareGroupArgs));
-            if (g.fallback || g.deferred || !(g.st->num_inliers > min_inl))
-                continue;
-            g.cam_flags = (kind == EST_ABS) ? active_cam_flags(g.cam1.model_id, g.item->opt->bundle) : 0;
-            nt++;
-            ncam += g.cam_flags ? 1u : 0u;
-            if (kind == EST_ABS) { // robust.cc:103-123: the bundle sees the pixels as they are, scaled by 1 / focal
-                CameraParams raw_cam;
-                std::memset(&raw_cam, 0, sizeof(raw_cam));
-                raw_cam.model_id = CAM_NULL;
-                hp2[i].a_raw = gc.raw.as<double>() + g.raw_a_off;
-                hp2[i].b_raw = gc.raw.as<double>() + g.raw_b_off;
-                hp2[i].n = g.n;
-                hp2[i].args = prepare_unproject(raw_cam, nullptr);
-                hp2[i].soa = reinterpret_cast<double *>(slot(i, L.pts2));
-                hp2[i].absmax_bits = nullptr;
-            }
-        }
+    } else { // (the fundamental matrix: resident groups returned above, every other kind took the merged tail)
+        uint32_t nt = 0;
+        for (uint32_t i = 0; i < count; ++i)
+            if (!(*pit[i]).fallback && !(*pit[i]).deferred && (*pit[i]).st->num_inliers > min_inl)
+                nt++;
         if (nt) {
             HIP_TRY(gc.h_tasks.ensure(sizeof(LMTask) * nt));
             LMTask *ht = gc.h_tasks.as<LMTask>();
-            if (kind == EST_ABS) {
-                HIP_TRY(hipMemcpyAsync(gc.args.p, hp2, sizeof(PrepareGroupArgs) * count, hipMemcpyHostToDevice, c->stream));
-                HIP_TRY(launch_group_prepare(gc.args.as<PrepareGroupArgs>(), count, max_n, c->stream));
-            }
-            uint32_t next_plain = 0, next_cam = nt - ncam;
+            uint32_t next = 0;
             for (uint32_t i = 0; i < count; ++i) {
                 GroupItem &g = (*pit[i]);
                 if (g.fallback || g.deferred || !(g.st->num_inliers > min_inl))
                     continue;
-                g.job0 = g.cam_flags ? next_cam++ : next_plain++;
-                LMTask &T = ht[g.job0];
-                std::memset(&T, 0, sizeof(T));
-                T.pts = g.prob.ps;
-                lm_params_from_record(kind, g.rec, T.params);
-                if (kind == EST_ABS) {
-                    double *soa2 = reinterpret_cast<double *>(slot(i, L.pts2));
-                    for (int d = 0; d < nd; ++d)
-                        T.pts.a[d] = soa2 + (size_t)d * g.n;
-                    pl_bundle_options b = g.item->opt->bundle;
-                    b.loss_scale = g.item->opt->bundle.loss_scale * g.scale;
-                    CameraParams cs = g.cam1;
-                    camera_rescale(cs, g.scale);
-                    T.opt = to_lm(b);
-                    T.cam = cs;
-                    T.cam_flags = g.cam_flags;
-                    T.point_scale = g.scale;
-                } else {
-                    T.opt = to_lm(g.scaled.bundle);
-                    std::memset(&T.cam, 0, sizeof(T.cam));
-                    T.cam.model_id = CAM_NULL;
-                    T.point_scale = 1.0;
-                }
-                T.prefilter_thr2 = 0.0;
-                T.mask = reinterpret_cast<uint8_t *>(slot(i, L.mask));
-                T.scratch = nullptr;
-                T.record_in = nullptr;
-                T.record_out = nullptr;
+                g.job0 = next++;
+                fill_bundle_task(i, g, ht[g.job0]);
+                lm_params_from_record(kind, g.rec, ht[g.job0].params);
             }
-            HIP_TRY(launch_lm_tasks(kind, gc.h_tasks.dev<LMTask>(), nt - ncam, max_n, c->stream));
-            HIP_TRY(launch_lm_cam(gc.h_tasks.dev<LMTask>() + (nt - ncam), ncam, c->stream));
+            HIP_TRY(launch_lm_tasks(kind, gc.h_tasks.dev<LMTask>(), nt, max_n, c->stream));
             HIP_TRY(wait_stream(c));
             for (uint32_t i = 0; i < count; ++i) {
                 GroupItem &g = (*pit[i]);
                 if (g.fallback || g.deferred || !(g.st->num_inliers > min_inl))
                     continue;
                 record_from_lm_params(kind, ht[g.job0].params, g.rec); // (final_refine: skipped never happens without a pre-filter)
-                if (g.cam_flags)
-                    g.cam_refined = ht[g.job0].cam;
             }
         }
     }
-    {
-        // results in the user's representation
-        for (uint32_t i = 0; i < count; ++i) {
-            GroupItem &g = (*pit[i]);
-            if (g.fallback || g.deferred)
-                continue;
-            pl_batch_item &it = *g.item;
-            if (kind == EST_ABS || kind == EST_REL) {
-                pose_from_record(g.rec, static_cast<pl_camera_pose *>(it.model));
-                if (kind == EST_ABS && g.st->num_inliers > min_inl) {
-                    // camera.rescale(scale) ... rescale(1 / scale) round trip of the reference (robust.cc:119-121)
-                    CameraParams back = g.cam1;
-                    camera_rescale(back, g.scale);
-                    if (g.cam_flags)
-                        back = g.cam_refined; // (the rescaled camera, intrinsics moved by the bundle)
-                    camera_rescale(back, 1.0 / g.scale);
-                    for (int k = 0; k < it.camera1->num_params && k < 12; ++k)
-                        it.camera1->params[k] = back.p[k];
-                }
-            } else {
-                Mat3 M;
-                for (int k = 0; k < 9; ++k)
-                    M.m[k] = g.rec[kMatOff + k];
-                if (kind == EST_FUND)
-                    M = mul(mul(transpose3(g.T2), M), g.T1); // robust.cc:590-591
-                else
-                    M = mul(mul(inverse3(g.T2), M), g.T1); // robust.cc:753-754
-                normalize_frobenius(M);
-                mat_to_colmajor(M, static_cast<double *>(it.model));
-            }
-            it.status = PL_OK;
-        }
+    // results in the user's representation
+    for (uint32_t i = 0; i < count; ++i) {
+        GroupItem &g = (*pit[i]);
+        if (g.fallback || g.deferred)
+            continue;
+        pl_batch_item &it = *g.item;
+        const bool bundled = g.st->num_inliers > min_inl;
+        front_finish(g.fe, g.rec, &g.cam_refined, it.model, kind == EST_ABS && bundled ? it.camera1 : nullptr);
+        it.status = PL_OK;
     }
     (void)t_group;
     return PL_OK;

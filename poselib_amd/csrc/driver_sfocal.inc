@@ -190,17 +190,7 @@ int run_shared_focal(Context *c, const pl_problem *p, const pl_robust_options *o
     const double t_start = now_s();
     std::memset(st, 0, sizeof(*st));
     const uint32_t n = p->n;
-    FocalLoopOptions lo;
-    lo.max_iterations = o->ransac.max_iterations;
-    lo.min_iterations = o->ransac.min_iterations;
-    lo.seed = o->ransac.seed;
-    lo.dyn_num_trials_mult = o->ransac.dyn_num_trials_mult;
-    lo.success_prob = o->ransac.success_prob;
-    lo.score_initial_model = o->ransac.score_initial_model != 0;
-    lo.max_error = o->max_error;
-    lo.progressive_sampling = o->ransac.progressive_sampling != 0; // sampling.cc:85-136, host-drawn (absolute_pose.h:80 / relative_pose.h:155: sampler(num_data, sample_sz, opt.ransac))
-    lo.max_prosac_iterations = o->ransac.max_prosac_iterations;
-    lo.max_focal = -1.0;
+    const FocalLoopOptions lo = focal_loop_options(*o, -1.0);
     DeviceSFocalBackend be{c, p, o->ransac.seed, o->max_error * o->max_error, lo_options(o->max_error)};
     FocalModel best;
     std::memset(&best, 0, sizeof(best));
@@ -218,13 +208,7 @@ int run_shared_focal(Context *c, const pl_problem *p, const pl_robust_options *o
     int rc = focal_lo_ransac_t<SharedFocalTraits>(be, n, lo, &best, &fs);
     if (rc != PL_OK)
         return rc;
-    st->refinements = fs.refinements;
-    st->iterations = fs.iterations;
-    st->num_inliers = fs.num_inliers;
-    st->inlier_ratio = fs.inlier_ratio;
-    st->model_score = fs.model_score;
-    st->hypotheses = fs.hypotheses;
-    st->iterations_evaluated = fs.iterations_evaluated;
+    stats_from_focal_loop(fs, st);
     for (int i = 0; i < 4; ++i)
         pose->q[i] = best.q[i];
     for (int i = 0; i < 3; ++i)
