@@ -301,9 +301,13 @@ int pl_score_model(pl_problem *p, const void *model, double max_error, uint64_t 
  * models and correspondences here to check that a filter never drops an inlier. */
 int pl_debug_score_stream(pl_problem *p, const void *models, size_t n, double max_error, uint32_t *counts,
                           double *scores, int32_t *path_used);
-/* Diagnostic entry: the scalar math of the device kernels, element-wise on `n` doubles - fn 0: the cube of the LM's
- * Nielsen update (optim/lm_impl.h:124 std::pow(., 3)), 1: sqrt, 2: reciprocal, 3 .. 6: cbrt / cos / sin / acos of
- * pl_libm.h.  tests/ compares them with the host's libm bit for bit. */
+/* Diagnostic entry: the scalar math of the device kernels, element-wise on `n` doubles (n <= 2^28) - fn 0: the cube of
+ * the LM's Nielsen update (optim/lm_impl.h:124 std::pow(., 3)), 1: sqrt, 2: reciprocal, 3 .. 6: cbrt / cos / sin / acos
+ * of pl_libm.h, 7 / 8: sine / cosine of pl_sincos (the quaternion exponential of the LM steps), 9: pf_half_rn((float)x),
+ * 10: pf_half_to_float((uint16_t)x), 11: pf_half_up((float)x) - the fp16 operand conversions of the matrix-core
+ * pre-filters, fp16 bit patterns passed and returned as their integer value.  Any other fn: PL_ERR_INVALID.
+ * cos and sincos follow glibc for |x| < 105414350, sin for |x| < 2.426265 (pl_libm.h); beyond, they return the device
+ * library's values.  tests/ compares every code with the host's libm / IEEE arithmetic bit for bit. */
 int pl_debug_device_math(int fn, const double *x, size_t n, double *out);
 /* Non-linear refinement of one model on the resident correspondences (robust/bundle.h:41-170:
  * bundle_adjust / refine_relpose / refine_fundamental / refine_homography).  camera: absolute pose only

@@ -404,7 +404,9 @@ class RansacBatch:
 
 def device_math(fn: int, x):
     """Diagnostic (pl_debug_device_math): the device kernels' scalar math on an array - 0: cube of the LM's Nielsen update,
-    1: sqrt, 2: reciprocal, 3: cbrt, 4: cos, 5: sin, 6: acos."""
+    1: sqrt, 2: reciprocal, 3: cbrt, 4: cos, 5: sin, 6: acos, 7: sine of sincos, 8: cosine of sincos, 9: fp16 bits of
+    float32(x) rounded to nearest, 10: float32 value of the fp16 bits x, 11: fp16 bits of the smallest fp16 >= float32(x).
+    fp16 bit patterns go in and come out as integer-valued doubles.  An unknown code raises PoseLibAmdError."""
     x = np.ascontiguousarray(x, dtype=np.float64)
     out = np.zeros_like(x)
     L.check(L.lib().pl_debug_device_math(int(fn), _ptr(x), C.c_size_t(x.size), _ptr(out)))

@@ -2373,6 +2373,8 @@ int pl_debug_score_stream(pl_problem *p, const void *models, size_t n, double ma
 }
 
 int pl_debug_device_math(int fn, const double *x, size_t n, double *out) {
+    if (fn < 0 || fn >= kDeviceMathFns)
+        return fail(PL_ERR_INVALID, "unknown device math function");
     if ((!x || !out) && n)
         return fail(PL_ERR_INVALID, "null pointer");
     if (n > (1u << 28))

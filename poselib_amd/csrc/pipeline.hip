@@ -926,13 +926,14 @@ __global__ __launch_bounds__(256) void k_undistort(const double *__restrict__ in
     out[2 * (size_t)i] = fx * u + cx;
     out[2 * (size_t)i + 1] = fy * v + cy;
 }
-// Diagnostic: the device's scalar math as the kernels call it, element-wise (pl_debug_device_math)
+// Diagnostic: the device's scalar math as the kernels call it, element-wise (pl_debug_device_math; the driver rejects
+// codes outside 0 .. kDeviceMathFns - 1 before the launch)
 __global__ __launch_bounds__(256) void k_device_math(int fn, const double *__restrict__ x, uint32_t n, double *__restrict__ out) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n)
         return;
     const double v = x[i];
-    double r;
+    double r, sn, cs;
     switch (fn) {
     case 0: r = lm_cube(v); break; // the cube of the Nielsen update (pl_refine.h)
     case 1: r = sqrt(v); break;
@@ -941,6 +942,12 @@ __global__ __launch_bounds__(256) void k_device_math(int fn, const double *__res
     case 4: r = pl_cos(v); break;
     case 5: r = pl_sin(v); break;
     case 6: r = pl_acos(v); break;
+    case 7: pl_sincos(v, sn, cs); r = sn; break; // (quat_exp's pair, pl_math.h)
+    case 8: pl_sincos(v, sn, cs); r = cs; break;
+    // fp16 operand conversions of the matrix-core pre-filters (pl_prefilter.h): bit patterns travel as their integer value
+    case 9: r = (double)pf_half_rn((float)v); break;
+    case 10: r = (double)pf_half_to_float((uint16_t)v); break;
+    case 11: r = (double)pf_half_up((float)v); break;
     default: r = v; break;
     }
     out[i] = r;

@@ -162,7 +162,9 @@ struct PrepareArgs {
 hipError_t launch_prepare(const double *a_raw, const double *b_raw, uint32_t n, const PrepareArgs &args, double *soa,
                           unsigned long long *absmax_bits, hipStream_t stream);
 // pixels of a distorting camera -> pixels of the distortion-free camera with the same focal lengths / principal point
-// diagnostic: fn 0 cube of the LM's Nielsen update, 1 sqrt, 2 reciprocal, 3 cbrt, 4 cos, 5 sin, 6 acos - as the kernels evaluate them
+// diagnostic: fn 0 cube of the LM's Nielsen update, 1 sqrt, 2 reciprocal, 3 cbrt, 4 cos, 5 sin, 6 acos, 7 / 8 sin / cos of
+// sincos, 9 fp16 round-to-nearest bits, 10 fp16 bits -> float, 11 fp16 round-up bits - as the kernels evaluate them
+constexpr int kDeviceMathFns = 12;
 hipError_t launch_device_math(int fn, const double *x, uint32_t n, double *out, hipStream_t stream);
 hipError_t launch_undistort(const double *in, uint32_t n, const CameraParams &cam, double fx, double fy, double cx,
                             double cy, double *out, hipStream_t stream);

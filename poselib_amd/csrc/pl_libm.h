@@ -99,7 +99,10 @@ template <bool FMA = true> PL_HD double do_sin(double x, double dx) {
 }
 } // namespace libm_detail
 
-// |x| < 105414350 (beyond that glibc switches to another reduction; the solvers' arguments are below 4.2)
+// Domain of pl_cos / pl_sin / pl_sincos - a contract, checked on the device by tests/test_gpu_device_math.py: glibc's bits
+// for |x| < 105414350 (cos, sincos) and |x| < 2.426265 (sin).  Beyond it glibc switches to another reduction that is not
+// restated here: the device library's cos / sin answer instead (finite for finite x, not glibc's last bit).  The kernels stay
+// inside: the cubic solvers' cos arguments lie in [-4.2, 1.1], quat_exp's sincos argument is half an LM rotation step.
 PL_HD double pl_cos(double x) {
     using namespace libm_detail;
     const uint32_t k = pl_hi(x) & 0x7fffffffu;
@@ -131,10 +134,10 @@ PL_HD double pl_cos(double x) {
         const double r = (n & 1) ? do_cos(b, db) : do_sin(b, db);
         return (n & 2) ? -r : r;
     }
-    return cos(x); // not reached by the solvers
+    return cos(x); // outside the domain (not reached by the solvers)
 }
 
-// sin for the arguments quat_exp produces (|x| < 2.426265; s_sin.c __sin)
+// s_sin.c __sin on the domain |x| < 2.426265 (above)
 PL_HD double pl_sin(double x) {
     using namespace libm_detail;
     const uint32_t k = pl_hi(x) & 0x7fffffffu;
@@ -146,7 +149,7 @@ PL_HD double pl_sin(double x) {
         const double t = kHp0 - fabs(x);
         return copysign(do_cos(t, kHp1), x);
     }
-    return sin(x); // not reached
+    return sin(x); // outside the domain
 }
 
 // sin and cos of the SAME argument: s_sincos.c __sincos, the sse2 build (libm exports one `sincos`, without an FMA variant).
@@ -198,7 +201,7 @@ PL_HD void pl_sincos(double x, double &sn, double &cs) {
         cs = pick(n + 1);
         return;
     }
-    sn = sin(x); // (rotation increments of an LM step never get here)
+    sn = sin(x); // outside the domain (rotation increments of an LM step never get here)
     cs = cos(x);
 }
 

@@ -313,14 +313,24 @@ template <int K, class Store> PL_HD void terms1(const Loss &loss, double r, cons
 // device therefore forms the (nearly) correctly rounded cube itself: x^2 = hi + lo and hi x = p + e exactly (FMA residuals), then
 // one rounding of p + (e + lo x).  The value only matters for mediocre steps (factor = 1 - cube > 1/3, i.e. rho < 0.94).
 // (the FMA form is a plain function so that the host test build can compare it with glibc's pow: tests/test_libm_vs_glibc.py)
-PL_HD double lm_cube_fma(double x) {
-    if (!(fabs(x) < 1e100) || fabs(x) < 1e-100)
-        return x * x * x; // inf / NaN / overflow / underflow: as pow
+PL_HD double lm_cube_two_product(double x) { // 2^-330 <= |x| <= 2^330: no residual overflows or underflows
     const double hi = x * x;
     const double lo = __builtin_fma(x, x, -hi);
     const double p = hi * x;
     const double e = __builtin_fma(hi, x, -p);
     return p + (e + lo * x); // (lo x and the inner sum round once each: NEARLY correctly rounded, see above)
+}
+PL_HD double lm_cube_fma(double x) {
+    const double ax = fabs(x);
+    if (ax >= 0x1p-330 && ax <= 0x1p330)
+        return lm_cube_two_product(x);
+    // beyond: the same form on x scaled by a power of two (exact), the cube scaled back - exact, or rounded once more into
+    // the subnormal range (within one ulp, where x * x * x can be 1.5 ulp off)
+    if (ax > 0x1p330 && ax < 0x1p342)
+        return lm_cube_two_product(x * 0x1p-30) * 0x1p90;
+    if (ax >= 0x1p-360 && ax < 0x1p-330)
+        return lm_cube_two_product(x * 0x1p60) * 0x1p-180;
+    return x * x * x; // 0, inf, NaN, cubes beyond the range (+-inf) or below half the smallest subnormal (+-0)
 }
 PL_HD double lm_cube(double x) {
 #if defined(__HIP_DEVICE_COMPILE__)

@@ -652,29 +652,139 @@ int hm_sfocal_lm(const double *const *pa, uint32_t n, double *pose7, double *foc
 
 void hm_factorized_F(const double *params, double *F) { factorized_F(params, F); }
 
-// pl_libm.h against the host's libm (glibc): number of arguments on which pl_cbrt and cbrt differ in any bit.
-// mode 0: any bit pattern; 1: uniform in [-10, 10]; 2: log-uniform magnitudes 2^-60..2^60, both signs; 3: subnormals
-uint64_t hm_cbrt_mismatches(uint64_t count, uint64_t seed, int mode, double *first_bad) {
-    uint64_t s = seed * 0x9E3779B97F4A7C15ull + 88172645463325252ull, bad = 0;
-    auto rnd = [&]() {
+// The argument streams of the libm tests.  tests/test_libm_vs_glibc.py walks them here against the host's libm;
+// tests/test_gpu_device_math.py reads the same arguments through hm_math_args and sends them to the device.
+namespace {
+enum { GEN_CBRT = 0, GEN_ACOS = 1, GEN_COS = 2, GEN_SIN = 3, GEN_SINCOS = 4 };
+struct ArgStream {
+    int which, mode; // mode: cbrt only - 0 any bit pattern; 1 uniform in [-10, 10]; 2 log-uniform magnitudes 2^-60..2^60,
+                     // both signs; 3 subnormals
+    uint64_t s, i = 0;
+    ArgStream(int which_, int mode_, uint64_t seed) : which(which_), mode(mode_), s(seed * 0x9E3779B97F4A7C15ull + 88172645463325252ull) {}
+    uint64_t rnd() {
         s ^= s << 13, s ^= s >> 7, s ^= s << 17;
         return s;
-    };
-    for (uint64_t i = 0; i < count; ++i) {
-        const uint64_t r = rnd();
+    }
+    double next() {
+        static const uint64_t edges[] = {0x3fc00000, 0x3fd00000, 0x3fe00000, 0x3fe80000, 0x3fed8000, 0x3fee8000, 0x3fef0000, 0x3ff00000};
         double x;
-        if (mode == 0) {
-            std::memcpy(&x, &r, 8);
-        } else if (mode == 1) {
-            x = ((double)(r >> 11) / 9007199254740992.0 - 0.5) * 20.0;
-        } else if (mode == 2) {
-            x = std::ldexp((double)(r >> 11) / 9007199254740992.0 + 0.5, (int)(rnd() % 121) - 60);
-            if (r & 1)
-                x = -x;
+        if (which == GEN_CBRT) {
+            const uint64_t r = rnd();
+            if (mode == 0) {
+                std::memcpy(&x, &r, 8);
+            } else if (mode == 1) {
+                x = ((double)(r >> 11) / 9007199254740992.0 - 0.5) * 20.0;
+            } else if (mode == 2) {
+                x = std::ldexp((double)(r >> 11) / 9007199254740992.0 + 0.5, (int)(rnd() % 121) - 60);
+                if (r & 1)
+                    x = -x;
+            } else {
+                const uint64_t b = r & 0x800fffffffffffffull;
+                std::memcpy(&x, &b, 8);
+            }
+        } else if (which == GEN_SINCOS) { // [-6, 6], [0, 0.9], [-2.4, 2.4] and down to 2^-40
+            const double u = (double)(rnd() >> 11) / 9007199254740992.0;
+            x = (i % 4 == 0) ? (u * 12 - 6) : (i % 4 == 1) ? u * 0.9 : (i % 4 == 2) ? (u * 4.8 - 2.4) : std::ldexp(2 * u - 1, -(int)((s >> 3) % 40));
         } else {
-            const uint64_t b = r & 0x800fffffffffffffull;
-            std::memcpy(&x, &b, 8);
+            const double u = (double)(rnd() >> 11) / 9007199254740992.0;
+            if (which == GEN_ACOS) { // (-1, 1) incl. the neighbourhoods of +-1 and 0 and the interval edges of the piecewise expansion
+                switch (i % 5) {
+                case 0:
+                    x = 2 * u - 1;
+                    break;
+                case 1:
+                    x = (u < 0.5 ? -1 : 1) * (1 - std::ldexp(u, -(int)(rnd() % 40)));
+                    break;
+                case 2:
+                    x = std::ldexp(2 * u - 1, -(int)(rnd() % 60));
+                    break;
+                case 3:
+                    x = (0.96875 + u * 0.03125) * ((rnd() & 1) ? 1 : -1);
+                    break;
+                default: {
+                    uint64_t b = edges[rnd() % 8] << 32;
+                    b += (int64_t)(rnd() % 2000) - 1000;
+                    std::memcpy(&x, &b, 8);
+                    if (rnd() & 1)
+                        x = -x;
+                }
+                }
+            } else if (which == GEN_COS) { // [-6, 6], [0, 1.0472] and tiny arguments
+                x = (i % 3 == 0) ? (u * 12 - 6) : (i % 3 == 1) ? u * 1.0472 : std::ldexp(2 * u - 1, -(int)(rnd() % 40));
+            } else { // sin: [-2.4, 2.4], [0, 0.5] and tiny arguments
+                x = (i % 3 == 0) ? (u * 4.8 - 2.4) : (i % 3 == 1) ? u * 0.5 : std::ldexp(2 * u - 1, -(int)(rnd() % 40));
+            }
         }
+        ++i;
+        return x;
+    }
+};
+
+// The host's libm, one function per loop and per (non-inlined) function: at -O1 and above GCC merges sin and cos of the same
+// argument into one sincos() call, whose last bit differs (pl_libm.h pl_sincos).
+__attribute__((noinline)) void glibc_cbrt(const double *x, uint64_t n, double *out) {
+    for (uint64_t i = 0; i < n; ++i)
+        out[i] = std::cbrt(x[i]);
+}
+__attribute__((noinline)) void glibc_acos(const double *x, uint64_t n, double *out) {
+    for (uint64_t i = 0; i < n; ++i)
+        out[i] = std::acos(x[i]);
+}
+__attribute__((noinline)) void glibc_cos(const double *x, uint64_t n, double *out) {
+    for (uint64_t i = 0; i < n; ++i)
+        out[i] = std::cos(x[i]);
+}
+__attribute__((noinline)) void glibc_sin(const double *x, uint64_t n, double *out) {
+    for (uint64_t i = 0; i < n; ++i)
+        out[i] = std::sin(x[i]);
+}
+__attribute__((noinline)) void glibc_sincos(const double *x, uint64_t n, double *sn, double *cs) {
+    for (uint64_t i = 0; i < n; ++i)
+        sincos(x[i], &sn[i], &cs[i]);
+}
+__attribute__((noinline)) void glibc_pow3(const double *x, uint64_t n, double *out) {
+    volatile double three = 3.0; // (a literal exponent would let the compiler expand the call)
+    for (uint64_t i = 0; i < n; ++i)
+        out[i] = std::pow(x[i], (double)three);
+}
+} // namespace
+
+// `count` arguments of stream `which` (GEN_*), written to out
+void hm_math_args(int which, int mode, uint64_t seed, uint64_t count, double *out) {
+    ArgStream g(which, mode, seed);
+    for (uint64_t i = 0; i < count; ++i)
+        out[i] = g.next();
+}
+
+// glibc on n arguments: which = GEN_CBRT .. GEN_SIN as above, GEN_SINCOS (out[0, n): sine, out[n, 2n): cosine), 5: pow(x, 3)
+void hm_glibc(int which, const double *x, uint64_t n, double *out) {
+    switch (which) {
+    case GEN_CBRT:
+        glibc_cbrt(x, n, out);
+        break;
+    case GEN_ACOS:
+        glibc_acos(x, n, out);
+        break;
+    case GEN_COS:
+        glibc_cos(x, n, out);
+        break;
+    case GEN_SIN:
+        glibc_sin(x, n, out);
+        break;
+    case GEN_SINCOS:
+        glibc_sincos(x, n, out, out + n);
+        break;
+    default:
+        glibc_pow3(x, n, out);
+    }
+}
+
+// pl_libm.h against the host's libm (glibc): number of arguments on which pl_cbrt and cbrt differ in any bit (modes: ArgStream)
+uint64_t hm_cbrt_mismatches(uint64_t count, uint64_t seed, int mode, double *first_bad) {
+    ArgStream g(GEN_CBRT, mode, seed);
+    uint64_t bad = 0;
+    for (uint64_t i = 0; i < count; ++i) {
+        const double x = g.next();
         const double mine = pl_cbrt(x), host = std::cbrt(x);
         if (std::memcmp(&mine, &host, 8) != 0 && !(mine != mine && host != host)) {
             if (!bad && first_bad)
@@ -687,13 +797,12 @@ uint64_t hm_cbrt_mismatches(uint64_t count, uint64_t seed, int mode, double *fir
 double hm_cbrt(double x) { return pl_cbrt(x); }
 double hm_sin(double x) { return pl_sin(x); }
 double hm_cos(double x) { return pl_cos(x); }
-// pl_sincos against the host's sincos(): number of arguments (three ranges) on which either result differs in any bit
+// pl_sincos against the host's sincos(): number of arguments (GEN_SINCOS) on which either result differs in any bit
 uint64_t hm_sincos_mismatches(uint64_t count, uint64_t seed, double *first_bad) {
-    uint64_t s = seed * 0x9E3779B97F4A7C15ull + 88172645463325252ull, bad = 0;
+    ArgStream g(GEN_SINCOS, 0, seed);
+    uint64_t bad = 0;
     for (uint64_t i = 0; i < count; ++i) {
-        s ^= s << 13, s ^= s >> 7, s ^= s << 17;
-        const double u = (double)(s >> 11) / 9007199254740992.0;
-        const double x = (i % 4 == 0) ? (u * 12 - 6) : (i % 4 == 1) ? u * 0.9 : (i % 4 == 2) ? (u * 4.8 - 2.4) : std::ldexp(2 * u - 1, -(int)((s >> 3) % 40));
+        const double x = g.next();
         double a, b, c, d;
         pl_sincos(x, a, b);
         sincos(x, &c, &d);
@@ -706,48 +815,19 @@ uint64_t hm_sincos_mismatches(uint64_t count, uint64_t seed, double *first_bad) 
     return bad;
 }
 
-// which: 0 acos on (-1, 1) incl. the interval edges of its piecewise expansion, 1 cos on [-6, 6] and tiny arguments,
-// 2 sin on [-2.4, 2.4] and tiny arguments: arguments on which pl_libm.h and the host's libm differ in any bit
+// which: 0 acos (GEN_ACOS), 1 cos (GEN_COS), 2 sin (GEN_SIN): arguments on which pl_libm.h and the host's libm differ in any bit
 uint64_t hm_libm_mismatches(int which, uint64_t count, uint64_t seed, double *first_bad) {
-    uint64_t s = seed * 0x9E3779B97F4A7C15ull + 88172645463325252ull, bad = 0;
-    auto rnd = [&]() {
-        s ^= s << 13, s ^= s >> 7, s ^= s << 17;
-        return s;
-    };
-    static const uint64_t edges[] = {0x3fc00000, 0x3fd00000, 0x3fe00000, 0x3fe80000, 0x3fed8000, 0x3fee8000, 0x3fef0000, 0x3ff00000};
+    ArgStream g(GEN_ACOS + which, 0, seed);
+    uint64_t bad = 0;
     for (uint64_t i = 0; i < count; ++i) {
-        const double u = (double)(rnd() >> 11) / 9007199254740992.0;
-        double x, mine, host;
-        if (which == 0) {
-            switch (i % 5) {
-            case 0:
-                x = 2 * u - 1;
-                break;
-            case 1:
-                x = (u < 0.5 ? -1 : 1) * (1 - std::ldexp(u, -(int)(rnd() % 40)));
-                break;
-            case 2:
-                x = std::ldexp(2 * u - 1, -(int)(rnd() % 60));
-                break;
-            case 3:
-                x = (0.96875 + u * 0.03125) * ((rnd() & 1) ? 1 : -1);
-                break;
-            default: {
-                uint64_t b = edges[rnd() % 8] << 32;
-                b += (int64_t)(rnd() % 2000) - 1000;
-                std::memcpy(&x, &b, 8);
-                if (rnd() & 1)
-                    x = -x;
-            }
-            }
+        const double x = g.next();
+        double mine, host;
+        if (which == 0)
             mine = pl_acos(x), host = std::acos(x);
-        } else if (which == 1) {
-            x = (i % 3 == 0) ? (u * 12 - 6) : (i % 3 == 1) ? u * 1.0472 : std::ldexp(2 * u - 1, -(int)(rnd() % 40));
+        else if (which == 1)
             mine = pl_cos(x), host = std::cos(x);
-        } else {
-            x = (i % 3 == 0) ? (u * 4.8 - 2.4) : (i % 3 == 1) ? u * 0.5 : std::ldexp(2 * u - 1, -(int)(rnd() % 40));
+        else
             mine = pl_sin(x), host = std::sin(x);
-        }
         if (std::memcmp(&mine, &host, 8) != 0 && !(mine != mine && host != host)) {
             if (!bad && first_bad)
                 *first_bad = x;

@@ -167,6 +167,32 @@ def half_rn(v):
     return bits, back
 
 
+GEN = {"cbrt": 0, "acos": 1, "cos": 2, "sin": 3, "sincos": 4}
+
+
+def math_args(which, count, seed, mode=0):
+    """the arguments of the libm tests' stream `which` (GEN; mode: the cbrt classes 0 .. 3), as test_libm_vs_glibc.py walks them"""
+    out = np.zeros(count)
+    lib().hm_math_args(GEN[which], int(mode), C.c_uint64(seed), C.c_uint64(count), _p(out))
+    return out
+
+
+def glibc(which, x):
+    """the host's libm on x: which = a GEN name or "pow3" (pow(x, 3)); "sincos" returns (sine, cosine)"""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    out = np.zeros(2 * x.size if which == "sincos" else x.size)
+    lib().hm_glibc(GEN.get(which, 5), _p(x), C.c_uint64(x.size), _p(out))
+    return (out[: x.size], out[x.size:]) if which == "sincos" else out
+
+
+def lm_cube(x):
+    """pl_refine.h lm_cube_fma, the device's form of the Nielsen update's cube"""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    out = np.zeros_like(x)
+    lib().hm_lm_cube(_p(x), C.c_uint64(x.size), _p(out))
+    return out
+
+
 def score(est, rec, cols, thr2):
     arrs, ptrs = _soa(cols)
     n = arrs[0].shape[0]

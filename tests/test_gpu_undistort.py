@@ -58,3 +58,64 @@ def test_undistort_rejects_what_it_does_not_cover(gpu):
     p = np.array([[500.0, 505.0], [10.0, 990.0]])
     sp = {"model": "SIMPLE_PINHOLE", "params": [800.0, 400.0, 300.0]}
     assert np.abs(P.undistort_points(sp, p) - p).max() < 1e-12  # a linear camera maps onto itself
+
+
+UNDISTORT_CAMERAS = [
+    {"model": "OPENCV", "width": 1280, "height": 720, "params": [800.0, 820.0, 640.0, 360.0, -0.3, 0.01, 1e-3, -2e-3]},
+    {"model": "OPENCV", "width": 1280, "height": 720, "params": [800.0, 780.0, 640.0, 360.0, 0.3, -0.05, -1.5e-3, 1e-3]},
+    {"model": "PINHOLE", "width": 1280, "height": 720, "params": [900.0, 600.0, 640.5, 360.25]},
+]
+
+
+def _hostile_pixels(cam):
+    """the principal point, the image's corners at 1x and 3x its size, 1e6 px, NaN / inf, and a grid out to 3.5x the
+    image size - beyond the fold of a strong distortion, where the Newton inverse runs all 100 iterations or diverges"""
+    w, h = cam["width"], cam["height"]
+    cx, cy = cam["params"][2:4]
+    pts = [(cx, cy)]
+    for s in (1.0, 3.0):
+        for a in (-0.5, 0.5):
+            for b in (-0.5, 0.5):
+                pts.append((cx + s * a * w, cy + s * b * h))
+    for a in (-1e6, 0.0, 1e6):
+        for b in (-1e6, 0.0, 1e6):
+            pts.append((cx + a, cy + b))
+    for bad in (np.nan, np.inf, -np.inf):
+        pts += [(bad, cy), (cx, bad), (bad, bad), (bad, 1e6)]
+    gx, gy = np.meshgrid(np.linspace(cx - 3.5 * w, cx + 3.5 * w, 301), np.linspace(cy - 3.5 * h, cy + 3.5 * h, 301))
+    return np.r_[np.array(pts, dtype=np.float64), np.c_[gx.ravel(), gy.ravel()]]
+
+
+def _same_bits(a, b):
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    return (a.view(np.uint64) == b.view(np.uint64)) | (np.isnan(a) & np.isnan(b))
+
+
+@pytest.mark.parametrize("ci", range(len(UNDISTORT_CAMERAS)))
+def test_undistort_hostile_pixels_bit_for_bit(gpu, ci):
+    """pl_undistort_points against the oracle's Camera::unproject and the host compile of camera_unproject (pl_refine.h)
+    on pixels far outside the image, where the iterative inverse does not converge, and on NaN / inf: every bit equal, a
+    NaN equal to a NaN"""
+    import hostmath_lib as HM
+
+    cam = UNDISTORT_CAMERAS[ci]
+    pix = _hostile_pixels(cam)
+    got = gpu.undistort_points(cam, pix)
+    fx, fy, cx, cy = cam["params"][:4]
+    with np.errstate(invalid="ignore", over="ignore"):
+        ref = _pinhole_pixels(cam, O.unproject(cam, pix))
+        mid = {"PINHOLE": 1, "OPENCV": 4}[cam["model"]]
+        hm = HM.unproject(HM.camera_params(mid, cam["params"]), pix)
+        hm = np.c_[fx * hm[:, 0] + cx, fy * hm[:, 1] + cy]
+    for name, want in (("oracle", ref), ("host compile", hm)):
+        same = _same_bits(got, want).all(axis=1)
+        i = int(np.argmin(same))
+        assert same.all(), (name, int((~same).sum()), pix[i].tolist(), got[i].tolist(), want[i].tolist())
+    assert np.isnan(got[~np.isfinite(pix).all(axis=1)]).any()
+    if cam["model"] == "OPENCV":
+        # the set holds pixels whose inverse did not converge: pushed through the distortion again they miss the input
+        with np.errstate(invalid="ignore", over="ignore"):
+            back = synth.opencv_distort_pixels(got, cam["params"])
+            miss = ~(np.abs(back - pix) < 1e-6).all(axis=1) & np.isfinite(pix).all(axis=1)
+        print(cam["params"][4:], "pixels without a converged inverse:", int(miss.sum()), "of", pix.shape[0])
+        assert miss.sum() > 1000
