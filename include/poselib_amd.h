@@ -104,7 +104,9 @@ typedef struct {
                                       P3P emits them for inconsistent samples; they have no inliers, utils.cc:36-65) */
 } pl_ransac_stats;
 
-/* misc/camera_models.h:56-60; supported ids: -1 NULL, 0 SIMPLE_PINHOLE, 1 PINHOLE, 4 OPENCV */
+/* misc/camera_models.h:56-60; supported ids: -1 NULL, 0 SIMPLE_PINHOLE {f cx cy}, 1 PINHOLE {fx fy cx cy},
+ * 2 SIMPLE_RADIAL {f cx cy k1}, 3 RADIAL {f cx cy k1 k2}, 4 OPENCV {fx fy cx cy k1 k2 p1 p2}; num_params at least the model's
+ * count.  Every other id (fisheye, FOV, division, FULL_OPENCV, thin-prism models) and a short num_params: PL_ERR_UNSUPPORTED */
 typedef struct {
     int32_t model_id, width, height, num_params;
     double params[12];
@@ -162,8 +164,10 @@ int pl_estimate_homography(const double *points2D_1, const double *points2D_2, s
 
 /* ---- un-distortion as a stage of its own (BASELINE config 3: pixels of an OPENCV camera in front of the homography /
  * 7-point estimators, which take no camera).  Every point goes through Camera::unproject (misc/camera_models.h:98-102;
- * OPENCV: the iterative inverse of misc/camera_models.cc:972-990) and comes back as the pixel of the distortion-free
- * camera with the same focal lengths and principal point: out = (fx u + cx, fy v + cy).  points2D, out: N x 2. ---- */
+ * OPENCV: the iterative inverse of misc/camera_models.cc:972-990; SIMPLE_RADIAL / RADIAL: the Newton inverse of the radial
+ * polynomial :579-611) and comes back as the pixel of the distortion-free
+ * camera with the same focal lengths and principal point: out = (fx u + cx, fy v + cy).  points2D, out: N x 2.
+ * camera: any supported model but NULL. ---- */
 int pl_undistort_points(const pl_camera *camera, const double *points2D, size_t n, double *out);
 
 /* ---- batched front-end: an array of independent problems (BASELINE config 4: many image pairs) ----
@@ -176,7 +180,7 @@ typedef struct {
                               * unknown focal length (pl_estimate_shared_focal_relative_pose).  Kind-4 items and kind-0 items with
                               * estimate_focal_length advance in lock-step groups of their own since round 5 (one launch sequence per
                               * group, every item bit-identical to its single call).  Kinds 0 - 3 with PROSAC, a warm start
-                              * (ransac.score_initial_model) or an OPENCV camera are group members like any other since round 6;
+                              * (ransac.score_initial_model) or a distorting camera (SIMPLE_RADIAL, RADIAL, OPENCV) are group members like any other since round 6;
                               * what still runs one at a time: min_iterations > 4096, fewer correspondences than sample size + 4,
                               * more than 16384, warm starts of the focal-length kinds (pl_last_batch_report counts them) */
     int32_t status;          /* out: PL_OK or the error of this item */
@@ -311,14 +315,17 @@ int pl_debug_score_stream(pl_problem *p, const void *models, size_t n, double ma
 int pl_debug_device_math(int fn, const double *x, size_t n, double *out);
 /* Non-linear refinement of one model on the resident correspondences (robust/bundle.h:41-170:
  * bundle_adjust / refine_relpose / refine_fundamental / refine_homography).  camera: absolute pose only
- * (NULL pointer = identity camera, i.e. normalised image points).  mask: optional N bytes, refine on the
+ * (NULL pointer = identity camera, i.e. normalised image points; otherwise any supported model, the points being its
+ * pixels).  mask: optional N bytes, refine on the
  * flagged correspondences only. */
 int pl_refine_model(pl_problem *p, const pl_bundle_options *opt, const pl_camera *camera, const uint8_t *mask,
                     void *model, uint32_t *lm_iterations);
 
 /* bundle_adjust(x, X, Image *image, BundleOptions) - the Image overload of robust/bundle.h:47-49 / bundle.cc:94-113 - on
  * an absolute-pose problem whose 2-D points are PIXELS: pose and, per opt->refine_focal_length / refine_principal_point /
- * refine_extra_params, the camera's intrinsics are refined together (robust/optim/absolute.h:49-171); both in / out. */
+ * refine_extra_params, the camera's intrinsics are refined together (robust/optim/absolute.h:49-171); both in / out.
+ * The flags select parameters in the reference's order (Camera::get_param_refinement_idx): focal, principal point, extra -
+ * SIMPLE_RADIAL {0}, {1, 2}, {3}; RADIAL {0}, {1, 2}, {3, 4}; OPENCV {0, 1}, {2, 3}, {4 .. 7}. */
 int pl_bundle_adjust_camera(pl_problem *p, const pl_bundle_options *opt, pl_camera *camera, const uint8_t *mask,
                             pl_camera_pose *pose, uint32_t *lm_iterations);
 

@@ -25,7 +25,7 @@ from . import _lib as L
 LAMBDA_UPDATES = {"NIELSEN": 0, "FIXED_FACTOR": 1}
 DAMPINGS = {"LEVENBERG": 0, "MARQUARDT": 1}
 LOSS_TYPES = {"TRIVIAL": 0, "TRUNCATED": 1, "HUBER": 2, "CAUCHY": 3, "TRUNCATED_CAUCHY": 4, "TRUNCATED_LE_ZACH": 5}
-CAMERA_MODEL_IDS = {"NULL": -1, "SIMPLE_PINHOLE": 0, "PINHOLE": 1, "OPENCV": 4}
+CAMERA_MODEL_IDS = {"NULL": -1, "SIMPLE_PINHOLE": 0, "PINHOLE": 1, "SIMPLE_RADIAL": 2, "RADIAL": 3, "OPENCV": 4}
 _CAMERA_NAMES = {v: k for k, v in CAMERA_MODEL_IDS.items()}
 KIND_ABS, KIND_REL, KIND_FUND, KIND_HOM = 0, 1, 2, 3
 KIND_SHARED_FOCAL = 4  # pl_batch_item only: estimate_shared_focal_relative_pose
@@ -75,7 +75,7 @@ class Camera:
     def focal(self):
         if not self.params:
             return 1.0
-        if self.model_id == 0:
+        if self.model_id in (0, 2, 3):
             return self.params[0]
         if self.model_id in (1, 4):
             return 0.5 * self.params[0] + 0.5 * self.params[1]

@@ -289,13 +289,16 @@ CameraParams to_cam(const pl_camera *c) {
 }
 bool camera_supported(const pl_camera *c) {
     return c->model_id == CAM_NULL || (c->model_id == CAM_SIMPLE_PINHOLE && c->num_params >= 3) ||
-           (c->model_id == CAM_PINHOLE && c->num_params >= 4) || (c->model_id == CAM_OPENCV && c->num_params >= 8);
+           (c->model_id == CAM_PINHOLE && c->num_params >= 4) || (c->model_id == CAM_SIMPLE_RADIAL && c->num_params >= 4) ||
+           (c->model_id == CAM_RADIAL && c->num_params >= 5) || (c->model_id == CAM_OPENCV && c->num_params >= 8);
 }
 double camera_focal(const pl_camera *c) { // misc/camera_models.cc:304-323
     if (c->num_params == 0)
         return 1.0;
     switch (c->model_id) {
     case CAM_SIMPLE_PINHOLE:
+    case CAM_SIMPLE_RADIAL:
+    case CAM_RADIAL:
         return 0.0 + c->params[0] / 1;
     case CAM_PINHOLE:
     case CAM_OPENCV:
@@ -305,7 +308,7 @@ double camera_focal(const pl_camera *c) { // misc/camera_models.cc:304-323
     }
 }
 void camera_set_focal(pl_camera *c, double f) { // misc/camera_models.cc:96-107 over the model's focal_idx
-    if (c->model_id == CAM_SIMPLE_PINHOLE && c->num_params >= 1) {
+    if ((c->model_id == CAM_SIMPLE_PINHOLE || camera_is_radial(c->model_id)) && c->num_params >= 1) {
         c->params[0] = f;
     } else if ((c->model_id == CAM_PINHOLE || c->model_id == CAM_OPENCV) && c->num_params >= 2) {
         c->params[0] = f;
@@ -315,7 +318,7 @@ void camera_set_focal(pl_camera *c, double f) { // misc/camera_models.cc:96-107 
 void camera_rescale(CameraParams &c, double s) { // misc/camera_models.cc:432-455
     if (c.num_params == 0)
         return;
-    if (c.model_id == CAM_SIMPLE_PINHOLE) {
+    if (c.model_id == CAM_SIMPLE_PINHOLE || camera_is_radial(c.model_id)) { // (the distortion parameters stay)
         c.p[0] *= s, c.p[1] *= s, c.p[2] *= s;
     } else if (c.model_id == CAM_PINHOLE || c.model_id == CAM_OPENCV) {
         for (int i = 0; i < 4; ++i)
@@ -1641,8 +1644,8 @@ void free_problem(pl_problem *p) {
 
 // The bound of max(|x|, |y|) of the prepared points that keeps the scorers' fp32 / fp16 pre-filters conservative (pl_prefilter.h).
 // Absolute pose through a linear camera and two-view problems from 1024 correspondences on (the matrix-core Sampson form; the O(N)
-// host pass is not worth it below) get it from the raw points on the host; absolute pose through OPENCV reads k_prepare's atomic
-// max back (the un-projection is iterative); smaller two-view problems get none (+inf).  make_problem_prepared and the groups'
+// host pass is not worth it below) get it from the raw points on the host; absolute pose through a non-linear camera (OPENCV,
+// SIMPLE_RADIAL, RADIAL: camera_is_nonlinear) reads k_prepare's atomic max back (the un-projection is iterative); smaller two-view problems get none (+inf).  make_problem_prepared and the groups'
 // stage A both decide it here.
 
 // upper bound of max(|x|, |y|) of the un-projected 2-D points of a linear camera (the un-projected coordinate is (px - c) / f up to
@@ -1664,7 +1667,7 @@ float host_xy_absmax(const CameraParams &cam, const double *a, size_t n) {
 }
 // Upper bound of the largest |coordinate| the prepared two-view points will have (pl_prefilter.h, fp16 Sampson form), from
 // the raw points on the host: linear cameras / the normalisation (x - c) / scale round at most once per operation.
-// +inf when it cannot be told without the device (OPENCV un-projection) or a coordinate is NaN.
+// +inf when it cannot be told without the device (a non-linear camera's un-projection) or a coordinate is NaN.
 float host_two_view_absmax(const PrepareArgs &pa, const double *a, const double *b, size_t n) {
     const float inf = std::numeric_limits<float>::infinity();
     double m = 0.0;
@@ -1704,7 +1707,7 @@ float host_two_view_absmax(const PrepareArgs &pa, const double *a, const double 
     return std::nextafter((float)m, inf);
 }
 bool prefilter_bound_on_device(int kind, const PrepareArgs &pa) {
-    return kind == EST_ABS && !(pa.mode == 0 && pa.cam1.model_id != CAM_OPENCV);
+    return kind == EST_ABS && !(pa.mode == 0 && !camera_is_nonlinear(pa.cam1.model_id));
 }
 // the bound when it comes from the host (prefilter_bound_on_device false)
 float host_prefilter_bound(int kind, const PrepareArgs &pa, const double *a, const double *b, size_t n) {
@@ -2408,7 +2411,7 @@ int pl_refine_model(pl_problem *p, const pl_bundle_options *opt, const pl_camera
     if (p->kind == EST_ABS && camera && active_cam_flags(to_cam(camera).model_id, *opt))
         return fail(PL_ERR_INVALID, "refine_* moves the camera: call pl_bundle_adjust_camera (camera in / out)");
     if (camera && !camera_supported(camera))
-        return fail(PL_ERR_UNSUPPORTED, "camera model not supported (NULL, SIMPLE_PINHOLE, PINHOLE, OPENCV)");
+        return fail(PL_ERR_UNSUPPORTED, "camera model not supported (NULL, SIMPLE_PINHOLE, PINHOLE, SIMPLE_RADIAL, RADIAL, OPENCV)");
     Context *c;
     int rc = get_context(&c);
     if (rc != PL_OK)
@@ -2458,7 +2461,7 @@ int pl_bundle_adjust_camera(pl_problem *p, const pl_bundle_options *opt, pl_came
     if (p->kind != EST_ABS)
         return fail(PL_ERR_INVALID, "pl_bundle_adjust_camera refines absolute poses");
     if (!camera_supported(camera))
-        return fail(PL_ERR_UNSUPPORTED, "camera model not supported (NULL, SIMPLE_PINHOLE, PINHOLE, OPENCV)");
+        return fail(PL_ERR_UNSUPPORTED, "camera model not supported (NULL, SIMPLE_PINHOLE, PINHOLE, SIMPLE_RADIAL, RADIAL, OPENCV)");
     Context *c;
     int rc = get_context(&c);
     if (rc != PL_OK)
@@ -2602,7 +2605,7 @@ int pl_estimate_absolute_pose(const double *points2D, const double *points3D, si
     if (rc != PL_OK)
         return rc;
     if (!camera || !camera_supported(camera))
-        return fail(PL_ERR_UNSUPPORTED, "camera model not supported (NULL, SIMPLE_PINHOLE, PINHOLE, OPENCV)");
+        return fail(PL_ERR_UNSUPPORTED, "camera model not supported (NULL, SIMPLE_PINHOLE, PINHOLE, SIMPLE_RADIAL, RADIAL, OPENCV)");
     Context *c;
     rc = get_context(&c);
     if (rc != PL_OK)
@@ -2685,7 +2688,7 @@ int pl_estimate_relative_pose(const double *x1, const double *x2, size_t n, cons
     if (rc != PL_OK)
         return rc;
     if (!camera1 || !camera2 || !camera_supported(camera1) || !camera_supported(camera2))
-        return fail(PL_ERR_UNSUPPORTED, "camera model not supported (NULL, SIMPLE_PINHOLE, PINHOLE, OPENCV)");
+        return fail(PL_ERR_UNSUPPORTED, "camera model not supported (NULL, SIMPLE_PINHOLE, PINHOLE, SIMPLE_RADIAL, RADIAL, OPENCV)");
     pl_ransac_stats local;
     return estimate_two_view(EST_REL, x1, x2, n, camera1, camera2, opt, pose, inliers, stats ? stats : &local);
 }
@@ -2759,7 +2762,7 @@ int pl_estimate_homography(const double *x1, const double *x2, size_t n, const p
 // ---------------------------------------------------------------------------- un-distortion stage
 int pl_undistort_points(const pl_camera *camera, const double *points2D, size_t n, double *out) {
     if (!camera || !camera_supported(camera) || camera->model_id == CAM_NULL)
-        return fail(PL_ERR_UNSUPPORTED, "camera model not supported (SIMPLE_PINHOLE, PINHOLE, OPENCV)");
+        return fail(PL_ERR_UNSUPPORTED, "camera model not supported (SIMPLE_PINHOLE, PINHOLE, SIMPLE_RADIAL, RADIAL, OPENCV)");
     if (n > 0x7fffffffu)
         return fail(PL_ERR_INVALID, "too many points");
     if (n && (!points2D || !out))
@@ -2772,7 +2775,7 @@ int pl_undistort_points(const pl_camera *camera, const double *points2D, size_t 
         return PL_OK;
     const CameraParams cam = to_cam(camera);
     double fx, fy, cx, cy;
-    if (camera->model_id == CAM_SIMPLE_PINHOLE)
+    if (camera->model_id == CAM_SIMPLE_PINHOLE || camera_is_radial(camera->model_id))
         fx = fy = cam.p[0], cx = cam.p[1], cy = cam.p[2];
     else
         fx = cam.p[0], fy = cam.p[1], cx = cam.p[2], cy = cam.p[3];

@@ -40,7 +40,7 @@ struct GroupContext { // per host thread AND device, kept for later groups
     int budget_threads = 0; // number of pool threads on the device the budget was computed for
     DevBuf arena, raw, args, lm_records, lm_scratch, seq_count, seq_score, sel_count;
     HostBuf h_raw, h_args, h_ctl, h_meta, h_recm, h_offsets, h_mask, h_tasks, h_count, h_score, h_tail;
-    HostBuf h_samples, h_absmax; // PROSAC samples of a step's members; max|x| read back from k_prepare_g (OPENCV absolute pose)
+    HostBuf h_samples, h_absmax; // PROSAC samples of a step's members; max|x| read back from k_prepare_g (absolute pose through a non-linear camera)
     HostBuf h_raw_alt, h_prep_args;          // the NEXT group's raw points (staged while this worker waits for the device); stage A's table
     const void *staged_first = nullptr;     // first item of the group whose raw points sit in h_raw_alt
     void release() { // pl_set_device moved the thread to another GPU: nothing of the old device may be reused
@@ -161,7 +161,7 @@ bool group_eligible(const pl_batch_item &it) {
     if (validate_options(&o) != PL_OK)
         return false;
     // (round 6: PROSAC - the member's samples are drawn on the host step by step -, warm starts - the initial model is scored and
-    // refined on the worker's stream before the lock-step loop - and OPENCV cameras of absolute-pose problems - max|x| of the
+    // refined on the worker's stream before the lock-step loop - and non-linear cameras (OPENCV, SIMPLE_RADIAL, RADIAL) of absolute-pose problems - max|x| of the
     // un-projected points rides stage A's read-back - are group members like any other)
     if (it.n < (size_t)sample_size(it.kind) + 4 || it.n > kGroupMaxPoints)
         return false;
@@ -461,7 +461,7 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
             hp[i].pad = 0;
             hp[i].args = g.fe.prep;
             hp[i].soa = reinterpret_cast<double *>(slot(i, L.pts));
-            // (the bound of max|x| comes from the host for the linear cameras; OPENCV: k_prepare_g leaves it in the slot)
+            // (the bound of max|x| comes from the host for the linear cameras; non-linear ones: k_prepare_g leaves it in the slot)
             hp[i].absmax_bits = prefilter_bound_on_device(kind, g.fe.prep) ? reinterpret_cast<unsigned long long *>(slot(i, L.absmax)) : nullptr;
             if (hp[i].absmax_bits) {
                 HIP_TRY(hipMemsetAsync(hp[i].absmax_bits, 0, sizeof(unsigned long long), c->stream));

@@ -915,7 +915,7 @@ __global__ __launch_bounds__(256) void k_prepare_g(const PrepareGroupArgs *pa) {
 
 // Un-distortion as a stage of its own (BASELINE config 3: "OPENCV camera model" in front of the homography / 7-point
 // estimators, which take no camera): pixel -> Camera::unproject (misc/camera_models.cc:1025-1032, the iterative
-// OPENCV inverse :972-990) -> pixel of the distortion-free camera with the same focal lengths and principal point.
+// OPENCV inverse :972-990, the radial models' Newton inverse :579-611) -> pixel of the distortion-free camera with the same focal lengths and principal point.
 __global__ __launch_bounds__(256) void k_undistort(const double *__restrict__ in, uint32_t n, CameraParams cam, double fx,
                                                    double fy, double cx, double cy, double *__restrict__ out) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;

@@ -14,6 +14,7 @@
 //   robust/optim/fundamental.h:41-121 + optim_utils.h:57-82   Sampson on the Bartoli-Sturm factorisation
 //   misc/camera_models.cc:668-755,919-1032,2704-2726  projections with Jacobians (NULL, SIMPLE_PINHOLE,
 //                                            PINHOLE, OPENCV)
+//   misc/camera_models.cc:579-611,764-913    SIMPLE_RADIAL and RADIAL: radial polynomial, Newton inverse
 #pragma once
 #include "pl_math.h"
 #include "pl_score.h"
@@ -21,7 +22,11 @@
 namespace pl {
 
 enum LossType : int { LOSS_TRIVIAL = 0, LOSS_TRUNCATED, LOSS_HUBER, LOSS_CAUCHY, LOSS_TRUNCATED_CAUCHY, LOSS_TRUNCATED_LE_ZACH };
-enum CameraId : int { CAM_NULL = -1, CAM_SIMPLE_PINHOLE = 0, CAM_PINHOLE = 1, CAM_OPENCV = 4 };
+enum CameraId : int { CAM_NULL = -1, CAM_SIMPLE_PINHOLE = 0, CAM_PINHOLE = 1, CAM_SIMPLE_RADIAL = 2, CAM_RADIAL = 3, CAM_OPENCV = 4 };
+// SIMPLE_RADIAL (f cx cy k1) and RADIAL (f cx cy k1 k2): one focal length, a polynomial in the squared radius
+PL_HD bool camera_is_radial(int model_id) { return model_id == CAM_SIMPLE_RADIAL || model_id == CAM_RADIAL; }
+// models whose un-projection is iterative: max(|x|, |y|) of the un-projected points cannot be bounded from the pixels on the host
+PL_HD bool camera_is_nonlinear(int model_id) { return model_id == CAM_OPENCV || camera_is_radial(model_id); }
 
 struct LMOptions {
     uint32_t max_iterations;
@@ -110,6 +115,33 @@ PL_HD void opencv_distort(double k1, double k2, double p1, double p2, double u, 
     dv = alpha * v + 2.0 * p2 * uv + p1 * (r2 + 2.0 * v2);
 }
 
+// camera_models.cc:579-611: the radius r with rd = (1 + k1 r^2 [+ k2 r^4]) r by Newton steps from r = rd (UNDIST_TOL 1e-10, at most
+// UNDIST_MAX_ITER 100), every expression in the reference's order of operations
+PL_HD double undistort_poly1(double k1, double rd) {
+    double r = rd;
+    for (int it = 0; it < 100; ++it) {
+        const double r2 = r * r;
+        const double f = k1 * r2 * r + r - rd;
+        if (fabs(f) < 1e-10)
+            break;
+        const double fp = 3.0 * k1 * r2 + 1.0;
+        r = r - f / fp;
+    }
+    return r;
+}
+PL_HD double undistort_poly2(double k1, double k2, double rd) {
+    double r = rd;
+    for (int it = 0; it < 100; ++it) {
+        const double r2 = r * r;
+        const double f = k2 * r2 * r2 * r + k1 * r2 * r + r - rd;
+        if (fabs(f) < 1e-10)
+            break;
+        const double fp = 5.0 * k2 * r2 * r2 + 3.0 * k1 * r2 + 1.0;
+        r = r - f / fp;
+    }
+    return r;
+}
+
 // pixel -> normalised image plane (camera_models.h:98-102: unit bearing first, then hnormalized)
 PL_HD void camera_unproject(const CameraParams &c, double px, double py, double &ox, double &oy) {
     double u, v;
@@ -142,6 +174,19 @@ PL_HD void camera_unproject(const CameraParams &c, double px, double py, double 
         }
         break;
     }
+    case CAM_SIMPLE_RADIAL:
+    case CAM_RADIAL: { // camera_models.cc:819-830, 895-907
+        u = (px - c.p[1]) / c.p[0];
+        v = (py - c.p[2]) / c.p[0];
+        const double r0 = sqrt(u * u + v * v);
+        if (fabs(r0) > 1e-8) {
+            const double r = (c.model_id == CAM_RADIAL) ? undistort_poly2(c.p[3], c.p[4], r0) : undistort_poly1(c.p[3], r0);
+            const double s = r / r0;
+            u *= s;
+            v *= s;
+        }
+        break;
+    }
     default: // CAM_NULL: bearing is (x, y, 1) un-normalised
         ox = px / 1.0;
         oy = py / 1.0;
@@ -169,10 +214,57 @@ PL_HD void camera_project(const CameraParams &c, Vec3 Z, double &ox, double &oy)
         oy = c.p[1] * dv + c.p[3];
         return;
     }
+    case CAM_SIMPLE_RADIAL: { // camera_models.cc:842-851: multiplies by 1 / z ...
+        const double inv_z = 1.0 / Z.z;
+        const double u = Z.x * inv_z, v = Z.y * inv_z;
+        const double r2 = u * u + v * v;
+        const double alpha = (1.0 + c.p[3] * r2);
+        ox = c.p[0] * alpha * u + c.p[1];
+        oy = c.p[0] * alpha * v + c.p[2];
+        return;
+    }
+    case CAM_RADIAL: { // ... :767-773: divides by z (hnormalized), unlike its project_with_jac
+        const double u = Z.x / Z.z, v = Z.y / Z.z;
+        const double r2 = u * u + v * v;
+        const double alpha = (1.0 + c.p[3] * r2 + c.p[4] * r2 * r2);
+        ox = c.p[0] * alpha * u + c.p[1];
+        oy = c.p[0] * alpha * v + c.p[2];
+        return;
+    }
     default:
         ox = Z.x / Z.z;
         oy = Z.y / Z.z;
     }
+}
+// camera_models.cc:774-818, 852-894: the radial models' project_with_jac up to jac = jac_d * [d(x/z, y/z)/dZ]; u, v, r2, alpha come
+// back for the parameter columns (pl_refine_cam.h)
+PL_HD void radial_project_jac(const CameraParams &c, Vec3 Z, double &ox, double &oy, double *J, double &u, double &v, double &r2,
+                              double &alpha) {
+    const double inv_z = 1.0 / Z.z;
+    u = Z.x * inv_z, v = Z.y * inv_z;
+    r2 = u * u + v * v;
+    double Jd[4];
+    if (c.model_id == CAM_RADIAL) {
+        alpha = (1.0 + c.p[3] * r2 + c.p[4] * r2 * r2);
+        const double alphap = (2.0 * c.p[3] + 4.0 * c.p[4] * r2);
+        Jd[0] = (alphap * u * u + alpha) * c.p[0];
+        Jd[1] = (alphap * u * v) * c.p[0];
+        Jd[3] = (alphap * v * v + alpha) * c.p[0];
+    } else {
+        alpha = (1.0 + c.p[3] * r2);
+        Jd[0] = (2.0 * c.p[3] * u * u + alpha) * c.p[0];
+        Jd[1] = (2.0 * c.p[3] * u * v) * c.p[0];
+        Jd[3] = (2.0 * c.p[3] * v * v + alpha) * c.p[0];
+    }
+    Jd[2] = Jd[1];
+    const double P[6] = {inv_z, 0.0, -u * inv_z, 0.0, inv_z, -v * inv_z};
+    PL_UNROLL
+    for (int a = 0; a < 2; ++a)
+        PL_UNROLL
+        for (int b = 0; b < 3; ++b)
+            J[3 * a + b] = Jd[2 * a] * P[b] + Jd[2 * a + 1] * P[3 + b];
+    ox = c.p[0] * alpha * u + c.p[1];
+    oy = c.p[0] * alpha * v + c.p[2];
 }
 // projection + d(xp)/dZ (2x3 row-major)
 PL_HD void camera_project_jac(const CameraParams &c, Vec3 Z, double &ox, double &oy, double *J) {
@@ -207,6 +299,12 @@ PL_HD void camera_project_jac(const CameraParams &c, Vec3 Z, double &ox, double 
         }
         ox = c.p[0] * du + c.p[2];
         oy = c.p[1] * dv + c.p[3];
+        return;
+    }
+    case CAM_SIMPLE_RADIAL:
+    case CAM_RADIAL: {
+        double u, v, r2, alpha;
+        radial_project_jac(c, Z, ox, oy, J, u, v, r2, alpha);
         return;
     }
     default: {

@@ -6,6 +6,7 @@
 //   robust/optim/absolute.h:49-171           Jacobian columns [rotation 3 | translation 3 | selected camera parameters],
 //                                            step adds the increments to the selected parameters
 //   misc/camera_models.cc:688-698, 739-747, 953-965, 1005-1021   d projection / d parameters (SIMPLE_PINHOLE, PINHOLE, OPENCV)
+//   misc/camera_models.cc:798-814, 877-890                       ... of RADIAL and SIMPLE_RADIAL
 //   misc/camera_models.cc get_param_refinement_idx: focal indices, principal-point indices, extra indices in that order
 //
 // PL_HD like pl_refine.h: k_lm_cam (lm_cam.hip) and the host test build (tests/hostmath) run the same functions; the
@@ -39,6 +40,17 @@ PL_HD int camera_refinement_idx(int model_id, int flags, int *idx) {
             idx[m++] = 0;
         if (pp)
             idx[m++] = 1, idx[m++] = 2;
+        break;
+    case CAM_SIMPLE_RADIAL:
+    case CAM_RADIAL:
+        if (f)
+            idx[m++] = 0;
+        if (pp)
+            idx[m++] = 1, idx[m++] = 2;
+        if (ex)
+            idx[m++] = 3;
+        if (ex && model_id == CAM_RADIAL)
+            idx[m++] = 4;
         break;
     case CAM_PINHOLE:
     case CAM_OPENCV:
@@ -108,6 +120,17 @@ PL_HD void camera_project_jac_params(const CameraParams &c, Vec3 Z, double &ox, 
         }
         ox = c.p[0] * du + c.p[2];
         oy = c.p[1] * dv + c.p[3];
+        return;
+    }
+    case CAM_SIMPLE_RADIAL:
+    case CAM_RADIAL: {
+        double u, v, r2, alpha;
+        radial_project_jac(c, Z, ox, oy, J, u, v, r2, alpha);
+        Jc[0][0] = alpha * u, Jc[1][0] = alpha * v;
+        Jc[0][1] = 1.0, Jc[1][2] = 1.0;
+        Jc[0][3] = c.p[0] * r2 * u, Jc[1][3] = c.p[0] * r2 * v;
+        if (c.model_id == CAM_RADIAL)
+            Jc[0][4] = c.p[0] * r2 * r2 * u, Jc[1][4] = c.p[0] * r2 * r2 * v;
         return;
     }
     default: { // identity camera: no parameters

@@ -207,3 +207,15 @@ def opencv_distort_pixels(pix: np.ndarray, params) -> np.ndarray:
     du = alpha * u + 2.0 * p1 * u * v + p2 * (r2 + 2.0 * u * u)
     dv = alpha * v + 2.0 * p2 * u * v + p1 * (r2 + 2.0 * v * v)
     return np.stack([fx * du + cx, fy * dv + cy], axis=1)
+
+
+def radial_distort_pixels(pix: np.ndarray, params) -> np.ndarray:
+    """Push pinhole pixels through a SIMPLE_RADIAL (f, cx, cy, k1) or RADIAL (f, cx, cy, k1, k2) camera with the same
+    f, cx, cy - what COLMAP's default models do to an image."""
+    f, cx, cy, k1 = params[:4]
+    k2 = params[4] if len(params) > 4 else 0.0
+    u = (pix[:, 0] - cx) / f
+    v = (pix[:, 1] - cy) / f
+    r2 = u * u + v * v
+    alpha = 1.0 + k1 * r2 + k2 * r2 * r2
+    return np.stack([f * alpha * u + cx, f * alpha * v + cy], axis=1)
