@@ -105,8 +105,13 @@ typedef struct {
 } pl_ransac_stats;
 
 /* misc/camera_models.h:56-60; supported ids: -1 NULL, 0 SIMPLE_PINHOLE {f cx cy}, 1 PINHOLE {fx fy cx cy},
- * 2 SIMPLE_RADIAL {f cx cy k1}, 3 RADIAL {f cx cy k1 k2}, 4 OPENCV {fx fy cx cy k1 k2 p1 p2}; num_params at least the model's
- * count.  Every other id (fisheye, FOV, division, FULL_OPENCV, thin-prism models) and a short num_params: PL_ERR_UNSUPPORTED */
+ * 2 SIMPLE_RADIAL {f cx cy k1}, 3 RADIAL {f cx cy k1 k2}, 4 OPENCV {fx fy cx cy k1 k2 p1 p2},
+ * 5 OPENCV_FISHEYE {fx fy cx cy k1 k2 k3 k4}, 8 SIMPLE_RADIAL_FISHEYE {f cx cy k}, 9 RADIAL_FISHEYE {f cx cy k1 k2} (the radius in
+ * the image is f theta (1 + k1 theta^2 + k2 theta^4 ...), theta the angle to the optical axis); num_params at least the model's
+ * count, for the fisheye models exactly the model's count (the reference's un-projection reads every parameter up to params.size()
+ * as a coefficient of that polynomial, its projection the model's own: a longer list makes the two disagree).  Every other id
+ * (FOV, THIN_PRISM_FISHEYE, division, FULL_OPENCV, thin-prism models, 1D_RADIAL, SPHERICAL) and a num_params that does not fit:
+ * PL_ERR_UNSUPPORTED */
 typedef struct {
     int32_t model_id, width, height, num_params;
     double params[12];
@@ -165,7 +170,7 @@ int pl_estimate_homography(const double *points2D_1, const double *points2D_2, s
 /* ---- un-distortion as a stage of its own (BASELINE config 3: pixels of an OPENCV camera in front of the homography /
  * 7-point estimators, which take no camera).  Every point goes through Camera::unproject (misc/camera_models.h:98-102;
  * OPENCV: the iterative inverse of misc/camera_models.cc:972-990; SIMPLE_RADIAL / RADIAL: the Newton inverse of the radial
- * polynomial :579-611) and comes back as the pixel of the distortion-free
+ * polynomial :579-611; the fisheye models: the Newton inverse of the polynomial in theta :613-662, then 1 / tan(theta)) and comes back as the pixel of the distortion-free
  * camera with the same focal lengths and principal point: out = (fx u + cx, fy v + cy).  points2D, out: N x 2.
  * camera: any supported model but NULL. ---- */
 int pl_undistort_points(const pl_camera *camera, const double *points2D, size_t n, double *out);
@@ -180,7 +185,7 @@ typedef struct {
                               * unknown focal length (pl_estimate_shared_focal_relative_pose).  Kind-4 items and kind-0 items with
                               * estimate_focal_length advance in lock-step groups of their own since round 5 (one launch sequence per
                               * group, every item bit-identical to its single call).  Kinds 0 - 3 with PROSAC, a warm start
-                              * (ransac.score_initial_model) or a distorting camera (SIMPLE_RADIAL, RADIAL, OPENCV) are group members like any other since round 6;
+                              * (ransac.score_initial_model) or a distorting camera (SIMPLE_RADIAL, RADIAL, OPENCV, the fisheye models) are group members like any other since round 6;
                               * what still runs one at a time: min_iterations > 4096, fewer correspondences than sample size + 4,
                               * more than 16384, warm starts of the focal-length kinds (pl_last_batch_report counts them) */
     int32_t status;          /* out: PL_OK or the error of this item */
@@ -313,6 +318,11 @@ int pl_debug_score_stream(pl_problem *p, const void *models, size_t n, double ma
  * cos and sincos follow glibc for |x| < 105414350, sin for |x| < 2.426265 (pl_libm.h); beyond, they return the device
  * library's values.  tests/ compares every code with the host's libm / IEEE arithmetic bit for bit. */
 int pl_debug_device_math(int fn, const double *x, size_t n, double *out);
+/* ... and the two functions the fisheye cameras need, element-wise on n <= 2^28 pairs - fn 0: out[i] = pl_atan2(x[i], y[i])
+ * (x is atan2's FIRST argument, the cameras' rho), fn 1: out[i] = pl_tan(x[i]) (y is not read and may be NULL).  Any other fn:
+ * PL_ERR_INVALID.  pl_atan2 follows glibc for every finite second argument and every finite non-zero first one, pl_tan for
+ * |x| <= 25 (pl_libm.h); beyond, they return the device library's values (finite input: finite or +-inf as tan goes). */
+int pl_debug_device_math2(int fn, const double *x, const double *y, size_t n, double *out);
 /* Non-linear refinement of one model on the resident correspondences (robust/bundle.h:41-170:
  * bundle_adjust / refine_relpose / refine_fundamental / refine_homography).  camera: absolute pose only
  * (NULL pointer = identity camera, i.e. normalised image points; otherwise any supported model, the points being its
@@ -325,7 +335,8 @@ int pl_refine_model(pl_problem *p, const pl_bundle_options *opt, const pl_camera
  * an absolute-pose problem whose 2-D points are PIXELS: pose and, per opt->refine_focal_length / refine_principal_point /
  * refine_extra_params, the camera's intrinsics are refined together (robust/optim/absolute.h:49-171); both in / out.
  * The flags select parameters in the reference's order (Camera::get_param_refinement_idx): focal, principal point, extra -
- * SIMPLE_RADIAL {0}, {1, 2}, {3}; RADIAL {0}, {1, 2}, {3, 4}; OPENCV {0, 1}, {2, 3}, {4 .. 7}. */
+ * SIMPLE_RADIAL {0}, {1, 2}, {3}; RADIAL {0}, {1, 2}, {3, 4}; OPENCV {0, 1}, {2, 3}, {4 .. 7}; OPENCV_FISHEYE {0, 1}, {2, 3},
+ * {4 .. 7}; SIMPLE_RADIAL_FISHEYE {0}, {1, 2}, {3}; RADIAL_FISHEYE {0}, {1, 2}, {3, 4}. */
 int pl_bundle_adjust_camera(pl_problem *p, const pl_bundle_options *opt, pl_camera *camera, const uint8_t *mask,
                             pl_camera_pose *pose, uint32_t *lm_iterations);
 

@@ -163,6 +163,7 @@ def _declare(L):
         "pl_score_model": (cint, [vp, vp, dbl, P(C.c_uint64), P(dbl)]),
         "pl_debug_score_stream": (cint, [vp, vp, sz, dbl, vp, vp, P(C.c_int32)]),
         "pl_debug_device_math": (cint, [cint, vp, sz, vp]),
+        "pl_debug_device_math2": (cint, [cint, vp, vp, sz, vp]),
         "pl_refine_model": (cint, [vp, P(BundleOptions), cam, vp, vp, P(C.c_uint32)]),
         "pl_bundle_adjust_camera": (cint, [vp, P(BundleOptions), cam, vp, P(CameraPose), P(C.c_uint32)]),
         "pl_p3p": (cint, [vp, vp, P(CameraPose)]),
@@ -197,7 +198,7 @@ EXPORTED_SYMBOLS = [
     "pl_estimate_fundamental", "pl_estimate_homography", "pl_ransac_pnp", "pl_ransac_relpose", "pl_ransac_fundamental",
     "pl_ransac_homography", "pl_problem_create", "pl_problem_destroy", "pl_ransac_run", "pl_ransac_run_sharded", "pl_score_model", "pl_debug_score_stream", "pl_refine_model", "pl_bundle_adjust_camera", "pl_p3p", "pl_relpose_5pt",
     "pl_essential_matrix_5pt", "pl_relpose_7pt", "pl_homography_4pt", "pl_solve_batch", "pl_estimate_batch", "pl_estimate_batch_devices", "pl_last_batch_report", "pl_undistort_points",
-    "pl_ransac_batch", "pl_debug_device_math", "pl_ransac_pnpf", "pl_ransac_shared_focal_relpose", "pl_refine_shared_focal_relpose",
+    "pl_ransac_batch", "pl_debug_device_math", "pl_debug_device_math2", "pl_ransac_pnpf", "pl_ransac_shared_focal_relpose", "pl_refine_shared_focal_relpose",
     "pl_estimate_shared_focal_relative_pose", "pl_solve_focal_batch", "pl_p35pf", "pl_relpose_6pt_shared_focal", "pl_set_lm_mode",
     "pl_abi_version",
 ]

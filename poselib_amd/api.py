@@ -25,7 +25,8 @@ from . import _lib as L
 LAMBDA_UPDATES = {"NIELSEN": 0, "FIXED_FACTOR": 1}
 DAMPINGS = {"LEVENBERG": 0, "MARQUARDT": 1}
 LOSS_TYPES = {"TRIVIAL": 0, "TRUNCATED": 1, "HUBER": 2, "CAUCHY": 3, "TRUNCATED_CAUCHY": 4, "TRUNCATED_LE_ZACH": 5}
-CAMERA_MODEL_IDS = {"NULL": -1, "SIMPLE_PINHOLE": 0, "PINHOLE": 1, "SIMPLE_RADIAL": 2, "RADIAL": 3, "OPENCV": 4}
+CAMERA_MODEL_IDS = {"NULL": -1, "SIMPLE_PINHOLE": 0, "PINHOLE": 1, "SIMPLE_RADIAL": 2, "RADIAL": 3, "OPENCV": 4,
+                    "OPENCV_FISHEYE": 5, "SIMPLE_RADIAL_FISHEYE": 8, "RADIAL_FISHEYE": 9}
 _CAMERA_NAMES = {v: k for k, v in CAMERA_MODEL_IDS.items()}
 KIND_ABS, KIND_REL, KIND_FUND, KIND_HOM = 0, 1, 2, 3
 KIND_SHARED_FOCAL = 4  # pl_batch_item only: estimate_shared_focal_relative_pose
@@ -75,9 +76,9 @@ class Camera:
     def focal(self):
         if not self.params:
             return 1.0
-        if self.model_id in (0, 2, 3):
+        if self.model_id in (0, 2, 3, 8, 9):
             return self.params[0]
-        if self.model_id in (1, 4):
+        if self.model_id in (1, 4, 5):
             return 0.5 * self.params[0] + 0.5 * self.params[1]
         return 1.0
 
@@ -410,6 +411,19 @@ def device_math(fn: int, x):
     x = np.ascontiguousarray(x, dtype=np.float64)
     out = np.zeros_like(x)
     L.check(L.lib().pl_debug_device_math(int(fn), _ptr(x), C.c_size_t(x.size), _ptr(out)))
+    return out
+
+
+def device_math2(fn: int, x, y=None):
+    """Diagnostic (pl_debug_device_math2): the device kernels' two-argument scalar math, element-wise - 0: pl_atan2(x, y), x being
+    atan2's first argument; 1: pl_tan(x) (y is not read).  An unknown code raises PoseLibAmdError."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    if y is not None:
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        if y.shape != x.shape:
+            raise ValueError("x and y differ in shape")
+    out = np.zeros_like(x)
+    L.check(L.lib().pl_debug_device_math2(int(fn), _ptr(x), None if y is None else _ptr(y), C.c_size_t(x.size), _ptr(out)))
     return out
 
 

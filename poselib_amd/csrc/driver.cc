@@ -287,10 +287,15 @@ CameraParams to_cam(const pl_camera *c) {
         r.p[i] = c->params[i];
     return r;
 }
+// The fisheye models take EXACTLY their parameter count: the reference's inverse (undistort_theta_poly, camera_models.cc:613-662) reads
+// every parameter from the first coefficient to params.size() as a further coefficient of the polynomial in theta, while its projection
+// reads the model's own - with more parameters than the model has, un-projection is no longer the inverse of projection.
 bool camera_supported(const pl_camera *c) {
     return c->model_id == CAM_NULL || (c->model_id == CAM_SIMPLE_PINHOLE && c->num_params >= 3) ||
            (c->model_id == CAM_PINHOLE && c->num_params >= 4) || (c->model_id == CAM_SIMPLE_RADIAL && c->num_params >= 4) ||
-           (c->model_id == CAM_RADIAL && c->num_params >= 5) || (c->model_id == CAM_OPENCV && c->num_params >= 8);
+           (c->model_id == CAM_RADIAL && c->num_params >= 5) || (c->model_id == CAM_OPENCV && c->num_params >= 8) ||
+           (c->model_id == CAM_OPENCV_FISHEYE && c->num_params == 8) || (c->model_id == CAM_SIMPLE_RADIAL_FISHEYE && c->num_params == 4) ||
+           (c->model_id == CAM_RADIAL_FISHEYE && c->num_params == 5);
 }
 double camera_focal(const pl_camera *c) { // misc/camera_models.cc:304-323
     if (c->num_params == 0)
@@ -299,28 +304,31 @@ double camera_focal(const pl_camera *c) { // misc/camera_models.cc:304-323
     case CAM_SIMPLE_PINHOLE:
     case CAM_SIMPLE_RADIAL:
     case CAM_RADIAL:
+    case CAM_SIMPLE_RADIAL_FISHEYE:
+    case CAM_RADIAL_FISHEYE:
         return 0.0 + c->params[0] / 1;
     case CAM_PINHOLE:
     case CAM_OPENCV:
+    case CAM_OPENCV_FISHEYE:
         return 0.0 + c->params[0] / 2 + c->params[1] / 2;
     default:
         return 1.0;
     }
 }
 void camera_set_focal(pl_camera *c, double f) { // misc/camera_models.cc:96-107 over the model's focal_idx
-    if ((c->model_id == CAM_SIMPLE_PINHOLE || camera_is_radial(c->model_id)) && c->num_params >= 1) {
-        c->params[0] = f;
-    } else if ((c->model_id == CAM_PINHOLE || c->model_id == CAM_OPENCV) && c->num_params >= 2) {
+    if (camera_has_two_focals(c->model_id) && c->num_params >= 2) {
         c->params[0] = f;
         c->params[1] = f;
+    } else if (c->model_id != CAM_NULL && !camera_has_two_focals(c->model_id) && c->num_params >= 1) {
+        c->params[0] = f;
     }
 }
 void camera_rescale(CameraParams &c, double s) { // misc/camera_models.cc:432-455
     if (c.num_params == 0)
         return;
-    if (c.model_id == CAM_SIMPLE_PINHOLE || camera_is_radial(c.model_id)) { // (the distortion parameters stay)
+    if (c.model_id != CAM_NULL && !camera_has_two_focals(c.model_id)) { // (the distortion parameters stay)
         c.p[0] *= s, c.p[1] *= s, c.p[2] *= s;
-    } else if (c.model_id == CAM_PINHOLE || c.model_id == CAM_OPENCV) {
+    } else if (camera_has_two_focals(c.model_id)) {
         for (int i = 0; i < 4; ++i)
             c.p[i] *= s;
     }
@@ -1645,7 +1653,7 @@ void free_problem(pl_problem *p) {
 // The bound of max(|x|, |y|) of the prepared points that keeps the scorers' fp32 / fp16 pre-filters conservative (pl_prefilter.h).
 // Absolute pose through a linear camera and two-view problems from 1024 correspondences on (the matrix-core Sampson form; the O(N)
 // host pass is not worth it below) get it from the raw points on the host; absolute pose through a non-linear camera (OPENCV,
-// SIMPLE_RADIAL, RADIAL: camera_is_nonlinear) reads k_prepare's atomic max back (the un-projection is iterative); smaller two-view problems get none (+inf).  make_problem_prepared and the groups'
+// SIMPLE_RADIAL, RADIAL, the fisheye models: camera_is_nonlinear) reads k_prepare's atomic max back (the un-projection is iterative); smaller two-view problems get none (+inf).  make_problem_prepared and the groups'
 // stage A both decide it here.
 
 // upper bound of max(|x|, |y|) of the un-projected 2-D points of a linear camera (the un-projected coordinate is (px - c) / f up to
@@ -2404,6 +2412,40 @@ int pl_debug_device_math(int fn, const double *x, size_t n, double *out) {
     return PL_OK;
 }
 
+int pl_debug_device_math2(int fn, const double *x, const double *y, size_t n, double *out) {
+    if (fn < 0 || fn >= kDeviceMath2Fns)
+        return fail(PL_ERR_INVALID, "unknown device math function");
+    if ((!x || !out || (fn == 0 && !y)) && n)
+        return fail(PL_ERR_INVALID, "null pointer");
+    if (n > (1u << 28))
+        return fail(PL_ERR_INVALID, "too many values");
+    Context *c;
+    int rc = get_context(&c);
+    if (rc != PL_OK)
+        return rc;
+    if (n == 0)
+        return PL_OK;
+    struct Scratch { // freed on every path
+        void *p = nullptr;
+        ~Scratch() {
+            if (p)
+                (void)hipFree(p);
+        }
+    } dx, dy, dout;
+    HIP_TRY(hipMalloc(&dx.p, sizeof(double) * n));
+    HIP_TRY(hipMalloc(&dout.p, sizeof(double) * n));
+    HIP_TRY(hipMemcpyAsync(dx.p, x, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+    if (fn == 0) {
+        HIP_TRY(hipMalloc(&dy.p, sizeof(double) * n));
+        HIP_TRY(hipMemcpyAsync(dy.p, y, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+    }
+    HIP_TRY(launch_device_math2(fn, static_cast<const double *>(dx.p), static_cast<const double *>(fn == 0 ? dy.p : dx.p), (uint32_t)n,
+                                static_cast<double *>(dout.p), c->stream));
+    HIP_TRY(hipMemcpyAsync(out, dout.p, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return PL_OK;
+}
+
 int pl_refine_model(pl_problem *p, const pl_bundle_options *opt, const pl_camera *camera, const uint8_t *mask,
                     void *model, uint32_t *lm_iterations) {
     if (!p || !model || !opt)
@@ -2411,7 +2453,7 @@ int pl_refine_model(pl_problem *p, const pl_bundle_options *opt, const pl_camera
     if (p->kind == EST_ABS && camera && active_cam_flags(to_cam(camera).model_id, *opt))
         return fail(PL_ERR_INVALID, "refine_* moves the camera: call pl_bundle_adjust_camera (camera in / out)");
     if (camera && !camera_supported(camera))
-        return fail(PL_ERR_UNSUPPORTED, "camera model not supported (NULL, SIMPLE_PINHOLE, PINHOLE, SIMPLE_RADIAL, RADIAL, OPENCV)");
+        return fail(PL_ERR_UNSUPPORTED, "camera model not supported (NULL, SIMPLE_PINHOLE, PINHOLE, SIMPLE_RADIAL, RADIAL, OPENCV, OPENCV_FISHEYE, SIMPLE_RADIAL_FISHEYE, RADIAL_FISHEYE)");
     Context *c;
     int rc = get_context(&c);
     if (rc != PL_OK)
@@ -2461,7 +2503,7 @@ int pl_bundle_adjust_camera(pl_problem *p, const pl_bundle_options *opt, pl_came
     if (p->kind != EST_ABS)
         return fail(PL_ERR_INVALID, "pl_bundle_adjust_camera refines absolute poses");
     if (!camera_supported(camera))
-        return fail(PL_ERR_UNSUPPORTED, "camera model not supported (NULL, SIMPLE_PINHOLE, PINHOLE, SIMPLE_RADIAL, RADIAL, OPENCV)");
+        return fail(PL_ERR_UNSUPPORTED, "camera model not supported (NULL, SIMPLE_PINHOLE, PINHOLE, SIMPLE_RADIAL, RADIAL, OPENCV, OPENCV_FISHEYE, SIMPLE_RADIAL_FISHEYE, RADIAL_FISHEYE)");
     Context *c;
     int rc = get_context(&c);
     if (rc != PL_OK)
@@ -2605,7 +2647,7 @@ int pl_estimate_absolute_pose(const double *points2D, const double *points3D, si
     if (rc != PL_OK)
         return rc;
     if (!camera || !camera_supported(camera))
-        return fail(PL_ERR_UNSUPPORTED, "camera model not supported (NULL, SIMPLE_PINHOLE, PINHOLE, SIMPLE_RADIAL, RADIAL, OPENCV)");
+        return fail(PL_ERR_UNSUPPORTED, "camera model not supported (NULL, SIMPLE_PINHOLE, PINHOLE, SIMPLE_RADIAL, RADIAL, OPENCV, OPENCV_FISHEYE, SIMPLE_RADIAL_FISHEYE, RADIAL_FISHEYE)");
     Context *c;
     rc = get_context(&c);
     if (rc != PL_OK)
@@ -2688,7 +2730,7 @@ int pl_estimate_relative_pose(const double *x1, const double *x2, size_t n, cons
     if (rc != PL_OK)
         return rc;
     if (!camera1 || !camera2 || !camera_supported(camera1) || !camera_supported(camera2))
-        return fail(PL_ERR_UNSUPPORTED, "camera model not supported (NULL, SIMPLE_PINHOLE, PINHOLE, SIMPLE_RADIAL, RADIAL, OPENCV)");
+        return fail(PL_ERR_UNSUPPORTED, "camera model not supported (NULL, SIMPLE_PINHOLE, PINHOLE, SIMPLE_RADIAL, RADIAL, OPENCV, OPENCV_FISHEYE, SIMPLE_RADIAL_FISHEYE, RADIAL_FISHEYE)");
     pl_ransac_stats local;
     return estimate_two_view(EST_REL, x1, x2, n, camera1, camera2, opt, pose, inliers, stats ? stats : &local);
 }
@@ -2762,7 +2804,7 @@ int pl_estimate_homography(const double *x1, const double *x2, size_t n, const p
 // ---------------------------------------------------------------------------- un-distortion stage
 int pl_undistort_points(const pl_camera *camera, const double *points2D, size_t n, double *out) {
     if (!camera || !camera_supported(camera) || camera->model_id == CAM_NULL)
-        return fail(PL_ERR_UNSUPPORTED, "camera model not supported (SIMPLE_PINHOLE, PINHOLE, SIMPLE_RADIAL, RADIAL, OPENCV)");
+        return fail(PL_ERR_UNSUPPORTED, "camera model not supported (SIMPLE_PINHOLE, PINHOLE, SIMPLE_RADIAL, RADIAL, OPENCV, OPENCV_FISHEYE, SIMPLE_RADIAL_FISHEYE, RADIAL_FISHEYE)");
     if (n > 0x7fffffffu)
         return fail(PL_ERR_INVALID, "too many points");
     if (n && (!points2D || !out))
@@ -2775,7 +2817,7 @@ int pl_undistort_points(const pl_camera *camera, const double *points2D, size_t 
         return PL_OK;
     const CameraParams cam = to_cam(camera);
     double fx, fy, cx, cy;
-    if (camera->model_id == CAM_SIMPLE_PINHOLE || camera_is_radial(camera->model_id))
+    if (!camera_has_two_focals(camera->model_id))
         fx = fy = cam.p[0], cx = cam.p[1], cy = cam.p[2];
     else
         fx = cam.p[0], fy = cam.p[1], cx = cam.p[2], cy = cam.p[3];

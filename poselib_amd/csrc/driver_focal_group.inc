@@ -79,7 +79,7 @@ int focal_group_estimator(const pl_batch_item &it) {
         if (o.min_fov != o.min_fov || o.tangent_sampson || o.estimate_extra_params)
             return -1; // (validate_options reports these)
         if (!camera_supported(it.camera1) || it.camera1->model_id == CAM_NULL)
-            return -1; // (SIMPLE_PINHOLE, PINHOLE, SIMPLE_RADIAL, RADIAL, OPENCV: every model whose focal length the estimate can be written to)
+            return -1; // (every supported model but NULL: every model whose focal length the estimate can be written to)
         return it.n >= (size_t)kFocalSample + 4 ? 0 : -1;
     }
     if (it.kind == 4) {

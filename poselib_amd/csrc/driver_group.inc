@@ -161,7 +161,7 @@ bool group_eligible(const pl_batch_item &it) {
     if (validate_options(&o) != PL_OK)
         return false;
     // (round 6: PROSAC - the member's samples are drawn on the host step by step -, warm starts - the initial model is scored and
-    // refined on the worker's stream before the lock-step loop - and non-linear cameras (OPENCV, SIMPLE_RADIAL, RADIAL) of absolute-pose problems - max|x| of the
+    // refined on the worker's stream before the lock-step loop - and non-linear cameras (OPENCV, SIMPLE_RADIAL, RADIAL, the fisheye models) of absolute-pose problems - max|x| of the
     // un-projected points rides stage A's read-back - are group members like any other)
     if (it.n < (size_t)sample_size(it.kind) + 4 || it.n > kGroupMaxPoints)
         return false;

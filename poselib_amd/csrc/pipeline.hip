@@ -915,7 +915,7 @@ __global__ __launch_bounds__(256) void k_prepare_g(const PrepareGroupArgs *pa) {
 
 // Un-distortion as a stage of its own (BASELINE config 3: "OPENCV camera model" in front of the homography / 7-point
 // estimators, which take no camera): pixel -> Camera::unproject (misc/camera_models.cc:1025-1032, the iterative
-// OPENCV inverse :972-990, the radial models' Newton inverse :579-611) -> pixel of the distortion-free camera with the same focal lengths and principal point.
+// OPENCV inverse :972-990, the radial models' Newton inverse :579-611, the fisheye models' :613-662) -> pixel of the distortion-free camera with the same focal lengths and principal point.
 __global__ __launch_bounds__(256) void k_undistort(const double *__restrict__ in, uint32_t n, CameraParams cam, double fx,
                                                    double fy, double cx, double cy, double *__restrict__ out) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
@@ -951,6 +951,20 @@ __global__ __launch_bounds__(256) void k_device_math(int fn, const double *__res
     default: r = v; break;
     }
     out[i] = r;
+}
+// ... and its two-argument functions (pl_debug_device_math2): 0 pl_atan2(x, y), 1 pl_tan(x)
+__global__ __launch_bounds__(256) void k_device_math2(int fn, const double *__restrict__ x, const double *__restrict__ y, uint32_t n,
+                                                      double *__restrict__ out) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n)
+        return;
+    out[i] = (fn == 0) ? pl_atan2(x[i], y[i]) : pl_tan(x[i]);
+}
+hipError_t launch_device_math2(int fn, const double *x, const double *y, uint32_t n, double *out, hipStream_t stream) {
+    if (n == 0)
+        return hipSuccess;
+    k_device_math2<<<dim3((n + 255) / 256), dim3(256), 0, stream>>>(fn, x, y, n, out);
+    return hipGetLastError();
 }
 hipError_t launch_device_math(int fn, const double *x, uint32_t n, double *out, hipStream_t stream) {
     if (n == 0)

@@ -6,6 +6,8 @@
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define PL_HD __host__ __device__ __forceinline__
+// a device function that stays a CALL: for a rarely taken branch whose registers would otherwise be charged to every path of a kernel
+#define PL_HD_CALL __host__ __device__ inline __attribute__((noinline))
 #define PL_UNROLL _Pragma("unroll") // small constant-trip loops over register arrays: no dynamic indexing -> no scratch
 // orders the LDS accesses of the lanes of one wavefront (the hardware executes a wavefront's LDS instructions in order; this keeps the
 // compiler from moving or caching accesses across the phases of the algorithm)
@@ -16,5 +18,6 @@
     } while (0)
 #else
 #define PL_HD inline
+#define PL_HD_CALL inline
 #define PL_UNROLL
 #endif

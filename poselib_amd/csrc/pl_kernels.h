@@ -166,6 +166,9 @@ hipError_t launch_prepare(const double *a_raw, const double *b_raw, uint32_t n, 
 // sincos, 9 fp16 round-to-nearest bits, 10 fp16 bits -> float, 11 fp16 round-up bits - as the kernels evaluate them
 constexpr int kDeviceMathFns = 12;
 hipError_t launch_device_math(int fn, const double *x, uint32_t n, double *out, hipStream_t stream);
+// diagnostic, two arguments: fn 0 pl_atan2(x, y), 1 pl_tan(x) (y not read)
+constexpr int kDeviceMath2Fns = 2;
+hipError_t launch_device_math2(int fn, const double *x, const double *y, uint32_t n, double *out, hipStream_t stream);
 hipError_t launch_undistort(const double *in, uint32_t n, const CameraParams &cam, double fx, double fy, double cx,
                             double cy, double *out, hipStream_t stream);
 // After the LM kernels: records of the refined models on the device (skipped tasks keep their input record), and the

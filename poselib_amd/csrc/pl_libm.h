@@ -25,6 +25,9 @@
 //             A host without FMA would run glibc's sse2 variant, whose results differ in the last bit for a small
 //             share of the arguments - the oracle then differs from this header exactly as it differs from itself
 //             on another machine.
+//   pl_atan2, pl_tan : e_atan2.c __ieee754_atan2 and s_tan.c __tan, FMA variants, for the fisheye camera models
+//             (misc/camera_models.cc:1049, 1190, ...); tables uatan.tbl / utan.tbl.  tests/test_libm_trig_vs_glibc.py checks
+//             both bit for bit against the host's libm (2e7 arguments each), tests/test_gpu_device_math2.py on the device.
 #pragma once
 #include "pl_defs.h"
 
@@ -282,6 +285,186 @@ PL_HD double pl_acos(double x) {
     if (k > 0x7ff00000u || (k == 0x7ff00000u && pl_lo(x) != 0u))
         return x + x; // NaN
     return (x - x) / (x - x); // |x| > 1
+}
+
+// ---- atan2 (e_atan2.c __ieee754_atan2, FMA variant) ----------------------------------------------------------------------
+// The fisheye projections call std::atan2(rho, z) (misc/camera_models.cc:1049, 1072, ...).  glibc 2.35's routine has one stage
+// (the multi-precision fall-backs left in 2.34): u = min(|x|, |y|) / max(|x|, |y|) with its rounding error du from an exact product,
+// then the odd polynomial below 1/16 or the expansion around the table point of u's interval of width 2^-8 (uatan.tbl), and the
+// result assembled per quadrant with pi / 2 or pi in two parts.  Restated as the operation sequence of __ieee754_atan2_fma.
+//
+// Domain - a contract, checked bit for bit on the host (tests/test_libm_trig_vs_glibc.py) and on the device
+// (tests/test_gpu_device_math2.py): glibc's bits for every finite x and every finite y != 0 (the cameras call it with
+// y = rho > 1e-8).  y = 0, infinities and NaN go to the plain atan2.  The thresholds, named as in e_atan2.c:
+namespace libm_detail {
+constexpr int32_t ATAN2_EP = 59768832;           // exponent difference (high words) from which y / x is "infinite": 57 << 20
+constexpr double ATAN2_TWO500 = 0x1p500, ATAN2_TWOM500 = 0x1p-500; // |x| or |y| beyond: both are scaled
+constexpr double ATAN2_INV16 = 0.0625;           // u below: polynomial, from it on: table
+constexpr double kAd3 = -0x1.5555555555555p-2, kAd5 = 0x1.99999999997fdp-3, kAd7 = -0x1.24924923f7603p-3,
+                 kAd9 = 0x1.c71c6e5129a3bp-4, kAd11 = -0x1.7458022b13c25p-4, kAd13 = 0x1.375f08b31cbcep-4; // (uatan.tbl d3 .. d13)
+constexpr double kOpi = 0x1.921FB54442D18p1, kOpi1 = 0x1.1A62633145C07p-53; // pi in two parts (kHp0, kHp1: pi / 2)
+PL_HD double atan_poly13(double v) {
+    return pl_fma(pl_fma(pl_fma(pl_fma(pl_fma(kAd13, v, kAd11), v, kAd9), v, kAd7), v, kAd5), v, kAd3);
+}
+PL_HD int atan_row(double u) { // i = (TWO52 + TWO8 * u) - TWO52 as an int, minus 16: the nearest multiple of 1 / 256 (ties to even)
+    return (int)(pl_fma(u, 256.0, 0x1p52) - 0x1p52) - 16;
+}
+} // namespace libm_detail
+
+PL_HD double pl_atan2(double y, double x) {
+    using namespace libm_detail;
+    const uint32_t ux = pl_hi(x), uy = pl_hi(y);
+    if ((ux & 0x7ff00000u) == 0x7ff00000u || (uy & 0x7ff00000u) == 0x7ff00000u || y == 0.0)
+        return atan2(y, x); // outside the domain
+    if (x == 0.0)
+        return (uy & 0x80000000u) ? -kHp0 : kHp0;
+    double ax = (x < 0) ? -x : x, ay = (y < 0) ? -y : y;
+    const int32_t de = (int32_t)(uy & 0x7ff00000u) - (int32_t)(ux & 0x7ff00000u);
+    if (de >= ATAN2_EP)
+        return (y > 0) ? kHp0 : -kHp0;
+    if (de <= -ATAN2_EP) {
+        if (x > 0)
+            return copysign(ay / ax, y);
+        return (y > 0) ? kOpi : -kOpi;
+    }
+    if (ax < ATAN2_TWOM500 || ay < ATAN2_TWOM500) {
+        ax *= ATAN2_TWO500;
+        ay *= ATAN2_TWO500;
+    }
+    if (ax > ATAN2_TWO500 || ay > ATAN2_TWO500) {
+        ax *= ATAN2_TWOM500;
+        ay *= ATAN2_TWOM500;
+    }
+    // u + du = min / max: the quotient, and the quotient of the exact remainder
+    const bool y_small = ay < ax;
+    const double num = y_small ? ay : ax, den = y_small ? ax : ay;
+    const double u = num / den;
+    const double pv = den * u;
+    const double pvv = pl_fma(den, u, -pv);
+    const double du = ((num - pv) - pvv) / den;
+    double z;
+    if (x > 0 && y_small) { // (i) atan(ay / ax)
+        if (u < ATAN2_INV16) {
+            const double v = u * u;
+            z = u + pl_fma(u * v, atan_poly13(v), du);
+        } else {
+            const double *c = kAtanRows[atan_row(u)];
+            const double t3 = u - c[0];
+            const double v = t3 + du;
+            const double dv = (fabs(t3) > fabs(du)) ? ((t3 - v) + du) : ((du - v) + t3);
+            const double p = (v * v) * pl_fma(pl_fma(pl_fma(c[6], v, c[5]), v, c[4]), v, c[3]);
+            z = pl_fma(v, c[2], pl_fma(dv, c[2], p)) + c[1];
+        }
+        return copysign(z, y);
+    }
+    // (ii) x > 0: pi / 2 - atan(ax / ay)   (iii) x < 0, |x| < |y|: pi / 2 + atan(ax / ay)   (iv) x < 0: pi - atan(ay / ax)
+    const bool plus = !(x > 0) && !(ay <= ax);
+    const bool whole = !(x > 0) && (ay <= ax);
+    const double P = whole ? kOpi : kHp0, P1 = whole ? kOpi1 : kHp1;
+    if (u < ATAN2_INV16) {
+        const double v = u * u;
+        const double zz = (u * v) * atan_poly13(v);
+        if (plus) {
+            const double t2 = P + u;
+            const double cor = (P > fabs(u)) ? ((P - t2) + u) : ((u - t2) + P);
+            z = (((cor + P1) + du) + zz) + t2;
+        } else {
+            const double t2 = P - u;
+            const double cor = (P > fabs(u)) ? ((P - t2) - u) : (P - (u + t2));
+            z = (((cor + P1) - du) - zz) + t2;
+        }
+    } else {
+        const double *c = kAtanRows[atan_row(u)];
+        const double v = (u - c[0]) + du;
+        const double p = pl_fma(pl_fma(pl_fma(pl_fma(c[6], v, c[5]), v, c[4]), v, c[3]), v, c[2]);
+        if (plus)
+            z = (P + c[1]) + pl_fma(v, p, P1);
+        else
+            z = (P - c[1]) + pl_fma(-v, p, P1);
+    }
+    return copysign(z, y);
+}
+
+// pl_atan2 out of line: the LM kernels (k_lm<0> sits at 255 VGPRs) reach it only for a fisheye camera; inlined, its registers cost
+// k_lm, k_lm_ordered, k_lm2 and k_lm_cam scratch on EVERY camera (profiles/fisheye_registers.md)
+PL_HD_CALL double pl_atan2_call(double y, double x) { return pl_atan2(y, x); }
+
+// ---- tan (s_tan.c __tan, FMA variant) ---------------------------------------------------------------------------------------
+// The fisheye un-projections call 1.0 / std::tan(theta) (misc/camera_models.cc:1190).  Polynomial up to 0.0608, up to 0.787
+// tan(x0 + z) = f + z' (g + f) / (g - z') around the table point x0 (utan.tbl: f = tan x0, g = cot x0), beyond that the argument is
+// reduced by multiples of pi / 2 in three parts and the same two forms give tan or -cot.
+//
+// Domain - the same kind of contract as pl_cos: glibc's bits for |x| <= TAN_DOMAIN_MAX = 25 (s_tan.c's g4; the Newton result of
+// the un-projection lies in [0, pi) whenever it converges).  Beyond it glibc reduces with more parts of pi / 2, which is not
+// restated: the plain tan answers (finite for finite x, not glibc's last bit); infinities and NaN give NaN as in glibc.
+// The thresholds, named as in utan.h:
+namespace libm_detail {
+constexpr double TAN_G1 = 0x1.b096cp-27;         // |x| up to 1.259e-8: x
+constexpr double TAN_G2 = 0x1.f212dp-5;          // up to 0.0608: polynomial (also of the reduced argument)
+constexpr double TAN_G3 = 0x1.92f1ap-1;          // up to 0.787: table
+constexpr double TAN_DOMAIN_MAX = 25.0;          // g4: up to here the three-part reduction
+constexpr double kTd3 = 0x1.5555555555555p-2, kTd5 = 0x1.11111111107c6p-3, kTd7 = 0x1.ba1ba1cdb8745p-5,
+                 kTd9 = 0x1.664ed49cfc666p-6, kTd11 = 0x1.2385a3cf2e4eap-7; // (utan.h d3 .. d11)
+constexpr double kTe0 = 0x1.5555555554dbdp-2, kTe1 = 0x1.11112e0a6b45fp-3;
+constexpr double kTmp3 = -0x1.cb3b399d747f2p-55; // third part of pi / 2 (mp1, mp2 as in pl_cos)
+PL_HD double tan_poly11(double v) { return pl_fma(pl_fma(pl_fma(pl_fma(kTd11, v, kTd9), v, kTd7), v, kTd5), v, kTd3); }
+// table form: w in (TAN_G2, TAN_G3], dw its low part; cot = false: tan(w + dw), cot = true: cot(w + dw)
+PL_HD double tan_table(double w, double dw, bool cot) {
+    const int i = (int)pl_fma(256.0, w, -15.5);
+    const double z = (w - kTanRows[i][0]) + dw;
+    const double z2 = z * z;
+    const double pz = pl_fma(z * z2, pl_fma(z2, kTe1, kTe0), z);
+    const double fi = kTanRows[i][1], gi = kTanRows[i][2];
+    const double num = (fi + gi) * pz;
+    return cot ? gi - num / (pz + fi) : num / (gi - pz) + fi;
+}
+} // namespace libm_detail
+
+PL_HD double pl_tan(double x) {
+    using namespace libm_detail;
+    if ((pl_hi(x) & 0x7ff00000u) == 0x7ff00000u)
+        return x - x;
+    const double w = (x < 0.0) ? -x : x;
+    if (w <= TAN_G1)
+        return x;
+    if (w <= TAN_G2) {
+        const double x2 = x * x;
+        return pl_fma(x * x2, tan_poly11(x2), x);
+    }
+    if (w <= TAN_G3) {
+        const double s = (x < 0.0) ? -1.0 : 1.0;
+        return tan_table(w, 0.0, false) * s; // (w - x0 + 0.0 = w - x0: it is never -0)
+    }
+    if (!(w <= TAN_DOMAIN_MAX))
+        return tan(x); // outside the domain
+    constexpr double hpinv = 0x1.45F306DC9C883p-1, toint = 0x1.8p52;
+    constexpr double mp1 = 0x1.921FB58000000p0, mp2 = -0x1.DDE973C000000p-27;
+    const double t = pl_fma(x, hpinv, toint);
+    const double xn = t - toint;
+    const uint32_t n = pl_lo(t) & 1u;
+    const double t1 = pl_fma(-xn, mp2, pl_fma(-xn, mp1, x));
+    const double a = pl_fma(-xn, kTmp3, t1);
+    const double da = pl_fma(-xn, kTmp3, t1 - a);
+    const bool neg = a < 0.0;
+    const double ya = neg ? -a : a, yya = neg ? -da : da, sy = neg ? -1.0 : 1.0;
+    if (ya <= TAN_G2) {
+        const double a2 = a * a;
+        const double t2 = pl_fma(a * a2, tan_poly11(a2), da);
+        const double y = a + t2;
+        if (!n)
+            return y;
+        // -cot: 1 / (b + db) in double-double arithmetic (EADD, DIV2)
+        const double b = y;
+        const double db = (fabs(a) > fabs(t2)) ? ((a - b) + t2) : ((t2 - b) + a);
+        const double c = 1.0 / b;
+        const double p = c * b;
+        const double pp = pl_fma(c, b, -p);
+        const double cc = pl_fma(-db, c, ((1.0 - p) - pp) + 0.0) / b;
+        const double z = c + cc;
+        const double zz = (c - z) + cc;
+        return -(zz + z);
+    }
+    return n ? tan_table(ya, yya, true) * -sy : tan_table(ya, yya, false) * sy;
 }
 
 PL_HD double pl_cbrt(double x) {

@@ -15,6 +15,8 @@
 //   misc/camera_models.cc:668-755,919-1032,2704-2726  projections with Jacobians (NULL, SIMPLE_PINHOLE,
 //                                            PINHOLE, OPENCV)
 //   misc/camera_models.cc:579-611,764-913    SIMPLE_RADIAL and RADIAL: radial polynomial, Newton inverse
+//   misc/camera_models.cc:613-662,1044-1201,1517-1652,1664-1790   OPENCV_FISHEYE, SIMPLE_RADIAL_FISHEYE, RADIAL_FISHEYE:
+//                                            atan2 / tan through pl_libm.h, the Newton inverse of the polynomial in theta
 #pragma once
 #include "pl_math.h"
 #include "pl_score.h"
@@ -22,11 +24,28 @@
 namespace pl {
 
 enum LossType : int { LOSS_TRIVIAL = 0, LOSS_TRUNCATED, LOSS_HUBER, LOSS_CAUCHY, LOSS_TRUNCATED_CAUCHY, LOSS_TRUNCATED_LE_ZACH };
-enum CameraId : int { CAM_NULL = -1, CAM_SIMPLE_PINHOLE = 0, CAM_PINHOLE = 1, CAM_SIMPLE_RADIAL = 2, CAM_RADIAL = 3, CAM_OPENCV = 4 };
+enum CameraId : int {
+    CAM_NULL = -1,
+    CAM_SIMPLE_PINHOLE = 0,
+    CAM_PINHOLE = 1,
+    CAM_SIMPLE_RADIAL = 2,
+    CAM_RADIAL = 3,
+    CAM_OPENCV = 4,
+    CAM_OPENCV_FISHEYE = 5,
+    CAM_SIMPLE_RADIAL_FISHEYE = 8,
+    CAM_RADIAL_FISHEYE = 9
+};
 // SIMPLE_RADIAL (f cx cy k1) and RADIAL (f cx cy k1 k2): one focal length, a polynomial in the squared radius
 PL_HD bool camera_is_radial(int model_id) { return model_id == CAM_SIMPLE_RADIAL || model_id == CAM_RADIAL; }
 // models whose un-projection is iterative: max(|x|, |y|) of the un-projected points cannot be bounded from the pixels on the host
-PL_HD bool camera_is_nonlinear(int model_id) { return model_id == CAM_OPENCV || camera_is_radial(model_id); }
+// OPENCV_FISHEYE (fx fy cx cy k1 k2 k3 k4), SIMPLE_RADIAL_FISHEYE (f cx cy k) and RADIAL_FISHEYE (f cx cy k1 k2): the radius in
+// the image is a polynomial in the angle theta to the optical axis
+PL_HD bool camera_is_fisheye(int model_id) {
+    return model_id == CAM_OPENCV_FISHEYE || model_id == CAM_SIMPLE_RADIAL_FISHEYE || model_id == CAM_RADIAL_FISHEYE;
+}
+// parameter layout: fx fy cx cy ... (two focal lengths) or f cx cy ... (one)
+PL_HD bool camera_has_two_focals(int model_id) { return model_id == CAM_PINHOLE || model_id == CAM_OPENCV || model_id == CAM_OPENCV_FISHEYE; }
+PL_HD bool camera_is_nonlinear(int model_id) { return model_id == CAM_OPENCV || camera_is_radial(model_id) || camera_is_fisheye(model_id); }
 
 struct LMOptions {
     uint32_t max_iterations;
@@ -142,6 +161,129 @@ PL_HD double undistort_poly2(double k1, double k2, double rd) {
     return r;
 }
 
+// camera_models.cc:613-662 undistort_theta_poly: theta with rd = theta (1 + sum_k params[k] theta^(2 (k - K0 + 1))), k = K0 ..
+// num_params - 1 (the reference loops to params.size()), by Newton steps (UNDIST_TOL 1e-10, at most UNDIST_MAX_ITER 100) from 0,
+// then - while the residual stays above the tolerance or theta comes out negative - from rd, rd / 2 and 3 rd / 2; what the last
+// start leaves is returned, converged or not.  K0 is a template argument so that every parameter index is a constant.
+template <int K0> PL_HD double undistort_theta_poly(const CameraParams &c, double rd) {
+    double theta = 0.0;
+    for (int start = 0; start < 4; ++start) {
+        theta = (start == 0) ? 0.0 : (start == 1) ? rd : (start == 2) ? 0.5 * rd : 1.5 * rd;
+        double f = 0.0;
+        for (int it = 0; it < 100; ++it) {
+            f = 1.0;
+            double fp = 1.0;
+            const double theta2 = theta * theta;
+            double theta2k = theta2;
+            double factor = 3.0;
+            PL_UNROLL
+            for (int k = K0; k < 12; ++k) {
+                if (k >= c.num_params)
+                    break;
+                const double t = theta2k * c.p[k];
+                f += t;
+                fp += factor * t;
+                theta2k *= theta2;
+                factor += 2.0;
+            }
+            f *= theta;
+            f -= rd;
+            if (fabs(f) < 1e-10)
+                break;
+            theta = theta - f / fp;
+        }
+        if (!(fabs(f) > 1e-10 || theta < 0))
+            break;
+    }
+    return theta;
+}
+// the fisheye models' parameters in one layout: k[j] multiplies theta^(2 j + 3); a coefficient the model lacks is +0.0, which
+// leaves every sum below bit for bit what the reference's shorter expression gives (x + 0.0 = x, theta is finite)
+struct FisheyeParams {
+    double fx, fy, cx, cy, k[4];
+};
+PL_HD FisheyeParams fisheye_params(const CameraParams &c) {
+    // (every parameter is read first and the layout chosen between VALUES: a choice between two elements of c.p would index the array at
+    // run time, which costs the kernels that keep the camera in registers a scratch copy of it)
+    const double p0 = c.p[0], p1 = c.p[1], p2 = c.p[2], p3 = c.p[3], p4 = c.p[4], p5 = c.p[5], p6 = c.p[6], p7 = c.p[7];
+    const bool two = c.model_id == CAM_OPENCV_FISHEYE, k2 = c.model_id == CAM_RADIAL_FISHEYE;
+    FisheyeParams f;
+    f.fx = p0, f.fy = two ? p1 : p0, f.cx = two ? p2 : p1, f.cy = two ? p3 : p2;
+    f.k[0] = two ? p4 : p3, f.k[1] = two ? p5 : (k2 ? p4 : 0.0), f.k[2] = two ? p6 : 0.0, f.k[3] = two ? p7 : 0.0;
+    return f;
+}
+// camera_models.cc:1177-1201, 1628-1652, 1766-1790 followed by hnormalized (camera_models.h:98-102)
+PL_HD void fisheye_unproject(const CameraParams &c, double px, double py, double &ox, double &oy) {
+    const FisheyeParams f = fisheye_params(c);
+    const double ux = (px - f.cx) / f.fx, uy = (py - f.cy) / f.fy;
+    const double rd = sqrt(ux * ux + uy * uy);
+    Vec3 b;
+    if (rd > 1e-8) {
+        const double theta = (c.model_id == CAM_OPENCV_FISHEYE) ? undistort_theta_poly<4>(c, rd) : undistort_theta_poly<3>(c, rd);
+        b.x = ux / rd;
+        b.y = uy / rd;
+        if (fabs(theta - 1.57079632679489661923) > 1e-8)
+            b.z = 1.0 / pl_tan(theta);
+        else
+            b.z = 0.0;
+    } else {
+        b.x = ux;
+        b.y = uy;
+        b.z = sqrt(1 - rd * rd);
+    }
+    b = normalized(b);
+    ox = b.x / b.z;
+    oy = b.y / b.z;
+}
+// camera_models.cc:1044-1157, 1517-1612, 1664-1764: project / project_with_jac of the three models.  J: d(xp)/dZ or nullptr; what
+// the parameter columns need comes back in q = {inv_r, theta, theta2, rd} (theta < 0: the pinhole branch next to the axis).  JAC is a template argument: the residual pass carries none of the Jacobian's registers.
+template <bool JAC> PL_HD void fisheye_project(const CameraParams &c, Vec3 Z, double &ox, double &oy, double *J, double *q) {
+    const FisheyeParams f = fisheye_params(c);
+    const double rho = sqrt(Z.x * Z.x + Z.y * Z.y);
+    if (rho > 1e-8) {
+        const double theta = pl_atan2_call(rho, Z.z);
+        const double theta2 = theta * theta;
+        const double theta4 = theta2 * theta2;
+        const double theta6 = theta2 * theta4;
+        const double theta8 = theta2 * theta6;
+        const double rd = theta * (1.0 + theta2 * f.k[0] + theta4 * f.k[1] + theta6 * f.k[2] + theta8 * f.k[3]);
+        const double inv_r = 1.0 / rho;
+        if constexpr (JAC) {
+            const double drho_dx = Z.x / rho;
+            const double drho_dy = Z.y / rho;
+            const double rho_z2 = rho * rho + Z.z * Z.z;
+            const double dtheta_drho = Z.z / rho_z2;
+            const double dtheta_dz = -rho / rho_z2;
+            const double drd_dtheta = (1.0 + 3.0 * theta2 * f.k[0] + 5.0 * theta4 * f.k[1] + 7.0 * theta6 * f.k[2] + 9.0 * theta8 * f.k[3]);
+            const double drd_dx = drd_dtheta * dtheta_drho * drho_dx;
+            const double drd_dy = drd_dtheta * dtheta_drho * drho_dy;
+            const double drd_dz = drd_dtheta * dtheta_dz;
+            const double dinv_r_drho = -1.0 / (rho * rho);
+            const double dinv_r_dx = dinv_r_drho * drho_dx;
+            const double dinv_r_dy = dinv_r_drho * drho_dy;
+            J[0] = f.fx * (inv_r * rd + Z.x * dinv_r_dx * rd + Z.x * inv_r * drd_dx);
+            J[1] = f.fx * Z.x * (dinv_r_dy * rd + inv_r * drd_dy);
+            J[2] = f.fx * Z.x * inv_r * drd_dz;
+            J[3] = f.fy * Z.y * (dinv_r_dx * rd + inv_r * drd_dx);
+            J[4] = f.fy * (inv_r * rd + Z.y * dinv_r_dy * rd + Z.y * inv_r * drd_dy);
+            J[5] = f.fy * Z.y * inv_r * drd_dz;
+            if (q)
+                q[0] = inv_r, q[1] = theta, q[2] = theta2, q[3] = rd;
+        }
+        ox = f.fx * Z.x * inv_r * rd + f.cx;
+        oy = f.fy * Z.y * inv_r * rd + f.cy;
+    } else { // very close to the principal axis: the distortion is ignored
+        ox = f.fx * Z.x + f.cx;
+        oy = f.fy * Z.y + f.cy;
+        if constexpr (JAC) {
+            J[0] = f.fx, J[1] = 0.0, J[2] = 0.0;
+            J[3] = 0.0, J[4] = f.fy, J[5] = 0.0;
+            if (q)
+                q[0] = 0.0, q[1] = -1.0, q[2] = 0.0, q[3] = 0.0;
+        }
+    }
+}
+
 // pixel -> normalised image plane (camera_models.h:98-102: unit bearing first, then hnormalized)
 PL_HD void camera_unproject(const CameraParams &c, double px, double py, double &ox, double &oy) {
     double u, v;
@@ -187,6 +329,11 @@ PL_HD void camera_unproject(const CameraParams &c, double px, double py, double 
         }
         break;
     }
+    case CAM_OPENCV_FISHEYE:
+    case CAM_SIMPLE_RADIAL_FISHEYE:
+    case CAM_RADIAL_FISHEYE:
+        fisheye_unproject(c, px, py, ox, oy);
+        return;
     default: // CAM_NULL: bearing is (x, y, 1) un-normalised
         ox = px / 1.0;
         oy = py / 1.0;
@@ -231,6 +378,11 @@ PL_HD void camera_project(const CameraParams &c, Vec3 Z, double &ox, double &oy)
         oy = c.p[0] * alpha * v + c.p[2];
         return;
     }
+    case CAM_OPENCV_FISHEYE:
+    case CAM_SIMPLE_RADIAL_FISHEYE:
+    case CAM_RADIAL_FISHEYE:
+        fisheye_project<false>(c, Z, ox, oy, nullptr, nullptr);
+        return;
     default:
         ox = Z.x / Z.z;
         oy = Z.y / Z.z;
@@ -307,6 +459,11 @@ PL_HD void camera_project_jac(const CameraParams &c, Vec3 Z, double &ox, double 
         radial_project_jac(c, Z, ox, oy, J, u, v, r2, alpha);
         return;
     }
+    case CAM_OPENCV_FISHEYE:
+    case CAM_SIMPLE_RADIAL_FISHEYE:
+    case CAM_RADIAL_FISHEYE:
+        fisheye_project<true>(c, Z, ox, oy, J, nullptr);
+        return;
     default: {
         ox = Z.x / Z.z;
         oy = Z.y / Z.z;

@@ -7,6 +7,7 @@
 //                                            step adds the increments to the selected parameters
 //   misc/camera_models.cc:688-698, 739-747, 953-965, 1005-1021   d projection / d parameters (SIMPLE_PINHOLE, PINHOLE, OPENCV)
 //   misc/camera_models.cc:798-814, 877-890                       ... of RADIAL and SIMPLE_RADIAL
+//   misc/camera_models.cc:1110-1155, 1577-1610, 1726-1762         ... of OPENCV_FISHEYE, SIMPLE_RADIAL_FISHEYE, RADIAL_FISHEYE
 //   misc/camera_models.cc get_param_refinement_idx: focal indices, principal-point indices, extra indices in that order
 //
 // PL_HD like pl_refine.h: k_lm_cam (lm_cam.hip) and the host test build (tests/hostmath) run the same functions; the
@@ -23,7 +24,7 @@
 
 namespace pl {
 
-constexpr int kCamMaxParams = 8;                   // OPENCV: fx fy cx cy k1 k2 p1 p2
+constexpr int kCamMaxParams = 8;                   // OPENCV: fx fy cx cy k1 k2 p1 p2, OPENCV_FISHEYE: fx fy cx cy k1 k2 k3 k4
 constexpr int kCamMaxK = 6 + kCamMaxParams;        // 14
 constexpr int kCamRow = 3 + 2 * kCamMaxK;          // 31 doubles per correspondence
 constexpr int kCamMaxEntries = kCamMaxK * (kCamMaxK + 1) / 2 + kCamMaxK; // 119
@@ -43,22 +44,25 @@ PL_HD int camera_refinement_idx(int model_id, int flags, int *idx) {
         break;
     case CAM_SIMPLE_RADIAL:
     case CAM_RADIAL:
+    case CAM_SIMPLE_RADIAL_FISHEYE:
+    case CAM_RADIAL_FISHEYE:
         if (f)
             idx[m++] = 0;
         if (pp)
             idx[m++] = 1, idx[m++] = 2;
         if (ex)
             idx[m++] = 3;
-        if (ex && model_id == CAM_RADIAL)
+        if (ex && (model_id == CAM_RADIAL || model_id == CAM_RADIAL_FISHEYE))
             idx[m++] = 4;
         break;
     case CAM_PINHOLE:
     case CAM_OPENCV:
+    case CAM_OPENCV_FISHEYE:
         if (f)
             idx[m++] = 0, idx[m++] = 1;
         if (pp)
             idx[m++] = 2, idx[m++] = 3;
-        if (ex && model_id == CAM_OPENCV)
+        if (ex && model_id != CAM_PINHOLE)
             idx[m++] = 4, idx[m++] = 5, idx[m++] = 6, idx[m++] = 7;
         break;
     default:
@@ -131,6 +135,43 @@ PL_HD void camera_project_jac_params(const CameraParams &c, Vec3 Z, double &ox, 
         Jc[0][3] = c.p[0] * r2 * u, Jc[1][3] = c.p[0] * r2 * v;
         if (c.model_id == CAM_RADIAL)
             Jc[0][4] = c.p[0] * r2 * r2 * u, Jc[1][4] = c.p[0] * r2 * r2 * v;
+        return;
+    }
+    case CAM_OPENCV_FISHEYE:
+    case CAM_SIMPLE_RADIAL_FISHEYE:
+    case CAM_RADIAL_FISHEYE: {
+        double q[4]; // inv_r, theta, theta2, rd
+        fisheye_project<true>(c, Z, ox, oy, J, q);
+        // (every column index below is a constant: Jc lives in registers)
+        const bool two = c.model_id == CAM_OPENCV_FISHEYE, k2 = c.model_id == CAM_RADIAL_FISHEYE;
+        const bool axis = q[1] < 0; // next to the axis: the pinhole columns, no distortion columns
+        const double inv_r = q[0], theta = q[1], theta2 = q[2], rd = q[3];
+        const double d0 = axis ? Z.x : Z.x * inv_r * rd, d1 = axis ? Z.y : Z.y * inv_r * rd;
+        Jc[0][0] = d0;
+        if (two) {
+            Jc[1][1] = d1;
+            Jc[0][2] = 1.0, Jc[1][3] = 1.0;
+        } else {
+            Jc[1][0] = d1;
+            Jc[0][1] = 1.0, Jc[1][2] = 1.0;
+        }
+        if (axis)
+            return;
+        // params[0] * x(0) * inv_r * theta * theta^(2 j + 2): theta2, theta4 = theta2 theta2, theta6 = theta2 theta4, theta8 = theta2 theta6
+        const double a0 = c.p[0] * Z.x * inv_r * theta, a1 = (two ? c.p[1] : c.p[0]) * Z.y * inv_r * theta;
+        const double theta4 = theta2 * theta2;
+        if (two) {
+            const double theta6 = theta2 * theta4;
+            const double theta8 = theta2 * theta6;
+            Jc[0][4] = a0 * theta2, Jc[1][4] = a1 * theta2;
+            Jc[0][5] = a0 * theta4, Jc[1][5] = a1 * theta4;
+            Jc[0][6] = a0 * theta6, Jc[1][6] = a1 * theta6;
+            Jc[0][7] = a0 * theta8, Jc[1][7] = a1 * theta8;
+        } else {
+            Jc[0][3] = a0 * theta2, Jc[1][3] = a1 * theta2;
+            if (k2)
+                Jc[0][4] = a0 * theta4, Jc[1][4] = a1 * theta4;
+        }
         return;
     }
     default: { // identity camera: no parameters

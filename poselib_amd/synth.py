@@ -209,6 +209,31 @@ def opencv_distort_pixels(pix: np.ndarray, params) -> np.ndarray:
     return np.stack([fx * du + cx, fy * dv + cy], axis=1)
 
 
+def fisheye_distort_pixels(pix: np.ndarray, model: str, params) -> np.ndarray:
+    """Push pinhole pixels through a fisheye camera with the same focal lengths and principal point: model "OPENCV_FISHEYE"
+    (fx, fy, cx, cy, k1 .. k4), "SIMPLE_RADIAL_FISHEYE" (f, cx, cy, k) or "RADIAL_FISHEYE" (f, cx, cy, k1, k2).  The pixel at the
+    angle theta to the optical axis lands at the radius theta (1 + k1 theta^2 + k2 theta^4 + ...) focal lengths from the
+    principal point."""
+    if model == "OPENCV_FISHEYE":
+        fx, fy, cx, cy = params[:4]
+        ks = list(params[4:8])
+    else:
+        fx = fy = params[0]
+        cx, cy = params[1:3]
+        ks = list(params[3:5 if model == "RADIAL_FISHEYE" else 4])
+    u = (pix[:, 0] - cx) / fx
+    v = (pix[:, 1] - cy) / fy
+    r = np.sqrt(u * u + v * v)
+    theta = np.arctan2(r, 1.0)
+    poly = np.ones_like(theta)
+    t2k = theta * theta
+    for k in ks:
+        poly = poly + k * t2k
+        t2k = t2k * theta * theta
+    s = np.where(r > 1e-12, theta * poly / np.maximum(r, 1e-300), 1.0)
+    return np.stack([fx * s * u + cx, fy * s * v + cy], axis=1)
+
+
 def radial_distort_pixels(pix: np.ndarray, params) -> np.ndarray:
     """Push pinhole pixels through a SIMPLE_RADIAL (f, cx, cy, k1) or RADIAL (f, cx, cy, k1, k2) camera with the same
     f, cx, cy - what COLMAP's default models do to an image."""

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Generates poselib_amd/csrc/pl_libm_tables.h: the tables behind pl_cos / pl_acos (pl_libm.h), i.e. behind glibc's
-IBM Accurate Mathematical Library routines (sysdeps/ieee754/dbl-64/s_sin.c, e_asin.c), from FIRST PRINCIPLES:
+"""Generates poselib_amd/csrc/pl_libm_tables.h: the tables behind pl_cos / pl_acos / pl_atan2 / pl_tan (pl_libm.h), i.e.
+behind glibc's IBM Accurate Mathematical Library routines (sysdeps/ieee754/dbl-64/s_sin.c, e_asin.c, e_atan2.c, s_tan.c),
+from FIRST PRINCIPLES:
 
   sin / cos table   x_k = k / 128, k = 0 .. 127:  sin(x_k), cos(x_k) as double-double (hi = nearest double, lo = nearest
                     double of the remainder)                                                     [s_sin.c __sincostab]
@@ -11,6 +12,13 @@ IBM Accurate Mathematical Library routines (sysdeps/ieee754/dbl-64/s_sin.c, e_as
                     higher coefficients are IBM's minimax-adjusted values - constants of the published algorithm that
                     cannot be re-derived - and are read from the libm of this image (glibc 2.35, LGPL-2.1+), see
                     extract_asncs().  Run in a container with that glibc; the generated header is committed.
+  atan table        glibc's uatan.tbl `cij`: per interval (width 2^-8) of [1/16, 1] a point x0 near the interval's middle -
+                    IBM moved it until atan(x0) is a double to 58 bits and more -, atan(x0), and the coefficients c1 .. c5
+                    of the expansion around x0.  atan(x0) and c1 = 1 / (1 + x0^2) are checked against
+                    first principles; the points x0 and c2 .. c5 cannot be re-derived and are read from the libm of this
+                    image, see extract_uatan().                                                  [e_atan2.c, s_atan.c]
+  tan table         glibc's utan.tbl `xfg`: per interval (width 2^-8) of [0.0608, 0.787] a point x0 chosen the same way,
+                    tan(x0) and cot(x0) (checked against first principles), see extract_utan().              [s_tan.c]
 
 The first two are computed with 90-digit decimal arithmetic, nothing is read from a libm for them.
 tests/test_libm_vs_glibc.py then checks pl_cos / pl_acos bit for bit against the host's libm on millions of arguments.
@@ -94,8 +102,100 @@ def extract_asncs(libm_path=GLIBC_LIBM):
     return T
 
 
+def atan_dec(x):
+    n = 0
+    while abs(x) > D(1) / 64:  # atan(x) = 2 atan(x / (1 + sqrt(1 + x^2)))
+        x = x / (1 + (1 + x * x).sqrt())
+        n += 1
+    x2, t, s, k = x * x, x, x, 1
+    while abs(t) > D(10) ** -85:
+        k += 2
+        t = -t * x2
+        s += t / k
+    return s * (2 ** n)
+
+
+UATAN_ROWS, UTAN_ROWS = 241, 186  # i = round(256 u) - 16, u in [1/16, 1]; i = trunc(256 w - 15.5), w in (0.0608, 0.787]
+
+
+def _find_rows(blob, stride, rows, fits):
+    """Every 8-aligned place of `blob` where a table of `rows` rows of `stride` doubles starts whose first row passes
+    fits(row) - glibc's tables carry no symbol in a stripped libm, so they are found by what they must contain."""
+    import struct
+
+    hits = []
+    for o in range(0, len(blob) - 8 * stride * rows + 1, 8):
+        if blob[o + 6:o + 8] != b"\xb0\x3f":  # (top 16 bits of a double in [1/16, 1/8))
+            continue
+        row = struct.unpack_from("<%dd" % stride, blob, o)
+        if fits(row):
+            hits.append(o)
+    return hits
+
+
+def _same_copies(blob, hits, nbytes, what):
+    assert hits, what + " not found"
+    for h in hits[1:]:  # (every translation unit and multiarch variant carries its own copy: they must be the same table)
+        assert blob[h:h + nbytes] == blob[hits[0]:hits[0] + nbytes], what
+    return hits[0]
+
+
+def extract_uatan(libm_path=GLIBC_LIBM):
+    """glibc's uatan.tbl (`cij`, sysdeps/ieee754/dbl-64/uatan.tbl, LGPL-2.1+) as published in the libm of this image
+    (glibc 2.35): rows {x0, atan(x0), c1, c2, c3, c4, c5}.  Found by its first row (x0 within 2e-3 of 1/16, then atan(x0)
+    and 1 / (1 + x0^2)); every row is then checked: x0 within 2^-9 of (i + 16) / 256, atan(x0) the nearest double and in fact
+    within 2^-58 relative, c1 = 1 / (1 + x0^2) within an ulp of first principles."""
+    import math
+    import struct
+
+    blob = open(libm_path, "rb").read()
+
+    def fits(r):
+        return abs(r[0] - 0.0625) < 2e-3 and abs(r[1] - math.atan(r[0])) < 1e-16 and abs(r[2] - 1 / (1 + r[0] * r[0])) < 1e-15
+
+    nb = 8 * 7 * UATAN_ROWS
+    at = _same_copies(blob, _find_rows(blob, 7, UATAN_ROWS, fits), nb, "uatan.tbl")
+    T = struct.unpack("<%dd" % (7 * UATAN_ROWS), blob[at:at + nb])
+    for i in range(UATAN_ROWS):
+        x0, a, c1 = (D(v) for v in T[7 * i:7 * i + 3])
+        assert abs(x0 - D(i + 16) / 256) < D(2) ** -9, i
+        exact = atan_dec(x0)
+        assert float(exact) == T[7 * i + 1] and abs(a - exact) < exact * D(2) ** -58, i
+        e1 = 1 / (1 + x0 * x0)
+        assert abs(c1 - e1) <= e1 * D(2) ** -52, i
+    return T
+
+
+def extract_utan(libm_path=GLIBC_LIBM):
+    """glibc's utan.tbl (`xfg`, sysdeps/ieee754/dbl-64/utan.tbl, LGPL-2.1+) as published in the libm of this image: rows
+    {x0, tan(x0), cot(x0), low part of cot(x0)}; the first three are returned (the path restated here reads no more).  Every
+    row is checked: x0 within 2^-12 of (i + 16) / 256, tan(x0) the nearest double and within 2^-58 relative, cot(x0) the
+    nearest double."""
+    import math
+    import struct
+
+    blob = open(libm_path, "rb").read()
+
+    def fits(r):
+        return (abs(r[0] - 0.0625) < 1e-6 and abs(r[1] - math.tan(r[0])) < 1e-16 and abs(r[2] * r[1] - 1.0) < 1e-15
+                and abs(r[3]) < 1e-15)
+
+    nb = 8 * 4 * UTAN_ROWS
+    at = _same_copies(blob, _find_rows(blob, 4, UTAN_ROWS, fits), nb, "utan.tbl")
+    T = struct.unpack("<%dd" % (4 * UTAN_ROWS), blob[at:at + nb])
+    out = []
+    for i in range(UTAN_ROWS):
+        x0 = D(T[4 * i])
+        assert abs(x0 - D(i + 16) / 256) < D(2) ** -12, i
+        s, c = sin_cos(x0)
+        assert float(s / c) == T[4 * i + 1] and abs(D(T[4 * i + 1]) - s / c) < (s / c) * D(2) ** -58, i
+        assert float(c / s) == T[4 * i + 2], i
+        out += T[4 * i:4 * i + 3]
+    return out
+
+
 def main(out_path):
-    lines = ["// GENERATED by scripts/gen_libm_tables.py - do not edit.  Tables of pl_cos / pl_acos (pl_libm.h), computed from",
+    lines = ["// GENERATED by scripts/gen_libm_tables.py - do not edit.  Tables of pl_cos / pl_acos / pl_atan2 / pl_tan (pl_libm.h), computed from",
              "// first principles with 80-digit arithmetic; see the generator for what each table holds.",
              "#pragma once", "namespace pl {", ""]
     lines.append("// sin(k / 128), cos(k / 128) as double-double: {sin hi, sin lo, cos hi, cos lo}")
@@ -124,6 +224,21 @@ def main(out_path):
         vals.append(float(v))
     for i in range(0, 128, 4):
         lines.append("    " + ", ".join(hexf(v) for v in vals[i:i + 4]) + ",")
+    lines.append("};")
+    lines.append("")
+    lines.append("// glibc 2.35 uatan.tbl `cij` (LGPL-2.1+; constants of the published algorithm, see extract_uatan in the generator):")
+    lines.append("// rows {x0, atan(x0), c1 .. c5} for x0 near (i + 16) / 256, i = 0 .. 240")
+    ua = list(extract_uatan())
+    lines.append("PL_TABLE double kAtanRows[%d][7] = {" % UATAN_ROWS)
+    for i in range(0, len(ua), 7):
+        lines.append("    {" + ", ".join(hexf(v) for v in ua[i:i + 7]) + "},")
+    lines.append("};")
+    lines.append("")
+    lines.append("// glibc 2.35 utan.tbl `xfg` (LGPL-2.1+, see extract_utan): rows {x0, tan(x0), cot(x0)} for x0 near (i + 16) / 256, i = 0 .. 185")
+    ut = list(extract_utan())
+    lines.append("PL_TABLE double kTanRows[%d][3] = {" % UTAN_ROWS)
+    for i in range(0, len(ut), 3):
+        lines.append("    {" + ", ".join(hexf(v) for v in ut[i:i + 3]) + "},")
     lines.append("};")
     lines.append("")
     lines.append("} // namespace pl")
