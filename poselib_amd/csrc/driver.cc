@@ -117,6 +117,7 @@ struct Context {
     // batch scratch
     DevBuf positions, samples, shadow16, lm2_states, lm2_partials, raw_a, raw_b, pts_arena, absmax, models, num_models, slots, num_hyp, part_count, part_score, count, score;
     DevBuf shadow, compact64;
+    DevBuf live, rank, points16; // k_score_mfma: live hypothesis list, its inverse, operand rows of the correspondences
     DevBuf offsets, ctl, blk_best, rec_meta, rec_models, delta, flags;
     DevBuf gen_stage; // workspace of the staged 5-point generator
     DevBuf iota; // iota[i] = i: a device-resident "number of hypotheses" for launches whose count the host knows
@@ -954,6 +955,12 @@ struct RansacRun {
                 s16.out = c->shadow16.p;
                 s16.g16 = sa.pf.g16, s16.c16 = sa.pf.c16, s16.thr = sa.pf.thr;
                 sa.shadow16 = c->shadow16.p;
+                // ... for the hypotheses without a NaN entry only (live list), and the operand rows of the correspondences
+                s16.point_rows = abs16_point_rows(N);
+                HIP_TRY(c->live.ensure(sizeof(uint32_t) * hcap));
+                HIP_TRY(c->rank.ensure(sizeof(uint32_t) * hcap));
+                HIP_TRY(c->points16.ensure(kAbs16PointBytes * s16.point_rows));
+                s16.live = c->live.as<uint32_t>(), s16.rank = c->rank.as<uint32_t>(), s16.points16 = c->points16.p;
             } else if (on_mfma && kind == EST_HOM) { // homography: operands of k_score_mfmah (k_hom16)
                 HIP_TRY(c->shadow16.ensure((hcap + kHom16Pad) * kHom16Bytes));
                 s16.out = c->shadow16.p;
@@ -968,10 +975,15 @@ struct RansacRun {
             }
             HIP_TRY(launch_compact2(ga.num_models, Bl, MAXM, blk_tot, true, c->slots.as<uint32_t>(),
                                     c->offsets.as<uint32_t>(), ga.models, prefilter ? c->shadow.as<float>() : nullptr,
-                                    prefilter ? c->compact64.as<double>() : nullptr, d_ctl, s16, c->stream));
+                                    prefilter ? c->compact64.as<double>() : nullptr, d_ctl, s16, p->ps, c->stream));
             sa.shadow = prefilter ? c->shadow.as<float>() : nullptr;
             sa.compact64 = prefilter ? c->compact64.as<double>() : nullptr;
             sa.num_hyp = &d_ctl->num_hyp;
+            if (s16.live) { // k_score_mfma streams the live list; everything else stays in the hypothesis index space
+                sa.slots = s16.live;
+                sa.num_hyp = &d_ctl->num_live;
+                sa.points16 = s16.points16;
+            }
             sa.hyp_capacity = (uint32_t)hcap;
             sa.thr2 = thr2;
             sa.part_count = c->part_count.as<uint32_t>();
@@ -982,7 +994,8 @@ struct RansacRun {
             HIP_TRY(launch_score(kind, sa, slices, c->stream));
             HIP_TRY(hipEventRecord(c->ev1, c->stream));
             FinalizeArgs fa;
-            fa.num_hyp = sa.num_hyp;
+            fa.num_hyp = &d_ctl->num_hyp;
+            fa.rank = s16.rank;
             fa.hyp_capacity = (uint32_t)hcap;
             fa.chunks = chunks;
             fa.n_points = N;
@@ -997,7 +1010,7 @@ struct RansacRun {
             blk_max = c->blk_best.as<uint32_t>();
             blk_min = reinterpret_cast<double *>(c->blk_best.as<char>() + 1024);
             const uint32_t init_max = (uint32_t)std::min<uint64_t>(best_min_inl, 0xffffffffu);
-            HIP_TRY(launch_finalize_records(fa, sa.slots, ga.models, blk_max, blk_min, init_max, best_min_score,
+            HIP_TRY(launch_finalize_records(fa, c->slots.as<uint32_t>(), ga.models, blk_max, blk_min, init_max, best_min_score,
                                             c->rec_meta.as<RecordMeta>(), c->rec_models.as<double>(), kRecordCap, d_ctl,
                                             c->h_rec_meta.dev<RecordMeta>(), c->h_gather_out.dev<double>(), kRecordFirst,
                                             c->stream));
@@ -2276,7 +2289,7 @@ int pl_score_model(pl_problem *p, const void *model, double max_error, uint64_t 
     return PL_OK;
 }
 
-// Diagnostic: an arbitrary list of models through the STREAMING scorer of the main loop (k_gather_models -> k_shadow16 ->
+// Diagnostic: an arbitrary list of models through the STREAMING scorer of the main loop (k_gather_models -> k_live_list / k_gather_shadow16 ->
 // k_score_mfma / k_score_queue -> k_finalize2), i.e. through the conservative pre-filters, instead of the sequential
 // scorer pl_score_model uses.  Lets tests feed adversarial models / points to the filters on the device.
 int pl_debug_score_stream(pl_problem *p, const void *models, size_t n, double max_error, uint32_t *counts,
@@ -2335,11 +2348,20 @@ int pl_debug_score_stream(pl_problem *p, const void *models, size_t n, double ma
     sa.slots = c->slots.as<uint32_t>();
     sa.shadow16 = nullptr;
     int path = sa.pf.enabled ? 1 : 0;
-    if (on_mfma && p->kind == EST_ABS) {
+    Shadow16Params s16;
+    if (on_mfma && p->kind == EST_ABS) { // as in the main loop: live list, operand rows of the live hypotheses and of the points
+        s16.point_rows = abs16_point_rows(p->n);
         HIP_TRY(c->shadow16.ensure(((size_t)H + kAbs16Pad) * kAbs16Bytes));
-        HIP_TRY(launch_shadow16(&d_ctl->num_hyp, c->shadow.as<float>(), H, sa.pf.g16, sa.pf.c16, sa.pf.thr,
-                                c->shadow16.p, c->stream));
+        HIP_TRY(c->live.ensure(sizeof(uint32_t) * H));
+        HIP_TRY(c->rank.ensure(sizeof(uint32_t) * H));
+        HIP_TRY(c->points16.ensure(kAbs16PointBytes * s16.point_rows));
+        s16.out = c->shadow16.p;
+        s16.g16 = sa.pf.g16, s16.c16 = sa.pf.c16, s16.thr = sa.pf.thr;
+        s16.live = c->live.as<uint32_t>(), s16.rank = c->rank.as<uint32_t>(), s16.points16 = c->points16.p;
+        HIP_TRY(launch_abs16(d_ctl, c->slots.as<uint32_t>(), c->models.as<double>(), H, p->ps, s16, c->stream));
         sa.shadow16 = c->shadow16.p;
+        sa.points16 = s16.points16;
+        sa.slots = s16.live;
         path = 2;
     } else if (on_mfma && p->kind == EST_HOM) {
         HIP_TRY(c->shadow16.ensure(((size_t)H + kHom16Pad) * kHom16Bytes));
@@ -2354,7 +2376,7 @@ int pl_debug_score_stream(pl_problem *p, const void *models, size_t n, double ma
     }
     sa.shadow = c->shadow.as<float>();
     sa.compact64 = c->compact64.as<double>();
-    sa.num_hyp = &d_ctl->num_hyp;
+    sa.num_hyp = s16.live ? &d_ctl->num_live : &d_ctl->num_hyp;
     sa.hyp_capacity = H;
     sa.thr2 = thr2;
     sa.part_count = c->part_count.as<uint32_t>();
@@ -2363,7 +2385,8 @@ int pl_debug_score_stream(pl_problem *p, const void *models, size_t n, double ma
     const uint32_t slices = std::max<uint32_t>(1u, std::min<uint32_t>(1536u / chunks, H));
     HIP_TRY(launch_score(p->kind, sa, slices, c->stream));
     FinalizeArgs fa;
-    fa.num_hyp = sa.num_hyp;
+    fa.num_hyp = &d_ctl->num_hyp;
+    fa.rank = s16.rank;
     fa.hyp_capacity = H;
     fa.chunks = chunks;
     fa.n_points = p->n;

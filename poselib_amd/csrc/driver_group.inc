@@ -30,7 +30,7 @@ constexpr uint32_t kGroupMaxAuto = 256;     // ... which grows with the size of 
 constexpr uint32_t kGroupMaxPoints = 16384; // larger problems gain nothing from grouping
 
 struct GroupLayout { // byte offsets inside one slot of the arena (the same for every slot of a step)
-    size_t positions, delta, flags, models, num_models, slots, offsets, ctl, shadow, compact64, shadow16, part_count,
+    size_t positions, delta, flags, models, num_models, slots, offsets, ctl, shadow, compact64, shadow16, live, rank, points16, part_count,
         part_score, count, score, blk_best, rec_meta, rec_models, gen_stage, pts, pts2, mask, tmp_model, absmax, samples, total;
 };
 
@@ -216,6 +216,10 @@ GroupLayout group_layout(int kind, uint32_t max_n, uint32_t max_B, uint32_t max_
     L.compact64 = take(sizeof(double) * kModelDoubles * hcap);
     L.shadow16 = take(kind == EST_ABS ? (hcap + kAbs16Pad) * kAbs16Bytes
                       : (kind == EST_HOM ? (hcap + kHom16Pad) * kHom16Bytes : (hcap + kSampson16Pad) * kSampson16Bytes));
+    // absolute pose on the matrix cores: live hypothesis list + inverse, operand rows of the correspondences (chunks of 64 P)
+    L.live = take(kind == EST_ABS ? sizeof(uint32_t) * hcap : 0);
+    L.rank = take(kind == EST_ABS ? sizeof(uint32_t) * hcap : 0);
+    L.points16 = take(kind == EST_ABS ? kAbs16PointBytes * chunks * 64 * (size_t)group_points_per_lane(kind) : 0);
     L.part_count = take(sizeof(uint32_t) * chunks * hcap);
     L.part_score = take(sizeof(double) * chunks * hcap);
     L.count = take(sizeof(uint32_t) * hcap);
@@ -809,8 +813,14 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
             // wavefront should see about three units of 64 hypotheses.  The list is shorter than its capacity: P3P fills 1.3 of 4
             // slots per iteration (sized by capacity, a group of 228 default-option problems launched 21 888 workgroups of which
             // two thirds of the wavefronts found no unit: 2.0 ms per step, r4b trace).
+            // Absolute pose on the matrix cores (k_score_mfma): its workgroups read the operand rows of their chunk from the
+            // problem's table instead of splitting them, and on the flagship workload (groups of 16 problems, 8 groups in flight)
+            // about six units per wavefront - half as many, longer-lived workgroups - measured 4.7 % faster than three; still
+            // fewer are faster again there, but leave a small group too few workgroups to fill the device
+            // (profiles/live_hypotheses.md).  The other scorers still split per workgroup and keep their value.
             const size_t hexp = (kind == EST_ABS) ? std::min<size_t>(hcap, (size_t)B + B / 2) : hcap;
-            a.slices = std::max<uint32_t>(1u, std::min<uint32_t>((uint32_t)((hexp / 64 + 23) / 24), 1536u / a.chunks));
+            const size_t units = (a.use_mfma && kind == EST_ABS) ? 48 : 24; // 64-hypothesis units per workgroup (8 wavefronts)
+            a.slices = std::max<uint32_t>(1u, std::min<uint32_t>((uint32_t)((hexp / 64 + units - 1) / units), 1536u / a.chunks));
             if (a.use_mfma && (kind == EST_REL || kind == EST_FUND)) // (every workgroup pays the fp16 split of its chunk: at least ~4 units of 64 hypotheses per wave)
                 a.slices = std::max<uint32_t>(1u, std::min<uint32_t>({a.slices, 512u / a.chunks, B / 2048u + 1u}));
             sa.pts = g.prob.ps;
@@ -820,6 +830,12 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
             sa.compact64 = reinterpret_cast<double *>(slot(i, L.compact64));
             sa.shadow16 = a.use_mfma ? slot(i, L.shadow16) : nullptr;
             sa.num_hyp = &d_ctl->num_hyp;
+            const bool live_list = a.use_mfma && kind == EST_ABS; // k_score_mfma streams the hypotheses without a NaN entry
+            if (live_list) {
+                sa.slots = reinterpret_cast<uint32_t *>(slot(i, L.live));
+                sa.num_hyp = &d_ctl->num_live;
+                sa.points16 = slot(i, L.points16);
+            }
             sa.hyp_capacity = (uint32_t)hcap;
             sa.thr2 = r.thr2;
             sa.part_count = reinterpret_cast<uint32_t *>(slot(i, L.part_count));
@@ -830,7 +846,7 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
             ca.B = B;
             ca.maxm = r.MAXM;
             ca.blk_tot = blk_tot;
-            ca.slots = const_cast<uint32_t *>(sa.slots);
+            ca.slots = reinterpret_cast<uint32_t *>(slot(i, L.slots));
             ca.offsets = reinterpret_cast<uint32_t *>(slot(i, L.offsets));
             ca.models = ga.models;
             ca.shadow = const_cast<float *>(sa.shadow);
@@ -842,11 +858,18 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
                 ca.s16.sampson = (kind == EST_ABS) ? 0 : (kind == EST_HOM ? 2 : 1);
                 if (kind == EST_HOM)
                     ca.s16.thr = sa.pf.h16;
+                if (live_list) {
+                    ca.s16.live = const_cast<uint32_t *>(sa.slots);
+                    ca.s16.rank = reinterpret_cast<uint32_t *>(slot(i, L.rank));
+                    ca.s16.points16 = slot(i, L.points16);
+                    ca.s16.point_rows = a.chunks * 64u * (uint32_t)P;
+                }
             }
             ca.host_offsets = nullptr; // (the one entry a stopping problem needs is fetched after the replay)
             // finalize + records
             RecordsArgs &ra = a.rec;
-            ra.f.num_hyp = sa.num_hyp;
+            ra.f.num_hyp = &d_ctl->num_hyp;
+            ra.f.rank = ca.s16.rank;
             ra.f.hyp_capacity = (uint32_t)hcap;
             ra.f.chunks = a.chunks;
             ra.f.n_points = N;
@@ -855,7 +878,7 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
             ra.f.part_score = sa.part_score;
             ra.f.count = reinterpret_cast<uint32_t *>(slot(i, L.count));
             ra.f.score = reinterpret_cast<double *>(slot(i, L.score));
-            ra.slots = sa.slots;
+            ra.slots = ca.slots;
             ra.models = ga.models;
             ra.blk_max = reinterpret_cast<uint32_t *>(slot(i, L.blk_best));
             ra.blk_min = reinterpret_cast<double *>(slot(i, L.blk_best) + 1024);

@@ -685,7 +685,7 @@ template <int EST, int P> __global__ __launch_bounds__(kQueueThreads) void k_sco
 // apart bound the inlier disc by a triangle (round 6; rounds 2 - 5: the axis-parallel square, four half-planes), and each
 // half-plane is linear in sixteen numbers of the correspondence (X high / low, 1, slack | p X high / low, p, |p|; p = c x + s y),
 // so three v_mfma_f32_32x32x16_f16 - one per direction, 32 hypotheses x 32 correspondences each - deliver the three signed
-// distances of a pair, slack included (operand rows: k_shadow16 in pipeline.hip; bound derivation in pl_prefilter.h).  The
+// distances of a pair, slack included (operand rows: shadow16_one / abs16_point_row in pipeline.hip; bound derivation in pl_prefilter.h).  The
 // vector ALU ORs the three sign bits of a pair (one v_or3) and shifts the result into a per-lane, per-hypothesis bit field over
 // the point groups (v_alignbit): 2 instructions per pair (round 2: 3, round 1: 4); the triangle lets 1.3 x the square's pairs
 // through to the exact pass.  After the PG tiles of a group of 32 hypotheses the bit fields are expanded into the wave's LDS
@@ -784,11 +784,14 @@ __device__ __forceinline__ void mfma_drain(const uint16_t *queue, uint32_t first
     }
 }
 
+// The hypothesis stream of this kernel is the LIVE list (pipeline.hip compact2_body): `slots` = record index per live position,
+// *num_hyp_ptr = its length, shadow16 and the partials are indexed by live position; k_finalize2 maps them back (rank[]).
 template <int PG>
 __device__ __forceinline__ void score_mfma_body(const PointSet &pts, const uint4 *__restrict__ shadow16,
+                                                const uint4 *__restrict__ points16,
                                                 const double *__restrict__ models, const uint32_t *__restrict__ slots,
                                                 const uint32_t *__restrict__ num_hyp_ptr, uint32_t hyp_capacity,
-                                                double thr2, const PrefilterArgs &pf, uint32_t *__restrict__ part_count,
+                                                double thr2, uint32_t *__restrict__ part_count,
                                                 double *__restrict__ part_score, uint32_t slice, uint32_t chunk,
                                                 uint32_t nslices) {
     constexpr int kWaves = kMfmaThreads / 64;
@@ -811,28 +814,19 @@ __device__ __forceinline__ void score_mfma_body(const PointSet &pts, const uint4
 #pragma unroll
     for (int g = 0; g < PG; ++g)
         validbits |= (chunk * NPW + g * 32 + col < pts.n) ? (1u << (PG - 1 - g)) : 0u;
-    // one thread per correspondence of the chunk: fp64 copy for the exact pass, fp16 operands for the filter
-    // (pl_prefilter.h pf16_abs_point: the host test build runs the same function)
+    // one thread per correspondence of the chunk: fp64 copy for the exact pass; the fp16 operands of the filter come ready
+    // from the problem's table (pipeline.hip abs16_point_row: built once per batch step, not once per workgroup - invalid
+    // columns included)
+    const uint4 *const prow = points16 + (size_t)chunk * NPW * 4;
     for (uint32_t j = threadIdx.x; j < (uint32_t)NPW; j += kMfmaThreads) {
         const uint32_t i = chunk * NPW + j;
-        const bool valid = i < pts.n;
-        const uint32_t ic = valid ? i : 0u;
-        double x[5];
+        const uint32_t ic = i < pts.n ? i : 0u;
 #pragma unroll
-        for (int d = 0; d < 5; ++d) {
-            x[d] = pts.a[d][ic];
-            s_pts[d][j] = x[d];
-        }
-        Abs16Point o;
-        pf16_abs_point(x[0], x[1], x[2], x[3], x[4], valid, pf.g16, pf.thr, o);
-        auto row = [](const uint16_t *h) {
-            return make_uint4((uint32_t)h[0] | ((uint32_t)h[1] << 16), (uint32_t)h[2] | ((uint32_t)h[3] << 16),
-                              (uint32_t)h[4] | ((uint32_t)h[5] << 16), (uint32_t)h[6] | ((uint32_t)h[7] << 16));
-        };
-        s_b[0][j >> 5][j & 31] = row(o.b0);
+        for (int d = 0; d < 5; ++d)
+            s_pts[d][j] = pts.a[d][ic];
 #pragma unroll
-        for (int d = 0; d < kAbs16Dirs; ++d)
-            s_b[1 + d][j >> 5][j & 31] = row(o.bp[d]);
+        for (int r = 0; r < 1 + kAbs16Dirs; ++r)
+            s_b[r][j >> 5][j & 31] = prow[(size_t)j * 4 + r];
     }
     if (threadIdx.x == 0)
         s_next_unit = 0;
@@ -1006,18 +1000,19 @@ __device__ __forceinline__ void score_mfma_body(const PointSet &pts, const uint4
 // amdgpu_waves_per_eu(4, 8): wavefronts per SIMD the register allocation aims at (48 accumulators + 16 bit fields + operands)
 template <int PG>
 __global__ __launch_bounds__(kMfmaThreads) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_score_mfma(PointSet pts, const uint4 *__restrict__ shadow16,
+                                                               const uint4 *__restrict__ points16,
                                                                const double *__restrict__ models,
                                                                const uint32_t *__restrict__ slots,
                                                                const uint32_t *__restrict__ num_hyp_ptr,
-                                                               uint32_t hyp_capacity, double thr2, PrefilterArgs pf,
+                                                               uint32_t hyp_capacity, double thr2,
                                                                uint32_t *__restrict__ part_count,
                                                                double *__restrict__ part_score,
                                                                uint32_t *__restrict__ tickets) {
     (void)tickets;
     uint32_t slice, chunk;
     slice_chunk_of_workgroup(gridDim.x, gridDim.y, slice, chunk);
-    score_mfma_body<PG>(pts, shadow16, models, slots, num_hyp_ptr, hyp_capacity, thr2, pf, part_count, part_score, slice, chunk,
-                        gridDim.x);
+    score_mfma_body<PG>(pts, shadow16, points16, models, slots, num_hyp_ptr, hyp_capacity, thr2, part_count, part_score, slice,
+                        chunk, gridDim.x);
 }
 template <int PG>
 __global__ __launch_bounds__(kMfmaThreads) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_score_mfma_g(const GroupArgs *ga) {
@@ -1026,8 +1021,8 @@ __global__ __launch_bounds__(kMfmaThreads) __attribute__((amdgpu_waves_per_eu(4,
     if (!g.active || !g.use_mfma || !slice_chunk_of_workgroup(g.slices, g.chunks, slice, chunk))
         return;
     const ScoreArgs &a = g.score;
-    score_mfma_body<PG>(a.pts, static_cast<const uint4 *>(a.shadow16), a.models, a.slots, a.num_hyp, a.hyp_capacity, a.thr2,
-                        a.pf, a.part_count, a.part_score, slice, chunk, g.slices);
+    score_mfma_body<PG>(a.pts, static_cast<const uint4 *>(a.shadow16), static_cast<const uint4 *>(a.points16), a.models, a.slots,
+                        a.num_hyp, a.hyp_capacity, a.thr2, a.part_count, a.part_score, slice, chunk, g.slices);
 }
 
 // ---- two-view Sampson scores: the pre-filter on the matrix cores ----------------------------------------------------
@@ -3070,6 +3065,12 @@ bool score_uses_mfma(int est, uint32_t n_points, const PrefilterArgs &pf) {
         return pf.t16 > 0.f; // (coordinates bounded by 8, threshold in range: make_prefilter_args)
     return pf.h16 > 0.f;     // homography: the same conditions
 }
+uint32_t abs16_point_rows(uint32_t n) { // chunks x (64 P = 32 PG) correspondences of k_score_mfma<2 P>
+    uint32_t c;
+    int P;
+    score_shape(EST_ABS, n, true, true, c, P);
+    return c * 64u * (uint32_t)P;
+}
 uint32_t score_chunks(int est, uint32_t n, bool streaming, bool mfma) {
     uint32_t c;
     int P;
@@ -3145,11 +3146,14 @@ static hipError_t launch_score_est(const ScoreArgs &a, uint32_t slices, hipStrea
                                                         std::max<uint32_t>(1u, 512u / chunks));
             const dim3 mgrid(xcd_slices(mslices), chunks);
             const dim3 mblock(kMfmaThreads);
+            if (!a.points16)
+                return hipErrorInvalidValue;
 #define PL_M_CASE(PP)                                                                                                  \
     case PP:                                                                                                           \
-        k_score_mfma<2 * PP><<<mgrid, mblock, 0, stream>>>(a.pts, static_cast<const uint4 *>(a.shadow16), a.models,      \
-                                                         a.slots, a.num_hyp, a.hyp_capacity, a.thr2, pf,               \
-                                                         a.part_count, a.part_score, a.tickets);                       \
+        k_score_mfma<2 * PP><<<mgrid, mblock, 0, stream>>>(a.pts, static_cast<const uint4 *>(a.shadow16),                \
+                                                         static_cast<const uint4 *>(a.points16), a.models, a.slots,    \
+                                                         a.num_hyp, a.hyp_capacity, a.thr2, a.part_count, a.part_score, \
+                                                         a.tickets);                                                   \
         break;
             switch (P) {
                 PL_M_CASE(1)

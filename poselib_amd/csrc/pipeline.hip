@@ -19,6 +19,7 @@
 //       iff count > max(previous counts) or score < min(previous scores).  Records (typically O(log H)) are
 //       appended with their 128-byte model so the host fetches a few KB instead of every score.
 #include "pl_kernels.h"
+#include "pl_device.h"
 #include "pl_refine.h"
 #include "pl_sampler.h"
 #include <algorithm>
@@ -416,65 +417,110 @@ __global__ __launch_bounds__(1024) void k_count_blocks(const uint32_t *num_model
     }
 }
 
+// live / rank (optional, absolute pose on the matrix cores): next to the hypothesis list `slots` - which stays what it is, NaN
+// models included: count[], score[], k_records and the host replay live in that index space - the same scan yields the list of
+// the hypotheses WITHOUT the NaN flag, in the same order (live[r] = record index of the r-th of them), its inverse rank[k] and
+// its length ctl->num_live.  k_score_mfma runs over that list only: a NaN pose has no inliers whatever the points are, and a
+// row of the matrix-core filter costs the same whether it can have one or not (12.8 % of the P3P hypotheses of a 70 % outlier
+// problem).  The position of a block's first live hypothesis comes from the generators' NaN counts per block of 1024
+// iterations (second table behind blk_tot), the positions inside the block from the records' flags: a stable compaction, no
+// atomics - which hypotheses share a unit of the scorer does not depend on scheduling.
 __device__ __forceinline__ void compact2_body(const uint32_t *num_models, uint32_t B, int maxm,
                                               const uint32_t *blk_tot, uint32_t *slots, uint32_t *offsets,
-                                              BatchCtl *ctl, uint32_t nblocks, uint32_t *host_offsets) {
-    __shared__ uint32_t wt[16], wo[16], wb[16], wn[16];
-    __shared__ uint32_t s_base;
+                                              BatchCtl *ctl, uint32_t nblocks, uint32_t *host_offsets,
+                                              const double *models, uint32_t *live, uint32_t *rank) {
+    __shared__ uint32_t wt[16], wo[16], wb[16], wn[16], wnb[16], wl[16], wlo[16];
+    __shared__ uint32_t s_base, s_live_base;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     // models of the blocks before this one (and, in the last block, the generators' NaN-model counts: second table behind
     // blk_tot, statistics): all lanes fetch, one wave sum each - one lane walking the table paid ~1 us per entry
-    uint32_t before = 0, nan_part = 0;
-    for (uint32_t j = threadIdx.x; j < blockIdx.x; j += 1024u)
+    uint32_t before = 0, nan_part = 0, nan_before = 0;
+    for (uint32_t j = threadIdx.x; j < blockIdx.x; j += 1024u) {
         before += blk_tot[j];
+        if (live)
+            nan_before += blk_tot[nblocks + j];
+    }
     const bool last = blockIdx.x == nblocks - 1;
     if (last)
         for (uint32_t j = threadIdx.x; j < nblocks; j += 1024u)
             nan_part += blk_tot[nblocks + j];
     before = wsum_u32(before);
     nan_part = wsum_u32(nan_part);
+    nan_before = wsum_u32(nan_before);
     const uint32_t i = blockIdx.x * 1024 + threadIdx.x;
     const uint32_t nm = (i < B) ? num_models[i] : 0u;
     const uint32_t inc = wscan_add(nm, lane);
-    if (lane == 63)
+    // bit m: model m of this iteration carries the NaN flag (maxm <= 40)
+    // (the first four flags - all an absolute-pose iteration has - as independent loads: one trip to memory, not nm)
+    uint64_t nanbits = 0;
+    if (live) {
+        const double *rec0 = models + (size_t)i * (uint32_t)maxm * kModelStride;
+        bool f[4];
+#pragma unroll
+        for (uint32_t m = 0; m < 4u; ++m)
+            f[m] = m < nm && record_is_nan(rec0 + (size_t)m * kModelStride);
+#pragma unroll
+        for (uint32_t m = 0; m < 4u; ++m)
+            nanbits |= f[m] ? (1ull << m) : 0ull;
+        for (uint32_t m = 4; m < nm; ++m)
+            nanbits |= record_is_nan(rec0 + (size_t)m * kModelStride) ? (1ull << m) : 0ull;
+    }
+    const uint32_t nl = nm - (uint32_t)__popcll(nanbits);
+    const uint32_t inc_l = live ? wscan_add(nl, lane) : 0u;
+    if (lane == 63) {
         wt[wave] = inc;
+        wl[wave] = inc_l;
+    }
     if (lane == 0) {
         wb[wave] = before;
         wn[wave] = nan_part;
+        wnb[wave] = nan_before;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        uint32_t s = 0, b = 0, nan = 0;
+        uint32_t s = 0, b = 0, nan = 0, nb = 0, sl = 0;
         for (int w = 0; w < 16; ++w) {
             wo[w] = s;
+            wlo[w] = sl;
             s += wt[w];
+            sl += wl[w];
             b += wb[w];
             nan += wn[w];
+            nb += wnb[w];
         }
         s_base = b;
+        s_live_base = b - nb;
         if (last) {
             ctl->num_hyp = b + s;
             ctl->nan_hyp = nan;
+            if (live)
+                ctl->num_live = b - nb + sl;
         }
     }
     __syncthreads();
     if (i < B) {
         const uint32_t o = s_base + wo[wave] + inc - nm;
+        uint32_t lo = s_live_base + wlo[wave] + inc_l - nl;
         offsets[i] = o;
         if (host_offsets)
             host_offsets[i] = o;
         for (uint32_t m = 0; m < nm; ++m) {
             const uint32_t slot = i * (uint32_t)maxm + m;
             slots[o + m] = slot;
+            if (live) {
+                const bool is_nan = (nanbits >> m) & 1ull;
+                rank[o + m] = is_nan ? kNoRank : lo;
+                if (!is_nan)
+                    live[lo++] = slot;
+            }
         }
     }
 }
 
 __global__ __launch_bounds__(1024) void k_compact2(const uint32_t *num_models, uint32_t B, int maxm,
                                                    const uint32_t *blk_tot, uint32_t *slots, uint32_t *offsets,
-                                                   const double *models, float *shadow_compact, double *compact64,
-                                                   BatchCtl *ctl) {
-    compact2_body(num_models, B, maxm, blk_tot, slots, offsets, ctl, gridDim.x, nullptr);
+                                                   const double *models, uint32_t *live, uint32_t *rank, BatchCtl *ctl) {
+    compact2_body(num_models, B, maxm, blk_tot, slots, offsets, ctl, gridDim.x, nullptr, models, live, rank);
 }
 __global__ __launch_bounds__(1024) void k_compact2_g(const GroupArgs *ga) {
     const GroupArgs &g = ga[blockIdx.z];
@@ -482,7 +528,42 @@ __global__ __launch_bounds__(1024) void k_compact2_g(const GroupArgs *ga) {
     if (!g.active || blockIdx.x >= nb)
         return;
     compact2_body(g.comp.num_models, g.comp.B, g.comp.maxm, g.comp.blk_tot, g.comp.slots, g.comp.offsets, g.comp.ctl, nb,
-                  g.comp.host_offsets);
+                  g.comp.host_offsets, g.comp.models, g.comp.s16.live, g.comp.s16.rank);
+}
+
+// The same for a list the host wrote (pl_debug_score_stream: `H` records in list order `slots`, no generator counts): one
+// workgroup walks the list in tiles of 1024.
+__global__ __launch_bounds__(1024) void k_live_list(BatchCtl *ctl, const uint32_t *slots, const double *models, uint32_t *live,
+                                                    uint32_t *rank) {
+    __shared__ uint32_t wl[16];
+    __shared__ uint32_t s_base;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t H = ctl->num_hyp;
+    if (threadIdx.x == 0)
+        s_base = 0;
+    __syncthreads();
+    for (uint32_t k0 = 0; k0 < H; k0 += 1024u) {
+        const uint32_t k = k0 + threadIdx.x;
+        const uint32_t slot = k < H ? slots[k] : 0u;
+        const uint32_t alive = (k < H && !record_is_nan(models + (size_t)slot * kModelStride)) ? 1u : 0u;
+        const uint32_t inc = wscan_add(alive, lane);
+        if (lane == 63)
+            wl[wave] = inc;
+        __syncthreads();
+        uint32_t r = s_base + inc - alive;
+        for (int w = 0; w < wave; ++w)
+            r += wl[w];
+        if (k < H)
+            rank[k] = alive ? r : kNoRank;
+        if (alive)
+            live[r] = slot;
+        __syncthreads();
+        if (threadIdx.x == 1023)
+            s_base = r + alive;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0)
+        ctl->num_live = s_base;
 }
 
 // Hypothesis-ordered copies of the records for the streaming scorer: 12 lanes move the 192 bytes of one record
@@ -521,10 +602,14 @@ __device__ __forceinline__ void finalize2_body(const FinalizeArgs &f, uint32_t *
     for (uint32_t k = k0 + threadIdx.x; k < k1; k += 256) {
         uint32_t c = 0;
         double s = 0.0;
-        for (uint32_t ch = 0; ch < f.chunks; ++ch) {
-            c += f.part_count[(size_t)ch * f.hyp_capacity + k];
-            s += f.part_score[(size_t)ch * f.hyp_capacity + k];
-        }
+        // column of the hypothesis' partials: k, or its position in the live list.  A NaN model has none: no inliers, i.e.
+        // count 0 and score n thr^2, the very bits the scorer's all-outlier row gave
+        const uint32_t col = f.rank ? f.rank[k] : k;
+        if (col != kNoRank)
+            for (uint32_t ch = 0; ch < f.chunks; ++ch) {
+                c += f.part_count[(size_t)ch * f.hyp_capacity + col];
+                s += f.part_score[(size_t)ch * f.hyp_capacity + col];
+            }
         const double sc = s + (double)(f.n_points - c) * f.thr2; // utils.cc:63 / :193-197
         f.count[k] = c;
         f.score[k] = sc;
@@ -690,51 +775,68 @@ __global__ __launch_bounds__(256) void k_records_g(const GroupArgs *ga) {
 //     block 1 = (R_20, R_21, R_22, R_20, R_21, R_22, t_2, Tm)
 // g = 2^-16 max|t_c| + c16 is the hypothesis' share of the slack (+inf: evaluate every point exactly, -inf: NaN model, no
 // inliers; the other entries are zero then), Tm = 2^-10 (1 + 2^-6) max|t_c| the factor of |p| (pl_prefilter.h).
-// shadow_of(k): the fp32 shadow (16 floats) of hypothesis k < H
+// eight fp16 bit patterns = one 16-byte operand row
+__device__ __forceinline__ uint4 half8_row(const uint16_t *h) {
+    return make_uint4((uint32_t)h[0] | ((uint32_t)h[1] << 16), (uint32_t)h[2] | ((uint32_t)h[3] << 16),
+                      (uint32_t)h[4] | ((uint32_t)h[5] << 16), (uint32_t)h[6] | ((uint32_t)h[7] << 16));
+}
+// Rows exist for the LIVE hypotheses only (compact2_body), indexed by live position r: a NaN model never reaches the scorer.
+// shadow_of(r): the fp32 shadow (16 floats) of live hypothesis r < H = ctl->num_live
 template <typename ShadowOf>
-__device__ __forceinline__ void shadow16_one(uint32_t k, uint32_t H, ShadowOf shadow_of, float c16, float thr,
+__device__ __forceinline__ void shadow16_one(uint32_t r, uint32_t H, ShadowOf shadow_of, float c16, float thr,
                                              uint4 *__restrict__ out) {
-    if (k >= ((H + 31u) & ~31u))
-        return; // groups of 32 past the last hypothesis are never read
+    if (r >= ((H + 31u) & ~31u))
+        return; // groups of 32 past the last live hypothesis are never read
     Abs16Model m;
-    pf16_abs_model(k < H ? shadow_of(k) : nullptr, c16, thr, m); // (pl_prefilter.h: the host test build runs the same)
-    uint4 *dst = out + (size_t)k * 4;
-    auto row = [](const uint16_t *h) {
-        return make_uint4((uint32_t)h[0] | ((uint32_t)h[1] << 16), (uint32_t)h[2] | ((uint32_t)h[3] << 16),
-                          (uint32_t)h[4] | ((uint32_t)h[5] << 16), (uint32_t)h[6] | ((uint32_t)h[7] << 16));
-    };
+    pf16_abs_model(r < H ? shadow_of(r) : nullptr, c16, thr, m); // (pl_prefilter.h: the host test build runs the same)
+    uint4 *dst = out + (size_t)r * 4;
 #pragma unroll
     for (int d = 0; d < kAbs16Dirs; ++d)
-        dst[d] = row(m.d[d]);
-    dst[3] = row(m.b1);
+        dst[d] = half8_row(m.d[d]);
+    dst[3] = half8_row(m.b1);
 }
 
-__global__ __launch_bounds__(256) void k_shadow16(const uint32_t *num_hyp, const float *__restrict__ shadow,
-                                                  uint32_t capacity16, float g16, float c16, float thr,
-                                                  uint4 *__restrict__ out) {
-    const uint32_t k = blockIdx.x * 256 + threadIdx.x;
-    if (k >= capacity16)
-        return;
-    (void)g16;
-    shadow16_one(k, *num_hyp, [&](uint32_t kk) { return shadow + (size_t)kk * 16; }, c16, thr, out);
+// The B operands of the same instructions - the correspondence side, pl_prefilter.h pf16_abs_point - depend on the problem's
+// points and the threshold alone, and k_score_mfma needs those of a chunk in every one of its workgroups (96 hypothesis slices
+// x 16 chunks per problem of the flagship workload: twelve fp16 splits and an fp64 square root per correspondence, 1536 times
+// over).  They are built HERE, once per launch of the operand kernel, i.e. once per batch step and with that step's threshold -
+// nothing is kept between steps, so no table can outlive the threshold it was built for -, as four rows of 16 B per
+// correspondence: [X_hi, X_lo, 1, w][second k block of direction 0][1][2].  Row i >= n: an invalid column (zero operands,
+// slack 65504), exactly what the scorer's prologue used to compute for it.
+__device__ __forceinline__ void abs16_point_row(const PointSet &pts, uint32_t i, float g16, float thr, uint4 *__restrict__ out) {
+    const bool valid = i < pts.n;
+    const uint32_t ic = valid ? i : 0u;
+    Abs16Point o;
+    pf16_abs_point(pts.a[0][ic], pts.a[1][ic], pts.a[2][ic], pts.a[3][ic], pts.a[4][ic], valid, g16, thr, o);
+    uint4 *dst = out + (size_t)i * 4;
+    dst[0] = half8_row(o.b0);
+#pragma unroll
+    for (int d = 0; d < kAbs16Dirs; ++d)
+        dst[1 + d] = half8_row(o.bp[d]);
 }
 
-// k_gather_models and k_shadow16 as ONE launch (both only depend on k_compact2's hypothesis list): blocks below
-// `gather_blocks` copy the records, the blocks above build the fp16 operand blocks straight from the records' shadows.
+// k_gather_models and the fp16 operands as ONE launch (both only depend on k_compact2's lists): blocks below `gather_blocks`
+// copy the records, the next `shadow_blocks` build the operand rows of the live hypotheses straight from the records' shadows,
+// the blocks above those the operand rows of the correspondences.
 __global__ __launch_bounds__(256) void k_gather_shadow16(BatchCtl *ctl, const uint32_t *slots, const double *models,
                                                          float *shadow_compact, double *compact64,
-                                                         uint32_t gather_blocks, uint32_t capacity16, float g16, float c16,
-                                                         float thr, uint4 *__restrict__ out16) {
+                                                         uint32_t gather_blocks, uint32_t shadow_blocks, PointSet pts,
+                                                         Shadow16Params s16) {
     if (blockIdx.x < gather_blocks) {
         gather_one(ctl, slots, models, shadow_compact, compact64, (uint64_t)blockIdx.x * 256 + threadIdx.x);
         return;
     }
-    const uint32_t k = (blockIdx.x - gather_blocks) * 256 + threadIdx.x;
-    if (k >= capacity16)
+    if (blockIdx.x >= gather_blocks + shadow_blocks) {
+        const uint32_t i = (blockIdx.x - gather_blocks - shadow_blocks) * 256 + threadIdx.x;
+        if (i < s16.point_rows)
+            abs16_point_row(pts, i, s16.g16, s16.thr, static_cast<uint4 *>(s16.points16));
         return;
-    shadow16_one(k, ctl->num_hyp,
-                 [&](uint32_t kk) { return reinterpret_cast<const float *>(models + (size_t)slots[kk] * kModelStride + kShadowOff); },
-                 c16, thr, out16);
+    }
+    const uint32_t r = (blockIdx.x - gather_blocks) * 256 + threadIdx.x;
+    const uint32_t *live = s16.live;
+    shadow16_one(r, ctl->num_live,
+                 [&](uint32_t rr) { return reinterpret_cast<const float *>(models + (size_t)live[rr] * kModelStride + kShadowOff); },
+                 s16.c16, s16.thr, static_cast<uint4 *>(s16.out));
 }
 
 // Operands of k_score_mfma2 (Sampson scores on the matrix cores): 96 B per hypothesis = six 16-byte k blocks
@@ -841,13 +943,17 @@ __global__ __launch_bounds__(256) void k_gather_shadow16_g(const GroupArgs *ga, 
             sampson16_one(k, H, capp, g.comp.slots, g.comp.models, static_cast<uint4 *>(g.comp.s16.out));
         return;
     }
+    // absolute pose: the operand rows of the correspondences (abs16_point_row) and of the live hypotheses
+    for (uint32_t i = k0; i < g.comp.s16.point_rows; i += nb * 256)
+        abs16_point_row(g.score.pts, i, g.comp.s16.g16, g.comp.s16.thr, static_cast<uint4 *>(g.comp.s16.points16));
     // (shadow16_one fills the last group of 32 up and ignores everything behind it)
-    const uint32_t end = (uint32_t)std::min<uint64_t>((cap + 31u) & ~31ull, ((uint64_t)H + 31u) & ~31ull);
-    const uint32_t *slots = g.comp.slots;
+    const uint32_t HL = g.comp.ctl->num_live;
+    const uint32_t end = (uint32_t)std::min<uint64_t>((cap + 31u) & ~31ull, ((uint64_t)HL + 31u) & ~31ull);
+    const uint32_t *live = g.comp.s16.live;
     const double *models = g.comp.models;
-    for (uint32_t k = k0; k < end; k += nb * 256)
-        shadow16_one(k, H,
-                     [&](uint32_t kk) { return reinterpret_cast<const float *>(models + (size_t)slots[kk] * kModelStride + kShadowOff); },
+    for (uint32_t r = k0; r < end; r += nb * 256)
+        shadow16_one(r, HL,
+                     [&](uint32_t rr) { return reinterpret_cast<const float *>(models + (size_t)live[rr] * kModelStride + kShadowOff); },
                      g.comp.s16.c16, g.comp.s16.thr, static_cast<uint4 *>(g.comp.s16.out));
 }
 
@@ -982,13 +1088,14 @@ hipError_t launch_undistort(const double *in, uint32_t n, const CameraParams &ca
 }
 
 // ------------------------------------------------------------------------------------ launchers
-hipError_t launch_shadow16(const uint32_t *num_hyp, const float *shadow_compact, uint32_t hyp_capacity, float g16,
-                           float c16, float thr, void *shadow16, hipStream_t stream) {
-    const uint32_t cap8 = (hyp_capacity + 31u) & ~31u;
-    if (cap8 == 0)
-        return hipSuccess;
-    k_shadow16<<<dim3((cap8 + 255) / 256), dim3(256), 0, stream>>>(num_hyp, shadow_compact, cap8, g16, c16, thr,
-                                                                   static_cast<uint4 *>(shadow16));
+hipError_t launch_abs16(BatchCtl *ctl, const uint32_t *slots, const double *models, uint32_t capacity, const PointSet &pts,
+                        const Shadow16Params &s16, hipStream_t stream) {
+    if (!s16.out || !s16.live || !s16.rank || !s16.points16)
+        return hipErrorInvalidValue;
+    k_live_list<<<dim3(1), dim3(1024), 0, stream>>>(ctl, slots, models, s16.live, s16.rank);
+    const uint32_t sblocks = (((capacity + 31u) & ~31u) + 255) / 256, pblocks = (s16.point_rows + 255) / 256;
+    if (sblocks + pblocks)
+        k_gather_shadow16<<<dim3(sblocks + pblocks), dim3(256), 0, stream>>>(ctl, slots, models, nullptr, nullptr, 0u, sblocks, pts, s16);
     return hipGetLastError();
 }
 
@@ -1030,12 +1137,16 @@ hipError_t launch_sample_positions(int K, uint64_t seed, uint64_t pos_base, uint
 
 hipError_t launch_compact2(const uint32_t *num_models, uint32_t B, int maxm, uint32_t *blk_tot, bool counted, uint32_t *slots,
                            uint32_t *offsets, const double *models, float *shadow_compact, double *compact64,
-                           BatchCtl *ctl, const Shadow16Params &s16, hipStream_t stream) {
+                           BatchCtl *ctl, const Shadow16Params &s16, const PointSet &pts, hipStream_t stream) {
     const uint32_t nb = (B + 1023) / 1024;
+    const bool abs16 = s16.out && s16.sampson == 0;
+    // (the live list starts every block at the generators' NaN counts: k_count_blocks does not count those)
+    if (abs16 && (!counted || !s16.live || !s16.rank || !s16.points16))
+        return hipErrorInvalidValue;
     if (!counted)
         k_count_blocks<<<dim3(nb), dim3(1024), 0, stream>>>(num_models, B, blk_tot);
-    k_compact2<<<dim3(nb), dim3(1024), 0, stream>>>(num_models, B, maxm, blk_tot, slots, offsets, models, shadow_compact,
-                                                    compact64, ctl);
+    k_compact2<<<dim3(nb), dim3(1024), 0, stream>>>(num_models, B, maxm, blk_tot, slots, offsets, models,
+                                                    abs16 ? s16.live : nullptr, abs16 ? s16.rank : nullptr, ctl);
     if (s16.out && s16.sampson == 2) {
         const uint32_t cap = (uint32_t)std::min<uint64_t>(((uint64_t)B * (uint64_t)maxm + 7u) & ~7ull, 0xffffff00ull);
         k_hom16<<<dim3(std::min<uint32_t>((cap + 255) / 256, 1024u)), dim3(256), 0, stream>>>(ctl, slots, models, cap, s16.thr,
@@ -1047,9 +1158,8 @@ hipError_t launch_compact2(const uint32_t *num_models, uint32_t B, int maxm, uin
         // matrix-core scorer: its fp16 operand blocks are built straight from the records, and its exact pass reads the
         // fp64 models from the records as well - no hypothesis-ordered copies
         const uint32_t cap8 = (uint32_t)(((uint64_t)B * (uint64_t)maxm + 31u) & ~31ull);
-        k_gather_shadow16<<<dim3((cap8 + 255) / 256), dim3(256), 0, stream>>>(ctl, slots, models, nullptr, nullptr, 0u, cap8,
-                                                                            s16.g16, s16.c16, s16.thr,
-                                                                            static_cast<uint4 *>(s16.out));
+        const uint32_t sblocks = (cap8 + 255) / 256, pblocks = (s16.point_rows + 255) / 256;
+        k_gather_shadow16<<<dim3(sblocks + pblocks), dim3(256), 0, stream>>>(ctl, slots, models, nullptr, nullptr, 0u, sblocks, pts, s16);
     } else if (shadow_compact && compact64) {
         const uint64_t threads = (uint64_t)B * (uint64_t)maxm * 12u; // capacity; lanes beyond num_hyp return at once
         k_gather_models<<<dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, stream>>>(ctl, slots, models,

@@ -53,12 +53,15 @@ struct GenerateArgs {
 struct ScoreArgs {
     PointSet pts;
     const double *models;
-    const uint32_t *slots;     // hypothesis k -> model record index (nullptr: identity)
+    const uint32_t *slots;     // hypothesis k -> model record index (nullptr: identity); k_score_mfma: the LIVE list
+                               // (record index of every hypothesis without the NaN flag, in hypothesis order)
     const float *shadow;       // optional compact [num_hyp][16] fp32 model shadows in hypothesis order (pre-filter)
     const double *compact64;   // optional compact [num_hyp][16] fp64 model fields in hypothesis order (pre-filter)
     const void *shadow16;      // optional fp16 MFMA operand blocks of the hypotheses (absolute pose, k_score_mfma):
-                               // 96 B per hypothesis in groups of 16, see k_shadow16 in pipeline.hip
-    const uint32_t *num_hyp;   // device scalar
+                               // 64 B per LIVE hypothesis, see shadow16_one in pipeline.hip
+    const void *points16 = nullptr; // k_score_mfma: fp16 operand rows of the correspondences (kAbs16PointBytes each, one per
+                               // correspondence of every chunk, see abs16_point_row in pipeline.hip)
+    const uint32_t *num_hyp;   // device scalar; k_score_mfma: BatchCtl.num_live, the length of the live list
     uint32_t hyp_capacity;     // row pitch of the partial arrays
     double thr2;
     PrefilterArgs pf;          // conservative fp32 pre-filter (pl_prefilter.h); pf.enabled == 0: exact evaluation
@@ -68,8 +71,11 @@ struct ScoreArgs {
 };
 constexpr uint32_t kMaxScoreChunks = 4096; // (2^31 correspondences / 64 P would be more; the driver rejects such sets)
 
+constexpr uint32_t kNoRank = 0xffffffffu; // rank[] of a NaN hypothesis: it has no row in the live list
 struct FinalizeArgs {
     const uint32_t *num_hyp;
+    const uint32_t *rank = nullptr; // k_score_mfma: hypothesis k -> its position in the live list, the column of its partials
+                                    // (kNoRank: NaN model, no inliers); nullptr: the partials are indexed by k
     uint32_t hyp_capacity, chunks, n_points;
     double thr2;
     const uint32_t *part_count;
@@ -112,7 +118,8 @@ struct BatchCtl {
     uint64_t pos_after;   // draws consumed after the batch's last iteration
     uint32_t nan_hyp;     // hypotheses of the batch with a NaN entry (counted by the generators, summed by k_compact2;
                           // the scorers skip them: no inliers)
-    uint32_t pad;
+    uint32_t num_live;    // hypotheses without the NaN flag = length of the live list the matrix-core absolute-pose scorer
+                          // runs over (k_compact2; 0 where no live list is built)
 };
 struct RecordMeta {
     uint32_t k, slot, count, pad;
@@ -179,10 +186,8 @@ hipError_t launch_task_records(int est, const LMTask *tasks, const double *recor
                                uint32_t num_tasks, LMTask *host_tasks, hipStream_t stream);
 hipError_t launch_select_record(const double *score_refined, double incumbent_score, const double *rec_refined,
                                 const double *rec_incumbent, double *out, hipStream_t stream);
-// fp16 A-operand blocks for k_score_mfma from the compact fp32 shadows (absolute pose); capacity = hypotheses rounded
-// up to a multiple of 8, 64 B each.
-hipError_t launch_shadow16(const uint32_t *num_hyp, const float *shadow_compact, uint32_t hyp_capacity, float g16,
-                           float c16, float thr, void *shadow16, hipStream_t stream);
+// rows of the correspondence operand table of k_score_mfma for n points (chunks x points per chunk of its launch)
+uint32_t abs16_point_rows(uint32_t n_points);
 bool score_uses_mfma(int est, uint32_t n_points, const PrefilterArgs &pf);
 // operands of k_score_mfma2 for `capacity` hypotheses listed in `slots` (+ the pad rows behind them)
 hipError_t launch_sampson16(BatchCtl *ctl, const uint32_t *slots, const double *models, uint32_t capacity, void *out,
@@ -211,23 +216,36 @@ hipError_t launch_sample_positions(int K, uint64_t seed, uint64_t pos_base, uint
                                    BatchCtl *ctl, uint32_t zero_words, hipStream_t stream);
 // counted: blk_tot already holds the per-block model counts (GenerateArgs.blk_tot); otherwise they are counted first
 // shadow16 != nullptr: the fp16 operand blocks of k_score_mfma are built in the same launch as the hypothesis-ordered
-// copies (Shadow16Params; see k_shadow16)
+// copies (Shadow16Params; see k_gather_shadow16)
 struct Shadow16Params {
     void *out = nullptr;
     float g16 = 0.f, c16 = 0.f, thr = 0.f;
     int sampson = 0; // 1: two-view, operands of k_score_mfma2 (96 B per hypothesis, pl_prefilter.h Sampson16Operand);
                      // 2: homography, operands of k_score_mfmah (256 B per hypothesis, Hom16Model; thr = PrefilterArgs.h16)
+    // absolute pose (sampson == 0, k_score_mfma) only.  The operand rows in `out` are those of the LIVE hypotheses, indexed by
+    // live position; k_compact2 writes the list and its inverse:
+    uint32_t *live = nullptr;   // [capacity] record index of the live hypotheses, ascending hypothesis index
+    uint32_t *rank = nullptr;   // [capacity] hypothesis k -> live position or kNoRank
+    void *points16 = nullptr;   // [point_rows] operand rows of the correspondences, rebuilt by every launch that builds `out`
+    uint32_t point_rows = 0;    // chunks x correspondences per chunk (rows past the last correspondence: invalid columns)
 };
 constexpr size_t kSampson16Bytes = 96;
 constexpr size_t kAbs16Bytes = 64;  // absolute pose (k_score_mfma): 3 directions + the shared second k block, 16 B each, per hypothesis
-constexpr size_t kAbs16Pad = 32;    // the last group of 32 is filled up
+constexpr size_t kAbs16Pad = 32;    // the last group of 32 (of the live list) is filled up
+constexpr size_t kAbs16PointBytes = 64; // ... and per correspondence: first k block + the second k block of the 3 directions
 constexpr size_t kSampson16Pad = 64; // operand rows a partial group of 32 may read past the last hypothesis
 constexpr size_t kHom16Bytes = 256; // homography (k_score_mfmah): 4 rows x 4 k blocks x 16 B per hypothesis, groups of 8
 constexpr size_t kHom16Pad = 8;     // the last group of 8 is filled up
 // blk_tot is followed by the generators' NaN-model table of the same length (nb = ceil(B / 1024) entries each)
+// pts: the problem's correspondences (read where s16.points16 is set)
 hipError_t launch_compact2(const uint32_t *num_models, uint32_t B, int maxm, uint32_t *blk_tot, bool counted, uint32_t *slots,
                            uint32_t *offsets, const double *models, float *shadow_compact, double *compact64,
-                           BatchCtl *ctl, const Shadow16Params &s16, hipStream_t stream);
+                           BatchCtl *ctl, const Shadow16Params &s16, const PointSet &pts, hipStream_t stream);
+// Everything k_score_mfma needs for `capacity` hypotheses that sit in `models` in list order `slots` (diagnostic entry
+// pl_debug_score_stream; the main loop gets the same from launch_compact2): live list + rank + ctl->num_live, the operand rows
+// of the live hypotheses and of the correspondences (all fields of s16 set).
+hipError_t launch_abs16(BatchCtl *ctl, const uint32_t *slots, const double *models, uint32_t capacity, const PointSet &pts,
+                        const Shadow16Params &s16, hipStream_t stream);
 // the two halves on their own (diagnostic entry pl_debug_score_stream): hypothesis-ordered copies of records that already
 // sit in `models` in list order `slots`, and the chunk partials -> (count, score) without the record scan
 hipError_t launch_gather_models(BatchCtl *ctl, const uint32_t *slots, const double *models, uint32_t capacity,

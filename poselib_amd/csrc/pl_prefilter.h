@@ -397,7 +397,7 @@ PL_HD bool pf16_sampson_outlier(const Sampson16Operand &model, const Sampson16Op
     return (bits >> 31) != 0u;
 }
 
-// ---- reprojection, fp16 / MFMA form: operands (header comment).  The kernels (k_shadow16, k_score_mfma) and the test-only
+// ---- reprojection, fp16 / MFMA form: operands (header comment).  The kernels (k_gather_shadow16, k_score_mfma) and the test-only
 // host build run these very functions ---------------------------------------------------------------------------------
 PL_HD uint16_t pf_half_toward_plus_inf(float v) { // any sign: the smallest fp16 >= v
     uint16_t b = pf_half_rn(v);
