@@ -76,7 +76,11 @@ typedef struct {
     pl_bundle_options bundle;
     double max_error;         /* 12.0 absolute pose, 1.0 otherwise */
     int32_t real_focal_check; /* fundamental only */
-    int32_t tangent_sampson;  /* relative pose: must be 0 (out of scope) */
+    int32_t tangent_sampson;  /* pl_estimate_relative_pose (and relative-pose items of pl_estimate_batch): robust.cc:255-284 - the
+                                 Sampson error is taken in the image, on unit bearings and the Jacobians of the un-projection
+                                 (Terekhov & Larsson, CVPR 2023), for all nine camera models, with FIXED cameras: together with
+                                 bundle.refine_focal_length / refine_principal_point / refine_extra_params the reference moves the
+                                 intrinsics - that is PL_ERR_UNSUPPORTED.  Every other entry point: must be 0 */
     int32_t estimate_focal_length; /* pl_estimate_absolute_pose: robust.cc:47-54 - RANSAC over pose AND focal length (ransac_pnpf,
                                       P3.5Pf), the camera's focal length is replaced and refined in the final bundle; every
                                       other entry point: must be 0 */
@@ -253,6 +257,12 @@ int pl_ransac_homography(const double *x1, const double *x2, size_t n, const pl_
 typedef struct pl_problem pl_problem;
 /* kind as in pl_default_robust_options; a = first point set (N x 2), b = second (N x 3 for kind 0, else N x 2) */
 int pl_problem_create(int kind, const double *a, const double *b, size_t n, pl_problem **out);
+/* A resident tangent-Sampson relative-pose problem: per correspondence the bearings of the two pixels and the 3x2 Jacobians of
+ * the un-projections (Camera::unproject_with_jac), computed on the device.  x1 / x2 (N x 2 pixels) and the cameras are taken as
+ * they stand: the level of ransac_relpose(x1, x2, camera1, camera2, ...), behind estimate_relative_pose's rescaling.  A null
+ * camera is the identity camera.  Models are pl_camera_pose. */
+int pl_problem_create_tangent(const double *x1, const double *x2, size_t n, const pl_camera *camera1, const pl_camera *camera2,
+                              pl_problem **out);
 void pl_problem_destroy(pl_problem *p);
 /* model: pl_camera_pose for kinds 0/1, double[9] column-major for kinds 2/3 */
 int pl_ransac_run(pl_problem *p, const pl_robust_options *opt, void *model, uint8_t *inliers, pl_ransac_stats *stats);
@@ -300,6 +310,10 @@ int pl_ransac_run_sharded(pl_problem *p, const pl_robust_options *opt, const pl_
 /* Score one model against the resident correspondences with the estimator's MSAC score
  * (robust/utils.cc:36-65, 158-239, 300-329 through estimators' score_model()).  model as in pl_ransac_run. */
 int pl_score_model(pl_problem *p, const void *model, double max_error, uint64_t *inlier_count, double *score);
+/* Diagnostic: the inlier mask (N bytes) of one model, as the estimators' final inlier pass computes it. */
+int pl_debug_inlier_mask(pl_problem *p, const void *model, double max_error, uint8_t *mask);
+/* Diagnostic: correspondences per chunk of the tangent-Sampson streaming scorer as built. */
+int pl_debug_tangent_chunk(void);
 /* Diagnostic entry (no counterpart in the reference): `n` models - pl_camera_pose[n] for kinds 0/1, double[n][9]
  * column-major for kinds 2/3 - through the STREAMING scorer of the batched main loop, i.e. through the conservative
  * pre-filters (fp16/MFMA or fp32) in front of the exact fp64 evaluation, instead of the sequential scorer behind

@@ -197,7 +197,7 @@ RansacStats estimate_relative_pose(const std::vector<Point2D> &points2D_1, const
                                    const Camera &camera1, const Camera &camera2, const RelativePoseOptions &opt,
                                    CameraPose *relative_pose, std::vector<char> *inliers) {
     pl_robust_options o = to_pl(1, opt.ransac, opt.bundle, opt.max_error);
-    o.tangent_sampson = opt.tangent_sampson; // -> PL_ERR_UNSUPPORTED
+    o.tangent_sampson = opt.tangent_sampson; // served with fixed cameras; with bundle.refine_* -> PL_ERR_UNSUPPORTED
     const pl_camera c1 = to_pl(camera1), c2 = to_pl(camera2);
     pl_camera_pose pose = to_pl(*relative_pose);
     pl_ransac_stats st;

@@ -157,6 +157,9 @@ def _declare(L):
         "pl_ransac_fundamental": (cint, [vp, vp, sz, opt, vp, vp, stats]),
         "pl_ransac_homography": (cint, [vp, vp, sz, opt, vp, vp, stats]),
         "pl_problem_create": (cint, [cint, vp, vp, sz, P(vp)]),
+        "pl_problem_create_tangent": (cint, [vp, vp, sz, cam, cam, P(vp)]),
+        "pl_debug_inlier_mask": (cint, [vp, vp, dbl, vp]),
+        "pl_debug_tangent_chunk": (cint, []),
         "pl_problem_destroy": (None, [vp]),
         "pl_ransac_run": (cint, [vp, opt, vp, vp, stats]),
         "pl_ransac_run_sharded": (cint, [vp, opt, P(Shard), vp, vp, stats]),
@@ -200,5 +203,5 @@ EXPORTED_SYMBOLS = [
     "pl_essential_matrix_5pt", "pl_relpose_7pt", "pl_homography_4pt", "pl_solve_batch", "pl_estimate_batch", "pl_estimate_batch_devices", "pl_last_batch_report", "pl_undistort_points",
     "pl_ransac_batch", "pl_debug_device_math", "pl_debug_device_math2", "pl_ransac_pnpf", "pl_ransac_shared_focal_relpose", "pl_refine_shared_focal_relpose",
     "pl_estimate_shared_focal_relative_pose", "pl_solve_focal_batch", "pl_p35pf", "pl_relpose_6pt_shared_focal", "pl_set_lm_mode",
-    "pl_abi_version",
+    "pl_abi_version", "pl_problem_create_tangent", "pl_debug_inlier_mask", "pl_debug_tangent_chunk",
 ]

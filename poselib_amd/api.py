@@ -707,6 +707,34 @@ class Problem:
             pass
 
 
+class TangentProblem(Problem):
+    """Resident tangent-Sampson relative-pose problem (pl_problem_create_tangent): bearings and un-projection Jacobians of the two
+    images' pixels, computed on the device.  x1 / x2 in pixels and the cameras as ransac_relpose(x1, x2, camera1, camera2, ...) takes
+    them (None: the identity camera).  Models are poses, as for KIND_REL."""
+
+    def __init__(self, x1, x2, camera1=None, camera2=None):
+        self.kind = KIND_REL  # (how the models are marshalled)
+        a, b = _pts(x1, 2), _pts(x2, 2)
+        self.n = a.shape[0]
+        self._h = C.c_void_p()
+        c1 = None if camera1 is None else _as_camera(camera1)._c()
+        c2 = None if camera2 is None else _as_camera(camera2)._c()
+        L.check(L.lib().pl_problem_create_tangent(_ptr(a), _ptr(b), C.c_size_t(self.n), None if c1 is None else C.byref(c1),
+                                                  None if c2 is None else C.byref(c2), C.byref(self._h)))
+
+
+def inlier_mask(problem, model, max_error):
+    """Diagnostic (pl_debug_inlier_mask): the inlier mask of one model on a resident problem."""
+    mask = np.zeros(max(problem.n, 1), dtype=np.uint8)
+    if problem.kind in (KIND_ABS, KIND_REL):
+        m = _cpose(model)
+        L.check(L.lib().pl_debug_inlier_mask(problem._h, C.byref(m), C.c_double(max_error), _ptr(mask)))
+    else:
+        M = np.ascontiguousarray(np.asarray(model, dtype=np.float64).T.reshape(9))
+        L.check(L.lib().pl_debug_inlier_mask(problem._h, _ptr(M), C.c_double(max_error), _ptr(mask)))
+    return mask[: problem.n].astype(bool)
+
+
 # ------------------------------------------------------------------------------------------ minimal solvers
 def _bearings(x, k):
     x = np.ascontiguousarray(x, dtype=np.float64)

@@ -340,7 +340,7 @@ void camera_rescale(CameraParams &c, double s) { // misc/camera_models.cc:432-45
 void params_from_record(int kind, const double *rec, double *params) {
     for (int i = 0; i < kParamDoubles; ++i)
         params[i] = 0.0;
-    if (kind == EST_ABS || kind == EST_REL) {
+    if (kind == EST_ABS || kind == EST_REL || kind == EST_RELT) {
         for (int i = 0; i < 7; ++i)
             params[i] = rec[i];
     } else {
@@ -373,10 +373,10 @@ void lm_params_from_record(int kind, const double *rec, double *params) {
     }
 }
 void identity_record(int kind, double *rec) {
-    if (kind == EST_ABS || kind == EST_REL) {
+    if (kind == EST_ABS || kind == EST_REL || kind == EST_RELT) {
         Quat q;
         q.w = 1.0, q.x = q.y = q.z = 0.0;
-        store_pose_model_q(rec, q, v3(0, 0, 0), kind == EST_REL);
+        store_pose_model_q(rec, q, v3(0, 0, 0), kind != EST_ABS);
     } else {
         Mat3 I;
         for (int i = 0; i < 9; ++i)
@@ -559,7 +559,7 @@ int run_refinements(Context *c, const pl_problem *p, std::vector<RefineJob> &job
         with_camera = with_camera || jobs[j].cam_flags != 0;
     if (with_camera && p->kind != EST_ABS)
         return fail(PL_ERR_INVALID, "camera intrinsics are refined with absolute poses only");
-    const bool use_lm2 = !with_camera && latency_mode && p->kind != EST_REL && !lm_sums_ordered(p->kind) && same_it && max_it >= 1 && max_it <= 32 && p->n >= lm2_min_points;
+    const bool use_lm2 = !with_camera && latency_mode && p->kind != EST_REL && p->kind != EST_RELT && !lm_sums_ordered(p->kind) && same_it && max_it >= 1 && max_it <= 32 && p->n >= lm2_min_points;
     if (use_lm2)
         HIP_TRY(c->lm_tasks.ensure(stage_bytes));
     LMTask *ht = c->h_tasks.as<LMTask>();
@@ -723,7 +723,7 @@ struct RansacRun {
     RansacRun(Context *c_, const pl_problem *p_, const pl_robust_options *o_, double *best_record_, uint8_t *inliers_,
               pl_ransac_stats *st_)
         : c(c_), p(p_), o(o_), best_record(best_record_), inliers(inliers_), st(st_), kind(p_->kind), N(p_->n),
-          K(sample_size(p_->kind)), MAXM((p_->kind == EST_REL) ? 8 : max_models(p_->kind)), ro(o_->ransac),
+          K(sample_size(p_->kind)), MAXM((p_->kind == EST_REL || p_->kind == EST_RELT) ? 8 : max_models(p_->kind)), ro(o_->ransac),
           thr2(o_->max_error * o_->max_error), lo_opt(lo_options(o_->max_error)),
           sh((g_shard && g_shard->world > 1) ? g_shard : nullptr), G(sh ? (uint32_t)sh->world : 1u),
           grank(sh ? (uint32_t)sh->rank : 0u), dyn_max(o_->ransac.max_iterations),
@@ -1746,9 +1746,9 @@ float host_prefilter_bound(int kind, const PrepareArgs &pa, const double *a, con
 // inputs: no upload); lm_only: the problem is only refined on, never scored - no max|x| read-back, no synchronisation
 int make_problem_prepared(Context *c, int kind, const double *a, const double *b, size_t n, const PrepareArgs &pa,
                           pl_problem *p, bool resident = false, bool lm_only = false) {
-    if (kind < 0 || kind > 3)
+    if (kind < 0 || kind > EST_RELT)
         return fail(PL_ERR_INVALID, "unknown problem kind");
-    if (n > 0x7fffffffu)
+    if (n > 0x7fffffffu / (kind == EST_RELT ? 18u : 1u))
         return fail(PL_ERR_INVALID, "too many correspondences");
     p->kind = kind;
     p->device = c->device;
@@ -1794,6 +1794,11 @@ int make_problem_prepared(Context *c, int kind, const double *a, const double *b
     HIP_TRY(launch_prepare(c->raw_src_a, c->raw_src_b, (uint32_t)n, pa, c->pts_arena.as<double>(),
                            c->absmax.as<unsigned long long>(), c->stream));
     p->d_pts = c->pts_arena.as<double>();
+    if (kind == EST_RELT) { // one block of 18 arrays behind a[0] (pl_kernels.h); its pre-filter takes no bound of the coordinates
+        p->ps.a[0] = p->d_pts;
+        p->ps.xy_absmax = std::numeric_limits<float>::infinity();
+        return PL_OK;
+    }
     for (int d = 0; d < nd; ++d)
         p->ps.a[d] = p->d_pts + (size_t)d * n;
     if (!reads_absmax) { // (stream order puts the next kernels behind k_prepare)
@@ -1861,13 +1866,13 @@ void normalize_frobenius(Mat3 &A) {
 
 // the caller's model (pl_camera_pose for absolute / relative pose, column-major 3 x 3 for F / H) <-> record
 void record_from_model(int kind, const void *model, double *rec) {
-    if (kind == EST_ABS || kind == EST_REL)
-        record_from_pose(static_cast<const pl_camera_pose *>(model), kind == EST_REL, rec);
+    if (kind == EST_ABS || kind == EST_REL || kind == EST_RELT)
+        record_from_pose(static_cast<const pl_camera_pose *>(model), kind != EST_ABS, rec);
     else
         store_matrix_model(rec, mat_from_colmajor(static_cast<const double *>(model)));
 }
 void model_from_record(int kind, const double *rec, void *model) {
-    if (kind == EST_ABS || kind == EST_REL) {
+    if (kind == EST_ABS || kind == EST_REL || kind == EST_RELT) {
         pose_from_record(rec, static_cast<pl_camera_pose *>(model));
     } else {
         Mat3 M;
@@ -1880,7 +1885,7 @@ void model_from_record(int kind, const double *rec, void *model) {
 int run_with_model(Context *c, pl_problem *p, const pl_robust_options *o, void *model, uint8_t *inliers,
                    pl_ransac_stats *st) {
     double rec[kModelStride];
-    if (o->ransac.score_initial_model)
+    if (o->ransac.score_initial_model && p->kind != EST_RELT) // (tangent Sampson: the identity whatever the caller's model, ransac.cc:159-160)
         record_from_model(p->kind, model, rec);
     else
         identity_record(p->kind, rec);
@@ -2001,6 +2006,18 @@ void front_begin(FrontEnd &fe, int kind, const double *a, const double *b, size_
         fe.prep = prepare_unproject(c1, &c2);
         break;
     }
+    case EST_RELT: { // robust.cc:249-265: pixels and cameras times the mean inverse focal length, then bearing + Jacobian per pixel
+        fe.scale = 0.5 * (1.0 / camera_focal(camera1) + 1.0 / camera_focal(camera2));
+        fe.scaled.max_error *= fe.scale;
+        fe.scaled.bundle.loss_scale *= fe.scale;
+        fe.scaled.tangent_sampson = 0; // (the kind carries it from here on)
+        fe.prep.mode = 3;
+        fe.prep.cam1 = to_cam(camera1), fe.prep.cam2 = to_cam(camera2);
+        camera_rescale(fe.prep.cam1, fe.scale);
+        camera_rescale(fe.prep.cam2, fe.scale);
+        fe.prep.scale = fe.scale;
+        break;
+    }
     default:
         fe.scale = normalization_of(a, b, n, kind == EST_HOM || !opt.real_focal_check, fe.T1, fe.T2, fe.prep);
         fe.scaled.max_error /= fe.scale;
@@ -2012,7 +2029,9 @@ void front_begin(FrontEnd &fe, int kind, const double *a, const double *b, size_
 // the record the loop starts from: the identity, or with ransac.score_initial_model the caller's model - poses as they are, F and H
 // in the normalised coordinates of the problem (robust.cc:566-569, 729-732)
 void front_initial_record(const FrontEnd &fe, const void *model, double *rec) {
-    if (!fe.scaled.ransac.score_initial_model) {
+    // (tangent Sampson: ransac_relpose with cameras resets best_model unconditionally, ransac.cc:159-160 - with score_initial_model
+    // the identity is what gets scored)
+    if (!fe.scaled.ransac.score_initial_model || fe.kind == EST_RELT) {
         identity_record(fe.kind, rec);
         return;
     }
@@ -2036,6 +2055,7 @@ uint64_t front_min_inliers(int kind) {
     case EST_ABS:
         return 3;
     case EST_REL:
+    case EST_RELT:
         return 5;
     case EST_FUND:
         return 7;
@@ -2084,7 +2104,7 @@ void front_set_focal(FrontEnd &fe, pl_camera *camera, double focal) {
 // camera.rescale(scale) ... rescale(1 / scale) round trip (robust.cc:119-121), with the intrinsics the bundle moved (cam_refined);
 // fund / hom: back to pixels (robust.cc:590-591, 753-754)
 void front_finish(const FrontEnd &fe, const double *rec, const CameraParams *cam_refined, void *model, pl_camera *camera) {
-    if (fe.kind == EST_ABS || fe.kind == EST_REL) {
+    if (fe.kind == EST_ABS || fe.kind == EST_REL || fe.kind == EST_RELT) {
         model_from_record(fe.kind, rec, model);
         if (!camera)
             return;
@@ -2228,6 +2248,89 @@ int pl_problem_create(int kind, const double *a, const double *b, size_t n, pl_p
     *out = p;
     return PL_OK;
 }
+// A resident tangent-Sampson problem (EST_RELT): bearings and un-projection Jacobians of the two images' pixels, computed on the
+// device (k_prepare mode 3).  The pixels and cameras are taken as they stand - the ransac_relpose(x1, x2, cam1, cam2, ...) level of
+// the reference, behind the rescaling of estimate_relative_pose (robust.cc:256-265).
+int pl_problem_create_tangent(const double *x1, const double *x2, size_t n, const pl_camera *camera1, const pl_camera *camera2,
+                              pl_problem **out) {
+    if (!out || ((!x1 || !x2) && n))
+        return fail(PL_ERR_INVALID, "points / output pointer is null");
+    if ((camera1 && !camera_supported(camera1)) || (camera2 && !camera_supported(camera2)))
+        return fail(PL_ERR_UNSUPPORTED, "camera model outside the supported set (or too few parameters)");
+    if (n > 0x7fffffffu / 18)
+        return fail(PL_ERR_INVALID, "too many correspondences");
+    Context *c;
+    int rc = get_context(&c);
+    if (rc != PL_OK)
+        return rc;
+    pl_problem *p = new pl_problem();
+    p->kind = EST_RELT;
+    p->device = c->device;
+    p->n = (uint32_t)n;
+    p->d_pts = nullptr;
+    std::memset(&p->ps, 0, sizeof(p->ps));
+    p->ps.n = (uint32_t)n;
+    p->ps.xy_absmax = std::numeric_limits<float>::infinity();
+    *out = p;
+    if (n == 0)
+        return PL_OK;
+    PrepareArgs pa;
+    std::memset(&pa, 0, sizeof(pa));
+    pa.mode = 3;
+    pa.cam1 = to_cam(camera1);
+    pa.cam2 = to_cam(camera2);
+    pa.scale = 1.0;
+    const size_t raw = sizeof(double) * 2 * n;
+    hipError_t e = c->raw_a.ensure(raw);
+    if (e == hipSuccess)
+        e = c->raw_b.ensure(raw);
+    if (e == hipSuccess)
+        e = hipMalloc((void **)&p->d_pts, sizeof(double) * 18 * n);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(c->raw_a.p, x1, raw, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(c->raw_b.p, x2, raw, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess)
+        e = launch_prepare(c->raw_a.as<double>(), c->raw_b.as<double>(), (uint32_t)n, pa, p->d_pts, nullptr, c->stream);
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        if (p->d_pts)
+            (void)hipFree(p->d_pts);
+        delete p;
+        *out = nullptr;
+        return fail(PL_ERR_HIP, "preparation of the tangent-Sampson problem", e);
+    }
+    p->ps.a[0] = p->d_pts;
+    return PL_OK;
+}
+// Diagnostic: correspondences per chunk of the tangent-Sampson streaming scorer as built (tests probe the sizes around it)
+int pl_debug_tangent_chunk(void) { return tangent_score_chunk(); }
+// Diagnostic: the inlier mask of one model on a resident problem, as the estimators' final get_inliers computes it (k_mask).
+int pl_debug_inlier_mask(pl_problem *p, const void *model, double max_error, uint8_t *mask) {
+    if (!p || !model || (!mask && p->n))
+        return fail(PL_ERR_INVALID, "problem / model / mask pointer is null");
+    Context *c;
+    int rc = get_context(&c);
+    if (rc != PL_OK)
+        return rc;
+    if (p->device != c->device)
+        return fail(PL_ERR_INVALID, "problem lives on another device than the calling thread's");
+    if (p->n == 0)
+        return PL_OK;
+    double rec[kModelStride];
+    if (p->kind == EST_ABS || p->kind == EST_REL || p->kind == EST_RELT)
+        record_from_pose(static_cast<const pl_camera_pose *>(model), p->kind != EST_ABS, rec);
+    else
+        store_matrix_model(rec, mat_from_colmajor(static_cast<const double *>(model)));
+    HIP_TRY(c->tmp_model.ensure(sizeof(double) * kModelStride));
+    HIP_TRY(c->mask.ensure(p->n));
+    HIP_TRY(hipMemcpyAsync(c->tmp_model.p, rec, sizeof(rec), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(launch_mask(p->kind, p->ps, c->tmp_model.as<double>(), max_error * max_error, c->mask.as<uint8_t>(), nullptr, c->stream));
+    HIP_TRY(hipMemcpyAsync(mask, c->mask.p, p->n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(wait_stream(c));
+    return PL_OK;
+}
 void pl_problem_destroy(pl_problem *p) {
     if (!p)
         return;
@@ -2272,8 +2375,8 @@ int pl_score_model(pl_problem *p, const void *model, double max_error, uint64_t 
     if (p->device != c->device)
         return fail(PL_ERR_INVALID, "problem lives on another device than the calling thread's");
     double rec[kModelStride];
-    if (p->kind == EST_ABS || p->kind == EST_REL)
-        record_from_pose(static_cast<const pl_camera_pose *>(model), p->kind == EST_REL, rec);
+    if (p->kind == EST_ABS || p->kind == EST_REL || p->kind == EST_RELT)
+        record_from_pose(static_cast<const pl_camera_pose *>(model), p->kind != EST_ABS, rec);
     else
         store_matrix_model(rec, mat_from_colmajor(static_cast<const double *>(model)));
     HIP_TRY(c->tmp_model.ensure(sizeof(double) * kModelStride));
@@ -2309,13 +2412,22 @@ int pl_debug_score_stream(pl_problem *p, const void *models, size_t n, double ma
     if (n == 0)
         return PL_OK;
     const uint32_t H = (uint32_t)n;
-    const bool pose_kind = (p->kind == EST_ABS || p->kind == EST_REL);
+    if (p->kind == EST_RELT && p->n == 0) { // (no correspondence: no chunk to hold)
+        for (uint32_t k = 0; k < H; ++k) {
+            if (counts)
+                counts[k] = 0;
+            if (scores)
+                scores[k] = 0.0;
+        }
+        return PL_OK;
+    }
+    const bool pose_kind = (p->kind == EST_ABS || p->kind == EST_REL || p->kind == EST_RELT);
     std::vector<double> recs((size_t)H * kModelStride);
     std::vector<uint32_t> ident(H);
     for (uint32_t k = 0; k < H; ++k) {
         ident[k] = k;
         if (pose_kind)
-            record_from_pose(static_cast<const pl_camera_pose *>(models) + k, p->kind == EST_REL, &recs[(size_t)k * kModelStride]);
+            record_from_pose(static_cast<const pl_camera_pose *>(models) + k, p->kind != EST_ABS, &recs[(size_t)k * kModelStride]);
         else
             store_matrix_model(&recs[(size_t)k * kModelStride], mat_from_colmajor(static_cast<const double *>(models) + 9 * (size_t)k));
     }
@@ -2484,9 +2596,9 @@ int pl_refine_model(pl_problem *p, const pl_bundle_options *opt, const pl_camera
     if (p->device != c->device)
         return fail(PL_ERR_INVALID, "problem lives on another device than the calling thread's");
     RefineJob j;
-    const bool pose_kind = (p->kind == EST_ABS || p->kind == EST_REL);
+    const bool pose_kind = (p->kind == EST_ABS || p->kind == EST_REL || p->kind == EST_RELT);
     if (pose_kind)
-        record_from_pose(static_cast<const pl_camera_pose *>(model), p->kind == EST_REL, j.record_in);
+        record_from_pose(static_cast<const pl_camera_pose *>(model), p->kind != EST_ABS, j.record_in);
     else
         store_matrix_model(j.record_in, mat_from_colmajor(static_cast<const double *>(model)));
     j.opt = to_lm(*opt);
@@ -2749,13 +2861,23 @@ int estimate_two_view(int kind, const double *x1, const double *x2, size_t n, co
 int pl_estimate_relative_pose(const double *x1, const double *x2, size_t n, const pl_camera *camera1,
                               const pl_camera *camera2, const pl_robust_options *opt, pl_camera_pose *pose,
                               uint8_t *inliers, pl_ransac_stats *stats) {
-    int rc = validate_options(opt);
+    // tangent_sampson (robust.cc:255-284) is served here and nowhere else: with fixed cameras, i.e. without bundle.refine_*
+    const bool tangent = opt && opt->tangent_sampson;
+    pl_robust_options plain;
+    if (tangent) {
+        plain = *opt;
+        plain.tangent_sampson = 0;
+    }
+    int rc = validate_options(tangent ? &plain : opt);
     if (rc != PL_OK)
         return rc;
+    if (tangent && (opt->bundle.refine_focal_length || opt->bundle.refine_principal_point || opt->bundle.refine_extra_params))
+        return fail(PL_ERR_UNSUPPORTED, "tangent_sampson with bundle.refine_focal_length / refine_principal_point / refine_extra_params "
+                                        "refines the intrinsics with the pose (CameraRelativePoseRefiner): not served, fixed cameras only");
     if (!camera1 || !camera2 || !camera_supported(camera1) || !camera_supported(camera2))
         return fail(PL_ERR_UNSUPPORTED, "camera model not supported (NULL, SIMPLE_PINHOLE, PINHOLE, SIMPLE_RADIAL, RADIAL, OPENCV, OPENCV_FISHEYE, SIMPLE_RADIAL_FISHEYE, RADIAL_FISHEYE)");
     pl_ransac_stats local;
-    return estimate_two_view(EST_REL, x1, x2, n, camera1, camera2, opt, pose, inliers, stats ? stats : &local);
+    return estimate_two_view(tangent ? EST_RELT : EST_REL, x1, x2, n, camera1, camera2, opt, pose, inliers, stats ? stats : &local);
 }
 
 int pl_estimate_shared_focal_relative_pose(const double *x1, const double *x2, size_t n, const double *pp, const pl_robust_options *opt,

@@ -72,7 +72,9 @@ __host__ __device__ inline RelStage rel_stage(void *stage, uint32_t num_iters) {
 
 // ---- stage 1 --------------------------------------------------------------------------------------------------------
 constexpr int kFrontThreads = 64;
-__device__ __forceinline__ void rel_front_body(const GenerateArgs &g, const RelStage &w) {
+// TANGENT (EST_RELT, CameraRelativePoseEstimator::generate_models, relative_pose.cc:88-95): the sampled bearings d1, d2 of the problem
+// go into the solver as they stand - normalising a unit vector again would change bits
+template <bool TANGENT> __device__ __forceinline__ void rel_front_body(const GenerateArgs &g, const RelStage &w) {
     const uint32_t it = blockIdx.x * kFrontThreads + threadIdx.x;
     if (it >= g.num_iters)
         return;
@@ -81,8 +83,15 @@ __device__ __forceinline__ void rel_front_body(const GenerateArgs &g, const RelS
     Vec3 b1[5], b2[5];
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
-        b1[k] = bearing(g.pts.a[0][idx[k]], g.pts.a[1][idx[k]]);
-        b2[k] = bearing(g.pts.a[2][idx[k]], g.pts.a[3][idx[k]]);
+        if constexpr (TANGENT) {
+            const double *c = g.pts.a[0] + idx[k];
+            const size_t n = g.pts.n;
+            b1[k] = v3(c[0], c[n], c[2 * n]);
+            b2[k] = v3(c[3 * n], c[4 * n], c[5 * n]);
+        } else {
+            b1[k] = bearing(g.pts.a[0][idx[k]], g.pts.a[1][idx[k]]);
+            b2[k] = bearing(g.pts.a[2][idx[k]], g.pts.a[3][idx[k]]);
+        }
     }
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
@@ -101,12 +110,13 @@ __device__ __forceinline__ void rel_front_body(const GenerateArgs &g, const RelS
         for (int k = 0; k < 13; ++k)
             w.az[(size_t)(i * 13 + k) * w.P + it] = Az[i][k];
 }
-__global__ __launch_bounds__(kFrontThreads) void k_rel_front(GenerateArgs g) { rel_front_body(g, rel_stage(g.stage, g.num_iters)); }
+__global__ __launch_bounds__(kFrontThreads) void k_rel_front(GenerateArgs g) { rel_front_body<false>(g, rel_stage(g.stage, g.num_iters)); }
+__global__ __launch_bounds__(kFrontThreads) void k_rel_front_tangent(GenerateArgs g) { rel_front_body<true>(g, rel_stage(g.stage, g.num_iters)); }
 __global__ __launch_bounds__(kFrontThreads) void k_rel_front_g(const GroupArgs *ga) {
     const GroupArgs &gg = ga[blockIdx.z];
     if (!gg.active || blockIdx.x * (uint32_t)kFrontThreads >= gg.gen.num_iters)
         return;
-    rel_front_body(gg.gen, rel_stage(gg.gen.stage, gg.gen.num_iters));
+    rel_front_body<false>(gg.gen, rel_stage(gg.gen.stage, gg.gen.num_iters));
 }
 
 // ---- stage 2 --------------------------------------------------------------------------------------------------------
@@ -307,9 +317,12 @@ __global__ __launch_bounds__(kPosesThreads) void k_rel_poses_g(const GroupArgs *
 }
 
 // ---- launchers ------------------------------------------------------------------------------------------------------
-hipError_t launch_generate_rel(const GenerateArgs &a, hipStream_t stream) {
+hipError_t launch_generate_rel(const GenerateArgs &a, hipStream_t stream, bool tangent) {
     const uint32_t B = a.num_iters;
-    k_rel_front<<<dim3((B + kFrontThreads - 1) / kFrontThreads), dim3(kFrontThreads), 0, stream>>>(a);
+    if (tangent)
+        k_rel_front_tangent<<<dim3((B + kFrontThreads - 1) / kFrontThreads), dim3(kFrontThreads), 0, stream>>>(a);
+    else
+        k_rel_front<<<dim3((B + kFrontThreads - 1) / kFrontThreads), dim3(kFrontThreads), 0, stream>>>(a);
     k_rel_roots<<<dim3((B + 63) / 64), dim3(64), 0, stream>>>(B, a.stage);
     k_rel_poses<<<dim3((B + kPosesThreads - 1) / kPosesThreads), dim3(kPosesThreads), 0, stream>>>(a);
     return hipGetLastError();

@@ -342,8 +342,20 @@ __device__ __forceinline__ bool eval_point(const double *M, const double *pt, do
         return sampson_pose_inlier(M, pt[0], pt[1], pt[2], pt[3], thr2, r2);
     else if constexpr (EST == EST_FUND)
         return sampson_inlier(M, pt[0], pt[1], pt[2], pt[3], thr2, r2);
+    else if constexpr (EST == EST_RELT)
+        return tangent_pose_inlier(M, pt, thr2, r2);
     else
         return homography_inlier(M, pt[0], pt[1], pt[2], pt[3], thr2, r2);
+}
+// correspondence i of the set (EST_RELT: one block of 18 arrays behind a[0], pl_kernels.h)
+template <int EST> __device__ __forceinline__ void load_point(const PointSet &pts, uint32_t i, double *x) {
+    constexpr int ND = point_doubles(EST);
+#pragma unroll
+    for (int d = 0; d < ND; ++d)
+        if constexpr (EST == EST_RELT)
+            x[d] = pts.a[0][(size_t)d * pts.n + i];
+        else
+            x[d] = pts.a[d][i];
 }
 
 typedef float v2f __attribute__((ext_vector_type(2)));
@@ -677,6 +689,240 @@ template <int EST, int P> __global__ __launch_bounds__(kQueueThreads) void k_sco
     const ScoreArgs &a = g.score;
     score_queue_body<EST, P>(a.pts, a.shadow, a.compact64, a.num_hyp, a.hyp_capacity, a.thr2, a.pf, a.part_count,
                              a.part_score, blockIdx.x, blockIdx.y, g.slices);
+}
+
+// ---- tangent Sampson: the streaming scorer of EST_RELT --------------------------------------------------------------
+// k_score_tangent: k_score_queue's scheme (stationary correspondences, hypotheses streamed as fp32 shadows through scalar loads,
+// conservative fp32 pre-filter -> wave-private queue -> exact fp64 drain) for correspondences of 18 numbers.  A lane holds
+// kTangentP = 2 correspondences: 36 fp32 operands (d1, d2, thr M1, thr M2) + 2 slack terms in registers, the 18 fp64 originals of
+// the chunk's 128 correspondences in LDS (18 KB; with the pair queues 8 KB, the accumulators 6 KB and the
+// inlier rings 10 KB: 43 016 B per workgroup of 8 wavefronts, which with 124 VGPRs still lets two workgroups share a CU).  Three
+// correspondences per lane would put 57 operands next to the filter's 30 temporaries of a packed pair - beyond the 128 VGPRs at
+// which two workgroups share a CU.  The filter (pl_prefilter.h, tangent Sampson) evaluates the pair of a lane with packed fp32
+// FMAs, operation for operation pf_tangent_outlier; the drain evaluates tangent_pose_inlier of pl_score.h, the expression of
+// k_score_seq<EST_RELT>.
+constexpr int kTangentP = 2;
+constexpr int kTangentChunk = 64 * kTangentP;
+__device__ __forceinline__ void score_tangent_body(const PointSet &pts, const float *__restrict__ shadow,
+                                                   const double *__restrict__ compact64,
+                                                   const uint32_t *__restrict__ num_hyp_ptr, uint32_t hyp_capacity, double thr2,
+                                                   const PrefilterArgs &pf, uint32_t *__restrict__ part_count,
+                                                   double *__restrict__ part_score, uint32_t slice, uint32_t chunk,
+                                                   uint32_t nslices) {
+    constexpr int kWaves = kQueueThreads / 64;
+    constexpr int ND = 18, P = kTangentP, NPW = kTangentChunk;
+    __shared__ double s_pts[ND][NPW];
+    __shared__ uint16_t s_queue[kWaves][kQueueCap]; // entries: hypothesis of the group << 9 | correspondence of the chunk
+    __shared__ double s_acc_s[kWaves][64];
+    __shared__ uint32_t s_acc_c[kWaves][64];
+    // the inliers found by the drains, in (hypothesis, correspondence) order: r^2 and hypothesis of the group.  They are summed 64 at
+    // a time from here, so the association of a hypothesis' sum depends on the sequence of its unit's inliers alone - not on how many
+    // non-inliers shared their drains: the scores come out with the same bits whether the filter runs or not
+    constexpr int kInlierCap = 128; // <= 63 waiting + 64 appended by one drain
+    __shared__ double s_inl_v[kWaves][kInlierCap];
+    __shared__ uint16_t s_inl_g[kWaves][kInlierCap];
+    __shared__ uint32_t s_next_unit;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+
+    float pf32[P][ND]; // d1, d2, thr M1, thr M2 in fp32
+    float bnd[P];      // the correspondence's slack W (+inf: never excluded)
+    uint64_t vmask[P];
+    const double thr = sqrt(thr2);
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+        const uint32_t i = chunk * NPW + p * 64 + lane;
+        const bool valid = i < pts.n;
+        const uint32_t ic = valid ? i : 0u;
+        vmask[p] = __builtin_amdgcn_ballot_w64(valid);
+        double x[ND];
+        load_point<EST_RELT>(pts, ic, x);
+        if (wave == p) {
+#pragma unroll
+            for (int d = 0; d < ND; ++d)
+                s_pts[d][p * 64 + lane] = x[d];
+        }
+        bnd[p] = pf_tangent_point(x, thr, pf32[p]);
+    }
+    if (threadIdx.x == 0)
+        s_next_unit = 0;
+    __syncthreads(); // the only workgroup barrier: fp64 correspondences are in LDS
+
+    const uint32_t H = *as_uniform(num_hyp_ptr);
+    const uniform_f32_ptr sh = as_uniform(shadow);
+    uint16_t *const queue = s_queue[wave];
+    double *const acc_s = s_acc_s[wave];
+    uint32_t *const acc_c = s_acc_c[wave];
+    double *const inl_v = s_inl_v[wave];
+    uint16_t *const inl_g = s_inl_g[wave];
+
+    const uint32_t waves_per_chunk = nslices * kWaves;
+    auto request_ticket = [&]() -> uint32_t { // per-lane value; lane 0 holds the workgroup's next unit
+        uint32_t t = 0;
+        if (lane == 0) {
+            const uint32_t k = atomicAdd(&s_next_unit, 1u);
+            t = slice * kWaves + (k % kWaves) + (k / kWaves) * waves_per_chunk;
+        }
+        return t;
+    };
+    uint32_t ticket = (uint32_t)__builtin_amdgcn_readfirstlane((int)request_ticket());
+    uint32_t kb, gn;
+    while (unit_of_ticket(ticket, H, waves_per_chunk, kb, gn)) {
+        const uint32_t pending = request_ticket(); // the next unit's index travels while this one is evaluated
+        acc_s[lane] = 0.0;
+        acc_c[lane] = 0;
+        uint32_t qhead = 0, qtail = 0; // wave-uniform ring positions
+        uint32_t ihead = 0, itail = 0; // ... and of the ring of inliers
+
+        auto add_inliers = [&](uint32_t n) { // n <= 64 waiting inliers, one per lane
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            const bool act = (uint32_t)lane < n;
+            const uint32_t at = (ihead + lane) & (kInlierCap - 1);
+            const uint32_t g = act ? (uint32_t)inl_g[at] : 0x7fu;
+            const double v = act ? inl_v[at] : 0.0;
+            const uint64_t actmask = __builtin_amdgcn_ballot_w64(act);
+            const uint32_t g0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)g);
+            if (!__builtin_amdgcn_ballot_w64(act && g != g0)) {
+                // all of them belong to one hypothesis (the usual case when a good model's inliers arrive): a plain wave sum
+                const double tot = wave_sum_dpp(v);
+                if (lane == 0) {
+                    acc_s[g0] += tot;
+                    acc_c[g0] += (uint32_t)__popcll(actmask);
+                }
+            } else {
+                // segmented inclusive scan; keys (hypothesis) ascend with the lane
+                add_run_totals(v, actmask, g, act, lane, acc_s, acc_c);
+            }
+            ihead += n;
+        };
+
+        auto drain = [&](uint32_t n) { // n <= 64 waiting pairs, one per lane
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            const bool act = (uint32_t)lane < n;
+            const uint32_t e = act ? (uint32_t)queue[(qhead + lane) & (kQueueCap - 1)] : 0xffffu;
+            const uint32_t g = e >> 9, pi = act ? (e & 0x1ffu) : 0u;
+            double x[ND];
+#pragma unroll
+            for (int d = 0; d < ND; ++d)
+                x[d] = s_pts[d][pi];
+            const double *Mp = compact64 + (size_t)(kb + (act ? g : 0u)) * kModelDoubles;
+            double M[kModelDoubles];
+#pragma unroll
+            for (int i = 0; i < kModelDoubles; ++i)
+                M[i] = Mp[i];
+            double r2;
+            const bool in = tangent_pose_inlier(M, x, thr2, r2) && act;
+            const uint64_t inmask = __builtin_amdgcn_ballot_w64(in);
+            if (inmask) { // append the inliers, still ordered by (hypothesis, correspondence)
+                const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(inmask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)inmask, 0u));
+                if (in) {
+                    inl_v[(itail + below) & (kInlierCap - 1)] = r2;
+                    inl_g[(itail + below) & (kInlierCap - 1)] = (uint16_t)g;
+                }
+                itail += (uint32_t)__popcll(inmask);
+                if (itail - ihead >= 64u)
+                    add_inliers(64u);
+            }
+            qhead += n;
+        };
+
+        auto step = [&](const float(&r)[15], uint32_t g) {
+            if (__float_as_uint(r[13]) != 0u)
+                return; // NaN model: zero inliers (pl_math.h store_shadow)
+            uint64_t m[P];
+            uint64_t any = 0;
+            if (!pf.enabled || !(r[14] < __builtin_huge_valf())) { // filter off, or a model outside its range: all exact
+#pragma unroll
+                for (int p = 0; p < P; ++p)
+                    m[p] = vmask[p], any |= m[p];
+            } else {
+                static_assert(P == 2, "one packed pair per lane");
+                const float sc = pf_tangent_scale(r[14]);
+                float e[9];
+#pragma unroll
+                for (int i = 0; i < 9; ++i)
+                    e[i] = r[i] * sc;
+                // the lane's two correspondences per packed fp32 instruction, operation for operation pf_tangent_outlier
+                v2f f[ND];
+#pragma unroll
+                for (int d = 0; d < ND; ++d)
+                    f[d] = v2f{pf32[0][d], pf32[1][d]};
+                const v2f *d1 = f, *d2 = f + 3, *n1 = f + 6, *n2 = f + 12;
+                const v2f v0 = pk_fma(bc(e[0]), d1[0], pk_fma(bc(e[1]), d1[1], bc(e[2]) * d1[2]));
+                const v2f v1 = pk_fma(bc(e[3]), d1[0], pk_fma(bc(e[4]), d1[1], bc(e[5]) * d1[2]));
+                const v2f v2 = pk_fma(bc(e[6]), d1[0], pk_fma(bc(e[7]), d1[1], bc(e[8]) * d1[2]));
+                const v2f w0 = pk_fma(bc(e[0]), d2[0], pk_fma(bc(e[3]), d2[1], bc(e[6]) * d2[2]));
+                const v2f w1 = pk_fma(bc(e[1]), d2[0], pk_fma(bc(e[4]), d2[1], bc(e[7]) * d2[2]));
+                const v2f w2 = pk_fma(bc(e[2]), d2[0], pk_fma(bc(e[5]), d2[1], bc(e[8]) * d2[2]));
+                const v2f C = pk_fma(d2[0], v0, pk_fma(d2[1], v1, d2[2] * v2));
+                const v2f a0 = pk_fma(n2[0], v0, pk_fma(n2[2], v1, n2[4] * v2));
+                const v2f a1 = pk_fma(n2[1], v0, pk_fma(n2[3], v1, n2[5] * v2));
+                const v2f b0 = pk_fma(n1[0], w0, pk_fma(n1[2], w1, n1[4] * w2));
+                const v2f b1 = pk_fma(n1[1], w0, pk_fma(n1[3], w1, n1[5] * w2));
+                const v2f S = pk_fma(b1, b1, pk_fma(b0, b0, pk_fma(a1, a1, a0 * a0)));
+                const v2f L = C * C;
+                const v2f R = pk_fma(bc(kPfTangentT), S, v2f{bnd[0], bnd[1]});
+#pragma unroll
+                for (int p = 0; p < P; ++p) {
+                    m[p] = vmask[p] & ~__builtin_amdgcn_ballot_w64(L[p] > R[p]);
+                    any |= m[p];
+                }
+            }
+            if (any) { // wave-uniform: append the survivors, ordered by (slot, lane)
+#pragma unroll
+                for (int p = 0; p < P; ++p) {
+                    if (m[p]) {
+                        const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(m[p] >> 32),
+                                                                         __builtin_amdgcn_mbcnt_lo((uint32_t)m[p], 0u));
+                        if ((m[p] >> lane) & 1u)
+                            queue[(qtail + below) & (kQueueCap - 1)] = (uint16_t)((g << 9) | (uint32_t)(p * 64 + lane));
+                        qtail += (uint32_t)__popcll(m[p]);
+                    }
+                }
+                while (qtail - qhead >= 64u)
+                    drain(64u);
+            }
+        };
+        auto fetch = [&](float(&r)[15], uint32_t g) {
+            const uniform_f32_ptr sp = sh + (size_t)(kb + g) * 16;
+#pragma unroll
+            for (int i = 0; i < 15; ++i)
+                r[i] = sp[i];
+        };
+
+        float ra[15], rb[15];
+        fetch(ra, 0);
+        for (uint32_t g = 0; g < gn; g += 2) {
+            const bool two = g + 1 < gn;
+            if (two)
+                fetch(rb, g + 1);
+            step(ra, g);
+            if (two) {
+                if (g + 2 < gn)
+                    fetch(ra, g + 2);
+                step(rb, g + 1);
+            }
+        }
+        while (qtail != qhead)
+            drain(min(64u, qtail - qhead));
+        if (itail != ihead)
+            add_inliers(itail - ihead);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        if ((uint32_t)lane < gn) {
+            const size_t o = (size_t)chunk * hyp_capacity + kb + lane;
+            part_score[o] = acc_s[lane];
+            part_count[o] = acc_c[lane];
+        }
+        ticket = (uint32_t)__builtin_amdgcn_readfirstlane((int)pending);
+    }
+}
+__global__ __launch_bounds__(kQueueThreads) void k_score_tangent(PointSet pts, const float *__restrict__ shadow,
+                                                                  const double *__restrict__ compact64,
+                                                                  const uint32_t *__restrict__ num_hyp_ptr, uint32_t hyp_capacity,
+                                                                  double thr2, PrefilterArgs pf, uint32_t *__restrict__ part_count,
+                                                                  double *__restrict__ part_score) {
+    score_tangent_body(pts, shadow, compact64, num_hyp_ptr, hyp_capacity, thr2, pf, part_count, part_score, blockIdx.x, blockIdx.y,
+                       gridDim.x);
 }
 
 // ---- absolute pose: the pre-filter on the matrix cores ----------------------------------------------------------
@@ -1521,9 +1767,7 @@ template <int EST> __device__ __forceinline__ void score_seq_body(const SeqScore
                 r2v[j] = 0.0;
                 if (i < a.pts.n) {
                     double x[ND];
-#pragma unroll
-                    for (int d = 0; d < ND; ++d)
-                        x[d] = a.pts.a[d][i];
+                    load_point<EST>(a.pts, i, x);
                     double r2;
                     const bool in = eval_point<EST>(M, x, a.thr2, r2);
                     if constexpr (EST == EST_ABS) {
@@ -1632,6 +1876,10 @@ __device__ __forceinline__ void mask_body(const PointSet &pts, const double *mod
     bool in;
     if constexpr (EST == EST_ABS) {
         in = reproj_mask(M, pts.a[0][i], pts.a[1][i], pts.a[2][i], pts.a[3][i], pts.a[4][i], thr2);
+    } else if constexpr (EST == EST_RELT) { // get_tangent_sampson_inliers, utils.cc:541-568: the score's own decision
+        double r2, pt[18];
+        load_point<EST>(pts, i, pt);
+        in = eval_point<EST>(M, pt, thr2, r2);
     } else {
         double r2;
         const double pt[4] = {pts.a[0][i], pts.a[1][i], pts.a[2][i], pts.a[3][i]};
@@ -1663,7 +1911,7 @@ __device__ __forceinline__ void lm_start_params(int est, const LMTask &T, double
     }
     for (int i = 0; i < kParamDoubles; ++i)
         cur[i] = 0.0;
-    if (est == EST_ABS || est == EST_REL) {
+    if (est == EST_ABS || est == EST_REL || est == EST_RELT) {
         for (int i = 0; i < 7; ++i)
             cur[i] = T.start_record[i];
     } else {
@@ -1901,10 +2149,16 @@ template <int EST> __global__ __launch_bounds__(kLMThreads) void k_lm(LMTask *ta
     // (tasks of several problems may share a launch: each stages its own points if they fit the launch's dynamic LDS)
     const bool lds_points = sizeof(double) * ND * (size_t)pts_global.n <= (size_t)lds_bytes;
     if (lds_points) {
-        for (int d = 0; d < ND; ++d) {
-            for (uint32_t i = threadIdx.x; i < pts_global.n; i += kLMThreads)
-                s_lm_points[(size_t)d * pts_global.n + i] = pts_global.a[d][i];
-            pts.a[d] = s_lm_points + (size_t)d * pts_global.n;
+        if constexpr (EST == EST_RELT) { // one block of ND arrays behind a[0]
+            for (size_t i = threadIdx.x; i < (size_t)ND * pts_global.n; i += kLMThreads)
+                s_lm_points[i] = pts_global.a[0][i];
+            pts.a[0] = s_lm_points;
+        } else {
+            for (int d = 0; d < ND; ++d) {
+                for (uint32_t i = threadIdx.x; i < pts_global.n; i += kLMThreads)
+                    s_lm_points[(size_t)d * pts_global.n + i] = pts_global.a[d][i];
+                pts.a[d] = s_lm_points + (size_t)d * pts_global.n;
+            }
         }
     }
 
@@ -2034,6 +2288,18 @@ template <int EST> __global__ __launch_bounds__(kLMThreads) void k_lm(LMTask *ta
                     accumulate2<K>(acc, loss, f0, f1, Jf, cntj);
                     accumulate2<K>(acc, loss, g0, g1, Jb, cntj);
                 }
+            } else if constexpr (EST == EST_RELT) {
+                double pt[ND];
+                load_point<EST>(pts, i, pt);
+                if (!jacobian_pass) {
+                    const double r = R::residual(ctx, pt);
+                    racc += 1.0 * loss_value(loss, r * r);
+                    cnt++;
+                } else {
+                    double J[K];
+                    const double r = R::jacobian(ctx, pt, J);
+                    accumulate1<K>(acc, loss, r, J, cntj);
+                }
             } else {
                 const double a0 = pts.a[0][i], a1 = pts.a[1][i], b0 = pts.a[2][i], b1 = pts.a[3][i];
                 if (!jacobian_pass) {
@@ -2094,6 +2360,18 @@ template <int EST> __global__ __launch_bounds__(kLMThreads) void k_lm(LMTask *ta
                         R::jacobian(ctx, a0, a1, b0, b1, f0, f1, Jf, g0, g1, Jb);
                         accumulate2<K>(term[0], loss, f0, f1, Jf, cnj);
                         accumulate2<K>(term[SUB - 1], loss, g0, g1, Jb, cnj);
+                    }
+                } else if constexpr (EST == EST_RELT) {
+                    double pt[ND];
+                    load_point<EST>(pts, i, pt);
+                    if (!jacobian_pass) {
+                        const double r = R::residual(ctx, pt);
+                        cterm[0] += 1.0 * loss_value(loss, r * r);
+                        cn++;
+                    } else {
+                        double J[K];
+                        const double r = R::jacobian(ctx, pt, J);
+                        accumulate1<K>(term[0], loss, r, J, cnj);
                     }
                 } else {
                     const double a0 = pts.a[0][i], a1 = pts.a[1][i], b0 = pts.a[2][i], b1 = pts.a[3][i];
@@ -2208,7 +2486,7 @@ template <int EST> __global__ __launch_bounds__(kLMThreads) void k_lm(LMTask *ta
         // wavefronts of them.  Which lane accumulates a correspondence changes, the set of terms does not; the reduction
         // over lanes and wavefronts below is in fixed order as before.
         const bool zero_weights = loss.type == LOSS_TRUNCATED || loss.type == LOSS_TRUNCATED_CAUCHY;
-        if (jac && zero_weights && !(EST == EST_REL && mask)) {
+        if (jac && zero_weights && !((EST == EST_REL || EST == EST_RELT) && mask)) {
             const int lane = threadIdx.x & 63;
             uint32_t *const q = s_queue[threadIdx.x >> 6];
             uint32_t qn = 0; // wave-uniform: correspondences waiting, q[0 .. qn)
@@ -2233,6 +2511,15 @@ template <int EST> __global__ __launch_bounds__(kLMThreads) void k_lm(LMTask *ta
                             racc += 1.0 * loss_value(loss, f0 * f0 + f1 * f1);
                             racc += 1.0 * loss_value(loss, g0 * g0 + g1 * g1);
                             cnt += 2;
+                        }
+                    } else if constexpr (EST == EST_RELT) {
+                        double pt[ND];
+                        load_point<EST>(pts, i, pt);
+                        const double r = R::residual(ctx, pt);
+                        keep = loss_weight(loss, r * r) != 0;
+                        if (res) {
+                            racc += 1.0 * loss_value(loss, r * r);
+                            cnt++;
                         }
                     } else {
                         const double r = R::residual(ctx, pts.a[0][i], pts.a[1][i], pts.a[2][i], pts.a[3][i]);
@@ -2298,7 +2585,7 @@ template <int EST> __global__ __launch_bounds__(kLMThreads) void k_lm(LMTask *ta
     };
 
     // The initial cost and the first iteration's normal equations are evaluated at the same point with the same loss: one sweep.
-    if constexpr (EST == EST_REL) {
+    if constexpr (EST == EST_REL || EST == EST_RELT) {
         if (threadIdx.x == 0)
             R::prepare_params(cur);
         __syncthreads();
@@ -2317,7 +2604,7 @@ template <int EST> __global__ __launch_bounds__(kLMThreads) void k_lm(LMTask *ta
     while (!ctl.done) {
         const bool fresh = ctl.rejac != 0;
         if (fresh && !have_next) {
-            if constexpr (EST == EST_REL) {
+            if constexpr (EST == EST_REL || EST == EST_RELT) {
                 if (threadIdx.x == 0)
                     R::prepare_params(cur);
                 __syncthreads();
@@ -2339,7 +2626,7 @@ template <int EST> __global__ __launch_bounds__(kLMThreads) void k_lm(LMTask *ta
 #endif
             if (!ctl.done) {
                 R::step(cur, ctx, ctl.sol, trial);
-                if constexpr (EST == EST_REL)
+                if constexpr (EST == EST_REL || EST == EST_RELT)
                     if (fuse)
                         R::prepare_params(trial); // (the tangent basis of the Jacobian at the trial point: what the next
                                                   // iteration computes from the accepted parameters)
@@ -2991,13 +3278,24 @@ __global__ __launch_bounds__(kLM2Threads) void k_lm2(PointSet pts, LMTask *tasks
         return hipErrorInvalidValue;                                                                                   \
     }
 
-size_t generate_stage_bytes(int est, uint32_t num_iters) { return est == EST_REL ? rel_stage_bytes(num_iters) : 0; }
+// ... and for the kernels that exist for EST_RELT as well (k_score_seq, k_mask, k_lm: no k_generate / k_lm_ordered / k_lm2 of that kind)
+#define PL_DISPATCH_EST5(est, ...)                                                                                    \
+    if ((est) == EST_RELT) {                                                                                           \
+        constexpr int E = EST_RELT;                                                                                    \
+        __VA_ARGS__;                                                                                                    \
+    } else {                                                                                                           \
+        PL_DISPATCH_EST(est, __VA_ARGS__)                                                                              \
+    }
+
+size_t generate_stage_bytes(int est, uint32_t num_iters) { return (est == EST_REL || est == EST_RELT) ? rel_stage_bytes(num_iters) : 0; }
 hipError_t launch_generate(int est, const GenerateArgs &a, hipStream_t stream) {
     if (a.num_iters == 0)
         return hipSuccess;
     const dim3 grid((a.num_iters + 63) / 64), block(64);
     if (est == EST_REL && a.stage) // four stages over a structure-of-arrays workspace (gen_rel.hip)
         return launch_generate_rel(a, stream);
+    if (est == EST_RELT) // (the staged generator alone serves the tangent-Sampson bearings)
+        return a.stage ? launch_generate_rel(a, stream, true) : hipErrorInvalidValue;
     PL_DISPATCH_EST(est, k_generate<E><<<grid, block, 0, stream>>>(a));
     return hipGetLastError();
 }
@@ -3021,6 +3319,11 @@ hipError_t launch_solve_batch(int est, const double *in, uint32_t np, double *mo
 // per-hypothesis overhead): pairs of points share packed instructions, an odd point costs as much as a pair.
 static void score_shape(int est, uint32_t n, bool streaming, bool mfma, uint32_t &chunks, int &P) {
     const uint32_t lanes = streaming ? 64u : (uint32_t)kScoreThreads;
+    if (est == EST_RELT) { // k_score_tangent: a fixed chunk (18 fp32 operands per correspondence bound the lane's share)
+        P = kTangentP;
+        chunks = std::max<uint32_t>(1u, (n + (uint32_t)kTangentChunk - 1) / (uint32_t)kTangentChunk);
+        return;
+    }
     if (streaming && mfma && (est == EST_REL || est == EST_FUND)) {
         // k_score_mfma2: PG = 2 P groups of 32 correspondences per chunk; relative pose keeps the bearings in LDS as
         // well and stops at 320 correspondences per workgroup (two workgroups per CU)
@@ -3057,7 +3360,7 @@ static void score_shape(int est, uint32_t n, bool streaming, bool mfma, uint32_t
 }
 bool score_uses_mfma(int est, uint32_t n_points, const PrefilterArgs &pf) {
     static const bool off = std::getenv("POSELIB_AMD_NO_MFMA") != nullptr;
-    if (off || !pf.enabled || n_points < 1024u)
+    if (off || !pf.enabled || n_points < 1024u || est == EST_RELT) // (tangent Sampson: no matrix-core form)
         return false;
     if (est == EST_ABS)
         return pf.g16 > 0.f && pf.thr <= 1.0f;
@@ -3196,10 +3499,20 @@ hipError_t launch_score_seq(int est, const SeqScoreArgs &a, hipStream_t stream) 
     if (a.cap == 0)
         return hipSuccess;
     const dim3 grid(std::min<uint32_t>(a.cap, 128u)), block(kSeqThreads); // (candidate lists hold a few dozen entries)
-    PL_DISPATCH_EST(est, k_score_seq<E><<<grid, block, 0, stream>>>(a));
+    PL_DISPATCH_EST5(est, k_score_seq<E><<<grid, block, 0, stream>>>(a));
     return hipGetLastError();
 }
+int tangent_score_chunk() { return kTangentChunk; }
 hipError_t launch_score(int est, const ScoreArgs &a, uint32_t slices, hipStream_t stream) {
+    if (est == EST_RELT) {
+        if (!a.shadow || !a.compact64)
+            return hipErrorInvalidValue; // only the streaming form exists
+        const uint32_t chunks = score_chunks(est, a.pts.n, true, false);
+        const dim3 qgrid(std::max<uint32_t>(1u, slices * (uint32_t)kScoreThreads / (uint32_t)kQueueThreads), chunks);
+        k_score_tangent<<<qgrid, dim3(kQueueThreads), 0, stream>>>(a.pts, a.shadow, a.compact64, a.num_hyp, a.hyp_capacity, a.thr2, a.pf,
+                                                                   a.part_count, a.part_score);
+        return hipGetLastError();
+    }
     PL_DISPATCH_EST(est, return launch_score_est<E>(a, slices, stream));
     return hipSuccess;
 }
@@ -3237,7 +3550,7 @@ bool lm_sums_ordered(int est) {
     if (tl_lm_force_ordered)
         return true;
     const int m = get_lm_mode();
-    return m == 1 || (m == 0 && est == EST_FUND);
+    return est != EST_RELT && (m == 1 || (m == 0 && est == EST_FUND)); // (tangent Sampson: k_lm alone, launch_lm_tasks)
 }
 #ifdef PL_LM_PROFILE
 extern "C" int pl_debug_lm_profile(unsigned long long *out16, int reset) {
@@ -3254,13 +3567,13 @@ extern "C" int pl_debug_lm_profile(unsigned long long *out16, int reset) {
 hipError_t launch_lm_tasks(int est, LMTask *tasks, uint32_t num_tasks, uint32_t max_points, hipStream_t stream) {
     if (num_tasks == 0)
         return hipSuccess;
-    if (est < 0 || est > 3)
+    if (est < 0 || est > EST_RELT)
         return hipErrorInvalidValue;
-    const int ordered = lm_sums_ordered(est) ? 1 : 0;
+    const int ordered = lm_sums_ordered(est) ? 1 : 0; // (never for EST_RELT: k_lm alone serves it)
     // stage the points in LDS when they fit next to the kernel's static LDS (160 KB per CU, one workgroup per CU); tasks
     // of a mixed launch whose points do not fit the launch's dynamic LDS read them from L2
     // (a request the points do not fit into would only keep every other workgroup off the CU: no staging then)
-    static std::atomic<int> dyn_limit[2][4] = {{{-1}, {-1}, {-1}, {-1}}, {{-1}, {-1}, {-1}, {-1}}}; // bytes of dynamic LDS the kernel may ask for
+    static std::atomic<int> dyn_limit[2][5] = {{{-1}, {-1}, {-1}, {-1}, {-1}}, {{-1}, {-1}, {-1}, {-1}, {-1}}}; // bytes of dynamic LDS the kernel may ask for
     int limit = dyn_limit[ordered][est].load(std::memory_order_acquire);
     if (limit < 0) {
         hipFuncAttributes fa;
@@ -3268,7 +3581,7 @@ hipError_t launch_lm_tasks(int est, LMTask *tasks, uint32_t num_tasks, uint32_t 
         if (ordered) {
             PL_DISPATCH_EST(est, e = hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&k_lm_ordered<E>)));
         } else {
-            PL_DISPATCH_EST(est, e = hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&k_lm<E>)));
+            PL_DISPATCH_EST5(est, e = hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&k_lm<E>)));
         }
         if (e != hipSuccess)
             return e;
@@ -3279,8 +3592,8 @@ hipError_t launch_lm_tasks(int est, LMTask *tasks, uint32_t num_tasks, uint32_t 
                 PL_DISPATCH_EST(est, e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_lm_ordered<E>),
                                                              hipFuncAttributeMaxDynamicSharedMemorySize, limit));
             } else {
-                PL_DISPATCH_EST(est, e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_lm<E>),
-                                                             hipFuncAttributeMaxDynamicSharedMemorySize, limit));
+                PL_DISPATCH_EST5(est, e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_lm<E>),
+                                                              hipFuncAttributeMaxDynamicSharedMemorySize, limit));
             }
             if (e != hipSuccess)
                 return e;
@@ -3292,7 +3605,7 @@ hipError_t launch_lm_tasks(int est, LMTask *tasks, uint32_t num_tasks, uint32_t 
     if (ordered) {
         PL_DISPATCH_EST(est, k_lm_ordered<E><<<dim3(num_tasks), dim3(kLMThreads), bytes, stream>>>(tasks, (uint32_t)bytes));
     } else {
-        PL_DISPATCH_EST(est, k_lm<E><<<dim3(num_tasks), dim3(kLMThreads), bytes, stream>>>(tasks, (uint32_t)bytes));
+        PL_DISPATCH_EST5(est, k_lm<E><<<dim3(num_tasks), dim3(kLMThreads), bytes, stream>>>(tasks, (uint32_t)bytes));
     }
     return hipGetLastError();
 }
@@ -3467,7 +3780,7 @@ hipError_t launch_mask(int est, const PointSet &pts, const double *model, double
     if (pts.n == 0)
         return hipSuccess;
     const dim3 grid((pts.n + 255) / 256), block(256);
-    PL_DISPATCH_EST(est, k_mask<E><<<grid, block, 0, stream>>>(pts, model, thr2, mask, host_mask));
+    PL_DISPATCH_EST5(est, k_mask<E><<<grid, block, 0, stream>>>(pts, model, thr2, mask, host_mask));
     return hipGetLastError();
 }
 

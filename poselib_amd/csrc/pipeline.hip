@@ -1012,6 +1012,27 @@ __global__ __launch_bounds__(256) void k_prepare(const double *__restrict__ a_ra
                                                  unsigned long long *absmax_bits) {
     prepare_body(a_raw, b_raw, n, g, soa, absmax_bits);
 }
+// mode 3 (tangent Sampson, EST_RELT): robust.cc:256-265 + Camera::unproject_with_jac per image -> the problem's 18 arrays
+// d1[3] d2[3] M1[6] M2[6].  A kernel of its own: the Jacobian's registers stay out of k_prepare / k_prepare_g.
+__global__ __launch_bounds__(256) void k_prepare_tangent(const double *__restrict__ a_raw, const double *__restrict__ b_raw, uint32_t n,
+                                                         PrepareArgs g, double *__restrict__ soa) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n)
+        return;
+    PL_UNROLL
+    for (int im = 0; im < 2; ++im) {
+        const double *raw = im ? b_raw : a_raw;
+        Vec3 d;
+        double M[6];
+        camera_unproject_with_jac(im ? g.cam2 : g.cam1, raw[2 * (size_t)i] * g.scale, raw[2 * (size_t)i + 1] * g.scale, d, M);
+        soa[(size_t)(3 * im + 0) * n + i] = d.x;
+        soa[(size_t)(3 * im + 1) * n + i] = d.y;
+        soa[(size_t)(3 * im + 2) * n + i] = d.z;
+        PL_UNROLL
+        for (int k = 0; k < 6; ++k)
+            soa[(size_t)(6 + 6 * im + k) * n + i] = M[k];
+    }
+}
 __global__ __launch_bounds__(256) void k_prepare_g(const PrepareGroupArgs *pa) {
     const PrepareGroupArgs &g = pa[blockIdx.z];
     if (blockIdx.x * 256u >= g.n)
@@ -1103,6 +1124,10 @@ hipError_t launch_prepare(const double *a_raw, const double *b_raw, uint32_t n, 
                           unsigned long long *absmax_bits, hipStream_t stream) {
     if (n == 0)
         return hipSuccess;
+    if (args.mode == 3) {
+        k_prepare_tangent<<<dim3((n + 255) / 256), dim3(256), 0, stream>>>(a_raw, b_raw, n, args, soa);
+        return hipGetLastError();
+    }
     k_prepare<<<dim3((n + 255) / 256), dim3(256), 0, stream>>>(a_raw, b_raw, n, args, soa, absmax_bits);
     return hipGetLastError();
 }

@@ -12,6 +12,7 @@ namespace pl {
 // Correspondences of one problem, structure-of-arrays in HBM, fp64.
 //   absolute pose : a[0..4] = x, y (normalised image plane), X, Y, Z
 //   two-view      : a[0..3] = x1, y1, x2, y2
+//   tangent Sampson (EST_RELT): a[0] = the block of 18 arrays d1[3] d2[3] M1[6] M2[6], component c at a[0] + c * n
 struct PointSet {
     const double *a[5];
     uint32_t n;
@@ -26,9 +27,9 @@ constexpr int kLMSeqPoints = 256; // up to this many correspondences k_lm sums i
 #endif
 constexpr int kLMThreads = PL_LM_THREADS; // k_lm: wavefront 0 adds the term rows in order, the others produce them (kernels.hip)
 
-PL_HD constexpr int sample_size(int est) { return est == EST_ABS ? 3 : est == EST_REL ? 5 : est == EST_FUND ? 7 : 4; }
-PL_HD constexpr int max_models(int est) { return est == EST_ABS ? 4 : est == EST_REL ? 40 : est == EST_FUND ? 3 : 1; }
-PL_HD constexpr int point_doubles(int est) { return est == EST_ABS ? 5 : 4; }
+PL_HD constexpr int sample_size(int est) { return est == EST_ABS ? 3 : (est == EST_REL || est == EST_RELT) ? 5 : est == EST_FUND ? 7 : 4; }
+PL_HD constexpr int max_models(int est) { return est == EST_ABS ? 4 : (est == EST_REL || est == EST_RELT) ? 40 : est == EST_FUND ? 3 : 1; }
+PL_HD constexpr int point_doubles(int est) { return est == EST_ABS ? 5 : est == EST_RELT ? 18 : 4; }
 
 struct BatchCtl;
 struct GenerateArgs {
@@ -151,7 +152,8 @@ hipError_t launch_generate(int est, const GenerateArgs &a, hipStream_t stream);
 size_t generate_stage_bytes(int est, uint32_t num_iters); // workspace of the staged 5-point generator (0: none)
 // the staged 5-point generator (gen_rel.hip): a.stage = workspace of rel_stage_bytes(a.num_iters)
 size_t rel_stage_bytes(uint32_t num_iters);
-hipError_t launch_generate_rel(const GenerateArgs &a, hipStream_t stream);
+// tangent: the correspondences are an EST_RELT block and its bearings are the solver's input (k_rel_front_tangent)
+hipError_t launch_generate_rel(const GenerateArgs &a, hipStream_t stream, bool tangent = false);
 struct GroupArgs;
 hipError_t launch_group_generate_rel(const GroupArgs *args, uint32_t max_B, uint32_t G, hipStream_t stream);
 // Front-end pre-processing on the device (robust.cc:40-46, 286-292; utils.cc:584-644 per-point part): AoS user
@@ -162,6 +164,8 @@ hipError_t launch_group_generate_rel(const GroupArgs *args, uint32_t max_B, uint
 struct PrepareArgs {
     int32_t mode;          // 0: a -> unproject(cam1), b = N x 3 copied; 1: a -> unproject(cam1), b -> unproject(cam2);
                            // 2: a -> (a - c1) / scale, b -> (b - c2) / scale   (subtract only if `centred`)
+                           // 3: tangent Sampson - a, b multiplied by `scale`, then bearing and Jacobian of the un-projection
+                           //    through cam1 / cam2 (already rescaled): the 18 arrays of an EST_RELT problem
     int32_t centred;
     CameraParams cam1, cam2;
     double c1x, c1y, c2x, c2y, scale;
@@ -202,6 +206,7 @@ hipError_t launch_lm2(int est, const PointSet &pts, LMTask *tasks, uint32_t num_
 // chunks = ceil(n / (kScoreThreads * P)); P is chosen inside from n (returned through *chunks_out)
 uint32_t score_chunks(int est, uint32_t n_points, bool prefilter, bool mfma = false);
 hipError_t launch_score(int est, const ScoreArgs &a, uint32_t slices, hipStream_t stream);
+int tangent_score_chunk(); // correspondences per chunk of k_score_tangent (EST_RELT)
 // num_models[iters] -> slots (compact list of record indices in (iteration, model) order) + count
 hipError_t launch_lm(int est, const PointSet &pts, LMTask *tasks, uint32_t num_tasks, hipStream_t stream);
 // host_mask (pinned, device-mapped; may be null): the kernel writes a second copy there itself - no copy dispatch

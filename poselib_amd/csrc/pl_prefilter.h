@@ -112,6 +112,25 @@
 //    thr = 1e-3 on normalised coordinates the band is 1.1 thresholds wide.  Model side of the slack slot = -inf: NaN model (no
 //    inliers); +inf: matrix outside [1e-18, 1e18] (every point evaluated exactly).  Correspondences with a coordinate beyond
 //    8 (or NaN) carry zero operands and the largest finite slack: never excluded.
+//  * tangent Sampson (k_score_tangent; pl_score.h tangent_sampson_sq), model E, correspondence (d1, d2, M1, M2):  inlier =>
+//    C^2 < thr2 D  with  C = d2^T E d1,  D = |M2^T E d1|^2 + |M1^T E^T d2|^2.  Both sides are homogeneous of degree two in E, so
+//    the kernel first multiplies the fp32 shadow of E by the power of two s that brings its padded max-abs entry fm into
+//    [1/2, 1) (exact; the per-model term of this form), and the threshold is folded into the correspondence: N = thr M, rounded
+//    to fp32 once, so that the test reads  C^2 < S,  S = |N2^T v|^2 + |N1^T w|^2,  v = E d1,  w = E^T d2, with every |E_ij| < 1.
+//    With  p1 = |d1|_1,  p2 = |d2|_1,  m1 = sum |N1_ij|,  m2 = sum |N2_ij|  and three-term FMA dot products (error below
+//    5u sum |terms|, input roundings included):  |v^_i - v_i| <= 5u p1,  |w^_j - w_j| <= 5u p2,
+//        |C^ - C| <= 5u p1 p2 + 5u p1 p2 (1 + 5u)            <= e_C = 16u p1 p2
+//        |a^_k - a_k| <= 5u p1 m2 + 5u p1 m2 (1 + 5u)        <= e_a = 16u p1 m2        (a = N2^T v;  b = N1^T w:  e_b = 16u p2 m1)
+//    (the reference multiplies (M^T E) d, the filter M^T (E d): the same numbers up to fp64 roundings, which the margins absorb).
+//    As in the Sampson form, with d = 1/64 and h = 1/16:  S <= (1 + d)(1 + 6u) S^ + 130 (e_a^2 + e_b^2)  (S^ is a sum of four
+//    squares, four roundings),  (|C^| - e_C)^2 >= (15/16) C^^2 - 15 e_C^2, so
+//        C^^2  >  T S^ + W,      T = (16/15)(1 + d)(1 + 96u),      W = (16/15)(1 + 96u)(16u)^2 (130 (p1^2 m2^2 + p2^2 m1^2) + 16 p1^2 p2^2)
+//    proves C^2 > (1 + 64u) S, a certain outlier; W >= 17 e_C^2 forces |C^| > e_C, and the 96u cover the roundings of C^ C^, of
+//    the final FMA and the reference's own.  W depends on the correspondence alone.  Range of the derivation: fm in
+//    [1e-18, 1e18] (else the shadow carries +inf: every correspondence evaluated exactly), every |d_j| <= 16 (a field of view
+//    of 173 degrees through the identity camera; unit bearings always), max |N_ij| in [1e-6, 1e6] (no square of an fp32 value
+//    leaves the normal range: a <= 3 * 1e6 * 48, W >= 1e-22); a correspondence outside it, or with a NaN, carries W = +inf and
+//    is never excluded.  NaN models are skipped (no inliers).
 //  * models with a NaN entry have no inliers at all (see store_shadow); models or thresholds outside the range in
 //    which fp32 keeps its relative accuracy (max-abs entry outside [1e-18, 1e18]) get an infinite slack, i.e. every
 //    point is evaluated exactly.
@@ -238,6 +257,64 @@ PL_HD bool pf_sampson_outlier(const float *r, float gf /* 16u * fm */, float t1,
     const float C = fmaf(b0, Ea0, fmaf(b1, Ea1, Ea2));
     const float S = fmaf(Eb1, Eb1, fmaf(Eb0, Eb0, fmaf(Ea1, Ea1, Ea0 * Ea0)));
     return C * C > fmaf(t1, S, (gf * gf) * w);
+}
+
+// ---- tangent Sampson (header comment) ----
+constexpr float kPfTangentT = 1.08334f;   // >= (16/15)(1 + 1/64)(1 + 96u) = 1.0833395...
+constexpr float kPfTangentW = 9.7014e-13f; // >= (16/15)(1 + 96u) 2^-40 = 9.70134e-13
+// the power of two s with s * fm in [1/2, 1); fm: the shadow's padded max-abs entry, a normal fp32 number in [1e-18, 1.1e18]
+PL_HD float pf_tangent_scale(float fm) {
+    union {
+        float f;
+        uint32_t u;
+    } a, b;
+    a.f = fm;
+    b.u = (253u - ((a.u >> 23) & 0xffu)) << 23;
+    return b.f;
+}
+// the correspondence's fp32 operands f[18] = d1, d2, thr M1, thr M2 and its slack W (+inf: never excluded)
+PL_HD float pf_tangent_point(const double *pt /* 18 */, double thr, float *f) {
+    double p1 = 0, p2 = 0, m1 = 0, m2 = 0, dmax = 0, nmax = 0;
+    bool nan = false;
+    PL_UNROLL
+    for (int j = 0; j < 3; ++j) {
+        const double a = fabs(pt[j]), b = fabs(pt[3 + j]);
+        p1 += a, p2 += b;
+        dmax = fmax(dmax, fmax(a, b));
+        nan = nan || a != a || b != b;
+        f[j] = (float)pt[j], f[3 + j] = (float)pt[3 + j];
+    }
+    PL_UNROLL
+    for (int j = 0; j < 6; ++j) {
+        const double n1 = thr * pt[6 + j], n2 = thr * pt[12 + j];
+        const double a = fabs(n1), b = fabs(n2);
+        m1 += a, m2 += b;
+        nmax = fmax(nmax, fmax(a, b));
+        nan = nan || a != a || b != b;
+        f[6 + j] = (float)n1, f[12 + j] = (float)n2;
+    }
+    if (nan || !(dmax <= 16.0) || !(nmax >= 1e-6 && nmax <= 1e6))
+        return __builtin_huge_valf();
+    const float fp1 = pf_up((float)p1), fp2 = pf_up((float)p2), fm1 = pf_up((float)m1), fm2 = pf_up((float)m2);
+    const float a = pf_up(fp1 * fm2), b = pf_up(fp2 * fm1), c = pf_up(fp1 * fp2);
+    return pf_up(kPfTangentW * pf_up(pf_up(130.f * pf_up(pf_up(a * a) + pf_up(b * b))) + pf_up(16.f * pf_up(c * c))));
+}
+// e: the model's shadow matrix times pf_tangent_scale (row-major); f, W: pf_tangent_point.  true = certainly not an inlier
+PL_HD bool pf_tangent_outlier(const float *e, const float *f, float W) {
+    const float *d1 = f, *d2 = f + 3, *n1 = f + 6, *n2 = f + 12;
+    const float v0 = fmaf(e[0], d1[0], fmaf(e[1], d1[1], e[2] * d1[2]));
+    const float v1 = fmaf(e[3], d1[0], fmaf(e[4], d1[1], e[5] * d1[2]));
+    const float v2 = fmaf(e[6], d1[0], fmaf(e[7], d1[1], e[8] * d1[2]));
+    const float w0 = fmaf(e[0], d2[0], fmaf(e[3], d2[1], e[6] * d2[2]));
+    const float w1 = fmaf(e[1], d2[0], fmaf(e[4], d2[1], e[7] * d2[2]));
+    const float w2 = fmaf(e[2], d2[0], fmaf(e[5], d2[1], e[8] * d2[2]));
+    const float C = fmaf(d2[0], v0, fmaf(d2[1], v1, d2[2] * v2));
+    const float a0 = fmaf(n2[0], v0, fmaf(n2[2], v1, n2[4] * v2));
+    const float a1 = fmaf(n2[1], v0, fmaf(n2[3], v1, n2[5] * v2));
+    const float b0 = fmaf(n1[0], w0, fmaf(n1[2], w1, n1[4] * w2));
+    const float b1 = fmaf(n1[1], w0, fmaf(n1[3], w1, n1[5] * w2));
+    const float S = fmaf(b1, b1, fmaf(b0, b0, fmaf(a1, a1, a0 * a0)));
+    return C * C > fmaf(kPfTangentT, S, W);
 }
 
 // ---- Sampson, fp16 / MFMA form: operands (header comment).  Portable fp16 conversions: the kernels, the operand builder

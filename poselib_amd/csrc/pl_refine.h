@@ -213,7 +213,8 @@ PL_HD FisheyeParams fisheye_params(const CameraParams &c) {
     return f;
 }
 // camera_models.cc:1177-1201, 1628-1652, 1766-1790 followed by hnormalized (camera_models.h:98-102)
-PL_HD void fisheye_unproject(const CameraParams &c, double px, double py, double &ox, double &oy) {
+// ... the unit bearing itself (the models' 3-D unproject)
+PL_HD Vec3 fisheye_unproject_bearing(const CameraParams &c, double px, double py) {
     const FisheyeParams f = fisheye_params(c);
     const double ux = (px - f.cx) / f.fx, uy = (py - f.cy) / f.fy;
     const double rd = sqrt(ux * ux + uy * uy);
@@ -231,7 +232,10 @@ PL_HD void fisheye_unproject(const CameraParams &c, double px, double py, double
         b.y = uy;
         b.z = sqrt(1 - rd * rd);
     }
-    b = normalized(b);
+    return normalized(b);
+}
+PL_HD void fisheye_unproject(const CameraParams &c, double px, double py, double &ox, double &oy) {
+    const Vec3 b = fisheye_unproject_bearing(c, px, py);
     ox = b.x / b.z;
     oy = b.y / b.z;
 }
@@ -284,8 +288,8 @@ template <bool JAC> PL_HD void fisheye_project(const CameraParams &c, Vec3 Z, do
     }
 }
 
-// pixel -> normalised image plane (camera_models.h:98-102: unit bearing first, then hnormalized)
-PL_HD void camera_unproject(const CameraParams &c, double px, double py, double &ox, double &oy) {
+// pixel -> bearing, the models' 3-D unproject: unit length, except the identity camera's (x, y, 1) (camera_models.cc:2724-2726)
+PL_HD Vec3 camera_unproject_bearing(const CameraParams &c, double px, double py) {
     double u, v;
     switch (c.model_id) {
     case CAM_SIMPLE_PINHOLE:
@@ -332,14 +336,15 @@ PL_HD void camera_unproject(const CameraParams &c, double px, double py, double 
     case CAM_OPENCV_FISHEYE:
     case CAM_SIMPLE_RADIAL_FISHEYE:
     case CAM_RADIAL_FISHEYE:
-        fisheye_unproject(c, px, py, ox, oy);
-        return;
+        return fisheye_unproject_bearing(c, px, py);
     default: // CAM_NULL: bearing is (x, y, 1) un-normalised
-        ox = px / 1.0;
-        oy = py / 1.0;
-        return;
+        return v3(px, py, 1.0);
     }
-    const Vec3 b = normalized(v3(u, v, 1.0));
+    return normalized(v3(u, v, 1.0));
+}
+// pixel -> normalised image plane (camera_models.h:98-102: unit bearing first, then hnormalized)
+PL_HD void camera_unproject(const CameraParams &c, double px, double py, double &ox, double &oy) {
+    const Vec3 b = camera_unproject_bearing(c, px, py);
     ox = b.x / b.z;
     oy = b.y / b.z;
 }
@@ -472,6 +477,27 @@ PL_HD void camera_project_jac(const CameraParams &c, Vec3 Z, double &ox, double 
         J[3] = 0.0, J[4] = zi, J[5] = -oy * zi;
     }
     }
+}
+
+// Camera::unproject_with_jac (camera_models.cc:456-489): the bearing d of a pixel and M = d(d)/d(pixel), 3x2 row-major, as the
+// pseudo-inverse of the projection's Jacobian at d:  J = project_with_jac(d) (2x3), B = J J^T, B^-1 = adj(B) / det, M = J^T B^-1.
+// Every sum in the reference's order (k ascending).  False: det(B) is zero or not finite - M is then whatever the division gave.
+PL_HD bool camera_unproject_with_jac(const CameraParams &c, double px, double py, Vec3 &d, double *M) {
+    d = camera_unproject_bearing(c, px, py);
+    double qx, qy, J[6];
+    camera_project_jac(c, d, qx, qy, J);
+    const double B00 = J[0] * J[0] + J[1] * J[1] + J[2] * J[2];
+    const double B01 = J[0] * J[3] + J[1] * J[4] + J[2] * J[5];
+    const double B10 = J[3] * J[0] + J[4] * J[1] + J[5] * J[2];
+    const double B11 = J[3] * J[3] + J[4] * J[4] + J[5] * J[5];
+    const double det = B00 * B11 - B01 * B10;
+    const double I00 = B11 / det, I01 = -B01 / det, I10 = -B10 / det, I11 = B00 / det;
+    PL_UNROLL
+    for (int i = 0; i < 3; ++i) {
+        M[2 * i] = J[i] * I00 + J[3 + i] * I10;
+        M[2 * i + 1] = J[i] * I01 + J[3 + i] * I11;
+    }
+    return det != 0.0 && det - det == 0.0;
 }
 
 // ------------------------------------------------------------------------------------ accumulators
@@ -968,6 +994,50 @@ template <> struct Refiner<EST_REL> {
     }
 };
 
+// ---- relative pose, tangent Sampson (optim/relative.h:168-266, FixCameraRelativePoseRefiner) ----
+// Parameters, tangent basis, d vec(E) / d parameters and the step are EST_REL's; a correspondence is the 18 doubles of pl_score.h.
+template <> struct Refiner<EST_RELT> {
+    static constexpr int K = 5;
+    PL_HD static void prepare_params(double *p) { Refiner<EST_REL>::prepare_params(p); }
+    PL_HD static void prepare(const double *p, RefineCtx &c) { Refiner<EST_REL>::prepare(p, c); }
+    PL_HD static double residual(const RefineCtx &c, const double *pt) { // relative.h:185-191
+        double g[4];
+        const double C = tangent_sampson_terms(c.M, pt, g);
+        const double nJc_sq = (g[2] * g[2] + g[3] * g[3]) + (g[0] * g[0] + g[1] * g[1]);
+        return C / sqrt(nJc_sq);
+    }
+    PL_HD static double jacobian(const RefineCtx &c, const double *pt, double *J) { // relative.h:207-247
+        const double *d1 = pt, *d2 = pt + 3, *M1 = pt + 6, *M2 = pt + 12;
+        double g[4]; // J_C
+        const double C = tangent_sampson_terms(c.M, pt, g);
+        const double nJ = sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2] + g[3] * g[3]);
+        const double inv = 1.0 / nJ;
+        const double r = C * inv;
+        const double s = C * inv * inv;
+        double dF[9];
+        PL_UNROLL
+        for (int i = 0; i < 3; ++i)
+            PL_UNROLL
+            for (int j = 0; j < 3; ++j) {
+                double f = d1[i] * d2[j];
+                f -= s * (g[0] * M1[2 * i] * d2[j] + g[1] * M1[2 * i + 1] * d2[j] + g[2] * M2[2 * j] * d1[i] + g[3] * M2[2 * j + 1] * d1[i]);
+                dF[3 * i + j] = f * inv;
+            }
+        PL_UNROLL
+        for (int k = 0; k < 5; ++k) {
+            double a = 0;
+            PL_UNROLL
+            for (int m = 0; m < 9; ++m)
+                a += dF[m] * c.D[m * 7 + k];
+            J[k] = a;
+        }
+        return r;
+    }
+    PL_HD static void step(const double *__restrict__ p, const RefineCtx &c, const double *__restrict__ dp, double *__restrict__ out) {
+        Refiner<EST_REL>::step(p, c, dp, out);
+    }
+};
+
 // ---- homography ----
 template <> struct Refiner<EST_HOM> {
     static constexpr int K = 8;
@@ -1133,10 +1203,10 @@ template <> struct Refiner<EST_FUND> {
 // Record (what the scorers consume) of a refined parameter block: pose (q, t) for the absolute / relative problems,
 // H row-major, or the Bartoli-Sturm factorisation of F (optim_utils.h:73-77).  est: pl_score.h Estimator.
 PL_HD void record_from_lm_params(int est, const double *params, double *rec) {
-    if (est == 0 || est == 1) {
+    if (est == 0 || est == 1 || est == 4) {
         Quat q;
         q.w = params[0], q.x = params[1], q.y = params[2], q.z = params[3];
-        store_pose_model_q(rec, q, v3(params[4], params[5], params[6]), est == 1);
+        store_pose_model_q(rec, q, v3(params[4], params[5], params[6]), est != 0);
     } else if (est == 3) {
         Mat3 H;
         for (int i = 0; i < 9; ++i)

@@ -11,7 +11,8 @@
 
 namespace pl {
 
-enum Estimator : int { EST_ABS = 0, EST_REL = 1, EST_FUND = 2, EST_HOM = 3 };
+// EST_RELT: relative pose scored by the tangent-Sampson error on bearings (the model record is EST_REL's)
+enum Estimator : int { EST_ABS = 0, EST_REL = 1, EST_FUND = 2, EST_HOM = 3, EST_RELT = 4 };
 
 // ---- absolute pose: correspondence = (x, y, X, Y, Z) ---------------------------------------
 // Returns the inlier decision; r2 is valid when the point is in front of the camera.
@@ -77,6 +78,46 @@ PL_HD bool homography_inlier(const double *M, double a0, double a1, double b0, d
     const double e1 = h1 * inv - b1;
     r2 = e0 * e0 + e1 * e1;
     return r2 < thr2;
+}
+
+// ---- tangent Sampson (utils.cc:269-298, 541-568): correspondence = 18 doubles  d1[3] d2[3] M1[6] M2[6] ------------------
+// d: bearings of the two pixels, M: 3x2 row-major Jacobians of the un-projections (camera_unproject_with_jac, pl_refine.h).
+// C = d2 . (E d1) and the two halves of the denominator, (M2^T E) d1 and (M1^T E^T) d2, with the reference's association:
+// the 2x3 products first, every sum with k ascending.  g[0..1] = (M1^T E^T) d2, g[2..3] = (M2^T E) d1 (J_C of relative.h:211-212).
+PL_HD double tangent_sampson_terms(const double *E /*row-major 3x3*/, const double *pt, double *g) {
+    const double *d1 = pt, *d2 = pt + 3, *M1 = pt + 6, *M2 = pt + 12;
+    const double v0 = E[0] * d1[0] + E[1] * d1[1] + E[2] * d1[2];
+    const double v1 = E[3] * d1[0] + E[4] * d1[1] + E[5] * d1[2];
+    const double v2 = E[6] * d1[0] + E[7] * d1[1] + E[8] * d1[2];
+    const double C = 0.0 + d2[0] * v0 + d2[1] * v1 + d2[2] * v2; // (Eigen's dot starts from zero: -0 never comes out)
+    PL_UNROLL
+    for (int i = 0; i < 2; ++i) {
+        // (M2^T E)(i, j) = sum_k M2(k, i) E(k, j);   (M1^T E^T)(i, j) = sum_k M1(k, i) E(j, k)
+        const double a0 = M2[i] * E[0] + M2[2 + i] * E[3] + M2[4 + i] * E[6];
+        const double a1 = M2[i] * E[1] + M2[2 + i] * E[4] + M2[4 + i] * E[7];
+        const double a2 = M2[i] * E[2] + M2[2 + i] * E[5] + M2[4 + i] * E[8];
+        g[2 + i] = a0 * d1[0] + a1 * d1[1] + a2 * d1[2];
+        const double b0 = M1[i] * E[0] + M1[2 + i] * E[1] + M1[4 + i] * E[2];
+        const double b1 = M1[i] * E[3] + M1[2 + i] * E[4] + M1[4 + i] * E[5];
+        const double b2 = M1[i] * E[6] + M1[2 + i] * E[7] + M1[4 + i] * E[8];
+        g[i] = b0 * d2[0] + b1 * d2[1] + b2 * d2[2];
+    }
+    return C;
+}
+PL_HD double tangent_sampson_sq(const double *E, const double *pt) {
+    double g[4];
+    const double C = tangent_sampson_terms(E, pt, g);
+    const double denom2 = (g[2] * g[2] + g[3] * g[3]) + (g[0] * g[0] + g[1] * g[1]);
+    return C * C / denom2;
+}
+// below the threshold AND positive depth of the two bearings (min depth 0.01); a NaN r2 (E = 0) is an outlier
+PL_HD bool tangent_pose_inlier(const double *M, const double *pt, double thr2, double &r2) {
+    r2 = tangent_sampson_sq(M + kMatOff, pt);
+    if (!(r2 < thr2))
+        return false;
+    Quat q;
+    q.w = M[0], q.x = M[1], q.y = M[2], q.z = M[3];
+    return check_cheirality(q, v3(M[4], M[5], M[6]), v3(pt[0], pt[1], pt[2]), v3(pt[3], pt[4], pt[5]), 0.01);
 }
 
 // ---- final inlier masks (different arithmetic form for absolute pose: utils.cc:374-384) -----
