@@ -128,7 +128,8 @@ typedef struct {
 
 void pl_default_ransac_options(pl_ransac_options *o);
 void pl_default_bundle_options(pl_bundle_options *o);
-/* kind: 0 absolute pose (max_error 12), 1 relative pose, 2 fundamental, 3 homography (max_error 1) */
+/* kind: 0 absolute pose (max_error 12), 1 relative pose, 2 fundamental, 3 homography (max_error 1), 5 absolute pose of a
+ * 1D-radial camera (AbsolutePoseOptions: max_error 12); 4 is not a problem kind */
 void pl_default_robust_options(pl_robust_options *o, int kind);
 
 /* ---- device management ---- */
@@ -252,10 +253,25 @@ int pl_ransac_fundamental(const double *x1, const double *x2, size_t n, const pl
                           uint8_t *inliers, pl_ransac_stats *stats);
 int pl_ransac_homography(const double *x1, const double *x2, size_t n, const pl_robust_options *opt, double *H,
                          uint8_t *inliers, pl_ransac_stats *stats);
+/* Absolute pose of a camera with unknown (or unmodelled) radial distortion - the reference's 1D-radial camera: no intrinsics,
+ * points2D are pixels relative to the centre of distortion (N x 2), points3D N x 3.  The pose has t[2] = 0: the error - the
+ * distance of a pixel from the radial line through its point's projection, on the projection's side of the centre - does not
+ * see the forward translation.
+ * pl_estimate_1D_radial_absolute_pose (robust.cc:889-934): the pixels, max_error and bundle.loss_scale are rescaled by the mean
+ * pixel norm, RANSAC on the radial 5-point solver (p5lp_radial) with local optimisation, then bundle_adjust_1D_radial over the
+ * inliers when there are more than 5.  n < 5: default stats, pose and inliers untouched.  bundle.refine_* has no effect.
+ * pl_ransac_1D_radial_pnp (ransac.cc:388-401): the RANSAC stage alone, nothing rescaled.
+ * The 1D-radial camera model inside the OTHER estimators (a pl_camera with that model id) stays unsupported. */
+int pl_estimate_1D_radial_absolute_pose(const double *points2D, const double *points3D, size_t n, const pl_robust_options *opt,
+                                        pl_camera_pose *pose, uint8_t *inliers, pl_ransac_stats *stats);
+int pl_ransac_1D_radial_pnp(const double *x, const double *X, size_t n, const pl_robust_options *opt, pl_camera_pose *pose,
+                            uint8_t *inliers, pl_ransac_stats *stats);
 
 /* ---- device-resident problems (inputs stay in HBM across calls; what bench.py times) ---- */
 typedef struct pl_problem pl_problem;
-/* kind as in pl_default_robust_options; a = first point set (N x 2), b = second (N x 3 for kind 0, else N x 2) */
+/* kind as in pl_default_robust_options; a = first point set (N x 2), b = second (N x 3 for kinds 0 and 5, else N x 2).  Kind 5
+ * (1D-radial absolute pose): a = centred pixels as pl_ransac_1D_radial_pnp takes them; models are pl_camera_pose; pl_refine_model is
+ * bundle_adjust_1D_radial; pl_ransac_run_sharded answers PL_ERR_UNSUPPORTED for it */
 int pl_problem_create(int kind, const double *a, const double *b, size_t n, pl_problem **out);
 /* A resident tangent-Sampson relative-pose problem: per correspondence the bearings of the two pixels and the 3x2 Jacobians of
  * the un-projections (Camera::unproject_with_jac), computed on the device.  x1 / x2 (N x 2 pixels) and the cameras are taken as
@@ -314,6 +330,14 @@ int pl_score_model(pl_problem *p, const void *model, double max_error, uint64_t 
 int pl_debug_inlier_mask(pl_problem *p, const void *model, double max_error, uint8_t *mask);
 /* Diagnostic: correspondences per chunk of the tangent-Sampson streaming scorer as built. */
 int pl_debug_tangent_chunk(void);
+/* ... and of the 1D-radial streaming scorer */
+int pl_debug_radial1d_chunk(void);
+/* Diagnostic: the generator kernel of a resident kind-5 problem on caller-supplied minimal samples (num_iters x 5 indices - the path
+ * PROSAC's host-drawn samples take) with slots_per_iter (1 .. 4) record slots per iteration.  models: num_iters x slots_per_iter
+ * records of 24 doubles (zero where none was written); num_models: num_iters; totals[3]: models counted, models with a NaN entry,
+ * overflow flag (an iteration had more solutions than slots: its count is 0). */
+int pl_debug_radial1d_generate(pl_problem *p, const uint32_t *samples, size_t num_iters, uint32_t slots_per_iter, double *models,
+                               uint32_t *num_models, uint32_t *totals);
 /* Diagnostic entry (no counterpart in the reference): `n` models - pl_camera_pose[n] for kinds 0/1, double[n][9]
  * column-major for kinds 2/3 - through the STREAMING scorer of the batched main loop, i.e. through the conservative
  * pre-filters (fp16/MFMA or fp32) in front of the exact fp64 evaluation, instead of the sequential scorer behind
@@ -356,6 +380,8 @@ int pl_bundle_adjust_camera(pl_problem *p, const pl_bundle_options *opt, pl_came
 
 /* ---- minimal solvers (solvers/ headers); unit bearing vectors in, solutions out; return = #solutions or <0 ---- */
 int pl_p3p(const double *x /* 3x3 */, const double *X /* 3x3 */, pl_camera_pose *out /* 4 */);
+/* p5lp_radial (solvers/p5lp_radial.h:49, the 2-D point form; a radial line l is the point (l_y, -l_x)): poses with t[2] = 0 */
+int pl_p5lp_radial(const double *x /* 5x2 */, const double *X /* 5x3 */, pl_camera_pose *out /* 4 */, int *count /* may be null */);
 int pl_relpose_5pt(const double *x1 /* 5x3 */, const double *x2 /* 5x3 */, pl_camera_pose *out /* 40 */);
 int pl_essential_matrix_5pt(const double *x1, const double *x2, double *E /* 10 x 9 column-major */);
 int pl_relpose_7pt(const double *x1 /* 7x3 */, const double *x2 /* 7x3 */, double *F /* 3 x 9 column-major */);
@@ -373,6 +399,7 @@ int pl_solve_focal_batch(int kind, const double *in, size_t count, double *out_m
  * in: count x (2*K*3) doubles ([first set K x 3][second set K x 3]); out_models: count x max_models x 24 doubles
  * (model records of 24 doubles: q[4] t[3] M[9 row-major] + 8 doubles of internal fp32 shadow, see
  * poselib_amd/csrc/pl_math.h); out_counts: count. */
+/* kind 5: p5lp_radial - first set = the 2-D points as K x 3 (third component not read), K = 5, max_models 4 */
 int pl_solve_batch(int kind, const double *in, size_t count, double *out_models, uint32_t *out_counts);
 
 #ifdef __cplusplus

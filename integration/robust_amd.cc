@@ -193,6 +193,17 @@ std::vector<RansacStats> estimate_absolute_pose_batch(const std::vector<std::vec
     return out;
 }
 
+// robust.h:176-178: absolute pose of a 1D-radial camera (no intrinsics; points2D relative to the centre of distortion)
+RansacStats estimate_1D_radial_absolute_pose(const std::vector<Point2D> &points2D, const std::vector<Point3D> &points3D,
+                                             const AbsolutePoseOptions &opt, CameraPose *pose, std::vector<char> *inliers) {
+    const pl_robust_options o = to_pl(5, opt.ransac, opt.bundle, opt.max_error);
+    pl_camera_pose p = to_pl(*pose);
+    pl_ransac_stats st;
+    check(pl_estimate_1D_radial_absolute_pose(raw(points2D), raw(points3D), points2D.size(), &o, &p, mask_of(inliers, points2D.size()), &st));
+    from_pl(p, pose);
+    return from_pl(st);
+}
+
 RansacStats estimate_relative_pose(const std::vector<Point2D> &points2D_1, const std::vector<Point2D> &points2D_2,
                                    const Camera &camera1, const Camera &camera2, const RelativePoseOptions &opt,
                                    CameraPose *relative_pose, std::vector<char> *inliers) {
@@ -251,6 +262,17 @@ RansacStats ransac_pnp(const std::vector<Point2D> &x, const std::vector<Point3D>
     pl_camera_pose pose = to_pl(*best_model);
     pl_ransac_stats st;
     check(pl_ransac_pnp(raw(x), raw(X), x.size(), &o, &pose, mask_of(best_inliers, x.size()), &st));
+    from_pl(pose, best_model);
+    return from_pl(st);
+}
+
+// ransac.h:114-116: RANSAC on the radial 5-point solver, x = pixels relative to the centre of distortion
+RansacStats ransac_1D_radial_pnp(const std::vector<Point2D> &x, const std::vector<Point3D> &X, const AbsolutePoseOptions &opt,
+                                 CameraPose *best_model, std::vector<char> *best_inliers) {
+    const pl_robust_options o = to_pl(5, opt.ransac, opt.bundle, opt.max_error);
+    pl_camera_pose pose = to_pl(*best_model);
+    pl_ransac_stats st;
+    check(pl_ransac_1D_radial_pnp(raw(x), raw(X), x.size(), &o, &pose, mask_of(best_inliers, x.size()), &st));
     from_pl(pose, best_model);
     return from_pl(st);
 }

@@ -30,6 +30,8 @@ CAMERA_MODEL_IDS = {"NULL": -1, "SIMPLE_PINHOLE": 0, "PINHOLE": 1, "SIMPLE_RADIA
 _CAMERA_NAMES = {v: k for k, v in CAMERA_MODEL_IDS.items()}
 KIND_ABS, KIND_REL, KIND_FUND, KIND_HOM = 0, 1, 2, 3
 KIND_SHARED_FOCAL = 4  # pl_batch_item only: estimate_shared_focal_relative_pose
+KIND_RAD1D = 5  # absolute pose of a 1D-radial camera (centred pixels, no intrinsics)
+_POSE_KINDS = (KIND_ABS, KIND_REL, KIND_RAD1D)  # problem kinds whose model is a CameraPose
 
 
 # ------------------------------------------------------------------------------------------ types
@@ -256,7 +258,8 @@ class Batch:
     single-problem functions return."""
 
     def __init__(self, problems):
-        kinds = {"abs": KIND_ABS, "rel": KIND_REL, "fund": KIND_FUND, "hom": KIND_HOM, "shared_focal": KIND_SHARED_FOCAL}
+        kinds = {"abs": KIND_ABS, "rel": KIND_REL, "fund": KIND_FUND, "hom": KIND_HOM, "shared_focal": KIND_SHARED_FOCAL,
+                 "radial1d": KIND_RAD1D}
         self.items = (L.BatchItem * len(problems))()
         self.keep = []
         for it, pr in zip(self.items, problems):
@@ -279,6 +282,11 @@ class Batch:
                 cam = None
                 c1, c2 = _as_camera(cam1)._c(), _as_camera(cam2)._c()
                 model = _cpose(init if init is not None else CameraPose())
+            elif kind == KIND_RAD1D:  # ("radial1d", centred pixels, points3D, opt)
+                _, a, b, opt = pr
+                a, b = _pts(a, 2), _pts(b, 3)
+                cam, c1, c2 = None, None, None
+                model = _cpose(init if init is not None else CameraPose())
             elif kind == KIND_SHARED_FOCAL:
                 _, a, b, pp, opt = pr
                 a, b = _pts(a, 2), _pts(b, 2)
@@ -298,7 +306,7 @@ class Batch:
             it.opt = C.pointer(o)
             it.camera1 = C.pointer(c1) if c1 is not None else None
             it.camera2 = C.pointer(c2) if c2 is not None else None
-            it.model = C.cast(C.pointer(model), C.c_void_p) if kind in (KIND_ABS, KIND_REL, KIND_SHARED_FOCAL) else _ptr(model)
+            it.model = C.cast(C.pointer(model), C.c_void_p) if kind in (KIND_ABS, KIND_REL, KIND_SHARED_FOCAL, KIND_RAD1D) else _ptr(model)
             it.inliers = _ptr(inl)
             it.stats = C.pointer(st)
             self.keep.append((kind, a, b, o, cam, c1, c2, model, inl, st, n))
@@ -328,7 +336,7 @@ class Batch:
             if kind == KIND_ABS:
                 out_cam = Camera(cam.model_id, list(c1.params[: c1.num_params]), cam.width, cam.height)
                 out.append((Image(_pypose(model), out_cam), info))
-            elif kind == KIND_REL:
+            elif kind in (KIND_REL, KIND_RAD1D):
                 out.append((_pypose(model), info))
             elif kind == KIND_SHARED_FOCAL:
                 out.append((_shared_focal_pair(model, c1.params[0], (c1.params[1], c1.params[2])), info))
@@ -374,7 +382,7 @@ class RansacBatch:
             o = _robust_options(opt, pr.kind, False)
             inl = np.zeros(max(pr.n, 1), dtype=np.uint8)
             st = L.RansacStats()
-            if pr.kind in (KIND_ABS, KIND_REL):
+            if pr.kind in _POSE_KINDS:
                 model = _cpose(CameraPose())
                 it.model = C.cast(C.pointer(model), C.c_void_p)
             else:
@@ -396,7 +404,7 @@ class RansacBatch:
         """what `Problem.run` returns, per item (`first`: only the first so many items)"""
         out = []
         for pr, o, model, inl, st in (self.keep if first is None else self.keep[:first]):
-            if pr.kind in (KIND_ABS, KIND_REL):
+            if pr.kind in _POSE_KINDS:
                 out.append((_pypose(model), _info(st, inl[: pr.n])))
             else:
                 out.append((model.reshape(3, 3).T.copy(), _info(st, inl[: pr.n])))
@@ -450,7 +458,7 @@ def _ransac(fn, kind, a, b, dim_b, opt, initial):
     n = a.shape[0]
     inl = np.zeros(max(n, 1), dtype=np.uint8)
     st = L.RansacStats()
-    if kind in (KIND_ABS, KIND_REL):
+    if kind in _POSE_KINDS:
         pose = _cpose(initial if initial is not None else CameraPose())
         L.check(getattr(L.lib(), fn)(_ptr(a), _ptr(b), C.c_size_t(n), C.byref(o), C.byref(pose), _ptr(inl), C.byref(st)))
         return _pypose(pose), _info(st, inl[:n])
@@ -461,6 +469,17 @@ def _ransac(fn, kind, a, b, dim_b, opt, initial):
 
 def ransac_pnp(x, X, opt=None, initial_pose=None):
     return _ransac("pl_ransac_pnp", KIND_ABS, x, X, 3, opt, initial_pose)
+
+
+def ransac_1D_radial_pnp(x, X, opt=None, initial_pose=None):
+    """ransac_1D_radial_pnp (ransac.cc:388-401): x = pixels relative to the centre of distortion, taken as they are"""
+    return _ransac("pl_ransac_1D_radial_pnp", KIND_RAD1D, x, X, 3, opt, initial_pose)
+
+
+def estimate_1D_radial_absolute_pose(points2D, points3D, opt=None, initial_pose=None):
+    """poselib.estimate_1D_radial_absolute_pose(points2D, points3D, opt, initial_pose) -> (CameraPose, info): absolute pose of a
+    camera with unknown radial distortion from pixels relative to the centre of distortion; the pose has t[2] = 0"""
+    return _ransac("pl_estimate_1D_radial_absolute_pose", KIND_RAD1D, points2D, points3D, 3, opt, initial_pose)
 
 
 def ransac_pnpf(x, X, opt=None):
@@ -579,7 +598,7 @@ class Problem:
     def __init__(self, kind: int, a, b):
         self.kind = kind
         a = _pts(a, 2)
-        b = _pts(b, 3 if kind == KIND_ABS else 2)
+        b = _pts(b, 3 if kind in (KIND_ABS, KIND_RAD1D) else 2)
         self.n = a.shape[0]
         self._h = C.c_void_p()
         L.check(L.lib().pl_problem_create(kind, _ptr(a), _ptr(b), C.c_size_t(self.n), C.byref(self._h)))
@@ -588,7 +607,7 @@ class Problem:
         o = _robust_options(opt, self.kind, initial is not None)
         inl = np.zeros(max(self.n, 1), dtype=np.uint8)
         st = L.RansacStats()
-        if self.kind in (KIND_ABS, KIND_REL):
+        if self.kind in _POSE_KINDS:
             model = _cpose(initial if initial is not None else CameraPose())
             L.check(L.lib().pl_ransac_run(self._h, C.byref(o), C.byref(model), _ptr(inl), C.byref(st)))
             return _pypose(model), _info(st, inl[: self.n])
@@ -619,7 +638,7 @@ class Problem:
 
         cb = L.ALLGATHER_FN(_cb)
         shard = L.Shard(rank, world, cb, None)
-        if self.kind in (KIND_ABS, KIND_REL):
+        if self.kind in _POSE_KINDS:
             model = _cpose(initial if initial is not None else CameraPose())
             rc = L.lib().pl_ransac_run_sharded(self._h, C.byref(o), C.byref(shard), C.byref(model), _ptr(inl), C.byref(st))
             if rc and errors:
@@ -637,7 +656,7 @@ class Problem:
         """MSAC score + inlier count of one model (the estimators' score_model())."""
         cnt = C.c_uint64(0)
         sc = C.c_double(0.0)
-        if self.kind in (KIND_ABS, KIND_REL):
+        if self.kind in _POSE_KINDS:
             m = _cpose(model)
             L.check(L.lib().pl_score_model(self._h, C.byref(m), C.c_double(max_error), C.byref(cnt), C.byref(sc)))
         else:
@@ -652,7 +671,7 @@ class Problem:
         1 = fp32 filter, 0 = no filter."""
         m = np.ascontiguousarray(models, dtype=np.float64)
         n = m.shape[0]
-        if self.kind in (KIND_ABS, KIND_REL):
+        if self.kind in _POSE_KINDS:
             assert m.shape == (n, 7)
             flat = np.ascontiguousarray(m.reshape(-1))  # pl_camera_pose = 7 packed doubles
         else:
@@ -672,7 +691,7 @@ class Problem:
         it = C.c_uint32(0)
         m8 = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
         args_tail = (C.byref(cam) if cam is not None else None, None if m8 is None else _ptr(m8))
-        if self.kind in (KIND_ABS, KIND_REL):
+        if self.kind in _POSE_KINDS:
             m = _cpose(model)
             L.check(L.lib().pl_refine_model(self._h, C.byref(o), *args_tail, C.byref(m), C.byref(it)))
             return _pypose(m), it.value
@@ -723,10 +742,23 @@ class TangentProblem(Problem):
                                                   None if c2 is None else C.byref(c2), C.byref(self._h)))
 
 
+def radial1d_generate(problem, samples, slots_per_iter=4):
+    """Diagnostic (pl_debug_radial1d_generate): the generator kernel of a KIND_RAD1D problem on explicit minimal samples (B, 5).
+    Returns (records (B, slots, 16), counts (B,), (models counted, NaN models, overflow flag))."""
+    idx = np.ascontiguousarray(samples, dtype=np.uint32).reshape(-1, 5)
+    B = idx.shape[0]
+    out = np.zeros((B, int(slots_per_iter), 24))
+    cnt = np.zeros(B, dtype=np.uint32)
+    tot = np.zeros(3, dtype=np.uint32)
+    L.check(L.lib().pl_debug_radial1d_generate(problem._h, _ptr(idx), C.c_size_t(B), C.c_uint32(int(slots_per_iter)), _ptr(out), _ptr(cnt),
+                                               _ptr(tot)))
+    return out[:, :, :16].copy(), cnt, tuple(int(v) for v in tot)
+
+
 def inlier_mask(problem, model, max_error):
     """Diagnostic (pl_debug_inlier_mask): the inlier mask of one model on a resident problem."""
     mask = np.zeros(max(problem.n, 1), dtype=np.uint8)
-    if problem.kind in (KIND_ABS, KIND_REL):
+    if problem.kind in _POSE_KINDS:
         m = _cpose(model)
         L.check(L.lib().pl_debug_inlier_mask(problem._h, C.byref(m), C.c_double(max_error), _ptr(mask)))
     else:
@@ -747,6 +779,16 @@ def p3p(x, X):
     x, X = _bearings(x, 3), _bearings(X, 3)
     out = (L.CameraPose * 4)()
     n = L.check(L.lib().pl_p3p(_ptr(x), _ptr(X), out))
+    return [_pypose(out[i]) for i in range(n)]
+
+
+def p5lp_radial(x, X):
+    """p5lp_radial on five 2-D points (5, 2) and 3-D points (5, 3); the reference's line form is x = (l_y, -l_x)"""
+    x, X = np.ascontiguousarray(x, dtype=np.float64), _bearings(X, 5)
+    if x.shape != (5, 2):
+        raise ValueError("expected 5 points of dimension 2")
+    out = (L.CameraPose * 4)()
+    n = L.check(L.lib().pl_p5lp_radial(_ptr(x), _ptr(X), out, None))
     return [_pypose(out[i]) for i in range(n)]
 
 
@@ -787,7 +829,7 @@ def solve_batch(kind: int, first, second):
     first = np.ascontiguousarray(first, dtype=np.float64)
     second = np.ascontiguousarray(second, dtype=np.float64)
     B, K = first.shape[0], first.shape[1]
-    maxm = {0: 4, 1: 40, 2: 3, 3: 1}[kind]
+    maxm = {0: 4, 1: 40, 2: 3, 3: 1, 5: 4}[kind]  # (5: p5lp_radial, first = the 2-D points with a third component that is not read)
     inp = np.ascontiguousarray(np.concatenate([first.reshape(B, -1), second.reshape(B, -1)], axis=1))
     out = np.zeros((B, maxm, 24))  # record pitch: 16 fp64 fields + fp32 shadow used by the scoring pre-filter
     cnt = np.zeros(B, dtype=np.uint32)

@@ -340,7 +340,7 @@ void camera_rescale(CameraParams &c, double s) { // misc/camera_models.cc:432-45
 void params_from_record(int kind, const double *rec, double *params) {
     for (int i = 0; i < kParamDoubles; ++i)
         params[i] = 0.0;
-    if (kind == EST_ABS || kind == EST_REL || kind == EST_RELT) {
+    if (kind == EST_ABS || kind == EST_REL || kind == EST_RELT || kind == EST_RAD1D) {
         for (int i = 0; i < 7; ++i)
             params[i] = rec[i];
     } else {
@@ -373,10 +373,10 @@ void lm_params_from_record(int kind, const double *rec, double *params) {
     }
 }
 void identity_record(int kind, double *rec) {
-    if (kind == EST_ABS || kind == EST_REL || kind == EST_RELT) {
+    if (kind == EST_ABS || kind == EST_REL || kind == EST_RELT || kind == EST_RAD1D) {
         Quat q;
         q.w = 1.0, q.x = q.y = q.z = 0.0;
-        store_pose_model_q(rec, q, v3(0, 0, 0), kind != EST_ABS);
+        store_pose_model_q(rec, q, v3(0, 0, 0), kind == EST_REL || kind == EST_RELT);
     } else {
         Mat3 I;
         for (int i = 0; i < 9; ++i)
@@ -559,7 +559,7 @@ int run_refinements(Context *c, const pl_problem *p, std::vector<RefineJob> &job
         with_camera = with_camera || jobs[j].cam_flags != 0;
     if (with_camera && p->kind != EST_ABS)
         return fail(PL_ERR_INVALID, "camera intrinsics are refined with absolute poses only");
-    const bool use_lm2 = !with_camera && latency_mode && p->kind != EST_REL && p->kind != EST_RELT && !lm_sums_ordered(p->kind) && same_it && max_it >= 1 && max_it <= 32 && p->n >= lm2_min_points;
+    const bool use_lm2 = !with_camera && latency_mode && p->kind != EST_REL && p->kind != EST_RELT && p->kind != EST_RAD1D && !lm_sums_ordered(p->kind) && same_it && max_it >= 1 && max_it <= 32 && p->n >= lm2_min_points;
     if (use_lm2)
         HIP_TRY(c->lm_tasks.ensure(stage_bytes));
     LMTask *ht = c->h_tasks.as<LMTask>();
@@ -1612,8 +1612,9 @@ int validate_options(const pl_robust_options *o, bool focal_entry = false) {
     return PL_OK;
 }
 
-int make_problem(Context *c, int kind, const double *a, const double *b, size_t n, pl_problem *p) {
-    if (kind < 0 || kind > 3)
+// scale_a: factor of the first point set on its way into the SoA block (1D-radial front-end, robust.cc:904-907; x * 1.0 = x elsewhere)
+int make_problem(Context *c, int kind, const double *a, const double *b, size_t n, pl_problem *p, double scale_a = 1.0) {
+    if ((kind < 0 || kind > 3) && kind != EST_RAD1D)
         return fail(PL_ERR_INVALID, "unknown problem kind");
     if (n > 0x7fffffffu)
         return fail(PL_ERR_INVALID, "too many correspondences");
@@ -1622,7 +1623,7 @@ int make_problem(Context *c, int kind, const double *a, const double *b, size_t 
     p->n = (uint32_t)n;
     p->d_pts = nullptr;
     const int nd = point_doubles(kind);
-    const int da = 2, db = (kind == EST_ABS) ? 3 : 2;
+    const int da = 2, db = (kind == EST_ABS || kind == EST_RAD1D) ? 3 : 2;
     std::memset(&p->ps, 0, sizeof(p->ps));
     p->ps.n = (uint32_t)n;
     if (n == 0)
@@ -1631,13 +1632,13 @@ int make_problem(Context *c, int kind, const double *a, const double *b, size_t 
     double amax = 0;
     for (size_t i = 0; i < n; ++i) {
         for (int d = 0; d < da; ++d) {
-            soa[(size_t)d * n + i] = a[da * i + d];
-            const double v = std::fabs(a[da * i + d]);
+            soa[(size_t)d * n + i] = a[da * i + d] * scale_a;
+            const double v = std::fabs(soa[(size_t)d * n + i]);
             amax = (v > amax || v != v) ? v : amax; // NaN propagates and disables the pre-filter
         }
         for (int d = 0; d < db; ++d) {
             soa[(size_t)(da + d) * n + i] = b[db * i + d];
-            if (kind != EST_ABS) { // two-view: the bound covers all four coordinates (pl_prefilter.h, fp16 Sampson form)
+            if (kind != EST_ABS && kind != EST_RAD1D) { // two-view: the bound covers all four coordinates (pl_prefilter.h, fp16 Sampson form)
                 const double v = std::fabs(b[db * i + d]);
                 amax = (v > amax || v != v) ? v : amax;
             }
@@ -1866,13 +1867,13 @@ void normalize_frobenius(Mat3 &A) {
 
 // the caller's model (pl_camera_pose for absolute / relative pose, column-major 3 x 3 for F / H) <-> record
 void record_from_model(int kind, const void *model, double *rec) {
-    if (kind == EST_ABS || kind == EST_REL || kind == EST_RELT)
-        record_from_pose(static_cast<const pl_camera_pose *>(model), kind != EST_ABS, rec);
+    if (kind == EST_ABS || kind == EST_REL || kind == EST_RELT || kind == EST_RAD1D)
+        record_from_pose(static_cast<const pl_camera_pose *>(model), kind == EST_REL || kind == EST_RELT, rec);
     else
         store_matrix_model(rec, mat_from_colmajor(static_cast<const double *>(model)));
 }
 void model_from_record(int kind, const double *rec, void *model) {
-    if (kind == EST_ABS || kind == EST_REL || kind == EST_RELT) {
+    if (kind == EST_ABS || kind == EST_REL || kind == EST_RELT || kind == EST_RAD1D) {
         pose_from_record(rec, static_cast<pl_camera_pose *>(model));
     } else {
         Mat3 M;
@@ -2104,7 +2105,7 @@ void front_set_focal(FrontEnd &fe, pl_camera *camera, double focal) {
 // camera.rescale(scale) ... rescale(1 / scale) round trip (robust.cc:119-121), with the intrinsics the bundle moved (cam_refined);
 // fund / hom: back to pixels (robust.cc:590-591, 753-754)
 void front_finish(const FrontEnd &fe, const double *rec, const CameraParams *cam_refined, void *model, pl_camera *camera) {
-    if (fe.kind == EST_ABS || fe.kind == EST_REL || fe.kind == EST_RELT) {
+    if (fe.kind == EST_ABS || fe.kind == EST_REL || fe.kind == EST_RELT || fe.kind == EST_RAD1D) {
         model_from_record(fe.kind, rec, model);
         if (!camera)
             return;
@@ -2212,7 +2213,7 @@ void pl_default_robust_options(pl_robust_options *o, int kind) {
     std::memset(o, 0, sizeof(*o));
     pl_default_ransac_options(&o->ransac);
     pl_default_bundle_options(&o->bundle);
-    o->max_error = (kind == 0) ? 12.0 : 1.0;
+    o->max_error = (kind == 0 || kind == EST_RAD1D) ? 12.0 : 1.0;
     o->min_fov = 5.0; // types.h:126
 }
 
@@ -2319,8 +2320,8 @@ int pl_debug_inlier_mask(pl_problem *p, const void *model, double max_error, uin
     if (p->n == 0)
         return PL_OK;
     double rec[kModelStride];
-    if (p->kind == EST_ABS || p->kind == EST_REL || p->kind == EST_RELT)
-        record_from_pose(static_cast<const pl_camera_pose *>(model), p->kind != EST_ABS, rec);
+    if (p->kind == EST_ABS || p->kind == EST_REL || p->kind == EST_RELT || p->kind == EST_RAD1D)
+        record_from_pose(static_cast<const pl_camera_pose *>(model), p->kind == EST_REL || p->kind == EST_RELT, rec);
     else
         store_matrix_model(rec, mat_from_colmajor(static_cast<const double *>(model)));
     HIP_TRY(c->tmp_model.ensure(sizeof(double) * kModelStride));
@@ -2359,6 +2360,8 @@ int pl_ransac_run_sharded(pl_problem *p, const pl_robust_options *opt, const pl_
         return fail(PL_ERR_INVALID, "shard: need 0 <= rank < world");
     if (shard->world > 1 && !shard->allgather)
         return fail(PL_ERR_INVALID, "shard: all-gather callback missing");
+    if (p && p->kind == EST_RAD1D)
+        return fail(PL_ERR_UNSUPPORTED, "1D-radial problems (kind 5) are not served by the sharded run");
     g_shard = shard;
     const int rc = pl_ransac_run(p, opt, model, inliers, stats);
     g_shard = nullptr;
@@ -2375,8 +2378,8 @@ int pl_score_model(pl_problem *p, const void *model, double max_error, uint64_t 
     if (p->device != c->device)
         return fail(PL_ERR_INVALID, "problem lives on another device than the calling thread's");
     double rec[kModelStride];
-    if (p->kind == EST_ABS || p->kind == EST_REL || p->kind == EST_RELT)
-        record_from_pose(static_cast<const pl_camera_pose *>(model), p->kind != EST_ABS, rec);
+    if (p->kind == EST_ABS || p->kind == EST_REL || p->kind == EST_RELT || p->kind == EST_RAD1D)
+        record_from_pose(static_cast<const pl_camera_pose *>(model), p->kind == EST_REL || p->kind == EST_RELT, rec);
     else
         store_matrix_model(rec, mat_from_colmajor(static_cast<const double *>(model)));
     HIP_TRY(c->tmp_model.ensure(sizeof(double) * kModelStride));
@@ -2412,7 +2415,7 @@ int pl_debug_score_stream(pl_problem *p, const void *models, size_t n, double ma
     if (n == 0)
         return PL_OK;
     const uint32_t H = (uint32_t)n;
-    if (p->kind == EST_RELT && p->n == 0) { // (no correspondence: no chunk to hold)
+    if ((p->kind == EST_RELT || p->kind == EST_RAD1D) && p->n == 0) { // (no correspondence: no chunk to hold)
         for (uint32_t k = 0; k < H; ++k) {
             if (counts)
                 counts[k] = 0;
@@ -2421,13 +2424,13 @@ int pl_debug_score_stream(pl_problem *p, const void *models, size_t n, double ma
         }
         return PL_OK;
     }
-    const bool pose_kind = (p->kind == EST_ABS || p->kind == EST_REL || p->kind == EST_RELT);
+    const bool pose_kind = (p->kind == EST_ABS || p->kind == EST_REL || p->kind == EST_RELT || p->kind == EST_RAD1D);
     std::vector<double> recs((size_t)H * kModelStride);
     std::vector<uint32_t> ident(H);
     for (uint32_t k = 0; k < H; ++k) {
         ident[k] = k;
         if (pose_kind)
-            record_from_pose(static_cast<const pl_camera_pose *>(models) + k, p->kind != EST_ABS, &recs[(size_t)k * kModelStride]);
+            record_from_pose(static_cast<const pl_camera_pose *>(models) + k, p->kind == EST_REL || p->kind == EST_RELT, &recs[(size_t)k * kModelStride]);
         else
             store_matrix_model(&recs[(size_t)k * kModelStride], mat_from_colmajor(static_cast<const double *>(models) + 9 * (size_t)k));
     }
@@ -2596,9 +2599,9 @@ int pl_refine_model(pl_problem *p, const pl_bundle_options *opt, const pl_camera
     if (p->device != c->device)
         return fail(PL_ERR_INVALID, "problem lives on another device than the calling thread's");
     RefineJob j;
-    const bool pose_kind = (p->kind == EST_ABS || p->kind == EST_REL || p->kind == EST_RELT);
+    const bool pose_kind = (p->kind == EST_ABS || p->kind == EST_REL || p->kind == EST_RELT || p->kind == EST_RAD1D);
     if (pose_kind)
-        record_from_pose(static_cast<const pl_camera_pose *>(model), p->kind != EST_ABS, j.record_in);
+        record_from_pose(static_cast<const pl_camera_pose *>(model), p->kind == EST_REL || p->kind == EST_RELT, j.record_in);
     else
         store_matrix_model(j.record_in, mat_from_colmajor(static_cast<const double *>(model)));
     j.opt = to_lm(*opt);
@@ -2764,6 +2767,74 @@ int pl_ransac_homography(const double *x1, const double *x2, size_t n, const pl_
     return ransac_oneshot(EST_HOM, x1, x2, n, opt, H, inliers, stats);
 }
 
+// ransac.cc:388-401: no scaling; the mask is get_inliers_1D_radial's (k_mask<EST_RAD1D>)
+int pl_ransac_1D_radial_pnp(const double *x, const double *X, size_t n, const pl_robust_options *opt, pl_camera_pose *pose,
+                            uint8_t *inliers, pl_ransac_stats *stats) {
+    return ransac_oneshot(EST_RAD1D, x, X, n, opt, pose, inliers, stats);
+}
+int pl_debug_radial1d_chunk(void) { return radial1d_score_chunk(); }
+// Diagnostic: the generator kernel of a resident kind-5 problem (k_generate<EST_RAD1D>) on caller-supplied minimal samples - the
+// path PROSAC's host-drawn samples take - with `slots_per_iter` record slots per iteration.  models: num_iters x slots_per_iter x 24
+// doubles (zero where no model was written), num_models: num_iters, totals: models counted per block table, models with the NaN
+// flag, BatchCtl.gen_overflow.
+int pl_debug_radial1d_generate(pl_problem *p, const uint32_t *samples, size_t num_iters, uint32_t slots_per_iter, double *models,
+                               uint32_t *num_models, uint32_t *totals) {
+    if (!p || !samples || !models || !num_models || !totals)
+        return fail(PL_ERR_INVALID, "null argument");
+    if (p->kind != EST_RAD1D)
+        return fail(PL_ERR_INVALID, "not a 1D-radial problem");
+    if (slots_per_iter < 1 || slots_per_iter > (uint32_t)max_models(EST_RAD1D) || num_iters == 0 || num_iters > (1u << 20))
+        return fail(PL_ERR_INVALID, "slots_per_iter must be 1..4, num_iters 1..2^20");
+    for (size_t i = 0; i < 5 * num_iters; ++i)
+        if (samples[i] >= p->n)
+            return fail(PL_ERR_INVALID, "sample index beyond the problem's correspondences");
+    Context *c;
+    int rc = get_context(&c);
+    if (rc != PL_OK)
+        return rc;
+    if (p->device != c->device)
+        return fail(PL_ERR_INVALID, "problem lives on another device than the calling thread's");
+    const uint32_t B = (uint32_t)num_iters, nblk = (B + 1023) / 1024;
+    const size_t rec_bytes = sizeof(double) * kModelStride * (size_t)B * slots_per_iter;
+    const size_t ctl_bytes = sizeof(BatchCtl) + sizeof(uint32_t) * (2 * (size_t)nblk + 2);
+    HIP_TRY(c->samples.ensure(sizeof(uint32_t) * 5 * B));
+    HIP_TRY(c->models.ensure(rec_bytes));
+    HIP_TRY(c->num_models.ensure(sizeof(uint32_t) * B));
+    HIP_TRY(c->ctl.ensure(ctl_bytes));
+    HIP_TRY(hipMemsetAsync(c->ctl.p, 0, ctl_bytes, c->stream));
+    HIP_TRY(hipMemsetAsync(c->models.p, 0, rec_bytes, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->samples.p, samples, sizeof(uint32_t) * 5 * B, hipMemcpyHostToDevice, c->stream));
+    uint32_t *blk_tot = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(c->ctl.p) + sizeof(BatchCtl));
+    GenerateArgs ga;
+    ga.pts = p->ps;
+    ga.seed = 0;
+    ga.pos_base = 0;
+    ga.positions = nullptr;
+    ga.samples = c->samples.as<uint32_t>();
+    ga.num_iters = B;
+    ga.slots_per_iter = slots_per_iter;
+    ga.ctl = c->ctl.as<BatchCtl>();
+    ga.models = c->models.as<double>();
+    ga.num_models = c->num_models.as<uint32_t>();
+    ga.real_focal_check = 0;
+    ga.blk_tot = blk_tot;
+    ga.blk_nan = blk_tot + nblk;
+    HIP_TRY(launch_generate(EST_RAD1D, ga, c->stream));
+    std::vector<unsigned char> hctl(ctl_bytes);
+    HIP_TRY(hipMemcpyAsync(models, c->models.p, rec_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(num_models, c->num_models.p, sizeof(uint32_t) * B, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(hctl.data(), c->ctl.p, ctl_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(wait_stream(c));
+    BatchCtl ctl;
+    std::memcpy(&ctl, hctl.data(), sizeof(ctl));
+    const uint32_t *tab = reinterpret_cast<const uint32_t *>(hctl.data() + sizeof(BatchCtl));
+    totals[0] = totals[1] = 0;
+    for (uint32_t b = 0; b < nblk; ++b)
+        totals[0] += tab[b], totals[1] += tab[nblk + b];
+    totals[2] = ctl.gen_overflow;
+    return PL_OK;
+}
+
 // ---------------------------------------------------------------------------- front-ends (robust.cc)
 // the final bundle of a front-end over the inliers of the loop's model (the device mask ransac_core / run_focal left in c->mask)
 int front_final_refine(Context *c, pl_problem *p, const FrontEnd &fe, double *rec, CameraParams *cam_refined) {
@@ -2828,6 +2899,62 @@ int pl_estimate_absolute_pose(const double *points2D, const double *points3D, si
     if (rc != PL_OK)
         return rc;
     front_finish(fe, rec, &refined, pose, camera);
+    return PL_OK;
+}
+
+// robust.cc:889-934: absolute pose of a 1D-radial camera from centred pixels.  The pixels are multiplied by n / sum |x_k| (summed in
+// index order) on the host as they are copied into the problem's block (one pass for the sum, the product in make_problem's copy;
+// the block is the resident-problem kind, uploaded once: its cost next to the pinned staging path has not been measured);
+// max_error and bundle.loss_scale with them.  The loop is
+// ransac_1D_radial_pnp's, the final bundle (bundle_adjust_1D_radial over the inliers, when there are more than 5) takes the caller's
+// bundle options; bundle.refine_* has no effect, as in the reference.  n < 5: default stats, pose and inliers untouched.
+int pl_estimate_1D_radial_absolute_pose(const double *points2D, const double *points3D, size_t n, const pl_robust_options *opt,
+                                        pl_camera_pose *pose, uint8_t *inliers, pl_ransac_stats *stats) {
+    int rc = validate_options(opt);
+    if (rc != PL_OK)
+        return rc;
+    if (!pose || ((!points2D || !points3D) && n))
+        return fail(PL_ERR_INVALID, "points / pose pointer is null");
+    pl_ransac_stats local;
+    pl_ransac_stats *st = stats ? stats : &local;
+    if (n < 5) {
+        std::memset(st, 0, sizeof(*st));
+        return PL_OK;
+    }
+    Context *c;
+    rc = get_context(&c);
+    if (rc != PL_OK)
+        return rc;
+    double scale = 0.0;
+    for (size_t k = 0; k < n; ++k)
+        scale += std::sqrt(0.0 + points2D[2 * k] * points2D[2 * k] + points2D[2 * k + 1] * points2D[2 * k + 1]);
+    scale = static_cast<double>(n) / scale;
+    pl_robust_options so = *opt;
+    so.max_error *= scale;
+    so.bundle.loss_scale *= scale;
+    pl_problem p;
+    rc = make_problem(c, EST_RAD1D, points2D, points3D, n, &p, scale); // (the pixels are multiplied as they are copied)
+    if (rc != PL_OK)
+        return rc;
+    double rec[kModelStride];
+    if (so.ransac.score_initial_model)
+        record_from_pose(pose, false, rec);
+    else
+        identity_record(EST_RAD1D, rec);
+    rc = ransac_core(c, &p, &so, rec, inliers, st);
+    if (rc == PL_OK && st->num_inliers > 5) {
+        CameraParams none;
+        std::memset(&none, 0, sizeof(none));
+        none.model_id = CAM_NULL;
+        double out[kModelStride];
+        rc = final_refine(c, &p, rec, to_lm(so.bundle), none, 1.0, out, nullptr);
+        if (rc == PL_OK)
+            std::memcpy(rec, out, sizeof(out));
+    }
+    free_problem(&p);
+    if (rc != PL_OK)
+        return rc;
+    pose_from_record(rec, pose);
     return PL_OK;
 }
 
@@ -2977,7 +3104,7 @@ int pl_undistort_points(const pl_camera *camera, const double *points2D, size_t 
 
 // ---------------------------------------------------------------------------- minimal solvers
 int pl_solve_batch(int kind, const double *in, size_t count, double *out_models, uint32_t *out_counts) {
-    if (kind < 0 || kind > 3)
+    if ((kind < 0 || kind > 3) && kind != EST_RAD1D) // (5: p5lp_radial - in: x 5 x 3 (third component not read), X 5 x 3; <= 4 models)
         return fail(PL_ERR_INVALID, "unknown solver kind");
     Context *c;
     int rc = get_context(&c);
@@ -3080,6 +3207,23 @@ int pl_p3p(const double *x, const double *X, pl_camera_pose *out) {
         return rc;
     for (uint32_t i = 0; i < n; ++i)
         pose_from_record(rec + i * kModelStride, out + i);
+    return (int)n;
+}
+int pl_p5lp_radial(const double *x, const double *X, pl_camera_pose *out, int *count) {
+    if (!x || !X || !out)
+        return fail(PL_ERR_INVALID, "null argument");
+    double x3[15];
+    for (int k = 0; k < 5; ++k)
+        x3[3 * k] = x[2 * k], x3[3 * k + 1] = x[2 * k + 1], x3[3 * k + 2] = 0.0;
+    double rec[4 * kModelStride];
+    uint32_t n = 0;
+    int rc = solve_one(EST_RAD1D, x3, X, rec, &n);
+    if (rc != PL_OK)
+        return rc;
+    for (uint32_t i = 0; i < n; ++i)
+        pose_from_record(rec + i * kModelStride, out + i);
+    if (count)
+        *count = (int)n;
     return (int)n;
 }
 int pl_relpose_5pt(const double *x1, const double *x2, pl_camera_pose *out) {

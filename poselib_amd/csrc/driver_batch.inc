@@ -138,8 +138,10 @@ int run_item(pl_batch_item &it) {
         return pl_estimate_shared_focal_relative_pose(it.a, it.b, it.n, it.camera1->params + 1, it.opt,
                                                       static_cast<pl_camera_pose *>(it.model), &it.camera1->params[0], it.inliers, it.stats);
     }
+    case EST_RAD1D: // 1D-radial absolute pose: a = centred pixels, b = 3-D points; no camera
+        return pl_estimate_1D_radial_absolute_pose(it.a, it.b, it.n, it.opt, static_cast<pl_camera_pose *>(it.model), it.inliers, it.stats);
     default:
-        return fail(PL_ERR_INVALID, "pl_batch_item.kind must be 0..4");
+        return fail(PL_ERR_INVALID, "pl_batch_item.kind must be 0..5");
     }
 }
 

@@ -37,6 +37,7 @@
 #include "pl_sampler.h"
 #include "pl_solver_h4.h"
 #include "pl_solver_p3p.h"
+#include "pl_solver_p5lp_radial.h"
 #include "pl_solver_rel.h"
 
 namespace pl {
@@ -207,6 +208,26 @@ template <int EST> __device__ __forceinline__ uint32_t generate_one(const Genera
         n = p3p_emit(xb[0], xb[1], xb[2], Xp[0], Xp[1], Xp[2], [&](int m, const Mat3 &R, const Vec3 &t) {
             n_nan += store_pose_model(rec + m * kModelStride, R, t, false) ? 1u : 0u;
         }); // (the generator kernels take generate_abs_wave instead: the second half on full wavefronts of candidates)
+    } else if constexpr (EST == EST_RAD1D) {
+        // absolute_pose.cc:353-361: the 2-D sample points as unit vectors, then p5lp_radial; one lane per sample, everything in registers
+        double xs[5][2], Xs[5][3];
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            normalized2(g.pts.a[0][idx[k]], g.pts.a[1][idx[k]], xs[k][0], xs[k][1]);
+            Xs[k][0] = g.pts.a[2][idx[k]], Xs[k][1] = g.pts.a[3][idx[k]], Xs[k][2] = g.pts.a[4][idx[k]];
+        }
+        const uint32_t room = g.slots_per_iter;
+        bool over = false;
+        n = p5lp_radial_emit(xs, Xs, [&](int m, const Mat3 &R, const Vec3 &t) {
+            if ((uint32_t)m < room)
+                n_nan += store_pose_model(rec + m * kModelStride, R, t, false) ? 1u : 0u;
+            else
+                over = true;
+        });
+        if (over) {
+            g.ctl->gen_overflow = 1;
+            n = 0;
+        }
     } else {
         Vec3 b1[K], b2[K];
 #pragma unroll
@@ -301,6 +322,13 @@ template <int EST> __global__ __launch_bounds__(64) void k_solve_batch(const dou
         n = p3p(a[0], a[1], a[2], b[0], b[1], b[2], sol);
         for (int m = 0; m < n; ++m)
             store_pose_model(rec + m * kModelStride, sol[m].R, sol[m].t, false);
+    } else if constexpr (EST == EST_RAD1D) { // a: the 2-D points (third component not read), b: the 3-D points
+        double xs[5][2], Xs[5][3];
+        for (int k = 0; k < 5; ++k) {
+            xs[k][0] = a[k].x, xs[k][1] = a[k].y;
+            Xs[k][0] = b[k].x, Xs[k][1] = b[k].y, Xs[k][2] = b[k].z;
+        }
+        n = p5lp_radial_emit(xs, Xs, [&](int m, const Mat3 &R, const Vec3 &t) { store_pose_model(rec + m * kModelStride, R, t, false); });
     } else if constexpr (EST == EST_HOM) {
         Mat3 H;
         n = homography_4pt(a, b, H, true);
@@ -344,6 +372,8 @@ __device__ __forceinline__ bool eval_point(const double *M, const double *pt, do
         return sampson_inlier(M, pt[0], pt[1], pt[2], pt[3], thr2, r2);
     else if constexpr (EST == EST_RELT)
         return tangent_pose_inlier(M, pt, thr2, r2);
+    else if constexpr (EST == EST_RAD1D)
+        return radial1d_inlier(M, pt[0], pt[1], pt[2], pt[3], pt[4], thr2, r2);
     else
         return homography_inlier(M, pt[0], pt[1], pt[2], pt[3], thr2, r2);
 }
@@ -922,6 +952,213 @@ __global__ __launch_bounds__(kQueueThreads) void k_score_tangent(PointSet pts, c
                                                                   double thr2, PrefilterArgs pf, uint32_t *__restrict__ part_count,
                                                                   double *__restrict__ part_score) {
     score_tangent_body(pts, shadow, compact64, num_hyp_ptr, hyp_capacity, thr2, pf, part_count, part_score, blockIdx.x, blockIdx.y,
+                       gridDim.x);
+}
+
+// ---- 1D-radial absolute pose: the streaming scorer of EST_RAD1D -------------------------------------------------------------------
+// k_score_radial1d: k_score_tangent's scheme (stationary correspondences, hypotheses streamed as fp32 shadows through scalar loads,
+// conservative fp32 pre-filter -> wave-private queue -> exact fp64 drain, inliers summed from a second ring so that the scores have
+// the same bits with the filter off) for correspondences of 5 numbers.  A lane holds kRadialP = 4 correspondences: 20 fp32 operands +
+// 8 slack factors in registers, the fp64 originals of the chunk's 256 correspondences in LDS.  The filter (pl_prefilter.h, 1D radial)
+// is pf_radial1d_outlier per correspondence; the drain evaluates radial1d_inlier of pl_score.h, the expression of
+// k_score_seq<EST_RAD1D>.
+constexpr int kRadialP = 4;
+constexpr int kRadialChunk = 64 * kRadialP;
+__device__ __forceinline__ void score_radial1d_body(const PointSet &pts, const float *__restrict__ shadow,
+                                                   const double *__restrict__ compact64,
+                                                   const uint32_t *__restrict__ num_hyp_ptr, uint32_t hyp_capacity, double thr2,
+                                                   const PrefilterArgs &pf, uint32_t *__restrict__ part_count,
+                                                   double *__restrict__ part_score, uint32_t slice, uint32_t chunk,
+                                                   uint32_t nslices) {
+    constexpr int kWaves = kQueueThreads / 64;
+    constexpr int ND = 5, P = kRadialP, NPW = kRadialChunk;
+    __shared__ double s_pts[ND][NPW];
+    __shared__ uint16_t s_queue[kWaves][kQueueCap]; // entries: hypothesis of the group << 9 | correspondence of the chunk
+    __shared__ double s_acc_s[kWaves][64];
+    __shared__ uint32_t s_acc_c[kWaves][64];
+    // the inliers found by the drains, in (hypothesis, correspondence) order: r^2 and hypothesis of the group.  They are summed 64 at
+    // a time from here, so the association of a hypothesis' sum depends on the sequence of its unit's inliers alone - not on how many
+    // non-inliers shared their drains: the scores come out with the same bits whether the filter runs or not
+    constexpr int kInlierCap = 128; // <= 63 waiting + 64 appended by one drain
+    __shared__ double s_inl_v[kWaves][kInlierCap];
+    __shared__ uint16_t s_inl_g[kWaves][kInlierCap];
+    __shared__ uint32_t s_next_unit;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+
+    float pf32[P][ND]; // x, y, X, Y, Z in fp32
+    float bnd[P][2];   // the correspondence's two slack factors (pl_prefilter.h)
+    uint64_t vmask[P];
+    const float thrp = pf_radial1d_thr(pf.thr);
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+        const uint32_t i = chunk * NPW + p * 64 + lane;
+        const bool valid = i < pts.n;
+        const uint32_t ic = valid ? i : 0u;
+        vmask[p] = __builtin_amdgcn_ballot_w64(valid);
+        double x[ND];
+        load_point<EST_RAD1D>(pts, ic, x);
+        if (wave == p) {
+#pragma unroll
+            for (int d = 0; d < ND; ++d)
+                s_pts[d][p * 64 + lane] = x[d];
+        }
+        pf_radial1d_point(x, pf.thr, pf32[p], bnd[p]);
+    }
+    if (threadIdx.x == 0)
+        s_next_unit = 0;
+    __syncthreads(); // the only workgroup barrier: fp64 correspondences are in LDS
+
+    const uint32_t H = *as_uniform(num_hyp_ptr);
+    const uniform_f32_ptr sh = as_uniform(shadow);
+    uint16_t *const queue = s_queue[wave];
+    double *const acc_s = s_acc_s[wave];
+    uint32_t *const acc_c = s_acc_c[wave];
+    double *const inl_v = s_inl_v[wave];
+    uint16_t *const inl_g = s_inl_g[wave];
+
+    const uint32_t waves_per_chunk = nslices * kWaves;
+    auto request_ticket = [&]() -> uint32_t { // per-lane value; lane 0 holds the workgroup's next unit
+        uint32_t t = 0;
+        if (lane == 0) {
+            const uint32_t k = atomicAdd(&s_next_unit, 1u);
+            t = slice * kWaves + (k % kWaves) + (k / kWaves) * waves_per_chunk;
+        }
+        return t;
+    };
+    uint32_t ticket = (uint32_t)__builtin_amdgcn_readfirstlane((int)request_ticket());
+    uint32_t kb, gn;
+    while (unit_of_ticket(ticket, H, waves_per_chunk, kb, gn)) {
+        const uint32_t pending = request_ticket(); // the next unit's index travels while this one is evaluated
+        acc_s[lane] = 0.0;
+        acc_c[lane] = 0;
+        uint32_t qhead = 0, qtail = 0; // wave-uniform ring positions
+        uint32_t ihead = 0, itail = 0; // ... and of the ring of inliers
+
+        auto add_inliers = [&](uint32_t n) { // n <= 64 waiting inliers, one per lane
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            const bool act = (uint32_t)lane < n;
+            const uint32_t at = (ihead + lane) & (kInlierCap - 1);
+            const uint32_t g = act ? (uint32_t)inl_g[at] : 0x7fu;
+            const double v = act ? inl_v[at] : 0.0;
+            const uint64_t actmask = __builtin_amdgcn_ballot_w64(act);
+            const uint32_t g0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)g);
+            if (!__builtin_amdgcn_ballot_w64(act && g != g0)) {
+                // all of them belong to one hypothesis (the usual case when a good model's inliers arrive): a plain wave sum
+                const double tot = wave_sum_dpp(v);
+                if (lane == 0) {
+                    acc_s[g0] += tot;
+                    acc_c[g0] += (uint32_t)__popcll(actmask);
+                }
+            } else {
+                // segmented inclusive scan; keys (hypothesis) ascend with the lane
+                add_run_totals(v, actmask, g, act, lane, acc_s, acc_c);
+            }
+            ihead += n;
+        };
+
+        auto drain = [&](uint32_t n) { // n <= 64 waiting pairs, one per lane
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            const bool act = (uint32_t)lane < n;
+            const uint32_t e = act ? (uint32_t)queue[(qhead + lane) & (kQueueCap - 1)] : 0xffffu;
+            const uint32_t g = e >> 9, pi = act ? (e & 0x1ffu) : 0u;
+            double x[ND];
+#pragma unroll
+            for (int d = 0; d < ND; ++d)
+                x[d] = s_pts[d][pi];
+            const double *Mp = compact64 + (size_t)(kb + (act ? g : 0u)) * kModelDoubles;
+            double M[kModelDoubles];
+#pragma unroll
+            for (int i = 0; i < kModelDoubles; ++i)
+                M[i] = Mp[i];
+            double r2;
+            const bool in = radial1d_inlier(M, x[0], x[1], x[2], x[3], x[4], thr2, r2) && act;
+            const uint64_t inmask = __builtin_amdgcn_ballot_w64(in);
+            if (inmask) { // append the inliers, still ordered by (hypothesis, correspondence)
+                const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(inmask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)inmask, 0u));
+                if (in) {
+                    inl_v[(itail + below) & (kInlierCap - 1)] = r2;
+                    inl_g[(itail + below) & (kInlierCap - 1)] = (uint16_t)g;
+                }
+                itail += (uint32_t)__popcll(inmask);
+                if (itail - ihead >= 64u)
+                    add_inliers(64u);
+            }
+            qhead += n;
+        };
+
+        auto step = [&](const float(&r)[15], uint32_t g) {
+            // a NaN among the entries this score reads (first two rows of R, t_x, t_y) makes every alpha NaN: zero inliers.  (The record's
+            // flag also covers the third row and t_z, which the score does not read: not used here.)
+            if ((r[0] != r[0]) | (r[1] != r[1]) | (r[2] != r[2]) | (r[3] != r[3]) | (r[4] != r[4]) | (r[5] != r[5]) | (r[9] != r[9]) | (r[10] != r[10]))
+                return;
+            uint64_t m[P];
+            uint64_t any = 0;
+            if (!pf.enabled || !(r[14] < __builtin_huge_valf())) { // filter off, or a model outside its range: all exact
+#pragma unroll
+                for (int p = 0; p < P; ++p)
+                    m[p] = vmask[p], any |= m[p];
+            } else {
+#pragma unroll
+                for (int p = 0; p < P; ++p) {
+                    m[p] = vmask[p] & ~__builtin_amdgcn_ballot_w64(pf_radial1d_outlier(r, thrp, pf32[p], bnd[p]));
+                    any |= m[p];
+                }
+            }
+            if (any) { // wave-uniform: append the survivors, ordered by (slot, lane)
+#pragma unroll
+                for (int p = 0; p < P; ++p) {
+                    if (m[p]) {
+                        const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(m[p] >> 32),
+                                                                         __builtin_amdgcn_mbcnt_lo((uint32_t)m[p], 0u));
+                        if ((m[p] >> lane) & 1u)
+                            queue[(qtail + below) & (kQueueCap - 1)] = (uint16_t)((g << 9) | (uint32_t)(p * 64 + lane));
+                        qtail += (uint32_t)__popcll(m[p]);
+                    }
+                }
+                while (qtail - qhead >= 64u)
+                    drain(64u);
+            }
+        };
+        auto fetch = [&](float(&r)[15], uint32_t g) {
+            const uniform_f32_ptr sp = sh + (size_t)(kb + g) * 16;
+#pragma unroll
+            for (int i = 0; i < 15; ++i)
+                r[i] = sp[i];
+        };
+
+        float ra[15], rb[15];
+        fetch(ra, 0);
+        for (uint32_t g = 0; g < gn; g += 2) {
+            const bool two = g + 1 < gn;
+            if (two)
+                fetch(rb, g + 1);
+            step(ra, g);
+            if (two) {
+                if (g + 2 < gn)
+                    fetch(ra, g + 2);
+                step(rb, g + 1);
+            }
+        }
+        while (qtail != qhead)
+            drain(min(64u, qtail - qhead));
+        if (itail != ihead)
+            add_inliers(itail - ihead);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        if ((uint32_t)lane < gn) {
+            const size_t o = (size_t)chunk * hyp_capacity + kb + lane;
+            part_score[o] = acc_s[lane];
+            part_count[o] = acc_c[lane];
+        }
+        ticket = (uint32_t)__builtin_amdgcn_readfirstlane((int)pending);
+    }
+}
+__global__ __launch_bounds__(kQueueThreads) void k_score_radial1d(PointSet pts, const float *__restrict__ shadow,
+                                                                  const double *__restrict__ compact64,
+                                                                  const uint32_t *__restrict__ num_hyp_ptr, uint32_t hyp_capacity,
+                                                                  double thr2, PrefilterArgs pf, uint32_t *__restrict__ part_count,
+                                                                  double *__restrict__ part_score) {
+    score_radial1d_body(pts, shadow, compact64, num_hyp_ptr, hyp_capacity, thr2, pf, part_count, part_score, blockIdx.x, blockIdx.y,
                        gridDim.x);
 }
 
@@ -1876,8 +2113,8 @@ __device__ __forceinline__ void mask_body(const PointSet &pts, const double *mod
     bool in;
     if constexpr (EST == EST_ABS) {
         in = reproj_mask(M, pts.a[0][i], pts.a[1][i], pts.a[2][i], pts.a[3][i], pts.a[4][i], thr2);
-    } else if constexpr (EST == EST_RELT) { // get_tangent_sampson_inliers, utils.cc:541-568: the score's own decision
-        double r2, pt[18];
+    } else if constexpr (EST == EST_RELT || EST == EST_RAD1D) { // get_tangent_sampson_inliers, utils.cc:541-568, and
+        double r2, pt[point_doubles(EST)];                           // get_inliers_1D_radial, utils.cc:571-582: the score's own decision
         load_point<EST>(pts, i, pt);
         in = eval_point<EST>(M, pt, thr2, r2);
     } else {
@@ -1911,7 +2148,7 @@ __device__ __forceinline__ void lm_start_params(int est, const LMTask &T, double
     }
     for (int i = 0; i < kParamDoubles; ++i)
         cur[i] = 0.0;
-    if (est == EST_ABS || est == EST_REL || est == EST_RELT) {
+    if (est == EST_ABS || est == EST_REL || est == EST_RELT || est == EST_RAD1D) {
         for (int i = 0; i < 7; ++i)
             cur[i] = T.start_record[i];
     } else {
@@ -1919,6 +2156,9 @@ __device__ __forceinline__ void lm_start_params(int est, const LMTask &T, double
             cur[i] = T.start_record[kMatOff + i];
     }
 }
+
+// estimators whose refiner takes a 2-D point, a 3-D point and returns a 2-vector residual (the call shape of Refiner<EST_ABS>)
+template <int EST> constexpr bool kAbsLike = (EST == EST_ABS || EST == EST_RAD1D);
 
 template <int N> struct BlockReduce {
     // Reduces N per-thread doubles (+ one counter) over the 1024-thread workgroup.  Result in out[0..N)
@@ -2260,7 +2500,7 @@ template <int EST> __global__ __launch_bounds__(kLMThreads) void k_lm(LMTask *ta
         // One correspondence into the normal equations (jac) or into the robust cost (!jac) of this thread's accumulators
         // (named directly - handed over as pointers they would live in scratch memory)
         auto point = [&](uint32_t i, bool jacobian_pass) {
-            if constexpr (EST == EST_ABS) {
+            if constexpr (kAbsLike<EST>) {
                 const double x = pts.a[0][i] * pscale, y = pts.a[1][i] * pscale;
                 const double X = pts.a[2][i], Y = pts.a[3][i], Z = pts.a[4][i];
                 double r0, r1;
@@ -2333,7 +2573,7 @@ template <int EST> __global__ __launch_bounds__(kLMThreads) void k_lm(LMTask *ta
             uint32_t cn = 0, cnj = 0;
             // (the same expressions as `point`, into this correspondence's own terms; the homography's backward block apart)
                 auto point_terms = [&](uint32_t i, bool jacobian_pass) {
-                if constexpr (EST == EST_ABS) {
+                if constexpr (kAbsLike<EST>) {
                     const double x = pts.a[0][i] * pscale, y = pts.a[1][i] * pscale;
                     const double X = pts.a[2][i], Y = pts.a[3][i], Z = pts.a[4][i];
                     double r0, r1;
@@ -2494,7 +2734,7 @@ template <int EST> __global__ __launch_bounds__(kLMThreads) void k_lm(LMTask *ta
                 const uint32_t i = base + (uint32_t)lane;
                 bool keep = false;
                 if (i < pts.n && !(mask && !mask[i])) { // (res: the residual pass's terms, in its per-lane order)
-                    if constexpr (EST == EST_ABS) {
+                    if constexpr (kAbsLike<EST>) {
                         double r0, r1;
                         const bool valid = R::residual(p, ctx, cam, pts.a[0][i] * pscale, pts.a[1][i] * pscale, pts.a[2][i],
                                                        pts.a[3][i], pts.a[4][i], r0, r1);
@@ -2888,13 +3128,13 @@ template <int EST> __global__ __launch_bounds__(kLMThreads, 2) void k_lm_ordered
                 const bool live = i < n && !(mask && !mask[i]);
                 double cterm[SUB];
                 double r0 = 0, r1 = 0, g0 = 0, g1 = 0;
-                double J[(EST == EST_ABS || EST == EST_HOM) ? 2 * K : K], Jb[(EST == EST_HOM) ? 2 * K : 1];
+                double J[(kAbsLike<EST> || EST == EST_HOM) ? 2 * K : K], Jb[(EST == EST_HOM) ? 2 * K : 1];
                 bool have = false; // this correspondence contributes a Jacobian row
 #pragma unroll
                 for (int u = 0; u < SUB; ++u)
                     cterm[u] = 0.0;
                 if (live) {
-                    if constexpr (EST == EST_ABS) {
+                    if constexpr (kAbsLike<EST>) {
                         const double x = pts.a[0][i] * pscale, y = pts.a[1][i] * pscale;
                         const double X = pts.a[2][i], Y = pts.a[3][i], Z = pts.a[4][i];
                         if (res) {
@@ -2941,7 +3181,7 @@ template <int EST> __global__ __launch_bounds__(kLMThreads, 2) void k_lm_ordered
                     if (jac) {
                         auto store = [&](int a, double v) { s_ring[slot][a][row] = v; };
                         if (have) {
-                            if constexpr (EST == EST_ABS)
+                            if constexpr (kAbsLike<EST>)
                                 terms2<K>(loss, r0, r1, J, cnj, store);
                             else if constexpr (EST == EST_HOM) {
                                 if (u == 0)
@@ -3279,9 +3519,27 @@ __global__ __launch_bounds__(kLM2Threads) void k_lm2(PointSet pts, LMTask *tasks
     }
 
 // ... and for the kernels that exist for EST_RELT as well (k_score_seq, k_mask, k_lm: no k_generate / k_lm_ordered / k_lm2 of that kind)
-#define PL_DISPATCH_EST5(est, ...)                                                                                    \
+#define PL_DISPATCH_EST_0TO4(est, ...)                                                                                    \
     if ((est) == EST_RELT) {                                                                                           \
         constexpr int E = EST_RELT;                                                                                    \
+        __VA_ARGS__;                                                                                                    \
+    } else {                                                                                                           \
+        PL_DISPATCH_EST(est, __VA_ARGS__)                                                                              \
+    }
+
+// The dispatch macros are named by the kinds they cover: PL_DISPATCH_EST kinds 0 - 3 (every kernel, the group forms and k_lm2
+// included), _0TO4 with EST_RELT (k_score_seq, k_mask, k_lm), _0TO5 with EST_RAD1D as well, _0123_5 the kernels EST_RAD1D has and
+// EST_RELT has not (k_generate, k_solve_batch, k_lm_ordered)
+#define PL_DISPATCH_EST_0TO5(est, ...)                                                                                    \
+    if ((est) == EST_RAD1D) {                                                                                          \
+        constexpr int E = EST_RAD1D;                                                                                   \
+        __VA_ARGS__;                                                                                                    \
+    } else {                                                                                                           \
+        PL_DISPATCH_EST_0TO4(est, __VA_ARGS__)                                                                             \
+    }
+#define PL_DISPATCH_EST_0123_5(est, ...)                                                                             \
+    if ((est) == EST_RAD1D) {                                                                                          \
+        constexpr int E = EST_RAD1D;                                                                                   \
         __VA_ARGS__;                                                                                                    \
     } else {                                                                                                           \
         PL_DISPATCH_EST(est, __VA_ARGS__)                                                                              \
@@ -3296,7 +3554,7 @@ hipError_t launch_generate(int est, const GenerateArgs &a, hipStream_t stream) {
         return launch_generate_rel(a, stream);
     if (est == EST_RELT) // (the staged generator alone serves the tangent-Sampson bearings)
         return a.stage ? launch_generate_rel(a, stream, true) : hipErrorInvalidValue;
-    PL_DISPATCH_EST(est, k_generate<E><<<grid, block, 0, stream>>>(a));
+    PL_DISPATCH_EST_0123_5(est, k_generate<E><<<grid, block, 0, stream>>>(a));
     return hipGetLastError();
 }
 
@@ -3309,7 +3567,7 @@ hipError_t launch_solve_batch(int est, const double *in, uint32_t np, double *mo
         k_solve_essential<<<grid, block, 0, stream>>>(in, np, models, num_models);
         return hipGetLastError();
     }
-    PL_DISPATCH_EST(est, k_solve_batch<E><<<grid, block, 0, stream>>>(in, np, models, num_models));
+    PL_DISPATCH_EST_0123_5(est, k_solve_batch<E><<<grid, block, 0, stream>>>(in, np, models, num_models));
     return hipGetLastError();
 }
 
@@ -3319,6 +3577,11 @@ hipError_t launch_solve_batch(int est, const double *in, uint32_t np, double *mo
 // per-hypothesis overhead): pairs of points share packed instructions, an odd point costs as much as a pair.
 static void score_shape(int est, uint32_t n, bool streaming, bool mfma, uint32_t &chunks, int &P) {
     const uint32_t lanes = streaming ? 64u : (uint32_t)kScoreThreads;
+    if (est == EST_RAD1D) { // k_score_radial1d: a fixed chunk
+        P = kRadialP;
+        chunks = std::max<uint32_t>(1u, (n + (uint32_t)kRadialChunk - 1) / (uint32_t)kRadialChunk);
+        return;
+    }
     if (est == EST_RELT) { // k_score_tangent: a fixed chunk (18 fp32 operands per correspondence bound the lane's share)
         P = kTangentP;
         chunks = std::max<uint32_t>(1u, (n + (uint32_t)kTangentChunk - 1) / (uint32_t)kTangentChunk);
@@ -3360,7 +3623,7 @@ static void score_shape(int est, uint32_t n, bool streaming, bool mfma, uint32_t
 }
 bool score_uses_mfma(int est, uint32_t n_points, const PrefilterArgs &pf) {
     static const bool off = std::getenv("POSELIB_AMD_NO_MFMA") != nullptr;
-    if (off || !pf.enabled || n_points < 1024u || est == EST_RELT) // (tangent Sampson: no matrix-core form)
+    if (off || !pf.enabled || n_points < 1024u || est == EST_RELT || est == EST_RAD1D) // (tangent Sampson, 1D radial: no matrix-core form)
         return false;
     if (est == EST_ABS)
         return pf.g16 > 0.f && pf.thr <= 1.0f;
@@ -3499,11 +3762,21 @@ hipError_t launch_score_seq(int est, const SeqScoreArgs &a, hipStream_t stream) 
     if (a.cap == 0)
         return hipSuccess;
     const dim3 grid(std::min<uint32_t>(a.cap, 128u)), block(kSeqThreads); // (candidate lists hold a few dozen entries)
-    PL_DISPATCH_EST5(est, k_score_seq<E><<<grid, block, 0, stream>>>(a));
+    PL_DISPATCH_EST_0TO5(est, k_score_seq<E><<<grid, block, 0, stream>>>(a));
     return hipGetLastError();
 }
 int tangent_score_chunk() { return kTangentChunk; }
+int radial1d_score_chunk() { return kRadialChunk; }
 hipError_t launch_score(int est, const ScoreArgs &a, uint32_t slices, hipStream_t stream) {
+    if (est == EST_RAD1D) {
+        if (!a.shadow || !a.compact64)
+            return hipErrorInvalidValue; // only the streaming form exists
+        const uint32_t chunks = score_chunks(est, a.pts.n, true, false);
+        const dim3 qgrid(std::max<uint32_t>(1u, slices * (uint32_t)kScoreThreads / (uint32_t)kQueueThreads), chunks);
+        k_score_radial1d<<<qgrid, dim3(kQueueThreads), 0, stream>>>(a.pts, a.shadow, a.compact64, a.num_hyp, a.hyp_capacity, a.thr2, a.pf,
+                                                                    a.part_count, a.part_score);
+        return hipGetLastError();
+    }
     if (est == EST_RELT) {
         if (!a.shadow || !a.compact64)
             return hipErrorInvalidValue; // only the streaming form exists
@@ -3567,21 +3840,21 @@ extern "C" int pl_debug_lm_profile(unsigned long long *out16, int reset) {
 hipError_t launch_lm_tasks(int est, LMTask *tasks, uint32_t num_tasks, uint32_t max_points, hipStream_t stream) {
     if (num_tasks == 0)
         return hipSuccess;
-    if (est < 0 || est > EST_RELT)
+    if (est < 0 || est > EST_RAD1D)
         return hipErrorInvalidValue;
     const int ordered = lm_sums_ordered(est) ? 1 : 0; // (never for EST_RELT: k_lm alone serves it)
     // stage the points in LDS when they fit next to the kernel's static LDS (160 KB per CU, one workgroup per CU); tasks
     // of a mixed launch whose points do not fit the launch's dynamic LDS read them from L2
     // (a request the points do not fit into would only keep every other workgroup off the CU: no staging then)
-    static std::atomic<int> dyn_limit[2][5] = {{{-1}, {-1}, {-1}, {-1}, {-1}}, {{-1}, {-1}, {-1}, {-1}, {-1}}}; // bytes of dynamic LDS the kernel may ask for
+    static std::atomic<int> dyn_limit[2][6] = {{{-1}, {-1}, {-1}, {-1}, {-1}, {-1}}, {{-1}, {-1}, {-1}, {-1}, {-1}, {-1}}}; // bytes of dynamic LDS the kernel may ask for
     int limit = dyn_limit[ordered][est].load(std::memory_order_acquire);
     if (limit < 0) {
         hipFuncAttributes fa;
         hipError_t e = hipSuccess;
         if (ordered) {
-            PL_DISPATCH_EST(est, e = hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&k_lm_ordered<E>)));
+            PL_DISPATCH_EST_0123_5(est, e = hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&k_lm_ordered<E>)));
         } else {
-            PL_DISPATCH_EST5(est, e = hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&k_lm<E>)));
+            PL_DISPATCH_EST_0TO5(est, e = hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&k_lm<E>)));
         }
         if (e != hipSuccess)
             return e;
@@ -3589,10 +3862,10 @@ hipError_t launch_lm_tasks(int est, LMTask *tasks, uint32_t num_tasks, uint32_t 
         limit = std::min<int>(limit, 128 * 1024);
         if (limit > 48 * 1024) {
             if (ordered) {
-                PL_DISPATCH_EST(est, e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_lm_ordered<E>),
+                PL_DISPATCH_EST_0123_5(est, e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_lm_ordered<E>),
                                                              hipFuncAttributeMaxDynamicSharedMemorySize, limit));
             } else {
-                PL_DISPATCH_EST5(est, e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_lm<E>),
+                PL_DISPATCH_EST_0TO5(est, e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_lm<E>),
                                                               hipFuncAttributeMaxDynamicSharedMemorySize, limit));
             }
             if (e != hipSuccess)
@@ -3603,9 +3876,9 @@ hipError_t launch_lm_tasks(int est, LMTask *tasks, uint32_t num_tasks, uint32_t 
     const size_t want = sizeof(double) * point_doubles(est) * (size_t)max_points;
     const size_t bytes = want <= (size_t)limit ? want : 0;
     if (ordered) {
-        PL_DISPATCH_EST(est, k_lm_ordered<E><<<dim3(num_tasks), dim3(kLMThreads), bytes, stream>>>(tasks, (uint32_t)bytes));
+        PL_DISPATCH_EST_0123_5(est, k_lm_ordered<E><<<dim3(num_tasks), dim3(kLMThreads), bytes, stream>>>(tasks, (uint32_t)bytes));
     } else {
-        PL_DISPATCH_EST5(est, k_lm<E><<<dim3(num_tasks), dim3(kLMThreads), bytes, stream>>>(tasks, (uint32_t)bytes));
+        PL_DISPATCH_EST_0TO5(est, k_lm<E><<<dim3(num_tasks), dim3(kLMThreads), bytes, stream>>>(tasks, (uint32_t)bytes));
     }
     return hipGetLastError();
 }
@@ -3780,7 +4053,7 @@ hipError_t launch_mask(int est, const PointSet &pts, const double *model, double
     if (pts.n == 0)
         return hipSuccess;
     const dim3 grid((pts.n + 255) / 256), block(256);
-    PL_DISPATCH_EST5(est, k_mask<E><<<grid, block, 0, stream>>>(pts, model, thr2, mask, host_mask));
+    PL_DISPATCH_EST_0TO5(est, k_mask<E><<<grid, block, 0, stream>>>(pts, model, thr2, mask, host_mask));
     return hipGetLastError();
 }
 

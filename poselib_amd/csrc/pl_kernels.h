@@ -11,6 +11,7 @@ namespace pl {
 
 // Correspondences of one problem, structure-of-arrays in HBM, fp64.
 //   absolute pose : a[0..4] = x, y (normalised image plane), X, Y, Z
+//   1D-radial absolute pose (EST_RAD1D): a[0..4] = x, y (centred pixels times the front-end's scale), X, Y, Z
 //   two-view      : a[0..3] = x1, y1, x2, y2
 //   tangent Sampson (EST_RELT): a[0] = the block of 18 arrays d1[3] d2[3] M1[6] M2[6], component c at a[0] + c * n
 struct PointSet {
@@ -27,9 +28,9 @@ constexpr int kLMSeqPoints = 256; // up to this many correspondences k_lm sums i
 #endif
 constexpr int kLMThreads = PL_LM_THREADS; // k_lm: wavefront 0 adds the term rows in order, the others produce them (kernels.hip)
 
-PL_HD constexpr int sample_size(int est) { return est == EST_ABS ? 3 : (est == EST_REL || est == EST_RELT) ? 5 : est == EST_FUND ? 7 : 4; }
-PL_HD constexpr int max_models(int est) { return est == EST_ABS ? 4 : (est == EST_REL || est == EST_RELT) ? 40 : est == EST_FUND ? 3 : 1; }
-PL_HD constexpr int point_doubles(int est) { return est == EST_ABS ? 5 : est == EST_RELT ? 18 : 4; }
+PL_HD constexpr int sample_size(int est) { return est == EST_ABS ? 3 : (est == EST_REL || est == EST_RELT || est == EST_RAD1D) ? 5 : est == EST_FUND ? 7 : 4; }
+PL_HD constexpr int max_models(int est) { return (est == EST_ABS || est == EST_RAD1D) ? 4 : (est == EST_REL || est == EST_RELT) ? 40 : est == EST_FUND ? 3 : 1; }
+PL_HD constexpr int point_doubles(int est) { return (est == EST_ABS || est == EST_RAD1D) ? 5 : est == EST_RELT ? 18 : 4; }
 
 struct BatchCtl;
 struct GenerateArgs {
@@ -207,6 +208,7 @@ hipError_t launch_lm2(int est, const PointSet &pts, LMTask *tasks, uint32_t num_
 uint32_t score_chunks(int est, uint32_t n_points, bool prefilter, bool mfma = false);
 hipError_t launch_score(int est, const ScoreArgs &a, uint32_t slices, hipStream_t stream);
 int tangent_score_chunk(); // correspondences per chunk of k_score_tangent (EST_RELT)
+int radial1d_score_chunk(); // correspondences per chunk of k_score_radial1d (EST_RAD1D)
 // num_models[iters] -> slots (compact list of record indices in (iteration, model) order) + count
 hipError_t launch_lm(int est, const PointSet &pts, LMTask *tasks, uint32_t num_tasks, hipStream_t stream);
 // host_mask (pinned, device-mapped; may be null): the kernel writes a second copy there itself - no copy dispatch

@@ -704,4 +704,38 @@ PL_HD bool pf16_hom_outlier(const Hom16Model &m, const Hom16Point &p, const int 
     return (bits >> 31) != 0u;
 }
 
+// ---- 1D-radial absolute pose (k_score_radial1d; pl_score.h radial1d_inlier), model (R, t), correspondence (x, X) ----
+// With Z = (r_1 X + t_x, r_2 X + t_y) and the unit vector z = Z / |Z|, r^2 = |x - (z . x) z|^2 is the squared 2-D cross product
+// (x_x z_y - x_y z_x)^2, so an inlier satisfies |x_x Z_y - x_y Z_x| < thr |Z| and x . Z > 0.  The filter evaluates Z, the cross
+// product c, the dot product d and |Z| in fp32 and excludes a pair only if  |c~| > thr' |Z~| + S  or  d~ < -S.  Bounds (u = 2^-24,
+// s = max |R_ij| and tm = max |t_i| of the record's shadow, both padded; nX = |X|_2, ax = |x_x| + |x_y|, G = s nX + tm):
+//   |Z~_i - Z_i| <= 8u (s (|X| + |Y| + |Z|) + tm) <= 16u G   (four fp32 operand roundings and three FMAs; sqrt(3) < 2)
+//   |Z_i| <= 2 G
+//   |c~ - c|, |d~ - d| <= ax 16u G + u ax 2 G + 2u ax 2 G (1 + ...) <= 24u ax G
+//   | |Z~| - |Z| | <= sqrt(2) 16u G + 3u |Z~|   (sum of two squares, square root)
+// so S = u G (40 ax + 32 thr) and thr' = thr (1 + 8u) cover them with room for the second-order terms, for the rounding of the
+// exact fp64 expression itself (2^-50 ax G at most) and for a square root two units off.  Any NaN makes both comparisons false: the
+// pair goes to the exact pass.  A model outside the fp32 range (shadow scale +inf) is not filtered at all.
+// f: x, y, X, Y, Z in fp32; w[0] = nX w[1], w[1] = u (40 ax + 32 thr): S = s w[0] + tm w[1]
+PL_HD void pf_radial1d_point(const double *pt /* 5 */, float thr_up, float *f, float *w) {
+    PL_UNROLL
+    for (int i = 0; i < 5; ++i)
+        f[i] = (float)pt[i];
+    const float ax = pf_up((float)(fabs(pt[0]) + fabs(pt[1])));
+    const float nX = pf_up((float)sqrt(pt[2] * pt[2] + pt[3] * pt[3] + pt[4] * pt[4]));
+    w[1] = pf_up(kPfU * pf_up(pf_up(40.f * ax) + pf_up(32.f * thr_up)));
+    w[0] = pf_up(nX * w[1]);
+}
+PL_HD float pf_radial1d_thr(float thr_up) { return pf_up(thr_up * (1.f + 8.f * kPfU)); }
+// r: the record's shadow (pl_math.h); thrp: pf_radial1d_thr.  true = certainly not an inlier
+PL_HD bool pf_radial1d_outlier(const float *r, float thrp, const float *f, const float *w) {
+    const float z0 = fmaf(r[0], f[2], fmaf(r[1], f[3], fmaf(r[2], f[4], r[9])));
+    const float z1 = fmaf(r[3], f[2], fmaf(r[4], f[3], fmaf(r[5], f[4], r[10])));
+    const float c = fmaf(f[0], z1, -(f[1] * z0));
+    const float d = fmaf(f[0], z0, f[1] * z1);
+    const float nz = sqrtf(fmaf(z0, z0, z1 * z1));
+    const float S = pf_up(fmaf(r[14], w[0], r[12] * w[1]));
+    return (fabsf(c) > fmaf(thrp, nz, S)) | (d < -S);
+}
+
 } // namespace pl

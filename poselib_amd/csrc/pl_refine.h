@@ -1038,6 +1038,70 @@ template <> struct Refiner<EST_RELT> {
     }
 };
 
+// ---- absolute pose of a 1D-radial camera (optim/absolute.h:342-409, Radial1DAbsolutePoseRefiner; camera parameters {0, 0}) ----
+// Five parameters: rotation (pre-multiplied step, quat_step_pre) and t_x, t_y; t_z is never touched.  The projection is the unit
+// vector of the first two coordinates (camera_models.cc:2288-2313), the residual alpha xp - x with alpha = xp . x; terms with
+// alpha < 0 are skipped (the scorer's test is alpha > 0: both as in the reference).  The residual takes Z = q X q* + t
+// (CameraPose::apply), the Jacobian Z = R(q) X + t, as the reference does.  Same call shape as Refiner<EST_ABS> (`cam` is not read).
+template <> struct Refiner<EST_RAD1D> {
+    static constexpr int K = 5;
+    PL_HD static void prepare(const double *p, RefineCtx &c) { Refiner<EST_ABS>::prepare(p, c); }
+    PL_HD static bool residual(const double *p, const RefineCtx &, const CameraParams &, double x, double y, double X, double Y,
+                               double Z, double &r0, double &r1) {
+        Quat q;
+        q.w = p[0], q.x = p[1], q.y = p[2], q.z = p[3];
+        const Vec3 Zc = quat_rotate(q, v3(X, Y, Z)) + v3(p[4], p[5], p[6]);
+        const double n = sqrt(0.0 + Zc.x * Zc.x + Zc.y * Zc.y);
+        const double nrm = n < 1e-8 ? 1e-8 : n;
+        const double v0 = Zc.x / nrm, v1 = Zc.y / nrm;
+        const double alpha = 0.0 + v0 * x + v1 * y;
+        if (alpha < 0)
+            return false;
+        r0 = alpha * v0 - x;
+        r1 = alpha * v1 - y;
+        return true;
+    }
+    PL_HD static bool jacobian(const double *p, const RefineCtx &c, const CameraParams &, double x, double y, double X, double Y,
+                               double Z, double &r0, double &r1, double *J /*2x5*/) {
+        const double *R = c.M;
+        const double RX0 = R[0] * X + R[1] * Y + R[2] * Z, RX1 = R[3] * X + R[4] * Y + R[5] * Z, RX2 = R[6] * X + R[7] * Y + R[8] * Z;
+        const double Z0 = RX0 + p[4], Z1 = RX1 + p[5];
+        const double n = sqrt(0.0 + Z0 * Z0 + Z1 * Z1);
+        const double nrm = n < 1e-8 ? 1e-8 : n;
+        const double v0 = Z0 / nrm, v1 = Z1 / nrm;
+        // (I - v v^T) / |z|
+        const double P00 = (1.0 - v0 * v0) / nrm, P01 = (0.0 - v0 * v1) / nrm, P10 = (0.0 - v1 * v0) / nrm, P11 = (1.0 - v1 * v1) / nrm;
+        const double alpha = 0.0 + v0 * x + v1 * y;
+        if (alpha < 0)
+            return false;
+        r0 = alpha * v0 - x;
+        r1 = alpha * v1 - y;
+        // d r / d z = (xp x^T + alpha I) (I - v v^T) / |z|, then d z / d (rotation, t_x, t_y)   (absolute.h:382-386)
+        const double B00 = v0 * x + alpha * 1.0, B01 = v0 * y + alpha * 0.0, B10 = v1 * x + alpha * 0.0, B11 = v1 * y + alpha * 1.0;
+        const double D[4] = {B00 * P00 + B01 * P10, B00 * P01 + B01 * P11, B10 * P00 + B11 * P10, B10 * P01 + B11 * P11};
+        PL_UNROLL
+        for (int a = 0; a < 2; ++a) {
+            const double d0 = D[2 * a], d1 = D[2 * a + 1];
+            J[5 * a + 0] = d0 * 0.0 + d1 * -RX2;
+            J[5 * a + 1] = d0 * RX2 + d1 * 0.0;
+            J[5 * a + 2] = d0 * -RX1 + d1 * RX0;
+            J[5 * a + 3] = d0 * 1.0 + d1 * 0.0;
+            J[5 * a + 4] = d0 * 0.0 + d1 * 1.0;
+        }
+        return true;
+    }
+    PL_HD static void step(const double *__restrict__ p, const RefineCtx &, const double *__restrict__ dp, double *__restrict__ out) {
+        Quat q;
+        q.w = p[0], q.x = p[1], q.y = p[2], q.z = p[3];
+        const Quat qn = quat_step_pre(q, v3(dp[0], dp[1], dp[2]));
+        PL_UNROLL
+        for (int i = 0; i < kParamDoubles; ++i)
+            out[i] = p[i];
+        out[0] = qn.w, out[1] = qn.x, out[2] = qn.y, out[3] = qn.z;
+        out[4] = p[4] + dp[3], out[5] = p[5] + dp[4];
+    }
+};
+
 // ---- homography ----
 template <> struct Refiner<EST_HOM> {
     static constexpr int K = 8;
@@ -1203,10 +1267,10 @@ template <> struct Refiner<EST_FUND> {
 // Record (what the scorers consume) of a refined parameter block: pose (q, t) for the absolute / relative problems,
 // H row-major, or the Bartoli-Sturm factorisation of F (optim_utils.h:73-77).  est: pl_score.h Estimator.
 PL_HD void record_from_lm_params(int est, const double *params, double *rec) {
-    if (est == 0 || est == 1 || est == 4) {
+    if (est == 0 || est == 1 || est == 4 || est == 5) {
         Quat q;
         q.w = params[0], q.x = params[1], q.y = params[2], q.z = params[3];
-        store_pose_model_q(rec, q, v3(params[4], params[5], params[6]), est != 0);
+        store_pose_model_q(rec, q, v3(params[4], params[5], params[6]), est == 1 || est == 4);
     } else if (est == 3) {
         Mat3 H;
         for (int i = 0; i < 9; ++i)

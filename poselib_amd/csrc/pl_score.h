@@ -12,7 +12,8 @@
 namespace pl {
 
 // EST_RELT: relative pose scored by the tangent-Sampson error on bearings (the model record is EST_REL's)
-enum Estimator : int { EST_ABS = 0, EST_REL = 1, EST_FUND = 2, EST_HOM = 3, EST_RELT = 4 };
+// EST_RAD1D: absolute pose of a 1D-radial camera (centred pixels, no intrinsics); the model record is EST_ABS's, t_z stays 0
+enum Estimator : int { EST_ABS = 0, EST_REL = 1, EST_FUND = 2, EST_HOM = 3, EST_RELT = 4, EST_RAD1D = 5 };
 
 // ---- absolute pose: correspondence = (x, y, X, Y, Z) ---------------------------------------
 // Returns the inlier decision; r2 is valid when the point is in front of the camera.
@@ -118,6 +119,23 @@ PL_HD bool tangent_pose_inlier(const double *M, const double *pt, double thr2, d
     Quat q;
     q.w = M[0], q.x = M[1], q.y = M[2], q.z = M[3];
     return check_cheirality(q, v3(M[4], M[5], M[6]), v3(pt[0], pt[1], pt[2]), v3(pt[3], pt[4], pt[5]), 0.01);
+}
+
+// ---- 1D-radial absolute pose (utils.cc:354-371, 571-582): correspondence = (x, y, X, Y, Z), x, y centred pixels ---------------
+// z = unit vector of the first two rows of R X + t; alpha = z . x; r^2 = |x - alpha z|^2: the pixel's distance from the radial line
+// through the projection.  Inlier iff r^2 < thr^2 and alpha > 0 (the pixel lies on the projection's side of the centre).
+// get_inliers_1D_radial forms the same expression, so the mask is this decision too.
+PL_HD bool radial1d_inlier(const double *M, double x, double y, double X, double Y, double Z, double thr2, double &r2) {
+    const double *R = M + kMatOff;
+    const double z0 = R[0] * X + R[1] * Y + R[2] * Z + M[4];
+    const double z1 = R[3] * X + R[4] * Y + R[5] * Z + M[5];
+    const double nrm = sqrt(0.0 + z0 * z0 + z1 * z1);
+    const double u0 = z0 / nrm, u1 = z1 / nrm;
+    const double alpha = 0.0 + u0 * x + u1 * y;
+    const double e0 = x - alpha * u0;
+    const double e1 = y - alpha * u1;
+    r2 = 0.0 + e0 * e0 + e1 * e1;
+    return (r2 < thr2) & (alpha > 0.0);
 }
 
 // ---- final inlier masks (different arithmetic form for absolute pose: utils.cc:374-384) -----

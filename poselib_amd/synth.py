@@ -105,6 +105,17 @@ def absolute_pose_scene(n: int, outlier_ratio: float, seed: int, noise_px: float
             "inlier_gt": ~is_out}
 
 
+def radial_1d_scene(n: int, outlier_ratio: float, seed: int, noise_px: float = 0.5, focal: float = 1000.0, fov_deg: float = 70.0):
+    """2D-3D correspondences of a camera with an unknown radial distortion, for estimate_1D_radial_absolute_pose: the pixels of
+    absolute_pose_scene relative to the principal point, each multiplied by 1 - 0.2 r^2 + 0.05 r^4 with r = |x| / 1000.  The pose
+    is known up to its forward translation: ground truth is q_gt, t_gt[:2] and inlier_gt."""
+    d = absolute_pose_scene(n, outlier_ratio, seed, noise_px=noise_px, focal=focal, fov_deg=fov_deg)
+    x = d["p2d"] - np.asarray(d["camera"]["params"][1:3])
+    r = np.linalg.norm(x, axis=1) / 1000.0
+    x = x * (1.0 - 0.2 * r ** 2 + 0.05 * r ** 4)[:, None]
+    return {"p2d": np.ascontiguousarray(x), "p3d": d["p3d"], "q_gt": d["q_gt"], "t_gt": d["t_gt"], "inlier_gt": d["inlier_gt"]}
+
+
 def _two_view_points(rs: Stream, n: int, R, t, s: float, planar: bool):
     """Normalised image points in both views of n scene points in front of both cameras."""
     x1 = np.zeros((0, 2))

@@ -1,0 +1,284 @@
+#!/usr/bin/env python
+"""Generates tests/golden/golden_radial1d_v1.json - frozen outputs of the reference for 1D-radial absolute pose: the minimal solver
+p5lp_radial, score and inlier mask of given poses (compute_msac_score_1D_radial / get_inliers_1D_radial), the refiner
+(bundle_adjust_1D_radial) and estimate_1D_radial_absolute_pose.
+
+PROVENANCE: produced by the REFERENCE'S OWN SOURCES through tests/ref_radial1d/ref_radial1d.cc, a stand-alone program of our own that
+tests/ref_radial1d_lib.py builds into a temporary directory from the reference's solvers/p5lp_radial.cc (compiled in place) and
+oracle/_ref, the reference compiled in place against oracle/eigen_shim.  Inputs are regenerated from poselib_amd.synth seeds and
+numpy's RandomState; large outputs are stored as SHA-256 digests of their bytes, small ones as repr() of every double.
+
+Conditions main() asserts, so that the fixture never encodes a failure: every estimator case with n >= 100 recovers the ground
+truth - rotation within 0.1 degree of q_gt up to the quaternion's sign, t[:2] within 1e-2, t[2] == 0, at least 99 % of the true
+inliers in the mask - else the next data seed is tried, at most 5; the solver samples include ones with 0, 2 and 4 models, planar
+ones and ones with a repeated point.  (A sample whose output is not finite is recorded as "non-finite" and a count, not as bits; none
+of the degenerate samples tried - repeated, identical, collinear, zero points - makes the reference emit one: they give no model.)
+Re-run (needs the reference build):
+    python tests/golden/make_golden_radial1d.py
+"""
+import hashlib
+import json
+import os
+import sys
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(HERE))
+sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+
+from poselib_amd import synth  # noqa: E402
+
+PATH = os.path.join(HERE, "golden_radial1d_v1.json")
+MAX_ERROR = 2.0  # pixels
+
+
+def reprs(v):
+    return [repr(float(x)) for x in np.asarray(v, dtype=np.float64).ravel()]
+
+
+def digest(arrs):
+    h = hashlib.sha256()
+    for a in arrs:
+        h.update(np.ascontiguousarray(a, dtype=np.float64).tobytes())
+    return h.hexdigest()
+
+
+def mask_hex(mask):
+    return np.packbits(np.asarray(mask).astype(np.uint8)).tobytes().hex()
+
+
+def quat_to_rotmat(q):
+    w, x, y, z = q
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                     [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+
+
+def front_scale(x):
+    """robust.cc:897-902: n / sum |x_k|, summed in index order"""
+    s = 0.0
+    for k in range(x.shape[0]):
+        s += float(np.sqrt(0.0 + x[k, 0] * x[k, 0] + x[k, 1] * x[k, 1]))
+    return x.shape[0] / s
+
+
+# ------------------------------------------------------------------------------------------ minimal solver
+SOLVER_SAMPLES = 240
+
+
+def solver_samples():
+    """(S, 5, 2) 2-D points and (S, 5, 3) 3-D points: consistent samples of a random pose with unit 2-D vectors (what the estimator
+    hands in), disturbed ones (fewer real roots), un-normalised 2-D points, planar scenes (X_z = 0: the NaN second root), a repeated
+    point, five identical points and a zero 2-D point"""
+    rs = np.random.RandomState(7100)
+    S = SOLVER_SAMPLES
+    xs, Xs, tags = np.zeros((S, 5, 2)), np.zeros((S, 5, 3)), []
+    for s in range(S):
+        q = rs.randn(4)
+        q /= np.linalg.norm(q)
+        R, t = quat_to_rotmat(q), rs.randn(3)
+        X = rs.randn(5, 3) * 2
+        tag = "consistent"
+        if s % 7 == 2:
+            X[:, 2] = 0.0
+            tag = "planar"
+        Z = X @ R.T + t
+        x = Z[:, :2] * rs.uniform(0.5, 2.0, (5, 1))
+        x /= np.linalg.norm(x, axis=1, keepdims=True)
+        if s % 3 == 1:
+            x = x + 0.3 * rs.randn(5, 2)
+            tag = "disturbed"
+        if s % 5 == 4:
+            x = x * rs.uniform(10.0, 500.0, (5, 1))
+            tag += "+scaled"
+        if s % 11 == 3:
+            x[1], X[1] = x[0], X[0]
+            tag = "repeated"
+        if s % 60 == 17:
+            x[:], X[:] = x[0], X[0]
+            tag = "identical"
+        if s % 60 == 47:
+            x[2] = 0.0
+            X[:] = 0.0
+            tag = "zero"
+        xs[s], Xs[s] = x, X
+        tags.append(tag)
+    return xs, Xs, tags
+
+
+def sample_digest(poses, count):
+    return digest([poses[:count]])[:16]
+
+
+# ------------------------------------------------------------------------------------------ generator
+GENERATE_SAMPLES = 200
+
+
+def generate_inputs():
+    """a scaled scene of 300 correspondences at 40 % outliers (pixels are NOT unit vectors: the generator normalises them) and 200
+    samples of 5 distinct indices: 100 drawn from the true inliers, 100 from all correspondences"""
+    d, x, scale = scaled_scene(300, 0.4, 7150)
+    rs = np.random.RandomState(7151)
+    inl = np.flatnonzero(d["inlier_gt"])
+    idx = np.array([rs.choice(inl, 5, replace=False) if s < GENERATE_SAMPLES // 2 else rs.choice(x.shape[0], 5, replace=False)
+                    for s in range(GENERATE_SAMPLES)])
+    return d, x, idx
+
+
+# ------------------------------------------------------------------------------------------ scenes
+SCORE_N = [5, 64, 257, 1000]
+REFINE_N = [6, 64, 255, 256, 257, 1000]
+REFINE_RUNS = {"truncated": ("TRUNCATED", 25), "cauchy": ("CAUCHY", 100)}
+
+
+def gt_pose(d):
+    return np.r_[d["q_gt"], d["t_gt"][:2], 0.0]
+
+
+def scaled_scene(n, outliers, seed):
+    """(scene, scaled pixels, scale): the correspondences as the front-end's RANSAC stage sees them"""
+    d = synth.radial_1d_scene(n, outliers, seed)
+    scale = front_scale(d["p2d"])
+    return d, d["p2d"] * scale, scale
+
+
+def score_scene(n):
+    return scaled_scene(n, 0.0 if n <= 5 else 0.3, 7200 + n)
+
+
+def score_poses(d, n):
+    """ground truth, near, far, the ground truth turned by 180 degrees about the optical axis (alpha < 0 for most points), one NaN entry"""
+    rs = np.random.RandomState(7250 + n)
+    gt = gt_pose(d)
+    near = gt.copy()
+    near[:4] += 2e-4 * rs.randn(4)
+    near[:4] /= np.linalg.norm(near[:4])
+    near[4:6] += 1e-3 * rs.randn(2)
+    far = np.r_[rs.randn(4), rs.randn(2), 0.0]
+    far[:4] /= np.linalg.norm(far[:4])
+    w, x, y, z = gt[:4]
+    turned = np.r_[-z, -y, x, w, -gt[4], -gt[5], 0.0]  # (0, 0, 0, 1) * q
+    nan = gt.copy()
+    nan[4] = np.nan
+    return {"gt": gt, "near": near, "far": far, "turned": turned, "nan": nan}
+
+
+def refine_inputs(n):
+    d, xs, scale = scaled_scene(n, 0.0 if n <= 6 else 0.2, 7300 + n)
+    rs = np.random.RandomState(7350 + n)
+    q = d["q_gt"] + 0.003 * rs.randn(4)
+    p0 = np.r_[q / np.linalg.norm(q), d["t_gt"][:2] + 0.003 * rs.randn(2), 0.0]
+    return d, xs, scale, p0
+
+
+# ------------------------------------------------------------------------------------------ estimator
+# name, n, outlier ratio, first data seed, options beyond max_error / ransac.seed, warm start
+EST_CASES = [
+    ("n400_o30", 400, 0.3, 477, {}, False),
+    ("n400_o60", 400, 0.6, 477, {}, False),
+    ("n2000_o50", 2000, 0.5, 2077, {}, False),
+    ("n4", 4, 0.0, 7404, {}, False),
+    ("n5", 5, 0.0, 7405, {}, False),
+    ("n6", 6, 0.0, 7406, {}, False),
+    ("n7", 7, 0.0, 7407, {}, False),
+    ("n12", 12, 0.0, 7412, {}, False),
+    ("prosac", 400, 0.3, 7420, {"progressive_sampling": True}, False),
+    ("warm", 400, 0.3, 7430, {}, True),
+]
+
+
+def est_inputs(case, data_seed):
+    name, n, outl, _, ransac_extra, warm = case
+    d = synth.radial_1d_scene(n, outl, data_seed)
+    opt = {"max_error": MAX_ERROR, "ransac": dict({"seed": 1}, **ransac_extra)}
+    initial = None
+    if warm:
+        rs = np.random.RandomState(7440)
+        q = d["q_gt"] + 0.01 * rs.randn(4)
+        initial = np.r_[q / np.linalg.norm(q), d["t_gt"][:2] + 0.01 * rs.randn(2), 0.0]
+        opt["ransac"]["score_initial_model"] = True
+    return d, opt, initial
+
+
+def recovers(d, pose, mask):
+    q, t = pose[:4], pose[4:]
+    c = min(1.0, abs(float(np.dot(q / np.linalg.norm(q), d["q_gt"]))))
+    angle = np.degrees(2.0 * np.arccos(c))
+    gt_in = d["inlier_gt"]
+    return bool(angle < 0.1 and np.abs(t[:2] - d["t_gt"][:2]).max() < 1e-2 and t[2] == 0 and
+                (mask & gt_in).sum() >= 0.99 * gt_in.sum())
+
+
+def main():
+    import ref_radial1d_lib as RR
+
+    G = {"version": 1, "max_error": MAX_ERROR}
+
+    xs, Xs, tags = solver_samples()
+    ret, cnt, poses = RR.p5lp_radial(xs, Xs)
+    finite = np.isfinite(poses).all(axis=(1, 2))
+    G["solver"] = {"input_sha256": digest([xs, Xs]), "tags": tags, "counts": [int(c) for c in cnt],
+                   "returns": [int(r) for r in ret],
+                   "poses": [sample_digest(poses[s], cnt[s]) if finite[s] else "non-finite" for s in range(len(cnt))],
+                   "first": {str(s): reprs(poses[s, :cnt[s]]) for s in range(12)}}
+    hist = np.bincount(cnt, minlength=5)
+    print("solver: counts histogram", hist.tolist(), "non-finite", int((~finite).sum()), "planar", tags.count("planar"))
+    assert hist[0] > 0 and hist[2] > 0 and hist[4] > 0 and tags.count("planar") > 0
+    assert any(tags[s] == "repeated" for s in range(len(tags)))
+
+    d, x, idx = generate_inputs()
+    gcnt, gposes = RR.generate_models(x, d["p3d"], idx)
+    assert np.isfinite(gposes).all()
+    G["generate"] = {"input_sha256": digest([x, d["p3d"], idx]), "counts": [int(c) for c in gcnt],
+                     "poses": [sample_digest(gposes[s], gcnt[s]) for s in range(len(gcnt))],
+                     "first": {str(s): reprs(gposes[s, :gcnt[s]]) for s in range(6)}}
+    print("generate: counts histogram", np.bincount(gcnt, minlength=5).tolist())
+    assert {2, 4} <= set(int(c) for c in gcnt)
+
+    G["scores"] = {}
+    for n in SCORE_N:
+        d, x, scale = score_scene(n)
+        rec = {"pixels_sha256": digest([x, d["p3d"]]), "scale": repr(scale), "max_error": repr(MAX_ERROR * scale), "poses": {}}
+        for name, pose in score_poses(d, n).items():
+            s, c, m = RR.score(pose, x, d["p3d"], MAX_ERROR * scale)
+            rec["poses"][name] = {"pose": reprs(pose), "score": repr(s), "count": c, "mask_hex": mask_hex(m)}
+            print("score", n, name, c, s)
+        assert rec["poses"]["gt"]["count"] >= 0.6 * n and rec["poses"]["nan"]["count"] == 0
+        assert rec["poses"]["turned"]["count"] <= 0.1 * n
+        G["scores"][str(n)] = rec
+
+    G["refine"] = {}
+    for n in REFINE_N:
+        d, x, scale, p0 = refine_inputs(n)
+        for run, (loss, iters) in REFINE_RUNS.items():
+            pose, it, c0, c1 = RR.refine(p0, x, d["p3d"], loss, MAX_ERROR * scale, iters)
+            G["refine"][f"{n}/{run}"] = {"input_sha256": digest([x, d["p3d"], p0]), "pose": reprs(pose), "iterations": it,
+                                         "initial_cost": repr(c0), "cost": repr(c1)}
+            print("refine", n, run, it, c0, c1)
+            assert it > 0 and c1 <= c0 and pose[6] == 0.0
+
+    G["estimates"] = {}
+    for case in EST_CASES:
+        name, n = case[0], case[1]
+        for attempt in range(5):
+            data_seed = case[3] + 100 * attempt
+            d, opt, initial = est_inputs(case, data_seed)
+            pose, mask, st = RR.estimate_1D_radial_absolute_pose(d["p2d"], d["p3d"], opt, initial)
+            ok = n < 100 or recovers(d, pose, mask)
+            print("estimate", name, "seed", data_seed, st, "recovers" if ok else "FAILS")
+            if ok:
+                break
+        assert ok, name
+        G["estimates"][name] = {"n": n, "data_seed": data_seed, "input_sha256": digest([d["p2d"], d["p3d"]]), "options": opt,
+                                "initial": None if initial is None else reprs(initial), "model": reprs(pose),
+                                "iterations": st["iterations"], "refinements": st["refinements"], "num_inliers": st["num_inliers"],
+                                "inlier_ratio": repr(st["inlier_ratio"]), "model_score": repr(st["model_score"]), "mask_hex": mask_hex(mask),
+                                "true_inliers_found": int((mask & d["inlier_gt"]).sum()), "true_inliers": int(d["inlier_gt"].sum())}
+    with open(PATH, "w") as f:
+        json.dump(G, f, indent=1)
+    print("wrote", PATH, os.path.getsize(PATH), "bytes")
+
+
+if __name__ == "__main__":
+    main()
