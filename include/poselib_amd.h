@@ -332,6 +332,15 @@ int pl_debug_inlier_mask(pl_problem *p, const void *model, double max_error, uin
 int pl_debug_tangent_chunk(void);
 /* ... and of the 1D-radial streaming scorer */
 int pl_debug_radial1d_chunk(void);
+/* Diagnostic: the hypothesis slices per chunk of correspondences that the scorer launch of a lock-step group (pl_ransac_batch,
+ * pl_estimate_batch) gives ONE member - a problem of `kind` (0, 1, 2, 3 or 5) with n_points correspondences and a batch of
+ * `iterations` iterations - when the chunks of correspondences of all active members of the launch, this one included, add up
+ * to launch_chunks (a smaller value counts as the member alone).  Whether a real member is scored on the matrix cores also
+ * depends on its coordinates and threshold; this entry assumes both in the pre-filters' range, so the kind, the size and
+ * POSELIB_AMD_NO_MFMA decide.  Absolute pose on the matrix cores (n_points >= 1024) takes
+ * fewer slices the more the launch holds; every other scorer does not depend on launch_chunks.  Host arithmetic only: no device
+ * is touched.  Returns the count (>= 1), or PL_ERR_INVALID. */
+int pl_debug_group_slices(int kind, uint32_t n_points, uint32_t iterations, uint32_t launch_chunks);
 /* Diagnostic: the generator kernel of a resident kind-5 problem on caller-supplied minimal samples (num_iters x 5 indices - the path
  * PROSAC's host-drawn samples take) with slots_per_iter (1 .. 4) record slots per iteration.  models: num_iters x slots_per_iter
  * records of 24 doubles (zero where none was written); num_models: num_iters; totals[3]: models counted, models with a NaN entry,

@@ -435,6 +435,13 @@ def device_math2(fn: int, x, y=None):
     return out
 
 
+def group_slices(kind: int, n_points: int, iterations: int, launch_chunks: int) -> int:
+    """Diagnostic (pl_debug_group_slices): hypothesis slices per chunk of correspondences that a group's scorer launch gives one
+    member of `n_points` correspondences with a batch of `iterations` iterations, when the chunks of all active members of the
+    launch add up to `launch_chunks`.  Host arithmetic only: works without a device."""
+    return L.check(L.lib().pl_debug_group_slices(int(kind), int(n_points), int(iterations), int(launch_chunks)))
+
+
 def ransac_batch(problems, opts, max_in_flight=4, group_size=16):
     """Many device-resident problems in one call (pl_ransac_batch): results of `problems[i].run(opts[i])`, bit for bit.
     Problems of the same kind advance in lock-step groups of `group_size` through one launch sequence."""

@@ -115,7 +115,7 @@ struct Context {
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // batch scratch
-    DevBuf positions, samples, shadow16, lm2_states, lm2_partials, raw_a, raw_b, pts_arena, absmax, models, num_models, slots, num_hyp, part_count, part_score, count, score;
+    DevBuf positions, samples, shadow16, lm2_states, lm2_partials, raw_a, raw_b, pts_arena, absmax, models, num_models, nan_bits, slots, num_hyp, part_count, part_score, count, score;
     DevBuf shadow, compact64;
     DevBuf live, rank, points16; // k_score_mfma: live hypothesis list, its inverse, operand rows of the correspondences
     DevBuf offsets, ctl, blk_best, rec_meta, rec_models, delta, flags;
@@ -939,6 +939,10 @@ struct RansacRun {
             ga.real_focal_check = o->real_focal_check;
             ga.blk_tot = blk_tot;
             ga.blk_nan = blk_tot + nblk;
+            if (on_mfma && kind == EST_ABS) { // the live list of k_compact2 is built from the generator's NaN flags per iteration
+                HIP_TRY(c->nan_bits.ensure(sizeof(uint32_t) * Bl));
+                ga.nan_bits = c->nan_bits.as<uint32_t>();
+            }
             if (const size_t sb = generate_stage_bytes(kind, Bl)) {
                 HIP_TRY(c->gen_stage.ensure(sb));
                 ga.stage = c->gen_stage.p;
@@ -961,6 +965,7 @@ struct RansacRun {
                 HIP_TRY(c->rank.ensure(sizeof(uint32_t) * hcap));
                 HIP_TRY(c->points16.ensure(kAbs16PointBytes * s16.point_rows));
                 s16.live = c->live.as<uint32_t>(), s16.rank = c->rank.as<uint32_t>(), s16.points16 = c->points16.p;
+                s16.nan_bits = ga.nan_bits;
             } else if (on_mfma && kind == EST_HOM) { // homography: operands of k_score_mfmah (k_hom16)
                 HIP_TRY(c->shadow16.ensure((hcap + kHom16Pad) * kHom16Bytes));
                 s16.out = c->shadow16.p;
@@ -2307,6 +2312,13 @@ int pl_problem_create_tangent(const double *x1, const double *x2, size_t n, cons
 }
 // Diagnostic: correspondences per chunk of the tangent-Sampson streaming scorer as built (tests probe the sizes around it)
 int pl_debug_tangent_chunk(void) { return tangent_score_chunk(); }
+// Diagnostic: hypothesis slices of one member of a grouped scorer launch (driver_group.inc: group_score_slices).  No device call.
+int pl_debug_group_slices(int kind, uint32_t n_points, uint32_t iterations, uint32_t launch_chunks) {
+    if (!(kind == EST_ABS || kind == EST_REL || kind == EST_FUND || kind == EST_HOM || kind == EST_RAD1D) || n_points == 0 ||
+        iterations == 0 || iterations > (1u << 30))
+        return fail(PL_ERR_INVALID, "pl_debug_group_slices: kind 0, 1, 2, 3 or 5, n_points > 0, 0 < iterations <= 2^30");
+    return debug_group_slices(kind, n_points, iterations, launch_chunks);
+}
 // Diagnostic: the inlier mask of one model on a resident problem, as the estimators' final get_inliers computes it (k_mask).
 int pl_debug_inlier_mask(pl_problem *p, const void *model, double max_error, uint8_t *mask) {
     if (!p || !model || (!mask && p->n))

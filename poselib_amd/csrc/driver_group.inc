@@ -30,7 +30,7 @@ constexpr uint32_t kGroupMaxAuto = 256;     // ... which grows with the size of 
 constexpr uint32_t kGroupMaxPoints = 16384; // larger problems gain nothing from grouping
 
 struct GroupLayout { // byte offsets inside one slot of the arena (the same for every slot of a step)
-    size_t positions, delta, flags, models, num_models, slots, offsets, ctl, shadow, compact64, shadow16, live, rank, points16, part_count,
+    size_t positions, delta, flags, models, num_models, nan_bits, slots, offsets, ctl, shadow, compact64, shadow16, live, rank, points16, part_count,
         part_score, count, score, blk_best, rec_meta, rec_models, gen_stage, pts, pts2, mask, tmp_model, absmax, samples, total;
 };
 
@@ -209,6 +209,7 @@ GroupLayout group_layout(int kind, uint32_t max_n, uint32_t max_B, uint32_t max_
     L.flags = take(sizeof(uint64_t) * ((size_t)max_M / 64 + 2));
     L.models = take(sizeof(double) * kModelStride * hcap);
     L.num_models = take(sizeof(uint32_t) * max_B);
+    L.nan_bits = take(kind == EST_ABS ? sizeof(uint32_t) * max_B : 0); // NaN flags per iteration (GenerateArgs.nan_bits)
     L.slots = take(sizeof(uint32_t) * hcap);
     L.offsets = take(sizeof(uint32_t) * max_B);
     L.ctl = take(sizeof(BatchCtl) + sizeof(uint32_t) * (2 * nblk + 2 + chunks));
@@ -299,6 +300,62 @@ void group_stage_in(GroupItem *const *pit, uint32_t count) {
     gc.staged_first = pit[0];
 }
 
+// Hypothesis slices per chunk of correspondences of one member of a grouped scorer launch (workgroups of the member = slices x
+// chunks).  Pure host arithmetic.  `hexp`: hypotheses the member's batch of `B` iterations is expected to hold, `chunks`: its
+// chunks of correspondences, `launch_chunks`: the chunks of ALL active members of the launch (the member's own included).
+//
+// A member alone in its launch (`solo`): every workgroup (8 wavefronts) pays the operand split of its chunk, so a wavefront should
+// see about three units of 64 hypotheses - 24 units per workgroup.  The list is shorter than its capacity: P3P fills 1.3 of 4 slots
+// per iteration (sized by capacity, a group of 228 default-option problems launched 21 888 workgroups of which two thirds of the
+// wavefronts found no unit: 2.0 ms per step).  k_score_mfma (absolute pose on the matrix cores) reads the operand rows of its
+// chunk from the problem's table instead of splitting them: 48 units per workgroup (profiles/live_hypotheses.md).
+//
+// k_score_mfma_g, many members: the launch as a whole should come to about kGroupScoreWorkgroups workgroups, however many
+// members share it - slices = ceil(kGroupScoreWorkgroups / launch_chunks), never more than `solo`, never less than one per
+// (member, chunk).  A full group of long runs (the flagship: 16 members x 16 chunks x 49 slices = 12 544 workgroups for 512
+// resident slots, a workgroup's LDS held until its slowest wavefront is done) gets fewer, longer-lived workgroups; a launch with
+// few members, or short lists, keeps exactly what it had.  No result depends on the count: every (chunk, hypothesis) partial
+// comes from one wavefront, whichever it is.  Where kGroupScoreWorkgroups comes from: profiles/group_slices.md.  The other scorers
+// (two-view, homography, fp32 queue, tangent, 1D-radial) still split per workgroup and keep `solo`.
+constexpr uint32_t kGroupScoreWorkgroups = 3328;
+static uint32_t group_score_slices(int kind, bool use_mfma, size_t hexp, uint32_t B, uint32_t chunks, uint32_t launch_chunks) {
+    const size_t units = (use_mfma && kind == EST_ABS) ? 48 : 24; // 64-hypothesis units per workgroup (8 wavefronts)
+    uint32_t solo = std::max<uint32_t>(1u, std::min<uint32_t>((uint32_t)((hexp / 64 + units - 1) / units), 1536u / chunks));
+    if (use_mfma && (kind == EST_REL || kind == EST_FUND)) // (every workgroup pays the fp16 split of its chunk: at least ~4 units of 64 hypotheses per wave)
+        solo = std::max<uint32_t>(1u, std::min<uint32_t>({solo, 512u / chunks, B / 2048u + 1u}));
+    if (!(use_mfma && kind == EST_ABS))
+        return solo;
+    launch_chunks = std::max(launch_chunks, chunks);
+    return std::max<uint32_t>(1u, std::min<uint32_t>((kGroupScoreWorkgroups + launch_chunks - 1) / launch_chunks, solo));
+}
+// The rule's inputs for one member, shared by run_group and pl_debug_group_slices:
+// record slots per iteration.  5-point: up to 40 poses are possible, the single-problem path starts with 8 and repeats a batch
+// with 40 when an iteration overflows (about one iteration in 2000 does: most default-option problems would leave the group);
+// 16 here, overflow = fallback.  The slot count only moves records around: same results.
+static uint32_t group_record_slots(int kind) { return (kind == EST_REL) ? 16u : (uint32_t)max_models(kind); }
+// chunks of correspondences: 64 P per chunk, or 32 PG = 64 Pm on the matrix-core Sampson form
+static uint32_t group_member_chunks(int kind, bool use_mfma, uint32_t n) {
+    const int P = (use_mfma && (kind == EST_REL || kind == EST_FUND)) ? group_mfma2_points_per_lane(kind) : group_points_per_lane(kind);
+    return std::max<uint32_t>(1u, (n + 64 * P - 1) / (64 * P));
+}
+// hypotheses a batch of B iterations is expected to hold (absolute pose: P3P fills 1.3 of its 4 slots; the others: capacity)
+static size_t group_expected_hypotheses(int kind, uint32_t B, size_t hcap) {
+    return (kind == EST_ABS) ? std::min<size_t>(hcap, (size_t)B + B / 2) : hcap;
+}
+// pl_debug_group_slices: the rule for one member of `n_points` correspondences and a batch of `iterations` iterations.  The one
+// input it cannot know is whether the member's scorer is the matrix-core one: run_group asks score_uses_mfma with the problem's
+// prefilter; here the prefilter of a problem with in-range coordinates and threshold is ASSUMED (ones in the fields
+// score_uses_mfma reads), so the size, the kind and POSELIB_AMD_NO_MFMA decide.
+static int debug_group_slices(int kind, uint32_t n_points, uint32_t iterations, uint32_t launch_chunks) {
+    PrefilterArgs pf{};
+    pf.enabled = 1;
+    pf.g16 = pf.t16 = pf.h16 = 1.0f, pf.thr = 1.0f;
+    const bool mfma = score_uses_mfma(kind, n_points, pf);
+    const size_t hcap = (size_t)iterations * group_record_slots(kind);
+    return (int)group_score_slices(kind, mfma, group_expected_hypotheses(kind, iterations, hcap), iterations,
+                                   group_member_chunks(kind, mfma, n_points), launch_chunks);
+}
+
 // One group: `count` items of the same kind.  Items the path cannot finish get fallback = true.
 // `max_steps` > 0: at most so many batch steps; problems that are still running then are DEFERRED (g.deferred: their RansacRun is
 // kept, stages D / E skip them) - pl_estimate_batch regroups the deferred problems of all groups and calls again with `resume`
@@ -346,10 +403,7 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
             raw_doubles += (size_t)db * g.n;
         }
     }
-    // record slots per iteration.  5-point: up to 40 poses are possible, the single-problem path starts with 8 and
-    // repeats a batch with 40 when an iteration overflows (about one iteration in 2000 does: most default-option problems
-    // would leave the group); 16 here, overflow = fallback.  The slot count only moves records around: same results.
-    const uint32_t maxm = (kind == EST_REL) ? 16u : (uint32_t)max_models(kind);
+    const uint32_t maxm = group_record_slots(kind); // record slots per iteration
     // draws per iteration (expected, without duplicates): sum_k N / (N - k), largest for the smallest problem of the group -
     // the same expression sizes every item's window below (M64), so no item of a full-size batch outgrows the slot
     uint32_t min_n = (*pit[0]).n;
@@ -719,6 +773,7 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
     }
 
     // ---- stage C: batch steps in lock-step ----
+    std::vector<size_t> hexp_of; // expected hypotheses of each member's batch of the step
     for (uint32_t step = 0;; ++step) {
         if (max_steps && step >= max_steps) { // the long runs of the group continue in a later, regrouped call
             for (uint32_t i = 0; i < count; ++i) {
@@ -737,6 +792,7 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
         dims.min_n = 0xffffffffu;
         uint32_t nactive = 0;
         std::vector<uint32_t> prosac_members;
+        hexp_of.assign(count, 0);
         for (uint32_t i = 0; i < count; ++i) {
             GroupItem &g = (*pit[i]);
             GroupArgs &a = ha[i];
@@ -772,8 +828,7 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
             ScoreArgs &sa = a.score;
             set_prefilter(sa, &g.prob, r.thr2);
             a.use_mfma = score_uses_mfma(kind, N, sa.pf) ? 1u : 0u;
-            const int Pi = (a.use_mfma && (kind == EST_REL || kind == EST_FUND)) ? Pm : P; // (matrix-core Sampson form: chunks of 32 PG = 64 Pm)
-            const uint32_t chunks_i = std::max<uint32_t>(1u, (N + 64 * Pi - 1) / (64 * Pi));
+            const uint32_t chunks_i = group_member_chunks(kind, a.use_mfma != 0, N);
             const size_t ctl_bytes = sizeof(BatchCtl) + sizeof(uint32_t) * (2 * (size_t)nblk + 2 + chunks_i);
             BatchCtl *d_ctl = reinterpret_cast<BatchCtl *>(slot(i, L.ctl));
             uint32_t *blk_tot = reinterpret_cast<uint32_t *>(d_ctl + 1);
@@ -802,6 +857,7 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
             ga.ctl = d_ctl;
             ga.models = reinterpret_cast<double *>(slot(i, L.models));
             ga.num_models = reinterpret_cast<uint32_t *>(slot(i, L.num_models));
+            ga.nan_bits = (a.use_mfma && kind == EST_ABS) ? reinterpret_cast<uint32_t *>(slot(i, L.nan_bits)) : nullptr; // (live list)
             ga.real_focal_check = g.fe.scaled.real_focal_check;
             ga.blk_tot = blk_tot;
             ga.blk_nan = blk_tot + nblk;
@@ -809,20 +865,9 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
             // scorer
             a.chunks = chunks_i;
             sa.tickets = blk_tot + 2 * (size_t)nblk + 2;
-            // hypothesis slices per chunk of correspondences: every workgroup (8 wavefronts) pays the operand split of its chunk, so a
-            // wavefront should see about three units of 64 hypotheses.  The list is shorter than its capacity: P3P fills 1.3 of 4
-            // slots per iteration (sized by capacity, a group of 228 default-option problems launched 21 888 workgroups of which
-            // two thirds of the wavefronts found no unit: 2.0 ms per step, r4b trace).
-            // Absolute pose on the matrix cores (k_score_mfma): its workgroups read the operand rows of their chunk from the
-            // problem's table instead of splitting them, and on the flagship workload (groups of 16 problems, 8 groups in flight)
-            // about six units per wavefront - half as many, longer-lived workgroups - measured 4.7 % faster than three; still
-            // fewer are faster again there, but leave a small group too few workgroups to fill the device
-            // (profiles/live_hypotheses.md).  The other scorers still split per workgroup and keep their value.
-            const size_t hexp = (kind == EST_ABS) ? std::min<size_t>(hcap, (size_t)B + B / 2) : hcap;
-            const size_t units = (a.use_mfma && kind == EST_ABS) ? 48 : 24; // 64-hypothesis units per workgroup (8 wavefronts)
-            a.slices = std::max<uint32_t>(1u, std::min<uint32_t>((uint32_t)((hexp / 64 + units - 1) / units), 1536u / a.chunks));
-            if (a.use_mfma && (kind == EST_REL || kind == EST_FUND)) // (every workgroup pays the fp16 split of its chunk: at least ~4 units of 64 hypotheses per wave)
-                a.slices = std::max<uint32_t>(1u, std::min<uint32_t>({a.slices, 512u / a.chunks, B / 2048u + 1u}));
+            // hypothesis slices per chunk of correspondences: chosen below, once the launch's active members are known
+            // (group_score_slices)
+            hexp_of[i] = group_expected_hypotheses(kind, B, hcap);
             sa.pts = g.prob.ps;
             sa.models = ga.models;
             sa.slots = reinterpret_cast<uint32_t *>(slot(i, L.slots));
@@ -861,6 +906,7 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
                 if (live_list) {
                     ca.s16.live = const_cast<uint32_t *>(sa.slots);
                     ca.s16.rank = reinterpret_cast<uint32_t *>(slot(i, L.rank));
+                    ca.s16.nan_bits = ga.nan_bits;
                     ca.s16.points16 = slot(i, L.points16);
                     ca.s16.point_rows = a.chunks * 64u * (uint32_t)P;
                 }
@@ -910,13 +956,25 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
             dims.max_B = std::max(dims.max_B, B);
             dims.max_hcap = std::max<uint32_t>(dims.max_hcap, (uint32_t)hcap);
             dims.max_chunks = std::max(dims.max_chunks, a.chunks);
-            dims.max_slices = std::max(dims.max_slices, a.slices);
             dims.any_mfma |= a.use_mfma;
             dims.any_queue |= a.use_mfma ? 0u : 1u;
             ++nactive;
         }
         if (nactive == 0)
             break;
+        {
+            uint32_t launch_chunks = 0; // of the members k_score_mfma_g serves (the others' workgroups are another kernel's)
+            for (uint32_t i = 0; i < count; ++i)
+                if (ha[i].active && ha[i].use_mfma)
+                    launch_chunks += ha[i].chunks;
+            for (uint32_t i = 0; i < count; ++i) {
+                GroupArgs &a = ha[i];
+                if (!a.active)
+                    continue;
+                a.slices = group_score_slices(kind, a.use_mfma != 0, hexp_of[i], a.gen.num_iters, a.chunks, launch_chunks);
+                dims.max_slices = std::max(dims.max_slices, a.slices);
+            }
+        }
         if (!prosac_members.empty()) {
             size_t words = 0;
             for (uint32_t i : prosac_members)

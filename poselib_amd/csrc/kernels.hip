@@ -136,11 +136,15 @@ __device__ __forceinline__ double lane_fetch(double v, int src) { return __shfl(
 __device__ __forceinline__ Vec3 lane_fetch(Vec3 v, int src) {
     return v3(lane_fetch(v.x, src), lane_fetch(v.y, src), lane_fetch(v.z, src));
 }
+// nan_bits: bit m = solution m of THIS lane's iteration carries the NaN flag.  The lane that writes a record is not the
+// iteration's owner: it sets the bit in the owner's LDS word.
 __device__ __forceinline__ int generate_abs_dense(const GenerateArgs &g, uint32_t it, bool live, const Vec3 *xb, const Vec3 *Xp,
-                                                  uint32_t &n_nan) {
+                                                  uint32_t &n_nan, uint32_t &nan_bits) {
     __shared__ uint8_t s_src[256];      // candidate -> owning lane | solution index << 6
     __shared__ double s_cand[3][256];   // its depths
+    __shared__ uint32_t s_nan[64];      // owning lane -> NaN flags of its solutions
     const int lane = threadIdx.x & 63;
+    s_nan[lane] = 0u;
     P3PFront f;
     double cand[4][3];
     int n = 0;
@@ -177,10 +181,14 @@ __device__ __forceinline__ int generate_abs_dense(const GenerateArgs &g, uint32_
             Vec3 t;
             p3p_back(o, s_cand[0][e], s_cand[1][e], s_cand[2][e], R, t);
             double *rec = g.models + ((size_t)(it0 + (uint32_t)owner) * g.slots_per_iter + (uint32_t)m) * kModelStride;
-            n_nan += store_pose_model(rec, R, t, false) ? 1u : 0u;
+            if (store_pose_model(rec, R, t, false)) {
+                ++n_nan;
+                atomicOr(&s_nan[owner], 1u << m);
+            }
         }
     }
     __syncthreads(); // (the list is rewritten by the next call - solver batches run several per workgroup)
+    nan_bits = s_nan[lane];
     return n;
 }
 
@@ -205,9 +213,15 @@ template <int EST> __device__ __forceinline__ uint32_t generate_one(const Genera
             xb[k] = bearing(g.pts.a[0][idx[k]], g.pts.a[1][idx[k]]);
             Xp[k] = v3(g.pts.a[2][idx[k]], g.pts.a[3][idx[k]], g.pts.a[4][idx[k]]);
         }
+        uint32_t bits = 0;
         n = p3p_emit(xb[0], xb[1], xb[2], Xp[0], Xp[1], Xp[2], [&](int m, const Mat3 &R, const Vec3 &t) {
-            n_nan += store_pose_model(rec + m * kModelStride, R, t, false) ? 1u : 0u;
+            if (store_pose_model(rec + m * kModelStride, R, t, false)) {
+                ++n_nan;
+                bits |= 1u << m;
+            }
         }); // (the generator kernels take generate_abs_wave instead: the second half on full wavefronts of candidates)
+        if (g.nan_bits)
+            g.nan_bits[it] = bits;
     } else if constexpr (EST == EST_RAD1D) {
         // absolute_pose.cc:353-361: the 2-D sample points as unit vectors, then p5lp_radial; one lane per sample, everything in registers
         double xs[5][2], Xs[5][3];
@@ -270,9 +284,13 @@ __device__ __forceinline__ uint32_t generate_abs_wave(const GenerateArgs &g, uin
             Xp[k] = v3(g.pts.a[2][idx[k]], g.pts.a[3][idx[k]], g.pts.a[4][idx[k]]);
         }
     }
-    const int n = generate_abs_dense(g, it, live, xb, Xp, n_nan);
-    if (live)
+    uint32_t bits;
+    const int n = generate_abs_dense(g, it, live, xb, Xp, n_nan, bits);
+    if (live) {
         g.num_models[it] = (uint32_t)n;
+        if (g.nan_bits)
+            g.nan_bits[it] = bits;
+    }
     return live ? (uint32_t)n : 0u;
 }
 template <int EST> __global__ __launch_bounds__(64) void k_generate(GenerateArgs g) {

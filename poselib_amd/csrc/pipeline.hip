@@ -428,7 +428,7 @@ __global__ __launch_bounds__(1024) void k_count_blocks(const uint32_t *num_model
 __device__ __forceinline__ void compact2_body(const uint32_t *num_models, uint32_t B, int maxm,
                                               const uint32_t *blk_tot, uint32_t *slots, uint32_t *offsets,
                                               BatchCtl *ctl, uint32_t nblocks, uint32_t *host_offsets,
-                                              const double *models, uint32_t *live, uint32_t *rank) {
+                                              const double *models, uint32_t *live, uint32_t *rank, const uint32_t *nan_bits) {
     __shared__ uint32_t wt[16], wo[16], wb[16], wn[16], wnb[16], wl[16], wlo[16];
     __shared__ uint32_t s_base, s_live_base;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -450,10 +450,14 @@ __device__ __forceinline__ void compact2_body(const uint32_t *num_models, uint32
     const uint32_t i = blockIdx.x * 1024 + threadIdx.x;
     const uint32_t nm = (i < B) ? num_models[i] : 0u;
     const uint32_t inc = wscan_add(nm, lane);
-    // bit m: model m of this iteration carries the NaN flag (maxm <= 40)
+    // bit m: model m of this iteration carries the NaN flag (maxm <= 40): the word the generator wrote for the iteration (one
+    // coalesced load; absolute pose, <= 4 models) or, without it, the flag words of the records - 768 B apart from thread to
+    // thread, a cache line per flag
     // (the first four flags - all an absolute-pose iteration has - as independent loads: one trip to memory, not nm)
     uint64_t nanbits = 0;
-    if (live) {
+    if (live && nan_bits) {
+        nanbits = (i < B) ? (uint64_t)nan_bits[i] : 0ull;
+    } else if (live) {
         const double *rec0 = models + (size_t)i * (uint32_t)maxm * kModelStride;
         bool f[4];
 #pragma unroll
@@ -519,8 +523,9 @@ __device__ __forceinline__ void compact2_body(const uint32_t *num_models, uint32
 
 __global__ __launch_bounds__(1024) void k_compact2(const uint32_t *num_models, uint32_t B, int maxm,
                                                    const uint32_t *blk_tot, uint32_t *slots, uint32_t *offsets,
-                                                   const double *models, uint32_t *live, uint32_t *rank, BatchCtl *ctl) {
-    compact2_body(num_models, B, maxm, blk_tot, slots, offsets, ctl, gridDim.x, nullptr, models, live, rank);
+                                                   const double *models, uint32_t *live, uint32_t *rank, const uint32_t *nan_bits,
+                                                   BatchCtl *ctl) {
+    compact2_body(num_models, B, maxm, blk_tot, slots, offsets, ctl, gridDim.x, nullptr, models, live, rank, nan_bits);
 }
 __global__ __launch_bounds__(1024) void k_compact2_g(const GroupArgs *ga) {
     const GroupArgs &g = ga[blockIdx.z];
@@ -528,7 +533,7 @@ __global__ __launch_bounds__(1024) void k_compact2_g(const GroupArgs *ga) {
     if (!g.active || blockIdx.x >= nb)
         return;
     compact2_body(g.comp.num_models, g.comp.B, g.comp.maxm, g.comp.blk_tot, g.comp.slots, g.comp.offsets, g.comp.ctl, nb,
-                  g.comp.host_offsets, g.comp.models, g.comp.s16.live, g.comp.s16.rank);
+                  g.comp.host_offsets, g.comp.models, g.comp.s16.live, g.comp.s16.rank, g.comp.s16.nan_bits);
 }
 
 // The same for a list the host wrote (pl_debug_score_stream: `H` records in list order `slots`, no generator counts): one
@@ -1171,7 +1176,8 @@ hipError_t launch_compact2(const uint32_t *num_models, uint32_t B, int maxm, uin
     if (!counted)
         k_count_blocks<<<dim3(nb), dim3(1024), 0, stream>>>(num_models, B, blk_tot);
     k_compact2<<<dim3(nb), dim3(1024), 0, stream>>>(num_models, B, maxm, blk_tot, slots, offsets, models,
-                                                    abs16 ? s16.live : nullptr, abs16 ? s16.rank : nullptr, ctl);
+                                                    abs16 ? s16.live : nullptr, abs16 ? s16.rank : nullptr,
+                                                    abs16 ? s16.nan_bits : nullptr, ctl);
     if (s16.out && s16.sampson == 2) {
         const uint32_t cap = (uint32_t)std::min<uint64_t>(((uint64_t)B * (uint64_t)maxm + 7u) & ~7ull, 0xffffff00ull);
         k_hom16<<<dim3(std::min<uint32_t>((cap + 255) / 256, 1024u)), dim3(256), 0, stream>>>(ctl, slots, models, cap, s16.thr,

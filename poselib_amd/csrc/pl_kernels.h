@@ -49,6 +49,9 @@ struct GenerateArgs {
     int32_t real_focal_check;  // fundamental only
     uint32_t *blk_tot = nullptr; // optional, zeroed: models per block of 1024 iterations, accumulated by the generator
     uint32_t *blk_nan = nullptr; // optional, zeroed: NaN models per block of 1024 iterations (statistics)
+    uint32_t *nan_bits = nullptr; // optional [num_iters], absolute pose only (<= 4 slots per iteration - the one kind that builds a
+                               // live list): bit m = model m of the iteration carries the NaN flag.  Every iteration writes its
+                               // entry, so the array needs no clearing; k_compact2 reads it instead of the records' flag words
     void *stage = nullptr;     // relative pose: workspace of generate_stage_bytes(); nullptr = single-kernel generator
 };
 
@@ -233,6 +236,8 @@ struct Shadow16Params {
     // live position; k_compact2 writes the list and its inverse:
     uint32_t *live = nullptr;   // [capacity] record index of the live hypotheses, ascending hypothesis index
     uint32_t *rank = nullptr;   // [capacity] hypothesis k -> live position or kNoRank
+    const uint32_t *nan_bits = nullptr; // optional [iterations]: the generator's NaN flags per iteration (GenerateArgs.nan_bits);
+                                // nullptr: k_compact2 reads the flag word of every record
     void *points16 = nullptr;   // [point_rows] operand rows of the correspondences, rebuilt by every launch that builds `out`
     uint32_t point_rows = 0;    // chunks x correspondences per chunk (rows past the last correspondence: invalid columns)
 };
