@@ -448,48 +448,304 @@ uint64_t sample_positions_k(int K, uint64_t seed, uint64_t pos, uint64_t N, uint
 // sampler is the uniform one again (sampling.cc:101-102).
 // (ProsacSampler: pl_sampler.h)
 
-// Parameters of the scoring kernels' conservative fp32 pre-filters (pl_prefilter.h).  Every value is rounded UP;
+// Parameters of the scoring kernels' conservative fp32 pre-filters (pl_prefilter.h) for a problem.  Every value is rounded UP;
 // POSELIB_AMD_NO_PREFILTER=1 disables the filters (exact evaluation of every point).
-void set_prefilter(ScoreArgs &sa, const pl_problem *p, double thr2) {
+PrefilterArgs problem_prefilter(const pl_problem *p, double thr2) {
     static const bool disabled = std::getenv("POSELIB_AMD_NO_PREFILTER") != nullptr;
-    sa.pf = make_prefilter_args(p->kind, thr2, p->ps.xy_absmax);
+    PrefilterArgs pf = make_prefilter_args(p->kind, thr2, p->ps.xy_absmax);
     if (disabled)
-        sa.pf.enabled = 0;
+        pf.enabled = 0;
+    return pf;
+}
+
+// k_score_seq in plain mode: the `n` (< kIotaEntries) model records at `models` in the reference's summation order, results to
+// count[] / score[] and to their pinned mirrors (written by the kernel itself)
+SeqScoreArgs plain_seq_args(const Context *c, const PointSet &pts, const double *models, uint32_t n, double thr2, uint32_t *count,
+                            double *score, uint32_t *host_count, double *host_score) {
+    SeqScoreArgs q;
+    q.pts = pts;
+    q.models = models;
+    q.cand = nullptr;
+    q.num = c->iota.as<uint32_t>() + n; // the count is read from the device-resident table: no upload
+    q.cap = n;
+    q.thr2 = thr2;
+    q.count = count, q.score = score;
+    q.host_count = host_count, q.host_score = host_score;
+    q.host_cand = nullptr;
+    q.host_cap = 0;
+    return q;
 }
 
 // Score `nrec` model records that already sit in device memory at `d_records`, in the reference's summation order
 // (k_score_seq).  Results land in c->count / c->score and in the pinned h_count / h_score buffers after the caller
 // synchronises.
-int enqueue_score_records(Context *c, const pl_problem *p, const double *d_records, uint32_t nrec, double thr2,
-                          bool time_it) {
-    (void)time_it;
+int enqueue_score_records(Context *c, const pl_problem *p, const double *d_records, uint32_t nrec, double thr2) {
     HIP_TRY(c->num_hyp.ensure(sizeof(uint32_t)));
     HIP_TRY(c->count.ensure(sizeof(uint32_t) * nrec));
     HIP_TRY(c->score.ensure(sizeof(double) * nrec));
     HIP_TRY(c->h_count.ensure(sizeof(uint32_t) * nrec));
     HIP_TRY(c->h_score.ensure(sizeof(double) * nrec));
-    const bool counted = nrec < kIotaEntries; // the count is read from the device-resident table: no upload
-    if (!counted)
+    SeqScoreArgs sa = plain_seq_args(c, p->ps, d_records, nrec, thr2, c->count.as<uint32_t>(), c->score.as<double>(),
+                                     c->h_count.dev<uint32_t>(), c->h_score.dev<double>());
+    if (nrec >= kIotaEntries) { // beyond the table: the count is uploaded
         HIP_TRY(hipMemcpyAsync(c->num_hyp.p, &nrec, sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    SeqScoreArgs sa;
-    sa.pts = p->ps;
-    sa.models = d_records;
-    sa.cand = nullptr;
-    sa.num = counted ? c->iota.as<uint32_t>() + nrec : c->num_hyp.as<uint32_t>();
-    sa.cap = nrec;
-    sa.thr2 = thr2;
-    sa.count = c->count.as<uint32_t>();
-    sa.score = c->score.as<double>();
-    sa.host_count = c->h_count.dev<uint32_t>(); // the kernel writes the pinned copies itself
-    sa.host_score = c->h_score.dev<double>();
-    sa.host_cand = nullptr;
-    sa.host_cap = 0;
+        sa.num = c->num_hyp.as<uint32_t>();
+    }
     HIP_TRY(launch_score_seq(p->kind, sa, c->stream));
     return PL_OK;
 }
 
 constexpr uint32_t kRecordCap = 1024;  // device record list capacity (overflow -> host scan fallback)
 constexpr uint32_t kRecordFirst = 64;  // records fetched together with the control block
+
+// ---- one batch step of ONE problem: positions -> generate -> compact/gather (+ fp16 operands) -> score -> finalize/records ->
+// candidates re-scored.  The single-problem path (RansacRun::enqueue_batch: buffers of the Context, k_x launches) and the groups
+// (run_group: slots of the arena, k_x_g launches over a table) size their buffers and build their kernel arguments HERE. ----
+struct BatchShape {
+    uint32_t B;          // iterations of the whole batch: the sampler walks all of them
+    uint32_t lo, Bl;     // this rank's share [lo, lo + Bl) of them: everything from the generator on
+    uint32_t M;          // the device sampler's window of draw positions (0: the positions come from the host)
+    uint32_t slots;      // record slots per iteration
+    uint32_t chunks;     // the scorer's chunks of correspondences
+    uint32_t point_rows; // matrix-core absolute pose: rows of the correspondences' operand table
+    bool use_mfma;       // scored on the matrix cores (score_uses_mfma)
+};
+struct BatchSizes { // bytes of every device buffer of the step
+    size_t positions, delta, flags, samples, models, num_models, nan_bits, slots, offsets, ctl, shadow, compact64, shadow16, live, rank,
+        points16, part_count, part_score, count, score, blk_best, rec_meta, rec_models, gen_stage;
+};
+struct BatchBuffers { // ... the buffers themselves, and where the kernels mirror their small results in pinned host memory
+    uint32_t *positions, *samples /* explicit minimal samples of the share */, *num_models, *nan_bits, *slots, *offsets, *live, *rank;
+    uint8_t *delta;
+    uint64_t *flags;
+    BatchCtl *ctl;
+    float *shadow;
+    double *models, *compact64, *part_score, *score, *rec_models;
+    uint32_t *part_count, *count;
+    RecordMeta *rec_meta;
+    char *shadow16, *points16, *blk_best, *gen_stage;
+    RecordMeta *host_meta; // the first kRecordFirst candidates ...
+    double *host_models;   // ... and their model records
+    BatchCtl *host_ctl;    // the control block as the last kernel of the step finds it
+};
+// Behind the control block, zeroed with it: models and NaN models per 1024 iterations (two tables of nblk + 1 entries, filled by
+// the generator), then the scorer's work counters (one per chunk of correspondences).
+uint32_t batch_blocks(uint32_t Bl) { return (Bl + 1023) / 1024; }
+size_t batch_ctl_bytes(uint32_t Bl, uint32_t chunks) {
+    static_assert(sizeof(BatchCtl) % 4 == 0, "zeroed as 32-bit words");
+    return sizeof(BatchCtl) + sizeof(uint32_t) * (2 * (size_t)batch_blocks(Bl) + 2 + chunks);
+}
+constexpr size_t kBlkMinOffset = 1024; // blk_best: 256 running maxima (uint32_t), from this offset 256 running minima (double)
+
+BatchSizes batch_step_sizes(int kind, const BatchShape &s) {
+    const size_t iters = std::max<uint32_t>(s.Bl, 1u), hcap = iters * s.slots;
+    // The live list, its inverse, the generator's NaN flags and the operand rows of the correspondences belong to the matrix-core
+    // absolute-pose scorer alone; the other operand blocks to the matrix-core scorer of their kind.  A single run knows its scorer
+    // and reserves them only then; a group packs one layout for all its members before any member's scorer is known and asks
+    // with use_mfma = true: every absolute-pose member has them.
+    const bool abs16 = s.use_mfma && kind == EST_ABS;
+    BatchSizes z;
+    z.positions = sizeof(uint32_t) * s.B;
+    z.delta = (size_t)s.M + 64;
+    z.flags = sizeof(uint64_t) * ((size_t)s.M / 64 + 2); // bitmap of redrawing positions
+    z.samples = sizeof(uint32_t) * (size_t)s.B * sample_size(kind); // PROSAC: host-drawn samples [B][K]
+    z.models = sizeof(double) * kModelStride * hcap;
+    z.num_models = sizeof(uint32_t) * iters;
+    z.nan_bits = abs16 ? sizeof(uint32_t) * iters : 0; // NaN flags per iteration (GenerateArgs.nan_bits)
+    z.slots = sizeof(uint32_t) * hcap;
+    z.offsets = sizeof(uint32_t) * iters;
+    z.ctl = batch_ctl_bytes(s.Bl, s.chunks);
+    z.shadow = sizeof(float) * 16 * hcap;
+    z.compact64 = sizeof(double) * kModelDoubles * hcap;
+    z.shadow16 = !s.use_mfma        ? 0
+                 : kind == EST_ABS ? (hcap + kAbs16Pad) * kAbs16Bytes
+                 : kind == EST_HOM ? (hcap + kHom16Pad) * kHom16Bytes
+                                   : (hcap + kSampson16Pad) * kSampson16Bytes;
+    z.live = z.rank = abs16 ? sizeof(uint32_t) * hcap : 0;
+    z.points16 = abs16 ? kAbs16PointBytes * s.point_rows : 0;
+    z.part_count = sizeof(uint32_t) * s.chunks * hcap;
+    z.part_score = sizeof(double) * s.chunks * hcap;
+    z.count = sizeof(uint32_t) * hcap;
+    z.score = sizeof(double) * hcap;
+    z.blk_best = kBlkMinOffset + sizeof(double) * 256;
+    z.rec_meta = sizeof(RecordMeta) * kRecordCap;
+    z.rec_models = sizeof(double) * kModelStride * kRecordCap;
+    z.gen_stage = generate_stage_bytes(kind, s.Bl);
+    return z;
+}
+
+struct BatchRun { // the state of a run its next batch step starts from (RansacRun::batch_run)
+    int kind;
+    PointSet pts;
+    uint64_t seed, pos; // pos: sampler draws consumed so far
+    double thr2;
+    PrefilterArgs pf;
+    uint32_t init_max; // best_min_inl / best_min_score: what a candidate has to beat
+    double init_min;
+    int32_t real_focal_check;
+    bool explicit_samples; // PROSAC: b.samples holds the share's samples
+};
+
+// Everything the kernels of the step need (GroupArgs: an entry of a group's table, or the arguments of the single-problem
+// launches), except `slices` - the scorer's grid is the caller's choice.
+void wire_batch_step(GroupArgs &a, const BatchRun &r, const BatchShape &s, const BatchBuffers &b) {
+    std::memset(&a, 0, sizeof(a));
+    const size_t hcap = (size_t)std::max<uint32_t>(s.Bl, 1u) * s.slots;
+    const uint32_t nblk = batch_blocks(s.Bl);
+    uint32_t *const blk_tot = reinterpret_cast<uint32_t *>(b.ctl + 1);
+    const bool live_list = s.use_mfma && r.kind == EST_ABS; // k_score_mfma streams the hypotheses without a NaN entry
+    a.active = 1;
+    a.use_mfma = s.use_mfma ? 1u : 0u;
+    a.chunks = s.chunks;
+    // sampler (its first kernel clears the control block and the tables behind it)
+    a.samp.seed = r.seed, a.samp.pos_base = r.pos, a.samp.N = r.pts.n, a.samp.B = s.B, a.samp.M = s.M;
+    a.samp.delta = b.delta;
+    a.samp.flagbits = b.flags;
+    a.samp.positions = b.positions;
+    a.samp.ctl = b.ctl;
+    a.samp.zero_words = (uint32_t)(batch_ctl_bytes(s.Bl, s.chunks) / 4);
+    // generator
+    GenerateArgs &ga = a.gen;
+    ga.pts = r.pts;
+    ga.seed = r.seed;
+    ga.pos_base = r.pos;
+    ga.positions = b.positions + s.lo;
+    ga.samples = r.explicit_samples ? b.samples : nullptr;
+    ga.num_iters = s.Bl;
+    ga.slots_per_iter = s.slots;
+    ga.ctl = b.ctl;
+    ga.models = b.models;
+    ga.num_models = b.num_models;
+    ga.real_focal_check = r.real_focal_check;
+    ga.blk_tot = blk_tot;
+    ga.blk_nan = blk_tot + nblk;
+    ga.nan_bits = live_list ? b.nan_bits : nullptr; // the live list of k_compact2 is built from the generator's NaN flags
+    ga.stage = generate_stage_bytes(r.kind, s.Bl) ? b.gen_stage : nullptr;
+    // compaction / gather / fp16 operands of the hypotheses, built in the same launch as the hypothesis-ordered copies
+    CompactArgs &ca = a.comp;
+    ca.num_models = b.num_models;
+    ca.B = s.Bl;
+    ca.maxm = (int32_t)s.slots;
+    ca.blk_tot = blk_tot;
+    ca.slots = b.slots;
+    ca.offsets = b.offsets;
+    ca.models = b.models;
+    ca.shadow = b.shadow;
+    ca.compact64 = b.compact64;
+    ca.ctl = b.ctl;
+    if (live_list) { // absolute pose: the operand rows of the live hypotheses and of the correspondences
+        ca.s16.out = b.shadow16;
+        ca.s16.g16 = r.pf.g16, ca.s16.c16 = r.pf.c16, ca.s16.thr = r.pf.thr;
+        ca.s16.live = b.live, ca.s16.rank = b.rank, ca.s16.nan_bits = ga.nan_bits;
+        ca.s16.points16 = b.points16, ca.s16.point_rows = s.point_rows;
+    } else if (s.use_mfma && r.kind == EST_HOM) { // homography: operands of k_score_mfmah (k_hom16)
+        ca.s16.out = b.shadow16;
+        ca.s16.sampson = 2;
+        ca.s16.thr = r.pf.h16;
+    } else if (s.use_mfma) { // two-view: operands of the Sampson forms (k_sampson16 / k_score_mfma2)
+        ca.s16.out = b.shadow16;
+        ca.s16.sampson = 1;
+    }
+    ca.host_offsets = nullptr; // (the one entry a stopping problem needs is fetched after the replay)
+    // scorer
+    ScoreArgs &sa = a.score;
+    sa.pts = r.pts;
+    sa.models = b.models;
+    sa.slots = b.slots;
+    sa.shadow = b.shadow;
+    sa.compact64 = b.compact64;
+    sa.shadow16 = ca.s16.out;
+    sa.num_hyp = &b.ctl->num_hyp;
+    if (live_list) { // the live list replaces the hypothesis list; everything else stays in the hypothesis index space
+        sa.slots = b.live;
+        sa.num_hyp = &b.ctl->num_live;
+        sa.points16 = b.points16;
+    }
+    sa.hyp_capacity = (uint32_t)hcap;
+    sa.thr2 = r.thr2;
+    sa.pf = r.pf;
+    sa.part_count = b.part_count;
+    sa.part_score = b.part_score;
+    sa.tickets = blk_tot + 2 * (size_t)nblk + 2;
+    // finalize + records
+    RecordsArgs &ra = a.rec;
+    ra.f.num_hyp = &b.ctl->num_hyp;
+    ra.f.rank = ca.s16.rank;
+    ra.f.hyp_capacity = (uint32_t)hcap;
+    ra.f.chunks = s.chunks;
+    ra.f.n_points = r.pts.n;
+    ra.f.thr2 = r.thr2;
+    ra.f.part_count = b.part_count;
+    ra.f.part_score = b.part_score;
+    ra.f.count = b.count;
+    ra.f.score = b.score;
+    ra.slots = b.slots;
+    ra.models = b.models;
+    ra.blk_max = reinterpret_cast<uint32_t *>(b.blk_best);
+    ra.blk_min = reinterpret_cast<double *>(b.blk_best + kBlkMinOffset);
+    ra.init_max = r.init_max;
+    ra.init_min = r.init_min;
+    ra.rec_meta = b.rec_meta;
+    ra.rec_models = b.rec_models;
+    ra.rec_cap = kRecordCap;
+    ra.ctl = b.ctl;
+    ra.host_meta = b.host_meta;
+    ra.host_models = b.host_models;
+    ra.host_cap = kRecordFirst;
+    // the listed candidates once more, summed like the reference sums them (decisions are taken on these); this last kernel of
+    // the step mirrors the control block into pinned host memory
+    SeqScoreArgs &qa = a.seq;
+    qa.pts = r.pts;
+    qa.models = b.models;
+    qa.cand = b.rec_meta;
+    qa.num = &b.ctl->num_records;
+    qa.cap = kRecordCap;
+    qa.thr2 = r.thr2;
+    qa.host_cand = b.host_meta;
+    qa.host_cap = kRecordFirst;
+    qa.ctl_src = b.ctl;
+    qa.ctl_host = b.host_ctl;
+}
+
+// The step's buffers in the Context (the single-problem path), grown to `z`.
+int context_batch_buffers(Context *c, const BatchSizes &z, BatchBuffers &b) {
+    auto grown = [](DevBuf &d, size_t bytes, auto *&ptr) {
+        const hipError_t e = d.ensure(bytes);
+        ptr = static_cast<std::remove_reference_t<decltype(ptr)>>(d.p);
+        return e;
+    };
+    HIP_TRY(grown(c->positions, z.positions, b.positions));
+    HIP_TRY(grown(c->delta, z.delta, b.delta));
+    HIP_TRY(grown(c->flags, z.flags, b.flags));
+    HIP_TRY(grown(c->samples, z.samples, b.samples));
+    HIP_TRY(grown(c->models, z.models, b.models));
+    HIP_TRY(grown(c->num_models, z.num_models, b.num_models));
+    HIP_TRY(grown(c->nan_bits, z.nan_bits, b.nan_bits));
+    HIP_TRY(grown(c->slots, z.slots, b.slots));
+    HIP_TRY(grown(c->offsets, z.offsets, b.offsets));
+    HIP_TRY(grown(c->ctl, z.ctl, b.ctl));
+    HIP_TRY(grown(c->shadow, z.shadow, b.shadow));
+    HIP_TRY(grown(c->compact64, z.compact64, b.compact64));
+    HIP_TRY(grown(c->shadow16, z.shadow16, b.shadow16));
+    HIP_TRY(grown(c->live, z.live, b.live));
+    HIP_TRY(grown(c->rank, z.rank, b.rank));
+    HIP_TRY(grown(c->points16, z.points16, b.points16));
+    HIP_TRY(grown(c->part_count, z.part_count, b.part_count));
+    HIP_TRY(grown(c->part_score, z.part_score, b.part_score));
+    HIP_TRY(grown(c->count, z.count, b.count));
+    HIP_TRY(grown(c->score, z.score, b.score));
+    HIP_TRY(grown(c->blk_best, z.blk_best, b.blk_best));
+    HIP_TRY(grown(c->rec_meta, z.rec_meta, b.rec_meta));
+    HIP_TRY(grown(c->rec_models, z.rec_models, b.rec_models));
+    HIP_TRY(grown(c->gen_stage, z.gen_stage, b.gen_stage));
+    HIP_TRY(c->h_small.ensure(sizeof(BatchCtl) + 64));
+    HIP_TRY(c->h_rec_meta.ensure(sizeof(RecordMeta) * kRecordCap));
+    HIP_TRY(c->h_gather_out.ensure(sizeof(double) * kModelStride * kRecordCap));
+    b.host_meta = c->h_rec_meta.dev<RecordMeta>();
+    b.host_models = c->h_gather_out.dev<double>();
+    b.host_ctl = c->h_small.dev<BatchCtl>();
+    return PL_OK;
+}
 
 struct RefineJob {
     double record_in[kModelStride]; // seed model
@@ -605,7 +861,7 @@ int run_refinements(Context *c, const pl_problem *p, std::vector<RefineJob> &job
         HIP_TRY(launch_lm(p->kind, p->ps, d_tasks, nj, c->stream)); // outputs + refined records: written by k_lm itself
     }
     if (rescore || tail) {
-        int rc = enqueue_score_records(c, p, c->lm_records.as<double>(), nj, tail ? tail->thr2 : thr2, false);
+        int rc = enqueue_score_records(c, p, c->lm_records.as<double>(), nj, tail ? tail->thr2 : thr2);
         if (rc != PL_OK)
             return rc;
     }
@@ -814,7 +1070,7 @@ struct RansacRun {
         HIP_TRY(c->tmp_model.ensure(sizeof(double) * kModelStride));
         HIP_TRY(hipMemcpyAsync(c->tmp_model.p, best_record, sizeof(double) * kModelStride, hipMemcpyHostToDevice,
                                c->stream));
-        int rc = enqueue_score_records(c, p, c->tmp_model.as<double>(), 1, thr2, false);
+        int rc = enqueue_score_records(c, p, c->tmp_model.as<double>(), 1, thr2);
         if (rc != PL_OK)
             return rc;
         HIP_TRY(wait_stream(c));
@@ -841,217 +1097,99 @@ struct RansacRun {
         return PL_OK;
     }
 
+    // the state the next batch step starts from
+    BatchRun batch_run() const {
+        BatchRun r;
+        r.kind = kind;
+        r.pts = p->ps;
+        r.seed = ro.seed;
+        r.pos = pos;
+        r.thr2 = thr2;
+        r.pf = problem_prefilter(p, thr2);
+        r.init_max = (uint32_t)std::min<uint64_t>(best_min_inl, 0xffffffffu);
+        r.init_min = best_min_score;
+        r.real_focal_check = o->real_focal_check;
+        r.explicit_samples = prosac;
+        return r;
+    }
+
     // ---- device: positions -> generate -> compact -> score -> finalize -> records, all on the stream ----
     int enqueue_batch(Batch &b) {
-        const uint32_t B = b.B, lo_g = b.lo_g, hi_g = b.hi_g, Bl = b.Bl;
-        (void)B, (void)lo_g, (void)hi_g, (void)Bl;
-        // ---- device: positions -> generate -> compact -> score -> finalize -> records ----
-        const size_t hcap = (size_t)std::max<uint32_t>(Bl, 1u) * MAXM;
-        ScoreArgs sa;
-        set_prefilter(sa, p, thr2);
-        const bool prefilter = true; // compact hypothesis stream for the streaming scorer (all estimators)
-        const bool on_mfma = score_uses_mfma(kind, N, sa.pf);
-        const uint32_t chunks = score_chunks(kind, N, prefilter, on_mfma);
-        if (prefilter) {
-            HIP_TRY(c->shadow.ensure(sizeof(float) * 16 * hcap));
-            HIP_TRY(c->compact64.ensure(sizeof(double) * kModelDoubles * hcap));
-        }
-        HIP_TRY(c->positions.ensure(sizeof(uint32_t) * B));
-        HIP_TRY(c->models.ensure(sizeof(double) * kModelStride * hcap));
-        HIP_TRY(c->num_models.ensure(sizeof(uint32_t) * std::max<uint32_t>(Bl, 1u)));
-        HIP_TRY(c->slots.ensure(sizeof(uint32_t) * hcap));
-        HIP_TRY(c->offsets.ensure(sizeof(uint32_t) * std::max<uint32_t>(Bl, 1u)));
-        // control block + models per 1024 iterations (zeroed together, filled by the generator)
-        // behind the control block, zeroed with it: models and NaN models per 1024 iterations (two tables of nblk + 1
-        // entries), the scorer's work counters (one per chunk of correspondences)
-        const uint32_t nblk = (Bl + 1023) / 1024;
-        const size_t ctl_bytes = sizeof(BatchCtl) + sizeof(uint32_t) * (2 * (size_t)nblk + 2 + chunks);
-        HIP_TRY(c->ctl.ensure(ctl_bytes));
-        HIP_TRY(c->part_count.ensure(sizeof(uint32_t) * chunks * hcap));
-        HIP_TRY(c->part_score.ensure(sizeof(double) * chunks * hcap));
-        HIP_TRY(c->count.ensure(sizeof(uint32_t) * hcap));
-        HIP_TRY(c->score.ensure(sizeof(double) * hcap));
-        HIP_TRY(c->blk_best.ensure((sizeof(uint32_t) + sizeof(double)) * 256 + 64));
-        HIP_TRY(c->rec_meta.ensure(sizeof(RecordMeta) * kRecordCap));
-        HIP_TRY(c->rec_models.ensure(sizeof(double) * kModelStride * kRecordCap));
-        HIP_TRY(c->h_small.ensure(sizeof(BatchCtl) + 64));
-        HIP_TRY(c->h_rec_meta.ensure(sizeof(RecordMeta) * kRecordCap));
-        HIP_TRY(c->h_gather_out.ensure(sizeof(double) * kModelStride * kRecordCap));
-        BatchCtl *d_ctl = c->ctl.as<BatchCtl>();
-        bool ctl_zeroed = false; // (the device sampler's first kernel clears the block; otherwise a memset does)
-        uint32_t *const blk_tot = reinterpret_cast<uint32_t *>(d_ctl + 1);
-
-        uint64_t pos_after = 0;
-        bool device_positions = !host_positions && !force_host_positions && !prosac;
-        const ProsacSampler prosac_at_batch_start = prosac_sampler; // a repeated batch draws the same samples
-        static_assert(sizeof(BatchCtl) % 4 == 0, "zeroed as 32-bit words");
-        if (prosac) {
-            HIP_TRY(c->h_positions.ensure(sizeof(uint32_t) * (size_t)B * K));
-            HIP_TRY(c->samples.ensure(sizeof(uint32_t) * (size_t)B * K));
-            uint32_t *hs = c->h_positions.as<uint32_t>();
-            for (uint32_t b = 0; b < B; ++b)
-                prosac_sampler.generate(hs + (size_t)b * K);
-            pos_after = prosac_sampler.pos;
-            if (Bl)
-                HIP_TRY(hipMemcpyAsync(c->samples.p, hs + (size_t)lo_g * K, sizeof(uint32_t) * (size_t)Bl * K,
-                                       hipMemcpyHostToDevice, c->stream));
-        }
-        if (device_positions) {
+        const BatchRun run = batch_run();
+        BatchShape s;
+        s.B = b.B, s.lo = b.lo_g, s.Bl = b.Bl, s.M = 0, s.slots = (uint32_t)MAXM;
+        s.use_mfma = score_uses_mfma(kind, N, run.pf);
+        s.chunks = score_chunks(kind, N, true, s.use_mfma);
+        s.point_rows = abs16_point_rows(N);
+        b.device_positions = !host_positions && !force_host_positions && !prosac;
+        if (b.device_positions) {
             // window of draw positions to evaluate: expected draws per iteration (sum N/(N-i)) + slack
             double per_it = 0;
             for (int i = 0; i < K; ++i)
                 per_it += static_cast<double>(N) / static_cast<double>(N - i);
-            const uint64_t M64 = (uint64_t)(B * per_it * 1.05) + 8192;
-            if (M64 > 0x7fffffffull || pos + M64 >= 0xffffffffull) {
-                device_positions = false;
-            } else {
-                const uint32_t M = (uint32_t)M64;
-                HIP_TRY(c->delta.ensure((size_t)M + 64));
-                HIP_TRY(c->flags.ensure(sizeof(uint64_t) * ((size_t)M / 64 + 2))); // bitmap of redrawing positions
-                HIP_TRY(launch_sample_positions(K, ro.seed, pos, N, B, M, c->delta.as<uint8_t>(),
-                                                c->flags.as<uint64_t>(), c->positions.as<uint32_t>(), d_ctl,
-                                                (uint32_t)(ctl_bytes / 4), c->stream));
-                ctl_zeroed = true;
-            }
+            const uint64_t M64 = (uint64_t)(s.B * per_it * 1.05) + 8192;
+            if (M64 > 0x7fffffffull || pos + M64 >= 0xffffffffull)
+                b.device_positions = false;
+            else
+                s.M = (uint32_t)M64;
         }
-        if (!ctl_zeroed)
-            HIP_TRY(hipMemsetAsync(d_ctl, 0, ctl_bytes, c->stream));
-        if (!device_positions && !prosac) {
-            HIP_TRY(c->h_positions.ensure(sizeof(uint32_t) * B));
-            pos_after = sample_positions_k(K, ro.seed, pos, N, B, c->h_positions.as<uint32_t>());
-            if (pos_after - pos >= 0xffffffffull)
+        const BatchSizes z = batch_step_sizes(kind, s);
+        BatchBuffers bb;
+        const int rc = context_batch_buffers(c, z, bb);
+        if (rc != PL_OK)
+            return rc;
+        GroupArgs a;
+        wire_batch_step(a, run, s, bb);
+        b.hcap = a.score.hyp_capacity;
+        b.d_ctl = bb.ctl;
+        b.prosac_at_batch_start = prosac_sampler; // a repeated batch draws the same samples
+
+        if (prosac) {
+            HIP_TRY(c->h_positions.ensure(z.samples));
+            uint32_t *hs = c->h_positions.as<uint32_t>();
+            for (uint32_t i = 0; i < s.B; ++i)
+                prosac_sampler.generate(hs + (size_t)i * K);
+            b.pos_after = prosac_sampler.pos;
+            if (s.Bl)
+                HIP_TRY(hipMemcpyAsync(bb.samples, hs + (size_t)s.lo * K, sizeof(uint32_t) * (size_t)s.Bl * K,
+                                       hipMemcpyHostToDevice, c->stream));
+        }
+        if (b.device_positions) // (its first kernel clears the control block; otherwise a memset does)
+            HIP_TRY(launch_sample_positions(K, a.samp, c->stream));
+        else
+            HIP_TRY(hipMemsetAsync(bb.ctl, 0, z.ctl, c->stream));
+        if (!b.device_positions && !prosac) {
+            HIP_TRY(c->h_positions.ensure(z.positions));
+            b.pos_after = sample_positions_k(K, ro.seed, pos, N, s.B, c->h_positions.as<uint32_t>());
+            if (b.pos_after - pos >= 0xffffffffull)
                 return fail(PL_ERR_UNSUPPORTED, "sampler draw window exceeds 32 bits");
-            HIP_TRY(hipMemcpyAsync(c->positions.p, c->h_positions.p, sizeof(uint32_t) * B, hipMemcpyHostToDevice,
-                                   c->stream));
+            HIP_TRY(hipMemcpyAsync(bb.positions, c->h_positions.p, z.positions, hipMemcpyHostToDevice, c->stream));
         }
-        if (Bl > 0) { // (a rank whose share of a short batch is empty only takes part in the exchange)
-            GenerateArgs ga;
-            ga.pts = p->ps;
-            ga.seed = ro.seed;
-            ga.pos_base = pos;
-            ga.positions = c->positions.as<uint32_t>() + lo_g;
-            ga.samples = prosac ? c->samples.as<uint32_t>() : nullptr;
-            ga.num_iters = Bl;
-            ga.slots_per_iter = (uint32_t)MAXM;
-            ga.ctl = d_ctl;
-            ga.models = c->models.as<double>();
-            ga.num_models = c->num_models.as<uint32_t>();
-            ga.real_focal_check = o->real_focal_check;
-            ga.blk_tot = blk_tot;
-            ga.blk_nan = blk_tot + nblk;
-            if (on_mfma && kind == EST_ABS) { // the live list of k_compact2 is built from the generator's NaN flags per iteration
-                HIP_TRY(c->nan_bits.ensure(sizeof(uint32_t) * Bl));
-                ga.nan_bits = c->nan_bits.as<uint32_t>();
-            }
-            if (const size_t sb = generate_stage_bytes(kind, Bl)) {
-                HIP_TRY(c->gen_stage.ensure(sb));
-                ga.stage = c->gen_stage.p;
-            }
-            HIP_TRY(launch_generate(kind, ga, c->stream));
-            sa.pts = p->ps;
-            sa.models = ga.models;
-            sa.slots = c->slots.as<uint32_t>();
-            sa.shadow16 = nullptr;
-            Shadow16Params s16;
-            if (on_mfma && kind == EST_ABS) { // fp16 operand blocks of the hypotheses for the matrix cores: built
-                                              // in the same launch as the hypothesis-ordered copies
-                HIP_TRY(c->shadow16.ensure((hcap + kAbs16Pad) * kAbs16Bytes));
-                s16.out = c->shadow16.p;
-                s16.g16 = sa.pf.g16, s16.c16 = sa.pf.c16, s16.thr = sa.pf.thr;
-                sa.shadow16 = c->shadow16.p;
-                // ... for the hypotheses without a NaN entry only (live list), and the operand rows of the correspondences
-                s16.point_rows = abs16_point_rows(N);
-                HIP_TRY(c->live.ensure(sizeof(uint32_t) * hcap));
-                HIP_TRY(c->rank.ensure(sizeof(uint32_t) * hcap));
-                HIP_TRY(c->points16.ensure(kAbs16PointBytes * s16.point_rows));
-                s16.live = c->live.as<uint32_t>(), s16.rank = c->rank.as<uint32_t>(), s16.points16 = c->points16.p;
-                s16.nan_bits = ga.nan_bits;
-            } else if (on_mfma && kind == EST_HOM) { // homography: operands of k_score_mfmah (k_hom16)
-                HIP_TRY(c->shadow16.ensure((hcap + kHom16Pad) * kHom16Bytes));
-                s16.out = c->shadow16.p;
-                s16.sampson = 2;
-                s16.thr = sa.pf.h16;
-                sa.shadow16 = c->shadow16.p;
-            } else if (on_mfma) { // two-view: operands of the Sampson forms (k_sampson16 / k_score_mfma2)
-                HIP_TRY(c->shadow16.ensure((hcap + kSampson16Pad) * kSampson16Bytes));
-                s16.out = c->shadow16.p;
-                s16.sampson = 1;
-                sa.shadow16 = c->shadow16.p;
-            }
-            HIP_TRY(launch_compact2(ga.num_models, Bl, MAXM, blk_tot, true, c->slots.as<uint32_t>(),
-                                    c->offsets.as<uint32_t>(), ga.models, prefilter ? c->shadow.as<float>() : nullptr,
-                                    prefilter ? c->compact64.as<double>() : nullptr, d_ctl, s16, p->ps, c->stream));
-            sa.shadow = prefilter ? c->shadow.as<float>() : nullptr;
-            sa.compact64 = prefilter ? c->compact64.as<double>() : nullptr;
-            sa.num_hyp = &d_ctl->num_hyp;
-            if (s16.live) { // k_score_mfma streams the live list; everything else stays in the hypothesis index space
-                sa.slots = s16.live;
-                sa.num_hyp = &d_ctl->num_live;
-                sa.points16 = s16.points16;
-            }
-            sa.hyp_capacity = (uint32_t)hcap;
-            sa.thr2 = thr2;
-            sa.part_count = c->part_count.as<uint32_t>();
-            sa.part_score = c->part_score.as<double>();
-            sa.tickets = blk_tot + 2 * (size_t)nblk + 2;
-            const uint32_t slices = std::max<uint32_t>(1u, std::min<uint32_t>(1536u / chunks, (uint32_t)hcap));
+        if (s.Bl > 0) { // (a rank whose share of a short batch is empty only takes part in the exchange)
+            const uint32_t slices = std::max<uint32_t>(1u, std::min<uint32_t>(1536u / s.chunks, a.score.hyp_capacity));
+            HIP_TRY(launch_generate(kind, a.gen, c->stream));
+            HIP_TRY(launch_compact2(a.comp, true, p->ps, c->stream));
             HIP_TRY(hipEventRecord(c->ev0, c->stream));
-            HIP_TRY(launch_score(kind, sa, slices, c->stream));
+            HIP_TRY(launch_score(kind, a.score, slices, c->stream));
             HIP_TRY(hipEventRecord(c->ev1, c->stream));
-            FinalizeArgs fa;
-            fa.num_hyp = &d_ctl->num_hyp;
-            fa.rank = s16.rank;
-            fa.hyp_capacity = (uint32_t)hcap;
-            fa.chunks = chunks;
-            fa.n_points = N;
-            fa.thr2 = thr2;
-            fa.part_count = sa.part_count;
-            fa.part_score = sa.part_score;
-            fa.count = c->count.as<uint32_t>();
-            fa.score = c->score.as<double>();
-            uint32_t *blk_max = c->blk_best.as<uint32_t>();
-            double *blk_min = reinterpret_cast<double *>(c->blk_best.as<char>() + 1024);
-            HIP_TRY(c->blk_best.ensure(1024 + sizeof(double) * 256));
-            blk_max = c->blk_best.as<uint32_t>();
-            blk_min = reinterpret_cast<double *>(c->blk_best.as<char>() + 1024);
-            const uint32_t init_max = (uint32_t)std::min<uint64_t>(best_min_inl, 0xffffffffu);
-            HIP_TRY(launch_finalize_records(fa, c->slots.as<uint32_t>(), ga.models, blk_max, blk_min, init_max, best_min_score,
-                                            c->rec_meta.as<RecordMeta>(), c->rec_models.as<double>(), kRecordCap, d_ctl,
-                                            c->h_rec_meta.dev<RecordMeta>(), c->h_gather_out.dev<double>(), kRecordFirst,
-                                            c->stream));
-            // the listed candidates once more, summed like the reference sums them (decisions are taken on these)
-            SeqScoreArgs qa;
-            qa.pts = p->ps;
-            qa.models = ga.models;
-            qa.cand = c->rec_meta.as<RecordMeta>();
-            qa.num = &d_ctl->num_records;
-            qa.cap = kRecordCap;
-            qa.thr2 = thr2;
-            qa.count = nullptr;
-            qa.score = nullptr;
-            qa.host_count = nullptr;
-            qa.host_score = nullptr;
-            qa.host_cand = c->h_rec_meta.dev<RecordMeta>();
-            qa.host_cap = kRecordFirst;
-            qa.ctl_src = d_ctl; // the last kernel of the batch mirrors the control block into pinned host memory
-            qa.ctl_host = c->h_small.dev<BatchCtl>();
-            HIP_TRY(launch_score_seq(kind, qa, c->stream));
+            HIP_TRY(launch_finalize_records(a.rec, c->stream));
+            HIP_TRY(launch_score_seq(kind, a.seq, c->stream));
             b.ctl_mirrored = true;
         }
-        b.pos_after = pos_after;
-        b.device_positions = device_positions;
-        b.hcap = hcap;
-        b.d_ctl = d_ctl;
-        b.prosac_at_batch_start = prosac_at_batch_start;
         return PL_OK;
     }
 
-    // The candidates (sorted by hypothesis index, scores summed in the reference's order) through the rule of
+    // The n candidates of one batch (scores summed in the reference's order), sorted by hypothesis index, through the rule of
     // ransac_impl.h:113-123: those that improve the running best become `imps`; the last one of an iteration seeds
-    // the local optimisation.
-    void keep_improving(const RecordMeta *meta, const uint32_t *order_, uint32_t n, uint32_t first_iteration) {
+    // the local optimisation.  first_iteration: absolute index of the first iteration of the batch (of this rank's share).
+    void list_improving(const RecordMeta *meta, uint32_t n, uint32_t first_iteration) {
+        imps.clear();
+        order.resize(n);
+        for (uint32_t a = 0; a < n; ++a)
+            order[a] = a;
+        std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return meta[x].k < meta[y].k; });
         for (uint32_t a = 0; a < n; ++a) {
-            const RecordMeta &m = meta[order_[a]];
+            const RecordMeta &m = meta[order[a]];
             const bool more = m.count > best_min_inl, better = m.score < best_min_score;
             if (!(more || better))
                 continue;
@@ -1065,7 +1203,7 @@ struct RansacRun {
             im.count = m.count;
             im.score = m.score;
             im.lo_seed = false;
-            im.gather = order_[a];
+            im.gather = order[a];
             if (!imps.empty() && imps.back().iter != im.iter)
                 imps.back().lo_seed = true;
             imps.push_back(im);
@@ -1076,14 +1214,12 @@ struct RansacRun {
 
     // ---- the one synchronisation of the batch; retry decisions; improving hypotheses of this rank's share ----
     int collect_improving(Batch &b) {
-        const uint32_t B = b.B, lo_g = b.lo_g, hi_g = b.hi_g, Bl = b.Bl;
-        (void)B, (void)lo_g, (void)hi_g, (void)Bl;
+        const uint32_t B = b.B, lo_g = b.lo_g, Bl = b.Bl;
         const size_t hcap = b.hcap;
         BatchCtl *const d_ctl = b.d_ctl;
         uint64_t &pos_after = b.pos_after;
         const bool device_positions = b.device_positions;
         const ProsacSampler &prosac_at_batch_start = b.prosac_at_batch_start;
-        (void)hcap;
         BatchCtl *h_ctl = c->h_small.as<BatchCtl>();
         RecordMeta *h_meta = c->h_rec_meta.as<RecordMeta>(); // the first kRecordFirst candidates: written by k_score_seq
         double *h_recm = c->h_gather_out.as<double>();
@@ -1147,11 +1283,7 @@ struct RansacRun {
                                        hipMemcpyDeviceToHost, c->stream));
                 HIP_TRY(wait_stream(c));
             }
-            order.resize(nrec);
-            for (uint32_t a = 0; a < nrec; ++a)
-                order[a] = a;
-            std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return h_meta[x].k < h_meta[y].k; });
-            keep_improving(h_meta, order.data(), nrec, (uint32_t)(it + lo_g));
+            list_improving(h_meta, nrec, (uint32_t)(it + lo_g));
         } else {
             // fallback (candidate list overflow, or POSELIB_AMD_HOST_RECORDS=1): scan every (tree-order) score on the
             // host with the same margin as k_records, have the candidates re-scored in the reference's summation
@@ -1221,10 +1353,7 @@ struct RansacRun {
                                            sizeof(double) * kModelStride, hipMemcpyDeviceToHost, c->stream));
                 HIP_TRY(wait_stream(c));
             }
-            order.resize(nc);
-            for (uint32_t a = 0; a < nc; ++a)
-                order[a] = a;
-            keep_improving(h_meta, order.data(), nc, (uint32_t)(it + lo_g));
+            list_improving(h_meta, nc, (uint32_t)(it + lo_g)); // (the scan listed them by hypothesis index already)
             h_rec = dst;
         }
 
@@ -2396,7 +2525,7 @@ int pl_score_model(pl_problem *p, const void *model, double max_error, uint64_t 
         store_matrix_model(rec, mat_from_colmajor(static_cast<const double *>(model)));
     HIP_TRY(c->tmp_model.ensure(sizeof(double) * kModelStride));
     HIP_TRY(hipMemcpyAsync(c->tmp_model.p, rec, sizeof(rec), hipMemcpyHostToDevice, c->stream));
-    rc = enqueue_score_records(c, p, c->tmp_model.as<double>(), 1, max_error * max_error, false);
+    rc = enqueue_score_records(c, p, c->tmp_model.as<double>(), 1, max_error * max_error);
     if (rc != PL_OK)
         return rc;
     HIP_TRY(wait_stream(c));
@@ -2447,82 +2576,45 @@ int pl_debug_score_stream(pl_problem *p, const void *models, size_t n, double ma
             store_matrix_model(&recs[(size_t)k * kModelStride], mat_from_colmajor(static_cast<const double *>(models) + 9 * (size_t)k));
     }
     const double thr2 = max_error * max_error;
-    ScoreArgs sa;
-    set_prefilter(sa, p, thr2);
-    const bool on_mfma = score_uses_mfma(p->kind, p->n, sa.pf);
-    const uint32_t chunks = score_chunks(p->kind, p->n, true, on_mfma);
-    HIP_TRY(c->models.ensure(sizeof(double) * kModelStride * H));
-    HIP_TRY(c->slots.ensure(sizeof(uint32_t) * H));
-    HIP_TRY(c->shadow.ensure(sizeof(float) * 16 * H));
-    HIP_TRY(c->compact64.ensure(sizeof(double) * kModelDoubles * H));
-    HIP_TRY(c->ctl.ensure(sizeof(BatchCtl) + 64 + sizeof(uint32_t) * chunks));
-    HIP_TRY(c->part_count.ensure(sizeof(uint32_t) * chunks * H));
-    HIP_TRY(c->part_score.ensure(sizeof(double) * chunks * H));
-    HIP_TRY(c->count.ensure(sizeof(uint32_t) * H));
-    HIP_TRY(c->score.ensure(sizeof(double) * H));
+    // the buffers and arguments of a batch step whose H "iterations" hold one model each (no sampler: B = 0): the scorer's part of
+    // them is used
+    BatchRun run{};
+    run.kind = p->kind;
+    run.pts = p->ps;
+    run.thr2 = thr2;
+    run.pf = problem_prefilter(p, thr2);
+    BatchShape s{};
+    s.Bl = H, s.slots = 1;
+    s.use_mfma = score_uses_mfma(p->kind, p->n, run.pf);
+    s.chunks = score_chunks(p->kind, p->n, true, s.use_mfma);
+    s.point_rows = abs16_point_rows(p->n);
+    const BatchSizes z = batch_step_sizes(p->kind, s);
+    BatchBuffers bb;
+    rc = context_batch_buffers(c, z, bb);
+    if (rc != PL_OK)
+        return rc;
+    bb.nan_bits = nullptr; // (no generator: k_live_list reads the records' flag words)
+    GroupArgs a;
+    wire_batch_step(a, run, s, bb);
     BatchCtl hc;
     std::memset(&hc, 0, sizeof(hc));
     hc.num_hyp = H;
-    BatchCtl *d_ctl = c->ctl.as<BatchCtl>();
-    HIP_TRY(hipMemsetAsync(d_ctl, 0, sizeof(BatchCtl) + 64 + sizeof(uint32_t) * chunks, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_ctl, &hc, sizeof(hc), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->models.p, recs.data(), sizeof(double) * recs.size(), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->slots.p, ident.data(), sizeof(uint32_t) * H, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(launch_gather_models(d_ctl, c->slots.as<uint32_t>(), c->models.as<double>(), H, c->shadow.as<float>(),
-                                 c->compact64.as<double>(), c->stream));
-    sa.pts = p->ps;
-    sa.models = c->models.as<double>();
-    sa.slots = c->slots.as<uint32_t>();
-    sa.shadow16 = nullptr;
-    int path = sa.pf.enabled ? 1 : 0;
-    Shadow16Params s16;
-    if (on_mfma && p->kind == EST_ABS) { // as in the main loop: live list, operand rows of the live hypotheses and of the points
-        s16.point_rows = abs16_point_rows(p->n);
-        HIP_TRY(c->shadow16.ensure(((size_t)H + kAbs16Pad) * kAbs16Bytes));
-        HIP_TRY(c->live.ensure(sizeof(uint32_t) * H));
-        HIP_TRY(c->rank.ensure(sizeof(uint32_t) * H));
-        HIP_TRY(c->points16.ensure(kAbs16PointBytes * s16.point_rows));
-        s16.out = c->shadow16.p;
-        s16.g16 = sa.pf.g16, s16.c16 = sa.pf.c16, s16.thr = sa.pf.thr;
-        s16.live = c->live.as<uint32_t>(), s16.rank = c->rank.as<uint32_t>(), s16.points16 = c->points16.p;
-        HIP_TRY(launch_abs16(d_ctl, c->slots.as<uint32_t>(), c->models.as<double>(), H, p->ps, s16, c->stream));
-        sa.shadow16 = c->shadow16.p;
-        sa.points16 = s16.points16;
-        sa.slots = s16.live;
-        path = 2;
-    } else if (on_mfma && p->kind == EST_HOM) {
-        HIP_TRY(c->shadow16.ensure(((size_t)H + kHom16Pad) * kHom16Bytes));
-        HIP_TRY(launch_hom16(d_ctl, c->slots.as<uint32_t>(), c->models.as<double>(), H, sa.pf.h16, c->shadow16.p, c->stream));
-        sa.shadow16 = c->shadow16.p;
-        path = 2;
-    } else if (on_mfma) {
-        HIP_TRY(c->shadow16.ensure(((size_t)H + kSampson16Pad) * kSampson16Bytes));
-        HIP_TRY(launch_sampson16(d_ctl, c->slots.as<uint32_t>(), c->models.as<double>(), H, c->shadow16.p, c->stream));
-        sa.shadow16 = c->shadow16.p;
-        path = 2;
-    }
-    sa.shadow = c->shadow.as<float>();
-    sa.compact64 = c->compact64.as<double>();
-    sa.num_hyp = s16.live ? &d_ctl->num_live : &d_ctl->num_hyp;
-    sa.hyp_capacity = H;
-    sa.thr2 = thr2;
-    sa.part_count = c->part_count.as<uint32_t>();
-    sa.part_score = c->part_score.as<double>();
-    sa.tickets = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(d_ctl) + sizeof(BatchCtl) + 64);
-    const uint32_t slices = std::max<uint32_t>(1u, std::min<uint32_t>(1536u / chunks, H));
-    HIP_TRY(launch_score(p->kind, sa, slices, c->stream));
-    FinalizeArgs fa;
-    fa.num_hyp = &d_ctl->num_hyp;
-    fa.rank = s16.rank;
-    fa.hyp_capacity = H;
-    fa.chunks = chunks;
-    fa.n_points = p->n;
-    fa.thr2 = thr2;
-    fa.part_count = sa.part_count;
-    fa.part_score = sa.part_score;
-    fa.count = c->count.as<uint32_t>();
-    fa.score = c->score.as<double>();
-    HIP_TRY(launch_finalize(fa, c->stream));
+    HIP_TRY(hipMemsetAsync(bb.ctl, 0, z.ctl, c->stream));
+    HIP_TRY(hipMemcpyAsync(bb.ctl, &hc, sizeof(hc), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(bb.models, recs.data(), sizeof(double) * recs.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(bb.slots, ident.data(), sizeof(uint32_t) * H, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(launch_gather_models(bb.ctl, bb.slots, bb.models, H, bb.shadow, bb.compact64, c->stream));
+    const Shadow16Params &s16 = a.comp.s16;
+    if (s16.out && s16.sampson == 0) // as in the main loop: live list, operand rows of the live hypotheses and of the points
+        HIP_TRY(launch_abs16(bb.ctl, bb.slots, bb.models, H, p->ps, s16, c->stream));
+    else if (s16.out && s16.sampson == 2)
+        HIP_TRY(launch_hom16(bb.ctl, bb.slots, bb.models, H, s16.thr, s16.out, c->stream));
+    else if (s16.out)
+        HIP_TRY(launch_sampson16(bb.ctl, bb.slots, bb.models, H, s16.out, c->stream));
+    const int path = s16.out ? 2 : (run.pf.enabled ? 1 : 0);
+    const uint32_t slices = std::max<uint32_t>(1u, std::min<uint32_t>(1536u / s.chunks, H));
+    HIP_TRY(launch_score(p->kind, a.score, slices, c->stream));
+    HIP_TRY(launch_finalize(a.rec.f, c->stream));
     if (counts)
         HIP_TRY(hipMemcpyAsync(counts, c->count.p, sizeof(uint32_t) * H, hipMemcpyDeviceToHost, c->stream));
     if (scores)

@@ -29,9 +29,9 @@ constexpr uint32_t kGroupMax = 128;         // problems per launch sequence: pl_
 constexpr uint32_t kGroupMaxAuto = 256;     // ... which grows with the size of the call up to this (driver.cc pl_estimate_batch)
 constexpr uint32_t kGroupMaxPoints = 16384; // larger problems gain nothing from grouping
 
-struct GroupLayout { // byte offsets inside one slot of the arena (the same for every slot of a step)
-    size_t positions, delta, flags, models, num_models, nan_bits, slots, offsets, ctl, shadow, compact64, shadow16, live, rank, points16, part_count,
-        part_score, count, score, blk_best, rec_meta, rec_models, gen_stage, pts, pts2, mask, tmp_model, absmax, samples, total;
+struct GroupLayout { // one slot of the arena (the same for every slot of a step): a batch step's buffers, then the group's own
+    BatchSizes batch;
+    size_t pts, pts2, mask, tmp_model, absmax, total; // byte offsets inside the slot
 };
 
 struct GroupContext { // per host thread AND device, kept for later groups
@@ -192,49 +192,64 @@ bool group_eligible_resident(const pl_ransac_item &it) {
     return true;
 }
 
+// A batch step's buffers packed one behind the other from `base`, 256-byte aligned each; returns the bytes they take (base ==
+// nullptr: only that).  The pinned mirrors are the caller's.
+size_t pack_batch_buffers(char *base, const BatchSizes &z, BatchBuffers &b) {
+    size_t o = 0;
+    auto take = [&](auto *&ptr, size_t bytes) {
+        ptr = reinterpret_cast<std::remove_reference_t<decltype(ptr)>>(reinterpret_cast<uintptr_t>(base) + o);
+        o += align_up(bytes);
+    };
+    take(b.positions, z.positions);
+    take(b.delta, z.delta);
+    take(b.flags, z.flags);
+    take(b.samples, z.samples);
+    take(b.models, z.models);
+    take(b.num_models, z.num_models);
+    take(b.nan_bits, z.nan_bits);
+    take(b.slots, z.slots);
+    take(b.offsets, z.offsets);
+    take(b.ctl, z.ctl);
+    take(b.shadow, z.shadow);
+    take(b.compact64, z.compact64);
+    take(b.shadow16, z.shadow16);
+    take(b.live, z.live);
+    take(b.rank, z.rank);
+    take(b.points16, z.points16);
+    take(b.part_count, z.part_count);
+    take(b.part_score, z.part_score);
+    take(b.count, z.count);
+    take(b.score, z.score);
+    take(b.blk_best, z.blk_best);
+    take(b.rec_meta, z.rec_meta);
+    take(b.rec_models, z.rec_models);
+    take(b.gen_stage, z.gen_stage);
+    return o;
+}
+
+// max_B iterations, a sampler window of max_M, maxm record slots per iteration, `chunks` chunks of 64 P correspondences (P: the
+// group's points per lane): room for every member, whichever scorer it turns out to use (batch_step_sizes)
 GroupLayout group_layout(int kind, uint32_t max_n, uint32_t max_B, uint32_t max_M, uint32_t maxm, uint32_t chunks,
                          bool resident = false) {
     GroupLayout L;
-    size_t o = 0;
+    BatchShape s;
+    s.B = s.Bl = max_B, s.lo = 0, s.M = max_M, s.slots = maxm, s.chunks = chunks;
+    s.point_rows = chunks * 64u * (uint32_t)group_points_per_lane(kind);
+    s.use_mfma = true;
+    L.batch = batch_step_sizes(kind, s);
+    BatchBuffers unused;
+    size_t o = pack_batch_buffers(nullptr, L.batch, unused);
     auto take = [&](size_t bytes) {
         const size_t at = o;
         o += align_up(bytes);
         return at;
     };
-    const size_t hcap = (size_t)std::max<uint32_t>(max_B, 1u) * maxm;
-    const size_t nblk = (max_B + 1023) / 1024;
     const int nd = point_doubles(kind);
-    L.positions = take(sizeof(uint32_t) * max_B);
-    L.delta = take((size_t)max_M + 64);
-    L.flags = take(sizeof(uint64_t) * ((size_t)max_M / 64 + 2));
-    L.models = take(sizeof(double) * kModelStride * hcap);
-    L.num_models = take(sizeof(uint32_t) * max_B);
-    L.nan_bits = take(kind == EST_ABS ? sizeof(uint32_t) * max_B : 0); // NaN flags per iteration (GenerateArgs.nan_bits)
-    L.slots = take(sizeof(uint32_t) * hcap);
-    L.offsets = take(sizeof(uint32_t) * max_B);
-    L.ctl = take(sizeof(BatchCtl) + sizeof(uint32_t) * (2 * nblk + 2 + chunks));
-    L.shadow = take(sizeof(float) * 16 * hcap);
-    L.compact64 = take(sizeof(double) * kModelDoubles * hcap);
-    L.shadow16 = take(kind == EST_ABS ? (hcap + kAbs16Pad) * kAbs16Bytes
-                      : (kind == EST_HOM ? (hcap + kHom16Pad) * kHom16Bytes : (hcap + kSampson16Pad) * kSampson16Bytes));
-    // absolute pose on the matrix cores: live hypothesis list + inverse, operand rows of the correspondences (chunks of 64 P)
-    L.live = take(kind == EST_ABS ? sizeof(uint32_t) * hcap : 0);
-    L.rank = take(kind == EST_ABS ? sizeof(uint32_t) * hcap : 0);
-    L.points16 = take(kind == EST_ABS ? kAbs16PointBytes * chunks * 64 * (size_t)group_points_per_lane(kind) : 0);
-    L.part_count = take(sizeof(uint32_t) * chunks * hcap);
-    L.part_score = take(sizeof(double) * chunks * hcap);
-    L.count = take(sizeof(uint32_t) * hcap);
-    L.score = take(sizeof(double) * hcap);
-    L.blk_best = take(1024 + sizeof(double) * 256);
-    L.rec_meta = take(sizeof(RecordMeta) * kRecordCap);
-    L.rec_models = take(sizeof(double) * kModelStride * kRecordCap);
-    L.gen_stage = take(generate_stage_bytes(kind, max_B) + 64);
     L.pts = take(resident ? 0 : sizeof(double) * nd * max_n);
     L.pts2 = take(kind == EST_ABS && !resident ? sizeof(double) * nd * max_n : 0);
     L.mask = take(max_n);
     L.tmp_model = take(sizeof(double) * kModelStride);
     L.absmax = take(sizeof(unsigned long long));
-    L.samples = take(sizeof(uint32_t) * 7 * (size_t)max_B); // PROSAC: a member's host-drawn samples [B][K], K <= 7 (28 B per iteration)
     L.total = align_up(o, 4096);
     return L;
 }
@@ -491,6 +506,14 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
     HIP_TRY(gc.h_mask.ensure(resident ? (size_t)max_n * count : raise_hw(g_hw_mask, (size_t)max_n * count)));
     char *const arena = gc.arena.as<char>();
     auto slot = [&](uint32_t i, size_t off) { return arena + (size_t)i * L.total + off; };
+    auto slot_buffers = [&](uint32_t i) { // member i's buffers of a batch step and the pinned mirrors of its small results
+        BatchBuffers b;
+        pack_batch_buffers(slot(i, 0), L.batch, b);
+        b.host_meta = gc.h_meta.dev<RecordMeta>() + (size_t)i * kRecordFirst;
+        b.host_models = gc.h_recm.dev<double>() + (size_t)i * kRecordFirst * kModelStride;
+        b.host_ctl = gc.h_ctl.dev<BatchCtl>() + i;
+        return b;
+    };
 
     // ---- stage A: raw points -> pinned block -> device; k_prepare_g (resident problems: their own SoA block) ----
     std::unique_ptr<PhaseTimer> ptA(new PhaseTimer(g_t_stageA));
@@ -657,16 +680,9 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
                 T.record_out = gc.lm_records.as<double>() + (size_t)t * kModelStride;
                 std::memcpy(hr + (size_t)t * kModelStride, r.jobs[j].record_in, sizeof(double) * kModelStride);
             }
-            q.pts = g.prob.ps;
-            q.models = gc.lm_records.as<double>() + (size_t)g.job0 * kModelStride;
-            q.cand = nullptr;
-            q.num = c->iota.as<uint32_t>() + nj;
-            q.cap = nj;
-            q.thr2 = r.thr2;
-            q.count = gc.seq_count.as<uint32_t>() + g.job0;
-            q.score = gc.seq_score.as<double>() + g.job0;
-            q.host_count = gc.h_count.dev<uint32_t>() + g.job0;
-            q.host_score = gc.h_score.dev<double>() + g.job0;
+            q = plain_seq_args(c, g.prob.ps, gc.lm_records.as<double>() + (size_t)g.job0 * kModelStride, nj, r.thr2,
+                               gc.seq_count.as<uint32_t>() + g.job0, gc.seq_score.as<double>() + g.job0,
+                               gc.h_count.dev<uint32_t>() + g.job0, gc.h_score.dev<double>() + g.job0);
         }
         if (max_jobs >= kIotaEntries)
             return fail(PL_ERR_UNSUPPORTED, "too many local optimisations in one batch of a grouped problem");
@@ -715,17 +731,9 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
         for (uint32_t w = 0; w < nw; ++w) {
             GroupItem &g = (*pit[warm_members[w]]);
             std::memcpy(hrec + (size_t)w * kModelStride, g.rec, sizeof(double) * kModelStride);
-            SeqScoreArgs &q = hs[warm_members[w]];
-            q.pts = g.prob.ps;
-            q.models = gc.lm_records.as<double>() + (size_t)w * kModelStride;
-            q.cand = nullptr;
-            q.num = c->iota.as<uint32_t>() + 1;
-            q.cap = 1;
-            q.thr2 = g.run->thr2;
-            q.count = gc.seq_count.as<uint32_t>() + w;
-            q.score = gc.seq_score.as<double>() + w;
-            q.host_count = gc.h_count.dev<uint32_t>() + w;
-            q.host_score = gc.h_score.dev<double>() + w;
+            hs[warm_members[w]] = plain_seq_args(c, g.prob.ps, gc.lm_records.as<double>() + (size_t)w * kModelStride, 1, g.run->thr2,
+                                                 gc.seq_count.as<uint32_t>() + w, gc.seq_score.as<double>() + w,
+                                                 gc.h_count.dev<uint32_t>() + w, gc.h_score.dev<double>() + w);
         }
         HIP_TRY(hipMemcpyAsync(gc.lm_records.p, hrec, sizeof(double) * kModelStride * nw, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipMemcpyAsync(gc.args.p, hs, sizeof(SeqScoreArgs) * count, hipMemcpyHostToDevice, c->stream));
@@ -823,138 +831,27 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
                 g.active = false, g.fallback = true;
                 continue;
             }
-            const size_t hcap = (size_t)B * r.MAXM;
-            const uint32_t nblk = (B + 1023) / 1024;
-            ScoreArgs &sa = a.score;
-            set_prefilter(sa, &g.prob, r.thr2);
-            a.use_mfma = score_uses_mfma(kind, N, sa.pf) ? 1u : 0u;
-            const uint32_t chunks_i = group_member_chunks(kind, a.use_mfma != 0, N);
-            const size_t ctl_bytes = sizeof(BatchCtl) + sizeof(uint32_t) * (2 * (size_t)nblk + 2 + chunks_i);
-            BatchCtl *d_ctl = reinterpret_cast<BatchCtl *>(slot(i, L.ctl));
-            uint32_t *blk_tot = reinterpret_cast<uint32_t *>(d_ctl + 1);
-            a.active = 1;
-            // sampler
-            a.samp.seed = r.ro.seed, a.samp.pos_base = r.pos, a.samp.N = N, a.samp.B = B, a.samp.M = (uint32_t)M64;
-            a.samp.delta = reinterpret_cast<uint8_t *>(slot(i, L.delta));
-            a.samp.flagbits = reinterpret_cast<uint64_t *>(slot(i, L.flags));
-            a.samp.positions = reinterpret_cast<uint32_t *>(slot(i, L.positions));
-            a.samp.ctl = d_ctl;
-            a.samp.zero_words = (uint32_t)(ctl_bytes / 4);
-            // generator
-            GenerateArgs &ga = a.gen;
-            ga.pts = g.prob.ps;
-            ga.seed = r.ro.seed;
-            ga.pos_base = r.pos;
-            ga.positions = a.samp.positions;
-            ga.samples = nullptr;
+            const BatchRun run = r.batch_run();
+            BatchShape s;
+            s.B = s.Bl = B, s.lo = 0, s.M = (uint32_t)M64, s.slots = (uint32_t)r.MAXM;
+            s.use_mfma = score_uses_mfma(kind, N, run.pf);
+            s.chunks = group_member_chunks(kind, s.use_mfma, N);
+            s.point_rows = s.chunks * 64u * (uint32_t)P;
+            const BatchBuffers bb = slot_buffers(i);
+            wire_batch_step(a, run, s, bb);
             if (r.prosac) { // the member's samples of this step, drawn on the host (sampling.cc:85-136), uploaded below
                 g.b.prosac_at_batch_start = r.prosac_sampler;
                 prosac_members.push_back(i);
-                ga.samples = reinterpret_cast<uint32_t *>(slot(i, L.samples));
             }
-            ga.num_iters = B;
-            ga.slots_per_iter = (uint32_t)r.MAXM;
-            ga.ctl = d_ctl;
-            ga.models = reinterpret_cast<double *>(slot(i, L.models));
-            ga.num_models = reinterpret_cast<uint32_t *>(slot(i, L.num_models));
-            ga.nan_bits = (a.use_mfma && kind == EST_ABS) ? reinterpret_cast<uint32_t *>(slot(i, L.nan_bits)) : nullptr; // (live list)
-            ga.real_focal_check = g.fe.scaled.real_focal_check;
-            ga.blk_tot = blk_tot;
-            ga.blk_nan = blk_tot + nblk;
-            ga.stage = generate_stage_bytes(kind, B) ? slot(i, L.gen_stage) : nullptr;
-            // scorer
-            a.chunks = chunks_i;
-            sa.tickets = blk_tot + 2 * (size_t)nblk + 2;
             // hypothesis slices per chunk of correspondences: chosen below, once the launch's active members are known
             // (group_score_slices)
+            const uint32_t hcap = a.score.hyp_capacity;
             hexp_of[i] = group_expected_hypotheses(kind, B, hcap);
-            sa.pts = g.prob.ps;
-            sa.models = ga.models;
-            sa.slots = reinterpret_cast<uint32_t *>(slot(i, L.slots));
-            sa.shadow = reinterpret_cast<float *>(slot(i, L.shadow));
-            sa.compact64 = reinterpret_cast<double *>(slot(i, L.compact64));
-            sa.shadow16 = a.use_mfma ? slot(i, L.shadow16) : nullptr;
-            sa.num_hyp = &d_ctl->num_hyp;
-            const bool live_list = a.use_mfma && kind == EST_ABS; // k_score_mfma streams the hypotheses without a NaN entry
-            if (live_list) {
-                sa.slots = reinterpret_cast<uint32_t *>(slot(i, L.live));
-                sa.num_hyp = &d_ctl->num_live;
-                sa.points16 = slot(i, L.points16);
-            }
-            sa.hyp_capacity = (uint32_t)hcap;
-            sa.thr2 = r.thr2;
-            sa.part_count = reinterpret_cast<uint32_t *>(slot(i, L.part_count));
-            sa.part_score = reinterpret_cast<double *>(slot(i, L.part_score));
-            // compaction / gather / fp16 operands
-            CompactArgs &ca = a.comp;
-            ca.num_models = ga.num_models;
-            ca.B = B;
-            ca.maxm = r.MAXM;
-            ca.blk_tot = blk_tot;
-            ca.slots = reinterpret_cast<uint32_t *>(slot(i, L.slots));
-            ca.offsets = reinterpret_cast<uint32_t *>(slot(i, L.offsets));
-            ca.models = ga.models;
-            ca.shadow = const_cast<float *>(sa.shadow);
-            ca.compact64 = const_cast<double *>(sa.compact64);
-            ca.ctl = d_ctl;
-            if (a.use_mfma) {
-                ca.s16.out = slot(i, L.shadow16);
-                ca.s16.g16 = sa.pf.g16, ca.s16.c16 = sa.pf.c16, ca.s16.thr = sa.pf.thr;
-                ca.s16.sampson = (kind == EST_ABS) ? 0 : (kind == EST_HOM ? 2 : 1);
-                if (kind == EST_HOM)
-                    ca.s16.thr = sa.pf.h16;
-                if (live_list) {
-                    ca.s16.live = const_cast<uint32_t *>(sa.slots);
-                    ca.s16.rank = reinterpret_cast<uint32_t *>(slot(i, L.rank));
-                    ca.s16.nan_bits = ga.nan_bits;
-                    ca.s16.points16 = slot(i, L.points16);
-                    ca.s16.point_rows = a.chunks * 64u * (uint32_t)P;
-                }
-            }
-            ca.host_offsets = nullptr; // (the one entry a stopping problem needs is fetched after the replay)
-            // finalize + records
-            RecordsArgs &ra = a.rec;
-            ra.f.num_hyp = &d_ctl->num_hyp;
-            ra.f.rank = ca.s16.rank;
-            ra.f.hyp_capacity = (uint32_t)hcap;
-            ra.f.chunks = a.chunks;
-            ra.f.n_points = N;
-            ra.f.thr2 = r.thr2;
-            ra.f.part_count = sa.part_count;
-            ra.f.part_score = sa.part_score;
-            ra.f.count = reinterpret_cast<uint32_t *>(slot(i, L.count));
-            ra.f.score = reinterpret_cast<double *>(slot(i, L.score));
-            ra.slots = ca.slots;
-            ra.models = ga.models;
-            ra.blk_max = reinterpret_cast<uint32_t *>(slot(i, L.blk_best));
-            ra.blk_min = reinterpret_cast<double *>(slot(i, L.blk_best) + 1024);
-            ra.init_max = (uint32_t)std::min<uint64_t>(r.best_min_inl, 0xffffffffu);
-            ra.init_min = r.best_min_score;
-            ra.rec_meta = reinterpret_cast<RecordMeta *>(slot(i, L.rec_meta));
-            ra.rec_models = reinterpret_cast<double *>(slot(i, L.rec_models));
-            ra.rec_cap = kRecordCap;
-            ra.ctl = d_ctl;
-            ra.host_meta = gc.h_meta.dev<RecordMeta>() + (size_t)i * kRecordFirst;
-            ra.host_models = gc.h_recm.dev<double>() + (size_t)i * kRecordFirst * kModelStride;
-            ra.host_cap = kRecordFirst;
-            // candidates in the reference's summation order; the control block goes to pinned memory with it
-            SeqScoreArgs &qa = a.seq;
-            qa.pts = g.prob.ps;
-            qa.models = ga.models;
-            qa.cand = ra.rec_meta;
-            qa.num = &d_ctl->num_records;
-            qa.cap = kRecordCap;
-            qa.thr2 = r.thr2;
-            qa.count = nullptr, qa.score = nullptr, qa.host_count = nullptr, qa.host_score = nullptr;
-            qa.host_cand = ra.host_meta;
-            qa.host_cap = kRecordFirst;
-            qa.ctl_src = d_ctl;
-            qa.ctl_host = gc.h_ctl.dev<BatchCtl>() + i;
             // grid extents
             dims.max_M = std::max(dims.max_M, a.samp.M);
             dims.min_n = std::min(dims.min_n, g.n);
             dims.max_B = std::max(dims.max_B, B);
-            dims.max_hcap = std::max<uint32_t>(dims.max_hcap, (uint32_t)hcap);
+            dims.max_hcap = std::max(dims.max_hcap, hcap);
             dims.max_chunks = std::max(dims.max_chunks, a.chunks);
             dims.any_mfma |= a.use_mfma;
             dims.any_queue |= a.use_mfma ? 0u : 1u;
@@ -989,7 +886,7 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
                 for (uint32_t bb = 0; bb < g.b.B; ++bb)
                     r.prosac_sampler.generate(hs + (size_t)bb * K);
                 g.b.pos_after = r.prosac_sampler.pos;
-                HIP_TRY(hipMemcpyAsync(slot(i, L.samples), hs, sizeof(uint32_t) * (size_t)g.b.B * K, hipMemcpyHostToDevice, c->stream));
+                HIP_TRY(hipMemcpyAsync(slot_buffers(i).samples, hs, sizeof(uint32_t) * (size_t)g.b.B * K, hipMemcpyHostToDevice, c->stream));
                 hs += (size_t)g.b.B * K;
             }
         }
@@ -1029,12 +926,7 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
             g.b.h_rec = gc.h_recm.as<double>() + (size_t)i * kRecordFirst * kModelStride;
             g.st->nan_hypotheses += hc.nan_hyp;
             const RecordMeta *meta = gc.h_meta.as<RecordMeta>() + (size_t)i * kRecordFirst;
-            r.imps.clear();
-            r.order.resize(hc.num_records);
-            for (uint32_t a = 0; a < hc.num_records; ++a)
-                r.order[a] = a;
-            std::sort(r.order.begin(), r.order.end(), [&](uint32_t x, uint32_t y) { return meta[x].k < meta[y].k; });
-            r.keep_improving(meta, r.order.data(), hc.num_records, (uint32_t)r.it);
+            r.list_improving(meta, hc.num_records, (uint32_t)r.it);
             r.make_jobs(g.b);
         }
         ptImp.reset();
@@ -1167,15 +1059,8 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
             T.record_out = gc.lm_records.as<double>() + (size_t)t * kModelStride;
             std::memcpy(hr + (size_t)t * kModelStride, g.rec, sizeof(double) * kModelStride);
             std::memcpy(hr + (size_t)(nt + t) * kModelStride, g.rec, sizeof(double) * kModelStride);
-            hs[i].pts = g.prob.ps;
-            hs[i].models = T.record_out;
-            hs[i].num = c->iota.as<uint32_t>() + 1;
-            hs[i].cap = 1;
-            hs[i].thr2 = r.thr2;
-            hs[i].count = gc.seq_count.as<uint32_t>() + t;
-            hs[i].score = gc.seq_score.as<double>() + t;
-            hs[i].host_count = gc.h_count.dev<uint32_t>() + t;
-            hs[i].host_score = gc.h_score.dev<double>() + t;
+            hs[i] = plain_seq_args(c, g.prob.ps, T.record_out, 1, r.thr2, gc.seq_count.as<uint32_t>() + t, gc.seq_score.as<double>() + t,
+                                   gc.h_count.dev<uint32_t>() + t, gc.h_score.dev<double>() + t);
             hsel[i].score_refined = hs[i].score;
             hsel[i].incumbent_score = g.st->model_score;
             hsel[i].rec_refined = T.record_out;
@@ -1187,7 +1072,7 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
                 hsel[i].count_out = gc.sel_count.as<uint32_t>() + i;
             }
             if (g.off_fetch >= 0) {
-                hsel[i].fetch_src = reinterpret_cast<const uint32_t *>(slot(i, L.offsets)) + g.off_fetch;
+                hsel[i].fetch_src = slot_buffers(i).offsets + g.off_fetch;
                 hsel[i].fetch_dst = gc.h_offsets.dev<uint32_t>() + i;
             }
             hm[i].model = d_tmp;

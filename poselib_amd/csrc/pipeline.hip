@@ -1137,9 +1137,13 @@ hipError_t launch_prepare(const double *a_raw, const double *b_raw, uint32_t n, 
     return hipGetLastError();
 }
 
-hipError_t launch_sample_positions(int K, uint64_t seed, uint64_t pos_base, uint64_t N, uint32_t B, uint32_t M,
-                                   uint8_t *delta, uint64_t *flagbits, uint32_t *positions, BatchCtl *ctl,
-                                   uint32_t zero_words, hipStream_t stream) {
+hipError_t launch_sample_positions(int K, const SampleArgs &a, hipStream_t stream) {
+    const uint64_t seed = a.seed, pos_base = a.pos_base, N = a.N;
+    const uint32_t B = a.B, M = a.M, zero_words = a.zero_words;
+    uint8_t *const delta = a.delta;
+    uint64_t *const flagbits = a.flagbits;
+    uint32_t *const positions = a.positions;
+    BatchCtl *const ctl = a.ctl;
     uint32_t *const zero = reinterpret_cast<uint32_t *>(ctl);
     const dim3 grid((M + 255) / 256), block(256);
     switch (K) {
@@ -1165,9 +1169,16 @@ hipError_t launch_sample_positions(int K, uint64_t seed, uint64_t pos_base, uint
     return hipGetLastError();
 }
 
-hipError_t launch_compact2(const uint32_t *num_models, uint32_t B, int maxm, uint32_t *blk_tot, bool counted, uint32_t *slots,
-                           uint32_t *offsets, const double *models, float *shadow_compact, double *compact64,
-                           BatchCtl *ctl, const Shadow16Params &s16, const PointSet &pts, hipStream_t stream) {
+hipError_t launch_compact2(const CompactArgs &a, bool counted, const PointSet &pts, hipStream_t stream) {
+    const uint32_t *const num_models = a.num_models;
+    const uint32_t B = a.B;
+    const int maxm = a.maxm;
+    uint32_t *const blk_tot = a.blk_tot, *const slots = a.slots, *const offsets = a.offsets;
+    const double *const models = a.models;
+    float *const shadow_compact = a.shadow;
+    double *const compact64 = a.compact64;
+    BatchCtl *const ctl = a.ctl;
+    const Shadow16Params &s16 = a.s16;
     const uint32_t nb = (B + 1023) / 1024;
     const bool abs16 = s16.out && s16.sampson == 0;
     // (the live list starts every block at the generators' NaN counts: k_count_blocks does not count those)
@@ -1280,14 +1291,12 @@ hipError_t launch_group_prepare(const PrepareGroupArgs *args, uint32_t G, uint32
     return hipGetLastError();
 }
 
-hipError_t launch_finalize_records(const FinalizeArgs &f, const uint32_t *slots, const double *models,
-                                   uint32_t *blk_max, double *blk_min, uint32_t init_max, double init_min,
-                                   RecordMeta *rec_meta, double *rec_models, uint32_t rec_cap, BatchCtl *ctl,
-                                   RecordMeta *host_meta, double *host_models, uint32_t host_cap, hipStream_t stream) {
-    k_finalize2<<<dim3(kRecBlocks), dim3(256), 0, stream>>>(f, blk_max, blk_min);
-    k_records<<<dim3(kRecBlocks), dim3(256), 0, stream>>>(f.num_hyp, f.count, f.score, slots, models, blk_max, blk_min,
-                                                          init_max, init_min, rec_meta, rec_models, rec_cap, ctl,
-                                                          host_meta, host_models, host_meta ? host_cap : 0u);
+hipError_t launch_finalize_records(const RecordsArgs &a, hipStream_t stream) {
+    const FinalizeArgs &f = a.f;
+    k_finalize2<<<dim3(kRecBlocks), dim3(256), 0, stream>>>(f, a.blk_max, a.blk_min);
+    k_records<<<dim3(kRecBlocks), dim3(256), 0, stream>>>(f.num_hyp, f.count, f.score, a.slots, a.models, a.blk_max, a.blk_min,
+                                                          a.init_max, a.init_min, a.rec_meta, a.rec_models, a.rec_cap, a.ctl,
+                                                          a.host_meta, a.host_models, a.host_meta ? a.host_cap : 0u);
     return hipGetLastError();
 }
 

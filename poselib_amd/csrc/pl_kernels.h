@@ -219,14 +219,8 @@ hipError_t launch_mask(int est, const PointSet &pts, const double *model, double
                        uint8_t *host_mask, hipStream_t stream);
 
 // ---- device-side bookkeeping (pipeline.hip) ----
-// zero_words: 32-bit words starting at `ctl` (control block + the generators' per-block model counts) that the first
-// kernel zeroes itself (0: the caller has done it)
-hipError_t launch_sample_positions(int K, uint64_t seed, uint64_t pos_base, uint64_t N, uint32_t B, uint32_t M,
-                                   uint8_t *delta, uint64_t *flagbits /* >= ceil(M / 64) words */, uint32_t *positions,
-                                   BatchCtl *ctl, uint32_t zero_words, hipStream_t stream);
-// counted: blk_tot already holds the per-block model counts (GenerateArgs.blk_tot); otherwise they are counted first
-// shadow16 != nullptr: the fp16 operand blocks of k_score_mfma are built in the same launch as the hypothesis-ordered
-// copies (Shadow16Params; see k_gather_shadow16)
+// the fp16 operand blocks of the matrix-core scorers, built in the same launch as the hypothesis-ordered copies (see
+// k_gather_shadow16); out == nullptr: none
 struct Shadow16Params {
     void *out = nullptr;
     float g16 = 0.f, c16 = 0.f, thr = 0.f;
@@ -248,11 +242,6 @@ constexpr size_t kAbs16PointBytes = 64; // ... and per correspondence: first k b
 constexpr size_t kSampson16Pad = 64; // operand rows a partial group of 32 may read past the last hypothesis
 constexpr size_t kHom16Bytes = 256; // homography (k_score_mfmah): 4 rows x 4 k blocks x 16 B per hypothesis, groups of 8
 constexpr size_t kHom16Pad = 8;     // the last group of 8 is filled up
-// blk_tot is followed by the generators' NaN-model table of the same length (nb = ceil(B / 1024) entries each)
-// pts: the problem's correspondences (read where s16.points16 is set)
-hipError_t launch_compact2(const uint32_t *num_models, uint32_t B, int maxm, uint32_t *blk_tot, bool counted, uint32_t *slots,
-                           uint32_t *offsets, const double *models, float *shadow_compact, double *compact64,
-                           BatchCtl *ctl, const Shadow16Params &s16, const PointSet &pts, hipStream_t stream);
 // Everything k_score_mfma needs for `capacity` hypotheses that sit in `models` in list order `slots` (diagnostic entry
 // pl_debug_score_stream; the main loop gets the same from launch_compact2): live list + rank + ctl->num_live, the operand rows
 // of the live hypotheses and of the correspondences (all fields of s16 set).
@@ -263,10 +252,6 @@ hipError_t launch_abs16(BatchCtl *ctl, const uint32_t *slots, const double *mode
 hipError_t launch_gather_models(BatchCtl *ctl, const uint32_t *slots, const double *models, uint32_t capacity,
                                 float *shadow_compact, double *compact64, hipStream_t stream);
 hipError_t launch_finalize(const FinalizeArgs &f, hipStream_t stream);
-hipError_t launch_finalize_records(const FinalizeArgs &f, const uint32_t *slots, const double *models,
-                                   uint32_t *blk_max, double *blk_min, uint32_t init_max, double init_min,
-                                   RecordMeta *rec_meta, double *rec_models, uint32_t rec_cap, BatchCtl *ctl,
-                                   RecordMeta *host_meta, double *host_models, uint32_t host_cap, hipStream_t stream);
 
 // ---- groups of problems: one launch sequence for MANY independent problems (BASELINE config 4) ----------------------
 // The problem index is a grid dimension (blockIdx.z) and every kernel fetches its arguments from a device-resident
@@ -276,16 +261,17 @@ struct SampleArgs {
     uint64_t seed, pos_base, N;
     uint32_t B, M;
     uint8_t *delta;
-    uint64_t *flagbits;
+    uint64_t *flagbits; // >= ceil(M / 64) words
     uint32_t *positions;
     BatchCtl *ctl;
-    uint32_t zero_words, pad;
+    uint32_t zero_words, pad; // zero_words: 32-bit words starting at `ctl` (control block + the tables behind it) that the
+                              // first kernel zeroes itself (0: the caller has done it)
 };
 struct CompactArgs {
     const uint32_t *num_models;
     uint32_t B;
     int32_t maxm;
-    uint32_t *blk_tot, *slots, *offsets;
+    uint32_t *blk_tot, *slots, *offsets; // blk_tot is followed by the generators' NaN-model table (ceil(B / 1024) + 1 entries each)
     const double *models;
     float *shadow;
     double *compact64;
@@ -308,6 +294,12 @@ struct RecordsArgs {
     double *host_models;
     uint32_t host_cap, pad;
 };
+// The single-problem forms of the three launches (the other kernels of a batch step: launch_generate, launch_score,
+// launch_score_seq).  counted: blk_tot already holds the per-block model counts (GenerateArgs.blk_tot), otherwise they are
+// counted first; pts: the problem's correspondences (read where s16.points16 is set)
+hipError_t launch_sample_positions(int K, const SampleArgs &a, hipStream_t stream);
+hipError_t launch_compact2(const CompactArgs &a, bool counted, const PointSet &pts, hipStream_t stream);
+hipError_t launch_finalize_records(const RecordsArgs &a, hipStream_t stream);
 struct MaskArgs {
     PointSet pts;
     const double *model;
@@ -326,7 +318,8 @@ struct SelectArgs {
     const uint32_t *fetch_src; // optional: one device word (a stopped problem's hypothesis offset) ...
     uint32_t *fetch_dst;       // ... copied to this (pinned host) address by the same launch
 };
-struct GroupArgs { // everything the kernels of one batch step need for ONE problem of the group
+struct GroupArgs { // everything the kernels of one batch step need for ONE problem: an entry of a group's table, or the
+                   // arguments of the single-problem launches (filled by wire_batch_step, driver.cc)
     uint32_t active;   // 0: the slot takes no part in this step
     uint32_t use_mfma; // absolute pose: scored by k_score_mfma (otherwise k_score_queue)
     uint32_t chunks, slices;
