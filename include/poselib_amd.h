@@ -347,6 +347,27 @@ int pl_debug_group_slices(int kind, uint32_t n_points, uint32_t iterations, uint
  * overflow flag (an iteration had more solutions than slots: its count is 0). */
 int pl_debug_radial1d_generate(pl_problem *p, const uint32_t *samples, size_t num_iters, uint32_t slots_per_iter, double *models,
                                uint32_t *num_models, uint32_t *totals);
+/* Diagnostic: the hypothesis generator of the main loop on its own - the kernels a batch step launches, wired as a batch step wires
+ * them - for a resident problem of kind 0, 1, 2, 3 or 5 or a tangent problem, with every iteration's output copied back.  tests/
+ * compares them with the reference estimators' generate_models hypothesis by hypothesis.
+ * Samples: either `samples` (num_iters x K indices, K = the kind's minimal sample; each must be < the problem's size) or `positions`
+ * (num_iters entries: draws consumed before each iteration, relative to pos_base) with `seed` for the device's own sampler; exactly one
+ * of the two is non-NULL.  slots_per_iter: record slots per iteration, 1 .. the kind's maximum (4, 40, 3, 1; kind 5: 4); an iteration
+ * with more solutions sets the overflow flag and counts 0.  real_focal_check: kind 2 only.
+ * route 0: the single-problem launch (kind 1 and tangent problems: the staged 5-point generator); 1: the single-kernel 5-point
+ * generator (kind 1 only); 2: the group form (kinds 0 - 3) over a table of three slots - slot 0 inactive, slot 1 this problem with all
+ * num_iters iterations, slot 2 this problem with its first ceil(num_iters / 3) iterations and output buffers of its own - launched for
+ * num_iters iterations.  Routes 0 and 1 have one member, route 2 two (slots 1 and 2); member m's outputs follow member m - 1's:
+ *   models     members x num_iters x slots_per_iter records of 24 doubles, zeroed before the launch
+ *   num_models members x num_iters, 0xffffffff before the launch
+ *   nan_bits   members x num_iters, may be NULL, written for kind 0 only (bit m: record m holds a NaN), 0xffffffff before the launch
+ *   blk_tot, blk_nan  members x ceil(num_iters / 1024): models and NaN models per block of 1024 iterations as the generator counted them
+ *   flags[3]   overflow flag of member 0, of member 1, and (route 2) the number of words the inactive slot's buffers changed in.
+ * PL_ERR_INVALID: num_iters 0 or above 2^20, slots_per_iter out of range, an index beyond the problem, fewer correspondences than K with
+ * `positions`, route 1 for another kind than 1, route 2 for a tangent or kind-5 problem. */
+int pl_debug_generate(pl_problem *p, const uint32_t *samples, uint64_t seed, uint64_t pos_base, const uint32_t *positions, size_t num_iters,
+                      uint32_t slots_per_iter, int real_focal_check, int route, double *models, uint32_t *num_models, uint32_t *nan_bits,
+                      uint32_t *blk_tot, uint32_t *blk_nan, uint32_t *flags);
 /* Diagnostic entry (no counterpart in the reference): `n` models - pl_camera_pose[n] for kinds 0/1, double[n][9]
  * column-major for kinds 2/3 - through the STREAMING scorer of the batched main loop, i.e. through the conservative
  * pre-filters (fp16/MFMA or fp32) in front of the exact fp64 evaluation, instead of the sequential scorer behind

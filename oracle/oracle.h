@@ -67,6 +67,13 @@ typedef struct {
 /* ---- sampler / loop control ---- */
 void orc_sampler_draw(uint64_t seed, uint64_t N, uint64_t K, uint64_t n_samples, int32_t prosac,
                       uint64_t max_prosac_iterations, uint64_t *out_idx /* n_samples*K */, uint64_t *state_after);
+/* the uniform sampler's samples and the draws consumed before each of them */
+void orc_sampler_draw_positions(uint64_t seed, uint64_t N, uint64_t K, uint64_t n_samples, uint64_t *out_idx /* n_samples*K */,
+                                uint64_t *out_pos /* n_samples */);
+/* generate_models of the estimators (kind 0 absolute pose, 1 relative pose, 2 fundamental, 3 homography) on caller-supplied samples
+ * of a point set: see src/c_api.cc */
+int64_t orc_generate_models(int32_t kind, const double *a, const double *b, size_t n, const uint64_t *samples, size_t B,
+                            int32_t real_focal_check, uint32_t *counts, double *models, double *sample_in);
 int32_t orc_random_int(uint64_t *state);
 double orc_all_inlier_probability(uint64_t inliers, uint64_t N, uint64_t K);
 uint64_t orc_dynamic_max_iter(uint64_t inliers, uint64_t N, uint64_t K, double log_fail, double mult, uint64_t min_it,

@@ -151,6 +151,51 @@ void orc_sampler_draw(uint64_t seed, uint64_t N, uint64_t K, uint64_t n_samples,
     if (state_after)
         *state_after = s.state;
 }
+// ... and the draws the uniform sampler had consumed BEFORE each sample (the position table of the device's sampler)
+void orc_sampler_draw_positions(uint64_t seed, uint64_t N, uint64_t K, uint64_t n_samples, uint64_t *out_idx, uint64_t *out_pos) {
+    RansacOptions o;
+    o.seed = seed;
+    Sampler s(N, K, o);
+    uint64_t walked = seed, pos = 0; // one splitmix64 step adds the same constant to the state: count the steps
+    for (uint64_t i = 0; i < n_samples; ++i) {
+        out_pos[i] = pos;
+        s.next(out_idx + i * K);
+        while (walked != s.state) {
+            splitmix_next_int(walked);
+            ++pos;
+        }
+    }
+}
+// The estimators' generate_models (estimators.cc) on caller-supplied samples.  kind 0: a = 2-D points (n x 2), b = 3-D points
+// (n x 3); kinds 1, 2, 3: a, b = the two images' points (n x 2).  samples: B x K indices below n.  counts: B; models: room for
+// B x max_models x (7 pose | 9 matrix, row-major) doubles, filled densely in emission order; sample_in (optional): B x 2 K x 3, the
+// solver's input of every sample ([first set K x 3][second set K x 3], the layout of the device's solver batches).  Returns the
+// number of models, or -1 for an index beyond n.
+int64_t orc_generate_models(int32_t kind, const double *a, const double *b, size_t n, const uint64_t *samples, size_t B,
+                            int32_t real_focal_check, uint32_t *counts, double *models, double *sample_in) {
+    static const int Ks[4] = {3, 5, 7, 4};
+    if (kind < 0 || kind > 3)
+        return -1;
+    const size_t K = Ks[kind];
+    for (size_t i = 0; i < B * K; ++i)
+        if (samples[i] >= n)
+            return -1;
+    const std::vector<V2> a2 = pts2(a, n);
+    const std::vector<V2> b2 = kind == 0 ? std::vector<V2>() : pts2(b, n);
+    const std::vector<V3> b3 = kind == 0 ? pts3(b, n) : std::vector<V3>();
+    std::vector<V3> first(sample_in ? B * K : 0), second(sample_in ? B * K : 0);
+    std::vector<double> out;
+    const size_t total = generate_models_on_samples(kind, a2, b2, b3, samples, B, real_focal_check != 0, counts, &out,
+                                                    sample_in ? first.data() : nullptr, sample_in ? second.data() : nullptr);
+    std::memcpy(models, out.data(), sizeof(double) * out.size());
+    for (size_t i = 0; sample_in && i < B; ++i)
+        for (size_t k = 0; k < K; ++k) {
+            double *f = sample_in + (i * 2 * K + k) * 3, *g = sample_in + (i * 2 * K + K + k) * 3;
+            f[0] = first[i * K + k].x, f[1] = first[i * K + k].y, f[2] = first[i * K + k].z;
+            g[0] = second[i * K + k].x, g[1] = second[i * K + k].y, g[2] = second[i * K + k].z;
+        }
+    return static_cast<int64_t>(total);
+}
 int32_t orc_random_int(uint64_t *state) { return splitmix_next_int(*state); }
 double orc_all_inlier_probability(uint64_t inliers, uint64_t N, uint64_t K) {
     return prob_all_inlier_sample(inliers, N, K);

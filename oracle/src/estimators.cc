@@ -20,6 +20,12 @@ BundleOptions lo_options(double max_error) { // absolute_pose.cc:61-64 (same in 
     return b;
 }
 
+// generate_models on a caller's sample (generate_models_on_samples): the solver's input as the estimator built it
+void keep_sample(const V3 *a, const V3 *b, int K, V3 *first, V3 *second) {
+    for (int k = 0; k < K && first; ++k)
+        first[k] = a[k], second[k] = b[k];
+}
+
 struct AbsEstimator {
     const AbsolutePoseOptions &opt;
     const std::vector<V2> &x;
@@ -31,11 +37,15 @@ struct AbsEstimator {
     void generate(std::vector<Pose> *models) {
         uint64_t s[3];
         sampler.next(s);
+        generate_from(s, models);
+    }
+    void generate_from(const uint64_t *s, std::vector<Pose> *models, V3 *first = nullptr, V3 *second = nullptr) const {
         V3 xs[3], Xs[3];
         for (int k = 0; k < 3; ++k) {
             xs[k] = bearing(x[s[k]]);
             Xs[k] = X[s[k]];
         }
+        keep_sample(xs, Xs, 3, first, second);
         Pose sol[4];
         const int n = p3p(xs, Xs, sol);
         models->assign(sol, sol + n);
@@ -157,11 +167,15 @@ struct RelEstimator {
     void generate(std::vector<Pose> *models) {
         uint64_t s[5];
         sampler.next(s);
+        generate_from(s, models);
+    }
+    void generate_from(const uint64_t *s, std::vector<Pose> *models, V3 *first = nullptr, V3 *second = nullptr) const {
         V3 a[5], b[5];
         for (int k = 0; k < 5; ++k) {
             a[k] = bearing(x1[s[k]]);
             b[k] = bearing(x2[s[k]]);
         }
+        keep_sample(a, b, 5, first, second);
         Pose sol[40];
         const int n = relpose_5pt(a, b, sol);
         models->assign(sol, sol + n);
@@ -258,11 +272,15 @@ struct FundEstimator {
     void generate(std::vector<M3> *models) {
         uint64_t s[7];
         sampler.next(s);
+        generate_from(s, models);
+    }
+    void generate_from(const uint64_t *s, std::vector<M3> *models, V3 *first = nullptr, V3 *second = nullptr) const {
         V3 a[7], b[7];
         for (int k = 0; k < 7; ++k) {
             a[k] = bearing(x1[s[k]]);
             b[k] = bearing(x2[s[k]]);
         }
+        keep_sample(a, b, 7, first, second);
         M3 sol[3];
         const int n = relpose_7pt(a, b, sol);
         models->assign(sol, sol + n);
@@ -288,11 +306,15 @@ struct HomEstimator {
     void generate(std::vector<M3> *models) {
         uint64_t s[4];
         sampler.next(s);
+        generate_from(s, models);
+    }
+    void generate_from(const uint64_t *s, std::vector<M3> *models, V3 *first = nullptr, V3 *second = nullptr) const {
         V3 a[4], b[4];
         for (int k = 0; k < 4; ++k) {
             a[k] = bearing(x1[s[k]]);
             b[k] = bearing(x2[s[k]]);
         }
+        keep_sample(a, b, 4, first, second);
         models->clear();
         M3 H;
         if (homography_4pt(a, b, &H, true) > 0)
@@ -369,6 +391,54 @@ RansacStats ransac_homography(const std::vector<V2> &x1, const std::vector<V2> &
     const RansacStats st = lo_ransac(est, opt.ransac, best, trace);
     inliers_homography(*best, x1, x2, opt.max_error * opt.max_error, inliers);
     return st;
+}
+
+// The estimators' generate_models on caller-supplied minimal samples (sample i: K indices at samples + i * K) instead of the
+// sampler's.  counts[i]: models of sample i; models: their 7 (pose: q, t) or 9 (matrix, row-major) doubles in emission order, sample
+// after sample; first / second (optional, B x K each): the solver's input vectors of every sample.  Returns the number of models.
+size_t generate_models_on_samples(int kind, const std::vector<V2> &a2, const std::vector<V2> &b2, const std::vector<V3> &b3,
+                                  const uint64_t *samples, size_t B, bool real_focal_check, uint32_t *counts,
+                                  std::vector<double> *models, V3 *first, V3 *second) {
+    static const int Ks[4] = {3, 5, 7, 4};
+    const int K = Ks[kind];
+    AbsolutePoseOptions ao;
+    RelativePoseOptions ro;
+    ro.real_focal_check = real_focal_check;
+    HomographyOptions ho;
+    AbsEstimator abs_est(ao, a2, b3);
+    RelEstimator rel_est(ro, a2, b2);
+    FundEstimator fund_est(ro, a2, b2);
+    HomEstimator hom_est(ho, a2, b2);
+    std::vector<Pose> poses;
+    std::vector<M3> mats;
+    size_t total = 0;
+    models->clear();
+    for (size_t i = 0; i < B; ++i) {
+        const uint64_t *s = samples + i * K;
+        V3 *f = first ? first + i * K : nullptr, *g = second ? second + i * K : nullptr;
+        poses.clear();
+        mats.clear();
+        if (kind == 0)
+            abs_est.generate_from(s, &poses, f, g);
+        else if (kind == 1)
+            rel_est.generate_from(s, &poses, f, g);
+        else if (kind == 2)
+            fund_est.generate_from(s, &mats, f, g);
+        else
+            hom_est.generate_from(s, &mats, f, g);
+        counts[i] = static_cast<uint32_t>(poses.size() + mats.size());
+        total += counts[i];
+        for (const Pose &p : poses) {
+            for (int k = 0; k < 4; ++k)
+                models->push_back(p.q[k]);
+            models->push_back(p.t.x), models->push_back(p.t.y), models->push_back(p.t.z);
+        }
+        for (const M3 &M : mats)
+            for (int r = 0; r < 3; ++r)
+                for (int cidx = 0; cidx < 3; ++cidx)
+                    models->push_back(M.m[r][cidx]);
+    }
+    return total;
 }
 
 // ------------------------------------------------------------------------------------ front-ends

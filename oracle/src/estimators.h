@@ -51,6 +51,12 @@ RansacStats ransac_fundamental(const std::vector<V2> &x1, const std::vector<V2> 
 RansacStats ransac_homography(const std::vector<V2> &x1, const std::vector<V2> &x2, const HomographyOptions &opt,
                               M3 *best, std::vector<char> *inliers, LoopTrace *trace = nullptr);
 
+// generate_models of the four hot estimators (kind 0 absolute pose: a2 = 2-D points, b3 = 3-D points; 1 relative pose, 2 fundamental,
+// 3 homography: a2, b2 = the two images' points) on caller-supplied minimal samples: see estimators.cc
+size_t generate_models_on_samples(int kind, const std::vector<V2> &a2, const std::vector<V2> &b2, const std::vector<V3> &b3,
+                                  const uint64_t *samples, size_t B, bool real_focal_check, uint32_t *counts,
+                                  std::vector<double> *models, V3 *first, V3 *second);
+
 RansacStats estimate_absolute_pose(const std::vector<V2> &p2d, const std::vector<V3> &p3d, AbsolutePoseOptions opt,
                                    Image *image, std::vector<char> *inliers);
 RansacStats estimate_relative_pose(const std::vector<V2> &x1, const std::vector<V2> &x2, const Camera &cam1,

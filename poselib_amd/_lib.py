@@ -163,6 +163,7 @@ def _declare(L):
         "pl_debug_radial1d_chunk": (cint, []),
         "pl_debug_group_slices": (cint, [cint, C.c_uint32, C.c_uint32, C.c_uint32]),
         "pl_debug_radial1d_generate": (cint, [vp, vp, sz, C.c_uint32, vp, vp, vp]),
+        "pl_debug_generate": (cint, [vp, vp, u64, u64, vp, sz, C.c_uint32, cint, cint, vp, vp, vp, vp, vp, vp]),
         "pl_estimate_1D_radial_absolute_pose": (cint, [vp, vp, sz, opt, pose, vp, stats]),
         "pl_ransac_1D_radial_pnp": (cint, [vp, vp, sz, opt, pose, vp, stats]),
         "pl_p5lp_radial": (cint, [vp, vp, P(CameraPose), P(cint)]),
@@ -210,7 +211,7 @@ EXPORTED_SYMBOLS = [
     "pl_ransac_batch", "pl_debug_device_math", "pl_debug_device_math2", "pl_ransac_pnpf", "pl_ransac_shared_focal_relpose", "pl_refine_shared_focal_relpose",
     "pl_estimate_shared_focal_relative_pose", "pl_solve_focal_batch", "pl_p35pf", "pl_relpose_6pt_shared_focal", "pl_set_lm_mode",
     "pl_abi_version", "pl_problem_create_tangent", "pl_debug_inlier_mask", "pl_debug_tangent_chunk",
-    "pl_p5lp_radial", "pl_debug_radial1d_chunk", "pl_debug_radial1d_generate", "pl_debug_group_slices",
+    "pl_p5lp_radial", "pl_debug_radial1d_chunk", "pl_debug_radial1d_generate", "pl_debug_group_slices", "pl_debug_generate",
     # (pl_estimate_1D_radial_absolute_pose and pl_ransac_1D_radial_pnp carry the reference's capital D: declared above, exported by the
     # library, but outside the lower-case pattern tests/test_cabi_surface.py lists the header's symbols with)
 ]

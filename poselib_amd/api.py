@@ -762,6 +762,42 @@ def radial1d_generate(problem, samples, slots_per_iter=4):
     return out[:, :, :16].copy(), cnt, tuple(int(v) for v in tot)
 
 
+def debug_generate(problem, samples=None, seed=0, pos_base=0, positions=None, slots_per_iter=None, real_focal_check=False, route=0):
+    """Diagnostic (pl_debug_generate): the generator of the main loop on a resident problem (Problem of kind 0, 1, 2, 3, 5 or a
+    TangentProblem).  Either explicit `samples` (B, K) or `positions` (B,) of the device's own sampler with `seed` / `pos_base`.
+    route 0: single-problem launch, 1: single-kernel 5-point generator, 2: group form (two members: all B iterations, and the first
+    ceil(B / 3) with buffers of their own).  Returns a list with one dict per member: records (B, slots, 24), num_models (B,),
+    nan_bits (B,), blk_tot / blk_nan (ceil(B / 1024),), overflow; the group form's dicts also carry inactive_writes."""
+    tangent = isinstance(problem, TangentProblem)
+    kind = problem.kind
+    K = {KIND_ABS: 3, KIND_REL: 5, KIND_FUND: 7, KIND_HOM: 4, KIND_RAD1D: 5}[kind]
+    maxm = {KIND_ABS: 4, KIND_REL: 40, KIND_FUND: 3, KIND_HOM: 1, KIND_RAD1D: 4}[kind]
+    slots = maxm if slots_per_iter is None else int(slots_per_iter)
+    idx = None if samples is None else np.ascontiguousarray(samples, dtype=np.uint32).reshape(-1, K)
+    pos = None if positions is None else np.ascontiguousarray(positions, dtype=np.uint32).reshape(-1)
+    B = idx.shape[0] if idx is not None else 0 if pos is None else pos.shape[0]
+    members = 2 if route == 2 else 1
+    nblk = (B + 1023) // 1024
+    rec = np.zeros((members, B, max(slots, 1), 24))
+    cnt = np.zeros((members, max(B, 1)), dtype=np.uint32)
+    bits = np.zeros((members, max(B, 1)), dtype=np.uint32)
+    tot = np.zeros((members, max(nblk, 1)), dtype=np.uint32)
+    nan = np.zeros((members, max(nblk, 1)), dtype=np.uint32)
+    flags = np.zeros(3, dtype=np.uint32)
+    L.check(L.lib().pl_debug_generate(problem._h, None if idx is None else _ptr(idx), C.c_uint64(int(seed)), C.c_uint64(int(pos_base)),
+                                      None if pos is None else _ptr(pos), C.c_size_t(B), C.c_uint32(slots), C.c_int(int(bool(real_focal_check))),
+                                      C.c_int(int(route)), _ptr(rec), _ptr(cnt), _ptr(bits) if kind == KIND_ABS and not tangent else None,
+                                      _ptr(tot), _ptr(nan), _ptr(flags)))
+    out = []
+    for m in range(members):
+        d = {"records": rec[m], "num_models": cnt[m, :B], "nan_bits": bits[m, :B], "blk_tot": tot[m, :nblk], "blk_nan": nan[m, :nblk],
+             "overflow": int(flags[m])}
+        if route == 2:
+            d["inactive_writes"] = int(flags[2])
+        out.append(d)
+    return out
+
+
 def inlier_mask(problem, model, max_error):
     """Diagnostic (pl_debug_inlier_mask): the inlier mask of one model on a resident problem."""
     mask = np.zeros(max(problem.n, 1), dtype=np.uint8)
@@ -830,9 +866,10 @@ def homography_4pt(x1, x2):
     return [out.reshape(3, 3).T.copy()] if n else []
 
 
-def solve_batch(kind: int, first, second):
+def solve_batch(kind: int, first, second, full_records: bool = False):
     """Many minimal problems at once, one GPU lane each.  first/second: (B, K, 3).  Returns
-    (records (B, max_models, 16), counts (B,)) — record layout: q[4] t[3] M[9 row-major]."""
+    (records (B, max_models, 16), counts (B,)) — record layout: q[4] t[3] M[9 row-major]; full_records: all 24 doubles of every
+    record, the fp32 shadow of the scoring pre-filters included."""
     first = np.ascontiguousarray(first, dtype=np.float64)
     second = np.ascontiguousarray(second, dtype=np.float64)
     B, K = first.shape[0], first.shape[1]
@@ -841,7 +878,7 @@ def solve_batch(kind: int, first, second):
     out = np.zeros((B, maxm, 24))  # record pitch: 16 fp64 fields + fp32 shadow used by the scoring pre-filter
     cnt = np.zeros(B, dtype=np.uint32)
     L.check(L.lib().pl_solve_batch(kind, _ptr(inp), C.c_size_t(B), _ptr(out), _ptr(cnt)))
-    return out[:, :, :16].copy(), cnt
+    return (out if full_records else out[:, :, :16].copy()), cnt
 
 
 def undistort_points(camera, points2D):

@@ -2877,65 +2877,197 @@ int pl_ransac_1D_radial_pnp(const double *x, const double *X, size_t n, const pl
     return ransac_oneshot(EST_RAD1D, x, X, n, opt, pose, inliers, stats);
 }
 int pl_debug_radial1d_chunk(void) { return radial1d_score_chunk(); }
-// Diagnostic: the generator kernel of a resident kind-5 problem (k_generate<EST_RAD1D>) on caller-supplied minimal samples - the
-// path PROSAC's host-drawn samples take - with `slots_per_iter` record slots per iteration.  models: num_iters x slots_per_iter x 24
-// doubles (zero where no model was written), num_models: num_iters, totals: models counted per block table, models with the NaN
-// flag, BatchCtl.gen_overflow.
-int pl_debug_radial1d_generate(pl_problem *p, const uint32_t *samples, size_t num_iters, uint32_t slots_per_iter, double *models,
-                               uint32_t *num_models, uint32_t *totals) {
-    if (!p || !samples || !models || !num_models || !totals)
+// Diagnostic: the hypothesis generator of a resident problem on its own, wired by wire_batch_step as a batch step wires it, with the
+// outputs of every iteration copied back (the header describes the arguments).  Route 0: the single-problem launch (kinds 1 and
+// tangent: the staged generator), 1: the single-kernel 5-point generator, 2: the group form over a table of three slots - inactive,
+// this problem with all its iterations, this problem with its first ceil(B / 3) iterations - launched with max_B = B.  Records are
+// zeroed before the launch, counts and NaN flags set to 0xffffffff: an entry no lane wrote keeps that value.
+namespace {
+struct DebugGenSet { // the device buffers one slot of the launch writes; `own`: allocated here (slots 0 and 2 of the group form)
+    double *models = nullptr;
+    uint32_t *num_models = nullptr, *nan_bits = nullptr;
+    BatchCtl *ctl = nullptr;
+    char *stage = nullptr;
+    bool own = false;
+    ~DebugGenSet() {
+        if (own)
+            for (void *q : {(void *)models, (void *)num_models, (void *)nan_bits, (void *)ctl, (void *)stage})
+                if (q)
+                    (void)hipFree(q);
+    }
+};
+} // namespace
+int pl_debug_generate(pl_problem *p, const uint32_t *samples, uint64_t seed, uint64_t pos_base, const uint32_t *positions, size_t num_iters,
+                      uint32_t slots_per_iter, int real_focal_check, int route, double *models, uint32_t *num_models, uint32_t *nan_bits,
+                      uint32_t *blk_tot, uint32_t *blk_nan, uint32_t *flags) {
+    if (!p || !models || !num_models || !blk_tot || !blk_nan || !flags)
         return fail(PL_ERR_INVALID, "null argument");
-    if (p->kind != EST_RAD1D)
-        return fail(PL_ERR_INVALID, "not a 1D-radial problem");
-    if (slots_per_iter < 1 || slots_per_iter > (uint32_t)max_models(EST_RAD1D) || num_iters == 0 || num_iters > (1u << 20))
-        return fail(PL_ERR_INVALID, "slots_per_iter must be 1..4, num_iters 1..2^20");
-    for (size_t i = 0; i < 5 * num_iters; ++i)
-        if (samples[i] >= p->n)
-            return fail(PL_ERR_INVALID, "sample index beyond the problem's correspondences");
+    if ((samples != nullptr) == (positions != nullptr))
+        return fail(PL_ERR_INVALID, "give explicit samples or draw positions, not both");
+    const int kind = p->kind;
+    if (kind != EST_ABS && kind != EST_REL && kind != EST_FUND && kind != EST_HOM && kind != EST_RELT && kind != EST_RAD1D)
+        return fail(PL_ERR_INVALID, "problem kind has no generator");
+    if (route < 0 || route > 2 || (route == 1 && kind != EST_REL))
+        return fail(PL_ERR_INVALID, "route: 0 single launch, 1 single-kernel generator (kind 1 only), 2 group form");
+    if (route == 2 && (kind == EST_RELT || kind == EST_RAD1D))
+        return fail(PL_ERR_INVALID, "tangent and 1D-radial problems have no group form");
+    if (slots_per_iter < 1 || slots_per_iter > (uint32_t)max_models(kind) || num_iters == 0 || num_iters > (1u << 20))
+        return fail(PL_ERR_INVALID, "slots_per_iter must be 1..max_models(kind), num_iters 1..2^20");
+    const uint32_t K = (uint32_t)sample_size(kind);
+    if (samples) {
+        for (size_t i = 0; i < (size_t)K * num_iters; ++i)
+            if (samples[i] >= p->n)
+                return fail(PL_ERR_INVALID, "sample index beyond the problem's correspondences");
+    } else if (p->n < K) {
+        return fail(PL_ERR_INVALID, "fewer correspondences than a minimal sample");
+    }
     Context *c;
     int rc = get_context(&c);
     if (rc != PL_OK)
         return rc;
     if (p->device != c->device)
         return fail(PL_ERR_INVALID, "problem lives on another device than the calling thread's");
-    const uint32_t B = (uint32_t)num_iters, nblk = (B + 1023) / 1024;
-    const size_t rec_bytes = sizeof(double) * kModelStride * (size_t)B * slots_per_iter;
-    const size_t ctl_bytes = sizeof(BatchCtl) + sizeof(uint32_t) * (2 * (size_t)nblk + 2);
-    HIP_TRY(c->samples.ensure(sizeof(uint32_t) * 5 * B));
-    HIP_TRY(c->models.ensure(rec_bytes));
-    HIP_TRY(c->num_models.ensure(sizeof(uint32_t) * B));
-    HIP_TRY(c->ctl.ensure(ctl_bytes));
-    HIP_TRY(hipMemsetAsync(c->ctl.p, 0, ctl_bytes, c->stream));
-    HIP_TRY(hipMemsetAsync(c->models.p, 0, rec_bytes, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->samples.p, samples, sizeof(uint32_t) * 5 * B, hipMemcpyHostToDevice, c->stream));
-    uint32_t *blk_tot = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(c->ctl.p) + sizeof(BatchCtl));
-    GenerateArgs ga;
-    ga.pts = p->ps;
-    ga.seed = 0;
-    ga.pos_base = 0;
-    ga.positions = nullptr;
-    ga.samples = c->samples.as<uint32_t>();
-    ga.num_iters = B;
-    ga.slots_per_iter = slots_per_iter;
-    ga.ctl = c->ctl.as<BatchCtl>();
-    ga.models = c->models.as<double>();
-    ga.num_models = c->num_models.as<uint32_t>();
-    ga.real_focal_check = 0;
-    ga.blk_tot = blk_tot;
-    ga.blk_nan = blk_tot + nblk;
-    HIP_TRY(launch_generate(EST_RAD1D, ga, c->stream));
-    std::vector<unsigned char> hctl(ctl_bytes);
-    HIP_TRY(hipMemcpyAsync(models, c->models.p, rec_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(num_models, c->num_models.p, sizeof(uint32_t) * B, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(hctl.data(), c->ctl.p, ctl_bytes, hipMemcpyDeviceToHost, c->stream));
+    const uint32_t B = (uint32_t)num_iters, nblk = batch_blocks(B);
+    const int members = route == 2 ? 2 : 1;
+    BatchRun run{};
+    run.kind = kind;
+    run.pts = p->ps;
+    run.seed = seed, run.pos = pos_base;
+    run.real_focal_check = real_focal_check;
+    run.explicit_samples = samples != nullptr;
+    BatchShape s{};
+    s.B = s.Bl = B, s.slots = slots_per_iter, s.chunks = 1;
+    s.use_mfma = kind == EST_ABS; // (the scorer that reads the generator's NaN flags: wire_batch_step hands them over only then)
+    const BatchSizes z = batch_step_sizes(kind, s);
+    BatchBuffers bb;
+    rc = context_batch_buffers(c, z, bb);
+    if (rc != PL_OK)
+        return rc;
+    // slot 1 writes the Context's buffers; the group form's slots 2 and 0 get output buffers of their own, of the same size
+    DebugGenSet set[3];
+    set[0].models = bb.models, set[0].num_models = bb.num_models, set[0].nan_bits = bb.nan_bits, set[0].ctl = bb.ctl, set[0].stage = bb.gen_stage;
+    const int nsets = route == 2 ? 3 : 1;
+    for (int k = 1; k < nsets; ++k) {
+        set[k].own = true;
+        HIP_TRY(hipMalloc((void **)&set[k].models, z.models));
+        HIP_TRY(hipMalloc((void **)&set[k].num_models, z.num_models));
+        if (z.nan_bits)
+            HIP_TRY(hipMalloc((void **)&set[k].nan_bits, z.nan_bits));
+        HIP_TRY(hipMalloc((void **)&set[k].ctl, z.ctl));
+        if (z.gen_stage)
+            HIP_TRY(hipMalloc((void **)&set[k].stage, z.gen_stage));
+    }
+    for (int k = 0; k < nsets; ++k) {
+        HIP_TRY(hipMemsetAsync(set[k].models, 0, z.models, c->stream));
+        HIP_TRY(hipMemsetAsync(set[k].num_models, 0xff, z.num_models, c->stream));
+        if (z.nan_bits)
+            HIP_TRY(hipMemsetAsync(set[k].nan_bits, 0xff, z.nan_bits, c->stream));
+        HIP_TRY(hipMemsetAsync(set[k].ctl, 0, z.ctl, c->stream));
+    }
+    if (samples)
+        HIP_TRY(hipMemcpyAsync(bb.samples, samples, sizeof(uint32_t) * K * B, hipMemcpyHostToDevice, c->stream));
+    else
+        HIP_TRY(hipMemcpyAsync(bb.positions, positions, sizeof(uint32_t) * B, hipMemcpyHostToDevice, c->stream));
+    // the arguments of slot `k`'s generator over `iters` iterations: the batch step's own wiring on that slot's output buffers
+    auto wire = [&](GroupArgs &a, const DebugGenSet &o, uint32_t iters) {
+        BatchBuffers b = bb;
+        b.models = o.models, b.num_models = o.num_models, b.nan_bits = o.nan_bits, b.ctl = o.ctl, b.gen_stage = o.stage;
+        BatchShape sk = s;
+        sk.Bl = iters;
+        wire_batch_step(a, run, sk, b);
+        if (route == 1)
+            a.gen.stage = nullptr;
+    };
+    const uint32_t iters_of[2] = {B, (B + 2) / 3};
+    struct Scratch { // freed on every path
+        void *p = nullptr;
+        ~Scratch() {
+            if (p)
+                (void)hipFree(p);
+        }
+    } dtable;
+    GroupArgs ha[3];
+    if (route == 2) {
+        wire(ha[0], set[2], B);
+        ha[0].active = 0;
+        wire(ha[1], set[0], iters_of[0]);
+        wire(ha[2], set[1], iters_of[1]);
+        HIP_TRY(hipMalloc(&dtable.p, sizeof(ha)));
+        HIP_TRY(hipMemcpyAsync(dtable.p, ha, sizeof(ha), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(launch_group_generate(kind, static_cast<const GroupArgs *>(dtable.p), B, 3, c->stream));
+    } else {
+        wire(ha[1], set[0], B);
+        HIP_TRY(launch_generate(kind, ha[1].gen, c->stream));
+    }
+    const size_t rec_doubles = (size_t)kModelStride * B * slots_per_iter;
+    std::vector<unsigned char> hctl[3];
+    for (int k = 0; k < nsets; ++k)
+        hctl[k].resize(z.ctl);
+    for (int m = 0; m < members; ++m) {
+        HIP_TRY(hipMemcpyAsync(models + m * rec_doubles, set[m].models, sizeof(double) * rec_doubles, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(num_models + (size_t)m * B, set[m].num_models, sizeof(uint32_t) * B, hipMemcpyDeviceToHost, c->stream));
+        if (nan_bits && z.nan_bits)
+            HIP_TRY(hipMemcpyAsync(nan_bits + (size_t)m * B, set[m].nan_bits, sizeof(uint32_t) * B, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(hctl[m].data(), set[m].ctl, z.ctl, hipMemcpyDeviceToHost, c->stream));
+    }
+    std::vector<double> idle_models;
+    std::vector<uint32_t> idle_words;
+    if (route == 2) { // what the inactive slot's launch left of its buffers
+        idle_models.resize(rec_doubles);
+        idle_words.resize(2 * (size_t)B);
+        HIP_TRY(hipMemcpyAsync(idle_models.data(), set[2].models, sizeof(double) * rec_doubles, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(idle_words.data(), set[2].num_models, sizeof(uint32_t) * B, hipMemcpyDeviceToHost, c->stream));
+        if (z.nan_bits)
+            HIP_TRY(hipMemcpyAsync(idle_words.data() + B, set[2].nan_bits, sizeof(uint32_t) * B, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(hctl[2].data(), set[2].ctl, z.ctl, hipMemcpyDeviceToHost, c->stream));
+    }
     HIP_TRY(wait_stream(c));
-    BatchCtl ctl;
-    std::memcpy(&ctl, hctl.data(), sizeof(ctl));
-    const uint32_t *tab = reinterpret_cast<const uint32_t *>(hctl.data() + sizeof(BatchCtl));
+    flags[0] = flags[1] = flags[2] = 0;
+    for (int m = 0; m < members; ++m) { // the tables behind the control block, laid out for the member's own iterations
+        BatchCtl ctl;
+        std::memcpy(&ctl, hctl[m].data(), sizeof(ctl));
+        flags[m] = ctl.gen_overflow;
+        const uint32_t nb = batch_blocks(iters_of[m]);
+        const uint32_t *tab = reinterpret_cast<const uint32_t *>(hctl[m].data() + sizeof(BatchCtl));
+        for (uint32_t b = 0; b < nblk; ++b) {
+            blk_tot[(size_t)m * nblk + b] = b < nb ? tab[b] : 0u;
+            blk_nan[(size_t)m * nblk + b] = b < nb ? tab[nb + b] : 0u;
+        }
+    }
+    if (route == 2) {
+        uint32_t changed = 0;
+        for (double v : idle_models) {
+            uint64_t bits;
+            std::memcpy(&bits, &v, sizeof(bits));
+            changed += bits ? 1u : 0u;
+        }
+        for (size_t i = 0; i < (z.nan_bits ? 2 : 1) * (size_t)B; ++i)
+            changed += idle_words[i] != 0xffffffffu ? 1u : 0u;
+        for (unsigned char v : hctl[2])
+            changed += v ? 1u : 0u;
+        flags[2] = changed;
+    }
+    return PL_OK;
+}
+int pl_debug_radial1d_generate(pl_problem *p, const uint32_t *samples, size_t num_iters, uint32_t slots_per_iter, double *models,
+                               uint32_t *num_models, uint32_t *totals) {
+    if (!p || !samples || !models || !num_models || !totals)
+        return fail(PL_ERR_INVALID, "null argument");
+    if (p->kind != EST_RAD1D)
+        return fail(PL_ERR_INVALID, "not a 1D-radial problem");
+    if (num_iters == 0 || num_iters > (1u << 20))
+        return fail(PL_ERR_INVALID, "num_iters must be 1..2^20");
+    const uint32_t nblk = batch_blocks((uint32_t)num_iters);
+    std::vector<uint32_t> tab(2 * (size_t)nblk);
+    uint32_t flags[3];
+    const int rc = pl_debug_generate(p, samples, 0, 0, nullptr, num_iters, slots_per_iter, 0, 0, models, num_models, nullptr, tab.data(),
+                                     tab.data() + nblk, flags);
+    if (rc != PL_OK)
+        return rc;
     totals[0] = totals[1] = 0;
     for (uint32_t b = 0; b < nblk; ++b)
         totals[0] += tab[b], totals[1] += tab[nblk + b];
-    totals[2] = ctl.gen_overflow;
+    totals[2] = flags[0];
     return PL_OK;
 }
 

@@ -136,7 +136,7 @@ __global__ __launch_bounds__(kFrontThreads) void k_rel_front_g(const GroupArgs *
 //     of its root's iteration (75 loads over ~16 cache lines each): bound by the texture path, generator 3.56 -> 3.81 ms;
 //   * -amdgpu-sched-strategy=max-ilp for this file: 3.616 against 3.610 ms.
 struct SturmWorkFlat { // intervals to bisect and the leaves as found: one column per lane of LDS arrays; ordered leaves: workspace
-    static constexpr int kPendCap = 6, kLeafCap = kSturmSlots;
+    static constexpr int kPendCap = kSturmFlatPendCap, kLeafCap = kSturmFlatLeafCap;
     double *pa, *pb, *ua, *ub; // LDS
     unsigned *pi;              // LDS
     double *leaves;            // global, [2 * slot + {0, 1}][P], this iteration's column

@@ -3987,6 +3987,17 @@ template <int E> static hipError_t launch_group_score_est(const GroupArgs *args,
     return hipGetLastError();
 }
 
+// the generators of every active problem of the table: max_B = the longest member's iterations
+hipError_t launch_group_generate(int est, const GroupArgs *args, uint32_t max_B, uint32_t G, hipStream_t stream) {
+    if (G == 0 || max_B == 0)
+        return hipSuccess;
+    if (est == EST_REL)
+        return launch_group_generate_rel(args, max_B, G, stream);
+    const dim3 ggrid((max_B + 63) / 64, 1, G), gblock(64);
+    PL_DISPATCH_EST(est, k_generate_g<E><<<ggrid, gblock, 0, stream>>>(args));
+    return hipGetLastError();
+}
+
 hipError_t launch_group_batch(int est, const GroupArgs *args, const GroupDims &d, hipStream_t stream, hipEvent_t ev0,
                               hipEvent_t ev1) {
     if (d.G == 0)
@@ -3994,14 +4005,9 @@ hipError_t launch_group_batch(int est, const GroupArgs *args, const GroupDims &d
     hipError_t e = launch_group_positions(sample_size(est), args, d, stream);
     if (e != hipSuccess)
         return e;
-    const dim3 ggrid((d.max_B + 63) / 64, 1, d.G), gblock(64);
-    if (est == EST_REL) {
-        e = launch_group_generate_rel(args, d.max_B, d.G, stream);
-        if (e != hipSuccess)
-            return e;
-    } else {
-        PL_DISPATCH_EST(est, k_generate_g<E><<<ggrid, gblock, 0, stream>>>(args));
-    }
+    e = launch_group_generate(est, args, d.max_B, d.G, stream);
+    if (e != hipSuccess)
+        return e;
     e = launch_group_compact(args, d, stream);
     if (e != hipSuccess)
         return e;

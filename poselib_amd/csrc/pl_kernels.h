@@ -160,6 +160,8 @@ size_t rel_stage_bytes(uint32_t num_iters);
 hipError_t launch_generate_rel(const GenerateArgs &a, hipStream_t stream, bool tangent = false);
 struct GroupArgs;
 hipError_t launch_group_generate_rel(const GroupArgs *args, uint32_t max_B, uint32_t G, hipStream_t stream);
+// the generator launch of a group's batch step on its own (kinds 0 - 3; launch_group_batch and the diagnostic entry pl_debug_generate)
+hipError_t launch_group_generate(int est, const GroupArgs *args, uint32_t max_B, uint32_t G, hipStream_t stream);
 // Front-end pre-processing on the device (robust.cc:40-46, 286-292; utils.cc:584-644 per-point part): AoS user
 // buffers -> the problem's SoA block, with per-point un-projection (modes 0, 1) or the affine normalisation whose
 // centroid / scale the host has summed sequentially (mode 2; the two reductions of normalize_points are order

@@ -186,6 +186,11 @@ struct SturmWorkLocal {
     PL_HD void uleaf_get(int i, double &a, double &b) const { a = ua[i], b = ub[i]; }
 };
 
+// Capacities of the flat isolation's two lists in the batched generator (gen_rel.hip SturmWorkFlat: LDS columns).  Smaller than
+// SturmWorkLocal's: an interval waits to be bisected only while it holds >= 2 of the <= 10 roots, and the ranked list keeps
+// kSturmSlots leaves anyway (tests/ runs the flat form at these capacities against the recursion).
+constexpr int kSturmFlatPendCap = 6, kSturmFlatLeafCap = kSturmSlots;
+
 // Real roots of c[0] + c[1] z + ... + c[10] z^10, in the order the reference's recursion emits them (depth first,
 // left half first: sturm.h:210-231).  Two phases so that the lanes of a wavefront stay together: (1) the bisection
 // only records its leaves - intervals narrower than tol (the reference reports their right end as a root whatever

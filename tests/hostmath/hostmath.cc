@@ -258,6 +258,53 @@ int hm_sturm10_flat(const double *coef, double *roots) { // the batched generato
     SturmWorkLocal w;
     return sturm_roots_deg10_flat(coef, roots, w);
 }
+// the degree-10 determinant polynomial of a 5-point sample ([x1 5 x 3][x2 5 x 3] unit bearings): what k_rel_roots isolates
+void hm_rel5_poly(const double *in, double *c /* 11 */) {
+    Vec3 a[5], b[5];
+    for (int k = 0; k < 5; ++k) {
+        a[k] = v3(in[3 * k], in[3 * k + 1], in[3 * k + 2]);
+        b[k] = v3(in[3 * (5 + k)], in[3 * (5 + k) + 1], in[3 * (5 + k) + 2]);
+    }
+    double nb[36], Az[3][13];
+    rel5_front(a, b, nb, Az);
+    rel5_poly(Az, c);
+}
+// The flat isolation with the list capacities of the batched generator (SturmWorkFlat of gen_rel.hip keeps the same two lists in
+// LDS) against the recursion-shaped sturm_roots_deg10, on `count` polynomials of 11 coefficients.  Returns how many differ in the
+// number, the order or the bits of their roots (*first_bad: the first of them); *max_pending / *max_leaves: the most entries the
+// two lists ever held, refused ones included.
+namespace {
+struct SturmWorkGeneratorCaps : SturmWorkLocal {
+    static constexpr int kPendCap = kSturmFlatPendCap, kLeafCap = kSturmFlatLeafCap;
+};
+struct SturmWorkWatch : SturmWorkLocal { // room for everything: how long do the lists get?
+    int max_pending = 0, max_leaves = 0;
+    void pend_push(int i, double a, double b, unsigned info) { SturmWorkLocal::pend_push(i, a, b, info), max_pending = std::max(max_pending, i + 1); }
+    void uleaf_set(int i, double a, double b) { SturmWorkLocal::uleaf_set(i, a, b), max_leaves = std::max(max_leaves, i + 1); }
+};
+} // namespace
+uint64_t hm_sturm10_flat_generator_caps(const double *coefs, uint64_t count, int64_t *first_bad, int32_t *max_pending, int32_t *max_leaves) {
+    static_assert(SturmWorkGeneratorCaps::kPendCap == 6 && SturmWorkGeneratorCaps::kLeafCap == 12, "the generator's capacities");
+    uint64_t bad = 0;
+    *first_bad = -1, *max_pending = *max_leaves = 0;
+    for (uint64_t i = 0; i < count; ++i) {
+        const double *c = coefs + 11 * i;
+        double want[10], got[10];
+        SturmWorkGeneratorCaps w;
+        const int nw = sturm_roots_deg10(c, want), ng = sturm_roots_deg10_flat(c, got, w);
+        if (nw != ng || std::memcmp(want, got, sizeof(double) * nw) != 0) {
+            if (!bad)
+                *first_bad = (int64_t)i;
+            ++bad;
+        }
+        SturmWorkWatch watch;
+        double tmp[10];
+        sturm_roots_deg10_flat(c, tmp, watch);
+        *max_pending = std::max(*max_pending, watch.max_pending);
+        *max_leaves = std::max(*max_leaves, watch.max_leaves);
+    }
+    return bad;
+}
 
 // Build a model record from (q,t) or a row-major 3x3, as the generate kernel stores it.
 void hm_pose_record(const double *q4, const double *t3, int essential, double *rec) {

@@ -100,6 +100,24 @@ def sturm10(coef, flat=False):
     return out[:n]
 
 
+def rel5_poly(x1, x2):
+    """the degree-10 determinant polynomial (11 ascending coefficients) of a 5-point sample of unit bearings"""
+    inp = np.ascontiguousarray(np.concatenate([np.asarray(x1, float).ravel(), np.asarray(x2, float).ravel()]))
+    c = np.zeros(11)
+    lib().hm_rel5_poly(_p(inp), _p(c))
+    return c
+
+
+def sturm10_flat_generator_caps(coefs):
+    """sturm_roots_deg10_flat on a work type with the batched generator's list capacities against sturm_roots_deg10 on the polynomials
+    coefs (n, 11): (how many differ, index of the first, longest work list, longest leaf list - refused entries included)"""
+    c = np.ascontiguousarray(coefs, dtype=np.float64).reshape(-1, 11)
+    first, pend, leaves = C.c_int64(-1), C.c_int32(0), C.c_int32(0)
+    lib().hm_sturm10_flat_generator_caps.restype = C.c_uint64
+    bad = lib().hm_sturm10_flat_generator_caps(_p(c), C.c_uint64(c.shape[0]), C.byref(first), C.byref(pend), C.byref(leaves))
+    return int(bad), first.value, pend.value, leaves.value
+
+
 def pose_record(q, t, essential=False):
     rec = np.zeros(STRIDE)
     q = np.ascontiguousarray(q, dtype=np.float64)

@@ -142,6 +142,39 @@ def sampler_draw(seed, N, K, n_samples, prosac=False, max_prosac=100000):
     return out, st.value
 
 
+def sampler_draw_positions(seed, N, K, n_samples):
+    """The uniform sampler's samples (n_samples, K) and the draws it had consumed before each of them (n_samples,)."""
+    out = np.zeros((n_samples, K), dtype=np.uint64)
+    pos = np.zeros(n_samples, dtype=np.uint64)
+    lib().orc_sampler_draw_positions(u64(seed), u64(N), u64(K), u64(n_samples), _p(out), _p(pos))
+    return out, pos
+
+
+GENERATE_K = {0: 3, 1: 5, 2: 7, 3: 4}
+GENERATE_MAX = {0: 4, 1: 40, 2: 3, 3: 1}
+
+
+def generate_models(kind, a, b, samples, real_focal_check=False):
+    """The estimators' generate_models on explicit samples (B, K) of the points a (n, 2) / b (n, 3 for kind 0, else n, 2).  Returns
+    (counts (B,), models (B, max_models, 7 | 9) zero beyond the count - poses q, t or row-major matrices -, sample_in (B, 2 K, 3): the
+    solver's input vectors, the oracle's own bearings)."""
+    K, maxm, w = GENERATE_K[kind], GENERATE_MAX[kind], 7 if kind in (0, 1) else 9
+    a, b = _f(a), _f(b)
+    s = np.ascontiguousarray(samples, dtype=np.uint64).reshape(-1, K)
+    B = s.shape[0]
+    counts = np.zeros(B, dtype=np.uint32)
+    dense = np.zeros((B * maxm, w))
+    sample_in = np.zeros((B, 2 * K, 3))
+    lib().orc_generate_models.restype = C.c_int64
+    total = lib().orc_generate_models(i32(kind), _p(a), _p(b), C.c_size_t(a.shape[0]), _p(s), C.c_size_t(B), i32(int(real_focal_check)),
+                                      _p(counts), _p(dense), _p(sample_in))
+    assert total == int(counts.sum()) and counts.max(initial=0) <= maxm, total
+    models = np.zeros((B, maxm, w))
+    slot = np.arange(maxm)[None, :] < counts[:, None]
+    models[slot] = dense[:total]
+    return counts, models, sample_in
+
+
 def mock_ransac(num_data, sample_sz, inlier_count, ropt):
     st = Stats()
     o = ransac_opt(ropt)
