@@ -20,6 +20,7 @@
 // that the solver returns the reference's roots bit for bit ("The focal-length estimators").
 #include "pl_focal.h"
 #include "pl_kernels.h"
+#include "pl_global_focal.h"
 #include "pl_solver_p35pf.h"
 #include "pl_eigen_wave.h"
 #include "pl_lm_chain.inc"
@@ -70,7 +71,7 @@ __device__ __forceinline__ void focal_setup_body(const FocalGenArgs &g, uint32_t
 }
 __global__ __launch_bounds__(64) void k_focal_setup(FocalGenArgs g) { focal_setup_body(g, blockIdx.x); }
 __global__ __launch_bounds__(64) void k_focal_setup_g(const FocalGenArgs *__restrict__ gs) {
-    const FocalGenArgs g = gs[blockIdx.y];
+    const FocalGenArgs g = globalised(gs[blockIdx.y]);
     focal_setup_body(g, blockIdx.x);
 }
 
@@ -146,7 +147,7 @@ __device__ __forceinline__ void focal_solve_body(const FocalGenArgs &g, uint32_t
 }
 __global__ __launch_bounds__(64 * kSolveWaves) void k_focal_solve(FocalGenArgs g) { focal_solve_body(g, blockIdx.x); }
 __global__ __launch_bounds__(64 * kSolveWaves) void k_focal_solve_g(const FocalGenArgs *__restrict__ gs) {
-    const FocalGenArgs g = gs[blockIdx.y];
+    const FocalGenArgs g = globalised(gs[blockIdx.y]);
     focal_solve_body(g, blockIdx.x);
 }
 
@@ -200,7 +201,7 @@ __device__ __forceinline__ void focal_score_body(const FocalScoreArgs &a, uint32
 }
 __global__ __launch_bounds__(kFocalScoreThreads) void k_focal_score(FocalScoreArgs a) { focal_score_body(a, blockIdx.x); }
 __global__ __launch_bounds__(kFocalScoreThreads) void k_focal_score_g(const FocalScoreArgs *__restrict__ as) {
-    const FocalScoreArgs a = as[blockIdx.y];
+    const FocalScoreArgs a = globalised(as[blockIdx.y]);
     focal_score_body(a, blockIdx.x);
 }
 
@@ -272,7 +273,7 @@ __device__ __forceinline__ void focal_score_wg_body(const FocalScoreArgs &a, uin
 }
 __global__ __launch_bounds__(kFocalScoreThreads) void k_focal_score_wg(FocalScoreArgs a) { focal_score_wg_body(a, blockIdx.x); }
 __global__ __launch_bounds__(kFocalScoreThreads) void k_focal_score_wg_g(const FocalScoreArgs *__restrict__ as) {
-    const FocalScoreArgs a = as[blockIdx.y];
+    const FocalScoreArgs a = globalised(as[blockIdx.y]);
     focal_score_wg_body(a, blockIdx.x);
 }
 
@@ -292,7 +293,7 @@ __global__ void k_focal_mask(const double *x, const double *y, const double *X, 
     focal_mask_body(x, y, X, Y, Z, n, m, thr2, mask, host_mask, blockIdx.x * blockDim.x + threadIdx.x);
 }
 __global__ void k_focal_mask_g(const FocalMaskArgs *__restrict__ as) {
-    const FocalMaskArgs a = as[blockIdx.y];
+    const FocalMaskArgs a = globalised(as[blockIdx.y]);
     focal_mask_body(a.a[0], a.a[1], a.a[2], a.a[3], a.a[4], a.n, a.model, a.thr2, a.mask, a.host_mask, blockIdx.x * blockDim.x + threadIdx.x);
 }
 

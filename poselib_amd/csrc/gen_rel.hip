@@ -38,6 +38,7 @@
 //     spilled registers instead of 3600 v_cndmask: same instruction count).
 // Which lane works on which iteration never influences a result: everything is addressed by iteration.
 #include "pl_device.h"
+#include "pl_global.h"
 #include "pl_solver_rel.h"
 
 namespace pl {
@@ -116,7 +117,8 @@ __global__ __launch_bounds__(kFrontThreads) void k_rel_front_g(const GroupArgs *
     const GroupArgs &gg = ga[blockIdx.z];
     if (!gg.active || blockIdx.x * (uint32_t)kFrontThreads >= gg.gen.num_iters)
         return;
-    rel_front_body<false>(gg.gen, rel_stage(gg.gen.stage, gg.gen.num_iters));
+    const GenerateArgs g = globalised(gg.gen);
+    rel_front_body<false>(g, rel_stage(g.stage, g.num_iters));
 }
 
 // ---- stage 2 --------------------------------------------------------------------------------------------------------
@@ -202,7 +204,7 @@ __global__ __launch_bounds__(64) void k_rel_roots_g(const GroupArgs *ga) {
     const GroupArgs &gg = ga[blockIdx.z];
     if (!gg.active || blockIdx.x * 64u >= gg.gen.num_iters)
         return;
-    rel_roots_body(gg.gen.num_iters, rel_stage(gg.gen.stage, gg.gen.num_iters));
+    rel_roots_body(gg.gen.num_iters, rel_stage(as_global(gg.gen.stage), gg.gen.num_iters));
 }
 
 // ---- stage 3 --------------------------------------------------------------------------------------------------------
@@ -313,7 +315,8 @@ __global__ __launch_bounds__(kPosesThreads) void k_rel_poses_g(const GroupArgs *
     const GroupArgs &gg = ga[blockIdx.z];
     if (!gg.active || blockIdx.x * (uint32_t)kPosesThreads >= gg.gen.num_iters)
         return;
-    rel_poses_body(gg.gen, rel_stage(gg.gen.stage, gg.gen.num_iters));
+    const GenerateArgs g = globalised(gg.gen);
+    rel_poses_body(g, rel_stage(g.stage, g.num_iters));
 }
 
 // ---- launchers ------------------------------------------------------------------------------------------------------

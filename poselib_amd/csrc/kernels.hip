@@ -29,6 +29,7 @@
 // Exact arithmetic (fp64, reference association order) never runs on the matrix cores; only the filters' linear and
 // quadratic forms do.
 #include "pl_kernels.h"
+#include "pl_global.h"
 #include "pl_lm_chain.inc"
 #include "pl_device.h"
 #include <atomic>
@@ -308,7 +309,7 @@ template <int EST> __global__ __launch_bounds__(64) void k_generate_g(const Grou
     const GroupArgs &gg = ga[blockIdx.z];
     if (!gg.active || blockIdx.x * 64u >= gg.gen.num_iters)
         return;
-    const GenerateArgs &g = gg.gen;
+    const GenerateArgs g = globalised(gg.gen);
     const uint32_t it = blockIdx.x * 64 + threadIdx.x;
     uint32_t n_nan = 0;
     uint32_t n;
@@ -734,7 +735,7 @@ template <int EST, int P> __global__ __launch_bounds__(kQueueThreads) void k_sco
     const GroupArgs &g = ga[blockIdx.z];
     if (!g.active || g.use_mfma || blockIdx.y >= g.chunks || blockIdx.x >= g.slices)
         return;
-    const ScoreArgs &a = g.score;
+    const ScoreArgs a = globalised(g.score);
     score_queue_body<EST, P>(a.pts, a.shadow, a.compact64, a.num_hyp, a.hyp_capacity, a.thr2, a.pf, a.part_count,
                              a.part_score, blockIdx.x, blockIdx.y, g.slices);
 }
@@ -1521,7 +1522,7 @@ __global__ __launch_bounds__(kMfmaThreads) __attribute__((amdgpu_waves_per_eu(4,
     uint32_t slice, chunk;
     if (!g.active || !g.use_mfma || !slice_chunk_of_workgroup(g.slices, g.chunks, slice, chunk))
         return;
-    const ScoreArgs &a = g.score;
+    const ScoreArgs a = globalised(g.score);
     score_mfma_body<PG>(a.pts, static_cast<const uint4 *>(a.shadow16), static_cast<const uint4 *>(a.points16), a.models, a.slots,
                         a.num_hyp, a.hyp_capacity, a.thr2, a.part_count, a.part_score, slice, chunk, g.slices);
 }
@@ -1773,7 +1774,7 @@ template <int EST, int PG> __global__ __launch_bounds__(kMfmaThreads) void k_sco
     uint32_t slice, chunk;
     if (!g.active || !g.use_mfma || !slice_chunk_of_workgroup(g.slices, g.chunks, slice, chunk))
         return;
-    const ScoreArgs &a = g.score;
+    const ScoreArgs a = globalised(g.score);
     score_mfma2_body<EST, PG>(a.pts, static_cast<const uint4 *>(a.shadow16), a.models, a.slots, a.num_hyp, a.hyp_capacity,
                               a.thr2, a.pf, a.part_count, a.part_score, slice, chunk, g.slices);
 }
@@ -1970,7 +1971,7 @@ __global__ __launch_bounds__(kMfmaThreads) __attribute__((amdgpu_waves_per_eu(6,
     uint32_t slice, chunk;
     if (!g.active || !g.use_mfma || !slice_chunk_of_workgroup(g.slices, g.chunks, slice, chunk))
         return;
-    const ScoreArgs &a = g.score;
+    const ScoreArgs a = globalised(g.score);
     score_mfmah_body<PG>(a.pts, static_cast<const uint4 *>(a.shadow16), a.models, a.slots, a.num_hyp, a.hyp_capacity, a.thr2,
                          a.pf, a.part_count, a.part_score, slice, chunk, g.slices);
 }
@@ -2109,14 +2110,14 @@ template <int EST> __global__ __launch_bounds__(kSeqThreads) void k_score_seq_g(
     const SeqScoreArgs &a = arr[blockIdx.z];
     if (a.cap == 0 || a.num == nullptr)
         return;
-    score_seq_body<EST>(a);
+    score_seq_body<EST>(globalised(a));
 }
 // (the candidate re-scoring of a group's batch step: arguments inside the GroupArgs table)
 template <int EST> __global__ __launch_bounds__(kSeqThreads) void k_score_seq_gb(const GroupArgs *ga) {
     const GroupArgs &g = ga[blockIdx.z];
     if (!g.active)
         return;
-    score_seq_body<EST>(g.seq);
+    score_seq_body<EST>(globalised(g.seq));
 }
 
 // ------------------------------------------------------------------------------------ mask
@@ -2149,9 +2150,10 @@ template <int EST> __global__ __launch_bounds__(256) void k_mask(PointSet pts, c
     mask_body<EST>(pts, model, thr2, mask, host_mask);
 }
 template <int EST> __global__ __launch_bounds__(256) void k_mask_g(const MaskArgs *arr) {
-    const MaskArgs &a = arr[blockIdx.z];
-    if (blockIdx.x * 256u >= a.pts.n)
+    const MaskArgs &in = arr[blockIdx.z];
+    if (blockIdx.x * 256u >= in.pts.n)
         return;
+    const MaskArgs a = globalised(in);
     mask_body<EST>(a.pts, a.model, a.thr2, a.mask, a.host_mask);
 }
 
@@ -2159,7 +2161,8 @@ template <int EST> __global__ __launch_bounds__(256) void k_mask_g(const MaskArg
 // starting point of a refinement task: its parameter block, or (tasks enqueued behind the kernel that chooses their model) the
 // parameters of a model record in device memory - what driver.cc's params_from_record() extracts on the host
 __device__ __forceinline__ void lm_start_params(int est, const LMTask &T, double *cur) {
-    if (!T.start_record) {
+    const double *start_record = globalised(T).start_record; // (T itself may sit in LDS: only what it points to is global)
+    if (!start_record) {
         for (int i = 0; i < kParamDoubles; ++i)
             cur[i] = T.params[i];
         return;
@@ -2168,10 +2171,10 @@ __device__ __forceinline__ void lm_start_params(int est, const LMTask &T, double
         cur[i] = 0.0;
     if (est == EST_ABS || est == EST_REL || est == EST_RELT || est == EST_RAD1D) {
         for (int i = 0; i < 7; ++i)
-            cur[i] = T.start_record[i];
+            cur[i] = start_record[i];
     } else {
         for (int i = 0; i < 9; ++i)
-            cur[i] = T.start_record[kMatOff + i];
+            cur[i] = start_record[kMatOff + i];
     }
 }
 
@@ -2392,18 +2395,20 @@ template <int EST> __global__ __launch_bounds__(kLMThreads) void k_lm(LMTask *ta
         Tout.skipped = skipped ? 1u : 0u;
         Tout.cost = cost;
         Tout.initial_cost = initial_cost;
-        if (T.record_out) {
+        const LMTaskPointers G = globalised(T);
+        if (G.record_out) {
             if (skipped) { // refinement not run: model unchanged (relative_pose.cc:75-77)
                 for (int i = 0; i < kModelStride; ++i)
-                    T.record_out[i] = T.record_in[i];
+                    G.record_out[i] = G.record_in[i];
             } else {
-                record_from_lm_params(EST, params, T.record_out);
+                record_from_lm_params(EST, params, G.record_out);
             }
         }
     };
     extern __shared__ double s_lm_points[];
-    const PointSet pts_global = T.pts;
-    PointSet pts = pts_global;
+    const LMTaskPointers G = globalised(T); // what the task points to is device memory (pl_global.h) ...
+    const PointSet pts_global = G.pts;
+    PointSet pts = pts_global; // ... but THIS set points into LDS when the correspondences fit: its accesses stay flat
     // (tasks of several problems may share a launch: each stages its own points if they fit the launch's dynamic LDS)
     const bool lds_points = sizeof(double) * ND * (size_t)pts_global.n <= (size_t)lds_bytes;
     if (lds_points) {
@@ -2436,11 +2441,11 @@ template <int EST> __global__ __launch_bounds__(kLMThreads) void k_lm(LMTask *ta
     __shared__ uint32_t s_queue[kLMThreads / 64][128]; // per wavefront: correspondences waiting for their Jacobian
     __shared__ __attribute__((aligned(16))) double s_terms[132][NT + 1]; // small problems: the terms of 64 correspondences (x 2 for H) + cost; two column-major buffers of 64 rows for the others
 
-    const uint8_t *mask = T.mask;
+    const uint8_t *mask = G.mask;
     const double pscale = T.point_scale;
     const CameraParams cam = T.cam;
 
-    if (T.gate_count && *T.gate_count <= T.gate_min) { // (uniform: every thread reads the same word) the task does not run
+    if (G.gate_count && *G.gate_count <= T.gate_min) { // (uniform: every thread reads the same word) the task does not run
         if (threadIdx.x == 0) {
             Tout.iterations = 0;
             Tout.skipped = 2u;
@@ -2470,7 +2475,7 @@ template <int EST> __global__ __launch_bounds__(kLMThreads) void k_lm(LMTask *ta
                 double r2;
                 const bool in = sampson_pose_inlier(M, pts.a[0][i], pts.a[1][i], pts.a[2][i], pts.a[3][i],
                                                     T.prefilter_thr2, r2);
-                T.scratch[i] = in ? 1 : 0;
+                G.scratch[i] = in ? 1 : 0;
                 c += in;
             }
             double dummy[1] = {0.0};
@@ -2481,7 +2486,7 @@ template <int EST> __global__ __launch_bounds__(kLMThreads) void k_lm(LMTask *ta
                 s_skip = 1;
             __threadfence_block();
             __syncthreads();
-            mask = T.scratch;
+            mask = G.scratch;
         }
     }
     if (s_skip) {
@@ -2966,18 +2971,20 @@ template <int EST> __global__ __launch_bounds__(kLMThreads, 2) void k_lm_ordered
         Tout.skipped = skipped ? 1u : 0u;
         Tout.cost = cost;
         Tout.initial_cost = initial_cost;
-        if (T.record_out) {
+        const LMTaskPointers G = globalised(T);
+        if (G.record_out) {
             if (skipped) { // refinement not run: model unchanged (relative_pose.cc:75-77)
                 for (int i = 0; i < kModelStride; ++i)
-                    T.record_out[i] = T.record_in[i];
+                    G.record_out[i] = G.record_in[i];
             } else {
-                record_from_lm_params(EST, params, T.record_out);
+                record_from_lm_params(EST, params, G.record_out);
             }
         }
     };
     extern __shared__ double s_lm_points[];
-    const PointSet pts_global = T.pts;
-    PointSet pts = pts_global;
+    const LMTaskPointers G = globalised(T); // what the task points to is device memory (pl_global.h) ...
+    const PointSet pts_global = G.pts;
+    PointSet pts = pts_global; // ... but THIS set points into LDS when the correspondences fit: its accesses stay flat
     // (tasks of several problems may share a launch: each stages its own points if they fit the launch's dynamic LDS)
     const bool lds_points = sizeof(double) * ND * (size_t)pts_global.n <= (size_t)lds_bytes;
     if (lds_points) {
@@ -3020,11 +3027,11 @@ template <int EST> __global__ __launch_bounds__(kLMThreads, 2) void k_lm_ordered
         s_consumed = 0;
     uint32_t seq_base = 0; // batches handed through the ring so far (the same in every thread)
 
-    const uint8_t *mask = T.mask;
+    const uint8_t *mask = G.mask;
     const double pscale = T.point_scale;
     const CameraParams cam = T.cam;
 
-    if (T.gate_count && *T.gate_count <= T.gate_min) { // (uniform: every thread reads the same word) the task does not run
+    if (G.gate_count && *G.gate_count <= T.gate_min) { // (uniform: every thread reads the same word) the task does not run
         if (threadIdx.x == 0) {
             Tout.iterations = 0;
             Tout.skipped = 2u;
@@ -3054,7 +3061,7 @@ template <int EST> __global__ __launch_bounds__(kLMThreads, 2) void k_lm_ordered
                 double r2;
                 const bool in = sampson_pose_inlier(M, pts.a[0][i], pts.a[1][i], pts.a[2][i], pts.a[3][i],
                                                     T.prefilter_thr2, r2);
-                T.scratch[i] = in ? 1 : 0;
+                G.scratch[i] = in ? 1 : 0;
                 c += in;
             }
             double dummy[1] = {0.0};
@@ -3065,7 +3072,7 @@ template <int EST> __global__ __launch_bounds__(kLMThreads, 2) void k_lm_ordered
                 s_skip = 1;
             __threadfence_block();
             __syncthreads();
-            mask = T.scratch;
+            mask = G.scratch;
         }
     }
     if (s_skip) {
@@ -3444,7 +3451,7 @@ __global__ __launch_bounds__(kLM2Threads) void k_lm2(PointSet pts, LMTask *tasks
     if (pass == 0)
         return;
     const double *p = (pass == 3) ? st.trial : st.cur;
-    const uint8_t *mask = task.mask;
+    const uint8_t *mask = as_global(task.mask); // (k_lm2 takes its correspondences as a kernel argument; the mask is the one pointer it fetches)
     const double pscale = task.point_scale;
     const CameraParams cam = task.cam;
     const Loss loss = st.ctl.loss;
@@ -3929,7 +3936,7 @@ __global__ void k_select_record(const double *score_refined, double incumbent_sc
         out[threadIdx.x] = src[threadIdx.x];
 }
 __global__ void k_select_record_g(const SelectArgs *arr) {
-    const SelectArgs &a = arr[blockIdx.z];
+    const SelectArgs a = globalised(arr[blockIdx.z]);
     if (!a.out)
         return;
     const double *src = (*a.score_refined < a.incumbent_score) ? a.rec_refined : a.rec_incumbent;

@@ -16,6 +16,7 @@
 // equal the oracle's to the bit: the robust cost is summed in the reference's order as well, at every n since round 4.  The consumer loop is branch-free and takes eight rows per step (their LDS reads travel together, the
 // additions stay a chain in row order); the final bundle runs once per problem, on the inliers.
 #include "pl_kernels.h"
+#include "pl_global.h"
 #include "pl_lm_chain.inc"
 #include "pl_device.h"
 #include "pl_refine_cam.h"
@@ -63,12 +64,13 @@ __global__ __launch_bounds__(kCamThreads) void k_lm_cam(LMTask *tasks) {
         __syncthreads();
     }
     const LMTask &T = s_task;
-    const PointSet pts = T.pts;
-    const uint8_t *mask = T.mask;
+    const LMTaskPointers G = globalised(T); // what the task points to is device memory (pl_global.h)
+    const PointSet pts = G.pts;
+    const uint8_t *mask = G.mask;
     const double pscale = T.point_scale;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 
-    if (T.gate_count && *T.gate_count <= T.gate_min) { // (uniform) the task does not run: see LMTask
+    if (G.gate_count && *G.gate_count <= T.gate_min) { // (uniform) the task does not run: see LMTask
         if (threadIdx.x == 0) {
             Tout.iterations = 0;
             Tout.skipped = 2u;
@@ -76,11 +78,11 @@ __global__ __launch_bounds__(kCamThreads) void k_lm_cam(LMTask *tasks) {
         return;
     }
     if (threadIdx.x == 0) {
-        if (T.start_record) { // absolute pose: q, t of the chosen model's record
+        if (G.start_record) { // absolute pose: q, t of the chosen model's record
             for (int i = 0; i < kParamDoubles; ++i)
                 cur[i] = 0.0;
             for (int i = 0; i < 7; ++i)
-                cur[i] = T.start_record[i];
+                cur[i] = G.start_record[i];
         } else {
             for (int i = 0; i < kParamDoubles; ++i)
                 cur[i] = T.params[i];
@@ -356,8 +358,8 @@ __global__ __launch_bounds__(kCamThreads) void k_lm_cam(LMTask *tasks) {
         Tout.skipped = 0u;
         Tout.cost = ctl.cost;
         Tout.initial_cost = ctl.initial_cost;
-        if (T.record_out)
-            record_from_lm_params(EST_ABS, cur, T.record_out);
+        if (double *record_out = globalised(T).record_out)
+            record_from_lm_params(EST_ABS, cur, record_out);
     }
 }
 

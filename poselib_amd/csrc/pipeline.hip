@@ -19,6 +19,7 @@
 //       iff count > max(previous counts) or score < min(previous scores).  Records (typically O(log H)) are
 //       appended with their 128-byte model so the host fetches a few KB instead of every score.
 #include "pl_kernels.h"
+#include "pl_global.h"
 #include "pl_device.h"
 #include "pl_refine.h"
 #include "pl_sampler.h"
@@ -95,8 +96,8 @@ template <int K> __global__ __launch_bounds__(256) void k_sample_delta_g(const G
     const GroupArgs &g = ga[blockIdx.z];
     if (!g.active || blockIdx.x * 256u >= ((g.samp.M + 255u) & ~255u))
         return;
-    sample_delta_body<K>(g.samp.seed, g.samp.pos_base, g.samp.N, g.samp.M, g.samp.delta, g.samp.flagbits,
-                         reinterpret_cast<uint32_t *>(g.samp.ctl), g.samp.zero_words);
+    const SampleArgs s = globalised(g.samp);
+    sample_delta_body<K>(s.seed, s.pos_base, s.N, s.M, s.delta, s.flagbits, reinterpret_cast<uint32_t *>(s.ctl), s.zero_words);
 }
 
 // Capacities of the orbit walk's LDS tables, two builds of the kernel:
@@ -383,12 +384,11 @@ template <bool SMALL> __global__ __launch_bounds__(1024) void k_sample_orbit_g(c
     const GroupArgs &g = ga[blockIdx.z];
     if (!g.active)
         return;
+    const SampleArgs s = globalised(g.samp);
     if constexpr (SMALL)
-        sample_orbit_body<kSmallFlags, kSmallFlags, kSmallFlags>(g.samp.delta, g.samp.flagbits, g.samp.M, K, g.samp.B, g.samp.pos_base,
-                                                               g.samp.positions, g.samp.ctl);
+        sample_orbit_body<kSmallFlags, kSmallFlags, kSmallFlags>(s.delta, s.flagbits, s.M, K, s.B, s.pos_base, s.positions, s.ctl);
     else
-        sample_orbit_body<kMaxFlags, kParFlags, kMaxSegments>(g.samp.delta, g.samp.flagbits, g.samp.M, K, g.samp.B, g.samp.pos_base,
-                                                             g.samp.positions, g.samp.ctl);
+        sample_orbit_body<kMaxFlags, kParFlags, kMaxSegments>(s.delta, s.flagbits, s.M, K, s.B, s.pos_base, s.positions, s.ctl);
 }
 // expected number of flagged positions among M: a position is flagged when the K draws starting there repeat an index
 static bool orbit_small_build(uint32_t M, uint64_t N, int K) {
@@ -532,8 +532,9 @@ __global__ __launch_bounds__(1024) void k_compact2_g(const GroupArgs *ga) {
     const uint32_t nb = (g.comp.B + 1023u) / 1024u;
     if (!g.active || blockIdx.x >= nb)
         return;
-    compact2_body(g.comp.num_models, g.comp.B, g.comp.maxm, g.comp.blk_tot, g.comp.slots, g.comp.offsets, g.comp.ctl, nb,
-                  g.comp.host_offsets, g.comp.models, g.comp.s16.live, g.comp.s16.rank, g.comp.s16.nan_bits);
+    const CompactArgs c = globalised(g.comp);
+    compact2_body(c.num_models, c.B, c.maxm, c.blk_tot, c.slots, c.offsets, c.ctl, nb, c.host_offsets, c.models, c.s16.live,
+                  c.s16.rank, c.s16.nan_bits);
 }
 
 // The same for a list the host wrote (pl_debug_score_stream: `H` records in list order `slots`, no generator counts): one
@@ -649,7 +650,8 @@ __global__ __launch_bounds__(256) void k_finalize2_g(const GroupArgs *ga) {
     const GroupArgs &g = ga[blockIdx.z];
     if (!g.active)
         return;
-    finalize2_body(g.rec.f, g.rec.blk_max, g.rec.blk_min);
+    const RecordsArgs r = globalised(g.rec);
+    finalize2_body(r.f, r.blk_max, r.blk_min);
 }
 
 __device__ __forceinline__ void records_body(const uint32_t *num_hyp, const uint32_t *count, const double *score,
@@ -761,7 +763,7 @@ __global__ __launch_bounds__(256) void k_records_g(const GroupArgs *ga) {
     const GroupArgs &g = ga[blockIdx.z];
     if (!g.active)
         return;
-    const RecordsArgs &r = g.rec;
+    const RecordsArgs r = globalised(g.rec);
     records_body(r.f.num_hyp, r.f.count, r.f.score, r.slots, r.models, r.blk_max, r.blk_min, r.init_max, r.init_min,
                  r.rec_meta, r.rec_models, r.rec_cap, r.ctl, r.host_meta, r.host_models, r.host_meta ? r.host_cap : 0u);
 }
@@ -921,45 +923,47 @@ __global__ __launch_bounds__(256) void k_gather_shadow16_g(const GroupArgs *ga, 
     const GroupArgs &g = ga[blockIdx.z];
     if (!g.active)
         return;
-    const uint64_t cap = (uint64_t)g.comp.B * (uint64_t)g.comp.maxm;
-    const uint32_t H = g.comp.ctl->num_hyp;
+    const CompactArgs comp = globalised(g.comp);
+    const uint64_t cap = (uint64_t)comp.B * (uint64_t)comp.maxm;
+    const uint32_t H = comp.ctl->num_hyp;
     if (blockIdx.x < gather_blocks) {
-        if (g.comp.s16.out) // (the matrix-core scorer reads the records themselves)
+        if (comp.s16.out) // (the matrix-core scorer reads the records themselves)
             return;
         const uint64_t end = std::min<uint64_t>(cap, H) * 12u;
         for (uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x; t < end; t += (uint64_t)gather_blocks * 256)
-            gather_one(g.comp.ctl, g.comp.slots, g.comp.models, g.comp.shadow, g.comp.compact64, t);
+            gather_one(comp.ctl, comp.slots, comp.models, comp.shadow, comp.compact64, t);
         return;
     }
-    if (!g.comp.s16.out)
+    if (!comp.s16.out)
         return;
     const uint32_t nb = gridDim.x - gather_blocks;
     const uint32_t k0 = (blockIdx.x - gather_blocks) * 256 + threadIdx.x;
-    if (g.comp.s16.sampson == 2) {
+    if (comp.s16.sampson == 2) {
         const uint32_t end = (uint32_t)std::min<uint64_t>((cap + 7u) & ~7ull, ((uint64_t)H + 7u) & ~7ull);
         for (uint32_t k = k0; k < end; k += nb * 256)
-            hom16_one(k, H, g.comp.slots, g.comp.models, g.comp.s16.thr, static_cast<uint4 *>(g.comp.s16.out));
+            hom16_one(k, H, comp.slots, comp.models, comp.s16.thr, static_cast<uint4 *>(comp.s16.out));
         return;
     }
-    if (g.comp.s16.sampson) {
+    if (comp.s16.sampson) {
         const uint32_t capp = (uint32_t)std::min<uint64_t>(cap + kSampson16Pad, 0xffffff00ull);
         const uint32_t end = min(capp, H + (uint32_t)kSampson16Pad);
         for (uint32_t k = k0; k < end; k += nb * 256)
-            sampson16_one(k, H, capp, g.comp.slots, g.comp.models, static_cast<uint4 *>(g.comp.s16.out));
+            sampson16_one(k, H, capp, comp.slots, comp.models, static_cast<uint4 *>(comp.s16.out));
         return;
     }
     // absolute pose: the operand rows of the correspondences (abs16_point_row) and of the live hypotheses
-    for (uint32_t i = k0; i < g.comp.s16.point_rows; i += nb * 256)
-        abs16_point_row(g.score.pts, i, g.comp.s16.g16, g.comp.s16.thr, static_cast<uint4 *>(g.comp.s16.points16));
+    const PointSet pts = globalised(g.score.pts);
+    for (uint32_t i = k0; i < comp.s16.point_rows; i += nb * 256)
+        abs16_point_row(pts, i, comp.s16.g16, comp.s16.thr, static_cast<uint4 *>(comp.s16.points16));
     // (shadow16_one fills the last group of 32 up and ignores everything behind it)
-    const uint32_t HL = g.comp.ctl->num_live;
+    const uint32_t HL = comp.ctl->num_live;
     const uint32_t end = (uint32_t)std::min<uint64_t>((cap + 31u) & ~31ull, ((uint64_t)HL + 31u) & ~31ull);
-    const uint32_t *live = g.comp.s16.live;
-    const double *models = g.comp.models;
+    const uint32_t *live = comp.s16.live;
+    const double *models = comp.models;
     for (uint32_t r = k0; r < end; r += nb * 256)
         shadow16_one(r, HL,
                      [&](uint32_t rr) { return reinterpret_cast<const float *>(models + (size_t)live[rr] * kModelStride + kShadowOff); },
-                     g.comp.s16.c16, g.comp.s16.thr, static_cast<uint4 *>(g.comp.s16.out));
+                     comp.s16.c16, comp.s16.thr, static_cast<uint4 *>(comp.s16.out));
 }
 
 // ------------------------------------------------------------------------------------ front-end pre-processing
@@ -1039,10 +1043,12 @@ __global__ __launch_bounds__(256) void k_prepare_tangent(const double *__restric
     }
 }
 __global__ __launch_bounds__(256) void k_prepare_g(const PrepareGroupArgs *pa) {
-    const PrepareGroupArgs &g = pa[blockIdx.z];
-    if (blockIdx.x * 256u >= g.n)
+    const PrepareGroupArgs &in = pa[blockIdx.z];
+    if (blockIdx.x * 256u >= in.n)
         return;
-    prepare_body(g.a_raw, g.b_raw, g.n, g.args, g.soa, g.absmax_bits);
+    const PrepareGroupArgs g = globalised(in);
+    // (in.args, not g.args: the cameras' parameter arrays are indexed at run time, a private copy of them would live in scratch)
+    prepare_body(g.a_raw, g.b_raw, g.n, in.args, g.soa, g.absmax_bits);
 }
 
 // Un-distortion as a stage of its own (BASELINE config 3: "OPENCV camera model" in front of the homography / 7-point

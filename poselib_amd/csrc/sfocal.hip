@@ -25,6 +25,7 @@
 #include "pl_kernels.h"
 #include "pl_device.h"
 #include "pl_sfocal.h"
+#include "pl_global_focal.h"
 #include "pl_solver_6ptf.h"
 #include "pl_lm_chain.inc"
 #include <algorithm>
@@ -77,7 +78,7 @@ __device__ __forceinline__ void sfocal_setup_body(const SFocalGenArgs &g, uint32
 }
 __global__ __launch_bounds__(64) void k_sfocal_setup(SFocalGenArgs g) { sfocal_setup_body(g, blockIdx.x); }
 __global__ __launch_bounds__(64) void k_sfocal_setup_g(const SFocalGenArgs *__restrict__ gs) {
-    const SFocalGenArgs g = gs[blockIdx.y];
+    const SFocalGenArgs g = globalised(gs[blockIdx.y]);
     sfocal_setup_body(g, blockIdx.x);
 }
 
@@ -222,7 +223,7 @@ __device__ __forceinline__ void sfocal_solve_body(const SFocalGenArgs &g, uint32
 }
 __global__ __launch_bounds__(64 * kSolveWaves) void k_sfocal_solve(SFocalGenArgs g) { sfocal_solve_body(g, blockIdx.x); }
 __global__ __launch_bounds__(64 * kSolveWaves) void k_sfocal_solve_g(const SFocalGenArgs *__restrict__ gs) {
-    const SFocalGenArgs g = gs[blockIdx.y];
+    const SFocalGenArgs g = globalised(gs[blockIdx.y]);
     sfocal_solve_body(g, blockIdx.x);
 }
 
@@ -294,7 +295,7 @@ __device__ __forceinline__ void sfocal_score_body(const SFocalScoreArgs &a, uint
 }
 __global__ __launch_bounds__(kSFocalScoreThreads) void k_sfocal_score(SFocalScoreArgs a) { sfocal_score_body(a, blockIdx.x); }
 __global__ __launch_bounds__(kSFocalScoreThreads) void k_sfocal_score_g(const SFocalScoreArgs *__restrict__ as) {
-    const SFocalScoreArgs a = as[blockIdx.y];
+    const SFocalScoreArgs a = globalised(as[blockIdx.y]);
     sfocal_score_body(a, blockIdx.x);
 }
 
@@ -353,7 +354,7 @@ __device__ __forceinline__ void sfocal_score_wg_body(const SFocalScoreArgs &a, u
 }
 __global__ __launch_bounds__(kSFocalScoreThreads) void k_sfocal_score_wg(SFocalScoreArgs a) { sfocal_score_wg_body(a, blockIdx.x); }
 __global__ __launch_bounds__(kSFocalScoreThreads) void k_sfocal_score_wg_g(const SFocalScoreArgs *__restrict__ as) {
-    const SFocalScoreArgs a = as[blockIdx.y];
+    const SFocalScoreArgs a = globalised(as[blockIdx.y]);
     sfocal_score_wg_body(a, blockIdx.x);
 }
 
@@ -373,7 +374,7 @@ __global__ void k_sfocal_mask(const double *x1, const double *y1, const double *
     sfocal_mask_body(x1, y1, x2, y2, n, m, thr2, mask, host_mask, blockIdx.x * blockDim.x + threadIdx.x);
 }
 __global__ void k_sfocal_mask_g(const FocalMaskArgs *__restrict__ as) {
-    const FocalMaskArgs a = as[blockIdx.y];
+    const FocalMaskArgs a = globalised(as[blockIdx.y]);
     sfocal_mask_body(a.a[0], a.a[1], a.a[2], a.a[3], a.n, a.model, a.thr2, a.mask, a.host_mask, blockIdx.x * blockDim.x + threadIdx.x);
 }
 
@@ -406,9 +407,10 @@ __global__ __launch_bounds__(kSfLMThreads) void k_sfocal_lm(SFocalLMTask *tasks)
     }
     const SFocalLMTask &T = s_task;
     const uint32_t n = T.n;
-    const double *x1 = T.a[0], *y1 = T.a[1], *x2 = T.a[2], *y2 = T.a[3];
+    const SFocalLMTaskPointers G = globalised(T); // what the task points to is device memory (pl_global.h)
+    const double *x1 = G.a[0], *y1 = G.a[1], *x2 = G.a[2], *y2 = G.a[3];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint8_t *mask = T.mask;
+    const uint8_t *mask = G.mask;
 
     auto block_count = [&](uint32_t mine) -> uint32_t { // sum over the workgroup, returned to every lane
         const uint32_t ws = wave_sum_u32(mine);
@@ -439,7 +441,7 @@ __global__ __launch_bounds__(kSfLMThreads) void k_sfocal_lm(SFocalLMTask *tasks)
         uint32_t kept = 0;
         for (uint32_t i = threadIdx.x; i < n; i += kSfLMThreads) {
             const uint8_t v = sampson_sq(F, x1[i], y1[i], x2[i], y2[i]) < T.prefilter_thr2 ? 1 : 0;
-            T.scratch[i] = v;
+            G.scratch[i] = v;
             kept += v;
         }
         const uint32_t total = block_count(kept);
@@ -451,7 +453,7 @@ __global__ __launch_bounds__(kSfLMThreads) void k_sfocal_lm(SFocalLMTask *tasks)
             }
             return;
         }
-        mask = T.scratch;
+        mask = G.scratch;
         __threadfence_block();
         __syncthreads();
     }
