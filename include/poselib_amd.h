@@ -378,6 +378,44 @@ int pl_debug_generate(pl_problem *p, const uint32_t *samples, uint64_t seed, uin
  * models and correspondences here to check that a filter never drops an inlier. */
 int pl_debug_score_stream(pl_problem *p, const void *models, size_t n, double max_error, uint32_t *counts,
                           double *scores, int32_t *path_used);
+/* Diagnostic: how the streaming scorers cut n_points correspondences of a problem of `kind` (0 .. 5) - *chunks chunks of
+ * 64 * *points_per_lane correspondences (on the matrix-core forms: 2 * points_per_lane groups of 32) - on the fp32-queue form
+ * (matrix_core 0) or the matrix-core form (1), in the single-problem launch (group_form 0) or as a member of a lock-step group (1).
+ * Like pl_debug_group_slices it assumes coordinates and threshold in the pre-filters' range, so the kind, the size and
+ * POSELIB_AMD_NO_MFMA decide whether a matrix-core form exists: where none does, matrix_core 1 returns PL_ERR_UNSUPPORTED.  Kinds 4
+ * (tangent) and 5 (1D-radial) have neither a matrix-core nor a group form: PL_ERR_INVALID, as for n_points 0 or an unknown kind.
+ * Host arithmetic only: no device is touched.  tests/ derives its point counts from this entry. */
+int pl_debug_score_shape(int kind, uint32_t n_points, int matrix_core, int group_form, uint32_t *chunks,
+                         uint32_t *points_per_lane);
+/* Diagnostic: pl_debug_score_stream with the scorer's grid in the caller's hand, and the group form of the same kernels.
+ * A member is one resident problem with a model list of its own (models / n / max_error / counts / scores as in
+ * pl_debug_score_stream) and `slices`, the hypothesis slices - workgroups of 8 wavefronts - per chunk of correspondences:
+ * 0 = the rule production uses (route 0: pl_debug_score_stream's; route 2: the group's rule for the chunk total of the launch),
+ * 1 .. the launch's limit = a grid of exactly that many.  Out: path_used (as pl_debug_score_stream), slices_used, chunks.
+ *   route 0  the single-problem launch; one member of any kind.  pl_debug_score_stream is this route with slices 0.
+ *   route 2  the group form, kinds 0 - 3: a device-resident argument table whose slot 0 is INACTIVE - with buffers of its own,
+ *            filled with a pattern; *idle_changed receives the number of 32-bit words the launches changed in them, which must
+ *            be 0 - followed by the 1 .. 4 members, all of one kind.  Every member has buffers of its own; its list is prepared
+ *            by the helpers route 0 uses (hypothesis-ordered copies, live list, fp16 operands) on the group's chunk shape, its
+ *            table entry is wired as a batch step wires it, and the launches are the ones a group's batch step runs: the group
+ *            scorer dispatch - matrix-core and fp32-queue members in one call, each kernel launched if a member needs it - and
+ *            the group's finalize.  Members may differ in size, threshold, list length and scorer path.
+ * Before the launch every (chunk, hypothesis) partial is set to all-ones: a partial no wavefront writes shows as a wrong count.
+ * PL_ERR_INVALID: another route, slices beyond the limit, route 0 with more or fewer than one member, route 2 with no or more
+ * than four members, members of different kinds, a tangent or 1D-radial member, an empty list or an empty problem. */
+typedef struct pl_debug_score_member {
+    pl_problem *problem;
+    const void *models;
+    size_t n;
+    double max_error;
+    uint32_t *counts; /* n entries, may be NULL */
+    double *scores;   /* n entries, may be NULL */
+    uint32_t slices;
+    uint32_t slices_used; /* out */
+    uint32_t chunks;      /* out */
+    int32_t path_used;    /* out */
+} pl_debug_score_member;
+int pl_debug_score_stream_ex(int route, pl_debug_score_member *members, size_t num_members, uint32_t *idle_changed);
 /* Diagnostic entry: the scalar math of the device kernels, element-wise on `n` doubles (n <= 2^28) - fn 0: the cube of
  * the LM's Nielsen update (optim/lm_impl.h:124 std::pow(., 3)), 1: sqrt, 2: reciprocal, 3 .. 6: cbrt / cos / sin / acos
  * of pl_libm.h, 7 / 8: sine / cosine of pl_sincos (the quaternion exponential of the LM steps), 9: pf_half_rn((float)x),

@@ -80,6 +80,11 @@ class Shard(C.Structure):  # pl_shard
     _fields_ = [("rank", i32), ("world", i32), ("allgather", ALLGATHER_FN), ("user", C.c_void_p)]
 
 
+class DebugScoreMember(C.Structure):  # pl_debug_score_member
+    _fields_ = [("problem", C.c_void_p), ("models", C.c_void_p), ("n", C.c_size_t), ("max_error", f64), ("counts", C.c_void_p),
+                ("scores", C.c_void_p), ("slices", u32), ("slices_used", u32), ("chunks", u32), ("path_used", i32)]
+
+
 class PoseLibAmdError(RuntimeError):
     pass
 
@@ -172,6 +177,8 @@ def _declare(L):
         "pl_ransac_run_sharded": (cint, [vp, opt, P(Shard), vp, vp, stats]),
         "pl_score_model": (cint, [vp, vp, dbl, P(C.c_uint64), P(dbl)]),
         "pl_debug_score_stream": (cint, [vp, vp, sz, dbl, vp, vp, P(C.c_int32)]),
+        "pl_debug_score_shape": (cint, [cint, C.c_uint32, cint, cint, P(C.c_uint32), P(C.c_uint32)]),
+        "pl_debug_score_stream_ex": (cint, [cint, P(DebugScoreMember), sz, P(C.c_uint32)]),
         "pl_debug_device_math": (cint, [cint, vp, sz, vp]),
         "pl_debug_device_math2": (cint, [cint, vp, vp, sz, vp]),
         "pl_refine_model": (cint, [vp, P(BundleOptions), cam, vp, vp, P(C.c_uint32)]),
@@ -212,6 +219,7 @@ EXPORTED_SYMBOLS = [
     "pl_estimate_shared_focal_relative_pose", "pl_solve_focal_batch", "pl_p35pf", "pl_relpose_6pt_shared_focal", "pl_set_lm_mode",
     "pl_abi_version", "pl_problem_create_tangent", "pl_debug_inlier_mask", "pl_debug_tangent_chunk",
     "pl_p5lp_radial", "pl_debug_radial1d_chunk", "pl_debug_radial1d_generate", "pl_debug_group_slices", "pl_debug_generate",
+    "pl_debug_score_shape", "pl_debug_score_stream_ex",
     # (pl_estimate_1D_radial_absolute_pose and pl_ransac_1D_radial_pnp carry the reference's capital D: declared above, exported by the
     # library, but outside the lower-case pattern tests/test_cabi_surface.py lists the header's symbols with)
 ]

@@ -442,6 +442,39 @@ def group_slices(kind: int, n_points: int, iterations: int, launch_chunks: int) 
     return L.check(L.lib().pl_debug_group_slices(int(kind), int(n_points), int(iterations), int(launch_chunks)))
 
 
+def score_shape(kind: int, n_points: int, matrix_core: bool, group_form: bool):
+    """Diagnostic (pl_debug_score_shape): (chunks, points per lane) of the streaming scorer - fp32-queue or matrix-core form, single
+    launch or group member - for n_points correspondences; a chunk holds 64 * points_per_lane of them.  None where no problem of
+    this kind and size is scored on the matrix cores.  Host arithmetic only: works without a device."""
+    chunks, per_lane = C.c_uint32(0), C.c_uint32(0)
+    rc = L.lib().pl_debug_score_shape(int(kind), int(n_points), int(bool(matrix_core)), int(bool(group_form)), C.byref(chunks),
+                                      C.byref(per_lane))
+    if rc == L.PL_ERR_UNSUPPORTED:
+        return None
+    L.check(rc)
+    return chunks.value, per_lane.value
+
+
+def score_stream_group(members):
+    """Diagnostic (pl_debug_score_stream_ex, route 2): the group form of the streaming scorers.  members: up to four
+    (problem, models, max_error, slices) of one kind (0 - 3), slices 0 = the group's own rule; models as Problem.score_stream takes
+    them.  One launch scores them all behind an inactive table slot.  Returns ([{"counts", "scores", "path", "slices", "chunks"}
+    per member], words the launch changed in the inactive slot's buffers - which must be 0)."""
+    arr = (L.DebugScoreMember * max(len(members), 1))()
+    keep = []
+    for i, (problem, models, max_error, slices) in enumerate(members):
+        n, flat = problem._flat_models(models)
+        cnt = np.zeros(max(n, 1), dtype=np.uint32)
+        sc = np.zeros(max(n, 1), dtype=np.float64)
+        keep.append((n, flat, cnt, sc))
+        arr[i] = L.DebugScoreMember(problem._h, _ptr(flat), n, float(max_error), _ptr(cnt), _ptr(sc), int(slices), 0, 0, 0)
+    idle = C.c_uint32(0)
+    L.check(L.lib().pl_debug_score_stream_ex(2, arr, C.c_size_t(len(members)), C.byref(idle)))
+    out = [{"counts": cnt[:n], "scores": sc[:n], "path": arr[i].path_used, "slices": arr[i].slices_used, "chunks": arr[i].chunks}
+           for i, (n, _, cnt, sc) in enumerate(keep)]
+    return out, idle.value
+
+
 def ransac_batch(problems, opts, max_in_flight=4, group_size=16):
     """Many device-resident problems in one call (pl_ransac_batch): results of `problems[i].run(opts[i])`, bit for bit.
     Problems of the same kind advance in lock-step groups of `group_size` through one launch sequence."""
@@ -671,21 +704,29 @@ class Problem:
             L.check(L.lib().pl_score_model(self._h, _ptr(M), C.c_double(max_error), C.byref(cnt), C.byref(sc)))
         return sc.value, cnt.value
 
-    def score_stream(self, models, max_error):
-        """Diagnostic (pl_debug_score_stream): a list of models through the streaming scorer of the main loop, i.e.
-        through the conservative pre-filter in front of the exact evaluation.  models: (n, 7) array of q, t for pose
-        problems, (n, 3, 3) matrices otherwise.  Returns (counts, scores, path) with path 2 = matrix-core filter,
-        1 = fp32 filter, 0 = no filter."""
+    def _flat_models(self, models):
         m = np.ascontiguousarray(models, dtype=np.float64)
         n = m.shape[0]
         if self.kind in _POSE_KINDS:
             assert m.shape == (n, 7)
-            flat = np.ascontiguousarray(m.reshape(-1))  # pl_camera_pose = 7 packed doubles
-        else:
-            assert m.shape == (n, 3, 3)
-            flat = np.ascontiguousarray(np.transpose(m, (0, 2, 1)).reshape(-1))  # column-major
+            return n, np.ascontiguousarray(m.reshape(-1))  # pl_camera_pose = 7 packed doubles
+        assert m.shape == (n, 3, 3)
+        return n, np.ascontiguousarray(np.transpose(m, (0, 2, 1)).reshape(-1))  # column-major
+
+    def score_stream(self, models, max_error, slices=0):
+        """Diagnostic (pl_debug_score_stream): a list of models through the streaming scorer of the main loop, i.e.
+        through the conservative pre-filter in front of the exact evaluation.  models: (n, 7) array of q, t for pose
+        problems, (n, 3, 3) matrices otherwise.  Returns (counts, scores, path) with path 2 = matrix-core filter,
+        1 = fp32 filter, 0 = no filter.  slices > 0 (pl_debug_score_stream_ex, route 0): a grid of exactly that many
+        workgroups per chunk of correspondences instead of the entry's own rule."""
+        n, flat = self._flat_models(models)
         cnt = np.zeros(max(n, 1), dtype=np.uint32)
         sc = np.zeros(max(n, 1), dtype=np.float64)
+        if slices:
+            m = L.DebugScoreMember(self._h, _ptr(flat), n, float(max_error), _ptr(cnt), _ptr(sc), int(slices), 0, 0, 0)
+            L.check(L.lib().pl_debug_score_stream_ex(0, C.byref(m), C.c_size_t(1), None))
+            assert m.slices_used == int(slices) or n == 0
+            return cnt[:n], sc[:n], m.path_used
         path = C.c_int32(0)
         L.check(L.lib().pl_debug_score_stream(self._h, _ptr(flat), C.c_size_t(n), C.c_double(max_error), _ptr(cnt),
                                               _ptr(sc), C.byref(path)))

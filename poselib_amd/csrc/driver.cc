@@ -2539,8 +2539,47 @@ int pl_score_model(pl_problem *p, const void *model, double max_error, uint64_t 
 // Diagnostic: an arbitrary list of models through the STREAMING scorer of the main loop (k_gather_models -> k_live_list / k_gather_shadow16 ->
 // k_score_mfma / k_score_queue -> k_finalize2), i.e. through the conservative pre-filters, instead of the sequential
 // scorer pl_score_model uses.  Lets tests feed adversarial models / points to the filters on the device.
-int pl_debug_score_stream(pl_problem *p, const void *models, size_t n, double max_error, uint32_t *counts,
-                          double *scores, int32_t *path_used) {
+namespace {
+// the caller's models as records in list order (pl_camera_pose[n] or double[n][9] column-major)
+void debug_score_records(const pl_problem *p, const void *models, uint32_t H, std::vector<double> &recs) {
+    const bool pose_kind = (p->kind == EST_ABS || p->kind == EST_REL || p->kind == EST_RELT || p->kind == EST_RAD1D);
+    recs.assign((size_t)H * kModelStride, 0.0);
+    for (uint32_t k = 0; k < H; ++k) {
+        if (pose_kind)
+            record_from_pose(static_cast<const pl_camera_pose *>(models) + k, p->kind == EST_REL || p->kind == EST_RELT, &recs[(size_t)k * kModelStride]);
+        else
+            store_matrix_model(&recs[(size_t)k * kModelStride], mat_from_colmajor(static_cast<const double *>(models) + 9 * (size_t)k));
+    }
+}
+// What the generator, the compaction and the operand kernels of a batch step leave for the scorer, for a list the host wrote: the
+// records in `b.models` in list order, the hypothesis-ordered copies, and the fp16 operands (absolute pose: live list, rank and the
+// correspondences' rows as well) of the scorer `a` was wired for.  The partials are set to all-ones first: a (chunk, hypothesis)
+// entry no wavefront writes then reads as a count of 2^32 - 1 and a NaN score, whatever an earlier launch left there.
+int debug_score_prepare(Context *c, const pl_problem *p, const GroupArgs &a, const BatchBuffers &b, const BatchSizes &z,
+                        const std::vector<double> &recs, const std::vector<uint32_t> &ident, uint32_t H) {
+    BatchCtl hc;
+    std::memset(&hc, 0, sizeof(hc));
+    hc.num_hyp = H;
+    HIP_TRY(hipMemsetAsync(b.ctl, 0, z.ctl, c->stream));
+    HIP_TRY(hipMemcpyAsync(b.ctl, &hc, sizeof(hc), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(b.models, recs.data(), sizeof(double) * recs.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(b.slots, ident.data(), sizeof(uint32_t) * H, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(b.part_count, 0xff, z.part_count, c->stream));
+    HIP_TRY(hipMemsetAsync(b.part_score, 0xff, z.part_score, c->stream));
+    HIP_TRY(launch_gather_models(b.ctl, b.slots, b.models, H, b.shadow, b.compact64, c->stream));
+    const Shadow16Params &s16 = a.comp.s16;
+    if (s16.out && s16.sampson == 0) // as in the main loop: live list, operand rows of the live hypotheses and of the points
+        HIP_TRY(launch_abs16(b.ctl, b.slots, b.models, H, p->ps, s16, c->stream));
+    else if (s16.out && s16.sampson == 2)
+        HIP_TRY(launch_hom16(b.ctl, b.slots, b.models, H, s16.thr, s16.out, c->stream));
+    else if (s16.out)
+        HIP_TRY(launch_sampson16(b.ctl, b.slots, b.models, H, s16.out, c->stream));
+    return PL_OK;
+}
+// the single launch: slices_in 0 = the rule min(1536 / chunks, H) in workgroups of kScoreThreads, otherwise a grid of exactly
+// slices_in workgroups of 8 wavefronts per chunk
+int debug_score_single(pl_problem *p, const void *models, size_t n, double max_error, uint32_t slices_in, uint32_t *counts,
+                       double *scores, int32_t *path_used, uint32_t *slices_used, uint32_t *chunks_used) {
     if (!p || (!models && n))
         return fail(PL_ERR_INVALID, "problem / models pointer is null");
     if (n > (1u << 22))
@@ -2553,6 +2592,16 @@ int pl_debug_score_stream(pl_problem *p, const void *models, size_t n, double ma
         return fail(PL_ERR_INVALID, "problem lives on another device than the calling thread's");
     if (path_used)
         *path_used = 0;
+    if (slices_used)
+        *slices_used = 0;
+    if (chunks_used)
+        *chunks_used = 0;
+    const double thr2 = max_error * max_error;
+    const PrefilterArgs pf = problem_prefilter(p, thr2);
+    const bool use_mfma = score_uses_mfma(p->kind, p->n, pf);
+    const uint32_t chunks = score_chunks(p->kind, p->n, true, use_mfma);
+    if (slices_in > score_slice_limit(p->kind, chunks, use_mfma))
+        return fail(PL_ERR_INVALID, "slices beyond what the scorer's launch takes for this problem");
     if (n == 0)
         return PL_OK;
     const uint32_t H = (uint32_t)n;
@@ -2565,28 +2614,22 @@ int pl_debug_score_stream(pl_problem *p, const void *models, size_t n, double ma
         }
         return PL_OK;
     }
-    const bool pose_kind = (p->kind == EST_ABS || p->kind == EST_REL || p->kind == EST_RELT || p->kind == EST_RAD1D);
-    std::vector<double> recs((size_t)H * kModelStride);
+    std::vector<double> recs;
     std::vector<uint32_t> ident(H);
-    for (uint32_t k = 0; k < H; ++k) {
+    for (uint32_t k = 0; k < H; ++k)
         ident[k] = k;
-        if (pose_kind)
-            record_from_pose(static_cast<const pl_camera_pose *>(models) + k, p->kind == EST_REL || p->kind == EST_RELT, &recs[(size_t)k * kModelStride]);
-        else
-            store_matrix_model(&recs[(size_t)k * kModelStride], mat_from_colmajor(static_cast<const double *>(models) + 9 * (size_t)k));
-    }
-    const double thr2 = max_error * max_error;
+    debug_score_records(p, models, H, recs);
     // the buffers and arguments of a batch step whose H "iterations" hold one model each (no sampler: B = 0): the scorer's part of
     // them is used
     BatchRun run{};
     run.kind = p->kind;
     run.pts = p->ps;
     run.thr2 = thr2;
-    run.pf = problem_prefilter(p, thr2);
+    run.pf = pf;
     BatchShape s{};
     s.Bl = H, s.slots = 1;
-    s.use_mfma = score_uses_mfma(p->kind, p->n, run.pf);
-    s.chunks = score_chunks(p->kind, p->n, true, s.use_mfma);
+    s.use_mfma = use_mfma;
+    s.chunks = chunks;
     s.point_rows = abs16_point_rows(p->n);
     const BatchSizes z = batch_step_sizes(p->kind, s);
     BatchBuffers bb;
@@ -2596,23 +2639,13 @@ int pl_debug_score_stream(pl_problem *p, const void *models, size_t n, double ma
     bb.nan_bits = nullptr; // (no generator: k_live_list reads the records' flag words)
     GroupArgs a;
     wire_batch_step(a, run, s, bb);
-    BatchCtl hc;
-    std::memset(&hc, 0, sizeof(hc));
-    hc.num_hyp = H;
-    HIP_TRY(hipMemsetAsync(bb.ctl, 0, z.ctl, c->stream));
-    HIP_TRY(hipMemcpyAsync(bb.ctl, &hc, sizeof(hc), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(bb.models, recs.data(), sizeof(double) * recs.size(), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(bb.slots, ident.data(), sizeof(uint32_t) * H, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(launch_gather_models(bb.ctl, bb.slots, bb.models, H, bb.shadow, bb.compact64, c->stream));
-    const Shadow16Params &s16 = a.comp.s16;
-    if (s16.out && s16.sampson == 0) // as in the main loop: live list, operand rows of the live hypotheses and of the points
-        HIP_TRY(launch_abs16(bb.ctl, bb.slots, bb.models, H, p->ps, s16, c->stream));
-    else if (s16.out && s16.sampson == 2)
-        HIP_TRY(launch_hom16(bb.ctl, bb.slots, bb.models, H, s16.thr, s16.out, c->stream));
-    else if (s16.out)
-        HIP_TRY(launch_sampson16(bb.ctl, bb.slots, bb.models, H, s16.out, c->stream));
-    const int path = s16.out ? 2 : (run.pf.enabled ? 1 : 0);
-    const uint32_t slices = std::max<uint32_t>(1u, std::min<uint32_t>(1536u / s.chunks, H));
+    rc = debug_score_prepare(c, p, a, bb, z, recs, ident, H);
+    if (rc != PL_OK)
+        return rc;
+    const int path = a.comp.s16.out ? 2 : (run.pf.enabled ? 1 : 0);
+    // launch_score counts slices in workgroups of kScoreThreads; the streaming kernels run 8 wavefronts per workgroup
+    const uint32_t per = (uint32_t)kStreamWaves * 64u / (uint32_t)kScoreThreads;
+    const uint32_t slices = slices_in ? slices_in * per : std::max<uint32_t>(1u, std::min<uint32_t>(1536u / s.chunks, H));
     HIP_TRY(launch_score(p->kind, a.score, slices, c->stream));
     HIP_TRY(launch_finalize(a.rec.f, c->stream));
     if (counts)
@@ -2622,8 +2655,184 @@ int pl_debug_score_stream(pl_problem *p, const void *models, size_t n, double ma
     HIP_TRY(wait_stream(c));
     if (path_used)
         *path_used = path;
+    if (slices_used)
+        *slices_used = std::max<uint32_t>(1u, slices / per);
+    if (chunks_used)
+        *chunks_used = chunks;
     return PL_OK;
 }
+constexpr size_t kDebugScoreMembers = 4;
+// The group form: a device-resident table whose slot 0 is inactive and whose slots 1 .. count hold the caller's members, every slot
+// on an arena of its own (pack_batch_buffers), wired by wire_batch_step with the group's chunk shape, scored by launch_group_score
+// and finished by launch_group_finalize_records - the two launches a group's batch step runs behind its operand kernels.
+int debug_score_group(pl_debug_score_member *m, size_t count, uint32_t *idle_changed) {
+    if (!m || count == 0 || count > kDebugScoreMembers)
+        return fail(PL_ERR_INVALID, "the group form takes 1 .. 4 members");
+    for (size_t i = 0; i < count; ++i) {
+        if (!m[i].problem || !m[i].models || m[i].n == 0 || m[i].n > (1u << 22) || m[i].problem->n == 0)
+            return fail(PL_ERR_INVALID, "member: problem / models missing, no correspondences, or n outside 1 .. 2^22");
+        if (m[i].problem->kind != m[0].problem->kind)
+            return fail(PL_ERR_INVALID, "the members of a group are of one kind");
+    }
+    const int kind = m[0].problem->kind;
+    if (kind != EST_ABS && kind != EST_REL && kind != EST_FUND && kind != EST_HOM)
+        return fail(PL_ERR_INVALID, "tangent and 1D-radial problems have no group form");
+    Context *c;
+    int rc = get_context(&c);
+    if (rc != PL_OK)
+        return rc;
+    for (size_t i = 0; i < count; ++i)
+        if (m[i].problem->device != c->device)
+            return fail(PL_ERR_INVALID, "problem lives on another device than the calling thread's");
+    struct Slot {
+        BatchRun run{};
+        BatchShape s{};
+        BatchSizes z{};
+        BatchBuffers b{};
+        size_t bytes = 0;
+        char *arena = nullptr;
+        ~Slot() {
+            if (arena)
+                (void)hipFree(arena);
+        }
+    } slot[1 + kDebugScoreMembers];
+    struct Scratch { // freed on every path
+        void *p = nullptr;
+        ~Scratch() {
+            if (p)
+                (void)hipFree(p);
+        }
+    } dtable;
+    GroupArgs ha[1 + kDebugScoreMembers];
+    GroupDims dims{};
+    dims.G = (uint32_t)count + 1;
+    dims.P = group_points_per_lane(kind);
+    uint32_t launch_chunks = 0; // of the members k_score_mfma_g serves (run_group)
+    for (size_t i = 0; i < count; ++i) {
+        Slot &t = slot[i + 1];
+        const pl_problem *p = m[i].problem;
+        t.run.kind = kind;
+        t.run.pts = p->ps;
+        t.run.thr2 = m[i].max_error * m[i].max_error;
+        t.run.pf = problem_prefilter(p, t.run.thr2);
+        t.run.init_max = 0xffffffffu; // (no hypothesis improves on this: k_records_g lists none)
+        t.s.Bl = (uint32_t)m[i].n, t.s.slots = 1;
+        t.s.use_mfma = score_uses_mfma(kind, p->n, t.run.pf);
+        t.s.chunks = group_member_chunks(kind, t.s.use_mfma, p->n);
+        t.s.point_rows = t.s.chunks * 64u * (uint32_t)dims.P;
+        if (m[i].slices > score_slice_limit(kind, t.s.chunks, false))
+            return fail(PL_ERR_INVALID, "slices beyond what the scorer's launch takes for this member");
+        t.z = batch_step_sizes(kind, t.s);
+        if (t.s.use_mfma)
+            launch_chunks += t.s.chunks;
+    }
+    slot[0].run = slot[1].run, slot[0].s = slot[1].s, slot[0].z = slot[1].z; // the inactive slot: a copy of the first member's
+    for (size_t k = 0; k <= count; ++k) {
+        Slot &t = slot[k];
+        BatchBuffers unused;
+        t.bytes = pack_batch_buffers(nullptr, t.z, unused);
+        HIP_TRY(hipMalloc((void **)&t.arena, t.bytes));
+        HIP_TRY(hipMemsetAsync(t.arena, k == 0 ? 0xa5 : 0, t.bytes, c->stream));
+        pack_batch_buffers(t.arena, t.z, t.b);
+        t.b.nan_bits = nullptr; // (no generator: k_live_list reads the records' flag words)
+        t.b.host_meta = nullptr, t.b.host_models = nullptr, t.b.host_ctl = nullptr;
+        wire_batch_step(ha[k], t.run, t.s, t.b);
+    }
+    ha[0].active = 0;
+    for (size_t i = 0; i < count; ++i) {
+        GroupArgs &a = ha[i + 1];
+        const Slot &t = slot[i + 1];
+        const uint32_t H = t.s.Bl;
+        a.slices = m[i].slices ? m[i].slices
+                               : group_score_slices(kind, t.s.use_mfma, group_expected_hypotheses(kind, H, H), H, t.s.chunks, launch_chunks);
+        dims.max_B = std::max(dims.max_B, H);
+        dims.max_hcap = std::max(dims.max_hcap, a.score.hyp_capacity);
+        dims.max_chunks = std::max(dims.max_chunks, a.chunks);
+        dims.max_slices = std::max(dims.max_slices, a.slices);
+        dims.any_mfma |= a.use_mfma;
+        dims.any_queue |= a.use_mfma ? 0u : 1u;
+        std::vector<double> recs;
+        std::vector<uint32_t> ident(H);
+        for (uint32_t k = 0; k < H; ++k)
+            ident[k] = k;
+        debug_score_records(m[i].problem, m[i].models, H, recs);
+        rc = debug_score_prepare(c, m[i].problem, a, t.b, t.z, recs, ident, H);
+        if (rc != PL_OK)
+            return rc;
+        HIP_TRY(hipStreamSynchronize(c->stream)); // (recs / ident leave scope)
+    }
+    ha[0].slices = ha[1].slices;
+    HIP_TRY(hipMalloc(&dtable.p, sizeof(GroupArgs) * dims.G));
+    HIP_TRY(hipMemcpyAsync(dtable.p, ha, sizeof(GroupArgs) * dims.G, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(launch_group_score(kind, static_cast<const GroupArgs *>(dtable.p), dims, c->stream));
+    HIP_TRY(launch_group_finalize_records(static_cast<const GroupArgs *>(dtable.p), dims, c->stream));
+    for (size_t i = 0; i < count; ++i) {
+        const Slot &t = slot[i + 1];
+        if (m[i].counts)
+            HIP_TRY(hipMemcpyAsync(m[i].counts, t.b.count, sizeof(uint32_t) * t.s.Bl, hipMemcpyDeviceToHost, c->stream));
+        if (m[i].scores)
+            HIP_TRY(hipMemcpyAsync(m[i].scores, t.b.score, sizeof(double) * t.s.Bl, hipMemcpyDeviceToHost, c->stream));
+    }
+    std::vector<uint32_t> idle(slot[0].bytes / 4);
+    HIP_TRY(hipMemcpyAsync(idle.data(), slot[0].arena, idle.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(wait_stream(c));
+    uint32_t changed = 0;
+    for (uint32_t w : idle)
+        changed += w != 0xa5a5a5a5u ? 1u : 0u;
+    if (idle_changed)
+        *idle_changed = changed;
+    for (size_t i = 0; i < count; ++i) {
+        m[i].path_used = ha[i + 1].comp.s16.out ? 2 : (slot[i + 1].run.pf.enabled ? 1 : 0);
+        m[i].slices_used = ha[i + 1].slices;
+        m[i].chunks = ha[i + 1].chunks;
+    }
+    return PL_OK;
+}
+} // namespace
+int pl_debug_score_stream(pl_problem *p, const void *models, size_t n, double max_error, uint32_t *counts,
+                          double *scores, int32_t *path_used) {
+    return debug_score_single(p, models, n, max_error, 0, counts, scores, path_used, nullptr, nullptr);
+}
+// Diagnostic: pl_debug_score_stream with the scorer's grid in the caller's hand (route 0, one member), and the group form of the same
+// kernels (route 2, up to four members behind an inactive slot); the header states the contract.
+int pl_debug_score_stream_ex(int route, pl_debug_score_member *members, size_t num_members, uint32_t *idle_changed) {
+    if (idle_changed)
+        *idle_changed = 0;
+    if (route != 0 && route != 2)
+        return fail(PL_ERR_INVALID, "route: 0 single launch, 2 group form");
+    if (route == 2)
+        return debug_score_group(members, num_members, idle_changed);
+    if (!members || num_members != 1)
+        return fail(PL_ERR_INVALID, "the single launch takes one member");
+    pl_debug_score_member &m = members[0];
+    return debug_score_single(m.problem, m.models, m.n, m.max_error, m.slices, m.counts, m.scores, &m.path_used, &m.slices_used, &m.chunks);
+}
+// Diagnostic: chunks of correspondences and points per lane of the streaming scorers, as score_shape (single launch) or
+// group_member_chunks (group form) cut a problem.  No device call.
+int pl_debug_score_shape(int kind, uint32_t n_points, int matrix_core, int group_form, uint32_t *chunks, uint32_t *points_per_lane) {
+    const bool four = kind == EST_ABS || kind == EST_REL || kind == EST_FUND || kind == EST_HOM;
+    if (!(four || kind == EST_RELT || kind == EST_RAD1D) || n_points == 0 || !chunks || !points_per_lane)
+        return fail(PL_ERR_INVALID, "pl_debug_score_shape: kind 0 .. 5, n_points > 0, output pointers");
+    if (!four && (matrix_core || group_form))
+        return fail(PL_ERR_INVALID, "tangent and 1D-radial problems have neither a matrix-core nor a group form");
+    if (matrix_core) { // as pl_debug_group_slices: the prefilter of a problem with in-range coordinates and threshold is assumed
+        PrefilterArgs pf{};
+        pf.enabled = 1;
+        pf.g16 = pf.t16 = pf.h16 = 1.0f, pf.thr = 1.0f;
+        if (!score_uses_mfma(kind, n_points, pf))
+            return fail(PL_ERR_UNSUPPORTED, "no problem of this kind and size is scored on the matrix cores");
+    }
+    if (group_form) {
+        *chunks = group_member_chunks(kind, matrix_core != 0, n_points);
+        *points_per_lane = (uint32_t)((matrix_core && (kind == EST_REL || kind == EST_FUND)) ? group_mfma2_points_per_lane(kind)
+                                                                                           : group_points_per_lane(kind));
+    } else {
+        *chunks = score_chunks(kind, n_points, true, matrix_core != 0);
+        *points_per_lane = (uint32_t)score_points_per_lane(kind, n_points, true, matrix_core != 0);
+    }
+    return PL_OK;
+}
+
 
 int pl_debug_device_math(int fn, const double *x, size_t n, double *out) {
     if (fn < 0 || fn >= kDeviceMathFns)

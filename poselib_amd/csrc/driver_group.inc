@@ -329,8 +329,12 @@ void group_stage_in(GroupItem *const *pit, uint32_t count) {
 // members share it - slices = ceil(kGroupScoreWorkgroups / launch_chunks), never more than `solo`, never less than one per
 // (member, chunk).  A full group of long runs (the flagship: 16 members x 16 chunks x 49 slices = 12 544 workgroups for 512
 // resident slots, a workgroup's LDS held until its slowest wavefront is done) gets fewer, longer-lived workgroups; a launch with
-// few members, or short lists, keeps exactly what it had.  No result depends on the count: every (chunk, hypothesis) partial
-// comes from one wavefront, whichever it is.  Where kGroupScoreWorkgroups comes from: profiles/group_slices.md.  The other scorers
+// few members, or short lists, keeps exactly what it had.  No count depends on the slice count, and no decision: every (chunk,
+// hypothesis) partial comes from one wavefront, whichever it is, and candidates are re-scored sequentially.  The last bits of a
+// tree-order score can: a hypothesis's terms are added up per drain batch of its unit's queue, where a batch ends depends on the
+// unit's other hypotheses, and the tail rule of unit_of_ticket cuts the end of the list into units of 16, 32 or 64 by the number
+// of wavefronts per chunk (a hypothesis in the same unit under two slice counts gets the same bits; measured otherwise: one unit
+// in the last place, tests/test_gpu_score_stream.py).  Where kGroupScoreWorkgroups comes from: profiles/group_slices.md.  The other scorers
 // (two-view, homography, fp32 queue, tangent, 1D-radial) still split per workgroup and keep `solo`.
 constexpr uint32_t kGroupScoreWorkgroups = 3328;
 static uint32_t group_score_slices(int kind, bool use_mfma, size_t hexp, uint32_t B, uint32_t chunks, uint32_t launch_chunks) {

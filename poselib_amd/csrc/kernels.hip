@@ -3669,6 +3669,21 @@ uint32_t score_chunks(int est, uint32_t n, bool streaming, bool mfma) {
     return c;
 }
 
+static_assert(kQueueThreads == 64 * kStreamWaves && kMfmaThreads == 64 * kStreamWaves, "pl_kernels.h: kStreamWaves");
+int score_points_per_lane(int est, uint32_t n, bool streaming, bool mfma) {
+    uint32_t c;
+    int P;
+    score_shape(est, n, streaming, mfma, c, P);
+    return P;
+}
+// Most hypothesis slices (workgroups per chunk of correspondences) a single problem's streaming launch of `chunks` chunks takes.
+// The matrix-core forms of absolute pose and of the Sampson scores stop at one resident round of 512 workgroups (launch_score_est);
+// the others at the 1536 workgroups the callers' rules stop at.
+uint32_t score_slice_limit(int est, uint32_t chunks, bool mfma) {
+    const uint32_t round = (mfma && (est == EST_ABS || est == EST_REL || est == EST_FUND)) ? 512u : 1536u;
+    return std::max<uint32_t>(1u, round / std::max<uint32_t>(1u, chunks));
+}
+
 // slice count of a matrix-core scorer launch: a multiple of 8 from 8 on (slice_chunk_of_workgroup keeps a slice on one XCD)
 static uint32_t xcd_slices(uint32_t s) { return std::max<uint32_t>(1u, s); }
 
@@ -3684,7 +3699,7 @@ static hipError_t launch_score_est(const ScoreArgs &a, uint32_t slices, hipStrea
             // two workgroups fit a CU (LDS): one resident round of 512 workgroups - a second, half-empty round would cost
             // as much as the first, and every workgroup pays the fp16 split of its chunk before its first hypothesis
             const uint32_t mslices = std::min<uint32_t>(slices * (uint32_t)kScoreThreads / (uint32_t)kMfmaThreads,
-                                                        std::max<uint32_t>(1u, 512u / chunks));
+                                                        score_slice_limit(E, chunks, true));
             const dim3 mgrid(xcd_slices(mslices), chunks);
             const dim3 mblock(kMfmaThreads);
 #define PL_M2_CASE(PP)                                                                                                 \
@@ -3734,7 +3749,7 @@ static hipError_t launch_score_est(const ScoreArgs &a, uint32_t slices, hipStrea
         if (streaming && a.shadow16) { // pre-filter on the matrix cores (PG = 2 P groups of 32 points per wave)
             // two workgroups fit a CU (LDS, registers): one resident round of 512 workgroups, as for the Sampson form above
             const uint32_t mslices = std::min<uint32_t>(slices * (uint32_t)kScoreThreads / (uint32_t)kMfmaThreads,
-                                                        std::max<uint32_t>(1u, 512u / chunks));
+                                                        score_slice_limit(E, chunks, true));
             const dim3 mgrid(xcd_slices(mslices), chunks);
             const dim3 mblock(kMfmaThreads);
             if (!a.points16)
@@ -3994,6 +4009,15 @@ template <int E> static hipError_t launch_group_score_est(const GroupArgs *args,
     return hipGetLastError();
 }
 
+// the scorers of every active problem of the table (launch_group_batch and the diagnostic entry pl_debug_score_stream_ex)
+hipError_t launch_group_score(int est, const GroupArgs *args, const GroupDims &d, hipStream_t stream) {
+    if (d.G == 0)
+        return hipSuccess;
+    hipError_t e = hipSuccess;
+    PL_DISPATCH_EST(est, e = launch_group_score_est<E>(args, d, stream));
+    return e;
+}
+
 // the generators of every active problem of the table: max_B = the longest member's iterations
 hipError_t launch_group_generate(int est, const GroupArgs *args, uint32_t max_B, uint32_t G, hipStream_t stream) {
     if (G == 0 || max_B == 0)
@@ -4020,7 +4044,7 @@ hipError_t launch_group_batch(int est, const GroupArgs *args, const GroupDims &d
         return e;
     if (ev0 && (e = hipEventRecord(ev0, stream)) != hipSuccess)
         return e;
-    PL_DISPATCH_EST(est, e = launch_group_score_est<E>(args, d, stream));
+    e = launch_group_score(est, args, d, stream);
     if (e != hipSuccess)
         return e;
     if (ev1 && (e = hipEventRecord(ev1, stream)) != hipSuccess)

@@ -22,6 +22,7 @@ struct PointSet {
 };
 
 constexpr int kScoreThreads = 256; // 4 wavefronts per workgroup
+constexpr int kStreamWaves = 8;    // wavefronts per workgroup of the streaming scorers (kQueueThreads, kMfmaThreads in kernels.hip)
 constexpr int kLMSeqPoints = 256; // up to this many correspondences k_lm sums in the reference's order (one thread per correspondence)
 #ifndef PL_LM_THREADS
 #define PL_LM_THREADS 512
@@ -211,6 +212,10 @@ hipError_t launch_lm2(int est, const PointSet &pts, LMTask *tasks, uint32_t num_
                       uint32_t max_iterations, void *states, double *partials, hipStream_t stream);
 // chunks = ceil(n / (kScoreThreads * P)); P is chosen inside from n (returned through *chunks_out)
 uint32_t score_chunks(int est, uint32_t n_points, bool prefilter, bool mfma = false);
+int score_points_per_lane(int est, uint32_t n_points, bool streaming, bool mfma); // ... and the P that goes with the chunks
+// most hypothesis slices (workgroups per chunk) launch_score gives a streaming launch of `chunks` chunks
+uint32_t score_slice_limit(int est, uint32_t chunks, bool mfma);
+// slices: workgroups of kScoreThreads per chunk; the streaming kernels run 8 wavefronts per workgroup, i.e. slices / 2 of them
 hipError_t launch_score(int est, const ScoreArgs &a, uint32_t slices, hipStream_t stream);
 int tangent_score_chunk(); // correspondences per chunk of k_score_tangent (EST_RELT)
 int radial1d_score_chunk(); // correspondences per chunk of k_score_radial1d (EST_RAD1D)
@@ -349,6 +354,9 @@ struct GroupDims { // grid extents: maxima over the active problems of the group
 // ev0 / ev1 (optional): recorded around the scoring launch(es)
 hipError_t launch_group_batch(int est, const GroupArgs *args, const GroupDims &dims, hipStream_t stream,
                               hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+// the scorer launch(es) of the step on their own: matrix-core members (d.any_mfma) and fp32-queue members (d.any_queue) of the
+// table, on a grid of (d.max_slices, d.max_chunks, d.G); workgroups beyond a member's own slices or chunks return
+hipError_t launch_group_score(int est, const GroupArgs *args, const GroupDims &d, hipStream_t stream);
 hipError_t launch_group_score_seq(int est, const SeqScoreArgs *args, uint32_t G, uint32_t max_cap, hipStream_t stream);
 hipError_t launch_group_select(const SelectArgs *args, uint32_t G, hipStream_t stream);
 hipError_t launch_group_mask(int est, const MaskArgs *args, uint32_t G, uint32_t max_n, hipStream_t stream);
