@@ -172,6 +172,54 @@ int pl_estimate_fundamental(const double *points2D_1, const double *points2D_2, 
 int pl_estimate_homography(const double *points2D_1, const double *points2D_2, size_t n, const pl_robust_options *opt,
                            double *H /* 9, column-major */, uint8_t *inliers, pl_ransac_stats *stats);
 
+/* ---- correspondences that are already in device memory (the output of a GPU matcher) ----
+ * A point set as the _dev entry points below take it: rows of `cols` contiguous elements, float or double, `row_stride` ELEMENTS
+ * apart - a contiguous N x cols block (row_stride == cols), a column view of a wider block, every k-th row of one.
+ *   - The data must be COMPLETE when the call is made: the library works on a non-blocking stream of its own and takes no
+ *     stream or event from the caller - synchronise the producer's stream first.
+ *   - The data is read only during the call; pl_problem_create*_dev copy into the problem's own block before they return.
+ *   - fp32 values are widened exactly, so a call equals the host call on the same values as doubles, bit for bit: model, mask
+ *     and stats.
+ *   - The memory must be DEVICE memory (hipMalloc and what builds on it) of the device the calling thread selected
+ *     (pl_set_device), and the allocation must hold every row.  A host pointer, managed memory, memory of another device, a
+ *     misaligned address, a row_stride below cols, another dtype or cols than the argument takes: PL_ERR_INVALID with a message
+ *     that names the cause, before anything is launched.  n == 0 (and n below the estimator's minimum where the host form
+ *     returns default stats) reads no device memory; data may then be null.
+ * Models, stats and the `inliers` bytes stay in host memory. */
+#define PL_F64 0
+#define PL_F32 1
+typedef struct {
+    const void *data;    /* device address of element (0, 0), on the device the calling thread selected */
+    int64_t row_stride;  /* ELEMENTS between consecutive rows, >= cols; the columns of a row are contiguous */
+    int32_t dtype;       /* PL_F64 / PL_F32 */
+    int32_t cols;        /* 2 or 3: what the entry point expects for that argument */
+} pl_device_points;
+/* The host forms above with device-resident points; everything else as there.  pl_estimate_absolute_pose_dev with
+ * estimate_focal_length: PL_ERR_UNSUPPORTED (that estimator reads the points on the host).  Not served from device memory:
+ * pl_estimate_batch, the focal-length estimators, pl_estimate_1D_radial_absolute_pose, the pl_ransac_* one-shot entries,
+ * pl_undistort_points. */
+int pl_estimate_absolute_pose_dev(const pl_device_points *points2D, const pl_device_points *points3D, size_t n,
+                                  const pl_robust_options *opt, pl_camera *camera, pl_camera_pose *pose, uint8_t *inliers,
+                                  pl_ransac_stats *stats);
+int pl_estimate_relative_pose_dev(const pl_device_points *points2D_1, const pl_device_points *points2D_2, size_t n,
+                                  const pl_camera *camera1, const pl_camera *camera2, const pl_robust_options *opt,
+                                  pl_camera_pose *pose, uint8_t *inliers, pl_ransac_stats *stats);
+int pl_estimate_fundamental_dev(const pl_device_points *points2D_1, const pl_device_points *points2D_2, size_t n,
+                                const pl_robust_options *opt, double *F /* 9, column-major */, uint8_t *inliers,
+                                pl_ransac_stats *stats);
+int pl_estimate_homography_dev(const pl_device_points *points2D_1, const pl_device_points *points2D_2, size_t n,
+                               const pl_robust_options *opt, double *H /* 9, column-major */, uint8_t *inliers,
+                               pl_ransac_stats *stats);
+/* Every check the _dev entry points make on one argument that should hold n rows of `cols` columns, with their return code:
+ * first the checks that need no device (null descriptor, null data with n > 0, cols, row_stride, dtype, alignment, n beyond
+ * 2^31 - 1: PL_ERR_INVALID even on a machine without a GPU), then - n > 0 only - the memory's kind, device and extent. */
+int pl_debug_check_device_points(const pl_device_points *d, size_t n, int cols);
+/* Diagnostic: what the _dev front-ends read back from the device in place of the host's passes over the points, for two N x 2
+ * sets.  out[8]: the centroids c1x c1y c2x c2y (the sums in index order, divided by n; zeros when `centroid` is 0), the scale of
+ * the homography / fundamental normalisation (mean distance from the centroids in index order / sqrt(2)), the largest
+ * |(x - c) / scale| over all four coordinates, the largest |coordinate| of the first set, and 0. */
+int pl_debug_point_stats_dev(const pl_device_points *x1, const pl_device_points *x2, size_t n, int centroid, double *out);
+
 /* ---- un-distortion as a stage of its own (BASELINE config 3: pixels of an OPENCV camera in front of the homography /
  * 7-point estimators, which take no camera).  Every point goes through Camera::unproject (misc/camera_models.h:98-102;
  * OPENCV: the iterative inverse of misc/camera_models.cc:972-990; SIMPLE_RADIAL / RADIAL: the Newton inverse of the radial
@@ -279,6 +327,12 @@ int pl_problem_create(int kind, const double *a, const double *b, size_t n, pl_p
  * camera is the identity camera.  Models are pl_camera_pose. */
 int pl_problem_create_tangent(const double *x1, const double *x2, size_t n, const pl_camera *camera1, const pl_camera *camera2,
                               pl_problem **out);
+/* pl_problem_create (kinds 0 - 3 and 5) and pl_problem_create_tangent from device-resident points (pl_device_points above): the
+ * problem's block is written on the device, nothing passes through the host, and the problem equals the one the host form
+ * builds from the same values.  Such problems go into pl_ransac_run / pl_ransac_batch like any other. */
+int pl_problem_create_dev(int kind, const pl_device_points *a, const pl_device_points *b, size_t n, pl_problem **out);
+int pl_problem_create_tangent_dev(const pl_device_points *x1, const pl_device_points *x2, size_t n, const pl_camera *camera1,
+                                  const pl_camera *camera2, pl_problem **out);
 void pl_problem_destroy(pl_problem *p);
 /* model: pl_camera_pose for kinds 0/1, double[9] column-major for kinds 2/3 */
 int pl_ransac_run(pl_problem *p, const pl_robust_options *opt, void *model, uint8_t *inliers, pl_ransac_stats *stats);

@@ -85,6 +85,13 @@ class DebugScoreMember(C.Structure):  # pl_debug_score_member
                 ("scores", C.c_void_p), ("slices", u32), ("slices_used", u32), ("chunks", u32), ("path_used", i32)]
 
 
+PL_F64, PL_F32 = 0, 1
+
+
+class DevicePoints(C.Structure):  # pl_device_points: rows of `cols` contiguous fp32 / fp64 elements in DEVICE memory
+    _fields_ = [("data", C.c_void_p), ("row_stride", C.c_int64), ("dtype", i32), ("cols", i32)]
+
+
 class PoseLibAmdError(RuntimeError):
     pass
 
@@ -131,6 +138,7 @@ def _declare(L):
     vp, sz, dbl, cint = C.c_void_p, C.c_size_t, C.c_double, C.c_int
     P = C.POINTER
     opt, stats, cam, pose = P(RobustOptions), P(RansacStats), P(Camera), P(CameraPose)
+    dpts = P(DevicePoints)
     sig = {
         "pl_default_ransac_options": (None, [P(RansacOptions)]),
         "pl_default_bundle_options": (None, [P(BundleOptions)]),
@@ -145,6 +153,14 @@ def _declare(L):
         "pl_estimate_relative_pose": (cint, [vp, vp, sz, cam, cam, opt, pose, vp, stats]),
         "pl_estimate_fundamental": (cint, [vp, vp, sz, opt, vp, vp, stats]),
         "pl_estimate_homography": (cint, [vp, vp, sz, opt, vp, vp, stats]),
+        "pl_estimate_absolute_pose_dev": (cint, [dpts, dpts, sz, opt, cam, pose, vp, stats]),
+        "pl_estimate_relative_pose_dev": (cint, [dpts, dpts, sz, cam, cam, opt, pose, vp, stats]),
+        "pl_estimate_fundamental_dev": (cint, [dpts, dpts, sz, opt, vp, vp, stats]),
+        "pl_estimate_homography_dev": (cint, [dpts, dpts, sz, opt, vp, vp, stats]),
+        "pl_problem_create_dev": (cint, [cint, dpts, dpts, sz, P(vp)]),
+        "pl_problem_create_tangent_dev": (cint, [dpts, dpts, sz, cam, cam, P(vp)]),
+        "pl_debug_check_device_points": (cint, [dpts, sz, cint]),
+        "pl_debug_point_stats_dev": (cint, [dpts, dpts, sz, cint, vp]),
         "pl_estimate_batch": (cint, [P(BatchItem), sz, cint]),
         "pl_estimate_batch_devices": (cint, [P(BatchItem), sz, P(C.c_int), cint, cint]),
         "pl_last_batch_report": (None, [P(BatchReport)]),
@@ -220,6 +236,8 @@ EXPORTED_SYMBOLS = [
     "pl_abi_version", "pl_problem_create_tangent", "pl_debug_inlier_mask", "pl_debug_tangent_chunk",
     "pl_p5lp_radial", "pl_debug_radial1d_chunk", "pl_debug_radial1d_generate", "pl_debug_group_slices", "pl_debug_generate",
     "pl_debug_score_shape", "pl_debug_score_stream_ex",
+    "pl_estimate_absolute_pose_dev", "pl_estimate_relative_pose_dev", "pl_estimate_fundamental_dev", "pl_estimate_homography_dev",
+    "pl_problem_create_dev", "pl_problem_create_tangent_dev", "pl_debug_check_device_points", "pl_debug_point_stats_dev",
     # (pl_estimate_1D_radial_absolute_pose and pl_ransac_1D_radial_pnp carry the reference's capital D: declared above, exported by the
     # library, but outside the lower-case pattern tests/test_cabi_surface.py lists the header's symbols with)
 ]

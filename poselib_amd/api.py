@@ -17,6 +17,8 @@ All numerical work happens in the HIP library; this file only marshals numpy arr
 from __future__ import annotations
 
 import ctypes as C
+import sys
+import threading
 
 import numpy as np
 
@@ -186,6 +188,104 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+# ---- points that are already on the GPU: torch tensors, or any object with __cuda_array_interface__ (recognised by attribute,
+# torch is never imported here).  They reach the library as pl_device_points descriptors - float32 or float64, rows any number of
+# elements apart - and are read where they lie: nothing is copied to the host.
+_tls = threading.local()  # .device: what set_device() selected on this thread (0 before the first call, like the library)
+_TORCH_DTYPES = {"torch.float32": L.PL_F32, "torch.float64": L.PL_F64}
+_TYPESTR_DTYPES = {"<f4": (L.PL_F32, 4), "<f8": (L.PL_F64, 8), "=f4": (L.PL_F32, 4), "=f8": (L.PL_F64, 8)}
+
+
+def _selected_device() -> int:
+    return getattr(_tls, "device", 0)
+
+
+def _is_torch_tensor(a) -> bool:
+    return hasattr(a, "is_cuda") and hasattr(a, "data_ptr") and hasattr(a, "stride")
+
+
+def _on_device(a) -> bool:
+    if _is_torch_tensor(a):
+        return bool(a.is_cuda)  # (a CPU tensor goes the host way, through numpy)
+    return not isinstance(a, np.ndarray) and hasattr(a, "__cuda_array_interface__")
+
+
+def _device_points(a, dim):
+    """(pl_device_points descriptor, rows, the object that owns the memory) of a GPU tensor or __cuda_array_interface__ object.
+    float32 / float64 only; a column stride other than 1 is made contiguous on the device (the object's own .contiguous());
+    a torch tensor must live on the device this thread selected, and its current stream is synchronised - the library reads the
+    memory on a stream of its own and takes none from the caller."""
+    if _is_torch_tensor(a):
+        if a.dim() != 2 or a.shape[1] != dim:
+            raise ValueError(f"expected an (N, {dim}) tensor")
+        dtype = _TORCH_DTYPES.get(str(a.dtype))
+        if dtype is None:
+            raise ValueError(f"device points must be float32 or float64, not {a.dtype}")
+        index = a.device.index
+        torch = sys.modules.get(type(a).__module__.split(".")[0])
+        if index is None and torch is not None:
+            index = torch.cuda.current_device()
+        if index != _selected_device():
+            raise ValueError(f"the tensor lives on device {index}, this thread selected device {_selected_device()} (set_device)")
+        n = int(a.shape[0])
+        if n > 1 and (a.stride(1) != 1 or a.stride(0) < dim):
+            a = a.contiguous()
+        if torch is not None:
+            torch.cuda.current_stream(a.device).synchronize()
+        row = int(a.stride(0)) if n > 1 else dim
+        return L.DevicePoints(a.data_ptr() if n else None, row, dtype, dim), n, a
+    cai = a.__cuda_array_interface__
+    shape = tuple(cai["shape"])
+    if len(shape) != 2 or shape[1] != dim:
+        raise ValueError(f"expected an (N, {dim}) array")
+    if cai["typestr"] not in _TYPESTR_DTYPES:
+        raise ValueError(f"device points must be float32 or float64, not typestr {cai['typestr']!r}")
+    dtype, size = _TYPESTR_DTYPES[cai["typestr"]]
+    n = int(shape[0])
+    strides = cai.get("strides")
+    if strides is None:
+        row, col = dim, 1
+    else:
+        if strides[0] % size or strides[1] % size:
+            raise ValueError("byte strides of the device array are no multiple of its element size")
+        row, col = strides[0] // size, strides[1] // size
+    if n > 1 and (col != 1 or row < dim):
+        if not hasattr(a, "contiguous"):
+            raise ValueError("device points need a column stride of 1 (and the object has no .contiguous() to make them so)")
+        b = a.contiguous()
+        bs = b.__cuda_array_interface__.get("strides")
+        if bs is not None and tuple(bs) != (dim * size, size):
+            raise ValueError(".contiguous() of the device array did not return a contiguous array")
+        return _device_points(b, dim)
+    if n <= 1:
+        row = dim
+    return L.DevicePoints(int(cai["data"][0]) if n else None, int(row), dtype, dim), n, a
+
+
+class _Points:
+    """The two point sets of a call as the C-ABI takes them: host arrays (pointers to float64 data) or device descriptors."""
+
+    def __init__(self, a, b, dim_a, dim_b):
+        self.on_device = _on_device(a)
+        if self.on_device != _on_device(b):
+            raise ValueError("one point set is on the GPU and the other in host memory: pass both the same way")
+        if self.on_device:
+            da, self.n, keep_a = _device_points(a, dim_a)
+            db, nb, keep_b = _device_points(b, dim_b)
+            if nb != self.n:
+                raise ValueError(f"the point sets differ in length ({self.n} and {nb})")
+            self.keep = (da, db, keep_a, keep_b)
+            self.a, self.b = C.byref(da), C.byref(db)
+        else:
+            a, b = _pts(a, dim_a), _pts(b, dim_b)
+            self.n = a.shape[0]
+            self.keep = (a, b)
+            self.a, self.b = _ptr(a), _ptr(b)
+
+    def fn(self, name):
+        return getattr(L.lib(), name + "_dev" if self.on_device else name)
+
+
 def _info(st: L.RansacStats, inliers: np.ndarray):
     return {"refinements": st.refinements, "iterations": st.iterations, "num_inliers": st.num_inliers,
             "inlier_ratio": st.inlier_ratio, "model_score": st.model_score, "inliers": inliers.astype(bool).tolist(),
@@ -214,41 +314,41 @@ def _as_camera(cam) -> Camera:
 
 # ------------------------------------------------------------------------------------------ estimators
 def estimate_absolute_pose(points2D, points3D, camera, opt=None, initial_pose=None):
-    p2, p3 = _pts(points2D, 2), _pts(points3D, 3)
+    pts = _Points(points2D, points3D, 2, 3)
     cam = _as_camera(camera)
     o = _robust_options(opt, KIND_ABS, initial_pose is not None)
     c = cam._c()
     pose = _cpose(initial_pose if initial_pose is not None else CameraPose())
-    n = p2.shape[0]
+    n = pts.n
     inl = np.zeros(max(n, 1), dtype=np.uint8)
     st = L.RansacStats()
-    L.check(L.lib().pl_estimate_absolute_pose(_ptr(p2), _ptr(p3), C.c_size_t(n), C.byref(o), C.byref(c), C.byref(pose),
-                                              _ptr(inl), C.byref(st)))
+    L.check(pts.fn("pl_estimate_absolute_pose")(pts.a, pts.b, C.c_size_t(n), C.byref(o), C.byref(c), C.byref(pose),
+                                                _ptr(inl), C.byref(st)))
     out_cam = Camera(cam.model_id, list(c.params[: c.num_params]), cam.width, cam.height)
     return Image(_pypose(pose), out_cam), _info(st, inl[:n])
 
 
 def estimate_relative_pose(points2D_1, points2D_2, camera1, camera2, opt=None, initial_pose=None):
-    a, b = _pts(points2D_1, 2), _pts(points2D_2, 2)
+    pts = _Points(points2D_1, points2D_2, 2, 2)
     c1, c2 = _as_camera(camera1)._c(), _as_camera(camera2)._c()
     o = _robust_options(opt, KIND_REL, initial_pose is not None)
     pose = _cpose(initial_pose if initial_pose is not None else CameraPose())
-    n = a.shape[0]
+    n = pts.n
     inl = np.zeros(max(n, 1), dtype=np.uint8)
     st = L.RansacStats()
-    L.check(L.lib().pl_estimate_relative_pose(_ptr(a), _ptr(b), C.c_size_t(n), C.byref(c1), C.byref(c2), C.byref(o),
-                                              C.byref(pose), _ptr(inl), C.byref(st)))
+    L.check(pts.fn("pl_estimate_relative_pose")(pts.a, pts.b, C.c_size_t(n), C.byref(c1), C.byref(c2), C.byref(o),
+                                                C.byref(pose), _ptr(inl), C.byref(st)))
     return _pypose(pose), _info(st, inl[:n])
 
 
 def _estimate_matrix(fn, kind, points2D_1, points2D_2, opt, initial):
-    a, b = _pts(points2D_1, 2), _pts(points2D_2, 2)
+    pts = _Points(points2D_1, points2D_2, 2, 2)
     o = _robust_options(opt, kind, initial is not None)
     M = np.ascontiguousarray((np.eye(3) if initial is None else np.asarray(initial, dtype=np.float64)).T.reshape(9))
-    n = a.shape[0]
+    n = pts.n
     inl = np.zeros(max(n, 1), dtype=np.uint8)
     st = L.RansacStats()
-    L.check(getattr(L.lib(), fn)(_ptr(a), _ptr(b), C.c_size_t(n), C.byref(o), _ptr(M), _ptr(inl), C.byref(st)))
+    L.check(pts.fn(fn)(pts.a, pts.b, C.c_size_t(n), C.byref(o), _ptr(M), _ptr(inl), C.byref(st)))
     return M.reshape(3, 3).T.copy(), _info(st, inl[:n])
 
 
@@ -633,15 +733,15 @@ def ransac_homography(x1, x2, opt=None, initial_H=None):
 # ------------------------------------------------------------------------------------------ device-resident problems
 class Problem:
     """Correspondences uploaded once (SoA in HBM); `run` executes the LO-RANSAC loop on them.
-    This is the entry bench.py times: inputs are resident before the timed region starts."""
+    This is the entry bench.py times: inputs are resident before the timed region starts.
+    a, b: host arrays, or GPU tensors (float32 / float64, any row stride) - those are copied into the problem's block on the device."""
 
     def __init__(self, kind: int, a, b):
         self.kind = kind
-        a = _pts(a, 2)
-        b = _pts(b, 3 if kind in (KIND_ABS, KIND_RAD1D) else 2)
-        self.n = a.shape[0]
+        pts = _Points(a, b, 2, 3 if kind in (KIND_ABS, KIND_RAD1D) else 2)
+        self.n = pts.n
         self._h = C.c_void_p()
-        L.check(L.lib().pl_problem_create(kind, _ptr(a), _ptr(b), C.c_size_t(self.n), C.byref(self._h)))
+        L.check(pts.fn("pl_problem_create")(kind, pts.a, pts.b, C.c_size_t(self.n), C.byref(self._h)))
 
     def run(self, opt=None, initial=None):
         o = _robust_options(opt, self.kind, initial is not None)
@@ -781,13 +881,13 @@ class TangentProblem(Problem):
 
     def __init__(self, x1, x2, camera1=None, camera2=None):
         self.kind = KIND_REL  # (how the models are marshalled)
-        a, b = _pts(x1, 2), _pts(x2, 2)
-        self.n = a.shape[0]
+        pts = _Points(x1, x2, 2, 2)
+        self.n = pts.n
         self._h = C.c_void_p()
         c1 = None if camera1 is None else _as_camera(camera1)._c()
         c2 = None if camera2 is None else _as_camera(camera2)._c()
-        L.check(L.lib().pl_problem_create_tangent(_ptr(a), _ptr(b), C.c_size_t(self.n), None if c1 is None else C.byref(c1),
-                                                  None if c2 is None else C.byref(c2), C.byref(self._h)))
+        L.check(pts.fn("pl_problem_create_tangent")(pts.a, pts.b, C.c_size_t(self.n), None if c1 is None else C.byref(c1),
+                                                    None if c2 is None else C.byref(c2), C.byref(self._h)))
 
 
 def radial1d_generate(problem, samples, slots_per_iter=4):
@@ -939,6 +1039,25 @@ def device_count() -> int:
 
 def set_device(i: int):
     L.check(L.lib().pl_set_device(int(i)))
+    _tls.device = int(i)
+
+
+def check_device_points(desc, n: int, cols: int) -> int:
+    """Diagnostic (pl_debug_check_device_points): the return code of every check the _dev entry points make on one argument -
+    desc: a _lib.DevicePoints, or None for a null descriptor.  No kernel is launched."""
+    return L.lib().pl_debug_check_device_points(None if desc is None else C.byref(desc), C.c_size_t(int(n)), int(cols))
+
+
+def point_stats_dev(x1, x2, centroid=True):
+    """Diagnostic (pl_debug_point_stats_dev): what the GPU-input front-ends read back in place of the host's passes over the points,
+    for two (N, 2) GPU tensors: {"c1", "c2", "scale", "absmax_normalised", "absmax_first"}."""
+    pts = _Points(x1, x2, 2, 2)
+    if not pts.on_device:
+        raise ValueError("point_stats_dev takes GPU tensors")
+    out = np.zeros(8)
+    L.check(L.lib().pl_debug_point_stats_dev(pts.a, pts.b, C.c_size_t(pts.n), int(bool(centroid)), _ptr(out)))
+    return {"c1": out[0:2].copy(), "c2": out[2:4].copy(), "scale": float(out[4]), "absmax_normalised": float(out[5]),
+            "absmax_first": float(out[6])}
 
 
 def set_lm_mode(mode) -> int:

@@ -123,6 +123,7 @@ struct Context {
     DevBuf iota; // iota[i] = i: a device-resident "number of hypotheses" for launches whose count the host knows
     DevBuf lm_tasks, lm_records, gather_idx, gather_out, mask, lm_scratch, tmp_model, solve_in, solve_out, solve_cnt, focal_stage;
     HostBuf h_rec_meta, h_focal, h_in;
+    HostBuf h_pstats; // the record k_point_stats writes (the *_dev front-ends)
     const double *raw_src_a = nullptr, *raw_src_b = nullptr; // where the raw correspondences of the last make_problem_prepared live (device-visible)
     HostBuf h_absmax, h_positions, h_num_models, h_count, h_score, h_tasks, h_gather_idx, h_gather_out, h_mask,
         h_small, h_models;
@@ -1879,8 +1880,9 @@ float host_prefilter_bound(int kind, const PrepareArgs &pa, const double *a, con
 // hipMalloc / hipFree per call.  The problem is valid until the next make_problem_prepared on this thread.
 // resident: the raw correspondences of this call are already in c->raw_a / raw_b (second preparation of the same
 // inputs: no upload); lm_only: the problem is only refined on, never scored - no max|x| read-back, no synchronisation
+// bound: the pre-filter bound when the caller already has it (the *_dev front-ends: a and b are then not read); otherwise the host pass
 int make_problem_prepared(Context *c, int kind, const double *a, const double *b, size_t n, const PrepareArgs &pa,
-                          pl_problem *p, bool resident = false, bool lm_only = false) {
+                          pl_problem *p, bool resident = false, bool lm_only = false, const float *bound = nullptr) {
     if (kind < 0 || kind > EST_RELT)
         return fail(PL_ERR_INVALID, "unknown problem kind");
     if (n > 0x7fffffffu / (kind == EST_RELT ? 18u : 1u))
@@ -1937,7 +1939,7 @@ int make_problem_prepared(Context *c, int kind, const double *a, const double *b
     for (int d = 0; d < nd; ++d)
         p->ps.a[d] = p->d_pts + (size_t)d * n;
     if (!reads_absmax) { // (stream order puts the next kernels behind k_prepare)
-        p->ps.xy_absmax = lm_only ? std::numeric_limits<float>::infinity() : host_prefilter_bound(kind, pa, a, b, n);
+        p->ps.xy_absmax = lm_only ? std::numeric_limits<float>::infinity() : bound ? *bound : host_prefilter_bound(kind, pa, a, b, n);
         return PL_OK;
     }
     HIP_TRY(hipMemcpyAsync(c->h_absmax.p, c->absmax.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
@@ -2058,10 +2060,11 @@ int final_refine(Context *c, pl_problem *p, const double *record_in, const LMOpt
 // PoseLib/robust/utils.cc:584-644 with normalize_scale = shared_scale = true.  Only the two order-dependent reductions
 // (centroids, mean distance) are summed here, sequentially like the reference; the per-point part - subtract the
 // centroid, divide by the scale - is applied by k_prepare on the device with the same two operations per coordinate.
-double normalization_of(const double *x1, const double *x2, size_t n, bool centroid, Mat3 &T1, Mat3 &T2,
-                        PrepareArgs &pa) {
-    for (int i = 0; i < 9; ++i)
-        T1.m[i] = T2.m[i] = (i % 4 == 0) ? 1.0 : 0.0;
+struct PointNorm { // the two reductions: centroids (zero when the points are not centred) and the mean distance / sqrt(2)
+    double c1x = 0, c1y = 0, c2x = 0, c2y = 0, scale = 0;
+};
+PointNorm host_point_norm(const double *x1, const double *x2, size_t n, bool centroid) {
+    PointNorm pn;
     double c1x = 0, c1y = 0, c2x = 0, c2y = 0;
     if (centroid) {
         for (size_t k = 0; k < n; ++k) {
@@ -2070,8 +2073,6 @@ double normalization_of(const double *x1, const double *x2, size_t n, bool centr
         }
         c1x /= static_cast<double>(n), c1y /= static_cast<double>(n);
         c2x /= static_cast<double>(n), c2y /= static_cast<double>(n);
-        T1.m[2] = -c1x, T1.m[5] = -c1y;
-        T2.m[2] = -c2x, T2.m[5] = -c2y;
     }
     double scale = 0.0;
     for (size_t k = 0; k < n; ++k) {
@@ -2082,6 +2083,18 @@ double normalization_of(const double *x1, const double *x2, size_t n, bool centr
         scale += std::sqrt(b0 * b0 + b1 * b1);
     }
     scale /= std::sqrt(2) * n;
+    pn.c1x = c1x, pn.c1y = c1y, pn.c2x = c2x, pn.c2y = c2y, pn.scale = scale;
+    return pn;
+}
+// the transforms and k_prepare's arguments from the reductions - summed on the host (above) or by k_point_stats (the *_dev front-ends)
+double normalization_from(const PointNorm &pn, bool centroid, Mat3 &T1, Mat3 &T2, PrepareArgs &pa) {
+    for (int i = 0; i < 9; ++i)
+        T1.m[i] = T2.m[i] = (i % 4 == 0) ? 1.0 : 0.0;
+    if (centroid) {
+        T1.m[2] = -pn.c1x, T1.m[5] = -pn.c1y;
+        T2.m[2] = -pn.c2x, T2.m[5] = -pn.c2y;
+    }
+    const double scale = pn.scale;
     const double f = 1.0 / scale;
     for (int i = 0; i < 6; ++i) {
         T1.m[i] *= f;
@@ -2090,9 +2103,13 @@ double normalization_of(const double *x1, const double *x2, size_t n, bool centr
     std::memset(&pa, 0, sizeof(pa));
     pa.mode = 2;
     pa.centred = centroid ? 1 : 0;
-    pa.c1x = c1x, pa.c1y = c1y, pa.c2x = c2x, pa.c2y = c2y;
+    pa.c1x = pn.c1x, pa.c1y = pn.c1y, pa.c2x = pn.c2x, pa.c2y = pn.c2y;
     pa.scale = scale;
     return scale;
+}
+double normalization_of(const double *x1, const double *x2, size_t n, bool centroid, Mat3 &T1, Mat3 &T2,
+                        PrepareArgs &pa) {
+    return normalization_from(host_point_norm(x1, x2, n, centroid), centroid, T1, T2, pa);
 }
 
 // ---------------------------------------------------------------------------- front-ends (robust.cc)
@@ -2117,9 +2134,13 @@ pl_bundle_options front_bundle_options(const pl_robust_options &opt) {
     return bundle;
 }
 
+// homography / fundamental: are the points centred before they are scaled?  (robust.cc:552-562, 720-726)
+bool front_centred(int kind, const pl_robust_options &opt) { return kind == EST_HOM || !opt.real_focal_check; }
+
 // robust.cc:40-46 (abs), 249-253 / 286-292 (rel), 552-562 (fund), 720-726 (hom)
-void front_begin(FrontEnd &fe, int kind, const double *a, const double *b, size_t n, const pl_robust_options &opt,
-                 const pl_camera *camera1, const pl_camera *camera2) {
+// norm: the reductions of the homography / fundamental normalisation (not read for the other kinds)
+void front_begin_with(FrontEnd &fe, int kind, const PointNorm &norm, const pl_robust_options &opt, const pl_camera *camera1,
+                      const pl_camera *camera2) {
     fe.kind = kind;
     fe.scaled = opt;
     std::memset(&fe.prep, 0, sizeof(fe.prep));
@@ -2154,11 +2175,19 @@ void front_begin(FrontEnd &fe, int kind, const double *a, const double *b, size_
         break;
     }
     default:
-        fe.scale = normalization_of(a, b, n, kind == EST_HOM || !opt.real_focal_check, fe.T1, fe.T2, fe.prep);
+        fe.scale = normalization_from(norm, front_centred(kind, opt), fe.T1, fe.T2, fe.prep);
         fe.scaled.max_error /= fe.scale;
         fe.scaled.bundle.loss_scale /= fe.scale;
         break;
     }
+}
+// ... with the reductions from the caller's host arrays
+void front_begin(FrontEnd &fe, int kind, const double *a, const double *b, size_t n, const pl_robust_options &opt,
+                 const pl_camera *camera1, const pl_camera *camera2) {
+    PointNorm norm;
+    if (kind == EST_FUND || kind == EST_HOM)
+        norm = host_point_norm(a, b, n, front_centred(kind, opt));
+    front_begin_with(fe, kind, norm, opt, camera1, camera2);
 }
 
 // the record the loop starts from: the identity, or with ransac.score_initial_model the caller's model - poses as they are, F and H
@@ -3292,21 +3321,12 @@ int front_final_refine(Context *c, pl_problem *p, const FrontEnd &fe, double *re
     return rc;
 }
 
-int pl_estimate_absolute_pose(const double *points2D, const double *points3D, size_t n, const pl_robust_options *opt,
-                              pl_camera *camera, pl_camera_pose *pose, uint8_t *inliers, pl_ransac_stats *stats) {
-    int rc = validate_options(opt, /*focal_entry=*/true);
-    if (rc != PL_OK)
-        return rc;
-    if (!camera || !camera_supported(camera))
-        return fail(PL_ERR_UNSUPPORTED, "camera model not supported (NULL, SIMPLE_PINHOLE, PINHOLE, SIMPLE_RADIAL, RADIAL, OPENCV, OPENCV_FISHEYE, SIMPLE_RADIAL_FISHEYE, RADIAL_FISHEYE)");
-    Context *c;
-    rc = get_context(&c);
-    if (rc != PL_OK)
-        return rc;
-    FrontEnd fe;
-    front_begin(fe, EST_ABS, points2D, points3D, n, *opt, camera, nullptr);
+// absolute pose behind front_begin: the loop, the gated bundle on the raw pixels, front_finish.  bound: the pre-filter bound when the
+// points are already on the device (c->raw_src_*; points2D / points3D are then null), otherwise the host arrays are uploaded
+int absolute_pose_run(Context *c, FrontEnd &fe, const double *points2D, const double *points3D, size_t n, const float *bound,
+                      const pl_robust_options *opt, pl_camera *camera, pl_camera_pose *pose, uint8_t *inliers, pl_ransac_stats *stats) {
     pl_problem p;
-    rc = make_problem_prepared(c, EST_ABS, points2D, points3D, n, fe.prep, &p);
+    int rc = make_problem_prepared(c, EST_ABS, points2D, points3D, n, fe.prep, &p, /*resident=*/bound != nullptr, false, bound);
     if (rc != PL_OK)
         return rc;
     pl_ransac_stats local;
@@ -3345,6 +3365,22 @@ int pl_estimate_absolute_pose(const double *points2D, const double *points3D, si
         return rc;
     front_finish(fe, rec, &refined, pose, camera);
     return PL_OK;
+}
+
+int pl_estimate_absolute_pose(const double *points2D, const double *points3D, size_t n, const pl_robust_options *opt,
+                              pl_camera *camera, pl_camera_pose *pose, uint8_t *inliers, pl_ransac_stats *stats) {
+    int rc = validate_options(opt, /*focal_entry=*/true);
+    if (rc != PL_OK)
+        return rc;
+    if (!camera || !camera_supported(camera))
+        return fail(PL_ERR_UNSUPPORTED, "camera model not supported (NULL, SIMPLE_PINHOLE, PINHOLE, SIMPLE_RADIAL, RADIAL, OPENCV, OPENCV_FISHEYE, SIMPLE_RADIAL_FISHEYE, RADIAL_FISHEYE)");
+    Context *c;
+    rc = get_context(&c);
+    if (rc != PL_OK)
+        return rc;
+    FrontEnd fe;
+    front_begin(fe, EST_ABS, points2D, points3D, n, *opt, camera, nullptr);
+    return absolute_pose_run(c, fe, points2D, points3D, n, nullptr, opt, camera, pose, inliers, stats);
 }
 
 // robust.cc:889-934: absolute pose of a 1D-radial camera from centred pixels.  The pixels are multiplied by n / sum |x_k| (summed in
@@ -3404,18 +3440,13 @@ int pl_estimate_1D_radial_absolute_pose(const double *points2D, const double *po
 }
 
 // relative pose, fundamental matrix, homography: validate, front_begin, the loop, the gated bundle, front_finish
-int estimate_two_view(int kind, const double *x1, const double *x2, size_t n, const pl_camera *camera1, const pl_camera *camera2,
-                      const pl_robust_options *opt, void *model, uint8_t *inliers, pl_ransac_stats *st) {
-    Context *c;
-    int rc = get_context(&c);
-    if (rc != PL_OK)
-        return rc;
-    FrontEnd fe;
-    front_begin(fe, kind, x1, x2, n, *opt, camera1, camera2);
+// ... behind front_begin.  bound: as for absolute_pose_run
+int two_view_run(Context *c, const FrontEnd &fe, int kind, const double *x1, const double *x2, size_t n, const float *bound, void *model,
+                 uint8_t *inliers, pl_ransac_stats *st) {
     double rec[kModelStride];
     front_initial_record(fe, model, rec);
     pl_problem p;
-    rc = make_problem_prepared(c, kind, x1, x2, n, fe.prep, &p);
+    int rc = make_problem_prepared(c, kind, x1, x2, n, fe.prep, &p, /*resident=*/bound != nullptr, false, bound);
     if (rc != PL_OK)
         return rc;
     rc = ransac_core(c, &p, &fe.scaled, rec, inliers, st);
@@ -3428,6 +3459,16 @@ int estimate_two_view(int kind, const double *x1, const double *x2, size_t n, co
         return rc;
     front_finish(fe, rec, nullptr, model, nullptr);
     return PL_OK;
+}
+int estimate_two_view(int kind, const double *x1, const double *x2, size_t n, const pl_camera *camera1, const pl_camera *camera2,
+                      const pl_robust_options *opt, void *model, uint8_t *inliers, pl_ransac_stats *st) {
+    Context *c;
+    int rc = get_context(&c);
+    if (rc != PL_OK)
+        return rc;
+    FrontEnd fe;
+    front_begin(fe, kind, x1, x2, n, *opt, camera1, camera2);
+    return two_view_run(c, fe, kind, x1, x2, n, nullptr, model, inliers, st);
 }
 
 int pl_estimate_relative_pose(const double *x1, const double *x2, size_t n, const pl_camera *camera1,
@@ -3517,6 +3558,8 @@ int pl_estimate_homography(const double *x1, const double *x2, size_t n, const p
     }
     return estimate_two_view(EST_HOM, x1, x2, n, nullptr, nullptr, opt, H, inliers, st);
 }
+
+#include "driver_dev.inc"
 
 // ---------------------------------------------------------------------------- un-distortion stage
 int pl_undistort_points(const pl_camera *camera, const double *points2D, size_t n, double *out) {

@@ -1,0 +1,439 @@
+// poselib_amd — the *_dev entry points: correspondences in the caller's DEVICE memory (pl_device_points: fp32 or fp64, strided
+// rows).  Included by driver.cc inside extern "C", behind the host front-ends.
+//
+// Device input goes in front of the existing preparation and produces exactly what the host path would have uploaded:
+//   k_ingest        the caller's rows -> contiguous fp64 AoS in Context::raw_a / raw_b (an fp64 set with row_stride == cols is read
+//                   where it lies), which is what k_prepare / k_prepare_tangent take: make_problem_prepared(resident = true)
+//   k_point_stats   the numbers the host front-ends compute in passes over the caller's arrays - the two order-dependent
+//                   reductions of the homography / fundamental normalisation and the pre-filters' bound - one small record back
+//   k_ingest_soa    a resident problem's block, written on the device
+// From there both kinds of call run the same code (absolute_pose_run, two_view_run), so a _dev call returns the host call's bits.
+// Every check of the descriptors happens before the first launch: a caller's mistake is an error code, never a kernel reading a
+// host address.
+
+namespace {
+
+// the checks that need no device
+int check_points_plain(const pl_device_points *d, size_t n, int cols) {
+    if (!d)
+        return fail(PL_ERR_INVALID, "device points: descriptor is null");
+    if (n > 0x7fffffffu)
+        return fail(PL_ERR_INVALID, "too many correspondences");
+    if (d->cols != cols)
+        return fail(PL_ERR_INVALID, cols == 3 ? "device points: cols must be 3 for this argument" : "device points: cols must be 2 for this argument");
+    if (d->dtype != PL_F64 && d->dtype != PL_F32)
+        return fail(PL_ERR_INVALID, "device points: dtype must be PL_F64 or PL_F32");
+    if (d->row_stride < d->cols)
+        return fail(PL_ERR_INVALID, "device points: row_stride (elements) is below cols");
+    if (d->row_stride > ((int64_t)1 << 28)) // (n * row_stride * 8 stays far inside 64 bits)
+        return fail(PL_ERR_INVALID, "device points: row_stride beyond 2^28 elements");
+    if (!d->data && n)
+        return fail(PL_ERR_INVALID, "device points: data is null");
+    const uintptr_t elt = d->dtype == PL_F32 ? sizeof(float) : sizeof(double);
+    if (reinterpret_cast<uintptr_t>(d->data) % elt)
+        return fail(PL_ERR_INVALID, "device points: data is not aligned to its element size");
+    return PL_OK;
+}
+// ... and what the runtime knows about the address: device memory of the calling thread's device that holds every row (n > 0)
+int check_points_device(const Context *c, const pl_device_points *d, size_t n) {
+    if (n == 0)
+        return PL_OK;
+    hipPointerAttribute_t attr;
+    std::memset(&attr, 0, sizeof(attr));
+    const hipError_t e = hipPointerGetAttributes(&attr, d->data);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(PL_ERR_INVALID, "device points: data is not an address the HIP runtime knows (a host pointer?)");
+    }
+    if (attr.isManaged || attr.type == hipMemoryTypeManaged)
+        return fail(PL_ERR_INVALID, "device points: data is managed memory, device memory is required");
+    if (attr.type != hipMemoryTypeDevice)
+        return fail(PL_ERR_INVALID, "device points: data is host memory, device memory is required");
+    if (attr.device != c->device)
+        return fail(PL_ERR_INVALID, "device points: data lives on another device than the calling thread's (pl_set_device)");
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, const_cast<void *>(d->data)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(PL_ERR_INVALID, "device points: the allocation behind data cannot be found");
+    }
+    const size_t elt = d->dtype == PL_F32 ? sizeof(float) : sizeof(double);
+    const size_t need = ((n - 1) * (size_t)d->row_stride + (size_t)d->cols) * elt;
+    const uintptr_t lo = reinterpret_cast<uintptr_t>(base), at = reinterpret_cast<uintptr_t>(d->data);
+    if (at < lo || at - lo > size || need > size - (at - lo))
+        return fail(PL_ERR_INVALID, "device points: the rows reach beyond the allocation behind data");
+    return PL_OK;
+}
+
+IngestSrc ingest_src(const pl_device_points *d) {
+    IngestSrc s;
+    s.data = d->data;
+    s.row_stride = d->row_stride;
+    s.f32 = d->dtype == PL_F32;
+    s.cols = d->cols;
+    return s;
+}
+bool reads_in_place(const pl_device_points *d) { return d->dtype == PL_F64 && d->row_stride == d->cols; }
+
+// plain checks of both sets, the context, the device checks: everything in front of the first launch
+int open_device_points(const pl_device_points *a, int cols_a, const pl_device_points *b, int cols_b, size_t n, Context **c) {
+    int rc = check_points_plain(a, n, cols_a);
+    if (rc == PL_OK)
+        rc = check_points_plain(b, n, cols_b);
+    if (rc == PL_OK)
+        rc = get_context(c);
+    if (rc == PL_OK)
+        rc = check_points_device(*c, a, n);
+    if (rc == PL_OK)
+        rc = check_points_device(*c, b, n);
+    return rc;
+}
+
+// the fp64 AoS blocks of both sets: c->raw_src_a / raw_src_b (k_prepare's input) - the caller's memory where it already is one
+int ingest_points(Context *c, const pl_device_points *a, const pl_device_points *b, size_t n) {
+    c->raw_src_a = c->raw_src_b = nullptr;
+    if (n == 0)
+        return PL_OK;
+    double *out_a = nullptr, *out_b = nullptr;
+    if (!reads_in_place(a)) {
+        HIP_TRY(c->raw_a.ensure(sizeof(double) * a->cols * n));
+        out_a = c->raw_a.as<double>();
+    }
+    if (!reads_in_place(b)) {
+        HIP_TRY(c->raw_b.ensure(sizeof(double) * b->cols * n));
+        out_b = c->raw_b.as<double>();
+    }
+    HIP_TRY(launch_ingest(ingest_src(a), ingest_src(b), (uint32_t)n, out_a, out_b, c->stream));
+    c->raw_src_a = out_a ? out_a : static_cast<const double *>(a->data);
+    c->raw_src_b = out_b ? out_b : static_cast<const double *>(b->data);
+    return PL_OK;
+}
+
+// centre and focal lengths of a camera whose un-projection is (x - c) / f (host_xy_absmax, host_two_view_absmax); false: another model
+bool linear_camera_terms(const CameraParams &cam, double &cx, double &cy, double &fx, double &fy) {
+    cx = cy = 0, fx = fy = 1;
+    if (cam.model_id == CAM_SIMPLE_PINHOLE)
+        fx = fy = cam.p[0], cx = cam.p[1], cy = cam.p[2];
+    else if (cam.model_id == CAM_PINHOLE)
+        fx = cam.p[0], fy = cam.p[1], cx = cam.p[2], cy = cam.p[3];
+    else if (cam.model_id != CAM_NULL)
+        return false;
+    return true;
+}
+
+// k_point_stats on the ingested blocks, and its record
+int run_point_stats(Context *c, size_t n, PointStatsArgs args, PointStatsRecord *rec) {
+    args.n_as_double = static_cast<double>(n);
+    args.scale_divisor = std::sqrt(2) * n;
+    HIP_TRY(c->h_pstats.ensure(sizeof(PointStatsRecord)));
+    HIP_TRY(launch_point_stats(c->raw_src_a, c->raw_src_b, (uint32_t)n, args, c->h_pstats.dev<PointStatsRecord>(), c->stream));
+    HIP_TRY(wait_stream(c));
+    std::memcpy(rec, c->h_pstats.p, sizeof(*rec));
+    return PL_OK;
+}
+// the raw maximum as the host passes finish it (host_xy_absmax / host_two_view_absmax)
+float bound_from_max(double m, bool nan_is_unbounded) {
+    const float inf = std::numeric_limits<float>::infinity();
+    if (nan_is_unbounded && m != m)
+        return inf;
+    m = m * (1.0 + 1e-12);
+    return std::nextafter((float)m, inf);
+}
+
+// What front_begin and host_prefilter_bound take from the host arrays, from the ingested blocks instead: the reductions of the
+// normalisation (homography, fundamental) and the pre-filters' bound, in the same cases - absolute pose through a linear camera,
+// two-view problems from 1024 correspondences with linear cameras (an absolute-pose problem of a non-linear camera reads k_prepare's
+// maximum back: make_problem_prepared, as in the host call).  No launch where the host has no pass either.
+int device_front_stats(Context *c, int kind, size_t n, const pl_robust_options &opt, const pl_camera *camera1, const pl_camera *camera2,
+                       PointNorm *norm, float *bound) {
+    *bound = std::numeric_limits<float>::infinity();
+    if (n == 0)
+        return PL_OK;
+    PointStatsArgs args;
+    std::memset(&args, 0, sizeof(args));
+    PointStatsRecord rec;
+    if (kind == EST_ABS) {
+        const CameraParams cam = to_cam(camera1);
+        if (prefilter_bound_on_device(kind, prepare_unproject(cam, nullptr)))
+            return PL_OK;
+        args.bound = 1;
+        linear_camera_terms(cam, args.cx1, args.cy1, args.fx1, args.fy1);
+        int rc = run_point_stats(c, n, args, &rec);
+        if (rc == PL_OK)
+            *bound = bound_from_max(rec.absmax, false);
+        return rc;
+    }
+    if (kind == EST_REL) {
+        if (n < 1024 || !linear_camera_terms(to_cam(camera1), args.cx1, args.cy1, args.fx1, args.fy1) ||
+            !linear_camera_terms(to_cam(camera2), args.cx2, args.cy2, args.fx2, args.fy2))
+            return PL_OK;
+        args.bound = 2;
+        int rc = run_point_stats(c, n, args, &rec);
+        if (rc == PL_OK)
+            *bound = bound_from_max(rec.absmax, true);
+        return rc;
+    }
+    if (kind != EST_FUND && kind != EST_HOM) // (tangent Sampson: its pre-filter takes no bound)
+        return PL_OK;
+    args.norm = 1;
+    args.centred = front_centred(kind, opt) ? 1 : 0;
+    args.bound = n >= 1024 ? 3 : 0;
+    int rc = run_point_stats(c, n, args, &rec);
+    if (rc != PL_OK)
+        return rc;
+    norm->c1x = rec.c1x, norm->c1y = rec.c1y, norm->c2x = rec.c2x, norm->c2y = rec.c2y, norm->scale = rec.scale;
+    if (args.bound)
+        *bound = bound_from_max(rec.absmax, true);
+    return PL_OK;
+}
+
+int estimate_two_view_dev(int kind, const pl_device_points *x1, const pl_device_points *x2, size_t n, const pl_camera *camera1,
+                          const pl_camera *camera2, const pl_robust_options *opt, void *model, uint8_t *inliers, pl_ransac_stats *st) {
+    Context *c;
+    int rc = open_device_points(x1, 2, x2, 2, n, &c);
+    if (rc == PL_OK)
+        rc = ingest_points(c, x1, x2, n);
+    PointNorm norm;
+    float bound;
+    if (rc == PL_OK)
+        rc = device_front_stats(c, kind, n, *opt, camera1, camera2, &norm, &bound);
+    if (rc != PL_OK)
+        return rc;
+    FrontEnd fe;
+    front_begin_with(fe, kind, norm, *opt, camera1, camera2);
+    rc = two_view_run(c, fe, kind, nullptr, nullptr, n, &bound, model, inliers, st);
+    c->raw_src_a = c->raw_src_b = nullptr; // (the caller's memory is not read after the call)
+    return rc;
+}
+
+} // namespace
+
+int pl_debug_check_device_points(const pl_device_points *d, size_t n, int cols) {
+    int rc = check_points_plain(d, n, cols);
+    if (rc != PL_OK || n == 0)
+        return rc;
+    Context *c;
+    rc = get_context(&c);
+    if (rc != PL_OK)
+        return rc;
+    return check_points_device(c, d, n);
+}
+
+int pl_debug_point_stats_dev(const pl_device_points *x1, const pl_device_points *x2, size_t n, int centroid, double *out) {
+    if (!out)
+        return fail(PL_ERR_INVALID, "output pointer is null");
+    Context *c;
+    int rc = open_device_points(x1, 2, x2, 2, n, &c);
+    if (rc != PL_OK)
+        return rc;
+    for (int i = 0; i < 8; ++i)
+        out[i] = 0.0;
+    if (n == 0)
+        return PL_OK;
+    rc = ingest_points(c, x1, x2, n);
+    if (rc != PL_OK)
+        return rc;
+    PointStatsArgs args;
+    std::memset(&args, 0, sizeof(args));
+    args.norm = 1, args.centred = centroid ? 1 : 0, args.bound = 3;
+    PointStatsRecord rec;
+    rc = run_point_stats(c, n, args, &rec);
+    if (rc != PL_OK)
+        return rc;
+    out[0] = rec.c1x, out[1] = rec.c1y, out[2] = rec.c2x, out[3] = rec.c2y, out[4] = rec.scale, out[5] = rec.absmax;
+    std::memset(&args, 0, sizeof(args));
+    args.bound = 1; // the identity camera: |x - 0| / 1
+    args.fx1 = args.fy1 = 1.0;
+    rc = run_point_stats(c, n, args, &rec);
+    if (rc != PL_OK)
+        return rc;
+    out[6] = rec.absmax;
+    return PL_OK;
+}
+
+int pl_estimate_absolute_pose_dev(const pl_device_points *points2D, const pl_device_points *points3D, size_t n,
+                                  const pl_robust_options *opt, pl_camera *camera, pl_camera_pose *pose, uint8_t *inliers,
+                                  pl_ransac_stats *stats) {
+    int rc = validate_options(opt, /*focal_entry=*/true);
+    if (rc != PL_OK)
+        return rc;
+    if (opt->estimate_focal_length) // (its loop and compute_max_focal_length read the image points on the host)
+        return fail(PL_ERR_UNSUPPORTED, "estimate_focal_length is not served from device memory: use pl_estimate_absolute_pose");
+    if (!camera || !camera_supported(camera))
+        return fail(PL_ERR_UNSUPPORTED, "camera model not supported (NULL, SIMPLE_PINHOLE, PINHOLE, SIMPLE_RADIAL, RADIAL, OPENCV, OPENCV_FISHEYE, SIMPLE_RADIAL_FISHEYE, RADIAL_FISHEYE)");
+    Context *c;
+    rc = open_device_points(points2D, 2, points3D, 3, n, &c);
+    if (rc == PL_OK)
+        rc = ingest_points(c, points2D, points3D, n);
+    PointNorm norm;
+    float bound;
+    if (rc == PL_OK)
+        rc = device_front_stats(c, EST_ABS, n, *opt, camera, nullptr, &norm, &bound);
+    if (rc != PL_OK)
+        return rc;
+    FrontEnd fe;
+    front_begin_with(fe, EST_ABS, norm, *opt, camera, nullptr);
+    rc = absolute_pose_run(c, fe, nullptr, nullptr, n, &bound, opt, camera, pose, inliers, stats);
+    c->raw_src_a = c->raw_src_b = nullptr; // (the caller's memory is not read after the call)
+    return rc;
+}
+
+int pl_estimate_relative_pose_dev(const pl_device_points *x1, const pl_device_points *x2, size_t n, const pl_camera *camera1,
+                                  const pl_camera *camera2, const pl_robust_options *opt, pl_camera_pose *pose, uint8_t *inliers,
+                                  pl_ransac_stats *stats) {
+    const bool tangent = opt && opt->tangent_sampson; // (as pl_estimate_relative_pose)
+    pl_robust_options plain;
+    if (tangent) {
+        plain = *opt;
+        plain.tangent_sampson = 0;
+    }
+    int rc = validate_options(tangent ? &plain : opt);
+    if (rc != PL_OK)
+        return rc;
+    if (tangent && (opt->bundle.refine_focal_length || opt->bundle.refine_principal_point || opt->bundle.refine_extra_params))
+        return fail(PL_ERR_UNSUPPORTED, "tangent_sampson with bundle.refine_focal_length / refine_principal_point / refine_extra_params "
+                                        "refines the intrinsics with the pose (CameraRelativePoseRefiner): not served, fixed cameras only");
+    if (!camera1 || !camera2 || !camera_supported(camera1) || !camera_supported(camera2))
+        return fail(PL_ERR_UNSUPPORTED, "camera model not supported (NULL, SIMPLE_PINHOLE, PINHOLE, SIMPLE_RADIAL, RADIAL, OPENCV, OPENCV_FISHEYE, SIMPLE_RADIAL_FISHEYE, RADIAL_FISHEYE)");
+    pl_ransac_stats local;
+    return estimate_two_view_dev(tangent ? EST_RELT : EST_REL, x1, x2, n, camera1, camera2, opt, pose, inliers, stats ? stats : &local);
+}
+
+int pl_estimate_fundamental_dev(const pl_device_points *x1, const pl_device_points *x2, size_t n, const pl_robust_options *opt, double *F,
+                                uint8_t *inliers, pl_ransac_stats *stats) {
+    int rc = validate_options(opt);
+    if (rc == PL_OK)
+        rc = check_points_plain(x1, n, 2);
+    if (rc == PL_OK)
+        rc = check_points_plain(x2, n, 2);
+    if (rc != PL_OK)
+        return rc;
+    pl_ransac_stats local;
+    pl_ransac_stats *st = stats ? stats : &local;
+    if (n < 7) { // robust.cc:548-550: nothing is read
+        std::memset(st, 0, sizeof(*st));
+        st->model_score = std::numeric_limits<double>::max();
+        return PL_OK;
+    }
+    return estimate_two_view_dev(EST_FUND, x1, x2, n, nullptr, nullptr, opt, F, inliers, st);
+}
+
+int pl_estimate_homography_dev(const pl_device_points *x1, const pl_device_points *x2, size_t n, const pl_robust_options *opt, double *H,
+                               uint8_t *inliers, pl_ransac_stats *stats) {
+    int rc = validate_options(opt);
+    if (rc == PL_OK)
+        rc = check_points_plain(x1, n, 2);
+    if (rc == PL_OK)
+        rc = check_points_plain(x2, n, 2);
+    if (rc != PL_OK)
+        return rc;
+    pl_ransac_stats local;
+    pl_ransac_stats *st = stats ? stats : &local;
+    if (n < 4) { // robust.cc:716-718
+        std::memset(st, 0, sizeof(*st));
+        st->model_score = std::numeric_limits<double>::max();
+        return PL_OK;
+    }
+    return estimate_two_view_dev(EST_HOM, x1, x2, n, nullptr, nullptr, opt, H, inliers, st);
+}
+
+// pl_problem_create from device memory: k_ingest_soa writes the block and takes make_problem's maximum
+int pl_problem_create_dev(int kind, const pl_device_points *a, const pl_device_points *b, size_t n, pl_problem **out) {
+    if (!out)
+        return fail(PL_ERR_INVALID, "output pointer is null");
+    if ((kind < 0 || kind > 3) && kind != EST_RAD1D)
+        return fail(PL_ERR_INVALID, "unknown problem kind");
+    const bool two_view = kind != EST_ABS && kind != EST_RAD1D;
+    Context *c;
+    int rc = open_device_points(a, 2, b, two_view ? 2 : 3, n, &c);
+    if (rc != PL_OK)
+        return rc;
+    pl_problem *p = new pl_problem();
+    p->kind = kind;
+    p->device = c->device;
+    p->n = (uint32_t)n;
+    p->d_pts = nullptr;
+    std::memset(&p->ps, 0, sizeof(p->ps));
+    p->ps.n = (uint32_t)n;
+    *out = p;
+    if (n == 0)
+        return PL_OK;
+    const int nd = point_doubles(kind);
+    hipError_t e = c->absmax.ensure(sizeof(unsigned long long));
+    if (e == hipSuccess)
+        e = c->h_absmax.ensure(sizeof(unsigned long long));
+    if (e == hipSuccess)
+        e = hipMalloc((void **)&p->d_pts, sizeof(double) * nd * n);
+    if (e == hipSuccess)
+        e = hipMemsetAsync(c->absmax.p, 0, sizeof(unsigned long long), c->stream);
+    if (e == hipSuccess)
+        e = launch_ingest_soa(ingest_src(a), ingest_src(b), (uint32_t)n, two_view ? 1 : 0, p->d_pts, c->absmax.as<unsigned long long>(),
+                              c->stream);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(c->h_absmax.p, c->absmax.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        if (p->d_pts)
+            (void)hipFree(p->d_pts);
+        delete p;
+        *out = nullptr;
+        return fail(PL_ERR_HIP, "ingestion of the correspondences", e);
+    }
+    for (int d = 0; d < nd; ++d)
+        p->ps.a[d] = p->d_pts + (size_t)d * n;
+    double amax;
+    std::memcpy(&amax, c->h_absmax.p, sizeof(double));
+    p->ps.xy_absmax = std::nextafter((float)amax, std::numeric_limits<float>::infinity());
+    return PL_OK;
+}
+
+int pl_problem_create_tangent_dev(const pl_device_points *x1, const pl_device_points *x2, size_t n, const pl_camera *camera1,
+                                  const pl_camera *camera2, pl_problem **out) {
+    if (!out)
+        return fail(PL_ERR_INVALID, "output pointer is null");
+    if ((camera1 && !camera_supported(camera1)) || (camera2 && !camera_supported(camera2)))
+        return fail(PL_ERR_UNSUPPORTED, "camera model outside the supported set (or too few parameters)");
+    if (n > 0x7fffffffu / 18)
+        return fail(PL_ERR_INVALID, "too many correspondences");
+    Context *c;
+    int rc = open_device_points(x1, 2, x2, 2, n, &c);
+    if (rc != PL_OK)
+        return rc;
+    pl_problem *p = new pl_problem();
+    p->kind = EST_RELT;
+    p->device = c->device;
+    p->n = (uint32_t)n;
+    p->d_pts = nullptr;
+    std::memset(&p->ps, 0, sizeof(p->ps));
+    p->ps.n = (uint32_t)n;
+    p->ps.xy_absmax = std::numeric_limits<float>::infinity();
+    *out = p;
+    if (n == 0)
+        return PL_OK;
+    PrepareArgs pa;
+    std::memset(&pa, 0, sizeof(pa));
+    pa.mode = 3;
+    pa.cam1 = to_cam(camera1);
+    pa.cam2 = to_cam(camera2);
+    pa.scale = 1.0;
+    rc = ingest_points(c, x1, x2, n);
+    hipError_t e = hipSuccess;
+    if (rc == PL_OK) {
+        e = hipMalloc((void **)&p->d_pts, sizeof(double) * 18 * n);
+        if (e == hipSuccess)
+            e = launch_prepare(c->raw_src_a, c->raw_src_b, (uint32_t)n, pa, p->d_pts, nullptr, c->stream);
+        if (e == hipSuccess)
+            e = hipStreamSynchronize(c->stream);
+    }
+    c->raw_src_a = c->raw_src_b = nullptr; // (the caller's memory is not read after the call)
+    if (rc != PL_OK || e != hipSuccess) {
+        if (p->d_pts)
+            (void)hipFree(p->d_pts);
+        delete p;
+        *out = nullptr;
+        return rc != PL_OK ? rc : fail(PL_ERR_HIP, "preparation of the tangent-Sampson problem", e);
+    }
+    p->ps.a[0] = p->d_pts;
+    return PL_OK;
+}

@@ -189,6 +189,34 @@ constexpr int kDeviceMath2Fns = 2;
 hipError_t launch_device_math2(int fn, const double *x, const double *y, uint32_t n, double *out, hipStream_t stream);
 hipError_t launch_undistort(const double *in, uint32_t n, const CameraParams &cam, double fx, double fy, double cx,
                             double cy, double *out, hipStream_t stream);
+// ---- correspondences in the caller's device memory (ingest.hip): rows of `cols` contiguous fp32 / fp64 elements, row_stride
+// elements apart (pl_device_points once the driver has checked it)
+struct IngestSrc {
+    const void *data;
+    int64_t row_stride;
+    int32_t f32; // elements are float (widened exactly), otherwise double
+    int32_t cols;
+};
+// -> the contiguous fp64 AoS blocks k_prepare / k_prepare_tangent take (n x a.cols, n x b.cols)
+hipError_t launch_ingest(const IngestSrc &a, const IngestSrc &b, uint32_t n, double *out_a, double *out_b, hipStream_t stream);
+// -> the SoA block of a resident problem (a.cols + b.cols arrays of n) and, like make_problem, max |a| - with max |b| when
+// b_in_max - as an atomic max of bit patterns on *absmax_bits (zeroed by the caller; a NaN propagates)
+hipError_t launch_ingest_soa(const IngestSrc &a, const IngestSrc &b, uint32_t n, int b_in_max, double *soa,
+                             unsigned long long *absmax_bits, hipStream_t stream);
+// What the front-ends compute over the raw points on the host, from the fp64 AoS blocks (N x 2 each) on the device:
+//   norm     the two order-dependent reductions of the homography / fundamental normalisation (utils.cc:584-644) in index order
+//   bound    0 none; 1 max |(a - c1) / f1| (absolute pose, linear camera); 2 the same over both sets with their cameras (relative
+//            pose, linear cameras); 3 max |(x - centroid) / scale| with the centroids and scale of `norm` (requires norm)
+struct PointStatsArgs {
+    int32_t norm, centred, bound, pad;
+    double cx1, cy1, fx1, fy1, cx2, cy2, fx2, fy2; // bound 1 / 2
+    double n_as_double, scale_divisor;             // norm: n and sqrt(2) * n as the host forms them
+};
+struct PointStatsRecord { // what the call reads back
+    double c1x, c1y, c2x, c2y, scale, absmax, reserved[2];
+};
+hipError_t launch_point_stats(const double *a_raw, const double *b_raw, uint32_t n, const PointStatsArgs &args,
+                              PointStatsRecord *out /* device-visible */, hipStream_t stream);
 // After the LM kernels: records of the refined models on the device (skipped tasks keep their input record), and the
 // choice "refined model if its score beats `incumbent_score`, else the incumbent" of the final refinement
 // (ransac_impl.h:190-198) so that the inlier mask can follow without a host round trip.
