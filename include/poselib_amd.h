@@ -470,6 +470,45 @@ typedef struct pl_debug_score_member {
     int32_t path_used;    /* out */
 } pl_debug_score_member;
 int pl_debug_score_stream_ex(int route, pl_debug_score_member *members, size_t num_members, uint32_t *idle_changed);
+/* Diagnostic: the PRUNED form of the matrix-core absolute-pose scorer on a caller-given model list, whatever
+ * the gate of the batch steps says of its length: the first `lead` live hypotheses against every chunk of correspondences; their
+ * best count and score, with the incumbent's (init_max, init_min), place the split chunk c*; every hypothesis against the chunks in
+ * front of c*; the hypotheses that could still become candidates - the kept ones - against the rest; finalize and the candidate
+ * scan of a batch step.  Routes and the inactive slot as in pl_debug_score_stream_ex (route 0: one member, the single launches;
+ * route 2: 1 .. 4 members behind an inactive slot 0, the group launches).
+ *   counts / scores  per hypothesis, as pl_debug_score_stream for a kept one; for a pruned one what it scored in front of c* with
+ *                    every correspondence from c* on counted as an outlier: a count not above, a score not below the full ones
+ *   kept             per hypothesis, 1 or 0 (NaN models, never scored, report 1; cstar == chunks: all 1)
+ *   cand             hypothesis indices of the candidates the scan lists, in the order it listed them (num_cand of them, at most
+ *                    cand_cap are written)
+ * PL_ERR_UNSUPPORTED: a member whose problem is not scored on the matrix cores.  PL_ERR_INVALID: as pl_debug_score_stream_ex, or a
+ * member of another kind than absolute pose. */
+typedef struct pl_debug_prune_member {
+    pl_problem *problem;
+    const void *models; /* pl_camera_pose[n] */
+    size_t n;
+    double max_error;
+    double init_min;   /* the incumbent's score ... */
+    uint32_t init_max; /* ... and inlier count: what a candidate has to beat */
+    uint32_t cand_cap;
+    uint32_t *counts; /* n entries, may be NULL */
+    double *scores;   /* n entries, may be NULL */
+    uint8_t *kept;    /* n entries, may be NULL */
+    uint32_t *cand;   /* cand_cap entries */
+    /* out */
+    uint32_t num_cand;
+    uint32_t cstar, chunks, chunk_points; /* the split chunk, the chunks of the launch and the correspondences of one */
+    uint32_t lead;                        /* live positions of the lead */
+    uint32_t lead_max;
+    uint32_t num_live, num_selected;      /* hypotheses without a NaN entry; length of the selection list (0 when cstar == chunks) */
+    uint32_t slices, pad;                 /* workgroups of 8 wavefronts per chunk of phase A (the plain launch's; the lead runs on
+                                             min(slices, 2), phase B on ceil(slices / 4)) */
+    double lead_min;
+} pl_debug_prune_member;
+int pl_debug_score_pruned(int route, pl_debug_prune_member *members, size_t num_members, uint32_t *idle_changed);
+/* Diagnostic: 1 if a batch step of `iterations` iterations of a problem of `kind` with n_points correspondences, as a member of a
+ * lock-step group (pl_ransac_batch, pl_estimate_batch), scores in the pruned form, 0 if not; pl_ransac_run's own steps never do (coordinates and threshold in the pre-filter's range assumed, as pl_debug_group_slices).  Host arithmetic only. */
+int pl_debug_score_prune_gate(int kind, uint32_t n_points, uint32_t iterations);
 /* Diagnostic entry: the scalar math of the device kernels, element-wise on `n` doubles (n <= 2^28) - fn 0: the cube of
  * the LM's Nielsen update (optim/lm_impl.h:124 std::pow(., 3)), 1: sqrt, 2: reciprocal, 3 .. 6: cbrt / cos / sin / acos
  * of pl_libm.h, 7 / 8: sine / cosine of pl_sincos (the quaternion exponential of the LM steps), 9: pf_half_rn((float)x),

@@ -575,6 +575,40 @@ def score_stream_group(members):
     return out, idle.value
 
 
+def score_prune_gate(kind: int, n_points: int, iterations: int) -> bool:
+    """Diagnostic (pl_debug_score_prune_gate): whether a batch step of `iterations` iterations of such a problem scores in the
+    pruned form.  Host arithmetic only: works without a device."""
+    return bool(L.check(L.lib().pl_debug_score_prune_gate(int(kind), int(n_points), int(iterations))))
+
+
+def score_pruned(members, route=0):
+    """Diagnostic (pl_debug_score_pruned): the pruned form of the matrix-core absolute-pose scorer on caller-given lists.
+    members: (problem, models, max_error, init_max, init_min) - one for route 0 (single launches), up to four for route 2 (group
+    launches behind an inactive slot).  Returns ([{"counts", "scores", "kept", "cand", "cstar", "chunks", "chunk_points", "lead",
+    "lead_max", "lead_min", "num_live", "num_selected", "slices"} per member], words changed in the inactive slot - which must be 0)."""
+    arr = (L.DebugPruneMember * max(len(members), 1))()
+    keep = []
+    cap = 4096
+    for i, (problem, models, max_error, init_max, init_min) in enumerate(members):
+        n, flat = problem._flat_models(models)
+        cnt = np.zeros(max(n, 1), dtype=np.uint32)
+        sc = np.zeros(max(n, 1), dtype=np.float64)
+        kp = np.zeros(max(n, 1), dtype=np.uint8)
+        cand = np.zeros(cap, dtype=np.uint32)
+        keep.append((n, flat, cnt, sc, kp, cand))
+        arr[i] = L.DebugPruneMember(problem._h, _ptr(flat), n, float(max_error), float(init_min), int(init_max), cap, _ptr(cnt),
+                                    _ptr(sc), _ptr(kp), _ptr(cand))
+    idle = C.c_uint32(0)
+    L.check(L.lib().pl_debug_score_pruned(int(route), arr, C.c_size_t(len(members)), C.byref(idle)))
+    out = []
+    for i, (n, _, cnt, sc, kp, cand) in enumerate(keep):
+        a = arr[i]
+        out.append({"counts": cnt[:n], "scores": sc[:n], "kept": kp[:n].astype(bool), "cand": cand[:min(a.num_cand, cap)].copy(),
+                    "num_cand": a.num_cand, "cstar": a.cstar, "chunks": a.chunks, "chunk_points": a.chunk_points, "lead": a.lead,
+                    "lead_max": a.lead_max, "lead_min": a.lead_min, "num_live": a.num_live, "num_selected": a.num_selected, "slices": a.slices})
+    return out, idle.value
+
+
 def ransac_batch(problems, opts, max_in_flight=4, group_size=16):
     """Many device-resident problems in one call (pl_ransac_batch): results of `problems[i].run(opts[i])`, bit for bit.
     Problems of the same kind advance in lock-step groups of `group_size` through one launch sequence."""

@@ -117,6 +117,7 @@ struct Context {
     // batch scratch
     DevBuf positions, samples, shadow16, lm2_states, lm2_partials, raw_a, raw_b, pts_arena, absmax, models, num_models, nan_bits, slots, num_hyp, part_count, part_score, count, score;
     DevBuf shadow, compact64;
+    DevBuf prune_sel, prune_kept, prune_state; // pruned scoring of the live list (PruneArgs)
     DevBuf live, rank, points16; // k_score_mfma: live hypothesis list, its inverse, operand rows of the correspondences
     DevBuf offsets, ctl, blk_best, rec_meta, rec_models, delta, flags;
     DevBuf gen_stage; // workspace of the staged 5-point generator
@@ -510,10 +511,12 @@ struct BatchShape {
     uint32_t chunks;     // the scorer's chunks of correspondences
     uint32_t point_rows; // matrix-core absolute pose: rows of the correspondences' operand table
     bool use_mfma;       // scored on the matrix cores (score_uses_mfma)
+    bool prune = false;  // matrix-core absolute pose: the step scores in two phases (score_prune_gate, driver_group.inc)
 };
+bool score_prune_gate(int kind, bool use_mfma, uint32_t iterations, uint32_t chunks); // (driver_group.inc, next to group_score_slices)
 struct BatchSizes { // bytes of every device buffer of the step
     size_t positions, delta, flags, samples, models, num_models, nan_bits, slots, offsets, ctl, shadow, compact64, shadow16, live, rank,
-        points16, part_count, part_score, count, score, blk_best, rec_meta, rec_models, gen_stage;
+        points16, part_count, part_score, count, score, blk_best, rec_meta, rec_models, gen_stage, prune_sel, prune_kept, prune_state;
 };
 struct BatchBuffers { // ... the buffers themselves, and where the kernels mirror their small results in pinned host memory
     uint32_t *positions, *samples /* explicit minimal samples of the share */, *num_models, *nan_bits, *slots, *offsets, *live, *rank;
@@ -525,6 +528,9 @@ struct BatchBuffers { // ... the buffers themselves, and where the kernels mirro
     uint32_t *part_count, *count;
     RecordMeta *rec_meta;
     char *shadow16, *points16, *blk_best, *gen_stage;
+    uint32_t *prune_sel; // pruned scoring (PruneArgs): the selection list, ...
+    uint8_t *prune_kept; // ... kept / pruned per live position, ...
+    char *prune_state;   // ... the PruneState and, 256 bytes behind it, the kept positions per tile of 1024
     RecordMeta *host_meta; // the first kRecordFirst candidates ...
     double *host_models;   // ... and their model records
     BatchCtl *host_ctl;    // the control block as the last kernel of the step finds it
@@ -536,6 +542,8 @@ size_t batch_ctl_bytes(uint32_t Bl, uint32_t chunks) {
     static_assert(sizeof(BatchCtl) % 4 == 0, "zeroed as 32-bit words");
     return sizeof(BatchCtl) + sizeof(uint32_t) * (2 * (size_t)batch_blocks(Bl) + 2 + chunks);
 }
+constexpr size_t kPruneTilesOffset = 256; // prune_state: the PruneState, from this offset the kept positions per tile
+static_assert(sizeof(PruneState) <= kPruneTilesOffset, "prune_state layout");
 constexpr size_t kBlkMinOffset = 1024; // blk_best: 256 running maxima (uint32_t), from this offset 256 running minima (double)
 
 BatchSizes batch_step_sizes(int kind, const BatchShape &s) {
@@ -572,6 +580,10 @@ BatchSizes batch_step_sizes(int kind, const BatchShape &s) {
     z.rec_meta = sizeof(RecordMeta) * kRecordCap;
     z.rec_models = sizeof(double) * kModelStride * kRecordCap;
     z.gen_stage = generate_stage_bytes(kind, s.Bl);
+    // pruned scoring of the live list: reserved with the list (a group's slot serves steps that prune and steps that do not)
+    z.prune_sel = abs16 ? sizeof(uint32_t) * hcap : 0;
+    z.prune_kept = abs16 ? hcap : 0;
+    z.prune_state = abs16 ? kPruneTilesOffset + sizeof(uint32_t) * ((hcap + 1023) / 1024) : 0;
     return z;
 }
 
@@ -668,6 +680,17 @@ void wire_batch_step(GroupArgs &a, const BatchRun &r, const BatchShape &s, const
     sa.part_count = b.part_count;
     sa.part_score = b.part_score;
     sa.tickets = blk_tot + 2 * (size_t)nblk + 2;
+    if (s.prune && live_list) { // lead, c*, selection (launch_score_pruned / launch_group_score)
+        PruneArgs &pa = sa.prune;
+        pa.st = reinterpret_cast<PruneState *>(b.prune_state);
+        pa.blk_kept = reinterpret_cast<uint32_t *>(b.prune_state + kPruneTilesOffset);
+        pa.sel = b.prune_sel;
+        pa.kept = b.prune_kept;
+        pa.chunks = s.chunks;
+        pa.chunk_points = s.point_rows / s.chunks;
+        pa.init_max = r.init_max, pa.init_min = r.init_min;
+        pa.lead = kPruneLead;
+    }
     // finalize + records
     RecordsArgs &ra = a.rec;
     ra.f.num_hyp = &b.ctl->num_hyp;
@@ -680,6 +703,8 @@ void wire_batch_step(GroupArgs &a, const BatchRun &r, const BatchShape &s, const
     ra.f.part_score = b.part_score;
     ra.f.count = b.count;
     ra.f.score = b.score;
+    ra.f.kept = sa.prune.kept; // (nullptr: the step does not prune)
+    ra.f.prune = sa.prune.st;
     ra.slots = b.slots;
     ra.models = b.models;
     ra.blk_max = reinterpret_cast<uint32_t *>(b.blk_best);
@@ -739,6 +764,9 @@ int context_batch_buffers(Context *c, const BatchSizes &z, BatchBuffers &b) {
     HIP_TRY(grown(c->rec_meta, z.rec_meta, b.rec_meta));
     HIP_TRY(grown(c->rec_models, z.rec_models, b.rec_models));
     HIP_TRY(grown(c->gen_stage, z.gen_stage, b.gen_stage));
+    HIP_TRY(grown(c->prune_sel, z.prune_sel, b.prune_sel));
+    HIP_TRY(grown(c->prune_kept, z.prune_kept, b.prune_kept));
+    HIP_TRY(grown(c->prune_state, z.prune_state, b.prune_state));
     HIP_TRY(c->h_small.ensure(sizeof(BatchCtl) + 64));
     HIP_TRY(c->h_rec_meta.ensure(sizeof(RecordMeta) * kRecordCap));
     HIP_TRY(c->h_gather_out.ensure(sizeof(double) * kModelStride * kRecordCap));
@@ -1122,6 +1150,11 @@ struct RansacRun {
         s.use_mfma = score_uses_mfma(kind, N, run.pf);
         s.chunks = score_chunks(kind, N, true, s.use_mfma);
         s.point_rows = abs16_point_rows(N);
+        // (no pruning here, whatever score_prune_gate says of the step: this launch is ONE resident round of workgroups, chunks that
+        // return at once leave their compute units idle and the lead, the selection and phase B come on top - measured 0.113 ->
+        // 0.269 ms per step of the flagship problem, profiles/score_prune.md.  The single launches of the pruned form stay behind
+        // pl_debug_score_pruned route 0.)
+        s.prune = false;
         b.device_positions = !host_positions && !force_host_positions && !prosac;
         if (b.device_positions) {
             // window of draw positions to evaluate: expected draws per iteration (sum N/(N-i)) + slack
@@ -1171,7 +1204,10 @@ struct RansacRun {
             HIP_TRY(launch_generate(kind, a.gen, c->stream));
             HIP_TRY(launch_compact2(a.comp, true, p->ps, c->stream));
             HIP_TRY(hipEventRecord(c->ev0, c->stream));
-            HIP_TRY(launch_score(kind, a.score, slices, c->stream));
+            if (a.score.prune.st)
+                HIP_TRY(launch_score_pruned(a.score, slices, c->stream));
+            else
+                HIP_TRY(launch_score(kind, a.score, slices, c->stream));
             HIP_TRY(hipEventRecord(c->ev1, c->stream));
             HIP_TRY(launch_finalize_records(a.rec, c->stream));
             HIP_TRY(launch_score_seq(kind, a.seq, c->stream));
@@ -2817,7 +2853,191 @@ int debug_score_group(pl_debug_score_member *m, size_t count, uint32_t *idle_cha
     }
     return PL_OK;
 }
+// The pruned form of the matrix-core absolute-pose scorer (PruneArgs) on lists the caller wrote, whatever score_prune_gate says of
+// their length: route 0 - launch_score_pruned and launch_finalize_records, the launches of RansacRun::enqueue_batch, on the single
+// launch's chunk shape; route 2 - a table with an inactive slot 0 through launch_group_score and launch_group_finalize_records, on
+// the group's chunk shape.  Every slot has an arena of its own, as in debug_score_group.
+int debug_score_pruned(int route, pl_debug_prune_member *m, size_t count, uint32_t *idle_changed) {
+    if (route != 0 && route != 2)
+        return fail(PL_ERR_INVALID, "route: 0 single launch, 2 group form");
+    if (!m || count == 0 || count > (route == 0 ? 1 : kDebugScoreMembers))
+        return fail(PL_ERR_INVALID, "the single launch takes one member, the group form 1 .. 4");
+    for (size_t i = 0; i < count; ++i) {
+        if (!m[i].problem || !m[i].models || m[i].n == 0 || m[i].n > (1u << 22) || m[i].problem->n == 0)
+            return fail(PL_ERR_INVALID, "member: problem / models missing, no correspondences, or n outside 1 .. 2^22");
+        if (m[i].problem->kind != EST_ABS)
+            return fail(PL_ERR_INVALID, "the pruned scorer is the absolute-pose one");
+        if (m[i].cand_cap && !m[i].cand)
+            return fail(PL_ERR_INVALID, "member: cand_cap without cand");
+    }
+    Context *c;
+    int rc = get_context(&c);
+    if (rc != PL_OK)
+        return rc;
+    for (size_t i = 0; i < count; ++i)
+        if (m[i].problem->device != c->device)
+            return fail(PL_ERR_INVALID, "problem lives on another device than the calling thread's");
+    struct Slot {
+        BatchRun run{};
+        BatchShape s{};
+        BatchSizes z{};
+        BatchBuffers b{};
+        size_t bytes = 0;
+        char *arena = nullptr;
+        ~Slot() {
+            if (arena)
+                (void)hipFree(arena);
+        }
+    } slot[1 + kDebugScoreMembers];
+    struct Scratch { // freed on every path
+        void *p = nullptr;
+        ~Scratch() {
+            if (p)
+                (void)hipFree(p);
+        }
+    } dtable;
+    GroupArgs ha[1 + kDebugScoreMembers];
+    GroupDims dims{};
+    dims.G = (uint32_t)count + 1;
+    dims.P = group_points_per_lane(EST_ABS);
+    uint32_t launch_chunks = 0;
+    for (size_t i = 0; i < count; ++i) {
+        Slot &t = slot[i + 1];
+        const pl_problem *p = m[i].problem;
+        t.run.kind = EST_ABS;
+        t.run.pts = p->ps;
+        t.run.thr2 = m[i].max_error * m[i].max_error;
+        t.run.pf = problem_prefilter(p, t.run.thr2);
+        t.run.init_max = m[i].init_max;
+        t.run.init_min = m[i].init_min;
+        t.s.Bl = (uint32_t)m[i].n, t.s.slots = 1;
+        t.s.use_mfma = score_uses_mfma(EST_ABS, p->n, t.run.pf);
+        if (!t.s.use_mfma)
+            return fail(PL_ERR_UNSUPPORTED, "member: not scored on the matrix cores (size, threshold or coordinates out of range)");
+        if (route == 0) {
+            t.s.chunks = score_chunks(EST_ABS, p->n, true, true);
+            t.s.point_rows = abs16_point_rows(p->n);
+        } else {
+            t.s.chunks = group_member_chunks(EST_ABS, true, p->n);
+            t.s.point_rows = t.s.chunks * 64u * (uint32_t)dims.P;
+        }
+        t.s.prune = true;
+        t.z = batch_step_sizes(EST_ABS, t.s);
+        launch_chunks += t.s.chunks;
+    }
+    slot[0].run = slot[1].run, slot[0].s = slot[1].s, slot[0].z = slot[1].z; // the inactive slot: a copy of the first member's
+    for (size_t k = (route == 0 ? 1 : 0); k <= count; ++k) {
+        Slot &t = slot[k];
+        BatchBuffers unused;
+        t.bytes = pack_batch_buffers(nullptr, t.z, unused);
+        HIP_TRY(hipMalloc((void **)&t.arena, t.bytes));
+        HIP_TRY(hipMemsetAsync(t.arena, k == 0 ? 0xa5 : 0, t.bytes, c->stream));
+        pack_batch_buffers(t.arena, t.z, t.b);
+        t.b.nan_bits = nullptr; // (no generator: k_live_list reads the records' flag words)
+        t.b.host_meta = nullptr, t.b.host_models = nullptr, t.b.host_ctl = nullptr;
+        wire_batch_step(ha[k], t.run, t.s, t.b);
+    }
+    ha[0].active = 0;
+    for (size_t i = 0; i < count; ++i) {
+        GroupArgs &a = ha[i + 1];
+        const Slot &t = slot[i + 1];
+        const uint32_t H = t.s.Bl;
+        a.slices = group_score_slices(EST_ABS, true, group_expected_hypotheses(EST_ABS, H, H), H, t.s.chunks, launch_chunks);
+        dims.max_B = std::max(dims.max_B, H);
+        dims.max_hcap = std::max(dims.max_hcap, a.score.hyp_capacity);
+        dims.max_chunks = std::max(dims.max_chunks, a.chunks);
+        dims.max_slices = std::max(dims.max_slices, a.slices);
+        dims.any_mfma = dims.any_prune = 1;
+        std::vector<double> recs;
+        std::vector<uint32_t> ident(H);
+        for (uint32_t k = 0; k < H; ++k)
+            ident[k] = k;
+        debug_score_records(m[i].problem, m[i].models, H, recs);
+        rc = debug_score_prepare(c, m[i].problem, a, t.b, t.z, recs, ident, H);
+        if (rc != PL_OK)
+            return rc;
+        HIP_TRY(hipStreamSynchronize(c->stream)); // (recs / ident leave scope)
+    }
+    uint32_t single_slices = 0;
+    if (route == 0) {
+        const GroupArgs &a = ha[1];
+        const uint32_t slices = std::max<uint32_t>(1u, std::min<uint32_t>(1536u / a.chunks, a.score.hyp_capacity)); // enqueue_batch's
+        single_slices = std::max<uint32_t>(1u, std::min<uint32_t>(slices * (uint32_t)kScoreThreads / (64u * (uint32_t)kStreamWaves),
+                                                                  score_slice_limit(EST_ABS, a.chunks, true))); // (launch_score_pruned's grid)
+        HIP_TRY(launch_score_pruned(a.score, slices, c->stream));
+        HIP_TRY(launch_finalize_records(a.rec, c->stream));
+    } else {
+        ha[0].slices = ha[1].slices;
+        HIP_TRY(hipMalloc(&dtable.p, sizeof(GroupArgs) * dims.G));
+        HIP_TRY(hipMemcpyAsync(dtable.p, ha, sizeof(GroupArgs) * dims.G, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(launch_group_score(EST_ABS, static_cast<const GroupArgs *>(dtable.p), dims, c->stream));
+        HIP_TRY(launch_group_finalize_records(static_cast<const GroupArgs *>(dtable.p), dims, c->stream));
+    }
+    std::vector<std::vector<uint32_t>> rank(count);
+    std::vector<std::vector<uint8_t>> kept(count);
+    std::vector<std::vector<RecordMeta>> meta(count);
+    std::vector<PruneState> st(count);
+    std::vector<BatchCtl> ctl(count);
+    for (size_t i = 0; i < count; ++i) {
+        const Slot &t = slot[i + 1];
+        const uint32_t H = t.s.Bl;
+        if (m[i].counts)
+            HIP_TRY(hipMemcpyAsync(m[i].counts, t.b.count, sizeof(uint32_t) * H, hipMemcpyDeviceToHost, c->stream));
+        if (m[i].scores)
+            HIP_TRY(hipMemcpyAsync(m[i].scores, t.b.score, sizeof(double) * H, hipMemcpyDeviceToHost, c->stream));
+        rank[i].resize(H), kept[i].resize(H), meta[i].resize(kRecordCap);
+        HIP_TRY(hipMemcpyAsync(rank[i].data(), t.b.rank, sizeof(uint32_t) * H, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(kept[i].data(), t.b.prune_kept, H, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(meta[i].data(), t.b.rec_meta, sizeof(RecordMeta) * kRecordCap, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(&st[i], t.b.prune_state, sizeof(PruneState), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(&ctl[i], t.b.ctl, sizeof(BatchCtl), hipMemcpyDeviceToHost, c->stream));
+    }
+    std::vector<uint32_t> idle(route == 2 ? slot[0].bytes / 4 : 0);
+    if (!idle.empty())
+        HIP_TRY(hipMemcpyAsync(idle.data(), slot[0].arena, idle.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(wait_stream(c));
+    uint32_t changed = 0;
+    for (uint32_t w : idle)
+        changed += w != 0xa5a5a5a5u ? 1u : 0u;
+    if (idle_changed)
+        *idle_changed = changed;
+    for (size_t i = 0; i < count; ++i) {
+        const uint32_t H = slot[i + 1].s.Bl, chunks = slot[i + 1].s.chunks;
+        const bool split = st[i].cstar < chunks; // (otherwise nothing was pruned and the flags were not written)
+        if (m[i].kept)
+            for (uint32_t k = 0; k < H; ++k)
+                m[i].kept[k] = (!split || rank[i][k] == kNoRank || kept[i][rank[i][k]]) ? 1 : 0;
+        m[i].num_cand = ctl[i].num_records;
+        for (uint32_t r = 0; r < std::min<uint32_t>({ctl[i].num_records, m[i].cand_cap, kRecordCap}); ++r)
+            m[i].cand[r] = meta[i][r].k;
+        m[i].cstar = st[i].cstar;
+        m[i].chunks = chunks;
+        m[i].chunk_points = slot[i + 1].s.point_rows / chunks;
+        m[i].lead = kPruneLead;
+        m[i].lead_max = st[i].lead_max;
+        m[i].lead_min = st[i].lead_min;
+        m[i].num_live = ctl[i].num_live;
+        m[i].num_selected = st[i].sel_len;
+        m[i].slices = route == 0 ? single_slices : ha[i + 1].slices;
+        m[i].pad = 0;
+    }
+    return PL_OK;
+}
 } // namespace
+int pl_debug_score_pruned(int route, pl_debug_prune_member *members, size_t num_members, uint32_t *idle_changed) {
+    if (idle_changed)
+        *idle_changed = 0;
+    return debug_score_pruned(route, members, num_members, idle_changed);
+}
+int pl_debug_score_prune_gate(int kind, uint32_t n_points, uint32_t iterations) {
+    PrefilterArgs pf{}; // as pl_debug_group_slices: a prefilter in range is assumed
+    pf.enabled = 1;
+    pf.g16 = pf.t16 = pf.h16 = 1.0f, pf.thr = 1.0f;
+    if (n_points == 0)
+        return fail(PL_ERR_INVALID, "pl_debug_score_prune_gate: n_points > 0");
+    const bool mfma = score_uses_mfma(kind, n_points, pf);
+    return score_prune_gate(kind, mfma, iterations, kind == EST_ABS ? score_chunks(kind, n_points, true, mfma) : 1u) ? 1 : 0;
+}
 int pl_debug_score_stream(pl_problem *p, const void *models, size_t n, double max_error, uint32_t *counts,
                           double *scores, int32_t *path_used) {
     return debug_score_single(p, models, n, max_error, 0, counts, scores, path_used, nullptr, nullptr);

@@ -224,6 +224,9 @@ size_t pack_batch_buffers(char *base, const BatchSizes &z, BatchBuffers &b) {
     take(b.rec_meta, z.rec_meta);
     take(b.rec_models, z.rec_models);
     take(b.gen_stage, z.gen_stage);
+    take(b.prune_sel, z.prune_sel);
+    take(b.prune_kept, z.prune_kept);
+    take(b.prune_state, z.prune_state);
     return o;
 }
 
@@ -346,6 +349,17 @@ static uint32_t group_score_slices(int kind, bool use_mfma, size_t hexp, uint32_
         return solo;
     launch_chunks = std::max(launch_chunks, chunks);
     return std::max<uint32_t>(1u, std::min<uint32_t>((kGroupScoreWorkgroups + launch_chunks - 1) / launch_chunks, solo));
+}
+// Which batch steps of a GROUP score in two phases (PruneArgs in pl_kernels.h; DESIGN.md section 4): the matrix-core absolute-pose
+// scorer, when the step is long enough for four more small launches to be nothing and the lead to be a small part of its list - at
+// least kPruneMinIterations iterations - and when there is a chunk to save: at least kPruneMinChunks chunks of correspondences.  Both
+// are known on the host before the step; nothing else decides (no option, no environment variable).  Default-option problems (batches
+// of 512 ... 4096 iterations) and problems of fewer than three chunks keep the single launch.  So does the single-problem path
+// (RansacRun::enqueue_batch): a group's launch is several resident rounds of workgroups, so workgroups that return at once make room
+// for others; the single launch is one round, and there the pruned form measured slower.
+constexpr uint32_t kPruneMinIterations = 8192, kPruneMinChunks = 3;
+bool score_prune_gate(int kind, bool use_mfma, uint32_t iterations, uint32_t chunks) {
+    return kind == EST_ABS && use_mfma && iterations >= kPruneMinIterations && chunks >= kPruneMinChunks;
 }
 // The rule's inputs for one member, shared by run_group and pl_debug_group_slices:
 // record slots per iteration.  5-point: up to 40 poses are possible, the single-problem path starts with 8 and repeats a batch
@@ -841,6 +855,7 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
             s.use_mfma = score_uses_mfma(kind, N, run.pf);
             s.chunks = group_member_chunks(kind, s.use_mfma, N);
             s.point_rows = s.chunks * 64u * (uint32_t)P;
+            s.prune = score_prune_gate(kind, s.use_mfma, B, s.chunks);
             const BatchBuffers bb = slot_buffers(i);
             wire_batch_step(a, run, s, bb);
             if (r.prosac) { // the member's samples of this step, drawn on the host (sampling.cc:85-136), uploaded below
@@ -859,6 +874,7 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
             dims.max_chunks = std::max(dims.max_chunks, a.chunks);
             dims.any_mfma |= a.use_mfma;
             dims.any_queue |= a.use_mfma ? 0u : 1u;
+            dims.any_prune |= a.score.prune.st ? 1u : 0u;
             ++nactive;
         }
         if (nactive == 0)

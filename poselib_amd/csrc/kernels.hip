@@ -1288,14 +1288,19 @@ __device__ __forceinline__ void mfma_drain(const uint16_t *queue, uint32_t first
 
 // The hypothesis stream of this kernel is the LIVE list (pipeline.hip compact2_body): `slots` = record index per live position,
 // *num_hyp_ptr = its length, shadow16 and the partials are indexed by live position; k_finalize2 maps them back (rank[]).
-template <int PG>
+// MODE (pruned scoring, PruneArgs in pl_kernels.h): kScoreAll - the stream is the whole list, today's code instruction for
+// instruction; kScoreLead - its first `lead` positions; kScoreSel - the stream is the selection `sel` (*num_hyp_ptr = its length):
+// entry i stands for the live position sel[i], one level of indirection for the operand row, the record slot and the partial column.
+constexpr int kScoreAll = 0, kScoreLead = 1, kScoreSel = 2;
+template <int PG, int MODE = kScoreAll>
 __device__ __forceinline__ void score_mfma_body(const PointSet &pts, const uint4 *__restrict__ shadow16,
                                                 const uint4 *__restrict__ points16,
                                                 const double *__restrict__ models, const uint32_t *__restrict__ slots,
                                                 const uint32_t *__restrict__ num_hyp_ptr, uint32_t hyp_capacity,
                                                 double thr2, uint32_t *__restrict__ part_count,
                                                 double *__restrict__ part_score, uint32_t slice, uint32_t chunk,
-                                                uint32_t nslices) {
+                                                uint32_t nslices, const uint32_t *__restrict__ sel = nullptr,
+                                                uint32_t lead = 0) {
     constexpr int kWaves = kMfmaThreads / 64;
     constexpr int NPW = 32 * PG; // correspondences per chunk
     __shared__ double s_pts[5][NPW];
@@ -1334,7 +1339,7 @@ __device__ __forceinline__ void score_mfma_body(const PointSet &pts, const uint4
         s_next_unit = 0;
     __syncthreads(); // the only workgroup barrier
 
-    const uint32_t H = *as_uniform(num_hyp_ptr);
+    const uint32_t H = MODE == kScoreLead ? min(*as_uniform(num_hyp_ptr), lead) : *as_uniform(num_hyp_ptr);
     uint16_t *const queue = s_queue[wave];
     double *const acc_s = s_acc_s[wave];
     uint32_t *const acc_c = s_acc_c[wave];
@@ -1351,7 +1356,12 @@ __device__ __forceinline__ void score_mfma_body(const PointSet &pts, const uint4
     uint32_t kb, gn;
     while (unit_of_ticket<32u>(ticket, H, waves_per_chunk, kb, gn)) {
         const uint32_t pending = request_ticket(); // the next unit's index travels while this one is evaluated
-        const uint32_t unit_slots = slots[kb + min((uint32_t)lane, gn - 1u)]; // lane l: the record of the unit's hypothesis l
+        // kScoreSel, lane l: the live position of the unit's hypothesis l (a unit has at most 64) - the row of an operand group
+        // is a lane permutation of it, like the record's slot in the exact pass
+        uint32_t unit_pos = 0;
+        if constexpr (MODE == kScoreSel)
+            unit_pos = sel[kb + min((uint32_t)lane, gn - 1u)];
+        const uint32_t unit_slots = slots[MODE == kScoreSel ? unit_pos : kb + min((uint32_t)lane, gn - 1u)]; // lane l: the record of the unit's hypothesis l
         acc_s[lane] = 0.0;
         acc_c[lane] = 0;
         uint32_t qhead = 0, qtail = 0;
@@ -1371,6 +1381,8 @@ __device__ __forceinline__ void score_mfma_body(const PointSet &pts, const uint4
         // same for the three instructions)
         auto load_a = [&](uint32_t hg, uint4 (&A)[kAbs16Dirs]) {
             const uint4 *row = shadow16 + (size_t)(kb + 32u * hg + (uint32_t)col) * 4;
+            if constexpr (MODE == kScoreSel)
+                row = shadow16 + (size_t)(uint32_t)__shfl((int)unit_pos, (int)(32u * hg + (uint32_t)col), 64) * 4;
 #pragma unroll
             for (int d = 0; d < kAbs16Dirs; ++d)
                 A[d] = row[half ? 3 : d];
@@ -1491,7 +1503,7 @@ __device__ __forceinline__ void score_mfma_body(const PointSet &pts, const uint4
             drain(qtail - qhead);
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         if ((uint32_t)lane < gn) {
-            const size_t o = (size_t)chunk * hyp_capacity + kb + lane;
+            const size_t o = MODE == kScoreSel ? (size_t)chunk * hyp_capacity + unit_pos : (size_t)chunk * hyp_capacity + kb + lane;
             part_score[o] = acc_s[lane];
             part_count[o] = acc_c[lane];
         }
@@ -1526,8 +1538,197 @@ __global__ __launch_bounds__(kMfmaThreads) __attribute__((amdgpu_waves_per_eu(4,
     score_mfma_body<PG>(a.pts, static_cast<const uint4 *>(a.shadow16), static_cast<const uint4 *>(a.points16), a.models, a.slots,
                         a.num_hyp, a.hyp_capacity, a.thr2, a.part_count, a.part_score, slice, chunk, g.slices);
 }
+// The launches of a pruned step (a.prune.st set; launch_score_pruned, launch_group_score): the same body on the same grid of (slice,
+// chunk) workgroups, three times.  kScoreLead: the first positions of the list against every chunk - k_prune_lead turns them into the
+// split chunk c*; kScoreAll: the whole list, workgroups of the chunks from c* on return at once; kScoreSel: the selection of
+// k_prune_list, workgroups of the chunks in front of c* return at once.  c* sits in device memory, the grid is the host's: no
+// synchronisation between them.
+// Hypothesis slices per chunk of the three launches, from the slices of the plain launch: every workgroup holds a resident slot
+// (LDS) from its dispatch on, also one that finds no unit or returns at once.  The lead has 32 units of 64 hypotheses per chunk -
+// two workgroups of 8 wavefronts; phase B has the lead and the few per cent that were kept, on a quarter of the chunks: a quarter
+// of the slices (measured on the flagship groups with the plain launch's grid for all three: lead 0.81 ms and phase B 0.98 ms in
+// flight next to 2.46 ms of phase A - profiles/score_prune.md).  Which wavefront scores a unit has no influence on its result.
+template <int MODE> __host__ __device__ constexpr uint32_t pruned_slices(uint32_t slices) {
+    return MODE == kScoreLead ? (slices < 2u ? slices : 2u) : MODE == kScoreSel ? (slices + 3u) / 4u : slices;
+}
+template <int PG, int MODE> __device__ __forceinline__ void score_mfma_pruned(const ScoreArgs &a, uint32_t slice, uint32_t chunk, uint32_t nslices) {
+    const PruneArgs &pr = a.prune;
+    const uint32_t *len = a.num_hyp;
+    if (!pr.st) { // (a member of a group's table whose step does not prune: the kScoreAll launch alone, every chunk)
+        if (MODE != kScoreAll)
+            return;
+    } else if constexpr (MODE != kScoreLead) {
+        const uint32_t cstar = *as_uniform(&pr.st->cstar);
+        if (MODE == kScoreAll ? chunk >= cstar : chunk < cstar)
+            return;
+    }
+    if constexpr (MODE == kScoreSel)
+        len = &pr.st->sel_len;
+    score_mfma_body<PG, MODE>(a.pts, static_cast<const uint4 *>(a.shadow16), static_cast<const uint4 *>(a.points16), a.models, a.slots,
+                              len, a.hyp_capacity, a.thr2, a.part_count, a.part_score, slice, chunk, nslices, pr.sel, pr.lead);
+}
+template <int PG, int MODE>
+__global__ __launch_bounds__(kMfmaThreads) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_score_mfma_pr(ScoreArgs a) {
+    uint32_t slice, chunk;
+    slice_chunk_of_workgroup(gridDim.x, gridDim.y, slice, chunk);
+    score_mfma_pruned<PG, MODE>(a, slice, chunk, gridDim.x);
+}
+template <int PG, int MODE>
+__global__ __launch_bounds__(kMfmaThreads) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_score_mfma_pr_g(const GroupArgs *ga) {
+    const GroupArgs &g = ga[blockIdx.z];
+    uint32_t slice, chunk;
+    // (a member whose step does not prune takes part in the kScoreAll launch alone: its own slices)
+    const uint32_t ns = pruned_slices<MODE>(g.slices);
+    if (!g.active || !g.use_mfma || !slice_chunk_of_workgroup(ns, g.chunks, slice, chunk))
+        return;
+    score_mfma_pruned<PG, MODE>(globalised(g.score), slice, chunk, ns);
+}
 
 // ---- two-view Sampson scores: the pre-filter on the matrix cores ----------------------------------------------------
+// ---- pruned scoring: lead and selection ----
+// (PruneArgs in pl_kernels.h).  k_prune_lead: the first `lead` live positions hold the partials of every
+// chunk; their best count and score - summed as finalize2_body sums them - together with the incumbent's are what every later
+// position of k_records' scan has in front of it at least.  A hypothesis that has seen S correspondences with cs inliers ends with
+// a count <= cs + (N - S) and a score >= sum + (S - cs) thr^2: from S >= max(lead_min / thr^2, N - lead_max) on a hypothesis
+// without inliers is no candidate.  c* = the fewest chunks that hold so many correspondences (+ kPruneMargin).
+__device__ __forceinline__ void prune_lead_body(const ScoreArgs &a) {
+    __shared__ uint32_t wmax[4];
+    __shared__ double wmin[4];
+    const PruneArgs &pr = a.prune;
+    const uint32_t n = min(*a.num_hyp, pr.lead), N = a.pts.n;
+    uint32_t bmax = 0;
+    double bmin = 1.7976931348623157e308;
+    for (uint32_t p = threadIdx.x; p < n; p += 256) {
+        uint32_t c = 0;
+        double s = 0.0;
+        for (uint32_t ch = 0; ch < pr.chunks; ++ch) {
+            c += a.part_count[(size_t)ch * a.hyp_capacity + p];
+            s += a.part_score[(size_t)ch * a.hyp_capacity + p];
+        }
+        bmax = max(bmax, c);
+        bmin = fmin(bmin, s + (double)(N - c) * a.thr2);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        bmax = max(bmax, (uint32_t)__shfl_xor(bmax, off, 64));
+        bmin = fmin(bmin, __shfl_xor(bmin, off, 64));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        wmax[threadIdx.x >> 6] = bmax;
+        wmin[threadIdx.x >> 6] = bmin;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t lmax = pr.init_max;
+        double lmin = pr.init_min;
+        for (int w = 0; w < 4; ++w) {
+            lmax = max(lmax, wmax[w]);
+            lmin = fmin(lmin, wmin[w]);
+        }
+        // correspondences a hypothesis has to have seen; anything that is not a number below N keeps every chunk
+        const double need = fmax(lmin / a.thr2, (double)(N - min(lmax, N))) + (double)kPruneMargin;
+        uint32_t cstar = pr.chunks;
+        if (need < (double)N) // (so need / chunk_points < chunks)
+            cstar = (uint32_t)ceil(need / (double)pr.chunk_points);
+        pr.st->lead_max = lmax;
+        pr.st->lead_min = lmin;
+        pr.st->cstar = max(1u, min(cstar, pr.chunks));
+        pr.st->sel_len = 0;
+        pr.st->pad = 0;
+    }
+}
+__global__ __launch_bounds__(256) void k_prune_lead(ScoreArgs a) { prune_lead_body(a); }
+__global__ __launch_bounds__(256) void k_prune_lead_g(const GroupArgs *ga) {
+    const GroupArgs &g = ga[blockIdx.z];
+    if (!g.active || !g.use_mfma || !g.score.prune.st)
+        return;
+    prune_lead_body(globalised(g.score));
+}
+
+// kept or pruned, for the live position p of a tile of 1024 (one thread each): phase A left the partials of the chunks [0, c*),
+// S correspondences.  Lead positions are kept.
+__device__ __forceinline__ uint32_t prune_keeps(const ScoreArgs &a, uint32_t p, uint32_t H, uint32_t cstar) {
+    const PruneArgs &pr = a.prune;
+    if (p >= H)
+        return 0u;
+    if (p < pr.lead)
+        return 1u;
+    const uint32_t N = a.pts.n, S = min(cstar * pr.chunk_points, N);
+    uint32_t cs = 0;
+    double sum = 0.0;
+    for (uint32_t ch = 0; ch < cstar; ++ch) {
+        cs += a.part_count[(size_t)ch * a.hyp_capacity + p];
+        sum += a.part_score[(size_t)ch * a.hyp_capacity + p];
+    }
+    const bool pruned = cs + (N - S) <= pr.st->lead_max && sum + (double)(S - cs) * a.thr2 > pr.st->lead_min * (1.0 + kPruneScoreMargin);
+    return pruned ? 0u : 1u;
+}
+// Two passes over the live list, a workgroup per tile of 1024 positions, no atomics (as k_compact2: totals per tile first, then
+// every tile starts at the sum of the tiles in front of it): flags and tile totals, then the ascending list of the kept positions.
+__device__ __forceinline__ void prune_flags_body(const ScoreArgs &a) {
+    __shared__ uint32_t wt[16];
+    const PruneArgs &pr = a.prune;
+    const uint32_t H = *a.num_hyp, cstar = pr.st->cstar;
+    if (cstar >= pr.chunks || blockIdx.x * 1024u >= H) // nothing is pruned: the list stays empty and the flags unread
+        return;
+    const uint32_t p = blockIdx.x * 1024u + threadIdx.x;
+    const uint32_t keep = prune_keeps(a, p, H, cstar);
+    if (p < H)
+        pr.kept[p] = (uint8_t)keep;
+    const uint32_t tot = wave_sum_u32(keep);
+    if ((threadIdx.x & 63) == 0)
+        wt[threadIdx.x >> 6] = tot;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t t = 0;
+        for (int w = 0; w < 16; ++w)
+            t += wt[w];
+        pr.blk_kept[blockIdx.x] = t;
+    }
+}
+__device__ __forceinline__ void prune_list_body(const ScoreArgs &a) {
+    __shared__ uint32_t wt[16], wb[16];
+    const PruneArgs &pr = a.prune;
+    const uint32_t H = *a.num_hyp, cstar = pr.st->cstar;
+    if (cstar >= pr.chunks || blockIdx.x * 1024u >= H)
+        return;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t before = 0;
+    for (uint32_t j = threadIdx.x; j < blockIdx.x; j += 1024u)
+        before += pr.blk_kept[j];
+    before = wave_sum_u32(before);
+    const uint32_t p = blockIdx.x * 1024u + threadIdx.x;
+    const uint32_t keep = p < H ? (uint32_t)pr.kept[p] : 0u;
+    const uint32_t inc = wave_scan_u32(keep);
+    if (lane == 63)
+        wt[wave] = inc;
+    if (lane == 0)
+        wb[wave] = before;
+    __syncthreads();
+    uint32_t at = inc - keep;
+    for (int w = 0; w < 16; ++w)
+        at += wb[w] + (w < wave ? wt[w] : 0u);
+    if (keep)
+        pr.sel[at] = p;
+    if (p == H - 1u)
+        pr.st->sel_len = at + keep;
+}
+__global__ __launch_bounds__(1024) void k_prune_flags(ScoreArgs a) { prune_flags_body(a); }
+__global__ __launch_bounds__(1024) void k_prune_list(ScoreArgs a) { prune_list_body(a); }
+__global__ __launch_bounds__(1024) void k_prune_flags_g(const GroupArgs *ga) {
+    const GroupArgs &g = ga[blockIdx.z];
+    if (!g.active || !g.use_mfma || !g.score.prune.st)
+        return;
+    prune_flags_body(globalised(g.score));
+}
+__global__ __launch_bounds__(1024) void k_prune_list_g(const GroupArgs *ga) {
+    const GroupArgs &g = ga[blockIdx.z];
+    if (!g.active || !g.use_mfma || !g.score.prune.st)
+        return;
+    prune_list_body(globalised(g.score));
+}
+
+
 // k_score_mfma2<EST, PG> (EST = relative pose / fundamental matrix): same contract, same queue and the same exact pass as
 // k_score_queue, but pass A is three v_mfma_f32_32x32x16_f16 per 32 hypotheses x 32 correspondences: two accumulate the
 // bilinear form C~ = b^T F a over fp16 high / low splits of both factors, one the quadratic forms S~ = Cx + Cy plus the
@@ -3807,6 +4008,60 @@ hipError_t launch_score_seq(int est, const SeqScoreArgs &a, hipStream_t stream) 
 }
 int tangent_score_chunk() { return kTangentChunk; }
 int radial1d_score_chunk() { return kRadialChunk; }
+// the two small steps of a pruned scoring launch (launch_score_pruned / launch_group_score): a tile of 1024 live
+// positions per workgroup, the grid sized by the capacity of the list
+hipError_t launch_prune_lead(const ScoreArgs &a, hipStream_t stream) {
+    k_prune_lead<<<dim3(1), dim3(256), 0, stream>>>(a);
+    return hipGetLastError();
+}
+hipError_t launch_prune_select(const ScoreArgs &a, hipStream_t stream) {
+    const uint32_t nb = std::max<uint32_t>(1u, (a.hyp_capacity + 1023u) / 1024u);
+    k_prune_flags<<<dim3(nb), dim3(1024), 0, stream>>>(a);
+    k_prune_list<<<dim3(nb), dim3(1024), 0, stream>>>(a);
+    return hipGetLastError();
+}
+hipError_t launch_group_prune_lead(const GroupArgs *args, const GroupDims &d, hipStream_t stream) {
+    k_prune_lead_g<<<dim3(1, 1, d.G), dim3(256), 0, stream>>>(args);
+    return hipGetLastError();
+}
+hipError_t launch_group_prune_select(const GroupArgs *args, const GroupDims &d, hipStream_t stream) {
+    const uint32_t nb = std::max<uint32_t>(1u, (d.max_hcap + 1023u) / 1024u);
+    k_prune_flags_g<<<dim3(nb, 1, d.G), dim3(1024), 0, stream>>>(args);
+    k_prune_list_g<<<dim3(nb, 1, d.G), dim3(1024), 0, stream>>>(args);
+    return hipGetLastError();
+}
+// The pruned form of the matrix-core absolute-pose launch (a.prune set by wire_batch_step: at least three chunks, i.e. 4 or 5
+// points per lane): the grid of launch_score_est, lead -> c* -> phase A -> selection -> phase B.
+template <int PG> static hipError_t launch_score_pruned_pg(const ScoreArgs &a, dim3 grid, hipStream_t stream) {
+    const dim3 block(kMfmaThreads);
+    const dim3 lead_grid(pruned_slices<kScoreLead>(grid.x), grid.y), sel_grid(pruned_slices<kScoreSel>(grid.x), grid.y);
+    k_score_mfma_pr<PG, kScoreLead><<<lead_grid, block, 0, stream>>>(a);
+    hipError_t e = launch_prune_lead(a, stream);
+    if (e != hipSuccess)
+        return e;
+    k_score_mfma_pr<PG, kScoreAll><<<grid, block, 0, stream>>>(a);
+    e = launch_prune_select(a, stream);
+    if (e != hipSuccess)
+        return e;
+    k_score_mfma_pr<PG, kScoreSel><<<sel_grid, block, 0, stream>>>(a);
+    return hipGetLastError();
+}
+hipError_t launch_score_pruned(const ScoreArgs &a, uint32_t slices, hipStream_t stream) {
+    uint32_t chunks;
+    int P;
+    score_shape(EST_ABS, a.pts.n, true, true, chunks, P);
+    if (!a.shadow16 || !a.points16 || !a.prune.st || a.prune.chunks != chunks || a.prune.chunk_points != 64u * (uint32_t)P)
+        return hipErrorInvalidValue;
+    const uint32_t mslices = std::min<uint32_t>(slices * (uint32_t)kScoreThreads / (uint32_t)kMfmaThreads,
+                                                score_slice_limit(EST_ABS, chunks, true));
+    const dim3 grid(xcd_slices(mslices), chunks);
+    if (P == 4)
+        return launch_score_pruned_pg<8>(a, grid, stream);
+    if (P == 5)
+        return launch_score_pruned_pg<10>(a, grid, stream);
+    return hipErrorInvalidValue; // (fewer points per lane: fewer than three chunks, such steps do not prune)
+}
+
 hipError_t launch_score(int est, const ScoreArgs &a, uint32_t slices, hipStream_t stream) {
     if (est == EST_RAD1D) {
         if (!a.shadow || !a.compact64)
@@ -3989,7 +4244,18 @@ int group_points_per_lane(int est) { return (est == EST_REL || est == EST_FUND) 
 template <int E> static hipError_t launch_group_score_est(const GroupArgs *args, const GroupDims &d, hipStream_t stream) {
     const dim3 grid(std::max<uint32_t>(1u, d.max_slices), std::max<uint32_t>(1u, d.max_chunks), d.G);
     if constexpr (E == EST_ABS) {
-        if (d.any_mfma)
+        if (d.any_mfma && d.any_prune) { // lead -> c* -> phase A -> selection -> phase B (k_score_mfma_pr)
+            const dim3 lead_grid(pruned_slices<kScoreLead>(grid.x), grid.y, grid.z), sel_grid(pruned_slices<kScoreSel>(grid.x), grid.y, grid.z);
+            k_score_mfma_pr_g<10, kScoreLead><<<lead_grid, dim3(kMfmaThreads), 0, stream>>>(args);
+            hipError_t e = launch_group_prune_lead(args, d, stream);
+            if (e != hipSuccess)
+                return e;
+            k_score_mfma_pr_g<10, kScoreAll><<<grid, dim3(kMfmaThreads), 0, stream>>>(args);
+            e = launch_group_prune_select(args, d, stream);
+            if (e != hipSuccess)
+                return e;
+            k_score_mfma_pr_g<10, kScoreSel><<<sel_grid, dim3(kMfmaThreads), 0, stream>>>(args);
+        } else if (d.any_mfma)
             k_score_mfma_g<10><<<grid, dim3(kMfmaThreads), 0, stream>>>(args);
         if (d.any_queue)
             k_score_queue_g<EST_ABS, 5><<<grid, dim3(kQueueThreads), 0, stream>>>(args);

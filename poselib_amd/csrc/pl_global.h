@@ -79,6 +79,10 @@ __device__ __forceinline__ ScoreArgs globalised(ScoreArgs a) {
     a.part_count = as_global(a.part_count);
     a.part_score = as_global(a.part_score);
     a.tickets = as_global(a.tickets);
+    a.prune.st = as_global(a.prune.st);
+    a.prune.blk_kept = as_global(a.prune.blk_kept);
+    a.prune.sel = as_global(a.prune.sel);
+    a.prune.kept = as_global(a.prune.kept);
     return a;
 }
 __device__ __forceinline__ FinalizeArgs globalised(FinalizeArgs f) {
@@ -88,6 +92,8 @@ __device__ __forceinline__ FinalizeArgs globalised(FinalizeArgs f) {
     f.part_score = as_global(f.part_score);
     f.count = as_global(f.count);
     f.score = as_global(f.score);
+    f.kept = as_global(f.kept);
+    f.prune = as_global(f.prune);
     return f;
 }
 __device__ __forceinline__ RecordsArgs globalised(RecordsArgs r) {
