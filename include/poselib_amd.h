@@ -509,6 +509,53 @@ int pl_debug_score_pruned(int route, pl_debug_prune_member *members, size_t num_
 /* Diagnostic: 1 if a batch step of `iterations` iterations of a problem of `kind` with n_points correspondences, as a member of a
  * lock-step group (pl_ransac_batch, pl_estimate_batch), scores in the pruned form, 0 if not; pl_ransac_run's own steps never do (coordinates and threshold in the pre-filter's range assumed, as pl_debug_group_slices).  Host arithmetic only. */
 int pl_debug_score_prune_gate(int kind, uint32_t n_points, uint32_t iterations);
+/* Diagnostic: the shape of the device sampler (k_sample_delta / k_sample_orbit) for a batch of B iterations of samples of K out of N
+ * correspondences.  window: the draw positions a batch step evaluates, as the driver sizes them (the argument `window` 0), or the
+ * caller's.  build: the build of the orbit kernel the launcher picks for (window, N, K) - 1 small, 2 large; a group's launch picks
+ * one build for (largest window, smallest N) of its members.  Per build: the flagged positions it holds, the most of them pointer
+ * doubling follows (more, up to `flags`: the one-lane walk) and the segments of its table.  tile: positions per tile of the ordered
+ * append.  PL_ERR_INVALID: K outside {3, 4, 5, 7}, N < K, B == 0.  Host arithmetic only: no device is touched.  tests/ takes every
+ * one of these numbers from here. */
+typedef struct pl_debug_sampler_shape_info {
+    uint64_t window;
+    uint32_t build, tile;
+    uint32_t small_flags, small_doubling, small_segments;
+    uint32_t large_flags, large_doubling, large_segments;
+} pl_debug_sampler_shape_info;
+int pl_debug_sampler_shape(int K, uint64_t N, uint32_t B, uint64_t window, pl_debug_sampler_shape_info *out);
+/* Diagnostic: the device sampler on its own.  A member is one draw stream (seed, pos_base), N correspondences, B iterations and a
+ * window of M positions (0: the driver's, pl_debug_sampler_shape's `window`; M_used returns it - size delta and flagbits by it).
+ *   drawn    (planted NULL) k_sample_delta<K> evaluates the window and clears the control block, k_sample_orbit walks it: the two
+ *            kernels of a batch step, through their launcher.
+ *   planted  M bytes: the delta table itself - draws an iteration starting at each position consumes, K for an ordinary one.  The
+ *            entry uploads it with the bitmap of delta != K (no bit at or behind M), clears the control block with a memset, as a
+ *            step whose positions come from the host does, and launches the orbit kernel alone: tables no draw stream produces.
+ *   route 0  one single-problem launch per member, one after the other.
+ *   route 2  the group form: a device-resident table whose slot 0 is INACTIVE, with pattern-filled buffers of its own
+ *            (*idle_changed: the 32-bit words the launches changed in them, which must be 0), then the 1 .. 4 members, wired as a
+ *            batch step wires them, in ONE launch; all drawn or all planted.
+ *   build    0: as the launcher picks it (route 2: for the largest window and the smallest N), 1: small, 2: large.
+ * Every member has buffers of its own, filled with the byte 0xa5 first; positions are set to all-ones.  Out, per member: positions
+ * (B words, relative to pos_base; unspecified where orbit_error is set), delta (M bytes), flagbits (M / 64 + 2 words: the bitmap's
+ * ceil(M / 64) words and what lies behind them, which must still be the pattern), pos_after, orbit_error, build_used, delta_guard (1:
+ * the 64 bytes behind delta[M] kept the pattern), ctl_clear (1: apart from pos_after and orbit_error every word of the control block
+ * and of the tables behind it is zero, and the word behind them kept the pattern).
+ * PL_ERR_INVALID: another route or build, no or more than four members, K outside {3, 4, 5, 7}, N < K or N >= 2^32, B == 0 or
+ * B > 2^20, M > 2^31 - 1, pos_base + M >= 2^32 - 1 (the driver's own limits), a missing positions pointer, drawn and planted members
+ * in one group. */
+typedef struct pl_debug_sampler_member {
+    uint64_t seed, pos_base, N;
+    uint32_t B, M;
+    const uint8_t *planted; /* NULL: drawn */
+    uint32_t *positions;    /* out: B words */
+    uint8_t *delta;         /* out: M bytes, may be NULL */
+    uint64_t *flagbits;     /* out: M / 64 + 2 words, may be NULL */
+    /* out */
+    uint64_t pos_after;
+    uint32_t orbit_error, M_used, build_used;
+    int32_t delta_guard, ctl_clear, pad;
+} pl_debug_sampler_member;
+int pl_debug_sample_positions(int route, int K, int build, pl_debug_sampler_member *members, size_t num_members, uint32_t *idle_changed);
 /* Diagnostic entry: the scalar math of the device kernels, element-wise on `n` doubles (n <= 2^28) - fn 0: the cube of
  * the LM's Nielsen update (optim/lm_impl.h:124 std::pow(., 3)), 1: sqrt, 2: reciprocal, 3 .. 6: cbrt / cos / sin / acos
  * of pl_libm.h, 7 / 8: sine / cosine of pl_sincos (the quaternion exponential of the LM steps), 9: pf_half_rn((float)x),

@@ -92,6 +92,17 @@ class DebugPruneMember(C.Structure):  # pl_debug_prune_member
                 ("lead_max", u32), ("num_live", u32), ("num_selected", u32), ("slices", u32), ("pad", u32), ("lead_min", f64)]
 
 
+class DebugSamplerShape(C.Structure):  # pl_debug_sampler_shape_info
+    _fields_ = [("window", u64), ("build", u32), ("tile", u32), ("small_flags", u32), ("small_doubling", u32), ("small_segments", u32),
+                ("large_flags", u32), ("large_doubling", u32), ("large_segments", u32)]
+
+
+class DebugSamplerMember(C.Structure):  # pl_debug_sampler_member
+    _fields_ = [("seed", u64), ("pos_base", u64), ("N", u64), ("B", u32), ("M", u32), ("planted", C.c_void_p), ("positions", C.c_void_p),
+                ("delta", C.c_void_p), ("flagbits", C.c_void_p), ("pos_after", u64), ("orbit_error", u32), ("M_used", u32),
+                ("build_used", u32), ("delta_guard", i32), ("ctl_clear", i32), ("pad", i32)]
+
+
 PL_F64, PL_F32 = 0, 1
 
 
@@ -204,6 +215,8 @@ def _declare(L):
         "pl_debug_score_stream_ex": (cint, [cint, P(DebugScoreMember), sz, P(C.c_uint32)]),
         "pl_debug_score_pruned": (cint, [cint, P(DebugPruneMember), sz, P(C.c_uint32)]),
         "pl_debug_score_prune_gate": (cint, [cint, C.c_uint32, C.c_uint32]),
+        "pl_debug_sampler_shape": (cint, [cint, u64, C.c_uint32, u64, P(DebugSamplerShape)]),
+        "pl_debug_sample_positions": (cint, [cint, cint, cint, P(DebugSamplerMember), sz, P(C.c_uint32)]),
         "pl_debug_device_math": (cint, [cint, vp, sz, vp]),
         "pl_debug_device_math2": (cint, [cint, vp, vp, sz, vp]),
         "pl_refine_model": (cint, [vp, P(BundleOptions), cam, vp, vp, P(C.c_uint32)]),
@@ -247,6 +260,7 @@ EXPORTED_SYMBOLS = [
     "pl_debug_score_shape", "pl_debug_score_stream_ex", "pl_debug_score_pruned", "pl_debug_score_prune_gate",
     "pl_estimate_absolute_pose_dev", "pl_estimate_relative_pose_dev", "pl_estimate_fundamental_dev", "pl_estimate_homography_dev",
     "pl_problem_create_dev", "pl_problem_create_tangent_dev", "pl_debug_check_device_points", "pl_debug_point_stats_dev",
+    "pl_debug_sampler_shape", "pl_debug_sample_positions",
     # (pl_estimate_1D_radial_absolute_pose and pl_ransac_1D_radial_pnp carry the reference's capital D: declared above, exported by the
     # library, but outside the lower-case pattern tests/test_cabi_surface.py lists the header's symbols with)
 ]

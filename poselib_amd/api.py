@@ -575,6 +575,61 @@ def score_stream_group(members):
     return out, idle.value
 
 
+def sampler_shape(K: int, N: int, B: int, window: int = 0):
+    """Diagnostic (pl_debug_sampler_shape): the device sampler for B iterations of samples of K out of N - {"window": positions a batch
+    step evaluates (the driver's, or `window`), "build": "small" | "large" as the launcher picks it for (window, N, K), "small" /
+    "large": {"flags", "doubling", "segments"} capacities of either build of the orbit kernel, "tile": positions per tile of its
+    ordered append}.  Host arithmetic only: works without a device."""
+    s = L.DebugSamplerShape()
+    L.check(L.lib().pl_debug_sampler_shape(int(K), int(N), int(B), int(window), C.byref(s)))
+    return {"window": int(s.window), "build": "small" if s.build == 1 else "large", "tile": int(s.tile),
+            "small": {"flags": s.small_flags, "doubling": s.small_doubling, "segments": s.small_segments},
+            "large": {"flags": s.large_flags, "doubling": s.large_doubling, "segments": s.large_segments}}
+
+
+_SAMPLER_BUILDS = {None: 0, "small": 1, "large": 2}
+
+
+def sample_positions(K: int, members, build=None, group: bool = False):
+    """Diagnostic (pl_debug_sample_positions): the device sampler's kernels on their own.  members: up to four dicts {"seed",
+    "pos_base", "N", "B", "M" (0 / absent: the driver's window), "planted" (absent: the window is drawn; else the delta table itself,
+    M bytes, and only the orbit kernel runs)}.  build: None - the launcher's choice -, "small" or "large".  group False: one
+    single-problem launch per member; True: all members in one launch of the group form, behind an inactive table slot.  Returns
+    ([{"positions", "delta", "flagbits" (the bitmap's ceil(M / 64) words), "guard" (the words behind them), "pos_after",
+    "orbit_error", "M", "build", "delta_guard", "ctl_clear"} per member], words the launch changed in the inactive slot's buffers -
+    which must be 0)."""
+    arr = (L.DebugSamplerMember * max(len(members), 1))()
+    keep = []
+    for i, m in enumerate(members):
+        planted = m.get("planted")
+        if planted is not None:
+            planted = np.ascontiguousarray(planted, dtype=np.uint8)
+            M = int(planted.size)
+            if m.get("M", 0) not in (0, M):
+                raise ValueError("a planted table has M bytes")
+        else:
+            M = int(m.get("M", 0)) or sampler_shape(K, m["N"], m["B"])["window"]
+        pos = np.zeros(max(int(m["B"]), 1), dtype=np.uint32)
+        cap = M if M < (1 << 31) else 0  # (a longer window is refused before anything is written)
+        delta = np.zeros(cap + 1, dtype=np.uint8)
+        bits = np.zeros(cap // 64 + 2, dtype=np.uint64)
+        keep.append((planted, pos, delta, bits))
+        arr[i] = L.DebugSamplerMember(int(m.get("seed", 0)), int(m.get("pos_base", 0)), int(m["N"]), int(m["B"]), M,
+                                      None if planted is None else _ptr(planted), _ptr(pos), _ptr(delta), _ptr(bits))
+    idle = C.c_uint32(0)
+    L.check(L.lib().pl_debug_sample_positions(2 if group else 0, int(K), _SAMPLER_BUILDS[build], arr, C.c_size_t(len(members)),
+                                              C.byref(idle)))
+    out = []
+    for i, (_, pos, delta, bits) in enumerate(keep):
+        a = arr[i]
+        words = (a.M_used + 63) // 64
+        out.append({"positions": pos, "delta": delta[:a.M_used], "flagbits": bits[:words], "guard": bits[words:a.M_used // 64 + 2],
+                    "pos_after": int(a.pos_after), "orbit_error": int(a.orbit_error), "M": int(a.M_used),
+                    "build": "small" if a.build_used == 1 else "large", "delta_guard": bool(a.delta_guard),
+                    "ctl_clear": bool(a.ctl_clear)})
+    return out, idle.value
+
+
 def score_prune_gate(kind: int, n_points: int, iterations: int) -> bool:
     """Diagnostic (pl_debug_score_prune_gate): whether a batch step of `iterations` iterations of such a problem scores in the
     pruned form.  Host arithmetic only: works without a device."""

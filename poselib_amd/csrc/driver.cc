@@ -150,7 +150,7 @@ int get_context(Context **out) {
         return fail(PL_ERR_INVALID, "device index out of range");
     // (a context bound to another device is simply leaked for the lifetime of the thread)
     {
-        // the kernels are built for gfx950 only (k_sample_orbit alone keeps ~116 KB of static LDS): say so instead of
+        // the kernels are built for gfx950 only (k_sample_orbit's large build alone keeps ~140 KB of static LDS): say so instead of
         // failing with "invalid device function" at the first launch
         hipDeviceProp_t prop;
         HIP_TRY(hipGetDeviceProperties(&prop, g_requested_device));
@@ -514,6 +514,15 @@ struct BatchShape {
     bool prune = false;  // matrix-core absolute pose: the step scores in two phases (score_prune_gate, driver_group.inc)
 };
 bool score_prune_gate(int kind, bool use_mfma, uint32_t iterations, uint32_t chunks); // (driver_group.inc, next to group_score_slices)
+// The device sampler's window (BatchShape.M) for a batch of B iterations over N >= K correspondences: the draws an iteration is
+// expected to consume (sum N / (N - i)), 5 % on top, and 8192 positions of slack.  The single run, a group's slot and every member
+// of a group's step size their windows here, so no member of a full-size batch outgrows the slot.
+uint64_t sampler_window(uint32_t N, int K, uint32_t B) {
+    double per_it = 0;
+    for (int i = 0; i < K; ++i)
+        per_it += static_cast<double>(N) / static_cast<double>(N - (uint32_t)i);
+    return (uint64_t)(B * per_it * 1.05) + 8192;
+}
 struct BatchSizes { // bytes of every device buffer of the step
     size_t positions, delta, flags, samples, models, num_models, nan_bits, slots, offsets, ctl, shadow, compact64, shadow16, live, rank,
         points16, part_count, part_score, count, score, blk_best, rec_meta, rec_models, gen_stage, prune_sel, prune_kept, prune_state;
@@ -731,6 +740,14 @@ void wire_batch_step(GroupArgs &a, const BatchRun &r, const BatchShape &s, const
     qa.host_cap = kRecordFirst;
     qa.ctl_src = b.ctl;
     qa.ctl_host = b.host_ctl;
+}
+
+// A member's part in the extents of a group's sampler launch (launch_group_positions: the grid of k_sample_delta_g, the build of
+// k_sample_orbit_g); a fresh GroupDims starts with min_n = 0xffffffff.
+void group_dims_sampler(GroupDims &d, uint32_t M, uint32_t n, uint32_t B) {
+    d.max_M = std::max(d.max_M, M);
+    d.min_n = std::min(d.min_n, n);
+    d.max_B = std::max(d.max_B, B);
 }
 
 // The step's buffers in the Context (the single-problem path), grown to `z`.
@@ -1157,11 +1174,7 @@ struct RansacRun {
         s.prune = false;
         b.device_positions = !host_positions && !force_host_positions && !prosac;
         if (b.device_positions) {
-            // window of draw positions to evaluate: expected draws per iteration (sum N/(N-i)) + slack
-            double per_it = 0;
-            for (int i = 0; i < K; ++i)
-                per_it += static_cast<double>(N) / static_cast<double>(N - i);
-            const uint64_t M64 = (uint64_t)(s.B * per_it * 1.05) + 8192;
+            const uint64_t M64 = sampler_window(N, K, s.B); // window of draw positions to evaluate
             if (M64 > 0x7fffffffull || pos + M64 >= 0xffffffffull)
                 b.device_positions = false;
             else
@@ -3082,6 +3095,174 @@ int pl_debug_score_shape(int kind, uint32_t n_points, int matrix_core, int group
     return PL_OK;
 }
 
+// Diagnostic: the device sampler's window and the orbit kernel's builds, as the driver and the launchers compute them.  No device call.
+int pl_debug_sampler_shape(int K, uint64_t N, uint32_t B, uint64_t window, pl_debug_sampler_shape_info *out) {
+    if ((K != 3 && K != 4 && K != 5 && K != 7) || N < (uint64_t)K || N > 0xffffffffull || B == 0 || !out)
+        return fail(PL_ERR_INVALID, "pl_debug_sampler_shape: K in {3, 4, 5, 7}, K <= N < 2^32, B > 0, output pointer");
+    const uint64_t M = window ? window : sampler_window((uint32_t)N, K, B);
+    const OrbitShape sm = orbit_build_shape(true), lg = orbit_build_shape(false);
+    out->window = M;
+    out->build = (M <= 0xffffffffull && orbit_small_build((uint32_t)M, N, K)) ? 1u : 2u;
+    out->tile = sm.tile;
+    out->small_flags = sm.flags, out->small_doubling = sm.doubling, out->small_segments = sm.segments;
+    out->large_flags = lg.flags, out->large_doubling = lg.doubling, out->large_segments = lg.segments;
+    return PL_OK;
+}
+// Diagnostic: the sampler's launches on their own (the header states the contract).  Every slot - the inactive one of the group form
+// included - has an arena of its own that holds the four buffers the sampler touches, sized by batch_step_sizes and packed by
+// pack_batch_buffers; the table entries are wire_batch_step's.
+int pl_debug_sample_positions(int route, int K, int build, pl_debug_sampler_member *m, size_t count, uint32_t *idle_changed) {
+    if (idle_changed)
+        *idle_changed = 0;
+    if (route != 0 && route != 2)
+        return fail(PL_ERR_INVALID, "route: 0 single launches, 2 group form");
+    if (build < 0 || build > 2)
+        return fail(PL_ERR_INVALID, "build: 0 the launcher's choice, 1 small, 2 large");
+    if (K != 3 && K != 4 && K != 5 && K != 7)
+        return fail(PL_ERR_INVALID, "K: 3, 4, 5 or 7");
+    constexpr size_t kMembers = 4;
+    if (!m || count == 0 || count > kMembers)
+        return fail(PL_ERR_INVALID, "1 .. 4 members");
+    const int kind = K == 3 ? EST_ABS : K == 5 ? EST_REL : K == 7 ? EST_FUND : EST_HOM;
+    uint64_t window[kMembers];
+    for (size_t i = 0; i < count; ++i) {
+        if (m[i].N < (uint64_t)K || m[i].N > 0xffffffffull || m[i].B == 0 || m[i].B > (1u << 20) || !m[i].positions)
+            return fail(PL_ERR_INVALID, "member: K <= N < 2^32, B in 1 .. 2^20, positions");
+        window[i] = m[i].M ? m[i].M : sampler_window((uint32_t)m[i].N, K, m[i].B);
+        if (window[i] > 0x7fffffffull || m[i].pos_base + window[i] >= 0xffffffffull || m[i].pos_base >= 0xffffffffull) // (enqueue_batch's limits)
+            return fail(PL_ERR_INVALID, "member: a window beyond 2^31 - 1 positions, or one that ends at or beyond draw 2^32 - 1");
+        if (route == 2 && (m[i].planted != nullptr) != (m[0].planted != nullptr))
+            return fail(PL_ERR_INVALID, "a group is drawn or planted as a whole");
+    }
+    Context *c;
+    int rc = get_context(&c);
+    if (rc != PL_OK)
+        return rc;
+    struct Slot {
+        BatchRun run{};
+        BatchShape s{};
+        BatchSizes z{};
+        BatchBuffers b{};
+        size_t bytes = 0;
+        char *arena = nullptr;
+        ~Slot() {
+            if (arena)
+                (void)hipFree(arena);
+        }
+    } slot[1 + kMembers];
+    struct Scratch { // freed on every path
+        void *p = nullptr;
+        ~Scratch() {
+            if (p)
+                (void)hipFree(p);
+        }
+    } dtable;
+    GroupArgs ha[1 + kMembers];
+    GroupDims dims{};
+    dims.G = (uint32_t)count + 1;
+    dims.min_n = 0xffffffffu;
+    for (size_t i = 0; i < count; ++i) {
+        Slot &t = slot[i + 1];
+        t.run.kind = kind;
+        t.run.pts.n = (uint32_t)m[i].N;
+        t.run.seed = m[i].seed, t.run.pos = m[i].pos_base;
+        t.s.B = t.s.Bl = m[i].B, t.s.M = (uint32_t)window[i], t.s.slots = 1, t.s.chunks = 1;
+        const BatchSizes full = batch_step_sizes(kind, t.s);
+        t.z.positions = full.positions, t.z.delta = full.delta, t.z.flags = full.flags, t.z.ctl = full.ctl; // (the sampler's buffers only)
+    }
+    slot[0].run = slot[1].run, slot[0].s = slot[1].s, slot[0].z = slot[1].z; // the inactive slot: a copy of the first member's
+    std::vector<uint64_t> bits;
+    for (size_t k = (route == 0 ? 1 : 0); k <= count; ++k) {
+        Slot &t = slot[k];
+        BatchBuffers unused;
+        t.bytes = pack_batch_buffers(nullptr, t.z, unused);
+        t.bytes += 256; // (the word behind the control block is read back, whatever the block's size)
+        HIP_TRY(hipMalloc((void **)&t.arena, t.bytes));
+        HIP_TRY(hipMemsetAsync(t.arena, 0xa5, t.bytes, c->stream));
+        pack_batch_buffers(t.arena, t.z, t.b);
+        t.b.host_meta = nullptr, t.b.host_models = nullptr, t.b.host_ctl = nullptr;
+        wire_batch_step(ha[k], t.run, t.s, t.b);
+        if (k == 0)
+            continue;
+        const pl_debug_sampler_member &mi = m[k - 1];
+        group_dims_sampler(dims, t.s.M, t.run.pts.n, t.s.B);
+        HIP_TRY(hipMemsetAsync(t.b.positions, 0xff, t.z.positions, c->stream));
+        if (mi.planted) {
+            const uint32_t M = t.s.M, words = (M + 63u) / 64u;
+            bits.assign(words, 0ull);
+            for (uint32_t p = 0; p < M; ++p)
+                if (mi.planted[p] != (uint8_t)K)
+                    bits[p >> 6] |= 1ull << (p & 63u);
+            HIP_TRY(hipMemcpyAsync(t.b.delta, mi.planted, M, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync(t.b.flags, bits.data(), sizeof(uint64_t) * words, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipMemsetAsync(t.b.ctl, 0, t.z.ctl, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream)); // (`bits` is reused)
+        }
+    }
+    const bool planted = m[0].planted != nullptr;
+    uint32_t build_used[1 + kMembers] = {};
+    if (route == 0) {
+        for (size_t i = 0; i < count; ++i) {
+            const SampleArgs &sa = ha[i + 1].samp;
+            HIP_TRY(m[i].planted ? launch_sample_orbit(K, sa, c->stream, build) : launch_sample_positions(K, sa, c->stream, build));
+            build_used[i + 1] = build ? (uint32_t)build : (orbit_small_build(sa.M, sa.N, K) ? 1u : 2u);
+        }
+    } else {
+        ha[0].active = 0;
+        HIP_TRY(hipMalloc(&dtable.p, sizeof(GroupArgs) * dims.G));
+        HIP_TRY(hipMemcpyAsync(dtable.p, ha, sizeof(GroupArgs) * dims.G, hipMemcpyHostToDevice, c->stream));
+        const GroupArgs *table = static_cast<const GroupArgs *>(dtable.p);
+        HIP_TRY(planted ? launch_group_orbit(K, table, dims, c->stream, build) : launch_group_positions(K, table, dims, c->stream, build));
+        for (size_t i = 0; i < count; ++i)
+            build_used[i + 1] = build ? (uint32_t)build : (orbit_small_build(dims.max_M, dims.min_n, K) ? 1u : 2u);
+    }
+    std::vector<uint8_t> hdelta[kMembers];
+    std::vector<uint64_t> hflags[kMembers];
+    std::vector<uint32_t> hctl[kMembers];
+    for (size_t i = 0; i < count; ++i) {
+        const Slot &t = slot[i + 1];
+        hdelta[i].resize(t.z.delta), hflags[i].resize(t.z.flags / sizeof(uint64_t)), hctl[i].resize(t.z.ctl / 4 + 1);
+        HIP_TRY(hipMemcpyAsync(m[i].positions, t.b.positions, t.z.positions, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(hdelta[i].data(), t.b.delta, t.z.delta, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(hflags[i].data(), t.b.flags, t.z.flags, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(hctl[i].data(), t.b.ctl, sizeof(uint32_t) * hctl[i].size(), hipMemcpyDeviceToHost, c->stream));
+    }
+    std::vector<uint32_t> idle(route == 2 ? slot[0].bytes / 4 : 0);
+    if (!idle.empty())
+        HIP_TRY(hipMemcpyAsync(idle.data(), slot[0].arena, idle.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(wait_stream(c));
+    uint32_t changed = 0;
+    for (uint32_t w : idle)
+        changed += w != 0xa5a5a5a5u ? 1u : 0u;
+    if (idle_changed)
+        *idle_changed = changed;
+    for (size_t i = 0; i < count; ++i) {
+        const Slot &t = slot[i + 1];
+        const uint32_t M = t.s.M;
+        BatchCtl ctl;
+        std::memcpy(&ctl, hctl[i].data(), sizeof(ctl));
+        m[i].pos_after = ctl.pos_after;
+        m[i].orbit_error = ctl.orbit_error;
+        m[i].M_used = M;
+        m[i].build_used = build_used[i + 1];
+        if (m[i].delta)
+            std::memcpy(m[i].delta, hdelta[i].data(), M);
+        if (m[i].flagbits)
+            std::memcpy(m[i].flagbits, hflags[i].data(), t.z.flags);
+        bool guard = true;
+        for (size_t k = M; k < hdelta[i].size(); ++k)
+            guard = guard && hdelta[i][k] == 0xa5u;
+        m[i].delta_guard = guard ? 1 : 0;
+        ctl.pos_after = 0, ctl.orbit_error = 0;
+        std::memcpy(hctl[i].data(), &ctl, sizeof(ctl));
+        bool clear = hctl[i].back() == 0xa5a5a5a5u;
+        for (size_t k = 0; k + 1 < hctl[i].size(); ++k)
+            clear = clear && hctl[i][k] == 0u;
+        m[i].ctl_clear = clear ? 1 : 0;
+        m[i].pad = 0;
+    }
+    return PL_OK;
+}
 
 int pl_debug_device_math(int fn, const double *x, size_t n, double *out) {
     if (fn < 0 || fn >= kDeviceMathFns)

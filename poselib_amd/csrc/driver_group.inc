@@ -437,14 +437,11 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
         }
     }
     const uint32_t maxm = group_record_slots(kind); // record slots per iteration
-    // draws per iteration (expected, without duplicates): sum_k N / (N - k), largest for the smallest problem of the group -
-    // the same expression sizes every item's window below (M64), so no item of a full-size batch outgrows the slot
+    // the sampler window (sampler_window) is largest for the smallest problem of the group - the same function sizes every item's
+    // window below (M64), so no item of a full-size batch outgrows the slot
     uint32_t min_n = (*pit[0]).n;
     for (uint32_t i = 1; i < count; ++i)
         min_n = std::min(min_n, (*pit[i]).n);
-    double per_it = 0;
-    for (int i = 0; i < K; ++i)
-        per_it += static_cast<double>(min_n) / static_cast<double>(min_n - (uint32_t)i);
     // chunks of correspondences: 64 P per chunk, or 32 PG on the matrix-core Sampson form (the larger count sizes the arena)
     const int Pm = (kind == EST_REL || kind == EST_FUND) ? group_mfma2_points_per_lane(kind) : P;
     const uint32_t max_chunks = std::max<uint32_t>(1u, (max_n + 64 * std::min(P, Pm) - 1) / (64 * std::min(P, Pm)));
@@ -477,7 +474,7 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
     uint32_t max_M = 0;
     GroupLayout L;
     for (;;) {
-        max_M = (uint32_t)(max_B * per_it * 1.05) + 8192;
+        max_M = (uint32_t)sampler_window(min_n, K, max_B);
         L = group_layout(kind, max_n, max_B, max_M, maxm, max_chunks, resident);
         if (L.total * count <= arena_budget || max_B <= 4096)
             break;
@@ -841,10 +838,7 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
                 g.b.B = g.b.hi_g = g.b.Bl = max_B;
             const uint32_t B = g.b.B;
             const uint32_t N = g.n;
-            double pit = 0;
-            for (int k = 0; k < K; ++k)
-                pit += static_cast<double>(N) / static_cast<double>(N - k);
-            const uint64_t M64 = (uint64_t)(B * pit * 1.05) + 8192;
+            const uint64_t M64 = sampler_window(N, K, B);
             if (M64 > max_M || r.pos + M64 >= 0xffffffffull) {
                 g.active = false, g.fallback = true;
                 continue;
@@ -867,9 +861,7 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
             const uint32_t hcap = a.score.hyp_capacity;
             hexp_of[i] = group_expected_hypotheses(kind, B, hcap);
             // grid extents
-            dims.max_M = std::max(dims.max_M, a.samp.M);
-            dims.min_n = std::min(dims.min_n, g.n);
-            dims.max_B = std::max(dims.max_B, B);
+            group_dims_sampler(dims, a.samp.M, g.n, B);
             dims.max_hcap = std::max(dims.max_hcap, hcap);
             dims.max_chunks = std::max(dims.max_chunks, a.chunks);
             dims.any_mfma |= a.use_mfma;

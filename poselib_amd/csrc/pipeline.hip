@@ -391,7 +391,7 @@ template <bool SMALL> __global__ __launch_bounds__(1024) void k_sample_orbit_g(c
         sample_orbit_body<kMaxFlags, kParFlags, kMaxSegments>(s.delta, s.flagbits, s.M, K, s.B, s.pos_base, s.positions, s.ctl);
 }
 // expected number of flagged positions among M: a position is flagged when the K draws starting there repeat an index
-static bool orbit_small_build(uint32_t M, uint64_t N, int K) {
+bool orbit_small_build(uint32_t M, uint64_t N, int K) {
     if (N == 0)
         return false;
     double distinct = 1.0;
@@ -399,6 +399,16 @@ static bool orbit_small_build(uint32_t M, uint64_t N, int K) {
         distinct *= 1.0 - std::min(1.0, (double)i / (double)N);
     return (double)M * (1.0 - distinct) <= kOrbitSmallExpected;
 }
+OrbitShape orbit_build_shape(bool small) {
+    OrbitShape s;
+    s.flags = (uint32_t)(small ? kSmallFlags : kMaxFlags);
+    s.doubling = (uint32_t)(small ? kSmallFlags : kParFlags);
+    s.segments = (uint32_t)(small ? kSmallFlags : kMaxSegments);
+    s.tile = 1024u * (uint32_t)kOrbitWords * 64u;
+    return s;
+}
+// build: 0 = what orbit_small_build says of (M, N, K), 1 = the small build, 2 = the large one
+static bool orbit_take_small(int build, uint32_t M, uint64_t N, int K) { return build == 0 ? orbit_small_build(M, N, K) : build == 1; }
 
 // ------------------------------------------------------------------------------------ compaction
 __global__ __launch_bounds__(1024) void k_count_blocks(const uint32_t *num_models, uint32_t B, uint32_t *blk_tot) {
@@ -1152,7 +1162,7 @@ hipError_t launch_prepare(const double *a_raw, const double *b_raw, uint32_t n, 
     return hipGetLastError();
 }
 
-hipError_t launch_sample_positions(int K, const SampleArgs &a, hipStream_t stream) {
+hipError_t launch_sample_positions(int K, const SampleArgs &a, hipStream_t stream, int build) {
     const uint64_t seed = a.seed, pos_base = a.pos_base, N = a.N;
     const uint32_t B = a.B, M = a.M, zero_words = a.zero_words;
     uint8_t *const delta = a.delta;
@@ -1177,10 +1187,21 @@ hipError_t launch_sample_positions(int K, const SampleArgs &a, hipStream_t strea
     default:
         return hipErrorInvalidValue;
     }
-    if (orbit_small_build(M, N, K))
+    if (orbit_take_small(build, M, N, K))
         k_sample_orbit<true><<<dim3(1), dim3(1024), 0, stream>>>(delta, flagbits, M, K, B, pos_base, positions, ctl);
     else
         k_sample_orbit<false><<<dim3(1), dim3(1024), 0, stream>>>(delta, flagbits, M, K, B, pos_base, positions, ctl);
+    return hipGetLastError();
+}
+// the orbit walk alone, over a delta table and a bitmap that are in place (launch_sample_positions' second kernel; the diagnostic
+// entry pl_debug_sample_positions plants tables no draw stream produces)
+hipError_t launch_sample_orbit(int K, const SampleArgs &a, hipStream_t stream, int build) {
+    if (K != 3 && K != 4 && K != 5 && K != 7)
+        return hipErrorInvalidValue;
+    if (orbit_take_small(build, a.M, a.N, K))
+        k_sample_orbit<true><<<dim3(1), dim3(1024), 0, stream>>>(a.delta, a.flagbits, a.M, K, a.B, a.pos_base, a.positions, a.ctl);
+    else
+        k_sample_orbit<false><<<dim3(1), dim3(1024), 0, stream>>>(a.delta, a.flagbits, a.M, K, a.B, a.pos_base, a.positions, a.ctl);
     return hipGetLastError();
 }
 
@@ -1255,7 +1276,7 @@ hipError_t launch_finalize(const FinalizeArgs &f, hipStream_t stream) {
 }
 
 // ---- group launches (problem = blockIdx.z) ----
-hipError_t launch_group_positions(int K, const GroupArgs *args, const GroupDims &d, hipStream_t stream) {
+hipError_t launch_group_positions(int K, const GroupArgs *args, const GroupDims &d, hipStream_t stream, int build) {
     const dim3 grid((d.max_M + 255) / 256, 1, d.G), block(256);
     switch (K) {
     case 3:
@@ -1273,7 +1294,16 @@ hipError_t launch_group_positions(int K, const GroupArgs *args, const GroupDims 
     default:
         return hipErrorInvalidValue;
     }
-    if (orbit_small_build(d.max_M, d.min_n, K))
+    if (orbit_take_small(build, d.max_M, d.min_n, K))
+        k_sample_orbit_g<true><<<dim3(1, 1, d.G), dim3(1024), 0, stream>>>(args, K);
+    else
+        k_sample_orbit_g<false><<<dim3(1, 1, d.G), dim3(1024), 0, stream>>>(args, K);
+    return hipGetLastError();
+}
+hipError_t launch_group_orbit(int K, const GroupArgs *args, const GroupDims &d, hipStream_t stream, int build) { // the orbit walk alone
+    if (K != 3 && K != 4 && K != 5 && K != 7)
+        return hipErrorInvalidValue;
+    if (orbit_take_small(build, d.max_M, d.min_n, K))
         k_sample_orbit_g<true><<<dim3(1, 1, d.G), dim3(1024), 0, stream>>>(args, K);
     else
         k_sample_orbit_g<false><<<dim3(1, 1, d.G), dim3(1024), 0, stream>>>(args, K);

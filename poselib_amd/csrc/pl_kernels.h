@@ -365,7 +365,17 @@ struct RecordsArgs {
 // The single-problem forms of the three launches (the other kernels of a batch step: launch_generate, launch_score,
 // launch_score_seq).  counted: blk_tot already holds the per-block model counts (GenerateArgs.blk_tot), otherwise they are
 // counted first; pts: the problem's correspondences (read where s16.points16 is set)
-hipError_t launch_sample_positions(int K, const SampleArgs &a, hipStream_t stream);
+// build (host side, diagnostics): 0 = the orbit kernel's build as orbit_small_build picks it, 1 = the small build, 2 = the large one
+hipError_t launch_sample_positions(int K, const SampleArgs &a, hipStream_t stream, int build = 0);
+// ... and the orbit walk alone, over a delta table and a bitmap that are in place (pl_debug_sample_positions plants them)
+hipError_t launch_sample_orbit(int K, const SampleArgs &a, hipStream_t stream, int build = 0);
+// The orbit kernel's two builds: which one a window of M positions over N correspondences takes, and what each holds - flagged
+// positions, the most of them pointer doubling follows (more: the one-lane walk), segments - and the positions of a phase-1 tile.
+bool orbit_small_build(uint32_t M, uint64_t N, int K);
+struct OrbitShape {
+    uint32_t flags, doubling, segments, tile;
+};
+OrbitShape orbit_build_shape(bool small);
 hipError_t launch_compact2(const CompactArgs &a, bool counted, const PointSet &pts, hipStream_t stream);
 hipError_t launch_finalize_records(const RecordsArgs &a, hipStream_t stream);
 struct MaskArgs {
@@ -434,7 +444,8 @@ struct PrepareGroupArgs {
 };
 hipError_t launch_group_prepare(const PrepareGroupArgs *args, uint32_t G, uint32_t max_n, hipStream_t stream);
 // (pieces of launch_group_batch that live in pipeline.hip)
-hipError_t launch_group_positions(int K, const GroupArgs *args, const GroupDims &d, hipStream_t stream);
+hipError_t launch_group_positions(int K, const GroupArgs *args, const GroupDims &d, hipStream_t stream, int build = 0); // (build: launch_sample_positions)
+hipError_t launch_group_orbit(int K, const GroupArgs *args, const GroupDims &d, hipStream_t stream, int build = 0);     // the orbit walk alone
 hipError_t launch_group_compact(const GroupArgs *args, const GroupDims &d, hipStream_t stream);
 hipError_t launch_group_finalize_records(const GroupArgs *args, const GroupDims &d, hipStream_t stream);
 // LM over the tasks of many problems: every task carries its own correspondences (LMTask.pts)

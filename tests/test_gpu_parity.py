@@ -523,7 +523,7 @@ def test_point_counts_around_the_chunk_boundaries(gpu, n):
 @pytest.mark.parametrize("n", [8, 11, 24, 60, 200])
 def test_sampler_with_frequent_redraws(gpu, n):
     """Few correspondences: most iterations redraw a duplicate index (sampling.cc:46-61), so the device sampler's
-    orbit has a flag at almost every position (bitmap -> successor links -> segments; beyond 12288 flags or 4096
+    orbit has a flag at almost every position (bitmap -> successor links -> segments; beyond 8192 flags or 4096
     segments per batch it must fall back to the host walk) - long fixed-length runs must still follow the
     reference's draw stream exactly.  With so few correspondences the same sample recurs in permuted order and its
     models tie to the last bits of the MSAC score: `refinements` only agrees because every score
