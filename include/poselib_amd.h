@@ -195,9 +195,9 @@ typedef struct {
     int32_t cols;        /* 2 or 3: what the entry point expects for that argument */
 } pl_device_points;
 /* The host forms above with device-resident points; everything else as there.  pl_estimate_absolute_pose_dev with
- * estimate_focal_length: PL_ERR_UNSUPPORTED (that estimator reads the points on the host).  Not served from device memory:
- * pl_estimate_batch, the focal-length estimators, pl_estimate_1D_radial_absolute_pose, the pl_ransac_* one-shot entries,
- * pl_undistort_points. */
+ * estimate_focal_length: PL_ERR_UNSUPPORTED (that estimator reads the points on the host).  The batched form is
+ * pl_estimate_batch_dev (below, behind pl_estimate_batch).  Not served from device memory: the focal-length estimators,
+ * pl_estimate_1D_radial_absolute_pose, the pl_ransac_* one-shot entries, pl_undistort_points. */
 int pl_estimate_absolute_pose_dev(const pl_device_points *points2D, const pl_device_points *points3D, size_t n,
                                   const pl_robust_options *opt, pl_camera *camera, pl_camera_pose *pose, uint8_t *inliers,
                                   pl_ransac_stats *stats);
@@ -262,7 +262,47 @@ int pl_estimate_batch(pl_batch_item *items, size_t count, int max_in_flight);
  * whatever the list.  The process-per-GPU form (one rank per device, RCCL gather of the result records) is the Python
  * harness's: poselib_amd/sharding.py, bench.py --gpus N; INTEGRATION.md says which to use when. */
 int pl_estimate_batch_devices(pl_batch_item *items, size_t count, const int *devices, int num_devices, int max_in_flight);
-/* What the calling thread's last pl_estimate_batch / pl_estimate_batch_devices / pl_ransac_batch did with its items.  Items in
+/* pl_estimate_batch for correspondences that are already in DEVICE memory - the padded (pairs, N, 4) tensor of a GPU matcher, one
+ * view per item.  The record is pl_batch_item with the two host pointers replaced by pl_device_points descriptors (by value);
+ * every other field is unchanged, and model, inliers, stats, status, the options and the cameras stay in host memory.  The call
+ * runs on the device the calling thread selected and keeps the contract of the single _dev calls: the data is complete when the
+ * call is made and read only during it, fp32 widens exactly, and every item is bit-identical - model, mask, stats - to
+ * pl_estimate_batch on the same values as doubles.  Several calls may be in flight from different host threads;
+ * pl_last_batch_report reports the call like any other.
+ *   - Every descriptor is checked before anything is launched (the checks of the single _dev calls; an allocation's kind, device
+ *     and extent are asked of the runtime once per allocation and call, not per item).  A bad item gets status PL_ERR_INVALID
+ *     and a message that names its index and the cause; the other items run; the call returns the first failing item's status.
+ *     The checks that need no device come first: PL_ERR_INVALID before PL_ERR_NO_DEVICE.
+ *   - Kinds 0 - 3 advance in lock-step groups under exactly pl_estimate_batch's conditions (PROSAC, warm starts and distorting
+ *     cameras included).  The points of a group reach its kernels without passing through the host: one launch copies strided /
+ *     fp32 members into the group's block (contiguous fp64 members are read where they lie), one launch makes the host
+ *     front-ends' passes over the points of all members.  What a group does not take (too few or too many correspondences,
+ *     min_iterations > 4096, tangent_sampson, items a group hands back) runs through the matching pl_estimate_*_dev and is
+ *     counted solo / fallback.
+ *   - Kind 4, kind 5 and kind 0 with estimate_focal_length: item status PL_ERR_UNSUPPORTED, as for the single calls; nothing is read.
+ *   - Not offered: a form over several devices (the memory belongs to one), host and device items mixed in one call, inlier
+ *     masks in device memory, a producer stream or event (synchronise the producer first).
+ * Adding this record and entry point changes no existing record: PL_ABI_VERSION stays 5 (new symbols do not bump it). */
+typedef struct {
+    int32_t kind;            /* 0 absolute pose, 1 relative pose, 2 fundamental, 3 homography */
+    int32_t status;          /* out: PL_OK or the error of this item */
+    pl_device_points a;      /* points2D (kind 0) / points2D_1: N x 2 */
+    pl_device_points b;      /* points3D: N x 3 (kind 0) / points2D_2: N x 2 */
+    size_t n;
+    const pl_robust_options *opt;
+    pl_camera *camera1;      /* as pl_batch_item */
+    const pl_camera *camera2;
+    void *model;             /* in/out, host memory: pl_camera_pose (kinds 0, 1) or double[9] column-major (kinds 2, 3) */
+    uint8_t *inliers;        /* n bytes, host memory */
+    pl_ransac_stats *stats;
+} pl_batch_item_dev;
+int pl_estimate_batch_dev(pl_batch_item_dev *items, size_t count, int max_in_flight);
+/* Diagnostic: pl_debug_point_stats_dev for `count` pairs of N x 2 sets at once, through the grouped kernels a group of
+ * pl_estimate_batch_dev uses (one ingest launch, one statistics launch per pass, one synchronisation per pass).  x1, x2, n: count
+ * entries each; out: count x 8 doubles, member after member, laid out as pl_debug_point_stats_dev's (zeros for n == 0). */
+int pl_debug_point_stats_group_dev(const pl_device_points *x1, const pl_device_points *x2, const size_t *n, size_t count, int centroid,
+                                   double *out);
+/* What the calling thread's last pl_estimate_batch / pl_estimate_batch_devices / pl_estimate_batch_dev / pl_ransac_batch did with its items.  Items in
  * lock-step groups share one launch sequence (the advertised rate); `solo` items were outside the group path from the start
  * (options or sizes a group does not take - see pl_batch_item / pl_ransac_batch) and `fallback` items were handed back by their
  * group: both kinds ran through the single-problem entry points, correct but at that path's rate - a batch that is mostly solo

@@ -110,6 +110,12 @@ class DevicePoints(C.Structure):  # pl_device_points: rows of `cols` contiguous 
     _fields_ = [("data", C.c_void_p), ("row_stride", C.c_int64), ("dtype", i32), ("cols", i32)]
 
 
+class BatchItemDev(C.Structure):  # pl_batch_item_dev: pl_batch_item with the two host pointers replaced by descriptors (by value)
+    _fields_ = [("kind", i32), ("status", i32), ("a", DevicePoints), ("b", DevicePoints), ("n", C.c_size_t),
+                ("opt", C.POINTER(RobustOptions)), ("camera1", C.POINTER(Camera)), ("camera2", C.POINTER(Camera)),
+                ("model", C.c_void_p), ("inliers", C.c_void_p), ("stats", C.POINTER(RansacStats))]
+
+
 class PoseLibAmdError(RuntimeError):
     pass
 
@@ -181,6 +187,8 @@ def _declare(L):
         "pl_debug_point_stats_dev": (cint, [dpts, dpts, sz, cint, vp]),
         "pl_estimate_batch": (cint, [P(BatchItem), sz, cint]),
         "pl_estimate_batch_devices": (cint, [P(BatchItem), sz, P(C.c_int), cint, cint]),
+        "pl_estimate_batch_dev": (cint, [P(BatchItemDev), sz, cint]),
+        "pl_debug_point_stats_group_dev": (cint, [dpts, dpts, P(sz), sz, cint, vp]),
         "pl_last_batch_report": (None, [P(BatchReport)]),
         "pl_ransac_batch": (cint, [P(RansacItem), sz, cint, cint]),
         "pl_undistort_points": (cint, [cam, vp, sz, vp]),
@@ -260,7 +268,7 @@ EXPORTED_SYMBOLS = [
     "pl_debug_score_shape", "pl_debug_score_stream_ex", "pl_debug_score_pruned", "pl_debug_score_prune_gate",
     "pl_estimate_absolute_pose_dev", "pl_estimate_relative_pose_dev", "pl_estimate_fundamental_dev", "pl_estimate_homography_dev",
     "pl_problem_create_dev", "pl_problem_create_tangent_dev", "pl_debug_check_device_points", "pl_debug_point_stats_dev",
-    "pl_debug_sampler_shape", "pl_debug_sample_positions",
+    "pl_debug_sampler_shape", "pl_debug_sample_positions", "pl_estimate_batch_dev", "pl_debug_point_stats_group_dev",
     # (pl_estimate_1D_radial_absolute_pose and pl_ransac_1D_radial_pnp carry the reference's capital D: declared above, exported by the
     # library, but outside the lower-case pattern tests/test_cabi_surface.py lists the header's symbols with)
 ]

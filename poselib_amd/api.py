@@ -210,11 +210,12 @@ def _on_device(a) -> bool:
     return not isinstance(a, np.ndarray) and hasattr(a, "__cuda_array_interface__")
 
 
-def _device_points(a, dim):
+def _device_points(a, dim, streams=None):
     """(pl_device_points descriptor, rows, the object that owns the memory) of a GPU tensor or __cuda_array_interface__ object.
     float32 / float64 only; a column stride other than 1 is made contiguous on the device (the object's own .contiguous());
     a torch tensor must live on the device this thread selected, and its current stream is synchronised - the library reads the
-    memory on a stream of its own and takes none from the caller."""
+    memory on a stream of its own and takes none from the caller.  streams: a dict that collects {device: (torch, device)}
+    instead - the caller synchronises every device once when all its descriptors are made (_sync_streams; Batch)."""
     if _is_torch_tensor(a):
         if a.dim() != 2 or a.shape[1] != dim:
             raise ValueError(f"expected an (N, {dim}) tensor")
@@ -231,7 +232,10 @@ def _device_points(a, dim):
         if n > 1 and (a.stride(1) != 1 or a.stride(0) < dim):
             a = a.contiguous()
         if torch is not None:
-            torch.cuda.current_stream(a.device).synchronize()
+            if streams is None:
+                torch.cuda.current_stream(a.device).synchronize()
+            else:
+                streams.setdefault(index, (torch, a.device))
         row = int(a.stride(0)) if n > 1 else dim
         return L.DevicePoints(a.data_ptr() if n else None, row, dtype, dim), n, a
     cai = a.__cuda_array_interface__
@@ -256,10 +260,15 @@ def _device_points(a, dim):
         bs = b.__cuda_array_interface__.get("strides")
         if bs is not None and tuple(bs) != (dim * size, size):
             raise ValueError(".contiguous() of the device array did not return a contiguous array")
-        return _device_points(b, dim)
+        return _device_points(b, dim, streams)
     if n <= 1:
         row = dim
     return L.DevicePoints(int(cai["data"][0]) if n else None, int(row), dtype, dim), n, a
+
+
+def _sync_streams(streams):
+    for torch, device in streams.values():
+        torch.cuda.current_stream(device).synchronize()
 
 
 class _Points:
@@ -352,15 +361,42 @@ def _estimate_matrix(fn, kind, points2D_1, points2D_2, opt, initial):
     return M.reshape(3, 3).T.copy(), _info(st, inl[:n])
 
 
+class _DevicePts:
+    """One device point set of a Batch problem: its descriptor, its rows (.shape like an array) and the object that owns the memory"""
+
+    def __init__(self, a, dim, streams):
+        self.desc, n, self.owner = _device_points(a, dim, streams)
+        self.shape = (n, dim)
+
+
 class Batch:
     """An array of pl_batch_item descriptors (include/poselib_amd.h) marshalled once: `run()` is the C-ABI call
     pl_estimate_batch and nothing else (what bench_batch.py times), `results()` turns the outputs into the objects the
-    single-problem functions return."""
+    single-problem functions return.
+
+    The point sets of a problem may be GPU tensors or __cuda_array_interface__ objects instead of arrays (the views of a matcher's
+    padded (pairs, N, 4) tensor): the items then are pl_batch_item_dev records and `run()` is pl_estimate_batch_dev - nothing is
+    copied to the host.  A call is all-device or all-host; "shared_focal" and "radial1d" problems and `devices=` are host-only."""
 
     def __init__(self, problems):
         kinds = {"abs": KIND_ABS, "rel": KIND_REL, "fund": KIND_FUND, "hom": KIND_HOM, "shared_focal": KIND_SHARED_FOCAL,
                  "radial1d": KIND_RAD1D}
-        self.items = (L.BatchItem * len(problems))()
+        where = {_on_device(pr[1]) or _on_device(pr[2]) for pr in problems}
+        if len(where) > 1:
+            raise ValueError("host and device problems are mixed in one batch: a call is all-device or all-host")
+        self.on_device = True in where
+        if self.on_device:
+            for pr in problems:
+                if pr[0] in ("shared_focal", "radial1d"):
+                    raise ValueError(f"a {pr[0]!r} problem is not served from device memory: pass host arrays")
+                if _on_device(pr[1]) != _on_device(pr[2]):
+                    raise ValueError("one point set is on the GPU and the other in host memory: pass both the same way")
+        streams = {}
+
+        # (device points: the descriptor, the rows and the owner travel as one object)
+        pts = (lambda a, dim: _DevicePts(a, dim, streams)) if self.on_device else _pts
+
+        self.items = ((L.BatchItemDev if self.on_device else L.BatchItem) * len(problems))()
         self.keep = []
         for it, pr in zip(self.items, problems):
             kind = kinds[pr[0]]
@@ -372,37 +408,42 @@ class Batch:
             pr = tuple(pr[:-1]) + (opt,)
             if kind == KIND_ABS:
                 _, a, b, cam, opt = pr
-                a, b = _pts(a, 2), _pts(b, 3)
+                a, b = pts(a, 2), pts(b, 3)
                 cam = _as_camera(cam)
                 c1, c2 = cam._c(), None
                 model = _cpose(init if init is not None else CameraPose())
             elif kind == KIND_REL:
                 _, a, b, cam1, cam2, opt = pr
-                a, b = _pts(a, 2), _pts(b, 2)
+                a, b = pts(a, 2), pts(b, 2)
                 cam = None
                 c1, c2 = _as_camera(cam1)._c(), _as_camera(cam2)._c()
                 model = _cpose(init if init is not None else CameraPose())
             elif kind == KIND_RAD1D:  # ("radial1d", centred pixels, points3D, opt)
                 _, a, b, opt = pr
-                a, b = _pts(a, 2), _pts(b, 3)
+                a, b = pts(a, 2), pts(b, 3)
                 cam, c1, c2 = None, None, None
                 model = _cpose(init if init is not None else CameraPose())
             elif kind == KIND_SHARED_FOCAL:
                 _, a, b, pp, opt = pr
-                a, b = _pts(a, 2), _pts(b, 2)
+                a, b = pts(a, 2), pts(b, 2)
                 cam = Camera("SIMPLE_PINHOLE", [1.0, float(pp[0]), float(pp[1])])
                 c1, c2 = cam._c(), None
                 model = _cpose(CameraPose())
             else:
                 _, a, b, opt = pr
-                a, b = _pts(a, 2), _pts(b, 2)
+                a, b = pts(a, 2), pts(b, 2)
                 cam, c1, c2 = None, None, None
                 model = np.ascontiguousarray((np.eye(3) if init is None else np.asarray(init, dtype=np.float64)).T.reshape(9))
             o = _robust_options(opt, KIND_REL if kind == KIND_SHARED_FOCAL else kind, init is not None and kind != KIND_SHARED_FOCAL)
             n = a.shape[0]
+            if b.shape[0] != n and self.on_device:
+                raise ValueError(f"the point sets differ in length ({n} and {b.shape[0]})")
             inl = np.zeros(max(n, 1), dtype=np.uint8)
             st = L.RansacStats()
-            it.a, it.b, it.n = _ptr(a), _ptr(b), n
+            if self.on_device:
+                it.a, it.b, it.n = a.desc, b.desc, n
+            else:
+                it.a, it.b, it.n = _ptr(a), _ptr(b), n
             it.opt = C.pointer(o)
             it.camera1 = C.pointer(c1) if c1 is not None else None
             it.camera2 = C.pointer(c2) if c2 is not None else None
@@ -410,10 +451,16 @@ class Batch:
             it.inliers = _ptr(inl)
             it.stats = C.pointer(st)
             self.keep.append((kind, a, b, o, cam, c1, c2, model, inl, st, n))
+        _sync_streams(streams)  # (once per device, not per tensor: the producers' work is complete before run())
 
     def run(self, max_in_flight=8, devices=None):
         """devices: None = the calling thread's device (pl_estimate_batch); a list of device indices, or "all", = the items
         round-robined over those devices from this one process (pl_estimate_batch_devices)"""
+        if self.on_device:
+            if devices is not None:
+                raise ValueError("devices= with device points: the memory belongs to one device (set_device selects it)")
+            L.check(L.lib().pl_estimate_batch_dev(self.items, C.c_size_t(len(self.keep)), C.c_int(int(max_in_flight))))
+            return
         if devices is None:
             L.check(L.lib().pl_estimate_batch(self.items, C.c_size_t(len(self.keep)), C.c_int(int(max_in_flight))))
             return
@@ -464,7 +511,10 @@ def estimate_batch(problems, max_in_flight=8, devices=None):
     Returns the list of results in the same order.  Problems of the same kind advance in groups through ONE launch
     sequence (the problem index is a grid dimension of every kernel); `max_in_flight` host threads inside the library
     work on groups concurrently, each with its own HIP stream.  devices: a list of device indices (or "all") spreads the problems
-    over several GPUs from this one process (problem i on devices[i mod len]); None: the calling thread's device."""
+    over several GPUs from this one process (problem i on devices[i mod len]); None: the calling thread's device.
+    The point sets may be GPU tensors / __cuda_array_interface__ objects - for all problems of the call or for none (see Batch)."""
+    if devices is not None and any(_on_device(pr[1]) or _on_device(pr[2]) for pr in problems):
+        raise ValueError("devices= with device points: the memory belongs to one device (set_device selects it)")
     b = Batch(problems)
     b.run(max_in_flight, devices)
     return b.results()
@@ -1147,6 +1197,22 @@ def point_stats_dev(x1, x2, centroid=True):
     L.check(L.lib().pl_debug_point_stats_dev(pts.a, pts.b, C.c_size_t(pts.n), int(bool(centroid)), _ptr(out)))
     return {"c1": out[0:2].copy(), "c2": out[2:4].copy(), "scale": float(out[4]), "absmax_normalised": float(out[5]),
             "absmax_first": float(out[6])}
+
+
+def point_stats_group_dev(pairs, centroid=True):
+    """Diagnostic (pl_debug_point_stats_group_dev): point_stats_dev for a list of (x1, x2) pairs of device point sets at once,
+    through the grouped kernels of pl_estimate_batch_dev - one list entry per pair."""
+    keep = [_Points(x1, x2, 2, 2) for x1, x2 in pairs]
+    if not all(p.on_device for p in keep):
+        raise ValueError("point_stats_group_dev takes device points")
+    cnt = len(keep)
+    d1 = (L.DevicePoints * max(cnt, 1))(*[p.keep[0] for p in keep])
+    d2 = (L.DevicePoints * max(cnt, 1))(*[p.keep[1] for p in keep])
+    ns = (C.c_size_t * max(cnt, 1))(*[p.n for p in keep])
+    out = np.zeros((max(cnt, 1), 8))
+    L.check(L.lib().pl_debug_point_stats_group_dev(d1, d2, ns, C.c_size_t(cnt), int(bool(centroid)), _ptr(out)))
+    return [{"c1": o[0:2].copy(), "c2": o[2:4].copy(), "scale": float(o[4]), "absmax_normalised": float(o[5]),
+             "absmax_first": float(o[6])} for o in out[:cnt]]
 
 
 def set_lm_mode(mode) -> int:

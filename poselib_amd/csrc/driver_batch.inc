@@ -4,6 +4,7 @@
 //   pl_ransac_batch                device-resident problems in lock-step groups, every item on the device that holds its problem
 //   pl_estimate_batch              host-resident problems (the estimate_* front-ends) in lock-step groups
 //   pl_estimate_batch_devices      ... spread over several devices from one process
+//   pl_estimate_batch_dev          ... with the correspondences in the caller's device memory (pl_device_points per item)
 //   pl_last_batch_report           where the items of the last call went
 // ---------------------------------------------------------------------------- batched front-end
 // A persistent pool of host threads (each owns a Context: HIP stream + scratch arena, created on first use and kept
@@ -145,6 +146,31 @@ int run_item(pl_batch_item &it) {
     }
 }
 
+// ... of pl_estimate_batch_dev: the matching pl_estimate_*_dev (kinds 0 - 3; the others are answered before anything runs)
+int run_item_dev(const pl_batch_item_dev &it) {
+    switch (it.kind) {
+    case EST_ABS:
+        return pl_estimate_absolute_pose_dev(&it.a, &it.b, it.n, it.opt, it.camera1, static_cast<pl_camera_pose *>(it.model), it.inliers,
+                                             it.stats);
+    case EST_REL:
+        return pl_estimate_relative_pose_dev(&it.a, &it.b, it.n, it.camera1, it.camera2, it.opt, static_cast<pl_camera_pose *>(it.model),
+                                             it.inliers, it.stats);
+    case EST_FUND:
+        return pl_estimate_fundamental_dev(&it.a, &it.b, it.n, it.opt, static_cast<double *>(it.model), it.inliers, it.stats);
+    case EST_HOM:
+        return pl_estimate_homography_dev(&it.a, &it.b, it.n, it.opt, static_cast<double *>(it.model), it.inliers, it.stats);
+    default:
+        return fail(PL_ERR_UNSUPPORTED, "pl_batch_item_dev.kind: only kinds 0..3 are served from device memory");
+    }
+}
+int run_group_member_alone(GroupItem &g) { return g.ditem ? run_item_dev(*g.ditem) : run_item(*g.item); }
+// what pl_estimate_batch_dev hands to estimate_batch_on next to the host-side copies of its items (a == b == null)
+struct DeviceBatch {
+    const pl_batch_item_dev *items;
+    std::vector<int> decided;       // per item: PL_OK, or the status it got before anything ran (unsupported kind, rejected descriptor)
+    std::vector<std::string> cause; // ... and why
+};
+
 // one group of same-kind problems through the group launches; whatever it could not finish goes through the
 // single-problem entry points
 // POSELIB_AMD_GROUP_STEPS: batch steps a group of pl_estimate_batch runs before its unfinished problems are regrouped (0: never)
@@ -162,7 +188,7 @@ void run_group_job(std::vector<GroupItem *> &items, bool resume) {
         if (!resume)
             for (GroupItem *g : items)
                 if (!g->prepared)
-                    group_prepare_item(*g);
+                    g->ditem ? group_prepare_device_item(*g) : group_prepare_item(*g);
         t1 = now_s();
         rc = run_group(c, items.data(), (uint32_t)items.size(), false, resume ? 0u : group_step_budget(), resume);
     }
@@ -175,7 +201,7 @@ void run_group_job(std::vector<GroupItem *> &items, bool resume) {
         if (rc != PL_OK || g->fallback) {
             delete g->run;
             g->run = nullptr;
-            g->item->status = run_item(*g->item);
+            g->item->status = run_group_member_alone(*g);
             ++g_n_fallback;
             note_fallback_item();
             if (g->item->status != PL_OK)
@@ -388,8 +414,9 @@ int pl_ransac_batch(pl_ransac_item *items, size_t count, int max_in_flight, int 
     return rc;
 }
 
-// pl_estimate_batch on one device
-static int estimate_batch_on(int device, pl_batch_item *items, size_t count, int max_in_flight) {
+// pl_estimate_batch on one device (dev: the call is pl_estimate_batch_dev, `items` are the host-side copies of its items)
+static int estimate_batch_on(int device, pl_batch_item *items, size_t count, int max_in_flight, const DeviceBatch *dev = nullptr) {
+    const char *entry = dev ? "pl_estimate_batch_dev" : "pl_estimate_batch";
     int rc = device_usable(device); // fails loudly without a HIP device
     if (rc != PL_OK)
         return rc;
@@ -399,11 +426,16 @@ static int estimate_batch_on(int device, pl_batch_item *items, size_t count, int
     std::vector<size_t> by_kind[4], by_focal[2], solo;
     std::vector<std::function<void()>> jobs;
     for (size_t i = 0; i < count; ++i) {
+        if (dev && dev->decided[i] != PL_OK) { // (answered before the call got here: nothing runs for it)
+            items[i].status = dev->decided[i];
+            solo.push_back(i);
+            continue;
+        }
         items[i].status = PL_OK;
         int est;
-        if (!no_groups && group_eligible(items[i]))
+        if (!no_groups && group_eligible(items[i], dev != nullptr))
             by_kind[items[i].kind].push_back(i);
-        else if (!no_groups && (est = focal_group_estimator(items[i])) >= 0)
+        else if (!no_groups && !dev && (est = focal_group_estimator(items[i])) >= 0)
             by_focal[est].push_back(i); // the two focal-length estimators: their own lock-step groups (driver_focal_group.inc)
         else
             solo.push_back(i);
@@ -434,12 +466,15 @@ static int estimate_batch_on(int device, pl_batch_item *items, size_t count, int
         for (size_t j = lo; j < hi; ++j) {
             GroupItem g;
             g.item = &items[v[j]];
+            g.ditem = dev ? &dev->items[v[j]] : nullptr;
             g.kind = k;
             groups.back().push_back(g);
         }
     };
     std::vector<size_t> rest_lo(4, 0), rest_hi(4, 0);
-    const bool first_round = !group_env && eligible >= 4 * workers * first_sz;
+    // (a call whose points are on the device has no such copy: its groups start with two small launches, and the first round would
+    // only cut the small problems into more launch sequences - profiles/batch_device_points.md)
+    const bool first_round = !group_env && !dev && eligible >= 4 * workers * first_sz;
     for (int k = 0; k < 4; ++k) {
         std::vector<size_t> &v = by_kind[k];
         std::stable_sort(v.begin(), v.end(), [&](size_t a, size_t b) { return items[a].n > items[b].n; });
@@ -481,7 +516,10 @@ static int estimate_batch_on(int device, pl_batch_item *items, size_t count, int
     for (size_t gi : order) {
         std::vector<GroupItem *> *grp = &group_ptrs[gi];
         jobs.emplace_back([grp] { run_group_job(*grp, false); });
-        stage_fns.emplace_back([grp] { group_stage_in(grp->data(), (uint32_t)grp->size()); });
+        if (dev)
+            stage_fns.emplace_back(); // (nothing to copy: the group's stage A starts on the device)
+        else
+            stage_fns.emplace_back([grp] { group_stage_in(grp->data(), (uint32_t)grp->size()); });
     }
     // the focal-length estimators: groups of up to kFocalGroupMax / kSFocalGroupMax problems of similar size, at least one group per worker
     std::vector<std::vector<FocalGroupItem>> focal_groups;
@@ -521,8 +559,10 @@ static int estimate_batch_on(int device, pl_batch_item *items, size_t count, int
         stage_fns.emplace_back(); // (nothing to stage)
     }
     for (size_t i : solo) {
-        jobs.emplace_back([items, i] {
-            items[i].status = run_item(items[i]);
+        jobs.emplace_back([items, i, dev] {
+            if (dev && dev->decided[i] != PL_OK)
+                return;
+            items[i].status = dev ? run_item_dev(dev->items[i]) : run_item(items[i]);
             if (items[i].status != PL_OK)
                 note_worker_error();
         });
@@ -569,9 +609,9 @@ static int estimate_batch_on(int device, pl_batch_item *items, size_t count, int
             }
     }
     if (g_group_timing)
-        std::fprintf(stderr, "poselib_amd: pl_estimate_batch %zu items, %zu groups + %zu solo, %d workers: wall %.1f ms; workers' time: prepare %.1f, "
+        std::fprintf(stderr, "poselib_amd: %s %zu items, %zu groups + %zu solo, %d workers: wall %.1f ms; workers' time: prepare %.1f, "
                              "groups %.1f (of which waiting for the device %.1f in %llu waits), fallback items %.1f ms (%llu items)\n",
-                     count, groups.size(), solo.size(), w, (now_s() - t_pool) * 1e3, g_t_prep_ns.load() * 1e-6, g_t_group_ns.load() * 1e-6,
+                     entry, count, groups.size(), solo.size(), w, (now_s() - t_pool) * 1e3, g_t_prep_ns.load() * 1e-6, g_t_group_ns.load() * 1e-6,
                      g_t_wait_ns.load() * 1e-6, (unsigned long long)g_n_waits.load(), g_t_fallback_ns.load() * 1e-6,
                      (unsigned long long)g_n_fallback.load());
     if (g_group_timing)
@@ -581,8 +621,11 @@ static int estimate_batch_on(int device, pl_batch_item *items, size_t count, int
     const std::string werr = lease.pool->err.take();
     g_last_report = pl_batch_report{count, eligible, by_focal[0].size() + by_focal[1].size(), solo.size(), lease.pool->err.fallbacks.load()};
     for (size_t i = 0; i < count; ++i)
-        if (items[i].status != PL_OK)
-            return fail(items[i].status, ("pl_estimate_batch: item " + std::to_string(i) + " failed" + (werr.empty() ? "" : ": " + werr)).c_str());
+        if (items[i].status != PL_OK) {
+            if (dev && dev->decided[i] != PL_OK)
+                return fail(items[i].status, (std::string(entry) + ": item " + std::to_string(i) + ": " + dev->cause[i]).c_str());
+            return fail(items[i].status, (std::string(entry) + ": item " + std::to_string(i) + " failed" + (werr.empty() ? "" : ": " + werr)).c_str());
+        }
     return PL_OK;
 }
 
@@ -643,3 +686,83 @@ int pl_estimate_batch_devices(pl_batch_item *items, size_t count, const int *dev
     return rc;
 }
 
+
+// pl_estimate_batch with the correspondences in the caller's device memory.  Everything that can be said about an item without
+// running it is said first - the kind, then the descriptors' plain checks (no device needed), then what the runtime knows about
+// the memory (once per allocation) - and such an item is out of the call; the others go through estimate_batch_on as host-side
+// copies of their records (a == b == null) next to the caller's descriptors.
+int pl_estimate_batch_dev(pl_batch_item_dev *items, size_t count, int max_in_flight) {
+    if (count == 0)
+        return PL_OK;
+    if (!items)
+        return fail(PL_ERR_INVALID, "items pointer is null");
+    DeviceBatch dev;
+    dev.items = items;
+    dev.decided.assign(count, PL_OK);
+    dev.cause.resize(count);
+    auto decide = [&](size_t i, int rc) { // (rc came from fail(): g_err holds the cause)
+        dev.decided[i] = items[i].status = rc;
+        dev.cause[i] = g_err;
+    };
+    auto first_decided = [&]() -> int {
+        for (size_t i = 0; i < count; ++i)
+            if (dev.decided[i] != PL_OK)
+                return fail(dev.decided[i], ("pl_estimate_batch_dev: item " + std::to_string(i) + ": " + dev.cause[i]).c_str());
+        return PL_OK;
+    };
+    for (size_t i = 0; i < count; ++i) {
+        pl_batch_item_dev &it = items[i];
+        it.status = PL_OK;
+        if (it.kind < 0 || it.kind > 5) {
+            decide(i, fail(PL_ERR_INVALID, "pl_batch_item_dev.kind must be 0..3"));
+            continue;
+        }
+        if (it.kind == 4 || it.kind == EST_RAD1D) {
+            decide(i, fail(PL_ERR_UNSUPPORTED, it.kind == 4 ? "shared-focal relative pose (kind 4) is not served from device memory: use pl_estimate_batch"
+                                                            : "1D-radial absolute pose (kind 5) is not served from device memory: use pl_estimate_batch"));
+            continue;
+        }
+        if (it.kind == EST_ABS && it.opt && it.opt->estimate_focal_length) {
+            decide(i, fail(PL_ERR_UNSUPPORTED, "estimate_focal_length is not served from device memory: use pl_estimate_batch"));
+            continue;
+        }
+        int rc = check_points_plain(&it.a, it.n, 2);
+        if (rc == PL_OK)
+            rc = check_points_plain(&it.b, it.n, it.kind == EST_ABS ? 3 : 2);
+        if (rc != PL_OK)
+            decide(i, rc);
+    }
+    Context *c;
+    int rc = get_context(&c); // (the calling thread's device, as for every single-problem entry point)
+    if (rc != PL_OK) { // no device: what was decided without one comes first
+        const std::string why = g_err;
+        for (size_t i = 0; i < count; ++i)
+            if (dev.decided[i] == PL_OK)
+                items[i].status = rc;
+        const int first = first_decided();
+        return first != PL_OK ? first : fail(rc, why.c_str());
+    }
+    DeviceAllocationCache allocations;
+    for (size_t i = 0; i < count; ++i) {
+        if (dev.decided[i] != PL_OK)
+            continue;
+        rc = allocations.check(c, &items[i].a, items[i].n);
+        if (rc == PL_OK)
+            rc = allocations.check(c, &items[i].b, items[i].n);
+        if (rc != PL_OK)
+            decide(i, rc);
+    }
+    std::vector<pl_batch_item> host(count);
+    for (size_t i = 0; i < count; ++i) {
+        const pl_batch_item_dev &it = items[i];
+        pl_batch_item &h = host[i];
+        h.kind = it.kind, h.status = it.status;
+        h.a = h.b = nullptr;
+        h.n = it.n, h.opt = it.opt, h.camera1 = it.camera1, h.camera2 = it.camera2;
+        h.model = it.model, h.inliers = it.inliers, h.stats = it.stats;
+    }
+    rc = estimate_batch_on(c->device, host.data(), count, max_in_flight, &dev);
+    for (size_t i = 0; i < count; ++i)
+        items[i].status = host[i].status;
+    return rc;
+}

@@ -7,6 +7,8 @@
 //   k_point_stats   the numbers the host front-ends compute in passes over the caller's arrays - the two order-dependent
 //                   reductions of the homography / fundamental normalisation and the pre-filters' bound - one small record back
 //   k_ingest_soa    a resident problem's block, written on the device
+//   k_ingest_g, k_point_stats_g   the first two for all members of a lock-step group at once (pl_estimate_batch_dev:
+//                   group_stage_device below, called by run_group; the entry point itself is in driver_batch.inc)
 // From there both kinds of call run the same code (absolute_pose_run, two_view_run), so a _dev call returns the host call's bits.
 // Every check of the descriptors happens before the first launch: a caller's mistake is an error code, never a kernel reading a
 // host address.
@@ -35,12 +37,15 @@ int check_points_plain(const pl_device_points *d, size_t n, int cols) {
     return PL_OK;
 }
 // ... and what the runtime knows about the address: device memory of the calling thread's device that holds every row (n > 0)
-int check_points_device(const Context *c, const pl_device_points *d, size_t n) {
-    if (n == 0)
-        return PL_OK;
+// the allocation behind an address: device memory of the calling thread's device, and its extent
+struct DeviceAllocation {
+    uintptr_t lo = 0;
+    size_t size = 0;
+};
+int find_device_allocation(const Context *c, const void *data, DeviceAllocation *out) {
     hipPointerAttribute_t attr;
     std::memset(&attr, 0, sizeof(attr));
-    const hipError_t e = hipPointerGetAttributes(&attr, d->data);
+    const hipError_t e = hipPointerGetAttributes(&attr, data);
     if (e != hipSuccess) {
         (void)hipGetLastError();
         return fail(PL_ERR_INVALID, "device points: data is not an address the HIP runtime knows (a host pointer?)");
@@ -53,17 +58,55 @@ int check_points_device(const Context *c, const pl_device_points *d, size_t n) {
         return fail(PL_ERR_INVALID, "device points: data lives on another device than the calling thread's (pl_set_device)");
     hipDeviceptr_t base = nullptr;
     size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, const_cast<void *>(d->data)) != hipSuccess) {
+    if (hipMemGetAddressRange(&base, &size, const_cast<void *>(data)) != hipSuccess) {
         (void)hipGetLastError();
         return fail(PL_ERR_INVALID, "device points: the allocation behind data cannot be found");
     }
+    out->lo = reinterpret_cast<uintptr_t>(base);
+    out->size = size;
+    return PL_OK;
+}
+// ... holds every row
+int check_points_extent(const DeviceAllocation &al, const pl_device_points *d, size_t n) {
     const size_t elt = d->dtype == PL_F32 ? sizeof(float) : sizeof(double);
     const size_t need = ((n - 1) * (size_t)d->row_stride + (size_t)d->cols) * elt;
-    const uintptr_t lo = reinterpret_cast<uintptr_t>(base), at = reinterpret_cast<uintptr_t>(d->data);
-    if (at < lo || at - lo > size || need > size - (at - lo))
+    const uintptr_t at = reinterpret_cast<uintptr_t>(d->data);
+    if (at < al.lo || at - al.lo > al.size || need > al.size - (at - al.lo))
         return fail(PL_ERR_INVALID, "device points: the rows reach beyond the allocation behind data");
     return PL_OK;
 }
+int check_points_device(const Context *c, const pl_device_points *d, size_t n) {
+    if (n == 0)
+        return PL_OK;
+    DeviceAllocation al;
+    const int rc = find_device_allocation(c, d->data, &al);
+    return rc != PL_OK ? rc : check_points_extent(al, d, n);
+}
+// The same check for the many descriptors of one batch call, which commonly are views into a few allocations: the runtime is asked
+// once per allocation, every further address inside a known one only has its extent compared.
+struct DeviceAllocationCache {
+    std::vector<DeviceAllocation> known;
+    size_t last = 0;
+    int check(const Context *c, const pl_device_points *d, size_t n) {
+        if (n == 0)
+            return PL_OK;
+        const uintptr_t at = reinterpret_cast<uintptr_t>(d->data);
+        for (size_t k = 0; k < known.size(); ++k) {
+            const DeviceAllocation &al = known[(last + k) % known.size()];
+            if (at >= al.lo && at - al.lo < al.size) {
+                last = (last + k) % known.size();
+                return check_points_extent(al, d, n);
+            }
+        }
+        DeviceAllocation al;
+        const int rc = find_device_allocation(c, d->data, &al);
+        if (rc != PL_OK)
+            return rc;
+        known.push_back(al);
+        last = known.size() - 1;
+        return check_points_extent(al, d, n);
+    }
+};
 
 IngestSrc ingest_src(const pl_device_points *d) {
     IngestSrc s;
@@ -122,9 +165,12 @@ bool linear_camera_terms(const CameraParams &cam, double &cx, double &cy, double
 }
 
 // k_point_stats on the ingested blocks, and its record
-int run_point_stats(Context *c, size_t n, PointStatsArgs args, PointStatsRecord *rec) {
+void point_stats_sizes(PointStatsArgs &args, size_t n) {
     args.n_as_double = static_cast<double>(n);
     args.scale_divisor = std::sqrt(2) * n;
+}
+int run_point_stats(Context *c, size_t n, PointStatsArgs args, PointStatsRecord *rec) {
+    point_stats_sizes(args, n);
     HIP_TRY(c->h_pstats.ensure(sizeof(PointStatsRecord)));
     HIP_TRY(launch_point_stats(c->raw_src_a, c->raw_src_b, (uint32_t)n, args, c->h_pstats.dev<PointStatsRecord>(), c->stream));
     HIP_TRY(wait_stream(c));
@@ -144,46 +190,116 @@ float bound_from_max(double m, bool nan_is_unbounded) {
 // normalisation (homography, fundamental) and the pre-filters' bound, in the same cases - absolute pose through a linear camera,
 // two-view problems from 1024 correspondences with linear cameras (an absolute-pose problem of a non-linear camera reads k_prepare's
 // maximum back: make_problem_prepared, as in the host call).  No launch where the host has no pass either.
-int device_front_stats(Context *c, int kind, size_t n, const pl_robust_options &opt, const pl_camera *camera1, const pl_camera *camera2,
-                       PointNorm *norm, float *bound) {
-    *bound = std::numeric_limits<float>::infinity();
-    if (n == 0)
-        return PL_OK;
-    PointStatsArgs args;
+// The cases, as k_point_stats' arguments - one function for the single call (device_front_stats) and for the members of a group
+// (group_stage_device), whose kernel takes them from a table.  false: the host has no pass over this problem's points.
+bool front_stats_plan(int kind, size_t n, const pl_robust_options &opt, const pl_camera *camera1, const pl_camera *camera2,
+                      PointStatsArgs &args) {
     std::memset(&args, 0, sizeof(args));
-    PointStatsRecord rec;
+    if (n == 0)
+        return false;
+    point_stats_sizes(args, n);
     if (kind == EST_ABS) {
         const CameraParams cam = to_cam(camera1);
         if (prefilter_bound_on_device(kind, prepare_unproject(cam, nullptr)))
-            return PL_OK;
+            return false;
         args.bound = 1;
         linear_camera_terms(cam, args.cx1, args.cy1, args.fx1, args.fy1);
-        int rc = run_point_stats(c, n, args, &rec);
-        if (rc == PL_OK)
-            *bound = bound_from_max(rec.absmax, false);
-        return rc;
+        return true;
     }
     if (kind == EST_REL) {
         if (n < 1024 || !linear_camera_terms(to_cam(camera1), args.cx1, args.cy1, args.fx1, args.fy1) ||
             !linear_camera_terms(to_cam(camera2), args.cx2, args.cy2, args.fx2, args.fy2))
-            return PL_OK;
+            return false;
         args.bound = 2;
-        int rc = run_point_stats(c, n, args, &rec);
-        if (rc == PL_OK)
-            *bound = bound_from_max(rec.absmax, true);
-        return rc;
+        return true;
     }
     if (kind != EST_FUND && kind != EST_HOM) // (tangent Sampson: its pre-filter takes no bound)
-        return PL_OK;
+        return false;
     args.norm = 1;
     args.centred = front_centred(kind, opt) ? 1 : 0;
     args.bound = n >= 1024 ? 3 : 0;
-    int rc = run_point_stats(c, n, args, &rec);
-    if (rc != PL_OK)
-        return rc;
-    norm->c1x = rec.c1x, norm->c1y = rec.c1y, norm->c2x = rec.c2x, norm->c2y = rec.c2y, norm->scale = rec.scale;
+    return true;
+}
+// ... and what the front-end takes from the record of a planned pass
+void front_stats_take(const PointStatsArgs &args, const PointStatsRecord &rec, PointNorm *norm, float *bound) {
+    if (args.norm)
+        norm->c1x = rec.c1x, norm->c1y = rec.c1y, norm->c2x = rec.c2x, norm->c2y = rec.c2y, norm->scale = rec.scale;
     if (args.bound)
-        *bound = bound_from_max(rec.absmax, true);
+        *bound = bound_from_max(rec.absmax, /*nan_is_unbounded=*/args.bound != 1);
+}
+int device_front_stats(Context *c, int kind, size_t n, const pl_robust_options &opt, const pl_camera *camera1, const pl_camera *camera2,
+                       PointNorm *norm, float *bound) {
+    *bound = std::numeric_limits<float>::infinity();
+    PointStatsArgs args;
+    if (!front_stats_plan(kind, n, opt, camera1, camera2, args))
+        return PL_OK;
+    PointStatsRecord rec;
+    const int rc = run_point_stats(c, n, args, &rec);
+    if (rc == PL_OK)
+        front_stats_take(args, rec, norm, bound);
+    return rc;
+}
+
+// Stage A of a lock-step group whose members' points are in the caller's device memory (pl_estimate_batch_dev; run_group): ONE
+// k_ingest_g launch writes the members that are not contiguous fp64 into their slices of the group's raw block (the others are
+// read where they lie), ONE k_point_stats_g launch makes the host's passes of all members, one synchronisation brings every
+// record back (the kernel writes them into pinned memory itself); then the front-end arithmetic per member, from its record.
+// No pinned staging block and no upload of points.  `resume` (a regrouped long run): the front-ends are complete, only the raw
+// blocks are formed again.
+int group_stage_device(Context *c, GroupContext &gc, GroupItem *const *pit, uint32_t count, bool resume) {
+    HIP_TRY(gc.h_ingest.ensure(sizeof(IngestGroupArgs) * count));
+    IngestGroupArgs *hi = gc.h_ingest.as<IngestGroupArgs>();
+    uint32_t ingest_n = 0;
+    for (uint32_t i = 0; i < count; ++i) {
+        GroupItem &g = (*pit[i]);
+        const pl_device_points &a = g.ditem->a, &b = g.ditem->b;
+        std::memset(&hi[i], 0, sizeof(hi[i]));
+        double *out_a = reads_in_place(&a) ? nullptr : gc.raw.as<double>() + g.raw_a_off;
+        double *out_b = reads_in_place(&b) ? nullptr : gc.raw.as<double>() + g.raw_b_off;
+        g.raw_a = out_a ? out_a : static_cast<const double *>(a.data);
+        g.raw_b = out_b ? out_b : static_cast<const double *>(b.data);
+        if (!out_a && !out_b)
+            continue;
+        hi[i].a = ingest_src(&a), hi[i].b = ingest_src(&b);
+        hi[i].n = g.n;
+        hi[i].out_a = out_a, hi[i].out_b = out_b;
+        ingest_n = std::max(ingest_n, g.n);
+    }
+    HIP_TRY(launch_ingest_g(gc.h_ingest.dev<IngestGroupArgs>(), count, ingest_n, c->stream));
+    if (resume)
+        return PL_OK;
+    HIP_TRY(gc.h_pstats_args.ensure(sizeof(PointStatsGroupArgs) * count));
+    HIP_TRY(gc.h_pstats.ensure(sizeof(PointStatsRecord) * count));
+    PointStatsGroupArgs *hs = gc.h_pstats_args.as<PointStatsGroupArgs>();
+    bool any = false;
+    for (uint32_t i = 0; i < count; ++i) {
+        GroupItem &g = (*pit[i]);
+        const pl_batch_item &it = *g.item;
+        std::memset(&hs[i], 0, sizeof(hs[i]));
+        if (!front_stats_plan(g.kind, g.n, *it.opt, it.camera1, it.camera2, hs[i].args))
+            continue;
+        hs[i].a_raw = g.raw_a, hs[i].b_raw = g.raw_b;
+        hs[i].n = g.n;
+        hs[i].out = gc.h_pstats.dev<PointStatsRecord>() + i;
+        any = true;
+    }
+    if (any) {
+        HIP_TRY(launch_point_stats_g(gc.h_pstats_args.dev<PointStatsGroupArgs>(), count, c->stream));
+        HIP_TRY(wait_stream(c));
+    }
+    const PointStatsRecord *rec = gc.h_pstats.as<PointStatsRecord>();
+    for (uint32_t i = 0; i < count; ++i) {
+        GroupItem &g = (*pit[i]);
+        const pl_batch_item &it = *g.item;
+        PointNorm norm;
+        float bound = std::numeric_limits<float>::infinity();
+        if (hs[i].n)
+            front_stats_take(hs[i].args, rec[i], &norm, &bound);
+        front_begin_with(g.fe, g.kind, norm, *it.opt, it.camera1, it.camera2);
+        g.xy_absmax = bound;
+        g.have_absmax = true;
+        g.prepared = true;
+    }
     return PL_OK;
 }
 
@@ -248,6 +364,91 @@ int pl_debug_point_stats_dev(const pl_device_points *x1, const pl_device_points 
     if (rc != PL_OK)
         return rc;
     out[6] = rec.absmax;
+    return PL_OK;
+}
+
+int pl_debug_point_stats_group_dev(const pl_device_points *x1, const pl_device_points *x2, const size_t *n, size_t count, int centroid,
+                                   double *out) {
+    if (!out || !x1 || !x2 || !n)
+        return fail(PL_ERR_INVALID, "a pointer is null");
+    if (count == 0)
+        return PL_OK;
+    if (count > 65535)
+        return fail(PL_ERR_INVALID, "too many members");
+    int rc = PL_OK;
+    for (size_t i = 0; i < count && rc == PL_OK; ++i) {
+        rc = check_points_plain(&x1[i], n[i], 2);
+        if (rc == PL_OK)
+            rc = check_points_plain(&x2[i], n[i], 2);
+    }
+    Context *c = nullptr;
+    if (rc == PL_OK)
+        rc = get_context(&c);
+    DeviceAllocationCache allocations;
+    for (size_t i = 0; i < count && rc == PL_OK; ++i) {
+        rc = allocations.check(c, &x1[i], n[i]);
+        if (rc == PL_OK)
+            rc = allocations.check(c, &x2[i], n[i]);
+    }
+    if (rc != PL_OK)
+        return rc;
+    const uint32_t G = (uint32_t)count;
+    // the members' slices of one raw block (sets that are contiguous fp64 are read where they lie), the two tables, the records
+    size_t raw_doubles = 0;
+    for (size_t i = 0; i < count; ++i)
+        raw_doubles += (reads_in_place(&x1[i]) ? 0 : 2 * n[i]) + (reads_in_place(&x2[i]) ? 0 : 2 * n[i]);
+    HIP_TRY(c->raw_a.ensure(sizeof(double) * std::max<size_t>(raw_doubles, 1)));
+    const size_t table_bytes = (sizeof(IngestGroupArgs) + sizeof(PointStatsGroupArgs) + sizeof(PointStatsRecord)) * count;
+    HIP_TRY(c->h_pstats.ensure(table_bytes));
+    PointStatsRecord *rec = c->h_pstats.as<PointStatsRecord>();
+    PointStatsGroupArgs *hs = reinterpret_cast<PointStatsGroupArgs *>(rec + count);
+    IngestGroupArgs *hi = reinterpret_cast<IngestGroupArgs *>(hs + count);
+    PointStatsRecord *d_rec = c->h_pstats.dev<PointStatsRecord>();
+    PointStatsGroupArgs *d_hs = reinterpret_cast<PointStatsGroupArgs *>(d_rec + count);
+    IngestGroupArgs *d_hi = reinterpret_cast<IngestGroupArgs *>(d_hs + count);
+    std::memset(rec, 0, table_bytes);
+    size_t at = 0;
+    uint32_t ingest_n = 0;
+    for (size_t i = 0; i < count; ++i) {
+        out[8 * i + 0] = out[8 * i + 1] = out[8 * i + 2] = out[8 * i + 3] = out[8 * i + 4] = out[8 * i + 5] = out[8 * i + 6] = out[8 * i + 7] = 0.0;
+        if (n[i] == 0)
+            continue;
+        double *oa = nullptr, *ob = nullptr;
+        if (!reads_in_place(&x1[i]))
+            oa = c->raw_a.as<double>() + at, at += 2 * n[i];
+        if (!reads_in_place(&x2[i]))
+            ob = c->raw_a.as<double>() + at, at += 2 * n[i];
+        if (oa || ob) {
+            hi[i].a = ingest_src(&x1[i]), hi[i].b = ingest_src(&x2[i]);
+            hi[i].n = (uint32_t)n[i];
+            hi[i].out_a = oa, hi[i].out_b = ob;
+            ingest_n = std::max(ingest_n, (uint32_t)n[i]);
+        }
+        hs[i].a_raw = oa ? oa : static_cast<const double *>(x1[i].data);
+        hs[i].b_raw = ob ? ob : static_cast<const double *>(x2[i].data);
+        hs[i].n = (uint32_t)n[i];
+        hs[i].out = d_rec + i;
+        hs[i].args.norm = 1, hs[i].args.centred = centroid ? 1 : 0, hs[i].args.bound = 3;
+        point_stats_sizes(hs[i].args, n[i]);
+    }
+    HIP_TRY(launch_ingest_g(d_hi, G, ingest_n, c->stream));
+    HIP_TRY(launch_point_stats_g(d_hs, G, c->stream));
+    HIP_TRY(wait_stream(c));
+    for (size_t i = 0; i < count; ++i) {
+        if (n[i] == 0)
+            continue;
+        double *o = out + 8 * i;
+        o[0] = rec[i].c1x, o[1] = rec[i].c1y, o[2] = rec[i].c2x, o[3] = rec[i].c2y, o[4] = rec[i].scale, o[5] = rec[i].absmax;
+        std::memset(&hs[i].args, 0, sizeof(hs[i].args));
+        hs[i].args.bound = 1; // the identity camera: |x - 0| / 1
+        hs[i].args.fx1 = hs[i].args.fy1 = 1.0;
+        point_stats_sizes(hs[i].args, n[i]);
+    }
+    HIP_TRY(launch_point_stats_g(d_hs, G, c->stream));
+    HIP_TRY(wait_stream(c));
+    for (size_t i = 0; i < count; ++i)
+        if (n[i])
+            out[8 * i + 6] = rec[i].absmax;
     return PL_OK;
 }
 

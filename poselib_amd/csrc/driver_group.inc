@@ -8,7 +8,8 @@
 // (GroupArgs), so a group costs the launches of ONE problem:
 //
 //   stage A  raw correspondences of all problems -> one pinned block -> one upload; k_prepare_g (un-projection /
-//            normalisation, robust.cc:40-46, 286-292, utils.cc:584-644 per-point part)
+//            normalisation, robust.cc:40-46, 286-292, utils.cc:584-644 per-point part).  Points in the caller's device memory
+//            (pl_estimate_batch_dev): no pinned block and no upload - k_ingest_g, k_point_stats_g, then k_prepare_g
 //   stage C  per batch step: positions, generate, compact, gather, score, finalize, records, candidates re-scored -
 //            8..10 launches for the whole group, ONE synchronisation; the host replays every problem's sequential loop
 //            (RansacRun: the same code as the single-problem path); all triggered local optimisations of all problems
@@ -42,6 +43,7 @@ struct GroupContext { // per host thread AND device, kept for later groups
     HostBuf h_raw, h_args, h_ctl, h_meta, h_recm, h_offsets, h_mask, h_tasks, h_count, h_score, h_tail;
     HostBuf h_samples, h_absmax; // PROSAC samples of a step's members; max|x| read back from k_prepare_g (absolute pose through a non-linear camera)
     HostBuf h_raw_alt, h_prep_args;          // the NEXT group's raw points (staged while this worker waits for the device); stage A's table
+    HostBuf h_ingest, h_pstats_args, h_pstats; // groups of pl_estimate_batch_dev: the tables of k_ingest_g / k_point_stats_g, the members' records
     const void *staged_first = nullptr;     // first item of the group whose raw points sit in h_raw_alt
     void release() { // pl_set_device moved the thread to another GPU: nothing of the old device may be reused
         for (DevBuf *b : {&arena, &raw, &args, &lm_records, &lm_scratch, &seq_count, &seq_score, &sel_count}) {
@@ -50,7 +52,7 @@ struct GroupContext { // per host thread AND device, kept for later groups
             b->p = nullptr, b->cap = 0;
         }
         staged_first = nullptr;
-        for (HostBuf *b : {&h_raw, &h_args, &h_ctl, &h_meta, &h_recm, &h_offsets, &h_mask, &h_tasks, &h_count, &h_score, &h_tail, &h_raw_alt, &h_prep_args, &h_samples, &h_absmax}) {
+        for (HostBuf *b : {&h_raw, &h_args, &h_ctl, &h_meta, &h_recm, &h_offsets, &h_mask, &h_tasks, &h_count, &h_score, &h_tail, &h_raw_alt, &h_prep_args, &h_samples, &h_absmax, &h_ingest, &h_pstats_args, &h_pstats}) {
             if (b->p)
                 (void)hipHostFree(b->p);
             b->p = b->dp = nullptr, b->cap = 0;
@@ -127,6 +129,8 @@ thread_local pl_batch_report g_last_report = {0, 0, 0, 0, 0};
 
 struct GroupItem {
     pl_batch_item *item = nullptr;
+    const pl_batch_item_dev *ditem = nullptr; // pl_estimate_batch_dev: the caller's item, whose points are in device memory (`item`: its
+                                              // host-side copy with a == b == null; nothing of a group reads host points then)
     pl_ransac_item *ritem = nullptr; // device-resident problem (pl_ransac_batch) instead of `item`
     int kind = 0;
     uint32_t n = 0;
@@ -149,13 +153,16 @@ struct GroupItem {
     bool deferred = false; // still running after the group's step budget: continues in a regrouped call (run_group `resume`)
     int64_t off_fetch = -1; // entry of the slot's offsets table whose value (hypotheses up to the stop) stage D fetches
     size_t raw_a_off = 0, raw_b_off = 0; // offsets (doubles) into the group's raw block
+    const double *raw_a = nullptr, *raw_b = nullptr; // the member's fp64 AoS blocks on the device: its slices of the raw block, or -
+                                                     // contiguous fp64 sets of a pl_estimate_batch_dev item - the caller's memory
     double t_start = 0;
 };
 
 size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 
-bool group_eligible(const pl_batch_item &it) {
-    if (it.kind < 0 || it.kind > 3 || !it.opt || !it.model || !it.a || !it.b)
+// points_on_device: an item of pl_estimate_batch_dev (its descriptors have been checked; a and b are null)
+bool group_eligible(const pl_batch_item &it, bool points_on_device = false) {
+    if (it.kind < 0 || it.kind > 3 || !it.opt || !it.model || (!points_on_device && (!it.a || !it.b)))
         return false;
     const pl_robust_options &o = *it.opt;
     if (validate_options(&o) != PL_OK)
@@ -266,6 +273,20 @@ int group_prepare_item(GroupItem &g) {
     front_begin(g.fe, it.kind, it.a, it.b, it.n, *it.opt, it.camera1, it.camera2);
     return PL_OK;
 }
+
+// ... of an item whose points are in device memory: what run_group sizes the group by; the front-end itself follows in stage A,
+// from the record k_point_stats_g writes (group_stage_device, driver_dev.inc)
+int group_prepare_device_item(GroupItem &g) {
+    const pl_batch_item &it = *g.item;
+    g.kind = it.kind;
+    g.n = (uint32_t)it.n;
+    g.st = it.stats ? it.stats : &g.local_st;
+    g.fe.kind = it.kind;
+    g.fe.scaled = *it.opt;
+    return PL_OK;
+}
+bool reads_in_place(const pl_device_points *d);
+int group_stage_device(Context *c, GroupContext &gc, GroupItem *const *pit, uint32_t count, bool resume);
 
 int group_prepare_resident(GroupItem &g) {
     pl_ransac_item &it = *g.ritem;
@@ -429,13 +450,14 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
         // depend on how the iterations are cut into batches: the replay is exact)
         // (resident groups: long fixed-length runs are welcome - up to the whole run in one batch, arena permitting)
         max_B = std::max<uint32_t>(max_B, (uint32_t)std::min<uint64_t>(std::max<uint64_t>(grow, resident ? 2048 : kGroupJump), resident ? 131072 : (resume ? 32768 : kGroupJump)));
-        if (!resident) {
+        if (!resident) { // (a device set that is contiguous fp64 is read where it lies: no slice)
             g.raw_a_off = raw_doubles;
-            raw_doubles += 2 * (size_t)g.n;
+            raw_doubles += (g.ditem && reads_in_place(&g.ditem->a)) ? 0 : 2 * (size_t)g.n;
             g.raw_b_off = raw_doubles;
-            raw_doubles += (size_t)db * g.n;
+            raw_doubles += (g.ditem && reads_in_place(&g.ditem->b)) ? 0 : (size_t)db * g.n;
         }
     }
+    const bool from_device = !resident && (*pit[0]).ditem != nullptr; // (a group is all-device or all-host: pl_estimate_batch_dev)
     const uint32_t maxm = group_record_slots(kind); // record slots per iteration
     // the sampler window (sampler_window) is largest for the smallest problem of the group - the same function sizes every item's
     // window below (M64), so no item of a full-size batch outgrows the slot
@@ -489,7 +511,7 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
         }
         HIP_TRY(gc.arena.ensure(want));
     }
-    bool staged = !resident && gc.staged_first == (const void *)pit[0];
+    bool staged = !resident && !from_device && gc.staged_first == (const void *)pit[0];
     if (staged) // the raw points were copied into the alternate block while this worker waited for its previous group
         std::swap(gc.h_raw, gc.h_raw_alt);
     gc.staged_first = nullptr;
@@ -509,7 +531,8 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
     if (staged && gc.h_raw.cap < raw_bytes)
         staged = false;
     HIP_TRY(gc.raw.ensure(raw_bytes));
-    HIP_TRY(gc.h_raw.ensure(raw_bytes));
+    if (!from_device) // (no pinned staging block for points that are on the device already)
+        HIP_TRY(gc.h_raw.ensure(raw_bytes));
     HIP_TRY(gc.h_prep_args.ensure(sizeof(PrepareGroupArgs) * count));
     const size_t args_bytes = std::max({sizeof(GroupArgs), sizeof(PrepareGroupArgs), sizeof(SeqScoreArgs) + sizeof(SelectArgs) + sizeof(MaskArgs)}) * count;
     HIP_TRY(gc.args.ensure(args_bytes));
@@ -539,20 +562,31 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
             g.prob.borrowed = true;
         }
     } else {
-        double *h_raw = gc.h_raw.as<double>();
         uint32_t n_dev_absmax = 0;
-        if (!staged)
+        if (from_device) { // k_ingest_g, k_point_stats_g, the members' front-ends: no host copy of points
+            const int rc = group_stage_device(c, gc, pit, count, resume);
+            if (rc != PL_OK)
+                return rc;
+        } else {
+            double *h_raw = gc.h_raw.as<double>();
+            if (!staged)
+                for (uint32_t i = 0; i < count; ++i) {
+                    GroupItem &g = (*pit[i]);
+                    std::memcpy(h_raw + g.raw_a_off, g.item->a, sizeof(double) * 2 * g.n);
+                    std::memcpy(h_raw + g.raw_b_off, g.item->b, sizeof(double) * db * g.n);
+                }
+            HIP_TRY(hipMemcpyAsync(gc.raw.p, h_raw, sizeof(double) * raw_doubles, hipMemcpyHostToDevice, c->stream));
             for (uint32_t i = 0; i < count; ++i) {
                 GroupItem &g = (*pit[i]);
-                std::memcpy(h_raw + g.raw_a_off, g.item->a, sizeof(double) * 2 * g.n);
-                std::memcpy(h_raw + g.raw_b_off, g.item->b, sizeof(double) * db * g.n);
+                g.raw_a = gc.raw.as<double>() + g.raw_a_off;
+                g.raw_b = gc.raw.as<double>() + g.raw_b_off;
             }
-        HIP_TRY(hipMemcpyAsync(gc.raw.p, h_raw, sizeof(double) * raw_doubles, hipMemcpyHostToDevice, c->stream));
+        }
         PrepareGroupArgs *hp = gc.h_prep_args.as<PrepareGroupArgs>(); // (its own pinned table: stage C rewrites h_args without waiting)
         for (uint32_t i = 0; i < count; ++i) {
             GroupItem &g = (*pit[i]);
-            hp[i].a_raw = gc.raw.as<double>() + g.raw_a_off;
-            hp[i].b_raw = gc.raw.as<double>() + g.raw_b_off;
+            hp[i].a_raw = g.raw_a;
+            hp[i].b_raw = g.raw_b;
             hp[i].n = g.n;
             hp[i].pad = 0;
             hp[i].args = g.fe.prep;
@@ -1001,8 +1035,8 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
         CameraParams raw_cam;
         std::memset(&raw_cam, 0, sizeof(raw_cam));
         raw_cam.model_id = CAM_NULL;
-        h.a_raw = gc.raw.as<double>() + g.raw_a_off;
-        h.b_raw = gc.raw.as<double>() + g.raw_b_off;
+        h.a_raw = g.raw_a;
+        h.b_raw = g.raw_b;
         h.n = g.n;
         h.args = prepare_unproject(raw_cam, nullptr);
         h.soa = reinterpret_cast<double *>(slot(i, L.pts2));

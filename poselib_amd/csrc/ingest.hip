@@ -7,6 +7,8 @@
 //   k_point_stats   what the front-ends compute over the raw points on the host: the two ORDER-DEPENDENT reductions of the
 //                   homography / fundamental normalisation (utils.cc:584-644: centroid sums, then the mean distance), added
 //                   strictly in index order by one wavefront, and the order-free maxima behind the pre-filters' bound
+//   k_ingest_g, k_point_stats_g   the two for a lock-step group of problems (pl_estimate_batch_dev): the member is a grid
+//                   dimension, its arguments come from a device-visible table; the bodies are those of the single forms
 //
 // The build has -ffp-contract=off, fp64 sqrt and division on the device are IEEE (tests/test_gpu_device_math*): the sums carry
 // the host's bits.  The caller's pointers arrive as kernel arguments and are read as global memory (pl_global.h).
@@ -42,11 +44,8 @@ __device__ __forceinline__ void take_abs(double &m, double x) {
 } // namespace
 
 // One thread per correspondence: its row of each set, element by element (plain loads; rows are 8 - 24 bytes).
-__global__ __launch_bounds__(256) void k_ingest(IngestSrc a, IngestSrc b, uint32_t n, double *__restrict__ out_a,
-                                                double *__restrict__ out_b) {
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n)
-        return;
+__device__ __forceinline__ void ingest_row(const IngestSrc &a, const IngestSrc &b, uint32_t i, double *__restrict__ out_a,
+                                           double *__restrict__ out_b) {
     if (out_a) {
         const size_t row = (size_t)i * (size_t)a.row_stride;
         for (int d = 0; d < a.cols; ++d)
@@ -57,6 +56,25 @@ __global__ __launch_bounds__(256) void k_ingest(IngestSrc a, IngestSrc b, uint32
         for (int d = 0; d < b.cols; ++d)
             out_b[(size_t)i * b.cols + d] = ingest_load(b.data, b.f32, row + d);
     }
+}
+__global__ __launch_bounds__(256) void k_ingest(IngestSrc a, IngestSrc b, uint32_t n, double *__restrict__ out_a,
+                                                double *__restrict__ out_b) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n)
+        return;
+    ingest_row(a, b, i, out_a, out_b);
+}
+// ... of every member of a group: blockIdx.z is the member, the grid's extent the largest member's.  A member whose sets are both
+// read where they lie (out_a == out_b == null) has n == 0 in the table; blocks beyond a member's rows return.
+__global__ __launch_bounds__(256) void k_ingest_g(const IngestGroupArgs *tab) {
+    const IngestGroupArgs &in = tab[blockIdx.z];
+    const uint32_t n = in.n;
+    if (blockIdx.x * 256u >= n)
+        return;
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n)
+        return;
+    ingest_row(in.a, in.b, i, as_global(in.out_a), as_global(in.out_b)); // (the sources are read as global memory by ingest_load)
 }
 
 // ... straight into a resident problem's SoA block: a's columns, then b's, n doubles each (make_problem's layout and bound)
@@ -89,8 +107,9 @@ __global__ __launch_bounds__(256) void k_ingest_soa(IngestSrc a, IngestSrc b, ui
 // dependent additions and the result needs no broadcast.  All four wavefronts then take the maxima, which do not depend on the
 // order.
 constexpr int kStatsChunk = 256;
-__global__ __launch_bounds__(256) void k_point_stats(const double *__restrict__ a_raw, const double *__restrict__ b_raw, uint32_t n,
-                                                     PointStatsArgs g, PointStatsRecord *__restrict__ out) {
+// (the body of k_point_stats and of k_point_stats_g: one piece of code, so the sums of the two forms cannot drift apart)
+__device__ __forceinline__ void point_stats_body(const double *__restrict__ a_raw, const double *__restrict__ b_raw, uint32_t n,
+                                                 const PointStatsArgs &g, PointStatsRecord *__restrict__ out) {
     __shared__ double s_terms[4 * kStatsChunk];
     __shared__ double s_norm[5];
     __shared__ unsigned long long s_max;
@@ -185,11 +204,35 @@ __global__ __launch_bounds__(256) void k_point_stats(const double *__restrict__ 
         out->reserved[0] = out->reserved[1] = 0.0;
     }
 }
+__global__ __launch_bounds__(256) void k_point_stats(const double *__restrict__ a_raw, const double *__restrict__ b_raw, uint32_t n,
+                                                     PointStatsArgs g, PointStatsRecord *__restrict__ out) {
+    point_stats_body(a_raw, b_raw, n, g, out);
+}
+// One workgroup per member of a group (blockIdx.z); a member the host has no pass for (n == 0 in the table) gets no work and
+// no record.  n and the arguments are the same for the whole workgroup, so are the body's barriers.
+__global__ __launch_bounds__(256) void k_point_stats_g(const PointStatsGroupArgs *tab) {
+    const PointStatsGroupArgs &in = tab[blockIdx.z];
+    if (in.n == 0)
+        return;
+    point_stats_body(as_global(in.a_raw), as_global(in.b_raw), in.n, in.args, as_global(in.out));
+}
 
 hipError_t launch_ingest(const IngestSrc &a, const IngestSrc &b, uint32_t n, double *out_a, double *out_b, hipStream_t stream) {
     if (n == 0 || (!out_a && !out_b))
         return hipSuccess;
     k_ingest<<<dim3((n + 255) / 256), dim3(256), 0, stream>>>(a, b, n, out_a, out_b);
+    return hipGetLastError();
+}
+hipError_t launch_ingest_g(const IngestGroupArgs *tab, uint32_t G, uint32_t max_n, hipStream_t stream) {
+    if (G == 0 || max_n == 0)
+        return hipSuccess;
+    k_ingest_g<<<dim3((max_n + 255) / 256, 1, G), dim3(256), 0, stream>>>(tab);
+    return hipGetLastError();
+}
+hipError_t launch_point_stats_g(const PointStatsGroupArgs *tab, uint32_t G, hipStream_t stream) {
+    if (G == 0)
+        return hipSuccess;
+    k_point_stats_g<<<dim3(1, 1, G), dim3(256), 0, stream>>>(tab);
     return hipGetLastError();
 }
 hipError_t launch_ingest_soa(const IngestSrc &a, const IngestSrc &b, uint32_t n, int b_in_max, double *soa,

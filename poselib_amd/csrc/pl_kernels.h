@@ -245,6 +245,22 @@ struct PointStatsRecord { // what the call reads back
 };
 hipError_t launch_point_stats(const double *a_raw, const double *b_raw, uint32_t n, const PointStatsArgs &args,
                               PointStatsRecord *out /* device-visible */, hipStream_t stream);
+// The two for the members of a lock-step group (pl_estimate_batch_dev): one launch each, the member is blockIdx.z.  The tables are
+// device-visible (pinned and mapped, or device memory); the pointers in them are read as global memory.
+struct IngestGroupArgs {
+    IngestSrc a, b;
+    uint32_t n, pad;       // rows; 0: nothing to copy for this member (both sets are read where they lie)
+    double *out_a, *out_b; // the member's slices of the group's raw block; null: that set is contiguous fp64 and read in place
+};
+// blocks beyond a member's n return; max_n: the largest n of the table
+hipError_t launch_ingest_g(const IngestGroupArgs *tab, uint32_t G, uint32_t max_n, hipStream_t stream);
+struct PointStatsGroupArgs {
+    const double *a_raw, *b_raw; // fp64 AoS blocks (N x 2 each): the ingested slices or the caller's memory
+    uint32_t n, pad;             // 0: the host has no pass over this member's points - no work, no record
+    PointStatsArgs args;
+    PointStatsRecord *out;       // device-visible
+};
+hipError_t launch_point_stats_g(const PointStatsGroupArgs *tab, uint32_t G, hipStream_t stream);
 // After the LM kernels: records of the refined models on the device (skipped tasks keep their input record), and the
 // choice "refined model if its score beats `incumbent_score`, else the incumbent" of the final refinement
 // (ransac_impl.h:190-198) so that the inlier mask can follow without a host round trip.
