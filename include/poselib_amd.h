@@ -513,12 +513,14 @@ int pl_debug_score_stream_ex(int route, pl_debug_score_member *members, size_t n
 /* Diagnostic: the PRUNED form of the matrix-core absolute-pose scorer on a caller-given model list, whatever
  * the gate of the batch steps says of its length: the first `lead` live hypotheses against every chunk of correspondences; their
  * best count and score, with the incumbent's (init_max, init_min), place the split chunk c*; every hypothesis against the chunks in
- * front of c*; the hypotheses that could still become candidates - the kept ones - against the rest; finalize and the candidate
- * scan of a batch step.  Routes and the inactive slot as in pl_debug_score_stream_ex (route 0: one member, the single launches;
+ * front of c* through the matrix-core filter alone (survivor counts, an upper bound of the inlier counts); the positions those
+ * counts cannot exclude - the pre-selection - against every chunk, exactly; finalize and the candidate scan of a batch step.  Behind
+ * these launches the entry labels the pre-selected positions with the exact rule on their exact partials in front of c*: that label
+ * is `kept`.  Routes and the inactive slot as in pl_debug_score_stream_ex (route 0: one member, the single launches;
  * route 2: 1 .. 4 members behind an inactive slot 0, the group launches).
- *   counts / scores  per hypothesis, as pl_debug_score_stream for a kept one; for a pruned one what it scored in front of c* with
- *                    every correspondence from c* on counted as an outlier: a count not above, a score not below the full ones
- *   kept             per hypothesis, 1 or 0 (NaN models, never scored, report 1; cstar == chunks: all 1)
+ *   counts / scores  per hypothesis, as pl_debug_score_stream for a pre-selected one (every kept one is); a position dropped on its
+ *                    survivor count reports no inliers: count 0, score n thr^2 - a count not above, a score not below the full ones
+ *   kept             per hypothesis, 1 or 0: the exact rule (NaN models, never scored, report 1; cstar == chunks: all 1)
  *   cand             hypothesis indices of the candidates the scan lists, in the order it listed them (num_cand of them, at most
  *                    cand_cap are written)
  * PL_ERR_UNSUPPORTED: a member whose problem is not scored on the matrix cores.  PL_ERR_INVALID: as pl_debug_score_stream_ex, or a
@@ -540,12 +542,22 @@ typedef struct pl_debug_prune_member {
     uint32_t cstar, chunks, chunk_points; /* the split chunk, the chunks of the launch and the correspondences of one */
     uint32_t lead;                        /* live positions of the lead */
     uint32_t lead_max;
-    uint32_t num_live, num_selected;      /* hypotheses without a NaN entry; length of the selection list (0 when cstar == chunks) */
-    uint32_t slices, pad;                 /* workgroups of 8 wavefronts per chunk of phase A (the plain launch's; the lead runs on
-                                             min(slices, 2), phase B on ceil(slices / 4)) */
+    uint32_t num_live, num_selected;      /* hypotheses without a NaN entry; live hypotheses that are kept (0 when cstar == chunks) */
+    uint32_t slices, num_preselected;     /* workgroups of 8 wavefronts per chunk of the count launch (the plain launch's; the lead
+                                             runs on min(slices, 2), the exact launch on ceil(slices / 4)); live positions the exact
+                                             launch scored: the lead and what the survivor counts could not exclude (this
+                                             word was `pad`, always written 0: same offset and size, PL_ABI_VERSION stays) */
     double lead_min;
 } pl_debug_prune_member;
 int pl_debug_score_pruned(int route, pl_debug_prune_member *members, size_t num_members, uint32_t *idle_changed);
+/* Diagnostic: the count launch of the pruned form alone - the matrix-core filter without the exact pass - over the whole list and
+ * every chunk.  Members and routes as pl_debug_score_pruned: problem, models, n, max_error are read; chunks, chunk_points, num_live
+ * and slices are written; no lead, selection or finalize runs, so every other field and array of a member is neither read nor
+ * written.  survivors[i]: member i's [chunks][n] survivor counts in hypothesis order, chunks as pl_debug_score_shape
+ * gives them for the route; a NaN model reports 0.  guard_changed: words of the count columns behind the live list's end that the
+ * launch changed - which must be 0. */
+int pl_debug_score_survivors(int route, pl_debug_prune_member *members, size_t num_members, uint32_t *const *survivors,
+                             uint32_t *idle_changed, uint32_t *guard_changed);
 /* Diagnostic: 1 if a batch step of `iterations` iterations of a problem of `kind` with n_points correspondences, as a member of a
  * lock-step group (pl_ransac_batch, pl_estimate_batch), scores in the pruned form, 0 if not; pl_ransac_run's own steps never do (coordinates and threshold in the pre-filter's range assumed, as pl_debug_group_slices).  Host arithmetic only. */
 int pl_debug_score_prune_gate(int kind, uint32_t n_points, uint32_t iterations);

@@ -89,7 +89,7 @@ class DebugPruneMember(C.Structure):  # pl_debug_prune_member
     _fields_ = [("problem", C.c_void_p), ("models", C.c_void_p), ("n", C.c_size_t), ("max_error", f64), ("init_min", f64),
                 ("init_max", u32), ("cand_cap", u32), ("counts", C.c_void_p), ("scores", C.c_void_p), ("kept", C.c_void_p),
                 ("cand", C.c_void_p), ("num_cand", u32), ("cstar", u32), ("chunks", u32), ("chunk_points", u32), ("lead", u32),
-                ("lead_max", u32), ("num_live", u32), ("num_selected", u32), ("slices", u32), ("pad", u32), ("lead_min", f64)]
+                ("lead_max", u32), ("num_live", u32), ("num_selected", u32), ("slices", u32), ("num_preselected", u32), ("lead_min", f64)]
 
 
 class DebugSamplerShape(C.Structure):  # pl_debug_sampler_shape_info
@@ -222,6 +222,7 @@ def _declare(L):
         "pl_debug_score_shape": (cint, [cint, C.c_uint32, cint, cint, P(C.c_uint32), P(C.c_uint32)]),
         "pl_debug_score_stream_ex": (cint, [cint, P(DebugScoreMember), sz, P(C.c_uint32)]),
         "pl_debug_score_pruned": (cint, [cint, P(DebugPruneMember), sz, P(C.c_uint32)]),
+        "pl_debug_score_survivors": (cint, [cint, P(DebugPruneMember), sz, P(C.c_void_p), P(C.c_uint32), P(C.c_uint32)]),
         "pl_debug_score_prune_gate": (cint, [cint, C.c_uint32, C.c_uint32]),
         "pl_debug_sampler_shape": (cint, [cint, u64, C.c_uint32, u64, P(DebugSamplerShape)]),
         "pl_debug_sample_positions": (cint, [cint, cint, cint, P(DebugSamplerMember), sz, P(C.c_uint32)]),
@@ -265,7 +266,7 @@ EXPORTED_SYMBOLS = [
     "pl_estimate_shared_focal_relative_pose", "pl_solve_focal_batch", "pl_p35pf", "pl_relpose_6pt_shared_focal", "pl_set_lm_mode",
     "pl_abi_version", "pl_problem_create_tangent", "pl_debug_inlier_mask", "pl_debug_tangent_chunk",
     "pl_p5lp_radial", "pl_debug_radial1d_chunk", "pl_debug_radial1d_generate", "pl_debug_group_slices", "pl_debug_generate",
-    "pl_debug_score_shape", "pl_debug_score_stream_ex", "pl_debug_score_pruned", "pl_debug_score_prune_gate",
+    "pl_debug_score_shape", "pl_debug_score_stream_ex", "pl_debug_score_pruned", "pl_debug_score_survivors", "pl_debug_score_prune_gate",
     "pl_estimate_absolute_pose_dev", "pl_estimate_relative_pose_dev", "pl_estimate_fundamental_dev", "pl_estimate_homography_dev",
     "pl_problem_create_dev", "pl_problem_create_tangent_dev", "pl_debug_check_device_points", "pl_debug_point_stats_dev",
     "pl_debug_sampler_shape", "pl_debug_sample_positions", "pl_estimate_batch_dev", "pl_debug_point_stats_group_dev",

@@ -690,7 +690,8 @@ def score_pruned(members, route=0):
     """Diagnostic (pl_debug_score_pruned): the pruned form of the matrix-core absolute-pose scorer on caller-given lists.
     members: (problem, models, max_error, init_max, init_min) - one for route 0 (single launches), up to four for route 2 (group
     launches behind an inactive slot).  Returns ([{"counts", "scores", "kept", "cand", "cstar", "chunks", "chunk_points", "lead",
-    "lead_max", "lead_min", "num_live", "num_selected", "slices"} per member], words changed in the inactive slot - which must be 0)."""
+    "lead_max", "lead_min", "num_live", "num_selected", "num_preselected", "slices"} per member], words changed in the inactive slot
+    - which must be 0)."""
     arr = (L.DebugPruneMember * max(len(members), 1))()
     keep = []
     cap = 4096
@@ -710,8 +711,34 @@ def score_pruned(members, route=0):
         a = arr[i]
         out.append({"counts": cnt[:n], "scores": sc[:n], "kept": kp[:n].astype(bool), "cand": cand[:min(a.num_cand, cap)].copy(),
                     "num_cand": a.num_cand, "cstar": a.cstar, "chunks": a.chunks, "chunk_points": a.chunk_points, "lead": a.lead,
-                    "lead_max": a.lead_max, "lead_min": a.lead_min, "num_live": a.num_live, "num_selected": a.num_selected, "slices": a.slices})
+                    "lead_max": a.lead_max, "lead_min": a.lead_min, "num_live": a.num_live, "num_selected": a.num_selected, "num_preselected": a.num_preselected,
+                    "slices": a.slices})
     return out, idle.value
+
+
+def score_survivors(members, route=0):
+    """Diagnostic (pl_debug_score_survivors): the count launch of the pruned scorer alone, over the whole list and every chunk.
+    members: (problem, models, max_error) - one for route 0, up to four for route 2.  Returns ([{"survivors": (chunks, n) uint32,
+    "chunks", "chunk_points", "num_live", "slices"} per member], words changed in the inactive slot, words changed behind the live
+    lists' ends - both must be 0)."""
+    arr = (L.DebugPruneMember * max(len(members), 1))()
+    outs = (C.c_void_p * max(len(members), 1))()
+    keep = []
+    for i, (problem, models, max_error) in enumerate(members):
+        n, flat = problem._flat_models(models)
+        chunks = score_shape(problem.kind, problem.n, True, route == 2)[0]
+        sv = np.zeros((chunks, max(n, 1)), dtype=np.uint32)
+        keep.append((n, flat, sv))
+        arr[i] = L.DebugPruneMember(problem._h, _ptr(flat), n, float(max_error))
+        outs[i] = sv.ctypes.data
+    idle, guard = C.c_uint32(0), C.c_uint32(0)
+    L.check(L.lib().pl_debug_score_survivors(int(route), arr, C.c_size_t(len(members)), outs, C.byref(idle), C.byref(guard)))
+    out = []
+    for i, (n, _, sv) in enumerate(keep):
+        a = arr[i]
+        assert a.chunks == sv.shape[0], (a.chunks, sv.shape)
+        out.append({"survivors": sv[:, :n], "chunks": a.chunks, "chunk_points": a.chunk_points, "num_live": a.num_live, "slices": a.slices})
+    return out, idle.value, guard.value
 
 
 def ransac_batch(problems, opts, max_in_flight=4, group_size=16):

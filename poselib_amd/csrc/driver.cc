@@ -713,7 +713,6 @@ void wire_batch_step(GroupArgs &a, const BatchRun &r, const BatchShape &s, const
     ra.f.count = b.count;
     ra.f.score = b.score;
     ra.f.kept = sa.prune.kept; // (nullptr: the step does not prune)
-    ra.f.prune = sa.prune.st;
     ra.slots = b.slots;
     ra.models = b.models;
     ra.blk_max = reinterpret_cast<uint32_t *>(b.blk_best);
@@ -1168,8 +1167,9 @@ struct RansacRun {
         s.chunks = score_chunks(kind, N, true, s.use_mfma);
         s.point_rows = abs16_point_rows(N);
         // (no pruning here, whatever score_prune_gate says of the step: this launch is ONE resident round of workgroups, chunks that
-        // return at once leave their compute units idle and the lead, the selection and phase B come on top - measured 0.113 ->
-        // 0.269 ms per step of the flagship problem, profiles/score_prune.md.  The single launches of the pruned form stay behind
+        // return at once leave their compute units idle and the lead, the selection and the second scorer launch come on top -
+        // measured with the one-tier form: 0.113 -> 0.269 ms per step of the flagship problem, profiles/score_prune.md; the two-tier
+        // form was not measured on this path.  The single launches of the pruned form stay behind
         // pl_debug_score_pruned route 0.)
         s.prune = false;
         b.device_positions = !host_positions && !force_host_positions && !prosac;
@@ -2870,7 +2870,10 @@ int debug_score_group(pl_debug_score_member *m, size_t count, uint32_t *idle_cha
 // their length: route 0 - launch_score_pruned and launch_finalize_records, the launches of RansacRun::enqueue_batch, on the single
 // launch's chunk shape; route 2 - a table with an inactive slot 0 through launch_group_score and launch_group_finalize_records, on
 // the group's chunk shape.  Every slot has an arena of its own, as in debug_score_group.
-int debug_score_pruned(int route, pl_debug_prune_member *m, size_t count, uint32_t *idle_changed) {
+// survivors (pl_debug_score_survivors): the count launch alone, over the whole list and every chunk; survivors[i] takes member i's
+// [chunks][n] counts (hypothesis order, a NaN model reports 0), *guard_changed the words behind the live list's end that changed.
+int debug_score_pruned(int route, pl_debug_prune_member *m, size_t count, uint32_t *idle_changed, uint32_t *const *survivors = nullptr,
+                       uint32_t *guard_changed = nullptr) {
     if (route != 0 && route != 2)
         return fail(PL_ERR_INVALID, "route: 0 single launch, 2 group form");
     if (!m || count == 0 || count > (route == 0 ? 1 : kDebugScoreMembers))
@@ -2977,15 +2980,28 @@ int debug_score_pruned(int route, pl_debug_prune_member *m, size_t count, uint32
         const uint32_t slices = std::max<uint32_t>(1u, std::min<uint32_t>(1536u / a.chunks, a.score.hyp_capacity)); // enqueue_batch's
         single_slices = std::max<uint32_t>(1u, std::min<uint32_t>(slices * (uint32_t)kScoreThreads / (64u * (uint32_t)kStreamWaves),
                                                                   score_slice_limit(EST_ABS, a.chunks, true))); // (launch_score_pruned's grid)
-        HIP_TRY(launch_score_pruned(a.score, slices, c->stream));
-        HIP_TRY(launch_finalize_records(a.rec, c->stream));
+        if (survivors) {
+            HIP_TRY(launch_score_count(a.score, slices, c->stream));
+        } else {
+            HIP_TRY(launch_score_pruned(a.score, slices, c->stream));
+            HIP_TRY(launch_prune_label(a.score, c->stream));
+            HIP_TRY(launch_finalize_records(a.rec, c->stream));
+        }
     } else {
         ha[0].slices = ha[1].slices;
         HIP_TRY(hipMalloc(&dtable.p, sizeof(GroupArgs) * dims.G));
         HIP_TRY(hipMemcpyAsync(dtable.p, ha, sizeof(GroupArgs) * dims.G, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(launch_group_score(EST_ABS, static_cast<const GroupArgs *>(dtable.p), dims, c->stream));
-        HIP_TRY(launch_group_finalize_records(static_cast<const GroupArgs *>(dtable.p), dims, c->stream));
+        if (survivors) {
+            HIP_TRY(launch_group_score_count(static_cast<const GroupArgs *>(dtable.p), dims, c->stream));
+        } else {
+            HIP_TRY(launch_group_score(EST_ABS, static_cast<const GroupArgs *>(dtable.p), dims, c->stream));
+            // (the production step does not label: k_finalize2 needs dropped / not dropped alone)
+            for (size_t i = 0; i < count; ++i)
+                HIP_TRY(launch_prune_label(ha[i + 1].score, c->stream));
+            HIP_TRY(launch_group_finalize_records(static_cast<const GroupArgs *>(dtable.p), dims, c->stream));
+        }
     }
+    std::vector<std::vector<uint32_t>> part(count);
     std::vector<std::vector<uint32_t>> rank(count);
     std::vector<std::vector<uint8_t>> kept(count);
     std::vector<std::vector<RecordMeta>> meta(count);
@@ -2994,9 +3010,9 @@ int debug_score_pruned(int route, pl_debug_prune_member *m, size_t count, uint32
     for (size_t i = 0; i < count; ++i) {
         const Slot &t = slot[i + 1];
         const uint32_t H = t.s.Bl;
-        if (m[i].counts)
+        if (m[i].counts && !survivors)
             HIP_TRY(hipMemcpyAsync(m[i].counts, t.b.count, sizeof(uint32_t) * H, hipMemcpyDeviceToHost, c->stream));
-        if (m[i].scores)
+        if (m[i].scores && !survivors)
             HIP_TRY(hipMemcpyAsync(m[i].scores, t.b.score, sizeof(double) * H, hipMemcpyDeviceToHost, c->stream));
         rank[i].resize(H), kept[i].resize(H), meta[i].resize(kRecordCap);
         HIP_TRY(hipMemcpyAsync(rank[i].data(), t.b.rank, sizeof(uint32_t) * H, hipMemcpyDeviceToHost, c->stream));
@@ -3004,6 +3020,10 @@ int debug_score_pruned(int route, pl_debug_prune_member *m, size_t count, uint32
         HIP_TRY(hipMemcpyAsync(meta[i].data(), t.b.rec_meta, sizeof(RecordMeta) * kRecordCap, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipMemcpyAsync(&st[i], t.b.prune_state, sizeof(PruneState), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipMemcpyAsync(&ctl[i], t.b.ctl, sizeof(BatchCtl), hipMemcpyDeviceToHost, c->stream));
+        if (survivors) {
+            part[i].resize((size_t)t.s.chunks * ha[i + 1].score.hyp_capacity);
+            HIP_TRY(hipMemcpyAsync(part[i].data(), t.b.part_count, sizeof(uint32_t) * part[i].size(), hipMemcpyDeviceToHost, c->stream));
+        }
     }
     std::vector<uint32_t> idle(route == 2 ? slot[0].bytes / 4 : 0);
     if (!idle.empty())
@@ -3014,26 +3034,45 @@ int debug_score_pruned(int route, pl_debug_prune_member *m, size_t count, uint32
         changed += w != 0xa5a5a5a5u ? 1u : 0u;
     if (idle_changed)
         *idle_changed = changed;
+    uint32_t guard = 0;
     for (size_t i = 0; i < count; ++i) {
         const uint32_t H = slot[i + 1].s.Bl, chunks = slot[i + 1].s.chunks;
-        const bool split = st[i].cstar < chunks; // (otherwise nothing was pruned and the flags were not written)
-        if (m[i].kept)
-            for (uint32_t k = 0; k < H; ++k)
-                m[i].kept[k] = (!split || rank[i][k] == kNoRank || kept[i][rank[i][k]]) ? 1 : 0;
+        m[i].chunks = chunks;
+        m[i].chunk_points = slot[i + 1].s.point_rows / chunks;
+        m[i].num_live = ctl[i].num_live;
+        m[i].slices = route == 0 ? single_slices : ha[i + 1].slices;
+        if (survivors) { // (no lead, no selection, no finalize ran: every other field of the member stays as the caller left it)
+            const uint32_t hcap = ha[i + 1].score.hyp_capacity;
+            for (uint32_t ch = 0; ch < chunks; ++ch) {
+                for (uint32_t k = 0; k < H; ++k)
+                    survivors[i][(size_t)ch * H + k] = rank[i][k] == kNoRank ? 0u : part[i][(size_t)ch * hcap + rank[i][k]];
+                for (uint32_t p = ctl[i].num_live; p < hcap; ++p) // (debug_score_prepare fills the partials with 0xff)
+                    guard += part[i][(size_t)ch * hcap + p] != 0xffffffffu ? 1u : 0u;
+            }
+            continue;
+        }
+        const bool split = st[i].cstar < chunks; // (otherwise nothing was dropped or pruned)
+        // kept = the exact rule: the pre-selected positions that k_prune_label left alone
+        uint32_t selected = 0;
+        for (uint32_t k = 0; k < H; ++k) {
+            const bool live = rank[i][k] != kNoRank;
+            const bool kp = !split || !live || kept[i][rank[i][k]] == kKept;
+            selected += (split && live && kp) ? 1u : 0u;
+            if (m[i].kept)
+                m[i].kept[k] = kp ? 1 : 0;
+        }
         m[i].num_cand = ctl[i].num_records;
         for (uint32_t r = 0; r < std::min<uint32_t>({ctl[i].num_records, m[i].cand_cap, kRecordCap}); ++r)
             m[i].cand[r] = meta[i][r].k;
         m[i].cstar = st[i].cstar;
-        m[i].chunks = chunks;
-        m[i].chunk_points = slot[i + 1].s.point_rows / chunks;
         m[i].lead = kPruneLead;
         m[i].lead_max = st[i].lead_max;
         m[i].lead_min = st[i].lead_min;
-        m[i].num_live = ctl[i].num_live;
-        m[i].num_selected = st[i].sel_len;
-        m[i].slices = route == 0 ? single_slices : ha[i + 1].slices;
-        m[i].pad = 0;
+        m[i].num_selected = selected;
+        m[i].num_preselected = st[i].sel_len;
     }
+    if (guard_changed)
+        *guard_changed = guard;
     return PL_OK;
 }
 } // namespace
@@ -3041,6 +3080,19 @@ int pl_debug_score_pruned(int route, pl_debug_prune_member *members, size_t num_
     if (idle_changed)
         *idle_changed = 0;
     return debug_score_pruned(route, members, num_members, idle_changed);
+}
+int pl_debug_score_survivors(int route, pl_debug_prune_member *members, size_t num_members, uint32_t *const *survivors,
+                             uint32_t *idle_changed, uint32_t *guard_changed) {
+    if (idle_changed)
+        *idle_changed = 0;
+    if (guard_changed)
+        *guard_changed = 0;
+    if (!survivors)
+        return fail(PL_ERR_INVALID, "pl_debug_score_survivors: survivors missing");
+    for (size_t i = 0; i < num_members; ++i)
+        if (!survivors[i])
+            return fail(PL_ERR_INVALID, "pl_debug_score_survivors: a member without an output array");
+    return debug_score_pruned(route, members, num_members, idle_changed, survivors, guard_changed);
 }
 int pl_debug_score_prune_gate(int kind, uint32_t n_points, uint32_t iterations) {
     PrefilterArgs pf{}; // as pl_debug_group_slices: a prefilter in range is assumed

@@ -1286,12 +1286,71 @@ __device__ __forceinline__ void mfma_drain(const uint16_t *queue, uint32_t first
     }
 }
 
+// The filter of one group of 32 hypotheses against the PG point groups of a chunk (score_mfma_body and score_count_body): Aop - the
+// group's operand rows, s_b - the chunk's B operands in LDS ([0] first k block (X_hi, X_lo, 1, w), shared by the three instructions;
+// [1 + d] second k block of direction d).  out[v]: bit (PG - 1 - g) = point group g is a proven outlier of hypothesis row(v).
+template <int PG>
+__device__ __forceinline__ void abs16_tile_bits(const half8_t (&Aop)[kAbs16Dirs], const uint4 (&s_b)[1 + kAbs16Dirs][PG][32], int col, int half,
+                                                uint32_t (&out)[16]) {
+#pragma unroll
+    for (int v = 0; v < 16; ++v)
+        out[v] = 0u;
+    const float16_t kZero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    // The loop over the point groups, software-pipelined by hand: the three products of group g + 1 are issued BETWEEN the
+    // v_alignbit of group g (whose OR of sign bits sits in T), five or six vector instructions apart - an MFMA that has to
+    // wait for the matrix pipe (32 cycles per product) blocks the SIMD's vector issue for every wavefront
+    // (scripts/exp/overlap.cc), and three products back to back did that for 48 cycles per group.
+    auto products = [&](int g, float16_t &D0, float16_t &D1, float16_t &D2) {
+        half8_t Bop[kAbs16Dirs];
+#pragma unroll
+        for (int d = 0; d < kAbs16Dirs; ++d) {
+            const uint4 braw = s_b[half ? 1 + d : 0][g][col];
+            __builtin_memcpy(&Bop[d], &braw, 16);
+        }
+        D0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(Aop[0], Bop[0], kZero, 0, 0, 0);
+        D1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(Aop[1], Bop[1], kZero, 0, 0, 0);
+        D2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(Aop[2], Bop[2], kZero, 0, 0, 0);
+    };
+    float16_t D0, D1, D2;
+    products(0, D0, D1, D2);
+    // unrolled completely (PG - 1 <= 9 iterations): the LDS addresses of the operands become immediate offsets (3 of 35
+    // vector instructions per group): 131.0 -> 126.5 us per launch (unrolled 3 times: 125.9 / 129.1;
+    // profiles/r06_score_phases.md)
+#pragma unroll 16
+    for (int g = 1; g < PG; ++g) {
+        uint32_t T[16];
+#pragma unroll
+        for (int v = 0; v < 16; ++v) // proven outlier <=> one of the three signed distances is negative: OR of the sign bits (v_or3)
+            T[v] = __float_as_uint(D0[v]) | __float_as_uint(D1[v]) | __float_as_uint(D2[v]);
+        products(g, D0, D1, D2);
+#pragma unroll
+        for (int v = 0; v < 16; ++v)
+            out[v] = __builtin_amdgcn_alignbit(out[v], T[v], 31);
+        // the products of the next point group interleaved with the vector instructions of this one
+        __builtin_amdgcn_sched_group_barrier(0x002, 16, 0); // the v_or3
+        __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);  // the operands of the next group from LDS
+        __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
+    }
+#pragma unroll
+    for (int v = 0; v < 16; ++v) {
+        const uint32_t sg = __float_as_uint(D0[v]) | __float_as_uint(D1[v]) | __float_as_uint(D2[v]);
+        out[v] = __builtin_amdgcn_alignbit(out[v], sg, 31);
+    }
+}
+
 // The hypothesis stream of this kernel is the LIVE list (pipeline.hip compact2_body): `slots` = record index per live position,
 // *num_hyp_ptr = its length, shadow16 and the partials are indexed by live position; k_finalize2 maps them back (rank[]).
-// MODE (pruned scoring, PruneArgs in pl_kernels.h): kScoreAll - the stream is the whole list, today's code instruction for
-// instruction; kScoreLead - its first `lead` positions; kScoreSel - the stream is the selection `sel` (*num_hyp_ptr = its length):
-// entry i stands for the live position sel[i], one level of indirection for the operand row, the record slot and the partial column.
-constexpr int kScoreAll = 0, kScoreLead = 1, kScoreSel = 2;
+// MODE (pruned scoring, PruneArgs in pl_kernels.h): kScoreAll - the stream is the whole list (the plain launch); kScoreLead - its
+// first `lead` positions; kScoreSel - the stream is the selection `sel` (*num_hyp_ptr = its length): entry i stands for the live
+// position sel[i], one level of indirection for the operand row, the record slot and the partial column (sel == nullptr: the
+// identity); kScoreCount, kScoreCountAll - no modes of this body: score_count_body below.
+constexpr int kScoreAll = 0, kScoreLead = 1, kScoreSel = 2, kScoreCount = 3, kScoreCountAll = 4;
 template <int PG, int MODE = kScoreAll>
 __device__ __forceinline__ void score_mfma_body(const PointSet &pts, const uint4 *__restrict__ shadow16,
                                                 const uint4 *__restrict__ points16,
@@ -1360,7 +1419,7 @@ __device__ __forceinline__ void score_mfma_body(const PointSet &pts, const uint4
         // is a lane permutation of it, like the record's slot in the exact pass
         uint32_t unit_pos = 0;
         if constexpr (MODE == kScoreSel)
-            unit_pos = sel[kb + min((uint32_t)lane, gn - 1u)];
+            unit_pos = sel ? sel[kb + min((uint32_t)lane, gn - 1u)] : kb + min((uint32_t)lane, gn - 1u);
         const uint32_t unit_slots = slots[MODE == kScoreSel ? unit_pos : kb + min((uint32_t)lane, gn - 1u)]; // lane l: the record of the unit's hypothesis l
         acc_s[lane] = 0.0;
         acc_c[lane] = 0;
@@ -1397,56 +1456,7 @@ __device__ __forceinline__ void score_mfma_body(const PointSet &pts, const uint4
             if (hg + 1 < ngroups32) // next group's operands travel while this one is evaluated
                 load_a(hg + 1, Araw);
             uint32_t out[16]; // register v: bit (PG - 1 - g) = point group g is a proven outlier of hypothesis row(v)
-#pragma unroll
-            for (int v = 0; v < 16; ++v)
-                out[v] = 0u;
-            const float16_t kZero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-            // The loop over the point groups, software-pipelined by hand: the three products of group g + 1 are issued BETWEEN the
-            // v_alignbit of group g (whose OR of sign bits sits in T), five or six vector instructions apart - an MFMA that has to
-            // wait for the matrix pipe (32 cycles per product) blocks the SIMD's vector issue for every wavefront
-            // (scripts/exp/overlap.cc), and three products back to back did that for 48 cycles per group.
-            auto products = [&](int g, float16_t &D0, float16_t &D1, float16_t &D2) {
-                half8_t Bop[kAbs16Dirs];
-#pragma unroll
-                for (int d = 0; d < kAbs16Dirs; ++d) {
-                    const uint4 braw = s_b[half ? 1 + d : 0][g][col];
-                    __builtin_memcpy(&Bop[d], &braw, 16);
-                }
-                D0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(Aop[0], Bop[0], kZero, 0, 0, 0);
-                D1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(Aop[1], Bop[1], kZero, 0, 0, 0);
-                D2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(Aop[2], Bop[2], kZero, 0, 0, 0);
-            };
-            float16_t D0, D1, D2;
-            products(0, D0, D1, D2);
-            // unrolled completely (PG - 1 <= 9 iterations): the LDS addresses of the operands become immediate offsets (3 of 35
-            // vector instructions per group): 131.0 -> 126.5 us per launch (unrolled 3 times: 125.9 / 129.1;
-            // profiles/r06_score_phases.md)
-#pragma unroll 16
-            for (int g = 1; g < PG; ++g) {
-                uint32_t T[16];
-#pragma unroll
-                for (int v = 0; v < 16; ++v) // proven outlier <=> one of the three signed distances is negative: OR of the sign bits (v_or3)
-                    T[v] = __float_as_uint(D0[v]) | __float_as_uint(D1[v]) | __float_as_uint(D2[v]);
-                products(g, D0, D1, D2);
-#pragma unroll
-                for (int v = 0; v < 16; ++v)
-                    out[v] = __builtin_amdgcn_alignbit(out[v], T[v], 31);
-                // the products of the next point group interleaved with the vector instructions of this one
-                __builtin_amdgcn_sched_group_barrier(0x002, 16, 0); // the v_or3
-                __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);  // the operands of the next group from LDS
-                __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
-            }
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                const uint32_t sg = __float_as_uint(D0[v]) | __float_as_uint(D1[v]) | __float_as_uint(D2[v]);
-                out[v] = __builtin_amdgcn_alignbit(out[v], sg, 31);
-            }
+            abs16_tile_bits<PG>(Aop, s_b, col, half, out);
             // ---- expansion: register v = hypothesis rows 8 (v / 4) + v % 4 (lanes 0..31) and + 4 (lanes 32..63) ----
             // (only the last, partial group of a short unit has slots without a hypothesis: the per-lane test "slot < gn" - three
             // vector instructions per round - runs behind a SCALAR branch for that group only; round 5)
@@ -1511,6 +1521,105 @@ __device__ __forceinline__ void score_mfma_body(const PointSet &pts, const uint4
     }
 }
 
+// kScoreCount: the filter alone.  Same operands, tiles, tickets, units and (slice, chunk) placement as score_mfma_body, but behind a
+// group's tiles there is no queue and no exact pass: the survivors of hypothesis row(v) in this lane are popcount(~out[v] &
+// validbits), and the sum over the 32 lanes of a half is the hypothesis' survivor count of the chunk - an UPPER bound of its inlier
+// count there, since the filter only ever drops proven outliers.  A lane holds at most PG <= 10 per register and a 32-lane sum at
+// most 320: three counts travel in one register (10-bit fields), six registers through five DPP steps (wave_scan_u32's, without the
+// last broadcast: lanes 31 and 63 end with the totals of their halves).  survivors[chunk][position], one word per hypothesis of
+// the unit, written once per unit; positions in front of `first` are not scored.  Rows of a partial group that stand for no
+// hypothesis repeat the list's last operand row and are not written.  LDS: the B operands and one word per hypothesis of a unit.
+template <int PG>
+__device__ __forceinline__ void score_count_body(uint32_t n_points, const uint4 *__restrict__ shadow16, const uint4 *__restrict__ points16,
+                                                 const uint32_t *__restrict__ num_hyp_ptr, uint32_t hyp_capacity,
+                                                 uint32_t *__restrict__ survivors, uint32_t slice, uint32_t chunk, uint32_t nslices,
+                                                 uint32_t first) {
+    constexpr int kWaves = kMfmaThreads / 64;
+    constexpr int NPW = 32 * PG; // correspondences per chunk
+    __shared__ uint4 s_b[1 + kAbs16Dirs][PG][32];
+    __shared__ uint32_t s_cnt[kWaves][64];
+    __shared__ uint32_t s_next_unit;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int col = lane & 31, half = lane >> 5;
+    uint32_t validbits = 0; // bit (PG - 1 - g): group g holds a real correspondence in this column
+#pragma unroll
+    for (int g = 0; g < PG; ++g)
+        validbits |= (chunk * NPW + g * 32 + col < n_points) ? (1u << (PG - 1 - g)) : 0u;
+    const uint4 *const prow = points16 + (size_t)chunk * NPW * 4;
+    for (uint32_t j = threadIdx.x; j < (uint32_t)NPW; j += kMfmaThreads) {
+#pragma unroll
+        for (int r = 0; r < 1 + kAbs16Dirs; ++r)
+            s_b[r][j >> 5][j & 31] = prow[(size_t)j * 4 + r];
+    }
+    if (threadIdx.x == 0)
+        s_next_unit = 0;
+    __syncthreads(); // the only workgroup barrier
+
+    const uint32_t Hall = *as_uniform(num_hyp_ptr);
+    if (Hall <= first)
+        return;
+    const uint32_t H = Hall - first;
+    uint32_t *const cnt = s_cnt[wave];
+    const uint32_t waves_per_chunk = nslices * kWaves;
+    auto request_ticket = [&]() -> uint32_t { // per-lane value; lane 0 holds the workgroup's next unit
+        uint32_t t = 0;
+        if (lane == 0) {
+            const uint32_t k = atomicAdd(&s_next_unit, 1u);
+            t = slice * kWaves + (k % kWaves) + (k / kWaves) * waves_per_chunk;
+        }
+        return t;
+    };
+    uint32_t ticket = (uint32_t)__builtin_amdgcn_readfirstlane((int)request_ticket());
+    uint32_t kb, gn;
+    while (unit_of_ticket<32u>(ticket, H, waves_per_chunk, kb, gn)) {
+        const uint32_t pending = request_ticket(); // the next unit's index travels while this one is evaluated
+        const uint32_t ngroups32 = (gn + 31u) / 32u;
+        auto load_a = [&](uint32_t hg, uint4 (&A)[kAbs16Dirs]) {
+            const uint4 *row = shadow16 + (size_t)min(first + kb + 32u * hg + (uint32_t)col, Hall - 1u) * 4;
+#pragma unroll
+            for (int d = 0; d < kAbs16Dirs; ++d)
+                A[d] = row[half ? 3 : d];
+        };
+        uint4 Araw[kAbs16Dirs];
+        load_a(0, Araw);
+        for (uint32_t hg = 0; hg < ngroups32; ++hg) {
+            half8_t Aop[kAbs16Dirs];
+#pragma unroll
+            for (int d = 0; d < kAbs16Dirs; ++d)
+                __builtin_memcpy(&Aop[d], &Araw[d], 16);
+            if (hg + 1 < ngroups32) // next group's operands travel while this one is evaluated
+                load_a(hg + 1, Araw);
+            uint32_t out[16];
+            abs16_tile_bits<PG>(Aop, s_b, col, half, out);
+            uint32_t pk[6] = {0u, 0u, 0u, 0u, 0u, 0u}; // register v's count: field v % 3 of pk[v / 3]
+#pragma unroll
+            for (int v = 0; v < 16; ++v)
+                pk[v / 3] += (uint32_t)__popc(~out[v] & validbits) << (10 * (v % 3));
+#pragma unroll
+            for (int j = 0; j < 6; ++j) {
+                uint32_t s = pk[j];
+                s += dpp_shift_u32<0x111>(s);      // row_shr:1
+                s += dpp_shift_u32<0x112>(s);      // row_shr:2
+                s += dpp_shift_u32<0x114>(s);      // row_shr:4
+                s += dpp_shift_u32<0x118>(s);      // row_shr:8: lane 15 of every row holds the row's sum
+                s += dpp_shift_u32<0x142, 0xa>(s); // row_bcast:15 into rows 1 and 3: lanes 31 and 63 hold their half's
+                pk[j] = s;
+            }
+            if (col == 31) {
+#pragma unroll
+                for (int v = 0; v < 16; ++v) // row(v) = 8 (v / 4) + 4 half + v % 4, as in score_mfma_body's expansion
+                    cnt[hg * 32u + 8u * (uint32_t)(v >> 2) + 4u * (uint32_t)half + (uint32_t)(v & 3)] = (pk[v / 3] >> (10 * (v % 3))) & 0x3ffu;
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        if ((uint32_t)lane < gn)
+            survivors[(size_t)chunk * hyp_capacity + first + kb + lane] = cnt[lane];
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        ticket = (uint32_t)__builtin_amdgcn_readfirstlane((int)pending);
+    }
+}
+
 // amdgpu_waves_per_eu(4, 8): wavefronts per SIMD the register allocation aims at (48 accumulators + 16 bit fields + operands)
 template <int PG>
 __global__ __launch_bounds__(kMfmaThreads) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_score_mfma(PointSet pts, const uint4 *__restrict__ shadow16,
@@ -1538,34 +1647,42 @@ __global__ __launch_bounds__(kMfmaThreads) __attribute__((amdgpu_waves_per_eu(4,
     score_mfma_body<PG>(a.pts, static_cast<const uint4 *>(a.shadow16), static_cast<const uint4 *>(a.points16), a.models, a.slots,
                         a.num_hyp, a.hyp_capacity, a.thr2, a.part_count, a.part_score, slice, chunk, g.slices);
 }
-// The launches of a pruned step (a.prune.st set; launch_score_pruned, launch_group_score): the same body on the same grid of (slice,
-// chunk) workgroups, three times.  kScoreLead: the first positions of the list against every chunk - k_prune_lead turns them into the
-// split chunk c*; kScoreAll: the whole list, workgroups of the chunks from c* on return at once; kScoreSel: the selection of
-// k_prune_list, workgroups of the chunks in front of c* return at once.  c* sits in device memory, the grid is the host's: no
-// synchronisation between them.
-// Hypothesis slices per chunk of the three launches, from the slices of the plain launch: every workgroup holds a resident slot
-// (LDS) from its dispatch on, also one that finds no unit or returns at once.  The lead has 32 units of 64 hypotheses per chunk -
-// two workgroups of 8 wavefronts; phase B has the lead and the few per cent that were kept, on a quarter of the chunks: a quarter
-// of the slices (measured on the flagship groups with the plain launch's grid for all three: lead 0.81 ms and phase B 0.98 ms in
-// flight next to 2.46 ms of phase A - profiles/score_prune.md).  Which wavefront scores a unit has no influence on its result.
+// The scorer launches of a pruned step (a.prune.st set; launch_score_pruned, launch_group_score), on grids of (slice, chunk)
+// workgroups.  kScoreLead: the first positions of the list against every chunk - k_prune_lead turns them into the split chunk c*;
+// kScoreCount: the positions behind the lead against the chunks [0, c*), survivor counts only (score_count_body) - workgroups of the
+// chunks from c* on return at once, and all of them when c* = chunks: nothing can be dropped then; kScoreSel: the pre-selection of
+// k_prune_list against EVERY chunk, the exact scorer.  c* sits in device memory, the grid is the host's: no synchronisation between
+// them.  A member of a group's table whose step does not prune (prune.st == nullptr) is scored by the kScoreSel launch alone: its
+// whole list, every chunk.
+// Hypothesis slices per chunk of the launches, from the slices of the plain launch: every workgroup of the exact scorer holds a
+// resident slot (55 KB of LDS) from its dispatch on, also one that finds no unit or returns at once.  The lead has 32 units of 64
+// hypotheses per chunk - two workgroups of 8 wavefronts; the exact launch has the lead and the few per cent that the counts could not
+// exclude: a quarter of the slices (profiles/score_prune.md, profiles/score_count.md).  Which wavefront scores a unit has no
+// influence on its result.
 template <int MODE> __host__ __device__ constexpr uint32_t pruned_slices(uint32_t slices) {
     return MODE == kScoreLead ? (slices < 2u ? slices : 2u) : MODE == kScoreSel ? (slices + 3u) / 4u : slices;
 }
 template <int PG, int MODE> __device__ __forceinline__ void score_mfma_pruned(const ScoreArgs &a, uint32_t slice, uint32_t chunk, uint32_t nslices) {
+    static_assert(MODE == kScoreLead || MODE == kScoreSel || MODE == kScoreCount || MODE == kScoreCountAll, "the plain launch is k_score_mfma's");
     const PruneArgs &pr = a.prune;
-    const uint32_t *len = a.num_hyp;
-    if (!pr.st) { // (a member of a group's table whose step does not prune: the kScoreAll launch alone, every chunk)
-        if (MODE != kScoreAll)
-            return;
-    } else if constexpr (MODE != kScoreLead) {
+    if (!pr.st && MODE != kScoreSel)
+        return;
+    if constexpr (MODE == kScoreCountAll) { // (pl_debug_score_survivors alone: the whole list against every chunk)
+        score_count_body<PG>(a.pts.n, static_cast<const uint4 *>(a.shadow16), static_cast<const uint4 *>(a.points16), a.num_hyp,
+                             a.hyp_capacity, a.part_count, slice, chunk, nslices, 0u);
+    } else if constexpr (MODE == kScoreCount) {
         const uint32_t cstar = *as_uniform(&pr.st->cstar);
-        if (MODE == kScoreAll ? chunk >= cstar : chunk < cstar)
+        if (cstar >= pr.chunks || chunk >= cstar)
             return;
+        score_count_body<PG>(a.pts.n, static_cast<const uint4 *>(a.shadow16), static_cast<const uint4 *>(a.points16), a.num_hyp,
+                             a.hyp_capacity, a.part_count, slice, chunk, nslices, pr.lead);
+    } else {
+        // (kScoreSel without a selection: the identity, the whole live list)
+        const uint32_t *len = MODE == kScoreSel && pr.st ? &pr.st->sel_len : a.num_hyp;
+        score_mfma_body<PG, MODE>(a.pts, static_cast<const uint4 *>(a.shadow16), static_cast<const uint4 *>(a.points16), a.models, a.slots,
+                                  len, a.hyp_capacity, a.thr2, a.part_count, a.part_score, slice, chunk, nslices, pr.st ? pr.sel : nullptr,
+                                  pr.lead);
     }
-    if constexpr (MODE == kScoreSel)
-        len = &pr.st->sel_len;
-    score_mfma_body<PG, MODE>(a.pts, static_cast<const uint4 *>(a.shadow16), static_cast<const uint4 *>(a.points16), a.models, a.slots,
-                              len, a.hyp_capacity, a.thr2, a.part_count, a.part_score, slice, chunk, nslices, pr.sel, pr.lead);
 }
 template <int PG, int MODE>
 __global__ __launch_bounds__(kMfmaThreads) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_score_mfma_pr(ScoreArgs a) {
@@ -1577,7 +1694,6 @@ template <int PG, int MODE>
 __global__ __launch_bounds__(kMfmaThreads) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_score_mfma_pr_g(const GroupArgs *ga) {
     const GroupArgs &g = ga[blockIdx.z];
     uint32_t slice, chunk;
-    // (a member whose step does not prune takes part in the kScoreAll launch alone: its own slices)
     const uint32_t ns = pruned_slices<MODE>(g.slices);
     if (!g.active || !g.use_mfma || !slice_chunk_of_workgroup(ns, g.chunks, slice, chunk))
         return;
@@ -1645,14 +1761,36 @@ __global__ __launch_bounds__(256) void k_prune_lead_g(const GroupArgs *ga) {
     prune_lead_body(globalised(g.score));
 }
 
-// kept or pruned, for the live position p of a tile of 1024 (one thread each): phase A left the partials of the chunks [0, c*),
-// S correspondences.  Lead positions are kept.
+// The exact pruning rule: a hypothesis that has seen the S correspondences of the chunks [0, c*) with cs inliers, residuals summing
+// to `sum`, ends with a count <= cs + (N - S) and a score >= sum + (S - cs) thr^2; it is no candidate of k_records if neither can
+// beat the lead's.
+__device__ __forceinline__ bool prune_rule(uint32_t cs, double sum, uint32_t S, uint32_t N, double thr2, const PruneState &st) {
+    return cs + (N - S) <= st.lead_max && sum + (double)(S - cs) * thr2 > st.lead_min * (1.0 + kPruneScoreMargin);
+}
+// Pre-selection, for the live position p of a tile of 1024 (one thread each): the count launch left the SURVIVORS cs' of the chunks
+// [0, c*) in the count column.  The filter drops proven outliers only, so cs' >= cs, and sum r^2 >= 0: cs + (N - S) <= cs' + (N - S)
+// and sum + (S - cs) thr^2 >= (S - cs') thr^2 - a position the rule drops on (cs', 0) is one it prunes on the exact (cs, sum).
+// Lead positions are selected; with c* = chunks (no count launch) every position is.
 __device__ __forceinline__ uint32_t prune_keeps(const ScoreArgs &a, uint32_t p, uint32_t H, uint32_t cstar) {
     const PruneArgs &pr = a.prune;
     if (p >= H)
         return 0u;
-    if (p < pr.lead)
+    if (p < pr.lead || cstar >= pr.chunks)
         return 1u;
+    const uint32_t N = a.pts.n, S = min(cstar * pr.chunk_points, N);
+    uint32_t cs = 0;
+    for (uint32_t ch = 0; ch < cstar; ++ch)
+        cs += a.part_count[(size_t)ch * a.hyp_capacity + p];
+    return prune_rule(cs, 0.0, S, N, a.thr2, *pr.st) ? 0u : 1u;
+}
+// Diagnostic (pl_debug_score_pruned), behind the exact launch: the pre-selected positions behind the lead hold exact partials of
+// every chunk; those the exact rule prunes on their chunks [0, c*) are labelled kPrunedExact.  k_finalize2 treats every non-zero
+// label alike.
+__global__ __launch_bounds__(256) void k_prune_label(ScoreArgs a) {
+    const PruneArgs &pr = a.prune;
+    const uint32_t H = *a.num_hyp, cstar = pr.st->cstar, p = blockIdx.x * 256u + threadIdx.x;
+    if (p >= H || p < pr.lead || cstar >= pr.chunks || pr.kept[p] != kKept)
+        return;
     const uint32_t N = a.pts.n, S = min(cstar * pr.chunk_points, N);
     uint32_t cs = 0;
     double sum = 0.0;
@@ -1660,8 +1798,8 @@ __device__ __forceinline__ uint32_t prune_keeps(const ScoreArgs &a, uint32_t p, 
         cs += a.part_count[(size_t)ch * a.hyp_capacity + p];
         sum += a.part_score[(size_t)ch * a.hyp_capacity + p];
     }
-    const bool pruned = cs + (N - S) <= pr.st->lead_max && sum + (double)(S - cs) * a.thr2 > pr.st->lead_min * (1.0 + kPruneScoreMargin);
-    return pruned ? 0u : 1u;
+    if (prune_rule(cs, sum, S, N, a.thr2, *pr.st))
+        pr.kept[p] = kPrunedExact;
 }
 // Two passes over the live list, a workgroup per tile of 1024 positions, no atomics (as k_compact2: totals per tile first, then
 // every tile starts at the sum of the tiles in front of it): flags and tile totals, then the ascending list of the kept positions.
@@ -1669,7 +1807,7 @@ __device__ __forceinline__ void prune_flags_body(const ScoreArgs &a) {
     __shared__ uint32_t wt[16];
     const PruneArgs &pr = a.prune;
     const uint32_t H = *a.num_hyp, cstar = pr.st->cstar;
-    if (cstar >= pr.chunks || blockIdx.x * 1024u >= H) // nothing is pruned: the list stays empty and the flags unread
+    if (blockIdx.x * 1024u >= H)
         return;
     const uint32_t p = blockIdx.x * 1024u + threadIdx.x;
     const uint32_t keep = prune_keeps(a, p, H, cstar);
@@ -1689,8 +1827,8 @@ __device__ __forceinline__ void prune_flags_body(const ScoreArgs &a) {
 __device__ __forceinline__ void prune_list_body(const ScoreArgs &a) {
     __shared__ uint32_t wt[16], wb[16];
     const PruneArgs &pr = a.prune;
-    const uint32_t H = *a.num_hyp, cstar = pr.st->cstar;
-    if (cstar >= pr.chunks || blockIdx.x * 1024u >= H)
+    const uint32_t H = *a.num_hyp;
+    if (blockIdx.x * 1024u >= H)
         return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint32_t before = 0;
@@ -4031,7 +4169,7 @@ hipError_t launch_group_prune_select(const GroupArgs *args, const GroupDims &d, 
     return hipGetLastError();
 }
 // The pruned form of the matrix-core absolute-pose launch (a.prune set by wire_batch_step: at least three chunks, i.e. 4 or 5
-// points per lane): the grid of launch_score_est, lead -> c* -> phase A -> selection -> phase B.
+// points per lane): the grid of launch_score_est, lead -> c* -> survivor counts -> pre-selection -> exact scores.
 template <int PG> static hipError_t launch_score_pruned_pg(const ScoreArgs &a, dim3 grid, hipStream_t stream) {
     const dim3 block(kMfmaThreads);
     const dim3 lead_grid(pruned_slices<kScoreLead>(grid.x), grid.y), sel_grid(pruned_slices<kScoreSel>(grid.x), grid.y);
@@ -4039,27 +4177,47 @@ template <int PG> static hipError_t launch_score_pruned_pg(const ScoreArgs &a, d
     hipError_t e = launch_prune_lead(a, stream);
     if (e != hipSuccess)
         return e;
-    k_score_mfma_pr<PG, kScoreAll><<<grid, block, 0, stream>>>(a);
+    k_score_mfma_pr<PG, kScoreCount><<<grid, block, 0, stream>>>(a);
     e = launch_prune_select(a, stream);
     if (e != hipSuccess)
         return e;
     k_score_mfma_pr<PG, kScoreSel><<<sel_grid, block, 0, stream>>>(a);
     return hipGetLastError();
 }
-hipError_t launch_score_pruned(const ScoreArgs &a, uint32_t slices, hipStream_t stream) {
+static hipError_t pruned_grid(const ScoreArgs &a, uint32_t slices, dim3 &grid, int &P) {
     uint32_t chunks;
-    int P;
     score_shape(EST_ABS, a.pts.n, true, true, chunks, P);
     if (!a.shadow16 || !a.points16 || !a.prune.st || a.prune.chunks != chunks || a.prune.chunk_points != 64u * (uint32_t)P)
         return hipErrorInvalidValue;
     const uint32_t mslices = std::min<uint32_t>(slices * (uint32_t)kScoreThreads / (uint32_t)kMfmaThreads,
                                                 score_slice_limit(EST_ABS, chunks, true));
-    const dim3 grid(xcd_slices(mslices), chunks);
+    grid = dim3(xcd_slices(mslices), chunks);
+    return (P == 4 || P == 5) ? hipSuccess : hipErrorInvalidValue; // (fewer points per lane: fewer than three chunks, such steps do not prune)
+}
+hipError_t launch_score_pruned(const ScoreArgs &a, uint32_t slices, hipStream_t stream) {
+    dim3 grid;
+    int P;
+    const hipError_t e = pruned_grid(a, slices, grid, P);
+    if (e != hipSuccess)
+        return e;
+    return P == 4 ? launch_score_pruned_pg<8>(a, grid, stream) : launch_score_pruned_pg<10>(a, grid, stream);
+}
+// the filter alone over the whole list and every chunk (pl_debug_score_survivors: kScoreCountAll), on launch_score_pruned's grid
+hipError_t launch_score_count(const ScoreArgs &a, uint32_t slices, hipStream_t stream) {
+    dim3 grid;
+    int P;
+    const hipError_t e = pruned_grid(a, slices, grid, P);
+    if (e != hipSuccess)
+        return e;
     if (P == 4)
-        return launch_score_pruned_pg<8>(a, grid, stream);
-    if (P == 5)
-        return launch_score_pruned_pg<10>(a, grid, stream);
-    return hipErrorInvalidValue; // (fewer points per lane: fewer than three chunks, such steps do not prune)
+        k_score_mfma_pr<8, kScoreCountAll><<<grid, dim3(kMfmaThreads), 0, stream>>>(a);
+    else
+        k_score_mfma_pr<10, kScoreCountAll><<<grid, dim3(kMfmaThreads), 0, stream>>>(a);
+    return hipGetLastError();
+}
+hipError_t launch_prune_label(const ScoreArgs &a, hipStream_t stream) {
+    k_prune_label<<<dim3(std::max<uint32_t>(1u, (a.hyp_capacity + 255u) / 256u)), dim3(256), 0, stream>>>(a);
+    return hipGetLastError();
 }
 
 hipError_t launch_score(int est, const ScoreArgs &a, uint32_t slices, hipStream_t stream) {
@@ -4244,13 +4402,13 @@ int group_points_per_lane(int est) { return (est == EST_REL || est == EST_FUND) 
 template <int E> static hipError_t launch_group_score_est(const GroupArgs *args, const GroupDims &d, hipStream_t stream) {
     const dim3 grid(std::max<uint32_t>(1u, d.max_slices), std::max<uint32_t>(1u, d.max_chunks), d.G);
     if constexpr (E == EST_ABS) {
-        if (d.any_mfma && d.any_prune) { // lead -> c* -> phase A -> selection -> phase B (k_score_mfma_pr)
+        if (d.any_mfma && d.any_prune) { // lead -> c* -> survivor counts -> pre-selection -> exact scores (k_score_mfma_pr)
             const dim3 lead_grid(pruned_slices<kScoreLead>(grid.x), grid.y, grid.z), sel_grid(pruned_slices<kScoreSel>(grid.x), grid.y, grid.z);
             k_score_mfma_pr_g<10, kScoreLead><<<lead_grid, dim3(kMfmaThreads), 0, stream>>>(args);
             hipError_t e = launch_group_prune_lead(args, d, stream);
             if (e != hipSuccess)
                 return e;
-            k_score_mfma_pr_g<10, kScoreAll><<<grid, dim3(kMfmaThreads), 0, stream>>>(args);
+            k_score_mfma_pr_g<10, kScoreCount><<<grid, dim3(kMfmaThreads), 0, stream>>>(args);
             e = launch_group_prune_select(args, d, stream);
             if (e != hipSuccess)
                 return e;
@@ -4275,6 +4433,12 @@ template <int E> static hipError_t launch_group_score_est(const GroupArgs *args,
     return hipGetLastError();
 }
 
+// the same for a group's table, on launch_group_score's grid
+hipError_t launch_group_score_count(const GroupArgs *args, const GroupDims &d, hipStream_t stream) {
+    const dim3 grid(std::max<uint32_t>(1u, d.max_slices), std::max<uint32_t>(1u, d.max_chunks), d.G);
+    k_score_mfma_pr_g<10, kScoreCountAll><<<grid, dim3(kMfmaThreads), 0, stream>>>(args);
+    return hipGetLastError();
+}
 // the scorers of every active problem of the table (launch_group_batch and the diagnostic entry pl_debug_score_stream_ex)
 hipError_t launch_group_score(int est, const GroupArgs *args, const GroupDims &d, hipStream_t stream) {
     if (d.G == 0)

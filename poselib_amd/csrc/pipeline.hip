@@ -615,22 +615,17 @@ __device__ __forceinline__ void finalize2_body(const FinalizeArgs &f, uint32_t *
     const uint32_t k0 = min(H, blockIdx.x * per), k1 = min(H, k0 + per);
     uint32_t bmax = 0;
     double bmin = 1.7976931348623157e308;
-    // pruned step: a pruned position holds the partials of the chunks in front of c* only.  What it has not seen counts as
-    // outliers below - the bound it was pruned by -, so its values stay dominated by the lead's and k_records' running scan
-    // sees what it would have seen (c* = chunks: nothing was pruned, the flags were not written)
-    const uint32_t cstar = f.prune ? min(f.prune->cstar, f.chunks) : f.chunks;
+    // pruned step: a position the survivor counts dropped has no partials - its count column holds those counts, never inlier
+    // counts, its score column an earlier step's values - and reports no inliers: the bits of an all-outlier row, like a NaN
+    // model's.  Its true values are dominated by the lead's (the bound it was dropped by), so k_records' running scan decides
+    // what it would have decided.  Every other position holds this step's exact partials of every chunk
     for (uint32_t k = k0 + threadIdx.x; k < k1; k += 256) {
         uint32_t c = 0;
         double s = 0.0;
         // column of the hypothesis' partials: k, or its position in the live list.  A NaN model has none: no inliers, i.e.
         // count 0 and score n thr^2, the very bits the scorer's all-outlier row gave
         const uint32_t col = f.rank ? f.rank[k] : k;
-        if (col != kNoRank && cstar < f.chunks && !f.kept[col]) {
-            for (uint32_t ch = 0; ch < cstar; ++ch) {
-                c += f.part_count[(size_t)ch * f.hyp_capacity + col];
-                s += f.part_score[(size_t)ch * f.hyp_capacity + col];
-            }
-        } else if (col != kNoRank)
+        if (col != kNoRank && !(f.kept && f.kept[col] == kDropped))
             for (uint32_t ch = 0; ch < f.chunks; ++ch) {
                 c += f.part_count[(size_t)ch * f.hyp_capacity + col];
                 s += f.part_score[(size_t)ch * f.hyp_capacity + col];

@@ -93,7 +93,6 @@ __device__ __forceinline__ FinalizeArgs globalised(FinalizeArgs f) {
     f.count = as_global(f.count);
     f.score = as_global(f.score);
     f.kept = as_global(f.kept);
-    f.prune = as_global(f.prune);
     return f;
 }
 __device__ __forceinline__ RecordsArgs globalised(RecordsArgs r) {

@@ -56,9 +56,9 @@ struct GenerateArgs {
     void *stage = nullptr;     // relative pose: workspace of generate_stage_bytes(); nullptr = single-kernel generator
 };
 
-// ---- k_score_mfma with pruning: hypotheses that provably cannot become candidates of k_records are scored
-// against the first c* chunks of correspondences only.  lead -> (lead_max, lead_min, c*) -> phase A (whole live list, chunks
-// [0, c*)) -> selection of the kept positions -> phase B (selection, chunks [c*, chunks)).
+// ---- k_score_mfma with pruning: hypotheses that provably cannot become candidates of k_records are not
+// scored exactly at all.  lead -> (lead_max, lead_min, c*) -> survivor counts of the matrix-core filter (the list behind the lead,
+// chunks [0, c*)) -> pre-selection of the positions the counts cannot exclude -> exact scores (pre-selection, every chunk).
 constexpr uint32_t kPruneLead = 2048;   // live positions scored against every chunk first (a prefix of the hypothesis order)
 constexpr uint32_t kPruneMargin = 32;   // correspondences added to the bound that places c*
 constexpr double kPruneScoreMargin = 1e-6; // relative margin of the score test (k_records compares with 1e-9)
@@ -73,11 +73,13 @@ struct PruneArgs {
     PruneState *st = nullptr;  // nullptr: the step scores every live hypothesis against every chunk
     uint32_t *blk_kept = nullptr; // [ceil(hyp_capacity / 1024)] kept positions per tile of 1024 live positions
     uint32_t *sel = nullptr;   // [hyp_capacity] kept live positions, ascending
-    uint8_t *kept = nullptr;   // [hyp_capacity] per live position: 1 kept, 0 pruned (written only where c* < chunks)
+    uint8_t *kept = nullptr;   // [hyp_capacity] per live position: kDropped - no exact partials, kKept - pre-selected: exact
+                               // partials of every chunk; kPrunedExact: pl_debug_score_pruned's label, see k_prune_label
     uint32_t chunks = 0, chunk_points = 0; // the launch's chunks of correspondences and the correspondences of one
     uint32_t init_max = 0, lead = 0;   // what a candidate has to beat (RecordsArgs.init_max / init_min); lead length
     double init_min = 0.0;
 };
+constexpr uint8_t kDropped = 0, kKept = 1, kPrunedExact = 2;
 
 struct ScoreArgs {
     PointSet pts;
@@ -112,10 +114,9 @@ struct FinalizeArgs {
     const double *part_score;
     uint32_t *count; // [hyp_capacity]
     double *score;   // [hyp_capacity]
-    // pruned step (PruneArgs): a live position with kept[] == 0 has partials of the chunks [0, *cstar) only; its unseen
-    // correspondences count as outliers.  nullptr: every column holds all chunks
+    // pruned step (PruneArgs): a live position with kept[] == kDropped has no partials (its count column holds survivor counts
+    // or an earlier step's values) and reports no inliers.  nullptr: every column holds all chunks
     const uint8_t *kept = nullptr;
-    const PruneState *prune = nullptr;
 };
 
 struct LMTask {
@@ -289,9 +290,12 @@ int score_points_per_lane(int est, uint32_t n_points, bool streaming, bool mfma)
 uint32_t score_slice_limit(int est, uint32_t chunks, bool mfma);
 // slices: workgroups of kScoreThreads per chunk; the streaming kernels run 8 wavefronts per workgroup, i.e. slices / 2 of them
 hipError_t launch_score(int est, const ScoreArgs &a, uint32_t slices, hipStream_t stream);
-// absolute pose on the matrix cores with a.prune set: lead, phase A, selection, phase B; launch_prune_lead / launch_prune_select
+// absolute pose on the matrix cores with a.prune set: lead, survivor counts, pre-selection, exact scores; launch_prune_lead / launch_prune_select
 // are the two small steps between the scorer launches
 hipError_t launch_score_pruned(const ScoreArgs &a, uint32_t slices, hipStream_t stream);
+// diagnostic entries: the filter's counts alone, whole list and every chunk, and the exact rule's label of the pre-selected positions
+hipError_t launch_score_count(const ScoreArgs &a, uint32_t slices, hipStream_t stream);
+hipError_t launch_prune_label(const ScoreArgs &a, hipStream_t stream);
 hipError_t launch_prune_lead(const ScoreArgs &a, hipStream_t stream);
 hipError_t launch_prune_select(const ScoreArgs &a, hipStream_t stream);
 int tangent_score_chunk(); // correspondences per chunk of k_score_tangent (EST_RELT)
@@ -434,7 +438,7 @@ struct GroupDims { // grid extents: maxima over the active problems of the group
     uint32_t max_hcap;   // hypothesis slots
     uint32_t max_chunks, max_slices;
     uint32_t any_mfma, any_queue;
-    uint32_t any_prune;  // a member's matrix-core scorer prunes (ScoreArgs.prune.st): the step launches lead, selection and phase B
+    uint32_t any_prune;  // a member's matrix-core scorer prunes (ScoreArgs.prune.st): the step launches lead, counts, pre-selection and exact scores
     int P;               // points per lane of the scorers (chunk = 64 P correspondences)
 };
 // positions -> generate -> compact/gather(/fp16 operands) -> score -> finalize/records -> candidates re-scored: the
@@ -448,6 +452,7 @@ hipError_t launch_group_score(int est, const GroupArgs *args, const GroupDims &d
 // ... and the two small steps between the scorer launches of a pruned step (d.any_prune; launch_prune_lead / launch_prune_select)
 hipError_t launch_group_prune_lead(const GroupArgs *args, const GroupDims &d, hipStream_t stream);
 hipError_t launch_group_prune_select(const GroupArgs *args, const GroupDims &d, hipStream_t stream);
+hipError_t launch_group_score_count(const GroupArgs *args, const GroupDims &d, hipStream_t stream);
 hipError_t launch_group_score_seq(int est, const SeqScoreArgs *args, uint32_t G, uint32_t max_cap, hipStream_t stream);
 hipError_t launch_group_select(const SelectArgs *args, uint32_t G, hipStream_t stream);
 hipError_t launch_group_mask(int est, const MaskArgs *args, uint32_t G, uint32_t max_n, hipStream_t stream);
