@@ -558,6 +558,21 @@ int pl_debug_score_pruned(int route, pl_debug_prune_member *members, size_t num_
  * launch changed - which must be 0. */
 int pl_debug_score_survivors(int route, pl_debug_prune_member *members, size_t num_members, uint32_t *const *survivors,
                              uint32_t *idle_changed, uint32_t *guard_changed);
+/* Diagnostic: the pruned form as a batch step of a group launches it - pl_debug_score_pruned's sequence with the BOUND TIER between
+ * pre-selection and exact scores, the lead left out of the exact launch, and no labels.  Members and routes as pl_debug_score_pruned.
+ * Per member i and hypothesis k:
+ *   bound_counts[i][k], bound_scores[i][k]   the tier's upper bound of the inlier count and lower bound of the score, for a
+ *                    pre-selected position behind the lead - those of the last of the tier's two stages that saw it (the filter's
+ *                    verdict, then residual bounds for what the verdict leaves undecided); 0xffffffff / NaN for every other hypothesis, and for all when the tier
+ *                    does not run (cstar == chunks)
+ *   tiers[i][k]      0: exact scores (the lead, and what both tiers kept); 1: dropped on its survivor count; 2: dropped on its
+ *                    bounds; 3: NaN model, never scored
+ *   counts / scores / cand as pl_debug_score_pruned - a dropped position reports count 0, score n thr^2; kept: tiers == 0 or 3;
+ *                    num_selected: live hypotheses with exact scores; num_preselected: the entries the exact launch scored (without
+ *                    the lead when the tier ran).
+ * guard_changed: words of the count columns behind the live list's end that the launches changed - which must be 0. */
+int pl_debug_score_bounded(int route, pl_debug_prune_member *members, size_t num_members, uint32_t *const *bound_counts,
+                           double *const *bound_scores, uint8_t *const *tiers, uint32_t *idle_changed, uint32_t *guard_changed);
 /* Diagnostic: 1 if a batch step of `iterations` iterations of a problem of `kind` with n_points correspondences, as a member of a
  * lock-step group (pl_ransac_batch, pl_estimate_batch), scores in the pruned form, 0 if not; pl_ransac_run's own steps never do (coordinates and threshold in the pre-filter's range assumed, as pl_debug_group_slices).  Host arithmetic only. */
 int pl_debug_score_prune_gate(int kind, uint32_t n_points, uint32_t iterations);

@@ -741,6 +741,40 @@ def score_survivors(members, route=0):
     return out, idle.value, guard.value
 
 
+def score_bounded(members, route=0):
+    """Diagnostic (pl_debug_score_bounded): the pruned scorer as a group's batch step runs it, bound tier included, on caller-given
+    lists.  members and routes as score_pruned.  Returns ([score_pruned's fields and "bound_counts", "bound_scores", "tiers" per
+    member], words changed in the inactive slot, words changed behind the live lists' ends - both must be 0)."""
+    arr = (L.DebugPruneMember * max(len(members), 1))()
+    bcs, bss, trs = ((C.c_void_p * max(len(members), 1))() for _ in range(3))
+    keep = []
+    cap = 4096
+    for i, (problem, models, max_error, init_max, init_min) in enumerate(members):
+        n, flat = problem._flat_models(models)
+        cnt = np.zeros(max(n, 1), dtype=np.uint32)
+        sc = np.zeros(max(n, 1), dtype=np.float64)
+        kp = np.zeros(max(n, 1), dtype=np.uint8)
+        cand = np.zeros(cap, dtype=np.uint32)
+        bc = np.zeros(max(n, 1), dtype=np.uint32)
+        bs = np.zeros(max(n, 1), dtype=np.float64)
+        tr = np.zeros(max(n, 1), dtype=np.uint8)
+        keep.append((n, flat, cnt, sc, kp, cand, bc, bs, tr))
+        arr[i] = L.DebugPruneMember(problem._h, _ptr(flat), n, float(max_error), float(init_min), int(init_max), cap, _ptr(cnt),
+                                    _ptr(sc), _ptr(kp), _ptr(cand))
+        bcs[i], bss[i], trs[i] = bc.ctypes.data, bs.ctypes.data, tr.ctypes.data
+    idle, guard = C.c_uint32(0), C.c_uint32(0)
+    L.check(L.lib().pl_debug_score_bounded(int(route), arr, C.c_size_t(len(members)), bcs, bss, trs, C.byref(idle), C.byref(guard)))
+    out = []
+    for i, (n, _, cnt, sc, kp, cand, bc, bs, tr) in enumerate(keep):
+        a = arr[i]
+        out.append({"counts": cnt[:n], "scores": sc[:n], "kept": kp[:n].astype(bool), "cand": cand[:min(a.num_cand, cap)].copy(),
+                    "num_cand": a.num_cand, "cstar": a.cstar, "chunks": a.chunks, "chunk_points": a.chunk_points, "lead": a.lead,
+                    "lead_max": a.lead_max, "lead_min": a.lead_min, "num_live": a.num_live, "num_selected": a.num_selected,
+                    "num_preselected": a.num_preselected, "slices": a.slices, "bound_counts": bc[:n], "bound_scores": bs[:n],
+                    "tiers": tr[:n]})
+    return out, idle.value, guard.value
+
+
 def ransac_batch(problems, opts, max_in_flight=4, group_size=16):
     """Many device-resident problems in one call (pl_ransac_batch): results of `problems[i].run(opts[i])`, bit for bit.
     Problems of the same kind advance in lock-step groups of `group_size` through one launch sequence."""

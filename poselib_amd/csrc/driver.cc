@@ -699,6 +699,7 @@ void wire_batch_step(GroupArgs &a, const BatchRun &r, const BatchShape &s, const
         pa.chunk_points = s.point_rows / s.chunks;
         pa.init_max = r.init_max, pa.init_min = r.init_min;
         pa.lead = kPruneLead;
+        pa.bound = 1;
     }
     // finalize + records
     RecordsArgs &ra = a.rec;
@@ -2872,8 +2873,15 @@ int debug_score_group(pl_debug_score_member *m, size_t count, uint32_t *idle_cha
 // the group's chunk shape.  Every slot has an arena of its own, as in debug_score_group.
 // survivors (pl_debug_score_survivors): the count launch alone, over the whole list and every chunk; survivors[i] takes member i's
 // [chunks][n] counts (hypothesis order, a NaN model reports 0), *guard_changed the words behind the live list's end that changed.
+// bounded (pl_debug_score_bounded): the production sequence, bound tier included (PruneArgs.bound), no labels; per hypothesis the
+// tier's bounds (no bound: 0xffffffff / NaN) and what became of it.
+struct DebugBoundedOut {
+    uint32_t *const *bound_counts;
+    double *const *bound_scores;
+    uint8_t *const *tiers;
+};
 int debug_score_pruned(int route, pl_debug_prune_member *m, size_t count, uint32_t *idle_changed, uint32_t *const *survivors = nullptr,
-                       uint32_t *guard_changed = nullptr) {
+                       uint32_t *guard_changed = nullptr, const DebugBoundedOut *bounded = nullptr) {
     if (route != 0 && route != 2)
         return fail(PL_ERR_INVALID, "route: 0 single launch, 2 group form");
     if (!m || count == 0 || count > (route == 0 ? 1 : kDebugScoreMembers))
@@ -2911,7 +2919,7 @@ int debug_score_pruned(int route, pl_debug_prune_member *m, size_t count, uint32
             if (p)
                 (void)hipFree(p);
         }
-    } dtable;
+    } dtable, dbound[kDebugScoreMembers];
     GroupArgs ha[1 + kDebugScoreMembers];
     GroupDims dims{};
     dims.G = (uint32_t)count + 1;
@@ -2952,6 +2960,14 @@ int debug_score_pruned(int route, pl_debug_prune_member *m, size_t count, uint32
         t.b.nan_bits = nullptr; // (no generator: k_live_list reads the records' flag words)
         t.b.host_meta = nullptr, t.b.host_models = nullptr, t.b.host_ctl = nullptr;
         wire_batch_step(ha[k], t.run, t.s, t.b);
+        ha[k].score.prune.bound = bounded ? 1u : 0u;
+        if (bounded && k > 0) { // the tier's sums per live position: scores, then count words; 0xff = none written
+            const size_t hcap = ha[k].score.hyp_capacity;
+            HIP_TRY(hipMalloc(&dbound[k - 1].p, hcap * 16));
+            HIP_TRY(hipMemsetAsync(dbound[k - 1].p, 0xff, hcap * 16, c->stream));
+            ha[k].score.prune.bnd_score = static_cast<double *>(dbound[k - 1].p);
+            ha[k].score.prune.bnd_count = reinterpret_cast<uint32_t *>(ha[k].score.prune.bnd_score + hcap);
+        }
     }
     ha[0].active = 0;
     for (size_t i = 0; i < count; ++i) {
@@ -2964,6 +2980,7 @@ int debug_score_pruned(int route, pl_debug_prune_member *m, size_t count, uint32
         dims.max_chunks = std::max(dims.max_chunks, a.chunks);
         dims.max_slices = std::max(dims.max_slices, a.slices);
         dims.any_mfma = dims.any_prune = 1;
+        dims.any_bound = bounded ? 1u : 0u;
         std::vector<double> recs;
         std::vector<uint32_t> ident(H);
         for (uint32_t k = 0; k < H; ++k)
@@ -2984,7 +3001,8 @@ int debug_score_pruned(int route, pl_debug_prune_member *m, size_t count, uint32
             HIP_TRY(launch_score_count(a.score, slices, c->stream));
         } else {
             HIP_TRY(launch_score_pruned(a.score, slices, c->stream));
-            HIP_TRY(launch_prune_label(a.score, c->stream));
+            if (!bounded)
+                HIP_TRY(launch_prune_label(a.score, c->stream));
             HIP_TRY(launch_finalize_records(a.rec, c->stream));
         }
     } else {
@@ -2996,7 +3014,7 @@ int debug_score_pruned(int route, pl_debug_prune_member *m, size_t count, uint32
         } else {
             HIP_TRY(launch_group_score(EST_ABS, static_cast<const GroupArgs *>(dtable.p), dims, c->stream));
             // (the production step does not label: k_finalize2 needs dropped / not dropped alone)
-            for (size_t i = 0; i < count; ++i)
+            for (size_t i = 0; i < count && !bounded; ++i)
                 HIP_TRY(launch_prune_label(ha[i + 1].score, c->stream));
             HIP_TRY(launch_group_finalize_records(static_cast<const GroupArgs *>(dtable.p), dims, c->stream));
         }
@@ -3007,9 +3025,17 @@ int debug_score_pruned(int route, pl_debug_prune_member *m, size_t count, uint32
     std::vector<std::vector<RecordMeta>> meta(count);
     std::vector<PruneState> st(count);
     std::vector<BatchCtl> ctl(count);
+    std::vector<std::vector<uint32_t>> bcount(count);
+    std::vector<std::vector<double>> bscore(count);
     for (size_t i = 0; i < count; ++i) {
         const Slot &t = slot[i + 1];
         const uint32_t H = t.s.Bl;
+        if (bounded) {
+            const size_t hcap = ha[i + 1].score.hyp_capacity;
+            bcount[i].resize(hcap), bscore[i].resize(hcap);
+            HIP_TRY(hipMemcpyAsync(bcount[i].data(), ha[i + 1].score.prune.bnd_count, 4 * hcap, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipMemcpyAsync(bscore[i].data(), ha[i + 1].score.prune.bnd_score, 8 * hcap, hipMemcpyDeviceToHost, c->stream));
+        }
         if (m[i].counts && !survivors)
             HIP_TRY(hipMemcpyAsync(m[i].counts, t.b.count, sizeof(uint32_t) * H, hipMemcpyDeviceToHost, c->stream));
         if (m[i].scores && !survivors)
@@ -3020,7 +3046,7 @@ int debug_score_pruned(int route, pl_debug_prune_member *m, size_t count, uint32
         HIP_TRY(hipMemcpyAsync(meta[i].data(), t.b.rec_meta, sizeof(RecordMeta) * kRecordCap, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipMemcpyAsync(&st[i], t.b.prune_state, sizeof(PruneState), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipMemcpyAsync(&ctl[i], t.b.ctl, sizeof(BatchCtl), hipMemcpyDeviceToHost, c->stream));
-        if (survivors) {
+        if (survivors || bounded) {
             part[i].resize((size_t)t.s.chunks * ha[i + 1].score.hyp_capacity);
             HIP_TRY(hipMemcpyAsync(part[i].data(), t.b.part_count, sizeof(uint32_t) * part[i].size(), hipMemcpyDeviceToHost, c->stream));
         }
@@ -3050,6 +3076,20 @@ int debug_score_pruned(int route, pl_debug_prune_member *m, size_t count, uint32
                     guard += part[i][(size_t)ch * hcap + p] != 0xffffffffu ? 1u : 0u;
             }
             continue;
+        }
+        if (bounded) {
+            const uint32_t hcap = ha[i + 1].score.hyp_capacity;
+            for (uint32_t ch = 0; ch < chunks; ++ch)
+                for (uint32_t p = ctl[i].num_live; p < hcap; ++p)
+                    guard += part[i][(size_t)ch * hcap + p] != 0xffffffffu ? 1u : 0u;
+            for (uint32_t k = 0; k < H; ++k) { // 0 exact scores, 1 dropped on survivor counts, 2 dropped on bounds, 3 NaN model
+                const uint32_t p = rank[i][k];
+                const bool live = p != kNoRank;
+                const bool has = live && bcount[i][p] != 0xffffffffu;
+                bounded->bound_counts[i][k] = has ? bcount[i][p] : 0xffffffffu;
+                bounded->bound_scores[i][k] = has ? bscore[i][p] : std::numeric_limits<double>::quiet_NaN();
+                bounded->tiers[i][k] = !live ? 3 : kept[i][p] == kKept ? 0 : has ? 2 : 1;
+            }
         }
         const bool split = st[i].cstar < chunks; // (otherwise nothing was dropped or pruned)
         // kept = the exact rule: the pre-selected positions that k_prune_label left alone
@@ -3093,6 +3133,20 @@ int pl_debug_score_survivors(int route, pl_debug_prune_member *members, size_t n
         if (!survivors[i])
             return fail(PL_ERR_INVALID, "pl_debug_score_survivors: a member without an output array");
     return debug_score_pruned(route, members, num_members, idle_changed, survivors, guard_changed);
+}
+int pl_debug_score_bounded(int route, pl_debug_prune_member *members, size_t num_members, uint32_t *const *bound_counts,
+                           double *const *bound_scores, uint8_t *const *tiers, uint32_t *idle_changed, uint32_t *guard_changed) {
+    if (idle_changed)
+        *idle_changed = 0;
+    if (guard_changed)
+        *guard_changed = 0;
+    if (!bound_counts || !bound_scores || !tiers)
+        return fail(PL_ERR_INVALID, "pl_debug_score_bounded: output arrays missing");
+    for (size_t i = 0; i < num_members; ++i)
+        if (!bound_counts[i] || !bound_scores[i] || !tiers[i])
+            return fail(PL_ERR_INVALID, "pl_debug_score_bounded: a member without an output array");
+    const DebugBoundedOut out{bound_counts, bound_scores, tiers};
+    return debug_score_pruned(route, members, num_members, idle_changed, nullptr, guard_changed, &out);
 }
 int pl_debug_score_prune_gate(int kind, uint32_t n_points, uint32_t iterations) {
     PrefilterArgs pf{}; // as pl_debug_group_slices: a prefilter in range is assumed

@@ -901,6 +901,7 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
             dims.any_mfma |= a.use_mfma;
             dims.any_queue |= a.use_mfma ? 0u : 1u;
             dims.any_prune |= a.score.prune.st ? 1u : 0u;
+            dims.any_bound |= (a.score.prune.st && a.score.prune.bound) ? 1u : 0u;
             ++nactive;
         }
         if (nactive == 0)

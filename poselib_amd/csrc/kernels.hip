@@ -1866,6 +1866,198 @@ __global__ __launch_bounds__(1024) void k_prune_list_g(const GroupArgs *ga) {
     prune_list_body(globalised(g.score));
 }
 
+// ---- pruned scoring: the bound tier (PruneArgs.bound) ----
+// Behind the pre-selection the list holds the lead - its first min(H, lead) entries, the list ascends - and the positions the
+// survivor counts could not exclude: mostly hypotheses of three inlier samples, a thousand inliers each, nearly all of which lose
+// against the lead's best and would go through the fp64 exact pass pair by pair only to be told so.  k_score_bound: a dense fp32
+// pass over list entries, no matrix instructions, no queue, no fp64.  A workgroup owns a chunk of 64 P correspondences, every
+// wavefront keeps them in registers (fp32 copies and the per-point slack, as k_score_queue) and takes units of 64 list entries with
+// the launch's stride: lane l fetches entry l's fp32 shadow from its record, the wavefront then walks the 64 models through
+// v_readlane.  Per (entry, chunk) it writes an upper bound of the inliers into the count column and a lower bound of the chunk's
+// share of the score, an INTEGER number of quanta of thr^2 2^-20 stored as an exact double (at most 320 * 2^20, whatever the order
+// of the sum), into the score column.  Two stages, each followed by k_prune_bound:
+//   RESID = false, the entries behind the lead: pf_abs_outlier's verdict alone, two points per packed fp32 instruction as in
+//     k_score_queue - a proven outlier's share is thr^2 exactly (2^20 quanta), every other pair may be an inlier and shares 0.
+//     Ballots and scalar popcounts: no division, no per-lane value, no lane reduction.
+//   RESID = true, what stage one left undecided (the whole list: the lead has left it): pf_abs_r2_lower gives L <= r^2 per pair;
+//     pairs with L < thr^2 are counted, min(L, thr^2) / thr^2 in truncated quanta is summed over the lanes.
+// The columns of those entries hold survivor counts or an earlier step's values at this point; the exact launch overwrites the
+// columns of what k_prune_bound keeps.  Grids from the host, lengths from device memory: no synchronisation.
+constexpr int kBoundThreads = 256;
+template <int P, bool RESID>
+__device__ __forceinline__ void score_bound_body(const ScoreArgs &a, uint32_t slice, uint32_t chunk, uint32_t nslices) {
+    constexpr int kWaves = kBoundThreads / 64;
+    constexpr uint32_t NPW = 64u * P;
+    const PruneArgs &pr = a.prune;
+    if (!pr.st || !pr.bound || *as_uniform(&pr.st->cstar) >= pr.chunks)
+        return;
+    const uint32_t first = RESID ? 0u : min(*as_uniform(a.num_hyp), pr.lead), len = *as_uniform(&pr.st->sel_len);
+    if (len <= first)
+        return;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const PrefilterArgs pf = a.pf;
+    float x[P], y[P], X[P], Y[P], Z[P], fw[P];
+    bool valid[P];
+    uint64_t vmask[P]; // lanes of slot p that hold a real correspondence
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+        const uint32_t i = chunk * NPW + (uint32_t)p * 64u + (uint32_t)lane;
+        valid[p] = i < a.pts.n;
+        vmask[p] = __builtin_amdgcn_ballot_w64(valid[p]);
+        const uint32_t ic = valid[p] ? i : 0u;
+        const double Xd = a.pts.a[2][ic], Yd = a.pts.a[3][ic], Zd = a.pts.a[4][ic];
+        x[p] = (float)a.pts.a[0][ic], y[p] = (float)a.pts.a[1][ic];
+        X[p] = (float)Xd, Y[p] = (float)Yd, Z[p] = (float)Zd;
+        fw[p] = pf_point_abs(Xd, Yd, Zd, pf.gx);
+    }
+    const uint32_t nent = len - first;
+    for (uint32_t u = slice * kWaves + (uint32_t)wave; u * 64u < nent; u += nslices * kWaves) {
+        const uint32_t e = first + u * 64u + (uint32_t)lane;
+        const uint32_t pos = pr.sel[min(e, len - 1u)];
+        const float4 *sh = reinterpret_cast<const float4 *>(a.models + (size_t)a.slots[pos] * kModelStride + kShadowOff);
+        float4 rv[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            rv[k] = sh[k];
+        const uint32_t n = min(64u, nent - u * 64u);
+        uint32_t my_c = 0, my_q = 0;
+        for (uint32_t j = 0; j < n; ++j) {
+            float r[16];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                r[4 * k + 0] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rv[k].x), (int)j));
+                r[4 * k + 1] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rv[k].y), (int)j));
+                r[4 * k + 2] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rv[k].z), (int)j));
+                r[4 * k + 3] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rv[k].w), (int)j));
+            }
+            const float gt = pf_abs_bound_slack(r, pf.gx);
+            uint32_t c = 0, q = 0;
+            if constexpr (RESID) {
+#pragma unroll
+                for (int p = 0; p < P; ++p) {
+                    const float L = pf_abs_r2_lower(r, gt, x[p], y[p], X[p], Y[p], Z[p], fw[p]);
+                    c += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(valid[p] && L < pf.thr2_up));
+                    q += valid[p] ? pf_bound_quantum(L, pf.inv_thr2_dn) : 0u;
+                }
+                q = (uint32_t)__builtin_amdgcn_readlane((int)wave_scan_u32(q), 63);
+            } else {
+#pragma unroll
+                for (int p = 0; p + 1 < P; p += 2) {
+                    const v2f Xp = {X[p], X[p + 1]}, Yp = {Y[p], Y[p + 1]}, Zp = {Z[p], Z[p + 1]};
+                    const v2f xp = {x[p], x[p + 1]}, yp = {y[p], y[p + 1]}, w = {fw[p], fw[p + 1]};
+                    const v2f z0 = pk_fma(bc(r[0]), Xp, pk_fma(bc(r[1]), Yp, pk_fma(bc(r[2]), Zp, bc(r[9]))));
+                    const v2f z1 = pk_fma(bc(r[3]), Xp, pk_fma(bc(r[4]), Yp, pk_fma(bc(r[5]), Zp, bc(r[10]))));
+                    const v2f z2 = pk_fma(bc(r[6]), Xp, pk_fma(bc(r[7]), Yp, pk_fma(bc(r[8]), Zp, bc(r[11]))));
+                    const v2f a0 = pk_fma(-xp, z2, z0);
+                    const v2f a1 = pk_fma(-yp, z2, z1);
+                    const v2f W = w + bc(gt);
+                    const v2f B = pk_fma(bc(pf.thr), z2, W);
+#pragma unroll
+                    for (int e2 = 0; e2 < 2; ++e2) {
+                        const uint64_t out = vmask[p + e2] & (__builtin_amdgcn_ballot_w64(fmaxf(fabsf(a0[e2]), fabsf(a1[e2])) > B[e2]) |
+                                                              __builtin_amdgcn_ballot_w64(z2[e2] < -W[e2]));
+                        q += (uint32_t)__popcll(out);
+                        c += (uint32_t)__popcll(vmask[p + e2] & ~out);
+                    }
+                }
+                if constexpr (P & 1) {
+                    constexpr int p = P - 1;
+                    const uint64_t out = vmask[p] & __builtin_amdgcn_ballot_w64(pf_abs_outlier(r, gt, pf.thr, x[p], y[p], X[p], Y[p], Z[p], fw[p]));
+                    q += (uint32_t)__popcll(out);
+                    c += (uint32_t)__popcll(vmask[p] & ~out);
+                }
+                q <<= 20; // (kPfBoundScale quanta per proven outlier)
+            }
+            if ((uint32_t)lane == j)
+                my_c = c, my_q = q;
+        }
+        if ((uint32_t)lane < n) {
+            const size_t o = (size_t)chunk * a.hyp_capacity + pos;
+            a.part_count[o] = my_c;
+            a.part_score[o] = (double)my_q;
+        }
+    }
+}
+template <int P, bool RESID> __global__ __launch_bounds__(kBoundThreads) void k_score_bound(ScoreArgs a) {
+    uint32_t slice, chunk;
+    slice_chunk_of_workgroup(gridDim.x, gridDim.y, slice, chunk);
+    score_bound_body<P, RESID>(a, slice, chunk, gridDim.x);
+}
+template <bool RESID> __global__ __launch_bounds__(kBoundThreads) void k_score_bound_g(const GroupArgs *ga) {
+    const GroupArgs &g = ga[blockIdx.z];
+    uint32_t slice, chunk;
+    const uint32_t ns = pruned_slices<kScoreSel>(g.slices);
+    if (!g.active || !g.use_mfma || !g.score.prune.st || !slice_chunk_of_workgroup(ns, g.chunks, slice, chunk))
+        return;
+    score_bound_body<5, RESID>(globalised(g.score), slice, chunk, ns);
+}
+// k_prune_bound, one workgroup per problem, behind each stage of k_score_bound: per entry the bounds of all chunks, c_ub and
+// s_lb = thr^2 2^-20 sum q rounded DOWN.  c <= c_ub and s >= s_lb for the exact count and score, so an entry with c_ub <= lead_max
+// and s_lb > lead_min (1 + kPruneScoreMargin) is no candidate of k_records (prune_rule's argument): it is dropped, kept[] = kDropped.
+// The list is rebuilt in place, ascending.  Stage 0 starts behind the lead and writes from position 0: the lead leaves the list
+// - it stays kKept and keeps the columns the lead launch wrote, the exact launch does not score it a second time; a list that holds
+// nothing but the lead ends with length 0.  Stage 1 covers the whole list stage 0 left.  In place: tile by tile (1024 entries, all
+// read before the barrier) the entry at e goes to a position <= e, which is in this tile or an earlier one - whatever the lead's
+// length.  With c* = chunks the lead's values drop nothing and the tier does nothing: the list stays k_prune_list's, lead included.
+__device__ __forceinline__ void prune_bound_body(const ScoreArgs &a, int stage) {
+    __shared__ uint32_t wt[16];
+    const PruneArgs &pr = a.prune;
+    if (!pr.bound || pr.st->cstar >= pr.chunks)
+        return;
+    const uint32_t first = stage ? 0u : min(*a.num_hyp, pr.lead), len = pr.st->sel_len;
+    const uint32_t lead_max = pr.st->lead_max;
+    const double beat = pr.st->lead_min * (1.0 + kPruneScoreMargin);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t base = 0;
+    __syncthreads(); // (every thread holds the list's length before thread 0 writes the new one)
+    for (uint32_t t0 = first; t0 < len; t0 += 1024u) {
+        const uint32_t e = t0 + threadIdx.x;
+        uint32_t keep = 0, p = 0;
+        if (e < len) {
+            p = pr.sel[e];
+            uint32_t c = 0;
+            uint64_t q = 0;
+#pragma unroll 8
+            for (uint32_t ch = 0; ch < pr.chunks; ++ch) {
+                c += a.part_count[(size_t)ch * a.hyp_capacity + p];
+                q += (uint64_t)a.part_score[(size_t)ch * a.hyp_capacity + p];
+            }
+            const double qd = (double)q * 9.5367431640625e-07; // (2^-20: exact)
+            double s_lb = a.thr2 * qd;
+            if (fma(a.thr2, qd, -s_lb) < 0.0) // the product was rounded up (then it is positive): its predecessor
+                s_lb = __longlong_as_double(__double_as_longlong(s_lb) - 1);
+            keep = (c <= lead_max && s_lb > beat) ? 0u : 1u;
+            if (!keep)
+                pr.kept[p] = kDropped;
+            if (pr.bnd_count)
+                pr.bnd_count[p] = c, pr.bnd_score[p] = s_lb;
+        }
+        const uint32_t inc = wave_scan_u32(keep);
+        if (lane == 63)
+            wt[wave] = inc;
+        __syncthreads(); // (also: the tile's entries are read)
+        uint32_t at = base + inc - keep, tot = 0;
+        for (int w = 0; w < 16; ++w) {
+            at += w < wave ? wt[w] : 0u;
+            tot += wt[w];
+        }
+        if (keep)
+            pr.sel[at] = p;
+        base += tot;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0)
+        pr.st->sel_len = base;
+}
+__global__ __launch_bounds__(1024) void k_prune_bound(ScoreArgs a, int stage) { prune_bound_body(a, stage); }
+__global__ __launch_bounds__(1024) void k_prune_bound_g(const GroupArgs *ga, int stage) {
+    const GroupArgs &g = ga[blockIdx.z];
+    if (!g.active || !g.use_mfma || !g.score.prune.st)
+        return;
+    prune_bound_body(globalised(g.score), stage);
+}
+
 
 // k_score_mfma2<EST, PG> (EST = relative pose / fundamental matrix): same contract, same queue and the same exact pass as
 // k_score_queue, but pass A is three v_mfma_f32_32x32x16_f16 per 32 hypotheses x 32 correspondences: two accumulate the
@@ -4169,7 +4361,8 @@ hipError_t launch_group_prune_select(const GroupArgs *args, const GroupDims &d, 
     return hipGetLastError();
 }
 // The pruned form of the matrix-core absolute-pose launch (a.prune set by wire_batch_step: at least three chunks, i.e. 4 or 5
-// points per lane): the grid of launch_score_est, lead -> c* -> survivor counts -> pre-selection -> exact scores.
+// points per lane): the grid of launch_score_est, lead -> c* -> survivor counts -> pre-selection -> (a.prune.bound: fp32 bounds,
+// second selection ->) exact scores.
 template <int PG> static hipError_t launch_score_pruned_pg(const ScoreArgs &a, dim3 grid, hipStream_t stream) {
     const dim3 block(kMfmaThreads);
     const dim3 lead_grid(pruned_slices<kScoreLead>(grid.x), grid.y), sel_grid(pruned_slices<kScoreSel>(grid.x), grid.y);
@@ -4181,6 +4374,12 @@ template <int PG> static hipError_t launch_score_pruned_pg(const ScoreArgs &a, d
     e = launch_prune_select(a, stream);
     if (e != hipSuccess)
         return e;
+    if (a.prune.bound) { // bounds of the pre-selected positions behind the lead, and the list without the lead and what they drop
+        k_score_bound<PG / 2, false><<<sel_grid, dim3(kBoundThreads), 0, stream>>>(a);
+        k_prune_bound<<<dim3(1), dim3(1024), 0, stream>>>(a, 0);
+        k_score_bound<PG / 2, true><<<sel_grid, dim3(kBoundThreads), 0, stream>>>(a);
+        k_prune_bound<<<dim3(1), dim3(1024), 0, stream>>>(a, 1);
+    }
     k_score_mfma_pr<PG, kScoreSel><<<sel_grid, block, 0, stream>>>(a);
     return hipGetLastError();
 }
@@ -4412,6 +4611,12 @@ template <int E> static hipError_t launch_group_score_est(const GroupArgs *args,
             e = launch_group_prune_select(args, d, stream);
             if (e != hipSuccess)
                 return e;
+            if (d.any_bound) { // (as launch_score_pruned_pg)
+                k_score_bound_g<false><<<sel_grid, dim3(kBoundThreads), 0, stream>>>(args);
+                k_prune_bound_g<<<dim3(1, 1, d.G), dim3(1024), 0, stream>>>(args, 0);
+                k_score_bound_g<true><<<sel_grid, dim3(kBoundThreads), 0, stream>>>(args);
+                k_prune_bound_g<<<dim3(1, 1, d.G), dim3(1024), 0, stream>>>(args, 1);
+            }
             k_score_mfma_pr_g<10, kScoreSel><<<sel_grid, dim3(kMfmaThreads), 0, stream>>>(args);
         } else if (d.any_mfma)
             k_score_mfma_g<10><<<grid, dim3(kMfmaThreads), 0, stream>>>(args);

@@ -83,6 +83,8 @@ __device__ __forceinline__ ScoreArgs globalised(ScoreArgs a) {
     a.prune.blk_kept = as_global(a.prune.blk_kept);
     a.prune.sel = as_global(a.prune.sel);
     a.prune.kept = as_global(a.prune.kept);
+    a.prune.bnd_count = as_global(a.prune.bnd_count);
+    a.prune.bnd_score = as_global(a.prune.bnd_score);
     return a;
 }
 __device__ __forceinline__ FinalizeArgs globalised(FinalizeArgs f) {

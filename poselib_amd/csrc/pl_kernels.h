@@ -58,7 +58,8 @@ struct GenerateArgs {
 
 // ---- k_score_mfma with pruning: hypotheses that provably cannot become candidates of k_records are not
 // scored exactly at all.  lead -> (lead_max, lead_min, c*) -> survivor counts of the matrix-core filter (the list behind the lead,
-// chunks [0, c*)) -> pre-selection of the positions the counts cannot exclude -> exact scores (pre-selection, every chunk).
+// chunks [0, c*)) -> pre-selection of the positions the counts cannot exclude -> fp32 bounds of count and score of the pre-selected
+// positions behind the lead (every chunk), which drop what cannot beat the lead -> exact scores (what is left, every chunk).
 constexpr uint32_t kPruneLead = 2048;   // live positions scored against every chunk first (a prefix of the hypothesis order)
 constexpr uint32_t kPruneMargin = 32;   // correspondences added to the bound that places c*
 constexpr double kPruneScoreMargin = 1e-6; // relative margin of the score test (k_records compares with 1e-9)
@@ -78,6 +79,11 @@ struct PruneArgs {
     uint32_t chunks = 0, chunk_points = 0; // the launch's chunks of correspondences and the correspondences of one
     uint32_t init_max = 0, lead = 0;   // what a candidate has to beat (RecordsArgs.init_max / init_min); lead length
     double init_min = 0.0;
+    // The bound tier (k_score_bound, k_prune_bound: two stages) between pre-selection and exact scores; 0: the two-tier sequence, the lead
+    // stays in the selection (pl_debug_score_pruned, pl_debug_score_survivors)
+    uint32_t bound = 0, pad = 0;
+    uint32_t *bnd_count = nullptr; // optional (pl_debug_score_bounded) [hyp_capacity]: per pre-selected position behind the lead
+    double *bnd_score = nullptr;   // the tier's upper bound of the count and lower bound of the score
 };
 constexpr uint8_t kDropped = 0, kKept = 1, kPrunedExact = 2;
 
@@ -439,6 +445,7 @@ struct GroupDims { // grid extents: maxima over the active problems of the group
     uint32_t max_chunks, max_slices;
     uint32_t any_mfma, any_queue;
     uint32_t any_prune;  // a member's matrix-core scorer prunes (ScoreArgs.prune.st): the step launches lead, counts, pre-selection and exact scores
+    uint32_t any_bound;  // ... and a pruning member runs the bound tier between pre-selection and exact scores (PruneArgs.bound)
     int P;               // points per lane of the scorers (chunk = 64 P correspondences)
 };
 // positions -> generate -> compact/gather(/fp16 operands) -> score -> finalize/records -> candidates re-scored: the

@@ -146,7 +146,7 @@ constexpr float kPfU = 5.9604644775390625e-08f; // 2^-24
 struct PrefilterArgs {
     float thr;     // sqrt(thr2), rounded up
     float gx;      // absolute pose: 32u (1 + max|x|,|y| + thr), rounded up
-    float thr2_up; // Sampson: thr2 (1 + 64u), rounded up
+    float thr2_up; // thr2 (1 + 64u), rounded up (Sampson filters; "may be an inlier" of the absolute-pose bound tier)
     int enabled;   // 0: exact evaluation of every point
     float g16;     // absolute pose, fp16 / MFMA form of the filter: 2^-11 (1 + 2^-6), rounded up (0: form not available)
     float c16;     //   and the absolute part (2e-7 + 5e-4) (1 + 1.3661 max|x|,|y| + thr)
@@ -154,6 +154,7 @@ struct PrefilterArgs {
     float w252;    //   and (16/15) (1 + 96u) 60, rounded up (factor of (na nb)^2 in the per-point term w)
     float t16;     // Sampson, fp16 / MFMA form: (16/15) 2^15 thr2 (1 + 256u), rounded up; 0 = that form is not available
     float h16;     // homography, fp16 / MFMA form: the threshold, rounded up; 0 = that form is not available
+    float inv_thr2_dn; // absolute pose, bound tier (pf_bound_quantum): 1 / thr2, rounded down
 };
 
 PL_HD float pf_up(float v) { return v * 1.000001f + 1e-30f; } // pads a non-negative bound upwards
@@ -163,7 +164,7 @@ PL_HD float pf_up(float v) { return v * 1.000001f + 1e-30f; } // pads a non-nega
 // the range fp32 can carry.
 inline PrefilterArgs make_prefilter_args(int est, double thr2, float xy_absmax) {
     PrefilterArgs a;
-    a.thr = a.gx = a.thr2_up = a.g16 = a.c16 = a.t1 = a.w252 = a.t16 = a.h16 = 0.f;
+    a.thr = a.gx = a.thr2_up = a.g16 = a.c16 = a.t1 = a.w252 = a.t16 = a.h16 = a.inv_thr2_dn = 0.f;
     a.enabled = 0;
     if (!(thr2 >= 1e-30 && thr2 <= 1e30))
         return a;
@@ -178,6 +179,7 @@ inline PrefilterArgs make_prefilter_args(int est, double thr2, float xy_absmax) 
     a.w252 = nextafterf((float)((16.0 / 15.0) * (1.0 + 96.0 * u) * 60.0), inf);
     if (est == 0) {
         a.gx = nextafterf((float)(32.0 * u * (1.0 + (double)xy_absmax + thr)), inf);
+        a.inv_thr2_dn = nextafterf((float)((1.0 / thr2) * (1.0 - 8.0 * u)), 0.f);
         // fp16 / MFMA form (round 6: three directions, p = c x + s y with |p| <= 1.3661 max(|x|, |y|); pf16_abs_model / _point)
         a.g16 = nextafterf((float)(4.8828125e-4 * 1.015625), inf); // 2^-11 (1 + 2^-6)
         // absolute part: operands below the fp16 normal range (also when the matrix pipe flushes them), fp32 accumulation
@@ -232,6 +234,65 @@ PL_HD bool pf_abs_outlier(const float *r, float gt /* gx * tmax */, float thr, f
     const float W = fw + gt;
     const float B = fmaf(thr, z2, W);
     return (fmaxf(fabsf(a0), fabsf(a1)) > B) | (z2 < -W);
+}
+
+// ---- reprojection: a lower bound of the squared residual (the bound tier of the pruned scorer, k_score_bound) ----
+// Same z^, a^0, a^1 and W = fw + gt as pf_abs_outlier, operation for operation; by the derivation at the top of this header
+// |a^i - a_i| <= W (a_i = z_i - p_i z_2, p = (x, y)) and |z^2 - z_2| <= W.  The reference's residual of a point in front of the
+// camera is r^2 = (a_0^2 + a_1^2) / z_2^2, and only a point with z_2 > 0 and r^2 < thr^2 is an inlier.
+//   z^2 < -W:   z_2 < 0, a proven outlier: +inf.
+//   z^2 >  W:   0 < z_2 <= z^2 + W and |a_i| >= (|a^i| - W)+, so
+//                   r^2 >= L = ((|a^0| - W)+^2 + (|a^1| - W)+^2) / (z^2 + W)^2.
+//               The evaluation of L rounds eight times in fp32 (two subtractions, a product and an FMA in the numerator; a sum
+//               and a product in the denominator; the reciprocal, one ulp on the device; the last product): a relative error
+//               below 10u.  kPfBoundDown = 1 - 2^-16 charges 256u, which also pays for the reference's own fp64 roundings.  That
+//               holds while numerator and denominator are normal numbers (a subnormal result is rounded with an ABSOLUTE error of
+//               2^-150): where either is below 2^-126 the function answers 0.  A subnormal square inside a normal numerator
+//               costs at most u of it.
+//   otherwise (|z^2| <= W, a numerator or denominator below the normal range, a slack that is infinite or NaN - coordinates or translations beyond the filter's range, see
+//               pf_abs_bound_slack - or an L that is not a finite number): nothing is known, 0.
+// The caller takes "may be an inlier" as L < thr2 rounded UP, and min(L, thr^2) / thr^2 as pf_bound_quantum below.
+constexpr float kPfBoundDown = 0.9999847412109375f; // 1 - 2^-16
+constexpr float kPfBoundScale = 1048576.f;          // 2^20: quanta per thr^2
+constexpr float kPfFltMin = 1.17549435e-38f;        // 2^-126
+PL_HD float pf_rcp(float v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_rcpf(v);
+#else
+    return 1.f / v;
+#endif
+}
+// gt of a model for the bound: pf_abs_outlier's gx * tmax, or +inf for a shadow the derivation does not cover - the NaN flag, or
+// matrix entries that are not those of a rotation (max-abs entry above 1, padded; +inf and NaN included)
+PL_HD float pf_abs_bound_slack(const float *r, float gx) {
+    const bool covered = (r[13] == 0.f) & (r[14] <= 1.0001f);
+    return covered ? pf_up(gx * r[12]) : __builtin_huge_valf();
+}
+PL_HD float pf_abs_r2_lower(const float *r, float gt, float x, float y, float X, float Y, float Z, float fw) {
+    const float z0 = fmaf(r[0], X, fmaf(r[1], Y, fmaf(r[2], Z, r[9])));
+    const float z1 = fmaf(r[3], X, fmaf(r[4], Y, fmaf(r[5], Z, r[10])));
+    const float z2 = fmaf(r[6], X, fmaf(r[7], Y, fmaf(r[8], Z, r[11])));
+    const float a0 = fmaf(-x, z2, z0);
+    const float a1 = fmaf(-y, z2, z1);
+    const float W = fw + gt;
+    const float n0 = fmaxf(fabsf(a0) - W, 0.f), n1 = fmaxf(fabsf(a1) - W, 0.f);
+    const float d = z2 + W;
+    const float num = fmaf(n1, n1, n0 * n0), dd = d * d;
+    const float L = (num * pf_rcp(dd)) * kPfBoundDown;
+    if (z2 < -W)
+        return __builtin_huge_valf();
+    // (false for a NaN on either side; a numerator or denominator below the normal range has lost its relative accuracy)
+    const bool known = (z2 > W) & (L < __builtin_huge_valf()) & (num >= kPfFltMin) & (dd >= kPfFltMin);
+    return known ? L : 0.f;
+}
+// The cruder bound of the tier's first stage: pf_abs_outlier's verdict alone - +inf for a proven outlier, 0 for everything else
+// (k_score_bound evaluates it two points per packed instruction and counts ballots; this form is the host build's)
+PL_HD float pf_abs_verdict_lower(const float *r, float gt, float thr, float x, float y, float X, float Y, float Z, float fw) {
+    return pf_abs_outlier(r, gt, thr, x, y, X, Y, Z, fw) ? __builtin_huge_valf() : 0.f;
+}
+// min(L, thr^2) / thr^2 in units of 2^-20, truncated: inv_thr2_dn <= 1 / thr^2, so the quantum never exceeds the exact ratio
+PL_HD uint32_t pf_bound_quantum(float L, float inv_thr2_dn) {
+    return (uint32_t)(fminf(L * inv_thr2_dn, 1.f) * kPfBoundScale);
 }
 
 PL_HD bool pf_hom_outlier(const float *r, float gh /* 32u * hm */, float thr, float a0, float a1, float b0, float b1,
