@@ -302,6 +302,55 @@ int pl_estimate_batch_dev(pl_batch_item_dev *items, size_t count, int max_in_fli
  * entries each; out: count x 8 doubles, member after member, laid out as pl_debug_point_stats_dev's (zeros for n == 0). */
 int pl_debug_point_stats_group_dev(const pl_device_points *x1, const pl_device_points *x2, const size_t *n, size_t count, int centroid,
                                    double *out);
+/* ---- device-resident matches WITH their confidences: which rows are correspondences, and in which order (PROSAC) ----
+ * A matcher leaves one confidence per row next to the matches and marks padding rows with a low (or NaN) one.  The _scored forms
+ * of the _dev entry points take that output as it is.  THE RULE, for an item of n rows, scores s[0..n) and a threshold min_score:
+ *   - row i is KEPT iff s[i] >= min_score (IEEE comparison): a NaN score is never kept.  min_score = -inf keeps every non-NaN
+ *     row; -inf itself is kept only then; a NaN min_score is PL_ERR_INVALID;
+ *   - kept rows are used in DESCENDING score (+inf first), equal scores in ASCENDING row index; -0.0 == 0.0;
+ *   - in numpy: keep = s >= min_score; order = np.flatnonzero(keep)[np.argsort(-s[keep], kind="stable")].
+ * (score, row) is a total order, so the permutation does not depend on how it is computed; fp32 scores widen exactly - a column
+ * of floats ranks like the same values as doubles.  The estimator then runs EXACTLY as the plain entry point would on the rows
+ * a[order], b[order] with n_used = len(order): the sampler's indices, the index-order sums of the normalisation, LM's summation
+ * order and inlier_ratio (num_inliers / n_used) are those of that call, bit for bit.  inliers[i] speaks of the CALLER's row i
+ * (n bytes; 0 for dropped rows).  Whatever the plain form serves or refuses for n_used rows, the scored form serves or refuses
+ * the same way (too few rows: default stats; tangent_sampson; estimate_focal_length: PL_ERR_UNSUPPORTED).
+ * Scores reorder and select - they do NOT switch PROSAC on: ransac.progressive_sampling selects the sampler, as everywhere.
+ *   - The scores get the checks the points get, in the same order (null descriptor, n beyond 2^31 - 1, dtype, stride < 1, null
+ *     data, alignment - PL_ERR_INVALID without a device -, then the memory's kind, device and extent).  They are read only
+ *     during the call and must be complete when it is made.
+ *   - How: a ranking kernel leaves the permutation and the kept count in device memory, a permuting copy (the ingest kernel
+ *     reading row order[j] into row j) writes the contiguous fp64 blocks the preparation takes - a scored item is never read where
+ *     it lies -, one synchronisation brings count and permutation back; the mask is scattered to the caller's numbering on the
+ *     host.  Any n up to 2^31 - 1; the work buffers are 24 bytes per row beyond 8192 rows, none below.
+ *   - Out of scope: masks or models in device memory, a producer stream, scored resident problems (pl_problem_create_dev),
+ *     scores for the focal-length, 1D-radial and pl_ransac_* entries, half-precision scores. */
+typedef struct {
+    const void *data;   /* device address of the first row's score */
+    int64_t stride;     /* ELEMENTS between consecutive rows' scores, >= 1: one column of a wider block is a valid source */
+    int32_t dtype;      /* PL_F64 / PL_F32 */
+    int32_t reserved;   /* 0 */
+    double min_score;   /* rows with score >= min_score are kept; -INFINITY keeps every non-NaN row */
+} pl_device_scores;
+/* kind 0 .. 3 as pl_batch_item_dev.kind; camera1 / camera2 / model as there (kind 0: camera1 in/out, pose; kind 1: both cameras,
+ * pose; kinds 2, 3: no cameras, double[9] column-major).  n_used (optional): the kept count. */
+int pl_estimate_dev_scored(int kind, const pl_device_points *a, const pl_device_points *b, const pl_device_scores *scores, size_t n,
+                           const pl_robust_options *opt, pl_camera *camera1, const pl_camera *camera2, void *model, uint8_t *inliers,
+                           pl_ransac_stats *stats, size_t *n_used);
+/* pl_estimate_batch_dev with scores: scores[i] belongs to items[i]; an entry whose data is NULL makes item i a plain item (scores
+ * == NULL: every item).  ALL scored items are ranked first - one launch sequence and one synchronisation per call, not per item -
+ * and the groups are then formed on n_used: an item is a group member when sample size + 4 <= n_used <= 16384, whatever its n.
+ * Every item equals its single call bit for bit, pl_last_batch_report reports the call like any other, and a bad scores
+ * descriptor fails its own item only (PL_ERR_INVALID, the message names index and cause).  n_used (optional): count entries,
+ * items[i].n for a plain item, 0 for an item that did not run. */
+int pl_estimate_batch_dev_scored(pl_batch_item_dev *items, const pl_device_scores *scores, size_t *n_used, size_t count,
+                                 int max_in_flight);
+/* Diagnostic: the permutation alone.  scores, n, kept: count entries; order: the members one after the other, n[k] slots each, the
+ * first kept[k] of them written.  count == 1 takes the kernels' single form, count > 1 the grouped one (one launch sequence for
+ * all members).  pl_debug_rank_tile: the rows one workgroup ranks out of LDS in a launch whose largest member has max_n rows -
+ * members up to it need one launch, larger ones merge passes through global memory. */
+int pl_debug_rank_scores(const pl_device_scores *scores, const size_t *n, size_t count, uint32_t *order, size_t *kept);
+int pl_debug_rank_tile(size_t max_n);
 /* What the calling thread's last pl_estimate_batch / pl_estimate_batch_devices / pl_estimate_batch_dev / pl_ransac_batch did with its items.  Items in
  * lock-step groups share one launch sequence (the advertised rate); `solo` items were outside the group path from the start
  * (options or sizes a group does not take - see pl_batch_item / pl_ransac_batch) and `fallback` items were handed back by their

@@ -116,6 +116,10 @@ class BatchItemDev(C.Structure):  # pl_batch_item_dev: pl_batch_item with the tw
                 ("model", C.c_void_p), ("inliers", C.c_void_p), ("stats", C.POINTER(RansacStats))]
 
 
+class DeviceScores(C.Structure):  # pl_device_scores: one confidence per row in DEVICE memory, `stride` elements apart
+    _fields_ = [("data", C.c_void_p), ("stride", C.c_int64), ("dtype", i32), ("reserved", i32), ("min_score", f64)]
+
+
 class PoseLibAmdError(RuntimeError):
     pass
 
@@ -189,6 +193,10 @@ def _declare(L):
         "pl_estimate_batch_devices": (cint, [P(BatchItem), sz, P(C.c_int), cint, cint]),
         "pl_estimate_batch_dev": (cint, [P(BatchItemDev), sz, cint]),
         "pl_debug_point_stats_group_dev": (cint, [dpts, dpts, P(sz), sz, cint, vp]),
+        "pl_estimate_dev_scored": (cint, [cint, dpts, dpts, P(DeviceScores), sz, opt, cam, cam, vp, vp, stats, P(sz)]),
+        "pl_estimate_batch_dev_scored": (cint, [P(BatchItemDev), P(DeviceScores), P(sz), sz, cint]),
+        "pl_debug_rank_scores": (cint, [P(DeviceScores), P(sz), sz, vp, P(sz)]),
+        "pl_debug_rank_tile": (cint, [sz]),
         "pl_last_batch_report": (None, [P(BatchReport)]),
         "pl_ransac_batch": (cint, [P(RansacItem), sz, cint, cint]),
         "pl_undistort_points": (cint, [cam, vp, sz, vp]),
@@ -273,6 +281,7 @@ EXPORTED_SYMBOLS = [
     "pl_estimate_absolute_pose_dev", "pl_estimate_relative_pose_dev", "pl_estimate_fundamental_dev", "pl_estimate_homography_dev",
     "pl_problem_create_dev", "pl_problem_create_tangent_dev", "pl_debug_check_device_points", "pl_debug_point_stats_dev",
     "pl_debug_sampler_shape", "pl_debug_sample_positions", "pl_estimate_batch_dev", "pl_debug_point_stats_group_dev",
+    "pl_estimate_dev_scored", "pl_estimate_batch_dev_scored", "pl_debug_rank_scores", "pl_debug_rank_tile",
     # (pl_estimate_1D_radial_absolute_pose and pl_ransac_1D_radial_pnp carry the reference's capital D: declared above, exported by the
     # library, but outside the lower-case pattern tests/test_cabi_surface.py lists the header's symbols with)
 ]

@@ -17,6 +17,7 @@ All numerical work happens in the HIP library; this file only marshals numpy arr
 from __future__ import annotations
 
 import ctypes as C
+import math
 import sys
 import threading
 
@@ -271,6 +272,97 @@ def _sync_streams(streams):
         torch.cuda.current_stream(device).synchronize()
 
 
+# ---- one confidence per row (a matcher's scores): which rows are correspondences, and in which order.  THE RULE
+# (include/poselib_amd.h): row i is kept iff scores[i] >= min_score (a NaN never is; min_score defaults to -inf), kept rows go in
+# descending score, equal scores (-0.0 == 0.0) in ascending row index.  Scores reorder and select; they do not switch PROSAC on -
+# ransac.progressive_sampling does, as everywhere.
+def _min_score(min_score) -> float:
+    m = -math.inf if min_score is None else float(min_score)
+    if m != m:
+        raise ValueError("min_score is NaN")
+    return m
+
+
+def score_order(scores, min_score=None):
+    """THE RULE in numpy, for scores in host memory: the rows that are used, in the order they are used.  float32 scores are
+    widened (exactly) first, so a float32 array ranks like the same values as doubles - and like the device kernels."""
+    s = np.asarray(scores)
+    if s.ndim != 1 or s.dtype not in (np.float32, np.float64):
+        raise ValueError("scores: expected a one-dimensional float32 or float64 array")
+    s = s.astype(np.float64)
+    keep = s >= _min_score(min_score)
+    return np.flatnonzero(keep)[np.argsort(-s[keep], kind="stable")]
+
+
+def _device_scores(scores, n, min_score, streams=None):
+    """(pl_device_scores descriptor, the object that owns the memory) of a one-dimensional GPU tensor / __cuda_array_interface__
+    object of n elements - a column view of a wider block keeps its stride.  Synchronisation as _device_points."""
+    m = _min_score(min_score)
+    if _is_torch_tensor(scores):
+        if scores.dim() != 1:
+            raise ValueError("scores: expected a one-dimensional tensor")
+        dtype = _TORCH_DTYPES.get(str(scores.dtype))
+        if dtype is None:
+            raise ValueError(f"device scores must be float32 or float64, not {scores.dtype}")
+        index = scores.device.index
+        torch = sys.modules.get(type(scores).__module__.split(".")[0])
+        if index is None and torch is not None:
+            index = torch.cuda.current_device()
+        if index != _selected_device():
+            raise ValueError(f"the scores live on device {index}, this thread selected device {_selected_device()} (set_device)")
+        rows = int(scores.shape[0])
+        if rows > 1 and scores.stride(0) < 1:
+            scores = scores.contiguous()
+        if torch is not None:
+            if streams is None:
+                torch.cuda.current_stream(scores.device).synchronize()
+            else:
+                streams.setdefault(index, (torch, scores.device))
+        stride, ptr = (int(scores.stride(0)) if rows > 1 else 1), (scores.data_ptr() if rows else None)
+    else:
+        cai = scores.__cuda_array_interface__
+        shape = tuple(cai["shape"])
+        if len(shape) != 1:
+            raise ValueError("scores: expected a one-dimensional array")
+        if cai["typestr"] not in _TYPESTR_DTYPES:
+            raise ValueError(f"device scores must be float32 or float64, not typestr {cai['typestr']!r}")
+        dtype, size = _TYPESTR_DTYPES[cai["typestr"]]
+        rows = int(shape[0])
+        strides = cai.get("strides")
+        stride = 1
+        if strides is not None and rows > 1:
+            if strides[0] % size or strides[0] < size:
+                raise ValueError("the byte stride of the device scores is no positive multiple of their element size")
+            stride = strides[0] // size
+        ptr = int(cai["data"][0]) if rows else None
+    if rows != n:
+        raise ValueError(f"{rows} scores for {n} correspondences")
+    return L.DeviceScores(ptr, stride, dtype, 0, m), scores
+
+
+def _check_scores_args(on_device, scores, min_score):
+    if scores is None:
+        if min_score is not None:
+            raise ValueError("min_score without scores")
+        return
+    if on_device != _on_device(scores):
+        raise ValueError("points and scores must be in the same place: both on the GPU or both in host memory")
+
+
+def _scored_host(call, a, b, scores, min_score):
+    """scores in host memory: THE RULE in numpy, the plain call on a[order], b[order], the mask back in the caller's numbering"""
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    order = score_order(scores, min_score)
+    if len(np.asarray(scores)) != a.shape[0]:
+        raise ValueError(f"{len(np.asarray(scores))} scores for {a.shape[0]} correspondences")
+    model, info = call(a[order], b[order])
+    mask = np.zeros(a.shape[0], dtype=bool)
+    mask[order] = info["inliers"]
+    info["inliers"] = mask.tolist()
+    info["n_used"] = int(len(order))
+    return model, info
+
+
 class _Points:
     """The two point sets of a call as the C-ABI takes them: host arrays (pointers to float64 data) or device descriptors."""
 
@@ -295,8 +387,9 @@ class _Points:
         return getattr(L.lib(), name + "_dev" if self.on_device else name)
 
 
-def _info(st: L.RansacStats, inliers: np.ndarray):
-    return {"refinements": st.refinements, "iterations": st.iterations, "num_inliers": st.num_inliers,
+def _info(st: L.RansacStats, inliers: np.ndarray, n_used=None):
+    return {"n_used": len(inliers) if n_used is None else int(n_used),  # rows the estimator ran on (fewer than given: scores=)
+            "refinements": st.refinements, "iterations": st.iterations, "num_inliers": st.num_inliers,
             "inlier_ratio": st.inlier_ratio, "model_score": st.model_score, "inliers": inliers.astype(bool).tolist(),
             # extras (not in the reference): metric numerator and device timing
             "hypotheses": st.hypotheses, "iterations_evaluated": st.iterations_evaluated, "seconds": st.seconds,
@@ -322,7 +415,23 @@ def _as_camera(cam) -> Camera:
 
 
 # ------------------------------------------------------------------------------------------ estimators
-def estimate_absolute_pose(points2D, points3D, camera, opt=None, initial_pose=None):
+def _run_scored(kind, pts, scores, min_score, o, c1, c2, model, inl, st):
+    """pl_estimate_dev_scored: device points with device scores; returns n_used"""
+    sd, keep = _device_scores(scores, pts.n, min_score)
+    used = C.c_size_t(0)
+    L.check(L.lib().pl_estimate_dev_scored(kind, pts.a, pts.b, C.byref(sd), C.c_size_t(pts.n), C.byref(o),
+                                           None if c1 is None else C.byref(c1), None if c2 is None else C.byref(c2), model, _ptr(inl),
+                                           C.byref(st), C.byref(used)))
+    del keep
+    return int(used.value)
+
+
+def estimate_absolute_pose(points2D, points3D, camera, opt=None, initial_pose=None, scores=None, min_score=None):
+    """scores (one per row, where the points are) / min_score: the rows with score >= min_score are used, in descending score -
+    see score_order; info["inliers"] keeps the caller's numbering, info["n_used"] is the number of rows used"""
+    _check_scores_args(_on_device(points2D) or _on_device(points3D), scores, min_score)
+    if scores is not None and not _on_device(scores):
+        return _scored_host(lambda a, b: estimate_absolute_pose(a, b, camera, opt, initial_pose), points2D, points3D, scores, min_score)
     pts = _Points(points2D, points3D, 2, 3)
     cam = _as_camera(camera)
     o = _robust_options(opt, KIND_ABS, initial_pose is not None)
@@ -331,13 +440,21 @@ def estimate_absolute_pose(points2D, points3D, camera, opt=None, initial_pose=No
     n = pts.n
     inl = np.zeros(max(n, 1), dtype=np.uint8)
     st = L.RansacStats()
-    L.check(pts.fn("pl_estimate_absolute_pose")(pts.a, pts.b, C.c_size_t(n), C.byref(o), C.byref(c), C.byref(pose),
-                                                _ptr(inl), C.byref(st)))
+    used = None
+    if scores is not None:
+        used = _run_scored(KIND_ABS, pts, scores, min_score, o, c, None, C.cast(C.pointer(pose), C.c_void_p), inl, st)
+    else:
+        L.check(pts.fn("pl_estimate_absolute_pose")(pts.a, pts.b, C.c_size_t(n), C.byref(o), C.byref(c), C.byref(pose),
+                                                    _ptr(inl), C.byref(st)))
     out_cam = Camera(cam.model_id, list(c.params[: c.num_params]), cam.width, cam.height)
-    return Image(_pypose(pose), out_cam), _info(st, inl[:n])
+    return Image(_pypose(pose), out_cam), _info(st, inl[:n], used)
 
 
-def estimate_relative_pose(points2D_1, points2D_2, camera1, camera2, opt=None, initial_pose=None):
+def estimate_relative_pose(points2D_1, points2D_2, camera1, camera2, opt=None, initial_pose=None, scores=None, min_score=None):
+    _check_scores_args(_on_device(points2D_1) or _on_device(points2D_2), scores, min_score)
+    if scores is not None and not _on_device(scores):
+        return _scored_host(lambda a, b: estimate_relative_pose(a, b, camera1, camera2, opt, initial_pose), points2D_1, points2D_2,
+                            scores, min_score)
     pts = _Points(points2D_1, points2D_2, 2, 2)
     c1, c2 = _as_camera(camera1)._c(), _as_camera(camera2)._c()
     o = _robust_options(opt, KIND_REL, initial_pose is not None)
@@ -345,20 +462,31 @@ def estimate_relative_pose(points2D_1, points2D_2, camera1, camera2, opt=None, i
     n = pts.n
     inl = np.zeros(max(n, 1), dtype=np.uint8)
     st = L.RansacStats()
-    L.check(pts.fn("pl_estimate_relative_pose")(pts.a, pts.b, C.c_size_t(n), C.byref(c1), C.byref(c2), C.byref(o),
-                                                C.byref(pose), _ptr(inl), C.byref(st)))
-    return _pypose(pose), _info(st, inl[:n])
+    used = None
+    if scores is not None:
+        used = _run_scored(KIND_REL, pts, scores, min_score, o, c1, c2, C.cast(C.pointer(pose), C.c_void_p), inl, st)
+    else:
+        L.check(pts.fn("pl_estimate_relative_pose")(pts.a, pts.b, C.c_size_t(n), C.byref(c1), C.byref(c2), C.byref(o),
+                                                    C.byref(pose), _ptr(inl), C.byref(st)))
+    return _pypose(pose), _info(st, inl[:n], used)
 
 
-def _estimate_matrix(fn, kind, points2D_1, points2D_2, opt, initial):
+def _estimate_matrix(fn, kind, points2D_1, points2D_2, opt, initial, scores=None, min_score=None):
+    _check_scores_args(_on_device(points2D_1) or _on_device(points2D_2), scores, min_score)
+    if scores is not None and not _on_device(scores):
+        return _scored_host(lambda a, b: _estimate_matrix(fn, kind, a, b, opt, initial), points2D_1, points2D_2, scores, min_score)
     pts = _Points(points2D_1, points2D_2, 2, 2)
     o = _robust_options(opt, kind, initial is not None)
     M = np.ascontiguousarray((np.eye(3) if initial is None else np.asarray(initial, dtype=np.float64)).T.reshape(9))
     n = pts.n
     inl = np.zeros(max(n, 1), dtype=np.uint8)
     st = L.RansacStats()
-    L.check(pts.fn(fn)(pts.a, pts.b, C.c_size_t(n), C.byref(o), _ptr(M), _ptr(inl), C.byref(st)))
-    return M.reshape(3, 3).T.copy(), _info(st, inl[:n])
+    used = None
+    if scores is not None:
+        used = _run_scored(kind, pts, scores, min_score, o, None, None, _ptr(M), inl, st)
+    else:
+        L.check(pts.fn(fn)(pts.a, pts.b, C.c_size_t(n), C.byref(o), _ptr(M), _ptr(inl), C.byref(st)))
+    return M.reshape(3, 3).T.copy(), _info(st, inl[:n], used)
 
 
 class _DevicePts:
@@ -398,13 +526,28 @@ class Batch:
 
         self.items = ((L.BatchItemDev if self.on_device else L.BatchItem) * len(problems))()
         self.keep = []
+        # device items with scores: pl_estimate_batch_dev_scored (an entry without data is a plain item)
+        self.scores = (L.DeviceScores * max(len(problems), 1))()
+        self.n_used = (C.c_size_t * max(len(problems), 1))()
+        self.scored = False
         for it, pr in zip(self.items, problems):
             kind = kinds[pr[0]]
             it.kind = kind
             # a warm start: the options dict may carry "initial_model" (a CameraPose for "abs" / "rel", a 3 x 3 matrix for "fund" /
             # "hom") - the initial_pose / initial_F / initial_H argument of the single-problem functions; it sets score_initial_model
+            # ... and "scores" / "min_score": one confidence per row, where the points are (score_order has the rule)
             opt = dict(pr[-1] or {})
             init = opt.pop("initial_model", None)
+            scores, min_score = opt.pop("scores", None), opt.pop("min_score", None)
+            _check_scores_args(self.on_device, scores, min_score)
+            order, rows = None, None
+            if scores is not None and not self.on_device:  # host points: the rule in numpy, the plain item on the ranked rows
+                order = score_order(scores, min_score)
+                rows = len(np.asarray(scores))
+                pa, pb = np.asarray(pr[1], dtype=np.float64), np.asarray(pr[2], dtype=np.float64)
+                if pa.shape[0] != rows or pb.shape[0] != rows:
+                    raise ValueError(f"{rows} scores for {pa.shape[0]} and {pb.shape[0]} correspondences")
+                pr = (pr[0], pa[order], pb[order]) + tuple(pr[3:])
             pr = tuple(pr[:-1]) + (opt,)
             if kind == KIND_ABS:
                 _, a, b, cam, opt = pr
@@ -442,6 +585,9 @@ class Batch:
             st = L.RansacStats()
             if self.on_device:
                 it.a, it.b, it.n = a.desc, b.desc, n
+                if scores is not None:
+                    self.scores[len(self.keep)], order = _device_scores(scores, n, min_score, streams)  # (order: keeps the owner)
+                    self.scored = True
             else:
                 it.a, it.b, it.n = _ptr(a), _ptr(b), n
             it.opt = C.pointer(o)
@@ -450,7 +596,7 @@ class Batch:
             it.model = C.cast(C.pointer(model), C.c_void_p) if kind in (KIND_ABS, KIND_REL, KIND_SHARED_FOCAL, KIND_RAD1D) else _ptr(model)
             it.inliers = _ptr(inl)
             it.stats = C.pointer(st)
-            self.keep.append((kind, a, b, o, cam, c1, c2, model, inl, st, n))
+            self.keep.append((kind, a, b, o, cam, c1, c2, model, inl, st, n, order, rows))
         _sync_streams(streams)  # (once per device, not per tensor: the producers' work is complete before run())
 
     def run(self, max_in_flight=8, devices=None):
@@ -459,6 +605,10 @@ class Batch:
         if self.on_device:
             if devices is not None:
                 raise ValueError("devices= with device points: the memory belongs to one device (set_device selects it)")
+            if self.scored:
+                L.check(L.lib().pl_estimate_batch_dev_scored(self.items, self.scores, self.n_used, C.c_size_t(len(self.keep)),
+                                                             C.c_int(int(max_in_flight))))
+                return
             L.check(L.lib().pl_estimate_batch_dev(self.items, C.c_size_t(len(self.keep)), C.c_int(int(max_in_flight))))
             return
         if devices is None:
@@ -478,8 +628,15 @@ class Batch:
 
     def results(self):
         out = []
-        for kind, a, b, o, cam, c1, c2, model, inl, st, n in self.keep:
-            info = _info(st, inl[:n])
+        for i, (kind, a, b, o, cam, c1, c2, model, inl, st, n, order, rows) in enumerate(self.keep):
+            if self.on_device:
+                info = _info(st, inl[:n], self.n_used[i] if self.scored else None)
+            elif rows is not None:  # host scores: the mask of the ranked rows back in the caller's numbering
+                mask = np.zeros(rows, dtype=np.uint8)
+                mask[order] = inl[:n]
+                info = _info(st, mask, n)
+            else:
+                info = _info(st, inl[:n])
             if kind == KIND_ABS:
                 out_cam = Camera(cam.model_id, list(c1.params[: c1.num_params]), cam.width, cam.height)
                 out.append((Image(_pypose(model), out_cam), info))
@@ -783,12 +940,12 @@ def ransac_batch(problems, opts, max_in_flight=4, group_size=16):
     return b.results()
 
 
-def estimate_fundamental(points2D_1, points2D_2, opt=None, initial_F=None):
-    return _estimate_matrix("pl_estimate_fundamental", KIND_FUND, points2D_1, points2D_2, opt, initial_F)
+def estimate_fundamental(points2D_1, points2D_2, opt=None, initial_F=None, scores=None, min_score=None):
+    return _estimate_matrix("pl_estimate_fundamental", KIND_FUND, points2D_1, points2D_2, opt, initial_F, scores, min_score)
 
 
-def estimate_homography(points2D_1, points2D_2, opt=None, initial_H=None):
-    return _estimate_matrix("pl_estimate_homography", KIND_HOM, points2D_1, points2D_2, opt, initial_H)
+def estimate_homography(points2D_1, points2D_2, opt=None, initial_H=None, scores=None, min_score=None):
+    return _estimate_matrix("pl_estimate_homography", KIND_HOM, points2D_1, points2D_2, opt, initial_H, scores, min_score)
 
 
 # ------------------------------------------------------------------------------------------ ransac_* on normalised points
@@ -1246,6 +1403,42 @@ def check_device_points(desc, n: int, cols: int) -> int:
     """Diagnostic (pl_debug_check_device_points): the return code of every check the _dev entry points make on one argument -
     desc: a _lib.DevicePoints, or None for a null descriptor.  No kernel is launched."""
     return L.lib().pl_debug_check_device_points(None if desc is None else C.byref(desc), C.c_size_t(int(n)), int(cols))
+
+
+def rank_tile(max_n: int) -> int:
+    """Diagnostic (pl_debug_rank_tile): the rows one workgroup of the ranking kernel sorts out of LDS in a launch whose largest
+    member has max_n rows; larger members take merge passes through global memory."""
+    return int(L.lib().pl_debug_rank_tile(C.c_size_t(int(max_n))))
+
+
+def rank_scores(scores, min_score=None):
+    """Diagnostic (pl_debug_rank_scores): the permutation the scored entry points use - the rows of a one-dimensional device
+    array with score >= min_score, in descending score, ties in ascending row (score_order is the same rule in numpy).  A list of
+    arrays (min_score: one value, or one per array) is ranked by ONE launch sequence of the grouped kernels and returns a list."""
+    single = not isinstance(scores, (list, tuple))
+    members = [scores] if single else list(scores)
+    mins = list(min_score) if isinstance(min_score, (list, tuple)) else [min_score] * len(members)
+    if len(mins) != len(members):
+        raise ValueError("min_score: one value, or one per member")
+    if not all(_on_device(m) for m in members):
+        raise ValueError("rank_scores takes device arrays (score_order ranks host arrays)")
+    cnt = len(members)
+    if cnt == 0:
+        return []
+    ns = (C.c_size_t * cnt)(*[int(m.shape[0]) for m in members])
+    desc = (L.DeviceScores * cnt)()
+    keep = []
+    for k, (m, lo) in enumerate(zip(members, mins)):
+        desc[k], owner = _device_scores(m, ns[k], lo)
+        keep.append(owner)
+    order = np.zeros(max(sum(ns), 1), dtype=np.uint32)
+    kept = (C.c_size_t * cnt)()
+    L.check(L.lib().pl_debug_rank_scores(desc, ns, C.c_size_t(cnt), _ptr(order), kept))
+    out, at = [], 0
+    for k in range(cnt):
+        out.append(order[at:at + kept[k]].copy())
+        at += ns[k]
+    return out[0] if single else out
 
 
 def point_stats_dev(x1, x2, centroid=True):

@@ -125,6 +125,10 @@ struct Context {
     DevBuf lm_tasks, lm_records, gather_idx, gather_out, mask, lm_scratch, tmp_model, solve_in, solve_out, solve_cnt, focal_stage;
     HostBuf h_rec_meta, h_focal, h_in;
     HostBuf h_pstats; // the record k_point_stats writes (the *_dev front-ends)
+    // scored items (the *_dev_scored front-ends): the sides of the merge passes, the permutations, the permuted fp64 blocks; the
+    // argument tables and the kept counts the kernels write
+    DevBuf rank_keys, rank_rows, rank_order, ranked_pts;
+    HostBuf h_rank, h_rank_order;
     const double *raw_src_a = nullptr, *raw_src_b = nullptr; // where the raw correspondences of the last make_problem_prepared live (device-visible)
     HostBuf h_absmax, h_positions, h_num_models, h_count, h_score, h_tasks, h_gather_idx, h_gather_out, h_mask,
         h_small, h_models;
@@ -4067,6 +4071,7 @@ int pl_estimate_homography(const double *x1, const double *x2, size_t n, const p
 }
 
 #include "driver_dev.inc"
+#include "driver_scored.inc"
 
 // ---------------------------------------------------------------------------- un-distortion stage
 int pl_undistort_points(const pl_camera *camera, const double *points2D, size_t n, double *out) {

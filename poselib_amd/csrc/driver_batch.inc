@@ -691,11 +691,18 @@ int pl_estimate_batch_devices(pl_batch_item *items, size_t count, const int *dev
 // running it is said first - the kind, then the descriptors' plain checks (no device needed), then what the runtime knows about
 // the memory (once per allocation) - and such an item is out of the call; the others go through estimate_batch_on as host-side
 // copies of their records (a == b == null) next to the caller's descriptors.
-int pl_estimate_batch_dev(pl_batch_item_dev *items, size_t count, int max_in_flight) {
+// (scores: null, or count entries - pl_estimate_batch_dev_scored: the items whose entry has data are ranked first, all at once, and
+// enter the call as plain items over their kept rows in ranked order)
+static int estimate_batch_dev_impl(pl_batch_item_dev *items, const pl_device_scores *scores, size_t *n_used, size_t count,
+                                   int max_in_flight) {
     if (count == 0)
         return PL_OK;
     if (!items)
         return fail(PL_ERR_INVALID, "items pointer is null");
+    auto scored = [&](size_t i) { return scores && scores[i].data; };
+    if (n_used)
+        for (size_t i = 0; i < count; ++i)
+            n_used[i] = 0;
     DeviceBatch dev;
     dev.items = items;
     dev.decided.assign(count, PL_OK);
@@ -729,6 +736,8 @@ int pl_estimate_batch_dev(pl_batch_item_dev *items, size_t count, int max_in_fli
         int rc = check_points_plain(&it.a, it.n, 2);
         if (rc == PL_OK)
             rc = check_points_plain(&it.b, it.n, it.kind == EST_ABS ? 3 : 2);
+        if (rc == PL_OK && scored(i))
+            rc = check_scores_plain(&scores[i], it.n);
         if (rc != PL_OK)
             decide(i, rc);
     }
@@ -749,12 +758,60 @@ int pl_estimate_batch_dev(pl_batch_item_dev *items, size_t count, int max_in_fli
         rc = allocations.check(c, &items[i].a, items[i].n);
         if (rc == PL_OK)
             rc = allocations.check(c, &items[i].b, items[i].n);
+        if (rc == PL_OK && scored(i)) {
+            const pl_device_points p = scores_as_points(&scores[i]);
+            rc = name_the_scores(allocations.check(c, &p, items[i].n));
+        }
         if (rc != PL_OK)
             decide(i, rc);
     }
+    // the scored items: one ranking and one permuted copy for all of them, one synchronisation; from here on they are plain items
+    // of n_used rows whose contiguous fp64 blocks a group reads where they lie, and the groups form on n_used
+    std::vector<pl_batch_item_dev> ranked_items;
+    std::vector<RankMember> members;
+    std::vector<size_t> member_of(count, (size_t)-1);
+    std::vector<uint8_t> ranked_masks;
+    Ranking ranking;
+    for (size_t i = 0; i < count; ++i)
+        if (scored(i) && dev.decided[i] == PL_OK && items[i].n) {
+            member_of[i] = members.size();
+            members.emplace_back();
+            members.back().scores = &scores[i], members.back().n = items[i].n;
+            members.back().a = &items[i].a, members.back().b = &items[i].b;
+        }
+    if (scores) {
+        rc = ranking.run(c, members, /*grouped=*/true);
+        if (rc != PL_OK) {
+            for (size_t i = 0; i < count; ++i)
+                if (dev.decided[i] == PL_OK)
+                    items[i].status = rc;
+            return rc;
+        }
+        ranked_items.assign(items, items + count);
+        size_t mask_bytes = 0;
+        for (const RankMember &r : members)
+            mask_bytes += std::max<size_t>(r.kept, 1);
+        ranked_masks.assign(mask_bytes, 0);
+        size_t mask_at = 0;
+        for (size_t i = 0; i < count; ++i) {
+            if (scored(i) && !items[i].n)
+                continue; // (an empty item is what it is, with or without scores)
+            if (member_of[i] == (size_t)-1)
+                continue;
+            const RankMember &r = members[member_of[i]];
+            pl_batch_item_dev &it = ranked_items[i];
+            it.a = ranked_points(r.out_a, it.a.cols, r.kept), it.b = ranked_points(r.out_b, it.b.cols, r.kept);
+            it.n = r.kept;
+            if (it.inliers)
+                it.inliers = ranked_masks.data() + mask_at;
+            mask_at += std::max<size_t>(r.kept, 1);
+        }
+        dev.items = ranked_items.data();
+    }
+    const pl_batch_item_dev *run_items = dev.items;
     std::vector<pl_batch_item> host(count);
     for (size_t i = 0; i < count; ++i) {
-        const pl_batch_item_dev &it = items[i];
+        const pl_batch_item_dev &it = run_items[i];
         pl_batch_item &h = host[i];
         h.kind = it.kind, h.status = it.status;
         h.a = h.b = nullptr;
@@ -762,7 +819,21 @@ int pl_estimate_batch_dev(pl_batch_item_dev *items, size_t count, int max_in_fli
         h.model = it.model, h.inliers = it.inliers, h.stats = it.stats;
     }
     rc = estimate_batch_on(c->device, host.data(), count, max_in_flight, &dev);
-    for (size_t i = 0; i < count; ++i)
+    for (size_t i = 0; i < count; ++i) {
         items[i].status = host[i].status;
+        if (member_of[i] != (size_t)-1 && items[i].inliers) // the mask of the kept rows -> the caller's numbering
+            ranking.scatter(members[member_of[i]], ranked_items[i].inliers, items[i].inliers);
+        if (n_used && dev.decided[i] == PL_OK)
+            n_used[i] = run_items[i].n;
+    }
     return rc;
+}
+
+int pl_estimate_batch_dev(pl_batch_item_dev *items, size_t count, int max_in_flight) {
+    return estimate_batch_dev_impl(items, nullptr, nullptr, count, max_in_flight);
+}
+
+int pl_estimate_batch_dev_scored(pl_batch_item_dev *items, const pl_device_scores *scores, size_t *n_used, size_t count,
+                                 int max_in_flight) {
+    return estimate_batch_dev_impl(items, scores, n_used, count, max_in_flight);
 }

@@ -303,6 +303,39 @@ int group_stage_device(Context *c, GroupContext &gc, GroupItem *const *pit, uint
     return PL_OK;
 }
 
+// What a *_dev entry point says about its options and cameras before it looks at the points (kinds 0 - 3); the scored forms
+// (driver_scored.inc) say the same, first.
+int dev_entry_precheck(int kind, const pl_robust_options *opt, const pl_camera *camera1, const pl_camera *camera2) {
+    static const char *const unsupported_camera = "camera model not supported (NULL, SIMPLE_PINHOLE, PINHOLE, SIMPLE_RADIAL, RADIAL, OPENCV, OPENCV_FISHEYE, SIMPLE_RADIAL_FISHEYE, RADIAL_FISHEYE)";
+    if (kind == EST_ABS) {
+        const int rc = validate_options(opt, /*focal_entry=*/true);
+        if (rc != PL_OK)
+            return rc;
+        if (opt->estimate_focal_length) // (its loop and compute_max_focal_length read the image points on the host)
+            return fail(PL_ERR_UNSUPPORTED, "estimate_focal_length is not served from device memory: use pl_estimate_absolute_pose");
+        if (!camera1 || !camera_supported(camera1))
+            return fail(PL_ERR_UNSUPPORTED, unsupported_camera);
+        return PL_OK;
+    }
+    if (kind != EST_REL)
+        return validate_options(opt);
+    const bool tangent = opt && opt->tangent_sampson; // (as pl_estimate_relative_pose)
+    pl_robust_options plain;
+    if (tangent) {
+        plain = *opt;
+        plain.tangent_sampson = 0;
+    }
+    const int rc = validate_options(tangent ? &plain : opt);
+    if (rc != PL_OK)
+        return rc;
+    if (tangent && (opt->bundle.refine_focal_length || opt->bundle.refine_principal_point || opt->bundle.refine_extra_params))
+        return fail(PL_ERR_UNSUPPORTED, "tangent_sampson with bundle.refine_focal_length / refine_principal_point / refine_extra_params "
+                                        "refines the intrinsics with the pose (CameraRelativePoseRefiner): not served, fixed cameras only");
+    if (!camera1 || !camera2 || !camera_supported(camera1) || !camera_supported(camera2))
+        return fail(PL_ERR_UNSUPPORTED, unsupported_camera);
+    return PL_OK;
+}
+
 int estimate_two_view_dev(int kind, const pl_device_points *x1, const pl_device_points *x2, size_t n, const pl_camera *camera1,
                           const pl_camera *camera2, const pl_robust_options *opt, void *model, uint8_t *inliers, pl_ransac_stats *st) {
     Context *c;
@@ -455,13 +488,9 @@ int pl_debug_point_stats_group_dev(const pl_device_points *x1, const pl_device_p
 int pl_estimate_absolute_pose_dev(const pl_device_points *points2D, const pl_device_points *points3D, size_t n,
                                   const pl_robust_options *opt, pl_camera *camera, pl_camera_pose *pose, uint8_t *inliers,
                                   pl_ransac_stats *stats) {
-    int rc = validate_options(opt, /*focal_entry=*/true);
+    int rc = dev_entry_precheck(EST_ABS, opt, camera, nullptr);
     if (rc != PL_OK)
         return rc;
-    if (opt->estimate_focal_length) // (its loop and compute_max_focal_length read the image points on the host)
-        return fail(PL_ERR_UNSUPPORTED, "estimate_focal_length is not served from device memory: use pl_estimate_absolute_pose");
-    if (!camera || !camera_supported(camera))
-        return fail(PL_ERR_UNSUPPORTED, "camera model not supported (NULL, SIMPLE_PINHOLE, PINHOLE, SIMPLE_RADIAL, RADIAL, OPENCV, OPENCV_FISHEYE, SIMPLE_RADIAL_FISHEYE, RADIAL_FISHEYE)");
     Context *c;
     rc = open_device_points(points2D, 2, points3D, 3, n, &c);
     if (rc == PL_OK)
@@ -483,19 +512,9 @@ int pl_estimate_relative_pose_dev(const pl_device_points *x1, const pl_device_po
                                   const pl_camera *camera2, const pl_robust_options *opt, pl_camera_pose *pose, uint8_t *inliers,
                                   pl_ransac_stats *stats) {
     const bool tangent = opt && opt->tangent_sampson; // (as pl_estimate_relative_pose)
-    pl_robust_options plain;
-    if (tangent) {
-        plain = *opt;
-        plain.tangent_sampson = 0;
-    }
-    int rc = validate_options(tangent ? &plain : opt);
+    const int rc = dev_entry_precheck(EST_REL, opt, camera1, camera2);
     if (rc != PL_OK)
         return rc;
-    if (tangent && (opt->bundle.refine_focal_length || opt->bundle.refine_principal_point || opt->bundle.refine_extra_params))
-        return fail(PL_ERR_UNSUPPORTED, "tangent_sampson with bundle.refine_focal_length / refine_principal_point / refine_extra_params "
-                                        "refines the intrinsics with the pose (CameraRelativePoseRefiner): not served, fixed cameras only");
-    if (!camera1 || !camera2 || !camera_supported(camera1) || !camera_supported(camera2))
-        return fail(PL_ERR_UNSUPPORTED, "camera model not supported (NULL, SIMPLE_PINHOLE, PINHOLE, SIMPLE_RADIAL, RADIAL, OPENCV, OPENCV_FISHEYE, SIMPLE_RADIAL_FISHEYE, RADIAL_FISHEYE)");
     pl_ransac_stats local;
     return estimate_two_view_dev(tangent ? EST_RELT : EST_REL, x1, x2, n, camera1, camera2, opt, pose, inliers, stats ? stats : &local);
 }

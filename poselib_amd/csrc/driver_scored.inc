@@ -1,0 +1,257 @@
+// poselib_amd — device-resident matches with their confidences (pl_device_scores): the ranking in front of the *_dev entry points.
+// Included by driver.cc inside extern "C", behind driver_dev.inc; the batched form is in driver_batch.inc.
+//
+// A scored item becomes a plain one before anything of the existing path sees it:
+//   rank_sequence (rank.hip)   the permutation of the kept rows and their count, in device memory
+//   k_ingest_ranked            the caller's rows order[j] -> row j of contiguous fp64 blocks (Context::ranked_pts, n rows of room:
+//                              the launch follows the ranking on the stream and reads the count on the device)
+//   one synchronisation        the counts (the kernels write them into pinned memory) and the permutations come back
+// and the matching pl_estimate_*_dev runs on those blocks with n = n_used - contiguous fp64, so it reads them where they lie and
+// every check, every small-n answer and every refusal is that entry point's own.  Its mask (n_used bytes) is scattered into the
+// caller's numbering on the host, with the permutation that came back.
+namespace {
+
+int run_item_dev(const pl_batch_item_dev &it); // (driver_batch.inc: the matching pl_estimate_*_dev)
+
+int check_scores_plain(const pl_device_scores *d, size_t n) {
+    if (!d)
+        return fail(PL_ERR_INVALID, "device scores: descriptor is null");
+    if (n > 0x7fffffffu)
+        return fail(PL_ERR_INVALID, "too many correspondences");
+    if (d->dtype != PL_F64 && d->dtype != PL_F32)
+        return fail(PL_ERR_INVALID, "device scores: dtype must be PL_F64 or PL_F32");
+    if (d->stride < 1)
+        return fail(PL_ERR_INVALID, "device scores: stride (elements) is below 1");
+    if (d->stride > ((int64_t)1 << 28))
+        return fail(PL_ERR_INVALID, "device scores: stride beyond 2^28 elements");
+    if (!d->data && n)
+        return fail(PL_ERR_INVALID, "device scores: data is null");
+    const uintptr_t elt = d->dtype == PL_F32 ? sizeof(float) : sizeof(double);
+    if (reinterpret_cast<uintptr_t>(d->data) % elt)
+        return fail(PL_ERR_INVALID, "device scores: data is not aligned to its element size");
+    if (d->min_score != d->min_score)
+        return fail(PL_ERR_INVALID, "device scores: min_score is NaN");
+    return PL_OK;
+}
+// the scores as a one-column point set: the memory checks are those of the points, the message names the scores
+pl_device_points scores_as_points(const pl_device_scores *d) {
+    pl_device_points p;
+    p.data = d->data, p.row_stride = d->stride, p.dtype = d->dtype, p.cols = 1;
+    return p;
+}
+int name_the_scores(int rc) {
+    if (rc != PL_OK) {
+        const size_t at = g_err.find("device points");
+        if (at != std::string::npos)
+            g_err.replace(at, 13, "device scores");
+    }
+    return rc;
+}
+int check_scores_device(const Context *c, const pl_device_scores *d, size_t n) {
+    const pl_device_points p = scores_as_points(d);
+    return name_the_scores(check_points_device(c, &p, n));
+}
+
+RankSrc rank_src(const pl_device_scores *d) {
+    RankSrc s;
+    s.data = d->data, s.stride = d->stride, s.f32 = d->dtype == PL_F32, s.pad = 0, s.min_score = d->min_score;
+    return s;
+}
+
+// The members of one ranking: where each one's permutation lies in Context::rank_order and, with `ingest`, its blocks in
+// Context::ranked_pts.  Everything is enqueued on the context's stream; Ranking::run waits once and leaves the counts and the
+// permutations in host memory.
+struct RankMember {
+    const pl_device_scores *scores;
+    size_t n;
+    const pl_device_points *a = nullptr, *b = nullptr; // with both: the permuted copy follows the ranking
+    size_t order_at = 0;                               // (out) first slot of the member in the order block
+    double *out_a = nullptr, *out_b = nullptr;         // (out) its fp64 blocks, n rows of room each
+    size_t kept = 0;                                   // (out, after the wait)
+};
+struct Ranking {
+    const uint32_t *order = nullptr; // all members' slots, member after member (Context::h_rank_order: pinned - the permutations of a
+                                     // large batch are tens of megabytes, and a copy into pageable memory took longer than the ranking)
+    int run(Context *c, std::vector<RankMember> &m, bool grouped) {
+        const size_t count = m.size();
+        if (count == 0)
+            return PL_OK;
+        size_t slots = 0, merge_rows = 0, doubles = 0;
+        uint32_t max_n = 0;
+        bool ingest = false;
+        for (RankMember &r : m)
+            max_n = std::max(max_n, (uint32_t)r.n);
+        const uint32_t tile = rank_tile(max_n);
+        for (RankMember &r : m) {
+            r.order_at = slots;
+            slots += r.n;
+            if (r.n > tile)
+                merge_rows += r.n;
+            if (r.a && r.b)
+                doubles += (size_t)(r.a->cols + r.b->cols) * r.n, ingest = true;
+        }
+        HIP_TRY(c->rank_order.ensure(sizeof(uint32_t) * std::max<size_t>(slots, 1)));
+        if (merge_rows) {
+            HIP_TRY(c->rank_keys.ensure(sizeof(unsigned long long) * 2 * merge_rows));
+            HIP_TRY(c->rank_rows.ensure(sizeof(uint32_t) * 2 * merge_rows));
+        }
+        if (ingest)
+            HIP_TRY(c->ranked_pts.ensure(sizeof(double) * std::max<size_t>(doubles, 1)));
+        // pinned: the counts, then the two tables
+        const size_t counts_bytes = (sizeof(uint32_t) * count + 15) & ~(size_t)15;
+        HIP_TRY(c->h_rank.ensure(counts_bytes + (sizeof(RankArgs) + sizeof(IngestRankedArgs)) * count));
+        uint32_t *kept = c->h_rank.as<uint32_t>();
+        RankArgs *ra = reinterpret_cast<RankArgs *>(c->h_rank.as<char>() + counts_bytes);
+        IngestRankedArgs *ia = reinterpret_cast<IngestRankedArgs *>(ra + count);
+        uint32_t *d_kept = c->h_rank.dev<uint32_t>();
+        RankArgs *d_ra = reinterpret_cast<RankArgs *>(c->h_rank.dev<char>() + counts_bytes);
+        IngestRankedArgs *d_ia = reinterpret_cast<IngestRankedArgs *>(d_ra + count);
+        size_t merge_at = 0, doubles_at = 0;
+        for (size_t k = 0; k < count; ++k) {
+            RankMember &r = m[k];
+            kept[k] = 0;
+            std::memset(&ra[k], 0, sizeof(ra[k]));
+            std::memset(&ia[k], 0, sizeof(ia[k]));
+            ra[k].s = rank_src(r.scores);
+            ra[k].n = (uint32_t)r.n;
+            if (r.n > tile) {
+                ra[k].keys[0] = c->rank_keys.as<unsigned long long>() + 2 * merge_at, ra[k].keys[1] = ra[k].keys[0] + r.n;
+                ra[k].rows[0] = c->rank_rows.as<uint32_t>() + 2 * merge_at, ra[k].rows[1] = ra[k].rows[0] + r.n;
+                merge_at += r.n;
+            }
+            ra[k].order = c->rank_order.as<uint32_t>() + r.order_at;
+            ra[k].kept = d_kept + k;
+            if (r.a && r.b && r.n) {
+                r.out_a = c->ranked_pts.as<double>() + doubles_at, doubles_at += (size_t)r.a->cols * r.n;
+                r.out_b = c->ranked_pts.as<double>() + doubles_at, doubles_at += (size_t)r.b->cols * r.n;
+                ia[k].a = ingest_src(r.a), ia[k].b = ingest_src(r.b);
+                ia[k].n = (uint32_t)r.n;
+                ia[k].order = ra[k].order, ia[k].kept = ra[k].kept;
+                ia[k].out_a = r.out_a, ia[k].out_b = r.out_b;
+            }
+        }
+        if (grouped) {
+            HIP_TRY(launch_rank_g(d_ra, (uint32_t)count, max_n, c->stream));
+            if (ingest)
+                HIP_TRY(launch_ingest_ranked_g(d_ia, (uint32_t)count, max_n, c->stream));
+        } else {
+            for (size_t k = 0; k < count; ++k) {
+                HIP_TRY(launch_rank(ra[k], c->stream));
+                if (ia[k].n)
+                    HIP_TRY(launch_ingest_ranked(ia[k], c->stream));
+            }
+        }
+        HIP_TRY(c->h_rank_order.ensure(sizeof(uint32_t) * std::max<size_t>(slots, 1)));
+        order = c->h_rank_order.as<uint32_t>();
+        if (slots)
+            HIP_TRY(hipMemcpyAsync(c->h_rank_order.p, c->rank_order.p, sizeof(uint32_t) * slots, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(wait_stream(c));
+        for (size_t k = 0; k < count; ++k) {
+            if (kept[k] > m[k].n)
+                return fail(PL_ERR_HIP, "ranking of the scores: a kept count beyond the member's rows");
+            m[k].kept = kept[k];
+        }
+        return PL_OK;
+    }
+    // a mask over the kept rows -> the caller's numbering
+    void scatter(const RankMember &r, const uint8_t *ranked_mask, uint8_t *inliers) const {
+        std::memset(inliers, 0, r.n);
+        for (size_t j = 0; j < r.kept; ++j)
+            inliers[order[r.order_at + j]] = ranked_mask[j];
+    }
+};
+
+// a member's permuted blocks as the point sets of a plain item
+pl_device_points ranked_points(const double *data, int cols, size_t kept) {
+    pl_device_points p;
+    p.data = kept ? data : nullptr, p.row_stride = cols, p.dtype = PL_F64, p.cols = cols;
+    return p;
+}
+
+} // namespace
+
+int pl_debug_rank_tile(size_t max_n) { return (int)rank_tile((uint32_t)std::min<size_t>(max_n, 0x7fffffffu)); }
+
+int pl_debug_rank_scores(const pl_device_scores *scores, const size_t *n, size_t count, uint32_t *order, size_t *kept) {
+    if (!scores || !n || !order || !kept)
+        return fail(PL_ERR_INVALID, "a pointer is null");
+    if (count == 0)
+        return PL_OK;
+    int rc = PL_OK;
+    for (size_t k = 0; k < count && rc == PL_OK; ++k)
+        rc = check_scores_plain(&scores[k], n[k]);
+    Context *c = nullptr;
+    if (rc == PL_OK)
+        rc = get_context(&c);
+    DeviceAllocationCache allocations;
+    for (size_t k = 0; k < count && rc == PL_OK; ++k) {
+        const pl_device_points p = scores_as_points(&scores[k]);
+        rc = name_the_scores(allocations.check(c, &p, n[k]));
+    }
+    if (rc != PL_OK)
+        return rc;
+    std::vector<RankMember> m(count);
+    for (size_t k = 0; k < count; ++k)
+        m[k].scores = &scores[k], m[k].n = n[k];
+    Ranking ranking;
+    rc = ranking.run(c, m, /*grouped=*/count > 1);
+    if (rc != PL_OK)
+        return rc;
+    for (size_t k = 0; k < count; ++k) {
+        kept[k] = m[k].kept;
+        std::memcpy(order + m[k].order_at, ranking.order + m[k].order_at, sizeof(uint32_t) * m[k].kept);
+    }
+    return PL_OK;
+}
+
+int pl_estimate_dev_scored(int kind, const pl_device_points *a, const pl_device_points *b, const pl_device_scores *scores, size_t n,
+                           const pl_robust_options *opt, pl_camera *camera1, const pl_camera *camera2, void *model, uint8_t *inliers,
+                           pl_ransac_stats *stats, size_t *n_used) {
+    if (n_used)
+        *n_used = 0;
+    if (kind < 0 || kind > 3)
+        return fail(PL_ERR_INVALID, "pl_estimate_dev_scored: kind must be 0..3");
+    int rc = dev_entry_precheck(kind, opt, camera1, camera2); // what the plain entry point says before it looks at the points
+    if (rc == PL_OK)
+        rc = check_points_plain(a, n, 2);
+    if (rc == PL_OK)
+        rc = check_points_plain(b, n, kind == EST_ABS ? 3 : 2);
+    if (rc == PL_OK)
+        rc = check_scores_plain(scores, n);
+    Context *c = nullptr;
+    if (rc == PL_OK)
+        rc = get_context(&c);
+    if (rc == PL_OK)
+        rc = check_points_device(c, a, n);
+    if (rc == PL_OK)
+        rc = check_points_device(c, b, n);
+    if (rc == PL_OK)
+        rc = check_scores_device(c, scores, n);
+    if (rc != PL_OK)
+        return rc;
+    std::vector<RankMember> m(1);
+    m[0].scores = scores, m[0].n = n, m[0].a = a, m[0].b = b;
+    Ranking ranking;
+    if (n) {
+        rc = ranking.run(c, m, /*grouped=*/false);
+        if (rc != PL_OK)
+            return rc;
+    }
+    const size_t kept = m[0].kept;
+    pl_batch_item_dev it;
+    std::memset(&it, 0, sizeof(it));
+    it.kind = kind;
+    it.a = ranked_points(m[0].out_a, 2, kept), it.b = ranked_points(m[0].out_b, kind == EST_ABS ? 3 : 2, kept);
+    it.n = kept;
+    it.opt = opt, it.camera1 = camera1, it.camera2 = camera2, it.model = model, it.stats = stats;
+    std::vector<uint8_t> ranked_mask(std::max<size_t>(kept, 1), 0);
+    it.inliers = inliers ? ranked_mask.data() : nullptr;
+    rc = run_item_dev(it);
+    if (rc != PL_OK)
+        return rc;
+    if (inliers)
+        ranking.scatter(m[0], ranked_mask.data(), inliers);
+    if (n_used)
+        *n_used = kept;
+    return PL_OK;
+}

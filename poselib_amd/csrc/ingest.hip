@@ -7,6 +7,7 @@
 //   k_point_stats   what the front-ends compute over the raw points on the host: the two ORDER-DEPENDENT reductions of the
 //                   homography / fundamental normalisation (utils.cc:584-644: centroid sums, then the mean distance), added
 //                   strictly in index order by one wavefront, and the order-free maxima behind the pre-filters' bound
+//   k_ingest_ranked, k_ingest_ranked_g   k_ingest through a permutation: the rows an item's scores keep, in descending score (rank.hip)
 //   k_ingest_g, k_point_stats_g   the two for a lock-step group of problems (pl_estimate_batch_dev): the member is a grid
 //                   dimension, its arguments come from a device-visible table; the bodies are those of the single forms
 //
@@ -43,18 +44,19 @@ __device__ __forceinline__ void take_abs(double &m, double x) {
 
 } // namespace
 
-// One thread per correspondence: its row of each set, element by element (plain loads; rows are 8 - 24 bytes).
-__device__ __forceinline__ void ingest_row(const IngestSrc &a, const IngestSrc &b, uint32_t i, double *__restrict__ out_a,
+// One thread per correspondence: its row of each set, element by element (plain loads; rows are 8 - 24 bytes).  Row i of the
+// sources becomes row j of the blocks (j == i but for a ranked item).
+__device__ __forceinline__ void ingest_row(const IngestSrc &a, const IngestSrc &b, uint32_t i, uint32_t j, double *__restrict__ out_a,
                                            double *__restrict__ out_b) {
     if (out_a) {
         const size_t row = (size_t)i * (size_t)a.row_stride;
         for (int d = 0; d < a.cols; ++d)
-            out_a[(size_t)i * a.cols + d] = ingest_load(a.data, a.f32, row + d);
+            out_a[(size_t)j * a.cols + d] = ingest_load(a.data, a.f32, row + d);
     }
     if (out_b) {
         const size_t row = (size_t)i * (size_t)b.row_stride;
         for (int d = 0; d < b.cols; ++d)
-            out_b[(size_t)i * b.cols + d] = ingest_load(b.data, b.f32, row + d);
+            out_b[(size_t)j * b.cols + d] = ingest_load(b.data, b.f32, row + d);
     }
 }
 __global__ __launch_bounds__(256) void k_ingest(IngestSrc a, IngestSrc b, uint32_t n, double *__restrict__ out_a,
@@ -62,7 +64,7 @@ __global__ __launch_bounds__(256) void k_ingest(IngestSrc a, IngestSrc b, uint32
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n)
         return;
-    ingest_row(a, b, i, out_a, out_b);
+    ingest_row(a, b, i, i, out_a, out_b);
 }
 // ... of every member of a group: blockIdx.z is the member, the grid's extent the largest member's.  A member whose sets are both
 // read where they lie (out_a == out_b == null) has n == 0 in the table; blocks beyond a member's rows return.
@@ -74,8 +76,20 @@ __global__ __launch_bounds__(256) void k_ingest_g(const IngestGroupArgs *tab) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n)
         return;
-    ingest_row(in.a, in.b, i, as_global(in.out_a), as_global(in.out_b)); // (the sources are read as global memory by ingest_load)
+    ingest_row(in.a, in.b, i, i, as_global(in.out_a), as_global(in.out_b)); // (the sources are read as global memory by ingest_load)
 }
+// ... of an item with scores (rank.hip): output row j is the caller's row order[j], j below the kept count.  Both come from device
+// memory - the launch follows the ranking on the stream, no host round trip between them; in.n bounds the grid.
+__device__ __forceinline__ void ingest_ranked_body(const IngestRankedArgs &in) {
+    if (blockIdx.x * 256u >= in.n)
+        return;
+    const uint32_t j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= *as_global(in.kept))
+        return;
+    ingest_row(in.a, in.b, as_global(in.order)[j], j, as_global(in.out_a), as_global(in.out_b));
+}
+__global__ __launch_bounds__(256) void k_ingest_ranked(IngestRankedArgs in) { ingest_ranked_body(in); }
+__global__ __launch_bounds__(256) void k_ingest_ranked_g(const IngestRankedArgs *tab) { ingest_ranked_body(tab[blockIdx.z]); }
 
 // ... straight into a resident problem's SoA block: a's columns, then b's, n doubles each (make_problem's layout and bound)
 __global__ __launch_bounds__(256) void k_ingest_soa(IngestSrc a, IngestSrc b, uint32_t n, int b_in_max, double *__restrict__ soa,
@@ -228,6 +242,22 @@ hipError_t launch_ingest_g(const IngestGroupArgs *tab, uint32_t G, uint32_t max_
         return hipSuccess;
     k_ingest_g<<<dim3((max_n + 255) / 256, 1, G), dim3(256), 0, stream>>>(tab);
     return hipGetLastError();
+}
+hipError_t launch_ingest_ranked(const IngestRankedArgs &args, hipStream_t stream) {
+    if (args.n == 0)
+        return hipSuccess;
+    k_ingest_ranked<<<dim3((args.n + 255) / 256), dim3(256), 0, stream>>>(args);
+    return hipGetLastError();
+}
+hipError_t launch_ingest_ranked_g(const IngestRankedArgs *tab, uint32_t G, uint32_t max_n, hipStream_t stream) {
+    constexpr uint32_t kMembersPerLaunch = 32768; // (a grid's z extent ends at 65535)
+    for (uint32_t at = 0; at < G && max_n; at += kMembersPerLaunch) {
+        k_ingest_ranked_g<<<dim3((max_n + 255) / 256, 1, G - at < kMembersPerLaunch ? G - at : kMembersPerLaunch), dim3(256), 0, stream>>>(tab + at);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess)
+            return e;
+    }
+    return hipSuccess;
 }
 hipError_t launch_point_stats_g(const PointStatsGroupArgs *tab, uint32_t G, hipStream_t stream) {
     if (G == 0)

@@ -268,6 +268,40 @@ struct PointStatsGroupArgs {
     PointStatsRecord *out;       // device-visible
 };
 hipError_t launch_point_stats_g(const PointStatsGroupArgs *tab, uint32_t G, hipStream_t stream);
+// ---- one confidence per row next to the correspondences (rank.hip; pl_device_scores once the driver has checked it).  The rule:
+// row i is kept iff score[i] >= min_score (a NaN never is); kept rows go in descending score, equal scores (-0.0 == 0.0) in ascending
+// row index.  fp32 scores widen exactly, so one 64-bit key serves both dtypes and the pair (key, row) is a total order: the
+// permutation does not depend on how it is computed.
+struct RankSrc {
+    const void *data;
+    int64_t stride; // ELEMENTS between consecutive scores
+    int32_t f32, pad;
+    double min_score;
+};
+struct RankArgs {
+    RankSrc s;
+    uint32_t n, pad;
+    unsigned long long *keys[2]; // members beyond one tile: the two sides of the merge passes, n entries each; otherwise unused
+    uint32_t *rows[2];
+    uint32_t *order; // out: n slots, the first *kept are written
+    uint32_t *kept;  // out, device-visible
+};
+// rows one workgroup sorts in LDS for a launch whose largest member has max_n rows: members up to it need one launch, larger
+// ones log2(ceil(n / tile)) merge passes through global memory and a last launch that writes order / kept
+uint32_t rank_tile(uint32_t max_n);
+// the single form (the arguments travel as kernel arguments) and the grouped one (member = blockIdx.z, device-visible table)
+hipError_t launch_rank(const RankArgs &args, hipStream_t stream);
+hipError_t launch_rank_g(const RankArgs *tab, uint32_t G, uint32_t max_n, hipStream_t stream);
+// k_ingest / k_ingest_g reading row order[j] into output row j, j < *kept (both device-resident: no host round trip between the
+// ranking and the copy); n: the rows of the source, the upper bound of *kept.  Both sets are always written.
+struct IngestRankedArgs {
+    IngestSrc a, b;
+    uint32_t n, pad;
+    const uint32_t *order, *kept;
+    double *out_a, *out_b;
+};
+hipError_t launch_ingest_ranked(const IngestRankedArgs &args, hipStream_t stream);
+hipError_t launch_ingest_ranked_g(const IngestRankedArgs *tab, uint32_t G, uint32_t max_n, hipStream_t stream);
 // After the LM kernels: records of the refined models on the device (skipped tasks keep their input record), and the
 // choice "refined model if its score beats `incumbent_score`, else the incumbent" of the final refinement
 // (ransac_impl.h:190-198) so that the inlier mask can follow without a host round trip.

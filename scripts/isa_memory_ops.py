@@ -23,7 +23,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "poselib_amd", "csrc")
-FILES = ["kernels", "gen_rel", "lm_cam", "focal", "sfocal", "pipeline", "ingest"]
+FILES = ["kernels", "gen_rel", "lm_cam", "focal", "sfocal", "pipeline", "ingest", "rank"]
 
 
 def find_hipcc():
