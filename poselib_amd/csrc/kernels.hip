@@ -1373,6 +1373,16 @@ __device__ __forceinline__ void score_mfma_body(const PointSet &pts, const uint4
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int col = lane & 31, half = lane >> 5;
 
+    // The list's length first: a workgroup whose first ticket has no unit (tickets ascend, so none of its tickets has one) returns
+    // before it stages anything - behind the bound tier the selection is a handful of units and most slices are such workgroups.
+    const uint32_t H = MODE == kScoreLead ? min(*as_uniform(num_hyp_ptr), lead) : *as_uniform(num_hyp_ptr);
+    const uint32_t waves_per_chunk = nslices * kWaves;
+    {
+        uint32_t kb0, gn0;
+        if (!unit_of_ticket<32u>(slice * kWaves, H, waves_per_chunk, kb0, gn0))
+            return;
+    }
+
     // ---- stationary operand: PG groups of 32 correspondences; lane l carries column l % 32 of every group ----
     // The per-point data of the PG tiles live in LDS, not in registers: the tile loop below is a real loop (an
     // unrolled one makes the register allocator give every tile its own 16 accumulators and spill the rest).
@@ -1398,11 +1408,9 @@ __device__ __forceinline__ void score_mfma_body(const PointSet &pts, const uint4
         s_next_unit = 0;
     __syncthreads(); // the only workgroup barrier
 
-    const uint32_t H = MODE == kScoreLead ? min(*as_uniform(num_hyp_ptr), lead) : *as_uniform(num_hyp_ptr);
     uint16_t *const queue = s_queue[wave];
     double *const acc_s = s_acc_s[wave];
     uint32_t *const acc_c = s_acc_c[wave];
-    const uint32_t waves_per_chunk = nslices * kWaves;
     auto request_ticket = [&]() -> uint32_t { // per-lane value; lane 0 holds the workgroup's next unit
         uint32_t t = 0;
         if (lane == 0) {
@@ -1542,6 +1550,17 @@ __device__ __forceinline__ void score_count_body(uint32_t n_points, const uint4 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int col = lane & 31, half = lane >> 5;
+    // (as score_mfma_body: no staging for a workgroup without a unit)
+    const uint32_t Hall = *as_uniform(num_hyp_ptr);
+    if (Hall <= first)
+        return;
+    const uint32_t H = Hall - first;
+    const uint32_t waves_per_chunk = nslices * kWaves;
+    {
+        uint32_t kb0, gn0;
+        if (!unit_of_ticket<32u>(slice * kWaves, H, waves_per_chunk, kb0, gn0))
+            return;
+    }
     uint32_t validbits = 0; // bit (PG - 1 - g): group g holds a real correspondence in this column
 #pragma unroll
     for (int g = 0; g < PG; ++g)
@@ -1556,12 +1575,7 @@ __device__ __forceinline__ void score_count_body(uint32_t n_points, const uint4 
         s_next_unit = 0;
     __syncthreads(); // the only workgroup barrier
 
-    const uint32_t Hall = *as_uniform(num_hyp_ptr);
-    if (Hall <= first)
-        return;
-    const uint32_t H = Hall - first;
     uint32_t *const cnt = s_cnt[wave];
-    const uint32_t waves_per_chunk = nslices * kWaves;
     auto request_ticket = [&]() -> uint32_t { // per-lane value; lane 0 holds the workgroup's next unit
         uint32_t t = 0;
         if (lane == 0) {
@@ -1654,8 +1668,9 @@ __global__ __launch_bounds__(kMfmaThreads) __attribute__((amdgpu_waves_per_eu(4,
 // k_prune_list against EVERY chunk, the exact scorer.  c* sits in device memory, the grid is the host's: no synchronisation between
 // them.  A member of a group's table whose step does not prune (prune.st == nullptr) is scored by the kScoreSel launch alone: its
 // whole list, every chunk.
-// Hypothesis slices per chunk of the launches, from the slices of the plain launch: every workgroup of the exact scorer holds a
-// resident slot (55 KB of LDS) from its dispatch on, also one that finds no unit or returns at once.  The lead has 32 units of 64
+// Hypothesis slices per chunk of the launches, from the slices of the plain launch: a workgroup of the exact scorer that has a
+// unit holds a resident slot (55 KB of LDS) while it stages and scores; one whose first ticket finds no unit returns before the
+// staging (score_mfma_body), so slices beyond the list's units cost a dispatch and a scalar load.  The lead has 32 units of 64
 // hypotheses per chunk - two workgroups of 8 wavefronts; the exact launch has the lead and the few per cent that the counts could not
 // exclude: a quarter of the slices (profiles/score_prune.md, profiles/score_count.md).  Which wavefront scores a unit has no
 // influence on its result.
@@ -1870,49 +1885,94 @@ __global__ __launch_bounds__(1024) void k_prune_list_g(const GroupArgs *ga) {
 // Behind the pre-selection the list holds the lead - its first min(H, lead) entries, the list ascends - and the positions the
 // survivor counts could not exclude: mostly hypotheses of three inlier samples, a thousand inliers each, nearly all of which lose
 // against the lead's best and would go through the fp64 exact pass pair by pair only to be told so.  k_score_bound: a dense fp32
-// pass over list entries, no matrix instructions, no queue, no fp64.  A workgroup owns a chunk of 64 P correspondences, every
-// wavefront keeps them in registers (fp32 copies and the per-point slack, as k_score_queue) and takes units of 64 list entries with
-// the launch's stride: lane l fetches entry l's fp32 shadow from its record, the wavefront then walks the 64 models through
-// v_readlane.  Per (entry, chunk) it writes an upper bound of the inliers into the count column and a lower bound of the chunk's
-// share of the score, an INTEGER number of quanta of thr^2 2^-20 stored as an exact double (at most 320 * 2^20, whatever the order
-// of the sum), into the score column.  Two stages, each followed by k_prune_bound:
-//   RESID = false, the entries behind the lead: pf_abs_outlier's verdict alone, two points per packed fp32 instruction as in
-//     k_score_queue - a proven outlier's share is thr^2 exactly (2^20 quanta), every other pair may be an inlier and shares 0.
-//     Ballots and scalar popcounts: no division, no per-lane value, no lane reduction.
-//   RESID = true, what stage one left undecided (the whole list: the lead has left it): pf_abs_r2_lower gives L <= r^2 per pair;
+// pass over list entries, no matrix instructions, no queue, no fp64, and ONE launch for both stages of the tier.  A workgroup of 8
+// wavefronts owns a unit of 64 list entries behind the lead (units go to the member's kBoundGroups workgroups with a fixed stride,
+// no atomics; a workgroup without a unit returns before it touches a correspondence).  Wavefront w owns chunk w of 64 P
+// correspondences and keeps them in registers (fp32 copies and the per-point slack, as k_score_queue); a member with more than 8
+// chunks - the flagship has 16 - lets it walk the chunks w, w + 8, ..., reloading the correspondences for each and accumulating.  Lane l of every wavefront
+// fetches entry l's fp32 shadow from its record, the wavefront then walks models through v_readlane.  Per entry a wavefront leaves
+// an upper bound of the inliers of its chunks and a lower bound of their share of the score - an INTEGER number of quanta of
+// thr^2 2^-20, at most 320 * 2^20 per chunk - in LDS; behind a barrier wavefront 0 adds the 8 partials of every entry (integer sums:
+// the order and the chunking do not matter) and applies the rule below.  Two stages per unit:
+//   0, every entry of the unit: pf_abs_outlier's verdict alone, two points per packed fp32 instruction as in k_score_queue - a
+//     proven outlier's share is thr^2 exactly (2^20 quanta), every other pair may be an inlier and shares 0.  Ballots and scalar
+//     popcounts: no division, no per-lane value, no lane reduction.
+//   1, what stage 0 left undecided, compacted within the workgroup (about a sixth): pf_abs_r2_lower gives L <= r^2 per pair;
 //     pairs with L < thr^2 are counted, min(L, thr^2) / thr^2 in truncated quanta is summed over the lanes.
-// The columns of those entries hold survivor counts or an earlier step's values at this point; the exact launch overwrites the
-// columns of what k_prune_bound keeps.  Grids from the host, lengths from device memory: no synchronisation.
-constexpr int kBoundThreads = 256;
-template <int P, bool RESID>
-__device__ __forceinline__ void score_bound_body(const ScoreArgs &a, uint32_t slice, uint32_t chunk, uint32_t nslices) {
+// The rule of both stages: with c_ub the sum of the counts and s_lb = thr^2 2^-20 sum q rounded DOWN, c <= c_ub and s >= s_lb hold
+// for the exact count and score, so an entry with c_ub <= lead_max and s_lb > lead_min (1 + kPruneScoreMargin) is no candidate of
+// k_records (prune_rule's argument): kept[] = kDropped.  bnd_count / bnd_score (where set) hold the values of the last stage that
+// saw the entry.  Nothing goes to the partial columns: they keep survivor counts or an earlier step's values until the exact launch
+// overwrites the columns of what stays.  An entry's decision is complete inside one workgroup; k_prune_bound, the next launch,
+// rebuilds the list.  Grids from the host, lengths from device memory: no synchronisation.
+// Eight wavefronts, not sixteen: a workgroup of 1024 threads at this kernel's 119 VGPRs needs every SIMD of a compute unit nearly
+// empty at once, and next to the other groups' count launches (two workgroups of 8 wavefronts and 128 VGPRs per compute unit) the
+// dispatcher refills a half-empty unit before the other half drains - the launch stood 969 us in flight for 100 us of work.  Half
+// the size fits the slot one count workgroup leaves.  Measured next to each other (profiles/bound_fused.md): 16 wavefronts - the
+// parent's speed; 16 capped at 64 VGPRs - +1 %, with 52 spilled registers; 4 - +2.7 %; 8 - +3.9 %.
+constexpr int kBoundThreads = 512;
+// Workgroups per member: the flagship's members hold about 14 units behind the lead (profiles/bound_fused.md), so every unit has
+// a workgroup of its own there; longer lists walk with this stride.
+constexpr uint32_t kBoundGroups = 16;
+template <int P> __device__ __forceinline__ void score_bound_body(const ScoreArgs &a, uint32_t wg, uint32_t nwg) {
     constexpr int kWaves = kBoundThreads / 64;
     constexpr uint32_t NPW = 64u * P;
+    __shared__ uint32_t s_c[kWaves][64];
+    __shared__ uint64_t s_q[kWaves][64];
+    __shared__ uint32_t s_und[64]; // the unit's entries that stage 0 left undecided, ascending
+    __shared__ uint32_t s_nund;
     const PruneArgs &pr = a.prune;
     if (!pr.st || !pr.bound || *as_uniform(&pr.st->cstar) >= pr.chunks)
         return;
-    const uint32_t first = RESID ? 0u : min(*as_uniform(a.num_hyp), pr.lead), len = *as_uniform(&pr.st->sel_len);
-    if (len <= first)
+    const uint32_t first = min(*as_uniform(a.num_hyp), pr.lead), len = *as_uniform(&pr.st->sel_len);
+    if (len <= first || (uint64_t)wg * 64u >= len - first)
         return;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const PrefilterArgs pf = a.pf;
+    const uint32_t chunks = pr.chunks;
+    const bool resident = chunks <= (uint32_t)kWaves; // every wavefront has at most one chunk: loaded once, for every unit
     float x[P], y[P], X[P], Y[P], Z[P], fw[P];
     bool valid[P];
     uint64_t vmask[P]; // lanes of slot p that hold a real correspondence
+    auto load_chunk = [&](uint32_t chunk) {
 #pragma unroll
-    for (int p = 0; p < P; ++p) {
-        const uint32_t i = chunk * NPW + (uint32_t)p * 64u + (uint32_t)lane;
-        valid[p] = i < a.pts.n;
-        vmask[p] = __builtin_amdgcn_ballot_w64(valid[p]);
-        const uint32_t ic = valid[p] ? i : 0u;
-        const double Xd = a.pts.a[2][ic], Yd = a.pts.a[3][ic], Zd = a.pts.a[4][ic];
-        x[p] = (float)a.pts.a[0][ic], y[p] = (float)a.pts.a[1][ic];
-        X[p] = (float)Xd, Y[p] = (float)Yd, Z[p] = (float)Zd;
-        fw[p] = pf_point_abs(Xd, Yd, Zd, pf.gx);
-    }
+        for (int p = 0; p < P; ++p) {
+            const uint32_t i = chunk * NPW + (uint32_t)p * 64u + (uint32_t)lane;
+            valid[p] = i < a.pts.n;
+            vmask[p] = __builtin_amdgcn_ballot_w64(valid[p]);
+            const uint32_t ic = valid[p] ? i : 0u;
+            const double Xd = a.pts.a[2][ic], Yd = a.pts.a[3][ic], Zd = a.pts.a[4][ic];
+            x[p] = (float)a.pts.a[0][ic], y[p] = (float)a.pts.a[1][ic];
+            X[p] = (float)Xd, Y[p] = (float)Yd, Z[p] = (float)Zd;
+            fw[p] = pf_point_abs(Xd, Yd, Zd, pf.gx);
+        }
+    };
+    load_chunk(min((uint32_t)wave, chunks - 1u)); // (a wavefront without a chunk holds a copy it never evaluates)
+    const uint32_t lead_max = pr.st->lead_max;
+    const double beat = pr.st->lead_min * (1.0 + kPruneScoreMargin);
+    // wavefront 0, lane l: the sums of entry l over the wavefronts' partials and the rule; true: the entry stays
+    auto decide = [&](uint32_t pos) -> bool {
+        uint32_t c = 0;
+        uint64_t q = 0;
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w) {
+            c += s_c[w][lane];
+            q += s_q[w][lane];
+        }
+        const double qd = (double)q * 9.5367431640625e-07; // (2^-20: exact)
+        double s_lb = a.thr2 * qd;
+        if (fma(a.thr2, qd, -s_lb) < 0.0) // the product was rounded up (then it is positive): its predecessor
+            s_lb = __longlong_as_double(__double_as_longlong(s_lb) - 1);
+        const bool keep = !(c <= lead_max && s_lb > beat);
+        if (!keep)
+            pr.kept[pos] = kDropped;
+        if (pr.bnd_count)
+            pr.bnd_count[pos] = c, pr.bnd_score[pos] = s_lb;
+        return keep;
+    };
     const uint32_t nent = len - first;
-    for (uint32_t u = slice * kWaves + (uint32_t)wave; u * 64u < nent; u += nslices * kWaves) {
+    for (uint32_t u = wg; (uint64_t)u * 64u < nent; u += nwg) { // (workgroup-uniform: the barriers below are reached by all)
         const uint32_t e = first + u * 64u + (uint32_t)lane;
         const uint32_t pos = pr.sel[min(e, len - 1u)];
         const float4 *sh = reinterpret_cast<const float4 *>(a.models + (size_t)a.slots[pos] * kModelStride + kShadowOff);
@@ -1921,9 +1981,7 @@ __device__ __forceinline__ void score_bound_body(const ScoreArgs &a, uint32_t sl
         for (int k = 0; k < 4; ++k)
             rv[k] = sh[k];
         const uint32_t n = min(64u, nent - u * 64u);
-        uint32_t my_c = 0, my_q = 0;
-        for (uint32_t j = 0; j < n; ++j) {
-            float r[16];
+        auto model_of_lane = [&](uint32_t j, float (&r)[16]) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 r[4 * k + 0] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rv[k].x), (int)j));
@@ -1931,17 +1989,18 @@ __device__ __forceinline__ void score_bound_body(const ScoreArgs &a, uint32_t sl
                 r[4 * k + 2] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rv[k].z), (int)j));
                 r[4 * k + 3] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rv[k].w), (int)j));
             }
-            const float gt = pf_abs_bound_slack(r, pf.gx);
-            uint32_t c = 0, q = 0;
-            if constexpr (RESID) {
-#pragma unroll
-                for (int p = 0; p < P; ++p) {
-                    const float L = pf_abs_r2_lower(r, gt, x[p], y[p], X[p], Y[p], Z[p], fw[p]);
-                    c += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(valid[p] && L < pf.thr2_up));
-                    q += valid[p] ? pf_bound_quantum(L, pf.inv_thr2_dn) : 0u;
-                }
-                q = (uint32_t)__builtin_amdgcn_readlane((int)wave_scan_u32(q), 63);
-            } else {
+        };
+        // ---- stage 0: the verdict of every entry against the wavefront's chunks ----
+        uint32_t my_c = 0;
+        uint64_t my_q = 0;
+        for (uint32_t ch = (uint32_t)wave; ch < chunks; ch += (uint32_t)kWaves) {
+            if (!resident)
+                load_chunk(ch);
+            for (uint32_t j = 0; j < n; ++j) {
+                float r[16];
+                model_of_lane(j, r);
+                const float gt = pf_abs_bound_slack(r, pf.gx);
+                uint32_t c = 0, q = 0;
 #pragma unroll
                 for (int p = 0; p + 1 < P; p += 2) {
                     const v2f Xp = {X[p], X[p + 1]}, Yp = {Y[p], Y[p + 1]}, Zp = {Z[p], Z[p + 1]};
@@ -1967,47 +2026,75 @@ __device__ __forceinline__ void score_bound_body(const ScoreArgs &a, uint32_t sl
                     q += (uint32_t)__popcll(out);
                     c += (uint32_t)__popcll(vmask[p] & ~out);
                 }
-                q <<= 20; // (kPfBoundScale quanta per proven outlier)
+                if ((uint32_t)lane == j)
+                    my_c += c, my_q += q; // (proven outliers: kPfBoundScale quanta each, below)
             }
-            if ((uint32_t)lane == j)
-                my_c = c, my_q = q;
         }
-        if ((uint32_t)lane < n) {
-            const size_t o = (size_t)chunk * a.hyp_capacity + pos;
-            a.part_count[o] = my_c;
-            a.part_score[o] = (double)my_q;
+        s_c[wave][lane] = my_c;
+        s_q[wave][lane] = my_q << 20;
+        __syncthreads();
+        bool open = false; // wavefront 0, lane l: entry l is undecided
+        if (wave == 0) {
+            open = (uint32_t)lane < n && decide(pos);
+            const uint64_t und = __builtin_amdgcn_ballot_w64(open);
+            if (open)
+                s_und[__builtin_amdgcn_mbcnt_hi((uint32_t)(und >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)und, 0u))] = (uint32_t)lane;
+            if (lane == 0)
+                s_nund = (uint32_t)__popcll(und);
         }
+        __syncthreads(); // (also: the partials of stage 0 are read)
+        // ---- stage 1: residual bounds of the undecided entries, the correspondences still in registers ----
+        const uint32_t nund = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_nund);
+        if (nund) { // workgroup-uniform
+            my_c = 0, my_q = 0;
+            for (uint32_t ch = (uint32_t)wave; ch < chunks; ch += (uint32_t)kWaves) {
+                if (!resident)
+                    load_chunk(ch);
+                for (uint32_t k = 0; k < nund; ++k) {
+                    const uint32_t j = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_und[k]);
+                    float r[16];
+                    model_of_lane(j, r);
+                    const float gt = pf_abs_bound_slack(r, pf.gx);
+                    uint32_t c = 0, q = 0;
+#pragma unroll
+                    for (int p = 0; p < P; ++p) {
+                        const float L = pf_abs_r2_lower(r, gt, x[p], y[p], X[p], Y[p], Z[p], fw[p]);
+                        c += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(valid[p] && L < pf.thr2_up));
+                        q += valid[p] ? pf_bound_quantum(L, pf.inv_thr2_dn) : 0u;
+                    }
+                    q = (uint32_t)__builtin_amdgcn_readlane((int)wave_scan_u32(q), 63);
+                    if ((uint32_t)lane == j)
+                        my_c += c, my_q += q;
+                }
+            }
+            s_c[wave][lane] = my_c;
+            s_q[wave][lane] = my_q;
+            __syncthreads();
+            if (open)
+                (void)decide(pos);
+        }
+        __syncthreads(); // (the next unit writes the partials and the list of the undecided)
     }
 }
-template <int P, bool RESID> __global__ __launch_bounds__(kBoundThreads) void k_score_bound(ScoreArgs a) {
-    uint32_t slice, chunk;
-    slice_chunk_of_workgroup(gridDim.x, gridDim.y, slice, chunk);
-    score_bound_body<P, RESID>(a, slice, chunk, gridDim.x);
-}
-template <bool RESID> __global__ __launch_bounds__(kBoundThreads) void k_score_bound_g(const GroupArgs *ga) {
+template <int P> __global__ __launch_bounds__(kBoundThreads) void k_score_bound(ScoreArgs a) { score_bound_body<P>(a, blockIdx.x, gridDim.x); }
+__global__ __launch_bounds__(kBoundThreads) void k_score_bound_g(const GroupArgs *ga) {
     const GroupArgs &g = ga[blockIdx.z];
-    uint32_t slice, chunk;
-    const uint32_t ns = pruned_slices<kScoreSel>(g.slices);
-    if (!g.active || !g.use_mfma || !g.score.prune.st || !slice_chunk_of_workgroup(ns, g.chunks, slice, chunk))
+    if (!g.active || !g.use_mfma || !g.score.prune.st)
         return;
-    score_bound_body<5, RESID>(globalised(g.score), slice, chunk, ns);
+    score_bound_body<5>(globalised(g.score), blockIdx.x, gridDim.x);
 }
-// k_prune_bound, one workgroup per problem, behind each stage of k_score_bound: per entry the bounds of all chunks, c_ub and
-// s_lb = thr^2 2^-20 sum q rounded DOWN.  c <= c_ub and s >= s_lb for the exact count and score, so an entry with c_ub <= lead_max
-// and s_lb > lead_min (1 + kPruneScoreMargin) is no candidate of k_records (prune_rule's argument): it is dropped, kept[] = kDropped.
-// The list is rebuilt in place, ascending.  Stage 0 starts behind the lead and writes from position 0: the lead leaves the list
-// - it stays kKept and keeps the columns the lead launch wrote, the exact launch does not score it a second time; a list that holds
-// nothing but the lead ends with length 0.  Stage 1 covers the whole list stage 0 left.  In place: tile by tile (1024 entries, all
-// read before the barrier) the entry at e goes to a position <= e, which is in this tile or an earlier one - whatever the lead's
-// length.  With c* = chunks the lead's values drop nothing and the tier does nothing: the list stays k_prune_list's, lead included.
-__device__ __forceinline__ void prune_bound_body(const ScoreArgs &a, int stage) {
+// k_prune_bound, one workgroup per problem, behind k_score_bound: the list is rebuilt from the kept[] byte of every entry, in place,
+// ascending.  It starts behind the lead and writes from position 0: the lead leaves the list - it stays kKept and keeps the columns
+// the lead launch wrote, the exact launch does not score it a second time; a list that holds nothing but the lead ends with length
+// 0.  In place: tile by tile (1024 entries, all read before the barrier) the entry at e goes to a position <= e, which is in this
+// tile or an earlier one - whatever the lead's length.  With c* = chunks the lead's values drop nothing and the tier does nothing:
+// the list stays k_prune_list's, lead included.
+__device__ __forceinline__ void prune_bound_body(const ScoreArgs &a) {
     __shared__ uint32_t wt[16];
     const PruneArgs &pr = a.prune;
     if (!pr.bound || pr.st->cstar >= pr.chunks)
         return;
-    const uint32_t first = stage ? 0u : min(*a.num_hyp, pr.lead), len = pr.st->sel_len;
-    const uint32_t lead_max = pr.st->lead_max;
-    const double beat = pr.st->lead_min * (1.0 + kPruneScoreMargin);
+    const uint32_t first = min(*a.num_hyp, pr.lead), len = pr.st->sel_len;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint32_t base = 0;
     __syncthreads(); // (every thread holds the list's length before thread 0 writes the new one)
@@ -2016,22 +2103,7 @@ __device__ __forceinline__ void prune_bound_body(const ScoreArgs &a, int stage) 
         uint32_t keep = 0, p = 0;
         if (e < len) {
             p = pr.sel[e];
-            uint32_t c = 0;
-            uint64_t q = 0;
-#pragma unroll 8
-            for (uint32_t ch = 0; ch < pr.chunks; ++ch) {
-                c += a.part_count[(size_t)ch * a.hyp_capacity + p];
-                q += (uint64_t)a.part_score[(size_t)ch * a.hyp_capacity + p];
-            }
-            const double qd = (double)q * 9.5367431640625e-07; // (2^-20: exact)
-            double s_lb = a.thr2 * qd;
-            if (fma(a.thr2, qd, -s_lb) < 0.0) // the product was rounded up (then it is positive): its predecessor
-                s_lb = __longlong_as_double(__double_as_longlong(s_lb) - 1);
-            keep = (c <= lead_max && s_lb > beat) ? 0u : 1u;
-            if (!keep)
-                pr.kept[p] = kDropped;
-            if (pr.bnd_count)
-                pr.bnd_count[p] = c, pr.bnd_score[p] = s_lb;
+            keep = pr.kept[p] != kDropped ? 1u : 0u;
         }
         const uint32_t inc = wave_scan_u32(keep);
         if (lane == 63)
@@ -2050,12 +2122,12 @@ __device__ __forceinline__ void prune_bound_body(const ScoreArgs &a, int stage) 
     if (threadIdx.x == 0)
         pr.st->sel_len = base;
 }
-__global__ __launch_bounds__(1024) void k_prune_bound(ScoreArgs a, int stage) { prune_bound_body(a, stage); }
-__global__ __launch_bounds__(1024) void k_prune_bound_g(const GroupArgs *ga, int stage) {
+__global__ __launch_bounds__(1024) void k_prune_bound(ScoreArgs a) { prune_bound_body(a); }
+__global__ __launch_bounds__(1024) void k_prune_bound_g(const GroupArgs *ga) {
     const GroupArgs &g = ga[blockIdx.z];
     if (!g.active || !g.use_mfma || !g.score.prune.st)
         return;
-    prune_bound_body(globalised(g.score), stage);
+    prune_bound_body(globalised(g.score));
 }
 
 
@@ -4375,10 +4447,8 @@ template <int PG> static hipError_t launch_score_pruned_pg(const ScoreArgs &a, d
     if (e != hipSuccess)
         return e;
     if (a.prune.bound) { // bounds of the pre-selected positions behind the lead, and the list without the lead and what they drop
-        k_score_bound<PG / 2, false><<<sel_grid, dim3(kBoundThreads), 0, stream>>>(a);
-        k_prune_bound<<<dim3(1), dim3(1024), 0, stream>>>(a, 0);
-        k_score_bound<PG / 2, true><<<sel_grid, dim3(kBoundThreads), 0, stream>>>(a);
-        k_prune_bound<<<dim3(1), dim3(1024), 0, stream>>>(a, 1);
+        k_score_bound<PG / 2><<<dim3(kBoundGroups), dim3(kBoundThreads), 0, stream>>>(a);
+        k_prune_bound<<<dim3(1), dim3(1024), 0, stream>>>(a);
     }
     k_score_mfma_pr<PG, kScoreSel><<<sel_grid, block, 0, stream>>>(a);
     return hipGetLastError();
@@ -4612,10 +4682,8 @@ template <int E> static hipError_t launch_group_score_est(const GroupArgs *args,
             if (e != hipSuccess)
                 return e;
             if (d.any_bound) { // (as launch_score_pruned_pg)
-                k_score_bound_g<false><<<sel_grid, dim3(kBoundThreads), 0, stream>>>(args);
-                k_prune_bound_g<<<dim3(1, 1, d.G), dim3(1024), 0, stream>>>(args, 0);
-                k_score_bound_g<true><<<sel_grid, dim3(kBoundThreads), 0, stream>>>(args);
-                k_prune_bound_g<<<dim3(1, 1, d.G), dim3(1024), 0, stream>>>(args, 1);
+                k_score_bound_g<<<dim3(kBoundGroups, 1, d.G), dim3(kBoundThreads), 0, stream>>>(args);
+                k_prune_bound_g<<<dim3(1, 1, d.G), dim3(1024), 0, stream>>>(args);
             }
             k_score_mfma_pr_g<10, kScoreSel><<<sel_grid, dim3(kMfmaThreads), 0, stream>>>(args);
         } else if (d.any_mfma)
