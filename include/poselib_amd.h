@@ -625,6 +625,13 @@ int pl_debug_score_bounded(int route, pl_debug_prune_member *members, size_t num
 /* Diagnostic: 1 if a batch step of `iterations` iterations of a problem of `kind` with n_points correspondences, as a member of a
  * lock-step group (pl_ransac_batch, pl_estimate_batch), scores in the pruned form, 0 if not; pl_ransac_run's own steps never do (coordinates and threshold in the pre-filter's range assumed, as pl_debug_group_slices).  Host arithmetic only. */
 int pl_debug_score_prune_gate(int kind, uint32_t n_points, uint32_t iterations);
+/* Diagnostic: the kernel that refines ONE camera-less job of max_iterations LM iterations on a problem of `kind` with n_points
+ * correspondences (pl_refine_model, a local optimisation of pl_ransac_run) under the process's current LM mode (pl_set_lm_mode) and
+ * latency setting (POSELIB_AMD_LATENCY_MODE, read once): 0 k_lm - one workgroup; sums in the reference's order up to 256
+ * correspondences, tree sums beyond -, 1 k_lm_ordered - every sum in the reference's order -, 2 k_lm2 - *slices workgroups per
+ * task, one launch per iteration; *slices is 0 for the other two.  The function the driver itself asks.  PL_ERR_INVALID: unknown
+ * kind, n_points 0, slices NULL.  Host arithmetic only: no device is touched. */
+int pl_debug_lm_route(int kind, uint32_t n_points, uint64_t max_iterations, uint32_t *slices);
 /* Diagnostic: the shape of the device sampler (k_sample_delta / k_sample_orbit) for a batch of B iterations of samples of K out of N
  * correspondences.  window: the draw positions a batch step evaluates, as the driver sizes them (the argument `window` 0), or the
  * caller's.  build: the build of the orbit kernel the launcher picks for (window, N, K) - 1 small, 2 large; a group's launch picks

@@ -843,6 +843,13 @@ def score_prune_gate(kind: int, n_points: int, iterations: int) -> bool:
     return bool(L.check(L.lib().pl_debug_score_prune_gate(int(kind), int(n_points), int(iterations))))
 
 
+def lm_route(kind: int, n_points: int, max_iterations: int = 100):
+    """Diagnostic (pl_debug_lm_route): (route, slices) of one camera-less refinement job under the current LM mode and latency
+    setting - route 0 k_lm, 1 k_lm_ordered, 2 k_lm2 on `slices` workgroups.  Host arithmetic only: works without a device."""
+    slices = C.c_uint32(0)
+    return L.check(L.lib().pl_debug_lm_route(int(kind), int(n_points), int(max_iterations), C.byref(slices))), slices.value
+
+
 def score_pruned(members, route=0):
     """Diagnostic (pl_debug_score_pruned): the pruned form of the matrix-core absolute-pose scorer on caller-given lists.
     members: (problem, models, max_error, init_max, init_min) - one for route 0 (single launches), up to four for route 2 (group

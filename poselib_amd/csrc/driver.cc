@@ -359,23 +359,12 @@ void params_from_record(int kind, const double *rec, double *params) {
 void lm_params_from_record(int kind, const double *rec, double *params) {
     params_from_record(kind, rec, params);
     if (kind == EST_FUND) { // factorise F = U diag(1, sigma, 0) V^T  (bundle.cc:318-319)
-        Mat3 F, U, V;
+        Mat3 F;
         for (int i = 0; i < 9; ++i)
             F.m[i] = rec[kMatOff + i];
-        double s[3];
-        svd3(F, U, s, V);
-        if (det3(U) < 0)
-            for (int i = 0; i < 9; ++i)
-                U.m[i] = -U.m[i];
-        if (det3(V) < 0)
-            for (int i = 0; i < 9; ++i)
-                V.m[i] = -V.m[i];
-        const Quat qU = rotmat_to_quat(U), qV = rotmat_to_quat(V);
         for (int i = 0; i < kParamDoubles; ++i)
             params[i] = 0.0;
-        params[0] = qU.w, params[1] = qU.x, params[2] = qU.y, params[3] = qU.z;
-        params[4] = qV.w, params[5] = qV.x, params[6] = qV.y, params[7] = qV.z;
-        params[8] = s[1] / s[0];
+        fundamental_lm_params(F, params);
     }
 }
 void identity_record(int kind, double *rec) {
@@ -797,6 +786,33 @@ int context_batch_buffers(Context *c, const BatchSizes &z, BatchBuffers &b) {
     return PL_OK;
 }
 
+// Which kernel refines the camera-less jobs of one launch on a problem of `n` correspondences: 0 k_lm, 1 k_lm_ordered, 2 k_lm2 with
+// `slices` workgroups per task.  run_refinements and the diagnostic pl_debug_lm_route both ask here.
+// Large point sets with 6..8 parameters saturate the single CU k_lm gives a task; k_lm2 spreads every task over
+// several workgroups (one launch per LM iteration; only for short, bounded runs - the LO: 25 iterations - since it
+// costs max_iterations + 2 launches whatever the iteration count turns out to be).  Measured on MI355X at N = 10^4:
+// homography problems 2.2x, fundamental 1.5x shorter when the device serves one problem at a time; with many
+// problems in flight the long single-CU kernels overlap anyway and the extra launches cost throughput.  The two
+// kernels sum the normal equations in different orders (results agree to rounding, not to the bit), so the choice
+// must not depend on load or on the entry point: it is a process-wide setting, OFF by default - the grouped launches
+// of pl_estimate_batch refine with k_lm, and a problem gives the same bits whichever way it is submitted -,
+// POSELIB_AMD_LATENCY_MODE=1 switches it on for single large two-view problems.
+struct LMRoute {
+    int kernel;
+    uint32_t slices;
+};
+LMRoute lm_route(int kind, uint32_t n, bool same_it, uint32_t max_it) {
+    static const bool latency_mode = [] {
+        const char *e = std::getenv("POSELIB_AMD_LATENCY_MODE");
+        return e && e[0] == '1';
+    }();
+    const bool ordered = lm_sums_ordered(kind);
+    const uint32_t lm2_min_points = (kind == EST_ABS) ? 8192u : 2560u;
+    if (latency_mode && kind != EST_REL && kind != EST_RELT && kind != EST_RAD1D && !ordered && same_it && max_it >= 1 && max_it <= 32 && n >= lm2_min_points)
+        return {2, std::min<uint32_t>(16u, std::max<uint32_t>(2u, n / 512u))};
+    return {ordered ? 1 : 0, 0u};
+}
+
 struct RefineJob {
     double record_in[kModelStride]; // seed model
     LMOptions opt;
@@ -840,32 +856,19 @@ int run_refinements(Context *c, const pl_problem *p, std::vector<RefineJob> &job
     HIP_TRY(c->h_tasks.ensure(stage_bytes));
     HIP_TRY(c->lm_scratch.ensure((size_t)p->n * nj + 16));
     HIP_TRY(c->lm_records.ensure(sizeof(double) * kModelStride * nj));
-    // Large point sets with 6..8 parameters saturate the single CU k_lm gives a task; k_lm2 spreads every task over
-    // several workgroups (one launch per LM iteration; only for short, bounded runs - the LO: 25 iterations - since it
-    // costs max_iterations + 2 launches whatever the iteration count turns out to be).  Measured on MI355X at N = 10^4:
-    // homography problems 2.2x, fundamental 1.5x shorter when the device serves one problem at a time; with many
-    // problems in flight the long single-CU kernels overlap anyway and the extra launches cost throughput.  The two
-    // kernels sum the normal equations in different orders (results agree to rounding, not to the bit), so the choice
-    // must not depend on load or on the entry point: it is a process-wide setting, OFF by default - the grouped launches
-    // of pl_estimate_batch refine with k_lm, and a problem gives the same bits whichever way it is submitted -,
-    // POSELIB_AMD_LATENCY_MODE=1 switches it on for single large two-view problems.
-    static const bool latency_mode = [] {
-        const char *e = std::getenv("POSELIB_AMD_LATENCY_MODE");
-        return e && e[0] == '1';
-    }();
     uint32_t max_it = 0;
     bool same_it = true;
     for (uint32_t j = 0; j < nj; ++j) {
         same_it = same_it && (j == 0 || jobs[j].opt.max_iterations == max_it);
         max_it = std::max(max_it, jobs[j].opt.max_iterations);
     }
-    const uint32_t lm2_min_points = (p->kind == EST_ABS) ? 8192u : 2560u;
     bool with_camera = false;
     for (uint32_t j = 0; j < nj; ++j)
         with_camera = with_camera || jobs[j].cam_flags != 0;
     if (with_camera && p->kind != EST_ABS)
         return fail(PL_ERR_INVALID, "camera intrinsics are refined with absolute poses only");
-    const bool use_lm2 = !with_camera && latency_mode && p->kind != EST_REL && p->kind != EST_RELT && p->kind != EST_RAD1D && !lm_sums_ordered(p->kind) && same_it && max_it >= 1 && max_it <= 32 && p->n >= lm2_min_points;
+    const LMRoute route = lm_route(p->kind, p->n, same_it, max_it);
+    const bool use_lm2 = !with_camera && route.kernel == 2;
     if (use_lm2)
         HIP_TRY(c->lm_tasks.ensure(stage_bytes));
     LMTask *ht = c->h_tasks.as<LMTask>();
@@ -893,11 +896,14 @@ int run_refinements(Context *c, const pl_problem *p, std::vector<RefineJob> &job
         std::memcpy(hr + (size_t)nj * kModelStride, tail->incumbent_rec, sizeof(double) * kModelStride);
     if (use_lm2) {
         HIP_TRY(hipMemcpyAsync(c->lm_tasks.p, ht, stage_bytes, hipMemcpyHostToDevice, c->stream));
-        const uint32_t slices = std::min<uint32_t>(16u, std::max<uint32_t>(2u, p->n / 512u));
+        const uint32_t slices = route.slices;
         HIP_TRY(c->lm2_states.ensure(lm2_state_bytes(nj)));
         HIP_TRY(c->lm2_partials.ensure(lm2_partial_bytes(nj, slices)));
-        HIP_TRY(launch_lm2(p->kind, p->ps, d_tasks, nj, slices, max_it, c->lm2_states.p, c->lm2_partials.as<double>(),
-                           c->stream));
+        bool loss_changes = false; // between the iterations of a task: it then takes up to two launches per iteration
+        for (uint32_t j = 0; j < nj; ++j)
+            loss_changes = loss_changes || jobs[j].opt.loss_type == LOSS_TRUNCATED_LE_ZACH;
+        HIP_TRY(launch_lm2(p->kind, p->ps, d_tasks, nj, slices, max_it, loss_changes, c->lm2_states.p,
+                           c->lm2_partials.as<double>(), c->stream));
         // (k_task_records also writes the tasks' outputs into the pinned staging block: stream order puts that after the
         // upload above has read it)
         HIP_TRY(launch_task_records(p->kind, d_tasks, d_records_in, c->lm_records.as<double>(), nj,
@@ -3160,6 +3166,14 @@ int pl_debug_score_prune_gate(int kind, uint32_t n_points, uint32_t iterations) 
         return fail(PL_ERR_INVALID, "pl_debug_score_prune_gate: n_points > 0");
     const bool mfma = score_uses_mfma(kind, n_points, pf);
     return score_prune_gate(kind, mfma, iterations, kind == EST_ABS ? score_chunks(kind, n_points, true, mfma) : 1u) ? 1 : 0;
+}
+int pl_debug_lm_route(int kind, uint32_t n_points, uint64_t max_iterations, uint32_t *slices) {
+    const bool known = kind == EST_ABS || kind == EST_REL || kind == EST_FUND || kind == EST_HOM || kind == EST_RELT || kind == EST_RAD1D;
+    if (!known || n_points == 0 || !slices)
+        return fail(PL_ERR_INVALID, "pl_debug_lm_route: kind 0 .. 5, n_points > 0, slices pointer");
+    const LMRoute r = lm_route(kind, n_points, true, (uint32_t)std::min<uint64_t>(max_iterations, 0xffffffffu)); // (to_lm's clamp)
+    *slices = r.slices;
+    return r.kernel;
 }
 int pl_debug_score_stream(pl_problem *p, const void *models, size_t n, double max_error, uint32_t *counts,
                           double *scores, int32_t *path_used) {

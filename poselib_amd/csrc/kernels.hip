@@ -3919,12 +3919,15 @@ template <int EST> __global__ __launch_bounds__(kLMThreads, 2) void k_lm_ordered
 // out: one launch = "advance the LM state with the partial sums the previous launch left, then run the next pass over
 // my slice".  A pass evaluates the robust cost AND the normal equations at the same parameters (the trial point): if
 // the step is accepted these are exactly the normal equations lm_impl.h would compute next, if it is rejected they are
-// dropped and the previous ones are re-solved with the larger damping - so ONE launch per LM iteration.  Every
-// workgroup of a task reduces the same partials in the same order and runs the same scalar state machine
-// (pl_refine.h lm_begin / lm_solve / lm_update), so all of them arrive at the same state without talking to each
-// other; slice 0 stores it.  States and partials are double-buffered by launch parity.  The host enqueues
-// max_iterations + 2 launches; workgroups of finished tasks return at once.  No spinning, no inter-workgroup
-// synchronisation inside a launch.
+// dropped and the previous ones are re-solved with the larger damping - one launch per LM iteration (phase 3).
+// TRUNCATED_LE_ZACH is the exception: its mu grows after every iteration, so the trial point's normal equations, evaluated
+// with the old mu, are not the next iteration's.  Under that loss they are always dropped, and an accepted step is followed
+// by a pass at the new `cur` with the new mu (phase 2) before the next solve - two launches for an accepted iteration, one
+// for a rejected one, as k_lm's unfused sweeps.  Every workgroup of a task reduces the same partials in the same order and
+// runs the same scalar state machine (pl_refine.h lm_begin / lm_solve / lm_update), so all of them arrive at the same
+// state without talking to each other; slice 0 stores it.  States and partials are double-buffered by launch parity.  The
+// host enqueues max_iterations + 2 launches, 2 max_iterations + 2 where a task's loss is TRUNCATED_LE_ZACH; workgroups of
+// finished tasks return at once.  No spinning, no inter-workgroup synchronisation inside a launch.
 constexpr int kLM2Threads = 256;
 
 struct LM2State {
@@ -3932,7 +3935,7 @@ struct LM2State {
     double cur[kParamDoubles], trial[kParamDoubles];
     double normal[44]; // reduced [tri | Jtr] at `cur`
     uint32_t count;    // residuals with non-zero weight behind `normal`
-    int32_t phase;     // partials waiting for the next launch: 0 none, 1 pass at the start point, 3 pass at `trial`
+    int32_t phase;     // partials waiting for the next launch: 0 none, 1 pass at the start point, 2 pass at `cur`, 3 pass at `trial`
     int32_t finished;
     int32_t pad;
 };
@@ -3956,7 +3959,7 @@ __global__ __launch_bounds__(kLM2Threads) void k_lm2(PointSet pts, LMTask *tasks
     __shared__ RefineCtx ctx;
     __shared__ double sums[NV];
     __shared__ double scratch[kWaves][NV];
-    __shared__ int s_pass; // 0 nothing, 1 pass at cur, 3 pass at trial
+    __shared__ int s_pass; // 0 nothing, 1 and 2 pass at cur, 3 pass at trial
 
     if (threadIdx.x == 0) {
         if (first) {
@@ -4016,17 +4019,30 @@ __global__ __launch_bounds__(kLM2Threads) void k_lm2(PointSet pts, LMTask *tasks
                 solve_and_step(true);
             }
             break;
+        case 2: // normal equations at `cur` under the loss of the iteration that starts now (TRUNCATED_LE_ZACH, below)
+            take_normal();
+            solve_and_step(true);
+            break;
         default: { // cost and (speculative) normal equations at the trial point
+            // TRUNCATED_LE_ZACH changes the loss after every iteration (mu grows, bundle.cc:52-75): the trial point's normal
+            // equations were evaluated with the old mu and are not the next iteration's - as in k_lm (fuse == false) they are
+            // dropped, and an accepted step is followed by a pass at the new `cur` with the new mu: one launch more
+            const bool loss_changes = st.ctl.opt.loss_type == LOSS_TRUNCATED_LE_ZACH;
             const bool accepted = lm_update<K>(st.ctl, st.normal, sums[NT], cnt_res); // gradient of the OLD point
             if (accepted) {
                 for (int i = 0; i < kParamDoubles; ++i)
                     st.cur[i] = st.trial[i];
-                take_normal();
+                if (!loss_changes)
+                    take_normal();
             }
-            if (st.ctl.done)
+            if (st.ctl.done) {
                 finish = true;
-            else
+            } else if (accepted && loss_changes) {
+                next = 2;
+                st.phase = 2;
+            } else {
                 solve_and_step(accepted);
+            }
             break;
         }
         }
@@ -4779,17 +4795,18 @@ hipError_t launch_select_record(const double *score_refined, double incumbent_sc
     return hipGetLastError();
 }
 
-// Multi-workgroup LM (k_lm2): `slices` workgroups per task, max_iterations + 2 launches.
+// Multi-workgroup LM (k_lm2): `slices` workgroups per task, max_iterations + 2 launches - one more per iteration where a task's loss
+// changes between iterations (loss_changes: TRUNCATED_LE_ZACH), since an accepted step is then followed by a pass of its own.
 size_t lm2_state_bytes(uint32_t num_tasks) { return sizeof(LM2State) * 2 * (size_t)num_tasks; }
 size_t lm2_partial_bytes(uint32_t num_tasks, uint32_t slices) { return sizeof(double) * 2 * (size_t)num_tasks * slices * 48; }
 hipError_t launch_lm2(int est, const PointSet &pts, LMTask *tasks, uint32_t num_tasks, uint32_t slices,
-                      uint32_t max_iterations, void *states, double *partials, hipStream_t stream) {
+                      uint32_t max_iterations, bool loss_changes, void *states, double *partials, hipStream_t stream) {
     if (num_tasks == 0)
         return hipSuccess;
     if (est == EST_REL)
         return hipErrorInvalidValue; // the relative-pose LO (pre-filter, tangent basis) stays on k_lm
     const dim3 grid(slices, num_tasks), block(kLM2Threads);
-    const uint32_t launches = max_iterations + 2;
+    const uint32_t launches = (loss_changes ? 2u : 1u) * max_iterations + 2;
     for (uint32_t l = 0; l < launches; ++l) {
         switch (est) {
         case EST_ABS:

@@ -322,7 +322,7 @@ hipError_t launch_hom16(BatchCtl *ctl, const uint32_t *slots, const double *mode
 size_t lm2_state_bytes(uint32_t num_tasks);
 size_t lm2_partial_bytes(uint32_t num_tasks, uint32_t slices);
 hipError_t launch_lm2(int est, const PointSet &pts, LMTask *tasks, uint32_t num_tasks, uint32_t slices,
-                      uint32_t max_iterations, void *states, double *partials, hipStream_t stream);
+                      uint32_t max_iterations, bool loss_changes, void *states, double *partials, hipStream_t stream);
 // chunks = ceil(n / (kScoreThreads * P)); P is chosen inside from n (returned through *chunks_out)
 uint32_t score_chunks(int est, uint32_t n_points, bool prefilter, bool mfma = false);
 int score_points_per_lane(int est, uint32_t n_points, bool streaming, bool mfma); // ... and the P that goes with the chunks

@@ -613,9 +613,29 @@ PL_HD double lm_cube_fma(double x) {
         return lm_cube_two_product(x * 0x1p60) * 0x1p-180;
     return x * x * x; // 0, inf, NaN, cubes beyond the range (+-inf) or below half the smallest subnormal (+-0)
 }
+#if defined(PL_LM_CUBE_HOST_SWITCH) && !defined(__HIP_DEVICE_COMPILE__)
+// (the test-only host build of tests/hostmath alone defines this: its LM then runs with the device's cube on request, so
+// that it is a serial model of k_lm_ordered bit for bit, and keeps the cube's arguments; the product's host code always calls pow.
+// One process-wide record without a lock: the test build runs its refinements one at a time, on one thread)
+struct LMCubeHostSwitch {
+    int device_form = 0;
+    unsigned calls = 0;
+    double args[256];
+};
+inline LMCubeHostSwitch &lm_cube_host_switch() {
+    static LMCubeHostSwitch s;
+    return s;
+}
+#endif
 PL_HD double lm_cube(double x) {
 #if defined(__HIP_DEVICE_COMPILE__)
     return lm_cube_fma(x);
+#elif defined(PL_LM_CUBE_HOST_SWITCH)
+    LMCubeHostSwitch &s = lm_cube_host_switch();
+    if (s.calls < 256)
+        s.args[s.calls] = x;
+    s.calls++;
+    return s.device_form ? lm_cube_fma(x) : pow(x, 3);
 #else
     return pow(x, 3);
 #endif

@@ -122,4 +122,23 @@ inline void svd3(const Mat3 &A, Mat3 &U, double s[3], Mat3 &V) {
     }
 }
 
+// The Bartoli-Sturm factorisation with which a fundamental matrix enters the LM kernels, F = U diag(1, sigma, 0) V^T
+// (bundle.cc:318-319): params[0..3] = qU, params[4..7] = qV, params[8] = sigma.  The driver's entry of every fundamental-matrix
+// refinement; the test-only host build calls the same function.
+inline void fundamental_lm_params(const Mat3 &F, double *params) {
+    Mat3 U, V;
+    double s[3];
+    svd3(F, U, s, V);
+    if (det3(U) < 0)
+        for (int i = 0; i < 9; ++i)
+            U.m[i] = -U.m[i];
+    if (det3(V) < 0)
+        for (int i = 0; i < 9; ++i)
+            V.m[i] = -V.m[i];
+    const Quat qU = rotmat_to_quat(U), qV = rotmat_to_quat(V);
+    params[0] = qU.w, params[1] = qU.x, params[2] = qU.y, params[3] = qU.z;
+    params[4] = qV.w, params[5] = qV.x, params[6] = qV.y, params[7] = qV.z;
+    params[8] = s[1] / s[0];
+}
+
 } // namespace pl

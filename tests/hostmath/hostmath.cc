@@ -544,6 +544,42 @@ void hm_lm(int est, const double *const *pa, uint32_t n, double *params, const L
     }
 }
 
+// hm_lm with the Nielsen update's cube in the device's form (lm_cube_fma instead of pow) when device_cube != 0: the serial CPU
+// model of k_lm_ordered, bit for bit (PL_LM_CUBE_HOST_SWITCH, defined by this build alone)
+void hm_lm_ex(int est, const double *const *pa, uint32_t n, double *params, const LMOptions *opt, const CameraParams *cam,
+              double point_scale, double prefilter_thr2, const uint8_t *mask, int device_cube, uint32_t *iterations, uint32_t *skipped) {
+    lm_cube_host_switch().device_form = device_cube != 0;
+    lm_cube_host_switch().calls = 0;
+    hm_lm(est, pa, n, params, opt, cam, point_scale, prefilter_thr2, mask, iterations, skipped);
+    lm_cube_host_switch().device_form = 0;
+}
+// the arguments of the Nielsen update's cube in the last hm_lm_ex run (the first 256 of them): returns how many were written
+uint32_t hm_lm_cube_args(double *out, uint32_t capacity) {
+    const LMCubeHostSwitch &s = lm_cube_host_switch();
+    const uint32_t n = std::min<uint32_t>(std::min<uint32_t>(s.calls, 256u), capacity);
+    for (uint32_t i = 0; i < n; ++i)
+        out[i] = s.args[i];
+    return n;
+}
+
+// The parameter block with which a fundamental matrix (row-major) enters the LM kernels: the driver's own factorisation
+// (pl_svd3.h fundamental_lm_params, what driver.cc lm_params_from_record calls)
+void hm_fund_params(const double *F9, double *params) {
+    Mat3 F;
+    std::memcpy(F.m, F9, sizeof(F.m));
+    for (int i = 0; i < kParamDoubles; ++i)
+        params[i] = 0.0;
+    fundamental_lm_params(F, params);
+}
+// lm_cube of pl_refine.h as this build compiles it (PL_LM_CUBE_HOST_SWITCH): the device's form when device_cube != 0, pow otherwise
+double hm_lm_cube_switched(double x, int device_cube) {
+    lm_cube_host_switch().device_form = device_cube != 0;
+    lm_cube_host_switch().calls = 0;
+    const double r = lm_cube(x);
+    lm_cube_host_switch().device_form = 0;
+    return r;
+}
+
 // Serial evaluation of k_lm_cam's algorithm (lm_cam.hip): the same rows, the same per-entry sums in correspondence order.
 void hm_lm_cam(const double *const *pa, uint32_t n, double *params, const LMOptions *opt, CameraParams *cam_io, int cam_flags,
                double point_scale, const uint8_t *mask, uint32_t *iterations, double *costs /* initial, final */) {

@@ -238,7 +238,9 @@ def unproject(cam: CameraParams, xp):
     return out
 
 
-def lm(est, cols, params, opt: LMOptions, cam: CameraParams = None, point_scale=1.0, prefilter_thr2=0.0, mask=None):
+def lm(est, cols, params, opt: LMOptions, cam: CameraParams = None, point_scale=1.0, prefilter_thr2=0.0, mask=None, device_cube=False):
+    """the LM kernels' algorithm serially (hostmath.cc lm_serial).  device_cube: the Nielsen update's cube as the device forms it
+    (lm_cube_fma) instead of the host's pow - then a model of k_lm_ordered bit for bit."""
     arrs, ptrs = _soa(cols)
     n = arrs[0].shape[0]
     p = np.zeros(16)
@@ -247,9 +249,30 @@ def lm(est, cols, params, opt: LMOptions, cam: CameraParams = None, point_scale=
     it = C.c_uint32(0)
     sk = C.c_uint32(0)
     m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
-    lib().hm_lm(EST[est], ptrs, C.c_uint32(n), _p(p), C.byref(opt), C.byref(cam), C.c_double(point_scale),
-                C.c_double(prefilter_thr2), None if m is None else _p(m), C.byref(it), C.byref(sk))
+    lib().hm_lm_ex(EST[est], ptrs, C.c_uint32(n), _p(p), C.byref(opt), C.byref(cam), C.c_double(point_scale),
+                   C.c_double(prefilter_thr2), None if m is None else _p(m), C.c_int(int(bool(device_cube))), C.byref(it), C.byref(sk))
     return p, it.value, bool(sk.value)
+
+
+def lm_cube_args():
+    """the arguments of the Nielsen update's cube in the last lm() run"""
+    out = np.zeros(256)
+    lib().hm_lm_cube_args.restype = C.c_uint32
+    return out[: lib().hm_lm_cube_args(_p(out), C.c_uint32(out.size))].copy()
+
+
+def lm_cube_switched(x, device_cube):
+    """pl_refine.h lm_cube as this build compiles it: lm_cube_fma when device_cube, the host's pow otherwise"""
+    lib().hm_lm_cube_switched.restype = C.c_double
+    return lib().hm_lm_cube_switched(C.c_double(x), C.c_int(int(bool(device_cube))))
+
+
+def fund_params(F):
+    """the parameter block (qU, qV, sigma) with which the driver hands a fundamental matrix to the LM kernels"""
+    F = np.ascontiguousarray(np.asarray(F, dtype=np.float64).reshape(9))
+    p = np.zeros(16)
+    lib().hm_fund_params(_p(F), _p(p))
+    return p
 
 
 def lm_cam(cols, params, opt: LMOptions, cam: CameraParams, cam_flags, point_scale=1.0, mask=None):

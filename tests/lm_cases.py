@@ -1,0 +1,483 @@
+"""Inputs of the LM-kernel tests (tests/test_gpu_lm_kernels.py on the device, tests/test_lm_cases.py on the CPU): a deterministic
+table of refinement cases for the three kernels of kernels.hip - k_lm (route 0), k_lm_ordered (route 1), k_lm2 (route 2) -, the
+oracle's answer to each and the serial host model of the kernels (hostmath).  Everything here comes from the oracle, hostmath and
+numpy - no device.
+
+A case is one call of Problem.refine: the first n correspondences of the kind's scene (rows arranged where a structure of the kernel
+asks for it), a start model, the bundle options and an optional mask.  Point counts are stated against the constants they come from
+(pl_kernels.h), options are paired with sizes so that every option and every size occurs at least once per kind and kernel without the
+full cross product."""
+from __future__ import annotations
+
+import collections
+import functools
+import os
+import re
+import zlib
+
+import numpy as np
+
+import hostmath_lib as HM
+import oracle_lib as O
+from poselib_amd import synth
+
+KINDS = ("abs", "rel", "fund", "hom")
+KIND_ID = {"abs": 0, "rel": 1, "fund": 2, "hom": 3}
+MIN_SAMPLE = {"abs": 3, "rel": 5, "fund": 7, "hom": 4}
+LOSSES = ("TRIVIAL", "TRUNCATED", "HUBER", "CAUCHY", "TRUNCATED_CAUCHY", "TRUNCATED_LE_ZACH")
+ZERO_WEIGHT = ("TRUNCATED", "TRUNCATED_CAUCHY")  # the losses behind k_lm's queue of correspondences with a non-zero weight
+NIELSEN, FIXED_FACTOR = 0, 1
+LEVENBERG, MARQUARDT = 0, 1
+K_LM, K_LM_ORDERED, K_LM2 = 0, 1, 2  # pl_debug_lm_route
+
+
+def _kernel_constant(pattern):
+    src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "poselib_amd", "csrc", "pl_kernels.h")
+    return int(re.search(pattern, open(src).read()).group(1))
+
+
+WAVE = 64
+SEQ = _kernel_constant(r"constexpr int kLMSeqPoints = (\d+);")  # 256: up to here k_lm adds in the reference's order
+STRIDE = _kernel_constant(r"#define PL_LM_THREADS (\d+)")        # 512: threads of an LM workgroup = rows per sweep step
+RING = (STRIDE // WAVE - 1) * WAVE                               # 448: one ring round of k_lm_ordered's 7 producer wavefronts
+LM2_MIN = {"abs": 8192, "rel": None, "fund": 2560, "hom": 2560}  # run_refinements' lm2_min_points (relative pose: never)
+LM2_SLICE_ROWS, LM2_MIN_SLICES, LM2_MAX_SLICES = 512, 2, 16      # the slice rule clamp(n / 512, 2, 16)
+LM2_MAX_ITERATIONS = 32                                          # the gate's window 1 .. 32
+
+SEQ_NS = (8, WAVE - 1, WAVE, WAVE + 1, SEQ - 1, SEQ)
+TREE_NS = (SEQ + 1, STRIDE - 1, STRIDE, STRIDE + 1, 2 * STRIDE + 1, 1281)  # 1281 = 2.5 strides + 1: a ragged third sweep step
+RING_NS = (RING - 1, RING, RING + 1)
+LM2_NS = {"hom": (2560, 2561, 3071, 3072), "fund": (2560,), "abs": (8192,)}
+N_SCENE = {"abs": 8192, "rel": 1281, "fund": 3072, "hom": 3072}
+
+
+def lm2_slices(n):
+    return min(LM2_MAX_SLICES, max(LM2_MIN_SLICES, n // LM2_SLICE_ROWS))
+
+
+Case = collections.namedtuple("Case", "kind route n loss update damping max_iterations start stop mask scale")
+Case.__new__.__defaults__ = (25, "gentle", None, None, None)  # scale None: the start's loss scale (SCALE)
+
+
+def case_id(c):
+    return "-".join(str(v) for v in (c.kind, f"r{c.route}", c.n, c.loss, "FIXED" if c.update else "NIELSEN",
+                                     "MARQUARDT" if c.damping else "LEVENBERG", f"it{c.max_iterations}", c.start,
+                                     c.stop or "default", c.mask or "nomask") + (() if c.scale is None else (f"s{c.scale:g}",)))
+
+
+# ---- scenes --------------------------------------------------------------------------------------------------------------------------
+OUTLIERS = 0.3
+NOISE = 1e-3  # the scenes' noise in normalised coordinates: half a pixel at a focal length of 1000 leaves 5e-4 per coordinate
+
+
+def _skew(t):
+    return np.array([[0, -t[2], t[1]], [t[2], 0, -t[0]], [-t[1], t[0], 0]])
+
+
+@functools.lru_cache(maxsize=None)
+def scene(kind):
+    """(a, b, truth): normalised correspondences as the parity tests build them and the model that generated the inliers"""
+    n = N_SCENE[kind]
+    if kind == "abs":
+        d = synth.absolute_pose_scene(n, OUTLIERS, 9100)
+        par = d["camera"]["params"]
+        return (np.asarray(d["p2d"]) - np.array(par[-2:])) / par[0], np.asarray(d["p3d"]), np.r_[d["q_gt"], d["t_gt"]]
+    if kind == "hom":
+        d = synth.homography_scene(n, OUTLIERS, 9103)
+        a, b = (np.asarray(d["x1"]) - 500.0) / 1000.0, (np.asarray(d["x2"]) - 500.0) / 1000.0
+        H, _, _ = O.ransac_homography(a, b, {"max_error": 2e-3, "ransac": {"seed": 1, "max_iterations": 1000}})
+        return a, b, H / np.linalg.norm(H)
+    d = synth.relative_pose_scene(n, OUTLIERS, 9101 if kind == "rel" else 9102)
+    a, b = (np.asarray(d["x1"]) - 500.0) / 1000.0, (np.asarray(d["x2"]) - 500.0) / 1000.0
+    if kind == "rel":
+        return a, b, np.r_[d["q_gt"], d["t_gt"]]
+    F = _skew(d["t_gt"]) @ synth.quat_to_rotmat(np.asarray(d["q_gt"]))
+    return a, b, F / np.linalg.norm(F)
+
+
+def squared_residuals(kind, model, a, b):
+    """numpy's squared residuals of the refiners' cost (for a homography the smaller of forward and backward): what arranges rows
+    and builds masks - with a margin of 2 either side of a threshold, so that its last bits do not matter"""
+    if kind == "abs":
+        Z = b @ synth.quat_to_rotmat(model[:4]).T + model[4:]
+        return ((Z[:, :2] / Z[:, 2:3] - a) ** 2).sum(axis=1)
+    if kind == "hom":
+        def transfer(M, x, y):
+            z = np.c_[x, np.ones(len(x))] @ M.T
+            return ((z[:, :2] / z[:, 2:3] - y) ** 2).sum(axis=1)
+        return np.minimum(transfer(model, a, b), transfer(np.linalg.inv(model), b, a))
+    M = model if kind == "fund" else _skew(model[4:]) @ synth.quat_to_rotmat(model[:4])
+    x1, x2 = np.c_[a, np.ones(len(a))], np.c_[b, np.ones(len(b))]
+    Fx1, Ftx2 = x1 @ M.T, x2 @ M
+    c = (x2 * Fx1).sum(axis=1)
+    return c * c / (Fx1[:, 0] ** 2 + Fx1[:, 1] ** 2 + Ftx2[:, 0] ** 2 + Ftx2[:, 1] ** 2)
+
+
+# ---- starts and options --------------------------------------------------------------------------------------------------------------
+# Three starts.  gentle: 1e-3 from the truth, where the reference accepts nearly every step.  rough: within the range in which a local
+# optimisation starts (0.03 .. 0.2 in q and t, relative for matrices).  far: the distance from which the reference rejects steps of
+# every kind under the fused losses too - about a quarter of such cases, where 0.2 leaves homographies and absolute poses almost none.
+START = {"gentle": {k: 1e-3 for k in KINDS}, "rough": {"abs": 0.05, "rel": 0.05, "fund": 0.03, "hom": 0.03},
+         "far": {"abs": 0.4, "rel": 0.4, "fund": 0.2, "hom": 0.3}}
+STARTS = tuple(START)
+# loss scales: a start moves the residuals by about its own size - the truncated losses keep inliers at every start
+SCALE = {"gentle": {"abs": 0.012, "rel": 4e-3, "fund": 4e-3, "hom": 6e-3}, "rough": {"abs": 0.25, "rel": 0.05, "fund": 0.05, "hom": 0.1},
+         "far": {"abs": 0.5, "rel": 0.1, "fund": 0.1, "hom": 0.4}}
+# a value per stop rule at which it can end a run early (or, for the lambda bounds, change its course): lambda can neither grow
+# beyond its initial 1e-3 after a rejected step nor fall below 0.1 after an accepted one
+STOP_RULES = {"gradient_tol": {"gradient_tol": 1e-3}, "step_tol": {"step_tol": 1e-3}, "relative_cost_tol": {"relative_cost_tol": 1e-2},
+              "max_lambda": {"max_lambda": 1e-3}, "min_lambda": {"min_lambda": 1e-1}}
+
+
+def _rng(c, salt=0):
+    return np.random.RandomState(zlib.crc32(repr((tuple(c), salt)).encode()) & 0x7FFFFFFF)
+
+
+def start_model(c):
+    """The truth moved by the start's distance.  For the truncated losses: the first of ten fixed draws from which a truncated loss of
+    the start's scale keeps a quarter of the rows and drops a tenth, at three quarters of the distance if none of the ten does, and
+    so on (on the CPU a truncated loss without inliers ends at iteration 0, which tests nothing)."""
+    a, b, truth = scene(c.kind)
+    d = START[c.start][c.kind]
+    thr2 = loss_scale(c) ** 2
+    for attempt in range(100):
+        rs = _rng(c._replace(route=0, mask=None, stop=None), attempt)  # (routes and stop rules share their starts)
+        if c.kind in ("abs", "rel"):
+            q = truth[:4] + d * rs.randn(4)
+            model = np.r_[q / np.linalg.norm(q), truth[4:] + d * rs.randn(3)]
+        else:
+            model = truth + d * np.abs(truth).max() * rs.randn(3, 3)
+        if not c.loss.startswith("TRUNCATED") or c.scale is not None:
+            break
+        r2 = squared_residuals(c.kind, model, a[: c.n], b[: c.n])
+        if (r2 < thr2 / 2).mean() >= 0.25 and (r2 > 2 * thr2).mean() >= 0.1:
+            break
+        if attempt % 10 == 9:
+            d *= 0.75
+    return model
+
+
+def loss_scale(c):
+    return SCALE[c.start][c.kind] if c.scale is None else c.scale
+
+
+def bundle_options(c):
+    bo = {"loss_type": c.loss, "loss_scale": loss_scale(c), "max_iterations": c.max_iterations, "lambda_update": c.update,
+          "damping": c.damping}
+    if c.stop:
+        bo.update(STOP_RULES[c.stop])
+    return bo
+
+
+# ---- rows and masks ------------------------------------------------------------------------------------------------------------------
+def _arranged_rows(c, a, b, model):
+    """Zero-weight losses beyond one stride: rows 0 .. 63 all kept at the start (a wavefront whose queue fills exactly with its first
+    block), rows 64 .. 127 none kept (a wavefront with nothing from a block), the rest in the scene's order."""
+    n = c.n
+    if c.loss not in ZERO_WEIGHT or n <= STRIDE:
+        return np.arange(n)
+    thr2 = loss_scale(c) ** 2
+    r2 = squared_residuals(c.kind, model, a[:n], b[:n])
+    kept, dropped = np.flatnonzero(r2 < thr2 / 2)[:WAVE], np.flatnonzero(r2 > 2 * thr2)[:WAVE]
+    assert len(kept) == WAVE and len(dropped) == WAVE, (case_id(c), len(kept), len(dropped))
+    rest = np.setdiff1d(np.arange(n), np.r_[kept, dropped])
+    return np.r_[kept, dropped, rest]
+
+
+def _mask(c, a, b):
+    n = c.n
+    if c.mask is None:
+        return None
+    if c.mask == "ones":
+        return np.ones(n, dtype=np.uint8)
+    if c.mask == "block":  # one whole 64-aligned block zeroed: a wavefront has nothing in that sweep step
+        m = np.ones(n, dtype=np.uint8)
+        first = WAVE * ((n // WAVE) // 2)
+        m[first:first + WAVE] = 0
+        return m
+    if c.mask == "alternate":
+        return (np.arange(n) % 2 == 0).astype(np.uint8)
+    # "few", "few1", "few2", ...: min-sample + 1 rows of a set of more than 256 - inliers of the truth spread over the blocks of
+    # the set ("few") or, for the numbered variants, other fixed draws of them
+    assert c.mask.startswith("few") and n > SEQ
+    _, _, truth = scene(c.kind)
+    good = np.flatnonzero(squared_residuals(c.kind, truth, a, b) < (4 * NOISE) ** 2)
+    if c.mask == "few":
+        pick = good[np.linspace(0, len(good) - 1, MIN_SAMPLE[c.kind] + 1).astype(int)]
+    else:
+        pick = np.random.RandomState(1000 + int(c.mask[3:])).choice(good, MIN_SAMPLE[c.kind] + 1, replace=False)
+    m = np.zeros(n, dtype=np.uint8)
+    m[pick] = 1
+    return m
+
+
+@functools.lru_cache(maxsize=None)
+def inputs(c):
+    """(a, b, start model, bundle options, mask or None) of a case"""
+    a, b, _ = scene(c.kind)
+    model = start_model(c)
+    rows = _arranged_rows(c, a, b, model)
+    a, b = np.ascontiguousarray(a[rows]), np.ascontiguousarray(b[rows])
+    return a, b, model, bundle_options(c), _mask(c, a, b)
+
+
+def kept_blocks(c):
+    """(64-row blocks with no correspondence kept at the start, blocks with all 64 kept) under the case's zero-weight loss"""
+    a, b, model, bo, mask = inputs(c)
+    keep = squared_residuals(c.kind, model, a, b) < bo["loss_scale"] ** 2
+    if mask is not None:
+        keep &= mask.astype(bool)
+    blocks = keep[: WAVE * (c.n // WAVE)].reshape(-1, WAVE).sum(axis=1)
+    return int((blocks == 0).sum()), int((blocks == WAVE).sum())
+
+
+# ---- the oracle and the host model ---------------------------------------------------------------------------------------------------
+Result = collections.namedtuple("Result", "model iterations invalid_steps cost nu")
+NULL_CAMERA = {"model": "NULL", "width": 0, "height": 0, "params": []}
+
+
+def oracle_run(kind, a, b, model, bo):
+    if kind == "abs":
+        m, st = O.bundle_adjust(a, b, NULL_CAMERA, model, bo)
+    else:
+        m, st = O.refine({"rel": "relpose", "fund": "fundamental", "hom": "homography"}[kind], a, b, model, bo)
+    return Result(np.asarray(m), int(st.iterations), int(st.invalid_steps), float(st.cost), float(st.nu))
+
+
+@functools.lru_cache(maxsize=None)
+def oracle(c):
+    """the reference's answer: for a mask, its refinement of the compacted subset"""
+    a, b, model, bo, mask = inputs(c)
+    if mask is not None:
+        a, b = a[mask.astype(bool)], b[mask.astype(bool)]
+    return oracle_run(c.kind, a, b, model, bo)
+
+
+def oracle_permuted(c, salt):
+    """the oracle on a fixed permutation of the case's rows: the reference's own sensitivity to the order of its sums"""
+    a, b, model, bo, mask = inputs(c)
+    if mask is not None:
+        a, b = a[mask.astype(bool)], b[mask.astype(bool)]
+    order = _rng(c, salt).permutation(len(a))
+    return oracle_run(c.kind, a[order], b[order], model, bo)
+
+
+def oracle_accepts_after_a_rejection(c):
+    """the oracle's run iteration by iteration (max_iterations = 0, 1, ...): was a step accepted after one had been rejected?"""
+    a, b, model, bo, mask = inputs(c)
+    if mask is not None:
+        a, b = a[mask.astype(bool)], b[mask.astype(bool)]
+    prev = None
+    for k in range(oracle(c).iterations + 1):
+        r = oracle_run(c.kind, a, b, model, dict(bo, max_iterations=k))
+        if prev is not None and prev.invalid_steps >= 1 and r.invalid_steps == prev.invalid_steps and not np.array_equal(r.model, prev.model):
+            return True
+        prev = r
+    return False
+
+
+def hostmath(c, device_cube):
+    """the kernels' algorithm serially on the host (every sum in the reference's order): (model, iterations)"""
+    a, b, model, bo, mask = inputs(c)
+    opt = HM.lm_options(bo["max_iterations"], O.LOSS[bo["loss_type"]], bo["loss_scale"], lambda_update=bo["lambda_update"],
+                        damping=bo["damping"], **{k: v for k, v in bo.items() if k.endswith("_tol") or k.endswith("_lambda")})
+    cols = [a[:, 0], a[:, 1]] + [b[:, j] for j in range(b.shape[1])]
+    p0 = model if c.kind in ("abs", "rel") else HM.fund_params(model) if c.kind == "fund" else np.asarray(model).reshape(9)
+    p, it, _ = HM.lm(c.kind, cols, p0, opt, mask=mask, device_cube=device_cube)
+    if c.kind in ("abs", "rel"):
+        return p[:7].copy(), it
+    return (HM.factorized_F(p) if c.kind == "fund" else p[:9].reshape(3, 3).copy()), it
+
+
+def distance(kind, got, want):
+    """poses: the larger of |R - R'| and |t - t'| / max(1, |t'|); matrices: |A / |A| - B / |B||, the sign included"""
+    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
+    if kind in ("abs", "rel"):
+        dr = np.linalg.norm(synth.quat_to_rotmat(got[:4] / np.linalg.norm(got[:4])) - synth.quat_to_rotmat(want[:4] / np.linalg.norm(want[:4])))
+        return max(dr, np.linalg.norm(got[4:] - want[4:]) / max(1.0, np.linalg.norm(want[4:])))
+    return float(np.linalg.norm(got / np.linalg.norm(got) - want / np.linalg.norm(want)))
+
+
+# ---- the table -----------------------------------------------------------------------------------------------------------------------
+COMBINATIONS = [(loss, update, damping) for loss in LOSSES for update in (NIELSEN, FIXED_FACTOR) for damping in (LEVENBERG, MARQUARDT)]
+
+
+def _grid(kind, route, sizes, shift=0):
+    """all 24 loss / update / damping combinations over `sizes` in turn; the three starts in turn, so that every loss meets each"""
+    return [Case(kind, route, sizes[i % len(sizes)], loss, update, damping, 25, STARTS[(i + shift) % 3])
+            for i, (loss, update, damping) in enumerate(COMBINATIONS)]
+
+
+def _stop_case(kind, route, sizes, stop):
+    """The first of a fixed list of candidates whose course in the REFERENCE the rule changes: another iteration count than with the
+    default tolerances (tests/test_lm_cases.py asserts it for every case)."""
+    if stop.endswith("lambda"):  # the bounds of lambda matter after rejected (max) or accepted (min, FIXED_FACTOR) steps
+        # (first TRUNCATED_LE_ZACH with the gentle start's small scale away from it: the reference rejects nearly every step there)
+        candidates = [Case(kind, route, n, "TRUNCATED_LE_ZACH", FIXED_FACTOR if stop == "min_lambda" else update, damping, 25, start, stop,
+                           None, SCALE["gentle"][kind])
+                      for n in sizes for start in ("rough", "far") for damping in (LEVENBERG, MARQUARDT) for update in (NIELSEN, FIXED_FACTOR)]
+        candidates += [Case(kind, route, n, loss, FIXED_FACTOR if stop == "min_lambda" else update, damping, 25, start, stop)
+                      for n in sizes for start in ("far", "rough") for damping in (LEVENBERG, MARQUARDT) for update in (NIELSEN, FIXED_FACTOR)
+                      for loss in ("CAUCHY", "TRUNCATED", "HUBER", "TRIVIAL", "TRUNCATED_CAUCHY", "TRUNCATED_LE_ZACH")]
+    else:
+        candidates = [Case(kind, route, n, loss, NIELSEN, LEVENBERG, 25, start, stop) for n in sizes for start in STARTS
+                      for loss in ("CAUCHY", "TRUNCATED", "HUBER", "TRIVIAL", "TRUNCATED_CAUCHY", "TRUNCATED_LE_ZACH")]
+    for c in candidates:
+        if oracle(c).iterations != oracle(c._replace(stop=None)).iterations and oracle(c).iterations >= 1:
+            return c
+    return candidates[0]
+
+
+REJECTION_CASES = 5
+
+
+def _rejection_cases(kind, route, sizes):
+    """The first REJECTION_CASES of a fixed list of far starts under the FUSED losses (every loss but TRUNCATED_LE_ZACH) in which the
+    reference rejects a step - one of them, if the list holds one, with a step accepted after the rejection: what follows a
+    rejection in the kernels (the kept normal equations solved again with a larger lambda, the trial point's dropped) happens here."""
+    out, accepted_after = [], False
+    for i, (loss, update, damping) in enumerate(COMBINATIONS * 8):
+        if loss == "TRUNCATED_LE_ZACH":
+            continue
+        c = Case(kind, route, sizes[(i // len(COMBINATIONS) + i) % len(sizes)], loss, update, damping, 25 - i // len(COMBINATIONS), "far")
+        r = oracle(c)
+        if r.invalid_steps < 1 or not np.isfinite(r.model).all():
+            continue
+        after = oracle_accepts_after_a_rejection(c)
+        if len(out) < REJECTION_CASES - 1 or accepted_after or after:
+            out.append(c)
+            accepted_after = accepted_after or after
+        if len(out) == REJECTION_CASES:
+            break
+    return out
+
+
+def _stops_and_iterations(kind, route, n_small, n_large):
+    out = [_stop_case(kind, route, ((n_small, n_large), (n_large, n_small))[i % 2], stop) for i, stop in enumerate(STOP_RULES)]
+    for i, (mi, loss) in enumerate(((0, "CAUCHY"), (1, "TRUNCATED"), (0, "TRUNCATED"), (1, "TRUNCATED_LE_ZACH"))):
+        out.append(Case(kind, route, (n_small, n_large)[i % 2], loss, NIELSEN, LEVENBERG, mi, "rough"))
+    return out
+
+
+FEW_MASKS = ("few", "few1", "few2", "few3", "few4", "few5")
+
+
+def _few_case(kind, route, n, loss):
+    """The first of the fixed picks of min-sample + 1 rows on which the REFERENCE's refinement does not depend on the order of its
+    sums (order_stable: eight row permutations, 1e-11): a handful of rows can be a badly conditioned problem - the evenly spread
+    pick is one for relative poses and fundamental matrices -, and such a pick would fall to the filter of the tree routes."""
+    candidates = [Case(kind, route, n, loss, NIELSEN, LEVENBERG, 25, "gentle", None, mask) for mask in FEW_MASKS]
+    return next((c for c in candidates if order_stable(c)), candidates[0])
+
+
+def _masks(kind, route, n_small, n_large):
+    out = [Case(kind, route, n_small, "CAUCHY", NIELSEN, LEVENBERG, 25, "gentle", None, "ones"),
+           Case(kind, route, n_large, "TRUNCATED", NIELSEN, LEVENBERG, 25, "gentle", None, "ones"),
+           Case(kind, route, n_small, "TRUNCATED", FIXED_FACTOR, LEVENBERG, 25, "rough", None, "block"),
+           Case(kind, route, n_large, "TRUNCATED", NIELSEN, LEVENBERG, 25, "far", None, "block"),
+           Case(kind, route, n_large, "TRUNCATED_CAUCHY", NIELSEN, MARQUARDT, 25, "gentle", None, "alternate"),
+           Case(kind, route, n_small, "HUBER", NIELSEN, LEVENBERG, 25, "far", None, "alternate")]
+    if n_large > SEQ:  # (min-sample + 1 rows of MORE than 256)
+        out += [_few_case(kind, route, n_large, "CAUCHY"), _few_case(kind, route, n_large, "TRUNCATED")]
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def ordered_cases():
+    """results that must equal the host model bit for bit: k_lm_ordered (route 1) at every size, k_lm (route 0) up to SEQ rows"""
+    out = []
+    for kind in KINDS:
+        out += _grid(kind, K_LM, SEQ_NS)
+        out += _rejection_cases(kind, K_LM, SEQ_NS[1:])
+        out += _stops_and_iterations(kind, K_LM, WAVE + 1, SEQ)
+        out += _masks(kind, K_LM, SEQ - 1, SEQ)
+        out += _grid(kind, K_LM_ORDERED, SEQ_NS, 1)
+        out += _grid(kind, K_LM_ORDERED, RING_NS + TREE_NS)
+        out += _rejection_cases(kind, K_LM_ORDERED, RING_NS + TREE_NS)
+        out += _stops_and_iterations(kind, K_LM_ORDERED, SEQ - 1, RING + 1)
+        out += _masks(kind, K_LM_ORDERED, WAVE + 1, 2 * STRIDE + 1)
+    return list(dict.fromkeys(out))
+
+
+@functools.lru_cache(maxsize=None)
+def tree_candidates():
+    """k_lm beyond SEQ rows: tree sums, compared within a tolerance"""
+    out = []
+    for kind in KINDS:
+        out += _grid(kind, K_LM, TREE_NS)
+        out += _grid(kind, K_LM, TREE_NS[::-1], 1)
+        out += _rejection_cases(kind, K_LM, TREE_NS)
+        out += _stops_and_iterations(kind, K_LM, STRIDE + 1, 2 * STRIDE + 1)
+        out += _masks(kind, K_LM, STRIDE - 1, 2 * STRIDE + 1)
+    return list(dict.fromkeys(out))
+
+
+@functools.lru_cache(maxsize=None)
+def lm2_candidates():
+    """k_lm2 (latency mode; fundamental: LM mode 2 as well): the sizes of its gate and of its slice rule"""
+    out = []
+    for kind, ns in LM2_NS.items():
+        for i, n in enumerate(ns):
+            out.append(Case(kind, K_LM2, n, ("TRUNCATED", "TRUNCATED_LE_ZACH")[i % 2], NIELSEN, LEVENBERG, 25, ("far", "gentle")[i % 2]))
+        n = ns[0]
+        out += _rejection_cases(kind, K_LM2, ns)
+        out += [Case(kind, K_LM2, n, "TRUNCATED_LE_ZACH", NIELSEN, LEVENBERG, 25, "rough"),
+                Case(kind, K_LM2, n, "TRUNCATED", FIXED_FACTOR, MARQUARDT, 25, "gentle"),
+                Case(kind, K_LM2, n, "CAUCHY", NIELSEN, LEVENBERG, 25, "far"),
+                Case(kind, K_LM2, n, "HUBER", FIXED_FACTOR, LEVENBERG, LM2_MAX_ITERATIONS, "rough"),
+                Case(kind, K_LM2, n, "TRUNCATED_CAUCHY", FIXED_FACTOR, LEVENBERG, 25, "far"),
+                Case(kind, K_LM2, n, "TRUNCATED_CAUCHY", NIELSEN, LEVENBERG, 1, "rough"),
+                Case(kind, K_LM2, n, "TRUNCATED", NIELSEN, LEVENBERG, 25, "rough", None, "block"),
+                Case(kind, K_LM2, n, "TRIVIAL", NIELSEN, MARQUARDT, 25, "rough")]
+    return list(dict.fromkeys(out))
+
+
+ORDER_TOL = 1e-11     # the reference against itself on permuted rows: two orders below the device's bound
+TREE_TOL = 1e-9       # the project's bound for tree sums (test_score_and_refine_match_oracle)
+# Fixed permutations of the rows.  Three pass a case whose stop decision hangs on the last bits of a sum too easily: fund, 257 rows,
+# TRUNCATED, FIXED_FACTOR, gentle start ends after 10, 11 or 12 iterations in 57, 16 and 27 of 100 permutations of the REFERENCE's own
+# rows (models 1.3e-10 apart) and passes three with probability 0.18; eight let such a case through once in a hundred.
+PERMUTATIONS = (1, 2, 3, 4, 5, 6, 7, 8)
+
+
+@functools.lru_cache(maxsize=None)
+def order_spread(c):
+    """(iteration counts agree, largest distance) of the oracle's results over the fixed permutations of the case's rows"""
+    base = oracle(c)
+    runs = [oracle_permuted(c, s) for s in PERMUTATIONS]
+    same = all(r.iterations == base.iterations for r in runs)
+    finite = np.isfinite(base.model).all() and all(np.isfinite(r.model).all() for r in runs)
+    return same and finite, max(distance(c.kind, r.model, base.model) for r in runs) if finite else np.inf
+
+
+def order_stable(c):
+    same, spread = order_spread(c)
+    return same and spread <= ORDER_TOL
+
+
+@functools.lru_cache(maxsize=None)
+def tree_cases():
+    return [c for c in tree_candidates() if order_stable(c)]
+
+
+@functools.lru_cache(maxsize=None)
+def lm2_cases(kind=None):
+    return [c for c in lm2_candidates() if (kind is None or c.kind == kind) and order_stable(c)]
+
+
+def flat(kind, model):
+    """a Problem.refine result as an array: q, t of a CameraPose, or the matrix"""
+    return np.r_[model.q, model.t] if kind in ("abs", "rel") else np.asarray(model, dtype=np.float64)
+
+
+def refine_on_device(P, c, max_iterations=None):
+    """the case through Problem.refine of the product package P (a problem of its own, closed again): (model, iterations)"""
+    a, b, model, bo, mask = inputs(c)
+    if max_iterations is not None:
+        bo = dict(bo, max_iterations=max_iterations)
+    pr = P.Problem(KIND_ID[c.kind], a, b)
+    try:
+        got, it = pr.refine(P.CameraPose(model[:4], model[4:]) if c.kind in ("abs", "rel") else model, bo, mask=mask)
+    finally:
+        pr.close()
+    return flat(c.kind, got), it

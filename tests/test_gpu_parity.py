@@ -438,8 +438,10 @@ def test_estimate_batch_matches_single_calls(gpu):
 
 @pytest.mark.parametrize("mode", ["1", "0"])
 def test_multi_workgroup_and_single_workgroup_lm(gpu, mode):
-    """POSELIB_AMD_LATENCY_MODE=1 sends the LO of large homography / fundamental problems through k_lm2 (one task
-    spread over several workgroups, one launch per LM iteration); the default keeps every task on one workgroup (k_lm).
+    """POSELIB_AMD_LATENCY_MODE=1 sends the LO of large homography problems through k_lm2 (one task spread over several
+    workgroups, one launch per LM iteration); the default keeps every task on one workgroup (k_lm).  The fundamental half runs
+    k_lm_ordered under either setting: in the default LM mode the sums of a fundamental matrix's refinement are ordered, which
+    closes k_lm2's gate (tests/test_gpu_lm_kernels.py reaches k_lm2 for fundamental matrices, in LM mode 2).
     Both have to reproduce the oracle; run in subprocesses because the setting is read once per process."""
     import os
     import subprocess
