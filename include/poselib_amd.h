@@ -185,7 +185,8 @@ int pl_estimate_homography(const double *points2D_1, const double *points2D_2, s
  *     misaligned address, a row_stride below cols, another dtype or cols than the argument takes: PL_ERR_INVALID with a message
  *     that names the cause, before anything is launched.  n == 0 (and n below the estimator's minimum where the host form
  *     returns default stats) reads no device memory; data may then be null.
- * Models, stats and the `inliers` bytes stay in host memory. */
+ * Models and stats stay in host memory; so do the `inliers` bytes of these entry points (pl_estimate_dev_masked, below, writes them
+ * to device memory). */
 #define PL_F64 0
 #define PL_F32 1
 typedef struct {
@@ -197,7 +198,7 @@ typedef struct {
 /* The host forms above with device-resident points; everything else as there.  pl_estimate_absolute_pose_dev with
  * estimate_focal_length: PL_ERR_UNSUPPORTED (that estimator reads the points on the host).  The batched form is
  * pl_estimate_batch_dev (below, behind pl_estimate_batch).  Not served from device memory: the focal-length estimators,
- * pl_estimate_1D_radial_absolute_pose, the pl_ransac_* one-shot entries, pl_undistort_points. */
+ * pl_estimate_1D_radial_absolute_pose, the pl_ransac_* one-shot entries. */
 int pl_estimate_absolute_pose_dev(const pl_device_points *points2D, const pl_device_points *points3D, size_t n,
                                   const pl_robust_options *opt, pl_camera *camera, pl_camera_pose *pose, uint8_t *inliers,
                                   pl_ransac_stats *stats);
@@ -227,6 +228,40 @@ int pl_debug_point_stats_dev(const pl_device_points *x1, const pl_device_points 
  * camera with the same focal lengths and principal point: out = (fx u + cx, fy v + cy).  points2D, out: N x 2.
  * camera: any supported model but NULL. ---- */
 int pl_undistort_points(const pl_camera *camera, const double *points2D, size_t n, double *out);
+/* The same stage for points that are in DEVICE memory and stay there (a tensor of distorted keypoints in front of the _dev
+ * estimators): row i of `points2D` (fp32 or fp64, strided; fp32 widens exactly) is un-distorted into columns 0 and 1 of row i of
+ * `out`, fp64, bit for bit what pl_undistort_points gives on the same values as doubles.  Nothing passes through the host.
+ *   - camera: pl_undistort_points' rule (any supported model but NULL, otherwise PL_ERR_UNSUPPORTED).
+ *   - points2D: the checks of every _dev entry point.  out: the same checks, and dtype PL_F64, cols 2, an 8-byte aligned address,
+ *     row_stride >= 2, an allocation that holds every row.  The checks that need no device come first: PL_ERR_INVALID before
+ *     PL_ERR_NO_DEVICE.  n == 0 reads and writes nothing; data may then be null.
+ *   - Elements of a destination row beyond column 1 and rows beyond n are not written: columns of a wider block are a valid
+ *     destination.
+ *   - In place is allowed when the destination IS the source: same address, same row_stride, fp64.  Any other overlap of the two
+ *     byte ranges (first byte of row 0 to last byte of row n - 1, whatever lies between the rows) is PL_ERR_INVALID.
+ *   - The input must be complete when the call is made (synchronise the producer's stream first); the call returns after its own
+ *     stream has been waited for, so the output is complete and visible to any stream.
+ * Out of scope: fp32 output, a producer stream or event. */
+typedef struct {
+    void *data;          /* device address of element (0, 0), on the device the calling thread selected */
+    int64_t row_stride;  /* ELEMENTS between consecutive rows, >= 2 */
+    int32_t dtype;       /* PL_F64 only */
+    int32_t cols;        /* 2 */
+} pl_device_points_out;
+int pl_undistort_points_dev(const pl_camera *camera, const pl_device_points *points2D, size_t n, const pl_device_points_out *out);
+/* Many views at once - a matcher batch is 2 x pairs views over a handful of cameras; every item carries its own.  All descriptors
+ * are checked first (an allocation's kind, device and extent are asked of the runtime once per allocation and call); a bad item
+ * gets its own status and a message that names its index and the cause, the other items run: one argument table, one launch and
+ * one synchronisation per call.  Every item equals its single call bit for bit.  Returns the first failing item's status. */
+typedef struct {
+    int32_t status;           /* out: PL_OK or the error of this item */
+    int32_t reserved;         /* 0 */
+    const pl_camera *camera;
+    pl_device_points points2D;
+    size_t n;
+    pl_device_points_out out;
+} pl_undistort_item_dev;
+int pl_undistort_points_batch_dev(pl_undistort_item_dev *items, size_t count);
 
 /* ---- batched front-end: an array of independent problems (BASELINE config 4: many image pairs) ----
  * Every item is one call of the matching pl_estimate_* above; `max_in_flight` problems (<= 0: 8) are worked on
@@ -280,8 +315,8 @@ int pl_estimate_batch_devices(pl_batch_item *items, size_t count, const int *dev
  *     min_iterations > 4096, tangent_sampson, items a group hands back) runs through the matching pl_estimate_*_dev and is
  *     counted solo / fallback.
  *   - Kind 4, kind 5 and kind 0 with estimate_focal_length: item status PL_ERR_UNSUPPORTED, as for the single calls; nothing is read.
- *   - Not offered: a form over several devices (the memory belongs to one), host and device items mixed in one call, inlier
- *     masks in device memory, a producer stream or event (synchronise the producer first).
+ *   - Not offered: a form over several devices (the memory belongs to one), host and device items mixed in one call, a
+ *     producer stream or event (synchronise the producer first).  Inlier masks in device memory: pl_estimate_batch_dev_masked.
  * Adding this record and entry point changes no existing record: PL_ABI_VERSION stays 5 (new symbols do not bump it). */
 typedef struct {
     int32_t kind;            /* 0 absolute pose, 1 relative pose, 2 fundamental, 3 homography */
@@ -322,8 +357,9 @@ int pl_debug_point_stats_group_dev(const pl_device_points *x1, const pl_device_p
  *   - How: a ranking kernel leaves the permutation and the kept count in device memory, a permuting copy (the ingest kernel
  *     reading row order[j] into row j) writes the contiguous fp64 blocks the preparation takes - a scored item is never read where
  *     it lies -, one synchronisation brings count and permutation back; the mask is scattered to the caller's numbering on the
- *     host.  Any n up to 2^31 - 1; the work buffers are 24 bytes per row beyond 8192 rows, none below.
- *   - Out of scope: masks or models in device memory, a producer stream, scored resident problems (pl_problem_create_dev),
+ *     host (on the device, without a copy, by the _masked forms below).  Any n up to 2^31 - 1; the work buffers are 24 bytes per
+ *     row beyond 8192 rows, none below.
+ *   - Out of scope: models in device memory, a producer stream, scored resident problems (pl_problem_create_dev),
  *     scores for the focal-length, 1D-radial and pl_ransac_* entries, half-precision scores. */
 typedef struct {
     const void *data;   /* device address of the first row's score */
@@ -345,6 +381,35 @@ int pl_estimate_dev_scored(int kind, const pl_device_points *a, const pl_device_
  * items[i].n for a plain item, 0 for an item that did not run. */
 int pl_estimate_batch_dev_scored(pl_batch_item_dev *items, const pl_device_scores *scores, size_t *n_used, size_t count,
                                  int max_in_flight);
+/* ---- inlier masks written to DEVICE memory: what one does next with a mask is index the match tensor, so it need not come down ----
+ * A mask destination, parallel to pl_device_scores.  THE RULE, for an item of n rows: byte i * stride of the destination becomes 0
+ * or 1 for every i in [0, n) - all n of them, always - with the values of the host mask of the same call made on a buffer that was
+ * zero-filled beforehand: rows dropped by the scores give 0, and where the host form writes nothing (too few rows, an item that
+ * failed after its descriptors were accepted) all n bytes are 0.  No other byte is touched.  Model, stats, n_used, the status and
+ * pl_last_batch_report are bit for bit what the call with a host mask gives.
+ *   - The destination gets the points' checks (null descriptor, n beyond 2^31 - 1, stride < 1, null data - PL_ERR_INVALID without
+ *     a device -, then the memory's kind, device and extent); a bad descriptor fails its own item, whose destination is not touched.
+ *   - The destination must not overlap the points or the scores: that is the CALLER's contract, it is not checked.
+ *   - How: one launch zero-fills every destination of the call; the launch that computes the returned model's mask - of the
+ *     item's lock-step group, or of its single run (solo, fallback and deferred items take that route as well) - writes the flags
+ *     into the destination itself, a scored item's through the permutation its ranking left in device memory.  Such an item has
+ *     no pinned host mask, no device-to-host copy and no scatter on the host.  The call returns after its streams have been
+ *     waited for: the mask is complete and visible to any stream.
+ *   - Out of scope: models or stats in device memory (the front-ends finish the model on the host), a producer stream or event,
+ *     masks for resident problems (pl_problem_create_dev) and the pl_ransac_* entries, anything for kinds 4 and 5 and
+ *     estimate_focal_length, whose refusals stay as they are. */
+typedef struct {
+    uint8_t *data;      /* device address of row 0's flag */
+    int64_t stride;     /* BYTES between consecutive rows' flags, >= 1: a bool / uint8 tensor, or one column of a wider byte block */
+} pl_device_mask;
+/* pl_estimate_dev_scored (scores != NULL) or the plain _dev entry point of `kind` (scores == NULL) with the mask in device memory. */
+int pl_estimate_dev_masked(int kind, const pl_device_points *a, const pl_device_points *b, const pl_device_scores *scores /* may be NULL */,
+                           size_t n, const pl_robust_options *opt, pl_camera *camera1, const pl_camera *camera2, void *model,
+                           const pl_device_mask *mask, pl_ransac_stats *stats, size_t *n_used);
+/* pl_estimate_batch_dev_scored with masks[i] belonging to items[i]: an entry whose data is NULL makes item i an item with its host
+ * `inliers` pointer as ever (masks == NULL: every item); items[i].inliers is ignored when a device mask is given. */
+int pl_estimate_batch_dev_masked(pl_batch_item_dev *items, const pl_device_scores *scores /* may be NULL */, const pl_device_mask *masks,
+                                 size_t *n_used, size_t count, int max_in_flight);
 /* Diagnostic: the permutation alone.  scores, n, kept: count entries; order: the members one after the other, n[k] slots each, the
  * first kept[k] of them written.  count == 1 takes the kernels' single form, count > 1 the grouped one (one launch sequence for
  * all members).  pl_debug_rank_tile: the rows one workgroup ranks out of LDS in a launch whose largest member has max_n rows -

@@ -120,6 +120,19 @@ class DeviceScores(C.Structure):  # pl_device_scores: one confidence per row in 
     _fields_ = [("data", C.c_void_p), ("stride", C.c_int64), ("dtype", i32), ("reserved", i32), ("min_score", f64)]
 
 
+class DevicePointsOut(C.Structure):  # pl_device_points_out: fp64 rows in DEVICE memory that a call writes (columns 0 and 1)
+    _fields_ = [("data", C.c_void_p), ("row_stride", C.c_int64), ("dtype", i32), ("cols", i32)]
+
+
+class UndistortItemDev(C.Structure):  # pl_undistort_item_dev
+    _fields_ = [("status", i32), ("reserved", i32), ("camera", C.POINTER(Camera)), ("points2D", DevicePoints), ("n", C.c_size_t),
+                ("out", DevicePointsOut)]
+
+
+class DeviceMask(C.Structure):  # pl_device_mask: one flag byte per row in DEVICE memory, `stride` BYTES apart
+    _fields_ = [("data", C.c_void_p), ("stride", C.c_int64)]
+
+
 class PoseLibAmdError(RuntimeError):
     pass
 
@@ -195,11 +208,15 @@ def _declare(L):
         "pl_debug_point_stats_group_dev": (cint, [dpts, dpts, P(sz), sz, cint, vp]),
         "pl_estimate_dev_scored": (cint, [cint, dpts, dpts, P(DeviceScores), sz, opt, cam, cam, vp, vp, stats, P(sz)]),
         "pl_estimate_batch_dev_scored": (cint, [P(BatchItemDev), P(DeviceScores), P(sz), sz, cint]),
+        "pl_estimate_dev_masked": (cint, [cint, dpts, dpts, P(DeviceScores), sz, opt, cam, cam, vp, P(DeviceMask), stats, P(sz)]),
+        "pl_estimate_batch_dev_masked": (cint, [P(BatchItemDev), P(DeviceScores), P(DeviceMask), P(sz), sz, cint]),
         "pl_debug_rank_scores": (cint, [P(DeviceScores), P(sz), sz, vp, P(sz)]),
         "pl_debug_rank_tile": (cint, [sz]),
         "pl_last_batch_report": (None, [P(BatchReport)]),
         "pl_ransac_batch": (cint, [P(RansacItem), sz, cint, cint]),
         "pl_undistort_points": (cint, [cam, vp, sz, vp]),
+        "pl_undistort_points_dev": (cint, [cam, dpts, sz, P(DevicePointsOut)]),
+        "pl_undistort_points_batch_dev": (cint, [P(UndistortItemDev), sz]),
         "pl_ransac_pnp": (cint, [vp, vp, sz, opt, pose, vp, stats]),
         "pl_ransac_pnpf": (cint, [vp, vp, sz, opt, pose, P(dbl), vp, stats]),
         "pl_ransac_relpose": (cint, [vp, vp, sz, opt, pose, vp, stats]),
@@ -283,6 +300,7 @@ EXPORTED_SYMBOLS = [
     "pl_problem_create_dev", "pl_problem_create_tangent_dev", "pl_debug_check_device_points", "pl_debug_point_stats_dev",
     "pl_debug_sampler_shape", "pl_debug_sample_positions", "pl_estimate_batch_dev", "pl_debug_point_stats_group_dev",
     "pl_estimate_dev_scored", "pl_estimate_batch_dev_scored", "pl_debug_rank_scores", "pl_debug_rank_tile",
+    "pl_undistort_points_dev", "pl_undistort_points_batch_dev", "pl_estimate_dev_masked", "pl_estimate_batch_dev_masked",
     # (pl_estimate_1D_radial_absolute_pose and pl_ransac_1D_radial_pnp carry the reference's capital D: declared above, exported by the
     # library, but outside the lower-case pattern tests/test_cabi_surface.py lists the header's symbols with)
 ]

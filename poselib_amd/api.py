@@ -340,6 +340,55 @@ def _device_scores(scores, n, min_score, streams=None):
     return L.DeviceScores(ptr, stride, dtype, 0, m), scores
 
 
+def _device_mask(mask, n, streams=None):
+    """(pl_device_mask descriptor, the object that owns the memory) of inliers_out=: a one-dimensional GPU tensor /
+    __cuda_array_interface__ object of n one-byte elements (torch.bool, torch.uint8), strided allowed - the library writes one 0 / 1
+    byte per row there.  Synchronisation as _device_points."""
+    if _is_torch_tensor(mask):
+        if not mask.is_cuda:
+            raise ValueError("inliers_out= must be on the GPU")
+        if str(mask.dtype) not in ("torch.bool", "torch.uint8"):
+            raise ValueError(f"inliers_out= must be torch.bool or torch.uint8, not {mask.dtype}")
+        if mask.dim() != 1 or int(mask.shape[0]) != n:
+            raise ValueError(f"inliers_out=: expected {n} elements, got shape {tuple(mask.shape)}")
+        index = mask.device.index
+        torch = sys.modules.get(type(mask).__module__.split(".")[0])
+        if index is None and torch is not None:
+            index = torch.cuda.current_device()
+        if index != _selected_device():
+            raise ValueError(f"inliers_out= lives on device {index}, this thread selected device {_selected_device()} (set_device)")
+        if n > 1 and mask.stride(0) < 1:
+            raise ValueError("inliers_out= needs a positive stride")
+        if torch is not None:
+            if streams is None:
+                torch.cuda.current_stream(mask.device).synchronize()
+            else:
+                streams.setdefault(index, (torch, mask.device))
+        return L.DeviceMask(mask.data_ptr() if n else None, int(mask.stride(0)) if n > 1 else 1), mask
+    if not _on_device(mask):
+        raise ValueError("inliers_out= must be on the GPU")
+    cai = mask.__cuda_array_interface__
+    shape = tuple(cai["shape"])
+    if cai["typestr"] not in ("|b1", "|u1"):
+        raise ValueError(f"inliers_out= must hold one-byte bool / uint8 elements, not typestr {cai['typestr']!r}")
+    if len(shape) != 1 or int(shape[0]) != n:
+        raise ValueError(f"inliers_out=: expected {n} elements, got shape {shape}")
+    if cai["data"][1]:
+        raise ValueError("inliers_out= is read-only")
+    strides = cai.get("strides")
+    stride = 1
+    if strides is not None and n > 1:
+        if strides[0] < 1:
+            raise ValueError("inliers_out= needs a positive stride")
+        stride = int(strides[0])
+    return L.DeviceMask(int(cai["data"][0]) if n else None, stride), mask
+
+
+def _check_mask_args(on_device, inliers_out):
+    if inliers_out is not None and not on_device:
+        raise ValueError("inliers_out= goes with points on the GPU: host points return info['inliers'] as a list")
+
+
 def _check_scores_args(on_device, scores, min_score):
     if scores is None:
         if min_score is not None:
@@ -387,10 +436,12 @@ class _Points:
         return getattr(L.lib(), name + "_dev" if self.on_device else name)
 
 
-def _info(st: L.RansacStats, inliers: np.ndarray, n_used=None):
+def _info(st: L.RansacStats, inliers, n_used=None):
+    """inliers: the host mask (becomes a list of bool), or the caller's inliers_out= object, which is handed back as it is"""
+    host = isinstance(inliers, np.ndarray)
     return {"n_used": len(inliers) if n_used is None else int(n_used),  # rows the estimator ran on (fewer than given: scores=)
             "refinements": st.refinements, "iterations": st.iterations, "num_inliers": st.num_inliers,
-            "inlier_ratio": st.inlier_ratio, "model_score": st.model_score, "inliers": inliers.astype(bool).tolist(),
+            "inlier_ratio": st.inlier_ratio, "model_score": st.model_score, "inliers": inliers.astype(bool).tolist() if host else inliers,
             # extras (not in the reference): metric numerator and device timing
             "hypotheses": st.hypotheses, "iterations_evaluated": st.iterations_evaluated, "seconds": st.seconds,
             "score_kernel_ms": st.score_kernel_ms, "score_kernel_launches": st.score_kernel_launches,
@@ -415,21 +466,31 @@ def _as_camera(cam) -> Camera:
 
 
 # ------------------------------------------------------------------------------------------ estimators
-def _run_scored(kind, pts, scores, min_score, o, c1, c2, model, inl, st):
-    """pl_estimate_dev_scored: device points with device scores; returns n_used"""
-    sd, keep = _device_scores(scores, pts.n, min_score)
+def _run_scored(kind, pts, scores, min_score, o, c1, c2, model, inl, st, inliers_out=None):
+    """pl_estimate_dev_scored: device points with device scores; with inliers_out= (and then with or without scores)
+    pl_estimate_dev_masked: the mask stays on the device.  Returns n_used"""
+    sd, keep = _device_scores(scores, pts.n, min_score) if scores is not None else (None, None)
     used = C.c_size_t(0)
-    L.check(L.lib().pl_estimate_dev_scored(kind, pts.a, pts.b, C.byref(sd), C.c_size_t(pts.n), C.byref(o),
-                                           None if c1 is None else C.byref(c1), None if c2 is None else C.byref(c2), model, _ptr(inl),
-                                           C.byref(st), C.byref(used)))
+    cams = (None if c1 is None else C.byref(c1), None if c2 is None else C.byref(c2))
+    if inliers_out is not None:
+        md, keep_mask = _device_mask(inliers_out, pts.n)
+        L.check(L.lib().pl_estimate_dev_masked(kind, pts.a, pts.b, None if sd is None else C.byref(sd), C.c_size_t(pts.n), C.byref(o),
+                                               cams[0], cams[1], model, C.byref(md), C.byref(st), C.byref(used)))
+        del keep_mask
+    else:
+        L.check(L.lib().pl_estimate_dev_scored(kind, pts.a, pts.b, C.byref(sd), C.c_size_t(pts.n), C.byref(o), cams[0], cams[1], model,
+                                               _ptr(inl), C.byref(st), C.byref(used)))
     del keep
     return int(used.value)
 
 
-def estimate_absolute_pose(points2D, points3D, camera, opt=None, initial_pose=None, scores=None, min_score=None):
+def estimate_absolute_pose(points2D, points3D, camera, opt=None, initial_pose=None, scores=None, min_score=None, inliers_out=None):
     """scores (one per row, where the points are) / min_score: the rows with score >= min_score are used, in descending score -
-    see score_order; info["inliers"] keeps the caller's numbering, info["n_used"] is the number of rows used"""
+    see score_order; info["inliers"] keeps the caller's numbering, info["n_used"] is the number of rows used.
+    inliers_out (points on the GPU only): a device array of n one-byte elements (torch.bool / torch.uint8, strided allowed) that
+    receives the mask - it never comes down: info["inliers"] is that object and no list is built"""
     _check_scores_args(_on_device(points2D) or _on_device(points3D), scores, min_score)
+    _check_mask_args(_on_device(points2D) or _on_device(points3D), inliers_out)
     if scores is not None and not _on_device(scores):
         return _scored_host(lambda a, b: estimate_absolute_pose(a, b, camera, opt, initial_pose), points2D, points3D, scores, min_score)
     pts = _Points(points2D, points3D, 2, 3)
@@ -441,17 +502,20 @@ def estimate_absolute_pose(points2D, points3D, camera, opt=None, initial_pose=No
     inl = np.zeros(max(n, 1), dtype=np.uint8)
     st = L.RansacStats()
     used = None
-    if scores is not None:
-        used = _run_scored(KIND_ABS, pts, scores, min_score, o, c, None, C.cast(C.pointer(pose), C.c_void_p), inl, st)
+    if scores is not None or inliers_out is not None:
+        used = _run_scored(KIND_ABS, pts, scores, min_score, o, c, None, C.cast(C.pointer(pose), C.c_void_p), inl, st, inliers_out)
+        used = used if scores is not None else None
     else:
         L.check(pts.fn("pl_estimate_absolute_pose")(pts.a, pts.b, C.c_size_t(n), C.byref(o), C.byref(c), C.byref(pose),
                                                     _ptr(inl), C.byref(st)))
     out_cam = Camera(cam.model_id, list(c.params[: c.num_params]), cam.width, cam.height)
-    return Image(_pypose(pose), out_cam), _info(st, inl[:n], used)
+    return Image(_pypose(pose), out_cam), _info(st, inl[:n] if inliers_out is None else inliers_out, n if used is None else used)
 
 
-def estimate_relative_pose(points2D_1, points2D_2, camera1, camera2, opt=None, initial_pose=None, scores=None, min_score=None):
+def estimate_relative_pose(points2D_1, points2D_2, camera1, camera2, opt=None, initial_pose=None, scores=None, min_score=None,
+                           inliers_out=None):
     _check_scores_args(_on_device(points2D_1) or _on_device(points2D_2), scores, min_score)
+    _check_mask_args(_on_device(points2D_1) or _on_device(points2D_2), inliers_out)
     if scores is not None and not _on_device(scores):
         return _scored_host(lambda a, b: estimate_relative_pose(a, b, camera1, camera2, opt, initial_pose), points2D_1, points2D_2,
                             scores, min_score)
@@ -463,16 +527,18 @@ def estimate_relative_pose(points2D_1, points2D_2, camera1, camera2, opt=None, i
     inl = np.zeros(max(n, 1), dtype=np.uint8)
     st = L.RansacStats()
     used = None
-    if scores is not None:
-        used = _run_scored(KIND_REL, pts, scores, min_score, o, c1, c2, C.cast(C.pointer(pose), C.c_void_p), inl, st)
+    if scores is not None or inliers_out is not None:
+        used = _run_scored(KIND_REL, pts, scores, min_score, o, c1, c2, C.cast(C.pointer(pose), C.c_void_p), inl, st, inliers_out)
+        used = used if scores is not None else None
     else:
         L.check(pts.fn("pl_estimate_relative_pose")(pts.a, pts.b, C.c_size_t(n), C.byref(c1), C.byref(c2), C.byref(o),
                                                     C.byref(pose), _ptr(inl), C.byref(st)))
-    return _pypose(pose), _info(st, inl[:n], used)
+    return _pypose(pose), _info(st, inl[:n] if inliers_out is None else inliers_out, n if used is None else used)
 
 
-def _estimate_matrix(fn, kind, points2D_1, points2D_2, opt, initial, scores=None, min_score=None):
+def _estimate_matrix(fn, kind, points2D_1, points2D_2, opt, initial, scores=None, min_score=None, inliers_out=None):
     _check_scores_args(_on_device(points2D_1) or _on_device(points2D_2), scores, min_score)
+    _check_mask_args(_on_device(points2D_1) or _on_device(points2D_2), inliers_out)
     if scores is not None and not _on_device(scores):
         return _scored_host(lambda a, b: _estimate_matrix(fn, kind, a, b, opt, initial), points2D_1, points2D_2, scores, min_score)
     pts = _Points(points2D_1, points2D_2, 2, 2)
@@ -482,11 +548,12 @@ def _estimate_matrix(fn, kind, points2D_1, points2D_2, opt, initial, scores=None
     inl = np.zeros(max(n, 1), dtype=np.uint8)
     st = L.RansacStats()
     used = None
-    if scores is not None:
-        used = _run_scored(kind, pts, scores, min_score, o, None, None, _ptr(M), inl, st)
+    if scores is not None or inliers_out is not None:
+        used = _run_scored(kind, pts, scores, min_score, o, None, None, _ptr(M), inl, st, inliers_out)
+        used = used if scores is not None else None
     else:
         L.check(pts.fn(fn)(pts.a, pts.b, C.c_size_t(n), C.byref(o), _ptr(M), _ptr(inl), C.byref(st)))
-    return M.reshape(3, 3).T.copy(), _info(st, inl[:n], used)
+    return M.reshape(3, 3).T.copy(), _info(st, inl[:n] if inliers_out is None else inliers_out, n if used is None else used)
 
 
 class _DevicePts:
@@ -526,10 +593,14 @@ class Batch:
 
         self.items = ((L.BatchItemDev if self.on_device else L.BatchItem) * len(problems))()
         self.keep = []
+        self.mask_out = []  # per problem: the caller's inliers_out= object or None
         # device items with scores: pl_estimate_batch_dev_scored (an entry without data is a plain item)
         self.scores = (L.DeviceScores * max(len(problems), 1))()
         self.n_used = (C.c_size_t * max(len(problems), 1))()
         self.scored = False
+        # device items with "inliers_out": pl_estimate_batch_dev_masked (an entry without data keeps its host mask)
+        self.masks = (L.DeviceMask * max(len(problems), 1))()
+        self.masked = False
         for it, pr in zip(self.items, problems):
             kind = kinds[pr[0]]
             it.kind = kind
@@ -540,6 +611,9 @@ class Batch:
             init = opt.pop("initial_model", None)
             scores, min_score = opt.pop("scores", None), opt.pop("min_score", None)
             _check_scores_args(self.on_device, scores, min_score)
+            # ... and "inliers_out": a device array of n one-byte elements that receives the mask (device points only)
+            inliers_out = opt.pop("inliers_out", None)
+            _check_mask_args(self.on_device, inliers_out)
             order, rows = None, None
             if scores is not None and not self.on_device:  # host points: the rule in numpy, the plain item on the ranked rows
                 order = score_order(scores, min_score)
@@ -588,6 +662,9 @@ class Batch:
                 if scores is not None:
                     self.scores[len(self.keep)], order = _device_scores(scores, n, min_score, streams)  # (order: keeps the owner)
                     self.scored = True
+                if inliers_out is not None:
+                    self.masks[len(self.keep)], inliers_out = _device_mask(inliers_out, n, streams)
+                    self.masked = True
             else:
                 it.a, it.b, it.n = _ptr(a), _ptr(b), n
             it.opt = C.pointer(o)
@@ -597,6 +674,7 @@ class Batch:
             it.inliers = _ptr(inl)
             it.stats = C.pointer(st)
             self.keep.append((kind, a, b, o, cam, c1, c2, model, inl, st, n, order, rows))
+            self.mask_out.append(inliers_out)
         _sync_streams(streams)  # (once per device, not per tensor: the producers' work is complete before run())
 
     def run(self, max_in_flight=8, devices=None):
@@ -605,6 +683,10 @@ class Batch:
         if self.on_device:
             if devices is not None:
                 raise ValueError("devices= with device points: the memory belongs to one device (set_device selects it)")
+            if self.masked:
+                L.check(L.lib().pl_estimate_batch_dev_masked(self.items, self.scores if self.scored else None, self.masks, self.n_used,
+                                                             C.c_size_t(len(self.keep)), C.c_int(int(max_in_flight))))
+                return
             if self.scored:
                 L.check(L.lib().pl_estimate_batch_dev_scored(self.items, self.scores, self.n_used, C.c_size_t(len(self.keep)),
                                                              C.c_int(int(max_in_flight))))
@@ -630,7 +712,7 @@ class Batch:
         out = []
         for i, (kind, a, b, o, cam, c1, c2, model, inl, st, n, order, rows) in enumerate(self.keep):
             if self.on_device:
-                info = _info(st, inl[:n], self.n_used[i] if self.scored else None)
+                info = _info(st, inl[:n] if self.mask_out[i] is None else self.mask_out[i], self.n_used[i] if self.scored else n)
             elif rows is not None:  # host scores: the mask of the ranked rows back in the caller's numbering
                 mask = np.zeros(rows, dtype=np.uint8)
                 mask[order] = inl[:n]
@@ -947,12 +1029,12 @@ def ransac_batch(problems, opts, max_in_flight=4, group_size=16):
     return b.results()
 
 
-def estimate_fundamental(points2D_1, points2D_2, opt=None, initial_F=None, scores=None, min_score=None):
-    return _estimate_matrix("pl_estimate_fundamental", KIND_FUND, points2D_1, points2D_2, opt, initial_F, scores, min_score)
+def estimate_fundamental(points2D_1, points2D_2, opt=None, initial_F=None, scores=None, min_score=None, inliers_out=None):
+    return _estimate_matrix("pl_estimate_fundamental", KIND_FUND, points2D_1, points2D_2, opt, initial_F, scores, min_score, inliers_out)
 
 
-def estimate_homography(points2D_1, points2D_2, opt=None, initial_H=None, scores=None, min_score=None):
-    return _estimate_matrix("pl_estimate_homography", KIND_HOM, points2D_1, points2D_2, opt, initial_H, scores, min_score)
+def estimate_homography(points2D_1, points2D_2, opt=None, initial_H=None, scores=None, min_score=None, inliers_out=None):
+    return _estimate_matrix("pl_estimate_homography", KIND_HOM, points2D_1, points2D_2, opt, initial_H, scores, min_score, inliers_out)
 
 
 # ------------------------------------------------------------------------------------------ ransac_* on normalised points
@@ -1386,15 +1468,117 @@ def solve_batch(kind: int, first, second, full_records: bool = False):
     return (out if full_records else out[:, :, :16].copy()), cnt
 
 
-def undistort_points(camera, points2D):
+def _device_points_out(out, n, streams=None):
+    """(pl_device_points_out descriptor, the object that owns the memory) of an (n, 2) float64 GPU tensor / __cuda_array_interface__
+    object the library writes - a strided view (two columns of a wider block) keeps its strides; nothing is ever copied, so a
+    column stride other than 1 is an error.  Synchronisation as _device_points."""
+    if _is_torch_tensor(out):
+        if not out.is_cuda:
+            raise ValueError("out= must be on the GPU when the points are")
+        if out.dim() != 2 or out.shape[1] != 2 or int(out.shape[0]) != n:
+            raise ValueError(f"out=: expected an ({n}, 2) tensor, got {tuple(out.shape)}")
+        if str(out.dtype) != "torch.float64":
+            raise ValueError(f"out= must be float64, not {out.dtype}")
+        index = out.device.index
+        torch = sys.modules.get(type(out).__module__.split(".")[0])
+        if index is None and torch is not None:
+            index = torch.cuda.current_device()
+        if index != _selected_device():
+            raise ValueError(f"out= lives on device {index}, this thread selected device {_selected_device()} (set_device)")
+        if n > 1 and (out.stride(1) != 1 or out.stride(0) < 2):
+            raise ValueError("out= needs a column stride of 1 and a row stride of at least 2 elements")
+        if n == 1 and out.stride(1) != 1:
+            raise ValueError("out= needs a column stride of 1")
+        if torch is not None:
+            if streams is None:
+                torch.cuda.current_stream(out.device).synchronize()
+            else:
+                streams.setdefault(index, (torch, out.device))
+        row = int(out.stride(0)) if n > 1 else 2
+        return L.DevicePointsOut(out.data_ptr() if n else None, row, L.PL_F64, 2), out
+    if not _on_device(out):
+        raise ValueError("out= must be on the GPU when the points are")
+    cai = out.__cuda_array_interface__
+    shape = tuple(cai["shape"])
+    if len(shape) != 2 or shape[1] != 2 or int(shape[0]) != n:
+        raise ValueError(f"out=: expected an ({n}, 2) array, got {shape}")
+    if _TYPESTR_DTYPES.get(cai["typestr"], (None, 0))[0] != L.PL_F64:
+        raise ValueError(f"out= must be float64, not typestr {cai['typestr']!r}")
+    if cai["data"][1]:
+        raise ValueError("out= is read-only")
+    strides = cai.get("strides")
+    row = 2
+    if strides is not None:
+        if strides[0] % 8 or strides[1] != 8 or (n > 1 and strides[0] < 16):
+            raise ValueError("out= needs a column stride of 1 and a row stride of at least 2 elements")
+        if n > 1:
+            row = strides[0] // 8
+    return L.DevicePointsOut(int(cai["data"][0]) if n else None, int(row), L.PL_F64, 2), out
+
+
+def _new_device_out(points2D, n):
+    """a new (n, 2) float64 tensor next to a torch tensor; any other device array cannot be allocated from here"""
+    if not _is_torch_tensor(points2D):
+        raise ValueError("device points that are no torch tensor need out=: a float64 (N, 2) device array to write")
+    torch = sys.modules[type(points2D).__module__.split(".")[0]]
+    return torch.empty((n, 2), dtype=torch.float64, device=points2D.device)
+
+
+def undistort_points(camera, points2D, out=None):
     """Pixels of a distorting camera -> pixels of the distortion-free camera with the same focal lengths and principal
     point (pl_undistort_points: Camera::unproject per point on the device, then fx u + cx, fy v + cy).  The stage in
-    front of estimate_homography / estimate_fundamental, which take no camera."""
-    a = _pts(points2D, 2)
-    out = np.zeros_like(a)
+    front of estimate_homography / estimate_fundamental, which take no camera.
+
+    points2D on the GPU (a torch tensor or a __cuda_array_interface__ object, float32 or float64, strided rows): the result stays
+    there (pl_undistort_points_dev) - out= (float64, (N, 2), may be a strided view such as columns 0:2 of an (N, 4) tensor, or
+    points2D itself when that is float64) is written and returned; without it a torch tensor gives a new float64 tensor on its
+    device, any other device array needs out=.  The values are those of the host call on the same numbers as doubles, bit for bit."""
+    if not _on_device(points2D):
+        if out is not None:
+            raise ValueError("out= goes with points on the GPU; host points return a new array")
+        a = _pts(points2D, 2)
+        res = np.zeros_like(a)
+        c = _as_camera(camera)._c()
+        L.check(L.lib().pl_undistort_points(C.byref(c), _ptr(a), C.c_size_t(a.shape[0]), _ptr(res)))
+        return res
+    streams = {}
+    src, n, keep = _device_points(points2D, 2, streams)
+    if out is None:
+        out = _new_device_out(points2D, n)
+    dst, out = _device_points_out(out, n, streams)
+    _sync_streams(streams)
     c = _as_camera(camera)._c()
-    L.check(L.lib().pl_undistort_points(C.byref(c), _ptr(a), C.c_size_t(a.shape[0]), _ptr(out)))
+    L.check(L.lib().pl_undistort_points_dev(C.byref(c), C.byref(src), C.c_size_t(n), C.byref(dst)))
+    del keep
     return out
+
+
+def undistort_points_batch(items):
+    """undistort_points for many views in one call: items = [(camera, points2D, out_or_None), ...], all on the GPU
+    (pl_undistort_points_batch_dev: one launch and one synchronisation for the whole list) or all in host memory (a loop over
+    undistort_points).  Returns the list of outputs.  A matcher batch is 2 x pairs views over a handful of cameras."""
+    items = [tuple(it) + (None,) * (3 - len(it)) for it in items]
+    on = [_on_device(p) for _, p, _ in items]
+    if len(set(on)) > 1:
+        raise ValueError("host and device items mixed in one call: pass all point sets the same way")
+    if not items or not on[0]:
+        return [undistort_points(cam, p, o) for cam, p, o in items]
+    streams, keep, outs = {}, [], []
+    rec = (L.UndistortItemDev * len(items))()
+    for k, (cam, p, o) in enumerate(items):
+        src, n, owner = _device_points(p, 2, streams)
+        if o is None:
+            o = _new_device_out(p, n)
+        dst, o = _device_points_out(o, n, streams)
+        c = _as_camera(cam)._c()
+        keep.append((owner, c))
+        outs.append(o)
+        rec[k].camera = C.pointer(c)
+        rec[k].points2D, rec[k].n, rec[k].out = src, n, dst
+    _sync_streams(streams)
+    L.check(L.lib().pl_undistort_points_batch_dev(rec, C.c_size_t(len(items))))
+    del keep
+    return outs
 
 
 def device_count() -> int:

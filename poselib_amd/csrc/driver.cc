@@ -19,6 +19,7 @@
 #include "../../include/poselib_amd.h"
 #include "pl_focal.h"
 #include "pl_kernels.h"
+#include "pl_ranges.h"
 #include "pl_refine_cam.h"
 #include "pl_sfocal.h"
 #include "pl_solver_6ptf.h"
@@ -125,6 +126,8 @@ struct Context {
     DevBuf lm_tasks, lm_records, gather_idx, gather_out, mask, lm_scratch, tmp_model, solve_in, solve_out, solve_cnt, focal_stage;
     HostBuf h_rec_meta, h_focal, h_in;
     HostBuf h_pstats; // the record k_point_stats writes (the *_dev front-ends)
+    HostBuf h_undistort; // the member table of pl_undistort_points_batch_dev
+    HostBuf h_mask_fill; // ... and of the zero fill in front of a call with device masks (launch_mask_fill_g)
     // scored items (the *_dev_scored front-ends): the sides of the merge passes, the permutations, the permuted fp64 blocks; the
     // argument tables and the kept counts the kernels write
     DevBuf rank_keys, rank_rows, rank_order, ranked_pts;
@@ -139,6 +142,9 @@ thread_local Context *g_ctx = nullptr;
 
 thread_local int g_requested_device = 0;
 thread_local const pl_shard *g_shard = nullptr; // set around ransac_core by pl_ransac_run_sharded
+// set around a single-problem *_dev run whose inlier mask goes to the caller's device memory (run_item_dev, driver_batch.inc): the
+// launches that compute the returned model's mask write it there as well (RansacRun::run); the run's host `inliers` is then null
+thread_local const MaskDest *g_mask_dest = nullptr;
 
 int get_context(Context **out) {
     int ndev = 0;
@@ -837,6 +843,7 @@ struct MaskTail {
     const double *incumbent_rec; // host record of the incumbent (best model so far)
     double thr2;
     uint8_t *host_mask;          // N bytes or nullptr
+    const MaskDest *dst = nullptr; // the caller's device copy or nullptr
 };
 
 // Runs all jobs as one batched LM launch; the refined parameters become records ON THE DEVICE (k_task_records),
@@ -929,7 +936,7 @@ int run_refinements(Context *c, const pl_problem *p, std::vector<RefineJob> &job
                                      c->tmp_model.as<double>(), c->stream));
         HIP_TRY(c->h_mask.ensure(std::max<uint32_t>(p->n, 1u)));
         HIP_TRY(launch_mask(p->kind, p->ps, c->tmp_model.as<double>(), tail->thr2, c->mask.as<uint8_t>(),
-                            tail->host_mask ? c->h_mask.dev<uint8_t>() : nullptr, c->stream));
+                            tail->host_mask ? c->h_mask.dev<uint8_t>() : nullptr, c->stream, tail->dst));
     }
     HIP_TRY(wait_stream(c));
     if (tail && tail->host_mask && p->n) // the kernel wrote the pinned copy itself
@@ -1755,6 +1762,7 @@ struct RansacRun {
                 tail.incumbent_rec = best_record;
                 tail.thr2 = thr2;
                 tail.host_mask = inliers;
+                tail.dst = g_mask_dest;
                 int rc = run_refinements(c, p, fin, true, thr2, &tail);
                 if (rc != PL_OK)
                     return rc;
@@ -1775,7 +1783,7 @@ struct RansacRun {
                                    c->stream));
             HIP_TRY(c->h_mask.ensure(N));
             HIP_TRY(launch_mask(kind, p->ps, c->tmp_model.as<double>(), thr2, c->mask.as<uint8_t>(),
-                                inliers ? c->h_mask.dev<uint8_t>() : nullptr, c->stream));
+                                inliers ? c->h_mask.dev<uint8_t>() : nullptr, c->stream, g_mask_dest));
             HIP_TRY(wait_stream(c));
             if (inliers)
                 std::memcpy(inliers, c->h_mask.p, N);
@@ -4089,8 +4097,8 @@ int pl_estimate_homography(const double *x1, const double *x2, size_t n, const p
 
 // ---------------------------------------------------------------------------- un-distortion stage
 int pl_undistort_points(const pl_camera *camera, const double *points2D, size_t n, double *out) {
-    if (!camera || !camera_supported(camera) || camera->model_id == CAM_NULL)
-        return fail(PL_ERR_UNSUPPORTED, "camera model not supported (SIMPLE_PINHOLE, PINHOLE, SIMPLE_RADIAL, RADIAL, OPENCV, OPENCV_FISHEYE, SIMPLE_RADIAL_FISHEYE, RADIAL_FISHEYE)");
+    if (undistort_camera_check(camera) != PL_OK) // (driver_dev.inc: the device-memory form says the same)
+        return PL_ERR_UNSUPPORTED;
     if (n > 0x7fffffffu)
         return fail(PL_ERR_INVALID, "too many points");
     if (n && (!points2D || !out))

@@ -147,7 +147,12 @@ int run_item(pl_batch_item &it) {
 }
 
 // ... of pl_estimate_batch_dev: the matching pl_estimate_*_dev (kinds 0 - 3; the others are answered before anything runs)
-int run_item_dev(const pl_batch_item_dev &it) {
+// mdest: the item's inlier mask goes to the caller's device memory (it.inliers is null): the run's mask launch writes it there
+int run_item_dev(const pl_batch_item_dev &it, const MaskDest *mdest) {
+    struct Scope { // (a run that ends early leaves nothing set for the thread's next call)
+        explicit Scope(const MaskDest *d) { g_mask_dest = d; }
+        ~Scope() { g_mask_dest = nullptr; }
+    } scope(mdest);
     switch (it.kind) {
     case EST_ABS:
         return pl_estimate_absolute_pose_dev(&it.a, &it.b, it.n, it.opt, it.camera1, static_cast<pl_camera_pose *>(it.model), it.inliers,
@@ -163,12 +168,15 @@ int run_item_dev(const pl_batch_item_dev &it) {
         return fail(PL_ERR_UNSUPPORTED, "pl_batch_item_dev.kind: only kinds 0..3 are served from device memory");
     }
 }
-int run_group_member_alone(GroupItem &g) { return g.ditem ? run_item_dev(*g.ditem) : run_item(*g.item); }
+int run_group_member_alone(GroupItem &g) { return g.ditem ? run_item_dev(*g.ditem, g.mdest) : run_item(*g.item); }
 // what pl_estimate_batch_dev hands to estimate_batch_on next to the host-side copies of its items (a == b == null)
 struct DeviceBatch {
     const pl_batch_item_dev *items;
     std::vector<int> decided;       // per item: PL_OK, or the status it got before anything ran (unsupported kind, rejected descriptor)
     std::vector<std::string> cause; // ... and why
+    const MaskDest *masks = nullptr; // pl_estimate_batch_dev_masked: per item, where its inlier mask goes in the caller's device memory
+                                     // (data == null: to the item's host pointer as ever)
+    const MaskDest *mask_of(size_t i) const { return masks && masks[i].data ? &masks[i] : nullptr; }
 };
 
 // one group of same-kind problems through the group launches; whatever it could not finish goes through the
@@ -467,6 +475,7 @@ static int estimate_batch_on(int device, pl_batch_item *items, size_t count, int
             GroupItem g;
             g.item = &items[v[j]];
             g.ditem = dev ? &dev->items[v[j]] : nullptr;
+            g.mdest = dev ? dev->mask_of(v[j]) : nullptr;
             g.kind = k;
             groups.back().push_back(g);
         }
@@ -562,7 +571,7 @@ static int estimate_batch_on(int device, pl_batch_item *items, size_t count, int
         jobs.emplace_back([items, i, dev] {
             if (dev && dev->decided[i] != PL_OK)
                 return;
-            items[i].status = dev ? run_item_dev(dev->items[i]) : run_item(items[i]);
+            items[i].status = dev ? run_item_dev(dev->items[i], dev->mask_of(i)) : run_item(items[i]);
             if (items[i].status != PL_OK)
                 note_worker_error();
         });
@@ -693,13 +702,17 @@ int pl_estimate_batch_devices(pl_batch_item *items, size_t count, const int *dev
 // copies of their records (a == b == null) next to the caller's descriptors.
 // (scores: null, or count entries - pl_estimate_batch_dev_scored: the items whose entry has data are ranked first, all at once, and
 // enter the call as plain items over their kept rows in ranked order)
+// (masks: null, or count entries - pl_estimate_batch_dev_masked: an item whose entry has data gets its inlier mask there, in device
+// memory.  All such destinations are zero-filled by one launch in front of everything; the mask launch of the item's group, or of
+// its single run, then writes the flags itself - a scored item's through the permutation its ranking left on the device)
 static int estimate_batch_dev_impl(pl_batch_item_dev *items, const pl_device_scores *scores, size_t *n_used, size_t count,
-                                   int max_in_flight) {
+                                   int max_in_flight, const pl_device_mask *masks = nullptr) {
     if (count == 0)
         return PL_OK;
     if (!items)
         return fail(PL_ERR_INVALID, "items pointer is null");
     auto scored = [&](size_t i) { return scores && scores[i].data; };
+    auto masked = [&](size_t i) { return masks && masks[i].data; };
     if (n_used)
         for (size_t i = 0; i < count; ++i)
             n_used[i] = 0;
@@ -738,6 +751,8 @@ static int estimate_batch_dev_impl(pl_batch_item_dev *items, const pl_device_sco
             rc = check_points_plain(&it.b, it.n, it.kind == EST_ABS ? 3 : 2);
         if (rc == PL_OK && scored(i))
             rc = check_scores_plain(&scores[i], it.n);
+        if (rc == PL_OK && masked(i))
+            rc = check_mask_plain(&masks[i], it.n);
         if (rc != PL_OK)
             decide(i, rc);
     }
@@ -762,8 +777,31 @@ static int estimate_batch_dev_impl(pl_batch_item_dev *items, const pl_device_sco
             const pl_device_points p = scores_as_points(&scores[i]);
             rc = name_the_scores(allocations.check(c, &p, items[i].n));
         }
+        if (rc == PL_OK && masked(i) && items[i].n)
+            rc = name_the_mask(allocations.check_bytes(c, masks[i].data, mask_bytes(&masks[i], items[i].n)));
         if (rc != PL_OK)
             decide(i, rc);
+    }
+    // the device masks: zero flags everywhere first, one launch (a refused item's destination is not touched)
+    std::vector<MaskDest> mdest;
+    if (masks) {
+        mdest.assign(count, MaskDest{nullptr, 0, nullptr});
+        std::vector<MaskFillArgs> fill(count, MaskFillArgs{nullptr, 0, 0, 0});
+        for (size_t i = 0; i < count; ++i)
+            if (masked(i) && dev.decided[i] == PL_OK && items[i].n) {
+                mdest[i].data = masks[i].data, mdest[i].stride = masks[i].stride;
+                fill[i].data = masks[i].data, fill[i].stride = masks[i].stride, fill[i].n = (uint32_t)items[i].n;
+            }
+        rc = enqueue_mask_fill(c, fill.data(), count);
+        if (rc == PL_OK) // (the items run on the workers' streams)
+            rc = wait_stream(c) == hipSuccess ? PL_OK : fail(PL_ERR_HIP, "zero fill of the device masks");
+        if (rc != PL_OK) {
+            for (size_t i = 0; i < count; ++i)
+                if (dev.decided[i] == PL_OK)
+                    items[i].status = rc;
+            return rc;
+        }
+        dev.masks = mdest.data();
     }
     // the scored items: one ranking and one permuted copy for all of them, one synchronisation; from here on they are plain items
     // of n_used rows whose contiguous fp64 blocks a group reads where they lie, and the groups form on n_used
@@ -788,10 +826,10 @@ static int estimate_batch_dev_impl(pl_batch_item_dev *items, const pl_device_sco
             return rc;
         }
         ranked_items.assign(items, items + count);
-        size_t mask_bytes = 0;
+        size_t ranked_bytes = 0;
         for (const RankMember &r : members)
-            mask_bytes += std::max<size_t>(r.kept, 1);
-        ranked_masks.assign(mask_bytes, 0);
+            ranked_bytes += std::max<size_t>(r.kept, 1);
+        ranked_masks.assign(ranked_bytes, 0);
         size_t mask_at = 0;
         for (size_t i = 0; i < count; ++i) {
             if (scored(i) && !items[i].n)
@@ -805,7 +843,17 @@ static int estimate_batch_dev_impl(pl_batch_item_dev *items, const pl_device_sco
             if (it.inliers)
                 it.inliers = ranked_masks.data() + mask_at;
             mask_at += std::max<size_t>(r.kept, 1);
+            if (masks && mdest[i].data) // the flags of the ranked rows go to the caller's rows on the device
+                mdest[i].order = c->rank_order.as<uint32_t>() + r.order_at;
         }
+        dev.items = ranked_items.data();
+    }
+    if (masks) { // an item with a device mask has no host mask: its `inliers` is not read
+        if (ranked_items.empty())
+            ranked_items.assign(items, items + count);
+        for (size_t i = 0; i < count; ++i)
+            if (masked(i))
+                ranked_items[i].inliers = nullptr;
         dev.items = ranked_items.data();
     }
     const pl_batch_item_dev *run_items = dev.items;
@@ -821,7 +869,7 @@ static int estimate_batch_dev_impl(pl_batch_item_dev *items, const pl_device_sco
     rc = estimate_batch_on(c->device, host.data(), count, max_in_flight, &dev);
     for (size_t i = 0; i < count; ++i) {
         items[i].status = host[i].status;
-        if (member_of[i] != (size_t)-1 && items[i].inliers) // the mask of the kept rows -> the caller's numbering
+        if (member_of[i] != (size_t)-1 && items[i].inliers && !masked(i)) // the mask of the kept rows -> the caller's numbering
             ranking.scatter(members[member_of[i]], ranked_items[i].inliers, items[i].inliers);
         if (n_used && dev.decided[i] == PL_OK)
             n_used[i] = run_items[i].n;
@@ -836,4 +884,9 @@ int pl_estimate_batch_dev(pl_batch_item_dev *items, size_t count, int max_in_fli
 int pl_estimate_batch_dev_scored(pl_batch_item_dev *items, const pl_device_scores *scores, size_t *n_used, size_t count,
                                  int max_in_flight) {
     return estimate_batch_dev_impl(items, scores, n_used, count, max_in_flight);
+}
+
+int pl_estimate_batch_dev_masked(pl_batch_item_dev *items, const pl_device_scores *scores, const pl_device_mask *masks, size_t *n_used,
+                                 size_t count, int max_in_flight) {
+    return estimate_batch_dev_impl(items, scores, n_used, count, max_in_flight, masks);
 }

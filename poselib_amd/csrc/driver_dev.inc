@@ -75,6 +75,12 @@ int check_points_extent(const DeviceAllocation &al, const pl_device_points *d, s
         return fail(PL_ERR_INVALID, "device points: the rows reach beyond the allocation behind data");
     return PL_OK;
 }
+// ... the same for `need` bytes at an address (a mask destination: no element type)
+int check_bytes_extent(const DeviceAllocation &al, const void *data, size_t need) {
+    if (!range_inside(reinterpret_cast<uintptr_t>(data), need, al.lo, al.size))
+        return fail(PL_ERR_INVALID, "device points: the rows reach beyond the allocation behind data");
+    return PL_OK;
+}
 int check_points_device(const Context *c, const pl_device_points *d, size_t n) {
     if (n == 0)
         return PL_OK;
@@ -106,7 +112,71 @@ struct DeviceAllocationCache {
         last = known.size() - 1;
         return check_points_extent(al, d, n);
     }
+    // ... for `need` > 0 bytes at an address
+    int check_bytes(const Context *c, const void *data, size_t need) {
+        const uintptr_t at = reinterpret_cast<uintptr_t>(data);
+        for (size_t k = 0; k < known.size(); ++k) {
+            const DeviceAllocation &al = known[(last + k) % known.size()];
+            if (at >= al.lo && at - al.lo < al.size) {
+                last = (last + k) % known.size();
+                return check_bytes_extent(al, data, need);
+            }
+        }
+        DeviceAllocation al;
+        const int rc = find_device_allocation(c, data, &al);
+        if (rc != PL_OK)
+            return rc;
+        known.push_back(al);
+        last = known.size() - 1;
+        return check_bytes_extent(al, data, need);
+    }
 };
+
+// ---- an inlier mask's destination in the caller's device memory (pl_device_mask): the points' checks
+int check_mask_plain(const pl_device_mask *d, size_t n) {
+    if (!d)
+        return fail(PL_ERR_INVALID, "device mask: descriptor is null");
+    if (n > 0x7fffffffu)
+        return fail(PL_ERR_INVALID, "too many correspondences");
+    if (d->stride < 1)
+        return fail(PL_ERR_INVALID, "device mask: stride (bytes) is below 1");
+    if (d->stride > ((int64_t)1 << 31)) // (n * stride stays far inside 64 bits)
+        return fail(PL_ERR_INVALID, "device mask: stride beyond 2^31 bytes");
+    if (!d->data && n)
+        return fail(PL_ERR_INVALID, "device mask: data is null");
+    return PL_OK;
+}
+int name_the_mask(int rc) {
+    if (rc != PL_OK) {
+        const size_t at = g_err.find("device points");
+        if (at != std::string::npos)
+            g_err.replace(at, 13, "device mask");
+    }
+    return rc;
+}
+size_t mask_bytes(const pl_device_mask *d, size_t n) { return (n - 1) * (size_t)d->stride + 1; } // (n > 0)
+int check_mask_device(const Context *c, const pl_device_mask *d, size_t n) {
+    if (n == 0)
+        return PL_OK;
+    DeviceAllocation al;
+    const int rc = find_device_allocation(c, d->data, &al);
+    return name_the_mask(rc != PL_OK ? rc : check_bytes_extent(al, d->data, mask_bytes(d, n)));
+}
+// Zero flags in the destinations of `count` members (data == null or n == 0: none), enqueued on the context's stream: what a
+// destination holds for the rows the scores drop and for an item whose host form writes no mask.  The runs that follow on other
+// streams need a wait in between; a run on this stream does not.
+int enqueue_mask_fill(Context *c, const MaskFillArgs *members, size_t count) {
+    uint32_t max_n = 0;
+    for (size_t i = 0; i < count; ++i)
+        if (members[i].data)
+            max_n = std::max(max_n, members[i].n);
+    if (!max_n)
+        return PL_OK;
+    HIP_TRY(c->h_mask_fill.ensure(sizeof(MaskFillArgs) * count));
+    std::memcpy(c->h_mask_fill.p, members, sizeof(MaskFillArgs) * count);
+    HIP_TRY(launch_mask_fill_g(c->h_mask_fill.dev<MaskFillArgs>(), (uint32_t)count, max_n, c->stream));
+    return PL_OK;
+}
 
 IngestSrc ingest_src(const pl_device_points *d) {
     IngestSrc s;
@@ -656,4 +726,178 @@ int pl_problem_create_tangent_dev(const pl_device_points *x1, const pl_device_po
     }
     p->ps.a[0] = p->d_pts;
     return PL_OK;
+}
+
+// ---------------------------------------------------------------------------- un-distortion stage, device memory to device memory
+// pl_undistort_points for rows that are in the caller's device memory and stay there: k_undistort_dev / k_undistort_dev_g
+// (ingest.hip) read the source through the ingest loader and write the caller's fp64 rows.  The range arithmetic is pl_ranges.h.
+namespace {
+
+static const char *const undistort_unsupported_camera = "camera model not supported (SIMPLE_PINHOLE, PINHOLE, SIMPLE_RADIAL, RADIAL, OPENCV, OPENCV_FISHEYE, SIMPLE_RADIAL_FISHEYE, RADIAL_FISHEYE)";
+// every supported model but NULL (pl_undistort_points' rule)
+int undistort_camera_check(const pl_camera *camera) {
+    if (!camera || !camera_supported(camera) || camera->model_id == CAM_NULL)
+        return fail(PL_ERR_UNSUPPORTED, undistort_unsupported_camera);
+    return PL_OK;
+}
+// the camera and the distortion-free camera its output pixels belong to
+void undistort_camera_terms(const pl_camera *camera, CameraParams &cam, double &fx, double &fy, double &cx, double &cy) {
+    cam = to_cam(camera);
+    if (!camera_has_two_focals(camera->model_id))
+        fx = fy = cam.p[0], cx = cam.p[1], cy = cam.p[2];
+    else
+        fx = cam.p[0], fy = cam.p[1], cx = cam.p[2], cy = cam.p[3];
+}
+
+// the destination as a point set: its memory gets the points' checks, the messages name the destination
+pl_device_points out_as_points(const pl_device_points_out *d) {
+    pl_device_points p;
+    p.data = d->data, p.row_stride = d->row_stride, p.dtype = d->dtype, p.cols = d->cols;
+    return p;
+}
+int name_the_destination(int rc) {
+    if (rc != PL_OK) {
+        const size_t at = g_err.find("device points");
+        if (at != std::string::npos)
+            g_err.replace(at, 13, "destination");
+    }
+    return rc;
+}
+// the destination's checks that need no device
+int check_out_plain(const pl_device_points_out *d, size_t n) {
+    if (!d)
+        return fail(PL_ERR_INVALID, "destination: descriptor is null");
+    if (d->dtype != PL_F64)
+        return fail(PL_ERR_INVALID, "destination: dtype must be PL_F64 (fp32 output is not offered)");
+    const pl_device_points p = out_as_points(d);
+    return name_the_destination(check_points_plain(&p, n, 2)); // (row_stride >= cols == 2, 8-byte alignment, null data, n)
+}
+// Source and destination together: in place when the destination IS the source (same address, same stride, fp64), otherwise the
+// two byte ranges must not share a byte.
+int check_undistort_ranges(const pl_device_points *src, const pl_device_points_out *out, size_t n) {
+    if (n == 0)
+        return PL_OK;
+    if (out->data == src->data && out->row_stride == src->row_stride && src->dtype == PL_F64)
+        return PL_OK;
+    uint64_t src_bytes = 0, out_bytes = 0;
+    if (!rows_span_bytes(n, src->row_stride, 2, src->dtype == PL_F32 ? sizeof(float) : sizeof(double), &src_bytes) ||
+        !rows_span_bytes(n, out->row_stride, 2, sizeof(double), &out_bytes))
+        return fail(PL_ERR_INVALID, "destination: the rows' extent does not fit 64 bits");
+    if (ranges_overlap(reinterpret_cast<uintptr_t>(src->data), src_bytes, reinterpret_cast<uintptr_t>(out->data), out_bytes))
+        return fail(PL_ERR_INVALID, "destination: overlaps the source (in place needs the same address, the same row_stride and an fp64 source)");
+    return PL_OK;
+}
+int check_undistort_plain(const pl_camera *camera, const pl_device_points *src, size_t n, const pl_device_points_out *out) {
+    int rc = undistort_camera_check(camera);
+    if (rc == PL_OK)
+        rc = check_points_plain(src, n, 2);
+    if (rc == PL_OK)
+        rc = check_out_plain(out, n);
+    if (rc == PL_OK)
+        rc = check_undistort_ranges(src, out, n);
+    return rc;
+}
+UndistortDevArgs undistort_dev_args(const pl_camera *camera, const pl_device_points *src, size_t n, const pl_device_points_out *out) {
+    UndistortDevArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.src = ingest_src(src);
+    a.n = (uint32_t)n;
+    undistort_camera_terms(camera, a.cam, a.fx, a.fy, a.cx, a.cy);
+    a.out = static_cast<double *>(out->data);
+    a.out_stride = out->row_stride;
+    return a;
+}
+
+} // namespace
+
+int pl_undistort_points_dev(const pl_camera *camera, const pl_device_points *points2D, size_t n, const pl_device_points_out *out) {
+    int rc = check_undistort_plain(camera, points2D, n, out);
+    Context *c = nullptr;
+    if (rc == PL_OK)
+        rc = get_context(&c);
+    if (rc != PL_OK || n == 0)
+        return rc;
+    rc = check_points_device(c, points2D, n);
+    if (rc == PL_OK) {
+        const pl_device_points p = out_as_points(out);
+        rc = name_the_destination(check_points_device(c, &p, n));
+    }
+    if (rc != PL_OK)
+        return rc;
+    HIP_TRY(launch_undistort_dev(undistort_dev_args(camera, points2D, n, out), c->stream));
+    HIP_TRY(wait_stream(c));
+    return PL_OK;
+}
+
+int pl_undistort_points_batch_dev(pl_undistort_item_dev *items, size_t count) {
+    if (count == 0)
+        return PL_OK;
+    if (!items)
+        return fail(PL_ERR_INVALID, "items pointer is null");
+    if (count > 0x7fffffffu)
+        return fail(PL_ERR_INVALID, "too many items");
+    std::vector<std::string> cause(count);
+    auto decide = [&](size_t i, int rc) { // (rc came from fail(): g_err holds the cause)
+        items[i].status = rc;
+        cause[i] = g_err;
+    };
+    auto first_decided = [&]() -> int {
+        for (size_t i = 0; i < count; ++i)
+            if (items[i].status != PL_OK)
+                return fail(items[i].status, ("pl_undistort_points_batch_dev: item " + std::to_string(i) + ": " + cause[i]).c_str());
+        return PL_OK;
+    };
+    for (size_t i = 0; i < count; ++i) {
+        items[i].status = PL_OK;
+        const int rc = check_undistort_plain(items[i].camera, &items[i].points2D, items[i].n, &items[i].out);
+        if (rc != PL_OK)
+            decide(i, rc);
+    }
+    Context *c;
+    int rc = get_context(&c);
+    if (rc != PL_OK) { // no device: what was decided without one comes first
+        const std::string why = g_err;
+        const int first = first_decided();
+        for (size_t i = 0; i < count; ++i)
+            if (items[i].status == PL_OK)
+                items[i].status = rc;
+        return first != PL_OK ? first : fail(rc, why.c_str());
+    }
+    DeviceAllocationCache allocations;
+    uint32_t max_n = 0;
+    for (size_t i = 0; i < count; ++i) {
+        if (items[i].status != PL_OK)
+            continue;
+        rc = allocations.check(c, &items[i].points2D, items[i].n);
+        if (rc == PL_OK) {
+            const pl_device_points p = out_as_points(&items[i].out);
+            rc = name_the_destination(allocations.check(c, &p, items[i].n));
+        }
+        if (rc != PL_OK)
+            decide(i, rc);
+        else
+            max_n = std::max(max_n, (uint32_t)items[i].n);
+    }
+    // one table (pinned and mapped: the kernel reads it where it lies), one launch, one synchronisation; a refused or empty item is a
+    // member with n == 0
+    if (max_n) {
+        HIP_TRY(c->h_undistort.ensure(sizeof(UndistortDevArgs) * count));
+        UndistortDevArgs *tab = c->h_undistort.as<UndistortDevArgs>();
+        for (size_t i = 0; i < count; ++i) {
+            if (items[i].status == PL_OK && items[i].n)
+                tab[i] = undistort_dev_args(items[i].camera, &items[i].points2D, items[i].n, &items[i].out);
+            else
+                std::memset(&tab[i], 0, sizeof(tab[i]));
+        }
+        hipError_t e = launch_undistort_dev_g(c->h_undistort.dev<UndistortDevArgs>(), (uint32_t)count, max_n, c->stream);
+        if (e == hipSuccess)
+            e = wait_stream(c);
+        if (e != hipSuccess) {
+            for (size_t i = 0; i < count; ++i)
+                if (items[i].status == PL_OK)
+                    items[i].status = PL_ERR_HIP;
+            return fail(PL_ERR_HIP, "pl_undistort_points_batch_dev: the un-distortion launch", e);
+        }
+    }
+    return first_decided();
 }

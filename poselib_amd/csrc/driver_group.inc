@@ -156,6 +156,9 @@ struct GroupItem {
     const double *raw_a = nullptr, *raw_b = nullptr; // the member's fp64 AoS blocks on the device: its slices of the raw block, or -
                                                      // contiguous fp64 sets of a pl_estimate_batch_dev item - the caller's memory
     double t_start = 0;
+    const MaskDest *mdest = nullptr; // pl_estimate_batch_dev_masked: the item's inlier mask goes to the caller's device memory - stage
+                                     // D's mask launch writes it there, the member has no slice of the pinned mask block
+    uint32_t hmask_slot = 0;         // ... every other member's slice of that block
 };
 
 size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
@@ -541,7 +544,11 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
     HIP_TRY(gc.h_meta.ensure(sizeof(RecordMeta) * kRecordFirst * count));
     HIP_TRY(gc.h_recm.ensure(sizeof(double) * kModelStride * kRecordFirst * count));
     HIP_TRY(gc.h_offsets.ensure(sizeof(uint32_t) * (size_t)count));
-    HIP_TRY(gc.h_mask.ensure(resident ? (size_t)max_n * count : raise_hw(g_hw_mask, (size_t)max_n * count)));
+    uint32_t host_masks = 0; // members whose mask comes back to the host
+    for (uint32_t i = 0; i < count; ++i)
+        if (!(*pit[i]).mdest)
+            (*pit[i]).hmask_slot = host_masks++;
+    HIP_TRY(gc.h_mask.ensure(resident ? (size_t)max_n * host_masks : raise_hw(g_hw_mask, (size_t)max_n * host_masks)));
     char *const arena = gc.arena.as<char>();
     auto slot = [&](uint32_t i, size_t off) { return arena + (size_t)i * L.total + off; };
     auto slot_buffers = [&](uint32_t i) { // member i's buffers of a batch step and the pinned mirrors of its small results
@@ -1079,11 +1086,13 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
                 continue;
             double *d_tmp = reinterpret_cast<double *>(slot(i, L.tmp_model));
             uint8_t *d_mask = reinterpret_cast<uint8_t *>(slot(i, L.mask));
-            uint8_t *h_mask_dev = gc.h_mask.dev<uint8_t>() + (size_t)i * max_n;
             hm[i].pts = g.prob.ps;
             hm[i].thr2 = g.run->thr2;
             hm[i].mask = d_mask;
-            hm[i].host_mask = h_mask_dev;
+            if (g.mdest) // the caller's device memory, written by the mask launch itself: no pinned copy, nothing to copy out below
+                hm[i].dst = *g.mdest;
+            else
+                hm[i].host_mask = gc.h_mask.dev<uint8_t>() + (size_t)g.hmask_slot * max_n;
             if (!g.looped) { // fewer points than the sample (ransac_impl.h:161-163): mask of the untouched model
                 // (not reached: group_eligible keeps such problems out; kept for completeness)
                 g.fallback = true;
@@ -1189,8 +1198,8 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
                 g.st->num_inliers = gc.h_count.as<uint32_t>()[t];
             }
             uint8_t *user_mask = resident ? g.ritem->inliers : g.item->inliers;
-            if (user_mask)
-                std::memcpy(user_mask, gc.h_mask.as<uint8_t>() + (size_t)i * max_n, g.n);
+            if (user_mask && !g.mdest)
+                std::memcpy(user_mask, gc.h_mask.as<uint8_t>() + (size_t)g.hmask_slot * max_n, g.n);
             g.st->seconds = now_s() - g.t_start;
         }
     }

@@ -11,7 +11,7 @@
 // caller's numbering on the host, with the permutation that came back.
 namespace {
 
-int run_item_dev(const pl_batch_item_dev &it); // (driver_batch.inc: the matching pl_estimate_*_dev)
+int run_item_dev(const pl_batch_item_dev &it, const MaskDest *mdest = nullptr); // (driver_batch.inc: the matching pl_estimate_*_dev)
 
 int check_scores_plain(const pl_device_scores *d, size_t n) {
     if (!d)
@@ -254,4 +254,66 @@ int pl_estimate_dev_scored(int kind, const pl_device_points *a, const pl_device_
     if (n_used)
         *n_used = kept;
     return PL_OK;
+}
+
+// The single _dev call - with scores or without - whose inlier mask goes to the caller's device memory.  The destination is
+// zero-filled first, on the stream the run follows on; the run's mask launch (RansacRun::run) then writes the flags of its rows
+// there itself, a scored item's through the permutation its ranking left in device memory: no pinned host mask, no copy, no
+// scatter on the host.  Everything else is pl_estimate_dev_scored / the plain entry point.
+int pl_estimate_dev_masked(int kind, const pl_device_points *a, const pl_device_points *b, const pl_device_scores *scores, size_t n,
+                           const pl_robust_options *opt, pl_camera *camera1, const pl_camera *camera2, void *model,
+                           const pl_device_mask *mask, pl_ransac_stats *stats, size_t *n_used) {
+    if (n_used)
+        *n_used = 0;
+    if (kind < 0 || kind > 3)
+        return fail(PL_ERR_INVALID, "pl_estimate_dev_masked: kind must be 0..3");
+    int rc = dev_entry_precheck(kind, opt, camera1, camera2); // what the plain entry point says before it looks at the points
+    if (rc == PL_OK)
+        rc = check_points_plain(a, n, 2);
+    if (rc == PL_OK)
+        rc = check_points_plain(b, n, kind == EST_ABS ? 3 : 2);
+    if (rc == PL_OK && scores)
+        rc = check_scores_plain(scores, n);
+    if (rc == PL_OK)
+        rc = check_mask_plain(mask, n);
+    Context *c = nullptr;
+    if (rc == PL_OK)
+        rc = get_context(&c);
+    if (rc == PL_OK)
+        rc = check_points_device(c, a, n);
+    if (rc == PL_OK)
+        rc = check_points_device(c, b, n);
+    if (rc == PL_OK && scores)
+        rc = check_scores_device(c, scores, n);
+    if (rc == PL_OK)
+        rc = check_mask_device(c, mask, n);
+    if (rc != PL_OK)
+        return rc;
+    const MaskFillArgs fill = {mask->data, mask->stride, (uint32_t)n, 0};
+    rc = enqueue_mask_fill(c, &fill, 1);
+    if (rc != PL_OK)
+        return rc;
+    MaskDest dest = {mask->data, mask->stride, nullptr};
+    pl_batch_item_dev it;
+    std::memset(&it, 0, sizeof(it));
+    it.kind = kind;
+    it.a = *a, it.b = *b, it.n = n;
+    it.opt = opt, it.camera1 = camera1, it.camera2 = camera2, it.model = model, it.stats = stats;
+    if (scores) {
+        std::vector<RankMember> m(1);
+        m[0].scores = scores, m[0].n = n, m[0].a = a, m[0].b = b;
+        Ranking ranking;
+        if (n) {
+            rc = ranking.run(c, m, /*grouped=*/false);
+            if (rc != PL_OK)
+                return rc;
+        }
+        it.a = ranked_points(m[0].out_a, 2, m[0].kept), it.b = ranked_points(m[0].out_b, kind == EST_ABS ? 3 : 2, m[0].kept);
+        it.n = m[0].kept;
+        dest.order = c->rank_order.as<uint32_t>() + m[0].order_at;
+    }
+    rc = run_item_dev(it, n ? &dest : nullptr);
+    if (rc == PL_OK && n_used)
+        *n_used = it.n;
+    return rc;
 }

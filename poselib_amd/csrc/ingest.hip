@@ -10,6 +10,10 @@
 //   k_ingest_ranked, k_ingest_ranked_g   k_ingest through a permutation: the rows an item's scores keep, in descending score (rank.hip)
 //   k_ingest_g, k_point_stats_g   the two for a lock-step group of problems (pl_estimate_batch_dev): the member is a grid
 //                   dimension, its arguments come from a device-visible table; the bodies are those of the single forms
+//   k_undistort_dev, k_undistort_dev_g   the un-distortion stage (k_undistort, pipeline.hip) from the caller's rows into the
+//                   caller's fp64 rows (pl_undistort_points_dev / _batch_dev): nothing passes through the host
+//   k_mask_fill_g   zero flags in the callers' inlier-mask destinations (pl_estimate_dev_masked / _batch_dev_masked), in front of
+//                   the runs whose mask launches write the inliers' flags there
 //
 // The build has -ffp-contract=off, fp64 sqrt and division on the device are IEEE (tests/test_gpu_device_math*): the sums carry
 // the host's bits.  The caller's pointers arrive as kernel arguments and are read as global memory (pl_global.h).
@@ -231,6 +235,78 @@ __global__ __launch_bounds__(256) void k_point_stats_g(const PointStatsGroupArgs
     point_stats_body(as_global(in.a_raw), as_global(in.b_raw), in.n, in.args, as_global(in.out));
 }
 
+// The un-distortion stage between two blocks of the caller's device memory: row i of the source through the ingest loader,
+// camera_unproject, and k_undistort's expression (pipeline.hip; the same build flags) into columns 0 and 1 of row i of the
+// destination - the host entry point's bits.  Both elements of the row are read before either is written: a destination that IS
+// the source (same address, same stride, fp64) is served in place; the driver refuses every other overlap.
+__device__ __forceinline__ void undistort_row(const IngestSrc &src, const CameraParams &cam, double fx, double fy, double cx, double cy,
+                                              uint32_t i, double *out, int64_t out_stride) {
+    const size_t row = (size_t)i * (size_t)src.row_stride;
+    const double px = ingest_load(src.data, src.f32, row), py = ingest_load(src.data, src.f32, row + 1);
+    double u, v;
+    camera_unproject(cam, px, py, u, v);
+    double *o = as_global(out) + (size_t)i * (size_t)out_stride;
+    o[0] = fx * u + cx;
+    o[1] = fy * v + cy;
+}
+__global__ __launch_bounds__(256) void k_undistort_dev(UndistortDevArgs in) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= in.n)
+        return;
+    undistort_row(in.src, in.cam, in.fx, in.fy, in.cx, in.cy, i, in.out, in.out_stride);
+}
+// ... of every member of a call (blockIdx.z, k_ingest_g's shape): blocks beyond a member's rows return, a member with n == 0 (an
+// empty or refused item) does no work.  (in.cam, not a copy: the parameter array is indexed at run time, see k_prepare_g.)
+__global__ __launch_bounds__(256) void k_undistort_dev_g(const UndistortDevArgs *tab) {
+    const UndistortDevArgs &in = tab[blockIdx.z];
+    const uint32_t n = in.n;
+    if (blockIdx.x * 256u >= n)
+        return;
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n)
+        return;
+    undistort_row(in.src, in.cam, in.fx, in.fy, in.cx, in.cy, i, in.out, in.out_stride);
+}
+
+// Zero flags in the caller's mask destinations (pl_estimate_dev_masked / _batch_dev_masked), in front of the runs that write the
+// inliers' flags: one thread per row, one plain byte store.
+__global__ __launch_bounds__(256) void k_mask_fill_g(const MaskFillArgs *tab) {
+    const MaskFillArgs &in = tab[blockIdx.z];
+    const uint32_t n = in.n;
+    if (blockIdx.x * 256u >= n)
+        return;
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n)
+        return;
+    as_global(in.data)[(size_t)i * (size_t)in.stride] = 0;
+}
+hipError_t launch_mask_fill_g(const MaskFillArgs *tab, uint32_t G, uint32_t max_n, hipStream_t stream) {
+    constexpr uint32_t kMembersPerLaunch = 32768; // (a grid's z extent ends at 65535)
+    for (uint32_t at = 0; at < G && max_n; at += kMembersPerLaunch) {
+        k_mask_fill_g<<<dim3((max_n + 255) / 256, 1, G - at < kMembersPerLaunch ? G - at : kMembersPerLaunch), dim3(256), 0, stream>>>(tab + at);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess)
+            return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_undistort_dev(const UndistortDevArgs &args, hipStream_t stream) {
+    if (args.n == 0)
+        return hipSuccess;
+    k_undistort_dev<<<dim3((args.n + 255) / 256), dim3(256), 0, stream>>>(args);
+    return hipGetLastError();
+}
+hipError_t launch_undistort_dev_g(const UndistortDevArgs *tab, uint32_t G, uint32_t max_n, hipStream_t stream) {
+    constexpr uint32_t kMembersPerLaunch = 32768; // (a grid's z extent ends at 65535)
+    for (uint32_t at = 0; at < G && max_n; at += kMembersPerLaunch) {
+        k_undistort_dev_g<<<dim3((max_n + 255) / 256, 1, G - at < kMembersPerLaunch ? G - at : kMembersPerLaunch), dim3(256), 0, stream>>>(tab + at);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess)
+            return e;
+    }
+    return hipSuccess;
+}
 hipError_t launch_ingest(const IngestSrc &a, const IngestSrc &b, uint32_t n, double *out_a, double *out_b, hipStream_t stream) {
     if (n == 0 || (!out_a && !out_b))
         return hipSuccess;

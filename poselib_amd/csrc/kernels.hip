@@ -2725,7 +2725,8 @@ template <int EST> __global__ __launch_bounds__(kSeqThreads) void k_score_seq_gb
 
 // ------------------------------------------------------------------------------------ mask
 template <int EST>
-__device__ __forceinline__ void mask_body(const PointSet &pts, const double *model, double thr2, uint8_t *mask, uint8_t *host_mask) {
+__device__ __forceinline__ void mask_body(const PointSet &pts, const double *model, double thr2, uint8_t *mask, uint8_t *host_mask,
+                                          const MaskDest &dst) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= pts.n)
         return;
@@ -2747,17 +2748,21 @@ __device__ __forceinline__ void mask_body(const PointSet &pts, const double *mod
     mask[i] = in ? 1 : 0;
     if (host_mask)
         host_mask[i] = in ? 1 : 0;
+    if (dst.data) { // the caller's device copy: one plain byte store per row, through the ranking's permutation for a scored item
+        const size_t row = dst.order ? dst.order[i] : i;
+        dst.data[row * (size_t)dst.stride] = in ? 1 : 0;
+    }
 }
 template <int EST> __global__ __launch_bounds__(256) void k_mask(PointSet pts, const double *model, double thr2, uint8_t *mask,
-                                                                 uint8_t *host_mask) {
-    mask_body<EST>(pts, model, thr2, mask, host_mask);
+                                                                 uint8_t *host_mask, MaskDest dst) {
+    mask_body<EST>(pts, model, thr2, mask, host_mask, dst);
 }
 template <int EST> __global__ __launch_bounds__(256) void k_mask_g(const MaskArgs *arr) {
     const MaskArgs &in = arr[blockIdx.z];
     if (blockIdx.x * 256u >= in.pts.n)
         return;
     const MaskArgs a = globalised(in);
-    mask_body<EST>(a.pts, a.model, a.thr2, a.mask, a.host_mask);
+    mask_body<EST>(a.pts, a.model, a.thr2, a.mask, a.host_mask, a.dst);
 }
 
 // ------------------------------------------------------------------------------------ LM
@@ -4824,11 +4829,13 @@ hipError_t launch_lm2(int est, const PointSet &pts, LMTask *tasks, uint32_t num_
 }
 
 hipError_t launch_mask(int est, const PointSet &pts, const double *model, double thr2, uint8_t *mask,
-                       uint8_t *host_mask, hipStream_t stream) {
+                       uint8_t *host_mask, hipStream_t stream, const MaskDest *dst) {
     if (pts.n == 0)
         return hipSuccess;
     const dim3 grid((pts.n + 255) / 256), block(256);
-    PL_DISPATCH_EST_0TO5(est, k_mask<E><<<grid, block, 0, stream>>>(pts, model, thr2, mask, host_mask));
+    const MaskDest none = {nullptr, 0, nullptr};
+    const MaskDest d = dst ? *dst : none;
+    PL_DISPATCH_EST_0TO5(est, k_mask<E><<<grid, block, 0, stream>>>(pts, model, thr2, mask, host_mask, d));
     return hipGetLastError();
 }
 

@@ -129,6 +129,8 @@ __device__ __forceinline__ MaskArgs globalised(MaskArgs m) {
     m.model = as_global(m.model);
     m.mask = as_global(m.mask);
     m.host_mask = as_global(m.host_mask);
+    m.dst.data = as_global(m.dst.data);
+    m.dst.order = as_global(m.dst.order);
     return m;
 }
 __device__ __forceinline__ SelectArgs globalised(SelectArgs s) {

@@ -268,6 +268,19 @@ struct PointStatsGroupArgs {
     PointStatsRecord *out;       // device-visible
 };
 hipError_t launch_point_stats_g(const PointStatsGroupArgs *tab, uint32_t G, hipStream_t stream);
+// The un-distortion stage (launch_undistort) from the caller's device rows into the caller's fp64 rows (ingest.hip): one member of
+// pl_undistort_points_batch_dev, or the arguments of the single call
+struct UndistortDevArgs {
+    IngestSrc src;         // N x 2
+    uint32_t n, pad;       // rows; 0: no work
+    CameraParams cam;
+    double fx, fy, cx, cy; // the distortion-free camera the output pixels belong to
+    double *out;           // columns 0 and 1 of row i are written, nothing else
+    int64_t out_stride;    // ELEMENTS between rows, >= 2
+};
+hipError_t launch_undistort_dev(const UndistortDevArgs &args, hipStream_t stream);
+// member = blockIdx.z, device-visible table; max_n: the largest n of the table
+hipError_t launch_undistort_dev_g(const UndistortDevArgs *tab, uint32_t G, uint32_t max_n, hipStream_t stream);
 // ---- one confidence per row next to the correspondences (rank.hip; pl_device_scores once the driver has checked it).  The rule:
 // row i is kept iff score[i] >= min_score (a NaN never is); kept rows go in descending score, equal scores (-0.0 == 0.0) in ascending
 // row index.  fp32 scores widen exactly, so one 64-bit key serves both dtypes and the pair (key, row) is a total order: the
@@ -342,9 +355,26 @@ int tangent_score_chunk(); // correspondences per chunk of k_score_tangent (EST_
 int radial1d_score_chunk(); // correspondences per chunk of k_score_radial1d (EST_RAD1D)
 // num_models[iters] -> slots (compact list of record indices in (iteration, model) order) + count
 hipError_t launch_lm(int est, const PointSet &pts, LMTask *tasks, uint32_t num_tasks, hipStream_t stream);
+// An inlier mask's destination in the CALLER's device memory (pl_device_mask once the driver has checked it): the flag of the
+// run's row i goes to byte (order ? order[i] : i) * stride - order: the permutation a scored item's ranking left in device
+// memory (rank.hip), so the flags land in the caller's numbering without a host round trip.  data == null: none.
+struct MaskDest {
+    uint8_t *data;
+    int64_t stride; // BYTES between the flags of consecutive rows, >= 1
+    const uint32_t *order;
+};
 // host_mask (pinned, device-mapped; may be null): the kernel writes a second copy there itself - no copy dispatch
+// dst (may be null): ... and the caller's device copy, in the same launch
 hipError_t launch_mask(int est, const PointSet &pts, const double *model, double thr2, uint8_t *mask,
-                       uint8_t *host_mask, hipStream_t stream);
+                       uint8_t *host_mask, hipStream_t stream, const MaskDest *dst = nullptr);
+// Zero flags for the n rows of every member's destination (ingest.hip): what a destination holds for the rows its scores drop and
+// for an item whose host form writes no mask.  member = blockIdx.z, device-visible table; max_n: the largest n of the table
+struct MaskFillArgs {
+    uint8_t *data;
+    int64_t stride;
+    uint32_t n, pad;
+};
+hipError_t launch_mask_fill_g(const MaskFillArgs *tab, uint32_t G, uint32_t max_n, hipStream_t stream);
 
 // ---- device-side bookkeeping (pipeline.hip) ----
 // the fp16 operand blocks of the matrix-core scorers, built in the same launch as the hypothesis-ordered copies (see
@@ -443,6 +473,7 @@ struct MaskArgs {
     const double *model;
     double thr2;
     uint8_t *mask, *host_mask;
+    MaskDest dst; // the caller's device copy (pl_estimate_batch_dev_masked); data == null: none
 };
 struct SelectArgs {
     const double *score_refined;
