@@ -1344,6 +1344,67 @@ __device__ __forceinline__ void abs16_tile_bits(const half8_t (&Aop)[kAbs16Dirs]
     }
 }
 
+// The same filter with the operands exchanged, and counted (score_count_body alone): the instruction's two operands have one
+// layout - index = lane % 32, k block = lane / 32 -, so the chunk's rows first and the hypothesis group's registers second deliver
+// the transposed tile: lane l = hypothesis column l % 32 of the group, register v = correspondence row 8 (v / 4) + 4 (l / 32) + v % 4
+// of the point group.  All verdicts of a lane belong to ONE hypothesis, so they need no place of their own: ONE word takes
+// every (point group, register) pair in turn (v_alignbit: the word moves up, the pair's sign bit enters at the bottom), and
+// after every second point group it holds exactly that word's 32 pairs - pair p = 16 (g % 2) + v at bit 31 - p, nothing left
+// from before - and is counted once (v_bcnt).  Same products, same v_or3, same interleave as above.  Returns the survivors
+// among this lane's 16 PG rows.
+template <int PG>
+__device__ __forceinline__ uint32_t abs16_tile_count_t(const half8_t (&Aop)[kAbs16Dirs], const uint4 (&s_b)[1 + kAbs16Dirs][PG][32], int col,
+                                                       int half) {
+    static_assert(PG % 2 == 0, "a word holds the 32 pairs of two point groups");
+    const float16_t kZero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    auto products = [&](int g, float16_t &D0, float16_t &D1, float16_t &D2) {
+        half8_t Bop[kAbs16Dirs];
+#pragma unroll
+        for (int d = 0; d < kAbs16Dirs; ++d) {
+            const uint4 braw = s_b[half ? 1 + d : 0][g][col];
+            __builtin_memcpy(&Bop[d], &braw, 16);
+        }
+        D0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(Bop[0], Aop[0], kZero, 0, 0, 0);
+        D1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(Bop[1], Aop[1], kZero, 0, 0, 0);
+        D2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(Bop[2], Aop[2], kZero, 0, 0, 0);
+    };
+    uint32_t word = 0u, n = 0u; // n: proven outliers so far
+    float16_t D0, D1, D2;
+    products(0, D0, D1, D2);
+#pragma unroll 16
+    for (int g = 1; g < PG; ++g) {
+        uint32_t T[16];
+#pragma unroll
+        for (int v = 0; v < 16; ++v)
+            T[v] = __float_as_uint(D0[v]) | __float_as_uint(D1[v]) | __float_as_uint(D2[v]);
+        products(g, D0, D1, D2);
+#pragma unroll
+        for (int v = 0; v < 16; ++v) // (the verdicts of group g - 1)
+            word = __builtin_amdgcn_alignbit(word, T[v], 31);
+        if ((g - 1) % 2)
+            n += (uint32_t)__popc(word);
+        __builtin_amdgcn_sched_group_barrier(0x002, 16, 0); // the v_or3
+        __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);  // the operands of the next group from LDS
+        __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
+        // (a word's 32 pairs depend on nothing in front of them - the compiler sees that - and the counts are a sum: without
+        // this line the scheduler starts with the last two point groups beside the first, on a second set of accumulators)
+        __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (int v = 0; v < 16; ++v) {
+        const uint32_t sg = __float_as_uint(D0[v]) | __float_as_uint(D1[v]) | __float_as_uint(D2[v]);
+        word = __builtin_amdgcn_alignbit(word, sg, 31);
+    }
+    n += (uint32_t)__popc(word); // (PG - 1 is odd: a complete word)
+    return 16u * PG - n;
+}
+
 // The hypothesis stream of this kernel is the LIVE list (pipeline.hip compact2_body): `slots` = record index per live position,
 // *num_hyp_ptr = its length, shadow16 and the partials are indexed by live position; k_finalize2 maps them back (rank[]).
 // MODE (pruned scoring, PruneArgs in pl_kernels.h): kScoreAll - the stream is the whole list (the plain launch); kScoreLead - its
@@ -1530,13 +1591,21 @@ __device__ __forceinline__ void score_mfma_body(const PointSet &pts, const uint4
 }
 
 // kScoreCount: the filter alone.  Same operands, tiles, tickets, units and (slice, chunk) placement as score_mfma_body, but behind a
-// group's tiles there is no queue and no exact pass: the survivors of hypothesis row(v) in this lane are popcount(~out[v] &
-// validbits), and the sum over the 32 lanes of a half is the hypothesis' survivor count of the chunk - an UPPER bound of its inlier
-// count there, since the filter only ever drops proven outliers.  A lane holds at most PG <= 10 per register and a 32-lane sum at
-// most 320: three counts travel in one register (10-bit fields), six registers through five DPP steps (wave_scan_u32's, without the
-// last broadcast: lanes 31 and 63 end with the totals of their halves).  survivors[chunk][position], one word per hypothesis of
-// the unit, written once per unit; positions in front of `first` are not scored.  Rows of a partial group that stand for no
-// hypothesis repeat the list's last operand row and are not written.  LDS: the B operands and one word per hypothesis of a unit.
+// group's tiles there is no queue and no exact pass, and a hypothesis' verdicts need not form a run: the tile is computed
+// TRANSPOSED (abs16_tile_count_t), hypotheses on the columns, so lane l and lane l + 32 hold between them the 32 PG verdicts of
+// hypothesis l of the group and each counts its 16 PG: survivors of a full chunk = 16 PG - the lane's proven outliers.  The two
+// halves are added through one v_permlane32_swap; lanes 0..31 then hold 32 consecutive words of survivors[chunk][...] and store
+// them, group by group: no bit field per hypothesis row, no sums across 32 lanes, no staging in LDS, no fence.  The count is an
+// UPPER bound of the hypothesis' inlier count in the chunk, since the filter only ever drops proven outliers.  Rows without a
+// correspondence exist in a problem's last chunk alone (the production launch stops in front of it, kScoreCountAll does not),
+// `pad` of them, and there the count RELIES on what the table holds for them (pipeline.hip abs16_point_row, pl_prefilter.h
+// pf16_abs_point with valid = false): every operand zero but the constant's 1 and the slack 65504, so each of a hypothesis'
+// three sums is its own constant + 65504 + zeros - not negative for a finite constant (fp16: >= -65504; an exact zero sum is +0
+// under round to nearest, in any order) nor for + inf (a model outside fp16: everything survives), and - inf for - inf (no
+// model: everything is an outlier).  Such a row is a survivor of every hypothesis that has one at all, so the chunk's workgroups
+// - a wave-uniform branch - take `pad` off the total, and zero stays zero; the full chunks carry neither mask nor branch
+// body.  survivors[chunk][position], one word per hypothesis; positions in front of `first` are not scored.  Columns of a
+// partial group that stand for no hypothesis repeat the list's last operand row and are not written.  LDS: the B operands alone.
 template <int PG>
 __device__ __forceinline__ void score_count_body(uint32_t n_points, const uint4 *__restrict__ shadow16, const uint4 *__restrict__ points16,
                                                  const uint32_t *__restrict__ num_hyp_ptr, uint32_t hyp_capacity,
@@ -1545,10 +1614,8 @@ __device__ __forceinline__ void score_count_body(uint32_t n_points, const uint4 
     constexpr int kWaves = kMfmaThreads / 64;
     constexpr int NPW = 32 * PG; // correspondences per chunk
     __shared__ uint4 s_b[1 + kAbs16Dirs][PG][32];
-    __shared__ uint32_t s_cnt[kWaves][64];
     __shared__ uint32_t s_next_unit;
     const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int col = lane & 31, half = lane >> 5;
     // (as score_mfma_body: no staging for a workgroup without a unit)
     const uint32_t Hall = *as_uniform(num_hyp_ptr);
@@ -1561,10 +1628,7 @@ __device__ __forceinline__ void score_count_body(uint32_t n_points, const uint4 
         if (!unit_of_ticket<32u>(slice * kWaves, H, waves_per_chunk, kb0, gn0))
             return;
     }
-    uint32_t validbits = 0; // bit (PG - 1 - g): group g holds a real correspondence in this column
-#pragma unroll
-    for (int g = 0; g < PG; ++g)
-        validbits |= (chunk * NPW + g * 32 + col < n_points) ? (1u << (PG - 1 - g)) : 0u;
+    const uint32_t pad = chunk * NPW + NPW > n_points ? chunk * NPW + NPW - n_points : 0u; // wave-uniform: rows without a correspondence
     const uint4 *const prow = points16 + (size_t)chunk * NPW * 4;
     for (uint32_t j = threadIdx.x; j < (uint32_t)NPW; j += kMfmaThreads) {
 #pragma unroll
@@ -1575,7 +1639,6 @@ __device__ __forceinline__ void score_count_body(uint32_t n_points, const uint4 
         s_next_unit = 0;
     __syncthreads(); // the only workgroup barrier
 
-    uint32_t *const cnt = s_cnt[wave];
     auto request_ticket = [&]() -> uint32_t { // per-lane value; lane 0 holds the workgroup's next unit
         uint32_t t = 0;
         if (lane == 0) {
@@ -1604,32 +1667,16 @@ __device__ __forceinline__ void score_count_body(uint32_t n_points, const uint4 
                 __builtin_memcpy(&Aop[d], &Araw[d], 16);
             if (hg + 1 < ngroups32) // next group's operands travel while this one is evaluated
                 load_a(hg + 1, Araw);
-            uint32_t out[16];
-            abs16_tile_bits<PG>(Aop, s_b, col, half, out);
-            uint32_t pk[6] = {0u, 0u, 0u, 0u, 0u, 0u}; // register v's count: field v % 3 of pk[v / 3]
-#pragma unroll
-            for (int v = 0; v < 16; ++v)
-                pk[v / 3] += (uint32_t)__popc(~out[v] & validbits) << (10 * (v % 3));
-#pragma unroll
-            for (int j = 0; j < 6; ++j) {
-                uint32_t s = pk[j];
-                s += dpp_shift_u32<0x111>(s);      // row_shr:1
-                s += dpp_shift_u32<0x112>(s);      // row_shr:2
-                s += dpp_shift_u32<0x114>(s);      // row_shr:4
-                s += dpp_shift_u32<0x118>(s);      // row_shr:8: lane 15 of every row holds the row's sum
-                s += dpp_shift_u32<0x142, 0xa>(s); // row_bcast:15 into rows 1 and 3: lanes 31 and 63 hold their half's
-                pk[j] = s;
-            }
-            if (col == 31) {
-#pragma unroll
-                for (int v = 0; v < 16; ++v) // row(v) = 8 (v / 4) + 4 half + v % 4, as in score_mfma_body's expansion
-                    cnt[hg * 32u + 8u * (uint32_t)(v >> 2) + 4u * (uint32_t)half + (uint32_t)(v & 3)] = (pk[v / 3] >> (10 * (v % 3))) & 0x3ffu;
-            }
+            // this lane's half of the hypothesis' count
+            const uint32_t mine = abs16_tile_count_t<PG>(Aop, s_b, col, half);
+            // lanes 32..63 of the first result <- lanes 0..31, lanes 0..31 of the second <- lanes 32..63: every lane sees both halves
+            const auto both = __builtin_amdgcn_permlane32_swap(mine, mine, false, false);
+            uint32_t total = both[0] + both[1];
+            if (pad) // (see above: every row behind the chunk's end was counted as a survivor, or none was)
+                total = max(total, pad) - pad;
+            if (half == 0 && 32u * hg + (uint32_t)col < gn)
+                survivors[(size_t)chunk * hyp_capacity + first + kb + 32u * hg + (uint32_t)col] = total;
         }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        if ((uint32_t)lane < gn)
-            survivors[(size_t)chunk * hyp_capacity + first + kb + lane] = cnt[lane];
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         ticket = (uint32_t)__builtin_amdgcn_readfirstlane((int)pending);
     }
 }
