@@ -676,8 +676,10 @@ int pl_debug_score_survivors(int route, pl_debug_prune_member *members, size_t n
  * pre-selection and exact scores, the lead left out of the exact launch, and no labels.  Members and routes as pl_debug_score_pruned.
  * Per member i and hypothesis k:
  *   bound_counts[i][k], bound_scores[i][k]   the tier's upper bound of the inlier count and lower bound of the score, for a
- *                    pre-selected position behind the lead - those of the last of the tier's two stages that saw it (the filter's
- *                    verdict, then residual bounds for what the verdict leaves undecided); 0xffffffff / NaN for every other hypothesis, and for all when the tier
+ *                    pre-selected position behind the lead - those of the last of the tier's three stages that saw it (the survivor
+ *                    count over all n correspondences - bound_counts = that count c, bound_scores = (n - c) thr^2 rounded down -,
+ *                    then the fp32 filter's verdict for what that leaves, then residual bounds for what the verdict leaves
+ *                    undecided); 0xffffffff / NaN for every other hypothesis, and for all when the tier
  *                    does not run (cstar == chunks)
  *   tiers[i][k]      0: exact scores (the lead, and what both tiers kept); 1: dropped on its survivor count; 2: dropped on its
  *                    bounds; 3: NaN model, never scored
@@ -687,6 +689,15 @@ int pl_debug_score_survivors(int route, pl_debug_prune_member *members, size_t n
  * guard_changed: words of the count columns behind the live list's end that the launches changed - which must be 0. */
 int pl_debug_score_bounded(int route, pl_debug_prune_member *members, size_t num_members, uint32_t *const *bound_counts,
                            double *const *bound_scores, uint8_t *const *tiers, uint32_t *idle_changed, uint32_t *guard_changed);
+/* Diagnostic: pl_debug_score_bounded, and the count columns as its launches left them.  columns[i]: member i's [chunks][n] words in
+ * hypothesis order (a NaN model reports 0): exact inlier counts for a hypothesis with exact scores (tiers 0); for one dropped on its
+ * bounds (tiers 2) the matrix-core filter's survivor count of every chunk - the count launch's in front of cstar, from cstar on those
+ * of the launch that counts the pre-selection behind the lead for stage S of the bound tier; for one dropped on its survivor count
+ * (tiers 1) survivor counts in front of cstar and, from cstar on, whatever the column held before the step.  A new entry point next
+ * to an unchanged one: PL_ABI_VERSION stays 5. */
+int pl_debug_score_bounded_columns(int route, pl_debug_prune_member *members, size_t num_members, uint32_t *const *bound_counts,
+                                   double *const *bound_scores, uint8_t *const *tiers, uint32_t *const *columns, uint32_t *idle_changed,
+                                   uint32_t *guard_changed);
 /* Diagnostic: 1 if a batch step of `iterations` iterations of a problem of `kind` with n_points correspondences, as a member of a
  * lock-step group (pl_ransac_batch, pl_estimate_batch), scores in the pruned form, 0 if not; pl_ransac_run's own steps never do (coordinates and threshold in the pre-filter's range assumed, as pl_debug_group_slices).  Host arithmetic only. */
 int pl_debug_score_prune_gate(int kind, uint32_t n_points, uint32_t iterations);

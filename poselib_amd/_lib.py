@@ -250,6 +250,8 @@ def _declare(L):
         "pl_debug_score_survivors": (cint, [cint, P(DebugPruneMember), sz, P(C.c_void_p), P(C.c_uint32), P(C.c_uint32)]),
         "pl_debug_score_bounded": (cint, [cint, P(DebugPruneMember), sz, P(C.c_void_p), P(C.c_void_p), P(C.c_void_p), P(C.c_uint32),
                                            P(C.c_uint32)]),
+        "pl_debug_score_bounded_columns": (cint, [cint, P(DebugPruneMember), sz, P(C.c_void_p), P(C.c_void_p), P(C.c_void_p), P(C.c_void_p),
+                                                   P(C.c_uint32), P(C.c_uint32)]),
         "pl_debug_score_prune_gate": (cint, [cint, C.c_uint32, C.c_uint32]),
         "pl_debug_lm_route": (cint, [cint, C.c_uint32, u64, P(C.c_uint32)]),
         "pl_debug_sampler_shape": (cint, [cint, u64, C.c_uint32, u64, P(DebugSamplerShape)]),
@@ -295,7 +297,7 @@ EXPORTED_SYMBOLS = [
     "pl_abi_version", "pl_problem_create_tangent", "pl_debug_inlier_mask", "pl_debug_tangent_chunk",
     "pl_p5lp_radial", "pl_debug_radial1d_chunk", "pl_debug_radial1d_generate", "pl_debug_group_slices", "pl_debug_generate",
     "pl_debug_score_shape", "pl_debug_score_stream_ex", "pl_debug_score_pruned", "pl_debug_score_survivors", "pl_debug_score_prune_gate",
-    "pl_debug_score_bounded", "pl_debug_lm_route",
+    "pl_debug_score_bounded", "pl_debug_score_bounded_columns", "pl_debug_lm_route",
     "pl_estimate_absolute_pose_dev", "pl_estimate_relative_pose_dev", "pl_estimate_fundamental_dev", "pl_estimate_homography_dev",
     "pl_problem_create_dev", "pl_problem_create_tangent_dev", "pl_debug_check_device_points", "pl_debug_point_stats_dev",
     "pl_debug_sampler_shape", "pl_debug_sample_positions", "pl_estimate_batch_dev", "pl_debug_point_stats_group_dev",

@@ -987,12 +987,13 @@ def score_survivors(members, route=0):
     return out, idle.value, guard.value
 
 
-def score_bounded(members, route=0):
+def score_bounded(members, route=0, columns=False):
     """Diagnostic (pl_debug_score_bounded): the pruned scorer as a group's batch step runs it, bound tier included, on caller-given
     lists.  members and routes as score_pruned.  Returns ([score_pruned's fields and "bound_counts", "bound_scores", "tiers" per
-    member], words changed in the inactive slot, words changed behind the live lists' ends - both must be 0)."""
+    member], words changed in the inactive slot, words changed behind the live lists' ends - both must be 0).  columns
+    (pl_debug_score_bounded_columns): also "columns", the (chunks, n) words of the count columns as the launches left them."""
     arr = (L.DebugPruneMember * max(len(members), 1))()
-    bcs, bss, trs = ((C.c_void_p * max(len(members), 1))() for _ in range(3))
+    bcs, bss, trs, cls = ((C.c_void_p * max(len(members), 1))() for _ in range(4))
     keep = []
     cap = 4096
     for i, (problem, models, max_error, init_max, init_min) in enumerate(members):
@@ -1008,16 +1009,27 @@ def score_bounded(members, route=0):
         arr[i] = L.DebugPruneMember(problem._h, _ptr(flat), n, float(max_error), float(init_min), int(init_max), cap, _ptr(cnt),
                                     _ptr(sc), _ptr(kp), _ptr(cand))
         bcs[i], bss[i], trs[i] = bc.ctypes.data, bs.ctypes.data, tr.ctypes.data
+        if columns:
+            cl = np.zeros((score_shape(problem.kind, problem.n, True, route == 2)[0], max(n, 1)), dtype=np.uint32)
+            keep[-1] += (cl,)
+            cls[i] = cl.ctypes.data
     idle, guard = C.c_uint32(0), C.c_uint32(0)
-    L.check(L.lib().pl_debug_score_bounded(int(route), arr, C.c_size_t(len(members)), bcs, bss, trs, C.byref(idle), C.byref(guard)))
+    if columns:
+        L.check(L.lib().pl_debug_score_bounded_columns(int(route), arr, C.c_size_t(len(members)), bcs, bss, trs, cls, C.byref(idle),
+                                                       C.byref(guard)))
+    else:
+        L.check(L.lib().pl_debug_score_bounded(int(route), arr, C.c_size_t(len(members)), bcs, bss, trs, C.byref(idle), C.byref(guard)))
     out = []
-    for i, (n, _, cnt, sc, kp, cand, bc, bs, tr) in enumerate(keep):
+    for i, (n, _, cnt, sc, kp, cand, bc, bs, tr, *cl) in enumerate(keep):
         a = arr[i]
         out.append({"counts": cnt[:n], "scores": sc[:n], "kept": kp[:n].astype(bool), "cand": cand[:min(a.num_cand, cap)].copy(),
                     "num_cand": a.num_cand, "cstar": a.cstar, "chunks": a.chunks, "chunk_points": a.chunk_points, "lead": a.lead,
                     "lead_max": a.lead_max, "lead_min": a.lead_min, "num_live": a.num_live, "num_selected": a.num_selected,
                     "num_preselected": a.num_preselected, "slices": a.slices, "bound_counts": bc[:n], "bound_scores": bs[:n],
                     "tiers": tr[:n]})
+        if cl:
+            assert a.chunks == cl[0].shape[0], (a.chunks, cl[0].shape)
+            out[-1]["columns"] = cl[0][:, :n]
     return out, idle.value, guard.value
 
 

@@ -2892,11 +2892,13 @@ int debug_score_group(pl_debug_score_member *m, size_t count, uint32_t *idle_cha
 // survivors (pl_debug_score_survivors): the count launch alone, over the whole list and every chunk; survivors[i] takes member i's
 // [chunks][n] counts (hypothesis order, a NaN model reports 0), *guard_changed the words behind the live list's end that changed.
 // bounded (pl_debug_score_bounded): the production sequence, bound tier included (PruneArgs.bound), no labels; per hypothesis the
-// tier's bounds (no bound: 0xffffffff / NaN) and what became of it.
+// tier's bounds (no bound: 0xffffffff / NaN) and what became of it; columns (pl_debug_score_bounded_columns): the words of the count
+// columns as the sequence left them.
 struct DebugBoundedOut {
     uint32_t *const *bound_counts;
     double *const *bound_scores;
     uint8_t *const *tiers;
+    uint32_t *const *columns = nullptr; // optional: [chunks][n] per member
 };
 int debug_score_pruned(int route, pl_debug_prune_member *m, size_t count, uint32_t *idle_changed, uint32_t *const *survivors = nullptr,
                        uint32_t *guard_changed = nullptr, const DebugBoundedOut *bounded = nullptr) {
@@ -3107,6 +3109,8 @@ int debug_score_pruned(int route, pl_debug_prune_member *m, size_t count, uint32
                 bounded->bound_counts[i][k] = has ? bcount[i][p] : 0xffffffffu;
                 bounded->bound_scores[i][k] = has ? bscore[i][p] : std::numeric_limits<double>::quiet_NaN();
                 bounded->tiers[i][k] = !live ? 3 : kept[i][p] == kKept ? 0 : has ? 2 : 1;
+                for (uint32_t ch = 0; bounded->columns && ch < chunks; ++ch)
+                    bounded->columns[i][(size_t)ch * H + k] = live ? part[i][(size_t)ch * hcap + p] : 0u;
             }
         }
         const bool split = st[i].cstar < chunks; // (otherwise nothing was dropped or pruned)
@@ -3164,6 +3168,21 @@ int pl_debug_score_bounded(int route, pl_debug_prune_member *members, size_t num
         if (!bound_counts[i] || !bound_scores[i] || !tiers[i])
             return fail(PL_ERR_INVALID, "pl_debug_score_bounded: a member without an output array");
     const DebugBoundedOut out{bound_counts, bound_scores, tiers};
+    return debug_score_pruned(route, members, num_members, idle_changed, nullptr, guard_changed, &out);
+}
+int pl_debug_score_bounded_columns(int route, pl_debug_prune_member *members, size_t num_members, uint32_t *const *bound_counts,
+                                   double *const *bound_scores, uint8_t *const *tiers, uint32_t *const *columns, uint32_t *idle_changed,
+                                   uint32_t *guard_changed) {
+    if (idle_changed)
+        *idle_changed = 0;
+    if (guard_changed)
+        *guard_changed = 0;
+    if (!bound_counts || !bound_scores || !tiers || !columns)
+        return fail(PL_ERR_INVALID, "pl_debug_score_bounded_columns: output arrays missing");
+    for (size_t i = 0; i < num_members; ++i)
+        if (!bound_counts[i] || !bound_scores[i] || !tiers[i] || !columns[i])
+            return fail(PL_ERR_INVALID, "pl_debug_score_bounded_columns: a member without an output array");
+    const DebugBoundedOut out{bound_counts, bound_scores, tiers, columns};
     return debug_score_pruned(route, members, num_members, idle_changed, nullptr, guard_changed, &out);
 }
 int pl_debug_score_prune_gate(int kind, uint32_t n_points, uint32_t iterations) {

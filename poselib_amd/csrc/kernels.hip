@@ -1410,8 +1410,8 @@ __device__ __forceinline__ uint32_t abs16_tile_count_t(const half8_t (&Aop)[kAbs
 // MODE (pruned scoring, PruneArgs in pl_kernels.h): kScoreAll - the stream is the whole list (the plain launch); kScoreLead - its
 // first `lead` positions; kScoreSel - the stream is the selection `sel` (*num_hyp_ptr = its length): entry i stands for the live
 // position sel[i], one level of indirection for the operand row, the record slot and the partial column (sel == nullptr: the
-// identity); kScoreCount, kScoreCountAll - no modes of this body: score_count_body below.
-constexpr int kScoreAll = 0, kScoreLead = 1, kScoreSel = 2, kScoreCount = 3, kScoreCountAll = 4;
+// identity); kScoreCount, kScoreCountAll, kScoreCountSel - no modes of this body: score_count_body below.
+constexpr int kScoreAll = 0, kScoreLead = 1, kScoreSel = 2, kScoreCount = 3, kScoreCountAll = 4, kScoreCountSel = 5;
 template <int PG, int MODE = kScoreAll>
 __device__ __forceinline__ void score_mfma_body(const PointSet &pts, const uint4 *__restrict__ shadow16,
                                                 const uint4 *__restrict__ points16,
@@ -1606,11 +1606,15 @@ __device__ __forceinline__ void score_mfma_body(const PointSet &pts, const uint4
 // - a wave-uniform branch - take `pad` off the total, and zero stays zero; the full chunks carry neither mask nor branch
 // body.  survivors[chunk][position], one word per hypothesis; positions in front of `first` are not scored.  Columns of a
 // partial group that stand for no hypothesis repeat the list's last operand row and are not written.  LDS: the B operands alone.
-template <int PG>
+// SEL (kScoreCountSel): the stream is the selection `sel` behind its first `first` entries, *num_hyp_ptr = its length - entry e
+// stands for the live position sel[e], one level of indirection for the operand row and the destination column, as kScoreSel's;
+// lane l of a group fetches its entry's position with the operands, so the word needs no permutation.  Same tile, same
+// operands: a word of this form equals the word the plain form writes for that position and chunk.
+template <int PG, bool SEL = false>
 __device__ __forceinline__ void score_count_body(uint32_t n_points, const uint4 *__restrict__ shadow16, const uint4 *__restrict__ points16,
                                                  const uint32_t *__restrict__ num_hyp_ptr, uint32_t hyp_capacity,
                                                  uint32_t *__restrict__ survivors, uint32_t slice, uint32_t chunk, uint32_t nslices,
-                                                 uint32_t first) {
+                                                 uint32_t first, const uint32_t *__restrict__ sel = nullptr) {
     constexpr int kWaves = kMfmaThreads / 64;
     constexpr int NPW = 32 * PG; // correspondences per chunk
     __shared__ uint4 s_b[1 + kAbs16Dirs][PG][32];
@@ -1652,8 +1656,11 @@ __device__ __forceinline__ void score_count_body(uint32_t n_points, const uint4 
     while (unit_of_ticket<32u>(ticket, H, waves_per_chunk, kb, gn)) {
         const uint32_t pending = request_ticket(); // the next unit's index travels while this one is evaluated
         const uint32_t ngroups32 = (gn + 31u) / 32u;
+        uint32_t next_pos = 0; // SEL: the live position of the column whose operands load_a fetched last
         auto load_a = [&](uint32_t hg, uint4 (&A)[kAbs16Dirs]) {
             const uint4 *row = shadow16 + (size_t)min(first + kb + 32u * hg + (uint32_t)col, Hall - 1u) * 4;
+            if constexpr (SEL)
+                row = shadow16 + (size_t)(next_pos = sel[min(first + kb + 32u * hg + (uint32_t)col, Hall - 1u)]) * 4;
 #pragma unroll
             for (int d = 0; d < kAbs16Dirs; ++d)
                 A[d] = row[half ? 3 : d];
@@ -1665,6 +1672,7 @@ __device__ __forceinline__ void score_count_body(uint32_t n_points, const uint4 
 #pragma unroll
             for (int d = 0; d < kAbs16Dirs; ++d)
                 __builtin_memcpy(&Aop[d], &Araw[d], 16);
+            [[maybe_unused]] const uint32_t pos = next_pos; // (this group's, before the next group's travels)
             if (hg + 1 < ngroups32) // next group's operands travel while this one is evaluated
                 load_a(hg + 1, Araw);
             // this lane's half of the hypothesis' count
@@ -1674,7 +1682,10 @@ __device__ __forceinline__ void score_count_body(uint32_t n_points, const uint4 
             uint32_t total = both[0] + both[1];
             if (pad) // (see above: every row behind the chunk's end was counted as a survivor, or none was)
                 total = max(total, pad) - pad;
-            if (half == 0 && 32u * hg + (uint32_t)col < gn)
+            if constexpr (SEL) {
+                if (half == 0 && 32u * hg + (uint32_t)col < gn)
+                    survivors[(size_t)chunk * hyp_capacity + pos] = total;
+            } else if (half == 0 && 32u * hg + (uint32_t)col < gn)
                 survivors[(size_t)chunk * hyp_capacity + first + kb + 32u * hg + (uint32_t)col] = total;
         }
         ticket = (uint32_t)__builtin_amdgcn_readfirstlane((int)pending);
@@ -1711,7 +1722,10 @@ __global__ __launch_bounds__(kMfmaThreads) __attribute__((amdgpu_waves_per_eu(4,
 // The scorer launches of a pruned step (a.prune.st set; launch_score_pruned, launch_group_score), on grids of (slice, chunk)
 // workgroups.  kScoreLead: the first positions of the list against every chunk - k_prune_lead turns them into the split chunk c*;
 // kScoreCount: the positions behind the lead against the chunks [0, c*), survivor counts only (score_count_body) - workgroups of the
-// chunks from c* on return at once, and all of them when c* = chunks: nothing can be dropped then; kScoreSel: the pre-selection of
+// chunks from c* on return at once, and all of them when c* = chunks: nothing can be dropped then; kScoreCountSel (a step with the
+// bound tier alone): the pre-selection behind the lead against the chunks [c*, chunks), survivor counts again - the words the count
+// launch did not compute, into the same columns, so stage S of k_score_bound holds a selected position's survivors over all N;
+// workgroups of the chunks in front of c* return at once, and all of them when c* = chunks; kScoreSel: the pre-selection of
 // k_prune_list against EVERY chunk, the exact scorer.  c* sits in device memory, the grid is the host's: no synchronisation between
 // them.  A member of a group's table whose step does not prune (prune.st == nullptr) is scored by the kScoreSel launch alone: its
 // whole list, every chunk.
@@ -1722,10 +1736,11 @@ __global__ __launch_bounds__(kMfmaThreads) __attribute__((amdgpu_waves_per_eu(4,
 // exclude: a quarter of the slices (profiles/score_prune.md, profiles/score_count.md).  Which wavefront scores a unit has no
 // influence on its result.
 template <int MODE> __host__ __device__ constexpr uint32_t pruned_slices(uint32_t slices) {
-    return MODE == kScoreLead ? (slices < 2u ? slices : 2u) : MODE == kScoreSel ? (slices + 3u) / 4u : slices;
+    return MODE == kScoreLead ? (slices < 2u ? slices : 2u) : (MODE == kScoreSel || MODE == kScoreCountSel) ? (slices + 3u) / 4u : slices;
 }
 template <int PG, int MODE> __device__ __forceinline__ void score_mfma_pruned(const ScoreArgs &a, uint32_t slice, uint32_t chunk, uint32_t nslices) {
-    static_assert(MODE == kScoreLead || MODE == kScoreSel || MODE == kScoreCount || MODE == kScoreCountAll, "the plain launch is k_score_mfma's");
+    static_assert(MODE == kScoreLead || MODE == kScoreSel || MODE == kScoreCount || MODE == kScoreCountAll || MODE == kScoreCountSel,
+                  "the plain launch is k_score_mfma's");
     const PruneArgs &pr = a.prune;
     if (!pr.st && MODE != kScoreSel)
         return;
@@ -1738,6 +1753,14 @@ template <int PG, int MODE> __device__ __forceinline__ void score_mfma_pruned(co
             return;
         score_count_body<PG>(a.pts.n, static_cast<const uint4 *>(a.shadow16), static_cast<const uint4 *>(a.points16), a.num_hyp,
                              a.hyp_capacity, a.part_count, slice, chunk, nslices, pr.lead);
+    } else if constexpr (MODE == kScoreCountSel) {
+        if (!pr.bound)
+            return;
+        const uint32_t cstar = *as_uniform(&pr.st->cstar);
+        if (cstar >= pr.chunks || chunk < cstar)
+            return;
+        score_count_body<PG, true>(a.pts.n, static_cast<const uint4 *>(a.shadow16), static_cast<const uint4 *>(a.points16), &pr.st->sel_len,
+                                   a.hyp_capacity, a.part_count, slice, chunk, nslices, min(*as_uniform(a.num_hyp), pr.lead), pr.sel);
     } else {
         // (kScoreSel without a selection: the identity, the whole live list)
         const uint32_t *len = MODE == kScoreSel && pr.st ? &pr.st->sel_len : a.num_hyp;
@@ -1932,7 +1955,7 @@ __global__ __launch_bounds__(1024) void k_prune_list_g(const GroupArgs *ga) {
 // Behind the pre-selection the list holds the lead - its first min(H, lead) entries, the list ascends - and the positions the
 // survivor counts could not exclude: mostly hypotheses of three inlier samples, a thousand inliers each, nearly all of which lose
 // against the lead's best and would go through the fp64 exact pass pair by pair only to be told so.  k_score_bound: a dense fp32
-// pass over list entries, no matrix instructions, no queue, no fp64, and ONE launch for both stages of the tier.  A workgroup of 8
+// pass over list entries, no matrix instructions, no queue, no fp64, and ONE launch for the three stages of the tier.  A workgroup of 8
 // wavefronts owns a unit of 64 list entries behind the lead (units go to the member's kBoundGroups workgroups with a fixed stride,
 // no atomics; a workgroup without a unit returns before it touches a correspondence).  Wavefront w owns chunk w of 64 P
 // correspondences and keeps them in registers (fp32 copies and the per-point slack, as k_score_queue); a member with more than 8
@@ -1940,17 +1963,26 @@ __global__ __launch_bounds__(1024) void k_prune_list_g(const GroupArgs *ga) {
 // fetches entry l's fp32 shadow from its record, the wavefront then walks models through v_readlane.  Per entry a wavefront leaves
 // an upper bound of the inliers of its chunks and a lower bound of their share of the score - an INTEGER number of quanta of
 // thr^2 2^-20, at most 320 * 2^20 per chunk - in LDS; behind a barrier wavefront 0 adds the 8 partials of every entry (integer sums:
-// the order and the chunking do not matter) and applies the rule below.  Two stages per unit:
-//   0, every entry of the unit: pf_abs_outlier's verdict alone, two points per packed fp32 instruction as in k_score_queue - a
+// the order and the chunking do not matter) and applies the rule below.  Three stages per unit:
+//   S, every entry of the unit, wavefront 0 alone (lane l = entry l): the matrix-core filter's SURVIVOR count over all N
+//     correspondences.  The entry's count column holds one survivor word per chunk - [0, c*) from the count launch, [c*, chunks)
+//     from the kScoreCountSel launch in front of this one - and nothing overwrites them before the exact launch.  The filter drops
+//     proven outliers only, so c = their sum is an upper bound of the inliers and every other pair shares thr^2 exactly: the rule
+//     on c and (N - c) 2^20 quanta, which is prune_rule at S = N with 0 for the sum (the argument stands above prune_keeps).  About
+//     12 vector instructions and one MFMA per (entry, chunk) against stage 0's 90; it drops some 60 % of the entries on the
+//     flagship.  The counts are looser than stage 0's (30 - 50 pairs), so it is a first cut and replaces nothing.  What it leaves
+//     is compacted inside the workgroup, ascending (s_liv); a unit it empties fetches no shadow, loads no correspondence and runs
+//     neither of the other stages - a workgroup-uniform branch around them, the barriers stay uniform.
+//   0, what stage S left: pf_abs_outlier's verdict alone, two points per packed fp32 instruction as in k_score_queue - a
 //     proven outlier's share is thr^2 exactly (2^20 quanta), every other pair may be an inlier and shares 0.  Ballots and scalar
 //     popcounts: no division, no per-lane value, no lane reduction.
-//   1, what stage 0 left undecided, compacted within the workgroup (about a sixth): pf_abs_r2_lower gives L <= r^2 per pair;
+//   1, what stage 0 left undecided of those, compacted within the workgroup (s_und): pf_abs_r2_lower gives L <= r^2 per pair;
 //     pairs with L < thr^2 are counted, min(L, thr^2) / thr^2 in truncated quanta is summed over the lanes.
-// The rule of both stages: with c_ub the sum of the counts and s_lb = thr^2 2^-20 sum q rounded DOWN, c <= c_ub and s >= s_lb hold
+// The rule of all stages (decide): with c_ub the sum of the counts and s_lb = thr^2 2^-20 sum q rounded DOWN, c <= c_ub and s >= s_lb hold
 // for the exact count and score, so an entry with c_ub <= lead_max and s_lb > lead_min (1 + kPruneScoreMargin) is no candidate of
 // k_records (prune_rule's argument): kept[] = kDropped.  bnd_count / bnd_score (where set) hold the values of the last stage that
-// saw the entry.  Nothing goes to the partial columns: they keep survivor counts or an earlier step's values until the exact launch
-// overwrites the columns of what stays.  An entry's decision is complete inside one workgroup; k_prune_bound, the next launch,
+// saw the entry.  This kernel writes nothing to the partial columns: they keep survivor counts or an earlier step's values until the
+// exact launch overwrites the columns of what stays.  An entry's decision is complete inside one workgroup; k_prune_bound, the next launch,
 // rebuilds the list.  Grids from the host, lengths from device memory: no synchronisation.
 // Eight wavefronts, not sixteen: a workgroup of 1024 threads at this kernel's 119 VGPRs needs every SIMD of a compute unit nearly
 // empty at once, and next to the other groups' count launches (two workgroups of 8 wavefronts and 128 VGPRs per compute unit) the
@@ -1966,8 +1998,9 @@ template <int P> __device__ __forceinline__ void score_bound_body(const ScoreArg
     constexpr uint32_t NPW = 64u * P;
     __shared__ uint32_t s_c[kWaves][64];
     __shared__ uint64_t s_q[kWaves][64];
-    __shared__ uint32_t s_und[64]; // the unit's entries that stage 0 left undecided, ascending
-    __shared__ uint32_t s_nund;
+    __shared__ uint32_t s_liv[64]; // the unit's entries that stage S left undecided, ascending
+    __shared__ uint32_t s_und[64]; // those of them that stage 0 left undecided, ascending
+    __shared__ uint32_t s_nliv, s_nund;
     const PruneArgs &pr = a.prune;
     if (!pr.st || !pr.bound || *as_uniform(&pr.st->cstar) >= pr.chunks)
         return;
@@ -1995,18 +2028,11 @@ template <int P> __device__ __forceinline__ void score_bound_body(const ScoreArg
             fw[p] = pf_point_abs(Xd, Yd, Zd, pf.gx);
         }
     };
-    load_chunk(min((uint32_t)wave, chunks - 1u)); // (a wavefront without a chunk holds a copy it never evaluates)
+    bool loaded = false; // resident: the wavefront's chunk is in its registers (from the first unit that stage S does not empty)
     const uint32_t lead_max = pr.st->lead_max;
     const double beat = pr.st->lead_min * (1.0 + kPruneScoreMargin);
-    // wavefront 0, lane l: the sums of entry l over the wavefronts' partials and the rule; true: the entry stays
-    auto decide = [&](uint32_t pos) -> bool {
-        uint32_t c = 0;
-        uint64_t q = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) {
-            c += s_c[w][lane];
-            q += s_q[w][lane];
-        }
+    // wavefront 0, lane l: the rule on entry l's bounds - c inliers at most, q quanta of score at least; true: the entry stays
+    auto decide = [&](uint32_t pos, uint32_t c, uint64_t q) -> bool {
         const double qd = (double)q * 9.5367431640625e-07; // (2^-20: exact)
         double s_lb = a.thr2 * qd;
         if (fma(a.thr2, qd, -s_lb) < 0.0) // the product was rounded up (then it is positive): its predecessor
@@ -2018,109 +2044,142 @@ template <int P> __device__ __forceinline__ void score_bound_body(const ScoreArg
             pr.bnd_count[pos] = c, pr.bnd_score[pos] = s_lb;
         return keep;
     };
+    // the same on the sums of entry l over the wavefronts' partials (stages 0 and 1)
+    auto decide_partials = [&](uint32_t pos) -> bool {
+        uint32_t c = 0;
+        uint64_t q = 0;
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w) {
+            c += s_c[w][lane];
+            q += s_q[w][lane];
+        }
+        return decide(pos, c, q);
+    };
     const uint32_t nent = len - first;
     for (uint32_t u = wg; (uint64_t)u * 64u < nent; u += nwg) { // (workgroup-uniform: the barriers below are reached by all)
         const uint32_t e = first + u * 64u + (uint32_t)lane;
         const uint32_t pos = pr.sel[min(e, len - 1u)];
-        const float4 *sh = reinterpret_cast<const float4 *>(a.models + (size_t)a.slots[pos] * kModelStride + kShadowOff);
-        float4 rv[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            rv[k] = sh[k];
         const uint32_t n = min(64u, nent - u * 64u);
-        auto model_of_lane = [&](uint32_t j, float (&r)[16]) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                r[4 * k + 0] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rv[k].x), (int)j));
-                r[4 * k + 1] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rv[k].y), (int)j));
-                r[4 * k + 2] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rv[k].z), (int)j));
-                r[4 * k + 3] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rv[k].w), (int)j));
-            }
-        };
-        // ---- stage 0: the verdict of every entry against the wavefront's chunks ----
-        uint32_t my_c = 0;
-        uint64_t my_q = 0;
-        for (uint32_t ch = (uint32_t)wave; ch < chunks; ch += (uint32_t)kWaves) {
-            if (!resident)
-                load_chunk(ch);
-            for (uint32_t j = 0; j < n; ++j) {
-                float r[16];
-                model_of_lane(j, r);
-                const float gt = pf_abs_bound_slack(r, pf.gx);
-                uint32_t c = 0, q = 0;
-#pragma unroll
-                for (int p = 0; p + 1 < P; p += 2) {
-                    const v2f Xp = {X[p], X[p + 1]}, Yp = {Y[p], Y[p + 1]}, Zp = {Z[p], Z[p + 1]};
-                    const v2f xp = {x[p], x[p + 1]}, yp = {y[p], y[p + 1]}, w = {fw[p], fw[p + 1]};
-                    const v2f z0 = pk_fma(bc(r[0]), Xp, pk_fma(bc(r[1]), Yp, pk_fma(bc(r[2]), Zp, bc(r[9]))));
-                    const v2f z1 = pk_fma(bc(r[3]), Xp, pk_fma(bc(r[4]), Yp, pk_fma(bc(r[5]), Zp, bc(r[10]))));
-                    const v2f z2 = pk_fma(bc(r[6]), Xp, pk_fma(bc(r[7]), Yp, pk_fma(bc(r[8]), Zp, bc(r[11]))));
-                    const v2f a0 = pk_fma(-xp, z2, z0);
-                    const v2f a1 = pk_fma(-yp, z2, z1);
-                    const v2f W = w + bc(gt);
-                    const v2f B = pk_fma(bc(pf.thr), z2, W);
-#pragma unroll
-                    for (int e2 = 0; e2 < 2; ++e2) {
-                        const uint64_t out = vmask[p + e2] & (__builtin_amdgcn_ballot_w64(fmaxf(fabsf(a0[e2]), fabsf(a1[e2])) > B[e2]) |
-                                                              __builtin_amdgcn_ballot_w64(z2[e2] < -W[e2]));
-                        q += (uint32_t)__popcll(out);
-                        c += (uint32_t)__popcll(vmask[p + e2] & ~out);
-                    }
-                }
-                if constexpr (P & 1) {
-                    constexpr int p = P - 1;
-                    const uint64_t out = vmask[p] & __builtin_amdgcn_ballot_w64(pf_abs_outlier(r, gt, pf.thr, x[p], y[p], X[p], Y[p], Z[p], fw[p]));
-                    q += (uint32_t)__popcll(out);
-                    c += (uint32_t)__popcll(vmask[p] & ~out);
-                }
-                if ((uint32_t)lane == j)
-                    my_c += c, my_q += q; // (proven outliers: kPfBoundScale quanta each, below)
-            }
-        }
-        s_c[wave][lane] = my_c;
-        s_q[wave][lane] = my_q << 20;
-        __syncthreads();
-        bool open = false; // wavefront 0, lane l: entry l is undecided
+        // ---- stage S: the survivor words of the entry's column, every chunk (count launches: [0, c*) and [c*, chunks)) ----
+        bool live = false; // wavefront 0, lane l: entry l is undecided
         if (wave == 0) {
-            open = (uint32_t)lane < n && decide(pos);
-            const uint64_t und = __builtin_amdgcn_ballot_w64(open);
-            if (open)
-                s_und[__builtin_amdgcn_mbcnt_hi((uint32_t)(und >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)und, 0u))] = (uint32_t)lane;
+            if ((uint32_t)lane < n) {
+                uint32_t c = 0;
+                for (uint32_t ch = 0; ch < chunks; ++ch)
+                    c += a.part_count[(size_t)ch * a.hyp_capacity + pos];
+                c = min(c, a.pts.n); // (a chunk's word counts rows of the chunk: the sum is no more)
+                live = decide(pos, c, (uint64_t)(a.pts.n - c) << 20);
+            }
+            const uint64_t liv = __builtin_amdgcn_ballot_w64(live);
+            if (live)
+                s_liv[__builtin_amdgcn_mbcnt_hi((uint32_t)(liv >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)liv, 0u))] = (uint32_t)lane;
             if (lane == 0)
-                s_nund = (uint32_t)__popcll(und);
+                s_nliv = (uint32_t)__popcll(liv);
         }
-        __syncthreads(); // (also: the partials of stage 0 are read)
-        // ---- stage 1: residual bounds of the undecided entries, the correspondences still in registers ----
-        const uint32_t nund = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_nund);
-        if (nund) { // workgroup-uniform
-            my_c = 0, my_q = 0;
+        __syncthreads();
+        const uint32_t nliv = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_nliv);
+        if (nliv) { // workgroup-uniform: a unit that stage S emptied loads no correspondence and runs no stage
+            const float4 *sh = reinterpret_cast<const float4 *>(a.models + (size_t)a.slots[pos] * kModelStride + kShadowOff);
+            float4 rv[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                rv[k] = sh[k];
+            auto model_of_lane = [&](uint32_t j, float (&r)[16]) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    r[4 * k + 0] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rv[k].x), (int)j));
+                    r[4 * k + 1] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rv[k].y), (int)j));
+                    r[4 * k + 2] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rv[k].z), (int)j));
+                    r[4 * k + 3] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rv[k].w), (int)j));
+                }
+            };
+            // ---- stage 0: the verdict of every entry stage S left against the wavefront's chunks ----
+            uint32_t my_c = 0;
+            uint64_t my_q = 0;
             for (uint32_t ch = (uint32_t)wave; ch < chunks; ch += (uint32_t)kWaves) {
-                if (!resident)
+                if (!resident || !loaded)
                     load_chunk(ch);
-                for (uint32_t k = 0; k < nund; ++k) {
-                    const uint32_t j = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_und[k]);
+                for (uint32_t k = 0; k < nliv; ++k) {
+                    const uint32_t j = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_liv[k]);
                     float r[16];
                     model_of_lane(j, r);
                     const float gt = pf_abs_bound_slack(r, pf.gx);
                     uint32_t c = 0, q = 0;
 #pragma unroll
-                    for (int p = 0; p < P; ++p) {
-                        const float L = pf_abs_r2_lower(r, gt, x[p], y[p], X[p], Y[p], Z[p], fw[p]);
-                        c += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(valid[p] && L < pf.thr2_up));
-                        q += valid[p] ? pf_bound_quantum(L, pf.inv_thr2_dn) : 0u;
+                    for (int p = 0; p + 1 < P; p += 2) {
+                        const v2f Xp = {X[p], X[p + 1]}, Yp = {Y[p], Y[p + 1]}, Zp = {Z[p], Z[p + 1]};
+                        const v2f xp = {x[p], x[p + 1]}, yp = {y[p], y[p + 1]}, w = {fw[p], fw[p + 1]};
+                        const v2f z0 = pk_fma(bc(r[0]), Xp, pk_fma(bc(r[1]), Yp, pk_fma(bc(r[2]), Zp, bc(r[9]))));
+                        const v2f z1 = pk_fma(bc(r[3]), Xp, pk_fma(bc(r[4]), Yp, pk_fma(bc(r[5]), Zp, bc(r[10]))));
+                        const v2f z2 = pk_fma(bc(r[6]), Xp, pk_fma(bc(r[7]), Yp, pk_fma(bc(r[8]), Zp, bc(r[11]))));
+                        const v2f a0 = pk_fma(-xp, z2, z0);
+                        const v2f a1 = pk_fma(-yp, z2, z1);
+                        const v2f W = w + bc(gt);
+                        const v2f B = pk_fma(bc(pf.thr), z2, W);
+#pragma unroll
+                        for (int e2 = 0; e2 < 2; ++e2) {
+                            const uint64_t out = vmask[p + e2] & (__builtin_amdgcn_ballot_w64(fmaxf(fabsf(a0[e2]), fabsf(a1[e2])) > B[e2]) |
+                                                                  __builtin_amdgcn_ballot_w64(z2[e2] < -W[e2]));
+                            q += (uint32_t)__popcll(out);
+                            c += (uint32_t)__popcll(vmask[p + e2] & ~out);
+                        }
                     }
-                    q = (uint32_t)__builtin_amdgcn_readlane((int)wave_scan_u32(q), 63);
+                    if constexpr (P & 1) {
+                        constexpr int p = P - 1;
+                        const uint64_t out = vmask[p] & __builtin_amdgcn_ballot_w64(pf_abs_outlier(r, gt, pf.thr, x[p], y[p], X[p], Y[p], Z[p], fw[p]));
+                        q += (uint32_t)__popcll(out);
+                        c += (uint32_t)__popcll(vmask[p] & ~out);
+                    }
                     if ((uint32_t)lane == j)
-                        my_c += c, my_q += q;
+                        my_c += c, my_q += q; // (proven outliers: kPfBoundScale quanta each, below)
                 }
             }
+            loaded = true;
             s_c[wave][lane] = my_c;
-            s_q[wave][lane] = my_q;
+            s_q[wave][lane] = my_q << 20;
             __syncthreads();
-            if (open)
-                (void)decide(pos);
+            bool open = false; // wavefront 0, lane l: entry l is undecided
+            if (wave == 0) {
+                open = live && decide_partials(pos);
+                const uint64_t und = __builtin_amdgcn_ballot_w64(open);
+                if (open)
+                    s_und[__builtin_amdgcn_mbcnt_hi((uint32_t)(und >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)und, 0u))] = (uint32_t)lane;
+                if (lane == 0)
+                    s_nund = (uint32_t)__popcll(und);
+            }
+            __syncthreads(); // (also: the partials of stage 0 are read)
+            // ---- stage 1: residual bounds of the undecided entries, the correspondences still in registers ----
+            const uint32_t nund = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_nund);
+            if (nund) { // workgroup-uniform
+                my_c = 0, my_q = 0;
+                for (uint32_t ch = (uint32_t)wave; ch < chunks; ch += (uint32_t)kWaves) {
+                    if (!resident)
+                        load_chunk(ch);
+                    for (uint32_t k = 0; k < nund; ++k) {
+                        const uint32_t j = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_und[k]);
+                        float r[16];
+                        model_of_lane(j, r);
+                        const float gt = pf_abs_bound_slack(r, pf.gx);
+                        uint32_t c = 0, q = 0;
+#pragma unroll
+                        for (int p = 0; p < P; ++p) {
+                            const float L = pf_abs_r2_lower(r, gt, x[p], y[p], X[p], Y[p], Z[p], fw[p]);
+                            c += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(valid[p] && L < pf.thr2_up));
+                            q += valid[p] ? pf_bound_quantum(L, pf.inv_thr2_dn) : 0u;
+                        }
+                        q = (uint32_t)__builtin_amdgcn_readlane((int)wave_scan_u32(q), 63);
+                        if ((uint32_t)lane == j)
+                            my_c += c, my_q += q;
+                    }
+                }
+                s_c[wave][lane] = my_c;
+                s_q[wave][lane] = my_q;
+                __syncthreads();
+                if (open)
+                    (void)decide_partials(pos);
+            }
         }
-        __syncthreads(); // (the next unit writes the partials and the list of the undecided)
+        __syncthreads(); // (the next unit writes the partials and the lists of the undecided)
     }
 }
 template <int P> __global__ __launch_bounds__(kBoundThreads) void k_score_bound(ScoreArgs a) { score_bound_body<P>(a, blockIdx.x, gridDim.x); }
@@ -4515,6 +4574,7 @@ template <int PG> static hipError_t launch_score_pruned_pg(const ScoreArgs &a, d
     if (e != hipSuccess)
         return e;
     if (a.prune.bound) { // bounds of the pre-selected positions behind the lead, and the list without the lead and what they drop
+        k_score_mfma_pr<PG, kScoreCountSel><<<sel_grid, block, 0, stream>>>(a);
         k_score_bound<PG / 2><<<dim3(kBoundGroups), dim3(kBoundThreads), 0, stream>>>(a);
         k_prune_bound<<<dim3(1), dim3(1024), 0, stream>>>(a);
     }
@@ -4750,6 +4810,7 @@ template <int E> static hipError_t launch_group_score_est(const GroupArgs *args,
             if (e != hipSuccess)
                 return e;
             if (d.any_bound) { // (as launch_score_pruned_pg)
+                k_score_mfma_pr_g<10, kScoreCountSel><<<sel_grid, dim3(kMfmaThreads), 0, stream>>>(args);
                 k_score_bound_g<<<dim3(kBoundGroups, 1, d.G), dim3(kBoundThreads), 0, stream>>>(args);
                 k_prune_bound_g<<<dim3(1, 1, d.G), dim3(1024), 0, stream>>>(args);
             }

@@ -79,7 +79,7 @@ struct PruneArgs {
     uint32_t chunks = 0, chunk_points = 0; // the launch's chunks of correspondences and the correspondences of one
     uint32_t init_max = 0, lead = 0;   // what a candidate has to beat (RecordsArgs.init_max / init_min); lead length
     double init_min = 0.0;
-    // The bound tier (k_score_bound: two stages in one launch, k_prune_bound) between pre-selection and exact scores; 0: the two-tier sequence, the lead
+    // The bound tier (kScoreCountSel's survivor counts, k_score_bound: three stages in one launch, k_prune_bound) between pre-selection and exact scores; 0: the two-tier sequence, the lead
     // stays in the selection (pl_debug_score_pruned, pl_debug_score_survivors)
     uint32_t bound = 0, pad = 0;
     uint32_t *bnd_count = nullptr; // optional (pl_debug_score_bounded) [hyp_capacity]: per pre-selected position behind the lead
