@@ -28,6 +28,7 @@
 //   pl_atan2, pl_tan : e_atan2.c __ieee754_atan2 and s_tan.c __tan, FMA variants, for the fisheye camera models
 //             (misc/camera_models.cc:1049, 1190, ...); tables uatan.tbl / utan.tbl.  tests/test_libm_trig_vs_glibc.py checks
 //             both bit for bit against the host's libm (2e7 arguments each), tests/test_gpu_device_math2.py on the device.
+//   pl_log1p : s_log1p.c, for the Cauchy losses' cost (robust/robust_loss.h); no FMA variant, see below.
 #pragma once
 #include "pl_defs.h"
 
@@ -510,6 +511,87 @@ PL_HD double pl_cbrt(double x) {
     rb += (uint64_t)(int64_t)q << 52;
     __builtin_memcpy(&r, &rb, 8);
     return r;
+}
+
+// ---- log1p (s_log1p.c) -----------------------------------------------------------------------------------------------
+// The Cauchy losses' cost term (robust_loss.h: sq * log1p(r2 / sq)).  glibc's routine is fdlibm's: 1 + x = 2^k (1 + f) with
+// sqrt(2) / 2 < 1 + f < sqrt(2), the rounding error of 1 + x carried as c, log(1 + f) = f - f^2 / 2 + s (f^2 / 2 + R(s^2)) with
+// s = f / (2 + f) and a degree-14 polynomial R - in glibc evaluated in four independent pairs (R1 .. R4 below), which is what
+// makes its last bit differ from fdlibm's Horner form on one argument in 10^4.  Plain IEEE operations in a fixed order, no FMA
+// (glibc 2.35 has no FMA variant of s_log1p.c) => bit-identical to the host's log1p; tests/test_lm_cam_cases.py checks 2e7
+// arguments against the host libm.  ocml's log1p differs from it in the last bit often enough that a Nielsen update after a
+// mediocre step (pl_refine.h lm_cube) took another lambda than the reference: two of the 104 bundle adjustments of tests/lm_cam_cases.py under a Cauchy loss and the Nielsen update
+// ended in other last bits than the serial host model.
+PL_HD double pl_log1p(double x) {
+    constexpr double ln2_hi = 6.93147180369123816490e-01, ln2_lo = 1.90821492927058770002e-10, two54 = 1.80143985094819840000e+16;
+    constexpr double Lp1 = 6.666666666666735130e-01, Lp2 = 3.999999999940941908e-01, Lp3 = 2.857142874366239149e-01,
+                     Lp4 = 2.222219843214978396e-01, Lp5 = 1.818357216161805012e-01, Lp6 = 1.531383769920937332e-01,
+                     Lp7 = 1.479819860511658591e-01;
+    auto with_hi = [](double v, int32_t h) {
+        uint64_t b;
+        __builtin_memcpy(&b, &v, 8);
+        b = (b & 0xffffffffull) | ((uint64_t)(uint32_t)h << 32);
+        __builtin_memcpy(&v, &b, 8);
+        return v;
+    };
+    const int32_t hx = (int32_t)pl_hi(x), ax = hx & 0x7fffffff;
+    int32_t k = 1, hu = 0;
+    double f = 0.0, c = 0.0, u;
+    if (hx < 0x3FDA827A) { // x < 0.41422
+        if (ax >= 0x3ff00000)  // x <= -1: -inf at -1, NaN below
+            return (x == -1.0) ? -two54 / 0.0 : (x - x) / (x - x);
+        if (ax < 0x3e200000) // |x| < 2^-29
+            return (two54 + x > 0.0 && ax < 0x3c900000) ? x : x - x * x * 0.5;
+        if (hx > 0 || hx <= (int32_t)0xbfd2bec3) { // -0.2929 < x < 0.41422
+            k = 0;
+            f = x;
+            hu = 1;
+        }
+    }
+    if (hx >= 0x7ff00000)
+        return x + x;
+    if (k != 0) {
+        if (hx < 0x43400000) {
+            u = 1.0 + x;
+            hu = (int32_t)pl_hi(u);
+            k = (hu >> 20) - 1023;
+            c = (k > 0) ? 1.0 - (u - x) : x - (u - 1.0); // the correction term
+            c /= u;
+        } else {
+            u = x;
+            hu = (int32_t)pl_hi(u);
+            k = (hu >> 20) - 1023;
+            c = 0.0;
+        }
+        hu &= 0x000fffff;
+        if (hu < 0x6a09e) {
+            u = with_hi(u, hu | 0x3ff00000); // normalise u
+        } else {
+            k += 1;
+            u = with_hi(u, hu | 0x3fe00000); // normalise u / 2
+            hu = (0x00100000 - hu) >> 2;
+        }
+        f = u - 1.0;
+    }
+    const double hfsq = 0.5 * f * f;
+    if (hu == 0) { // |f| < 2^-20
+        if (f == 0.0) {
+            if (k == 0)
+                return 0.0;
+            c += k * ln2_lo;
+            return k * ln2_hi + c;
+        }
+        const double R = hfsq * (1.0 - 0.66666666666666666 * f);
+        return (k == 0) ? f - R : k * ln2_hi - ((R - (k * ln2_lo + c)) - f);
+    }
+    const double s = f / (2.0 + f);
+    const double z = s * s;
+    const double R1 = z * Lp1, z2 = z * z;
+    const double R2 = Lp2 + z * Lp3, z4 = z2 * z2;
+    const double R3 = Lp4 + z * Lp5, z6 = z4 * z2;
+    const double R4 = Lp6 + z * Lp7;
+    const double R = R1 + z2 * R2 + z4 * R3 + z6 * R4;
+    return (k == 0) ? f - (hfsq - s * (hfsq + R)) : k * ln2_hi - ((hfsq - (s * (hfsq + R) + (k * ln2_lo + c))) - f);
 }
 
 } // namespace pl

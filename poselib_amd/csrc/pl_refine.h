@@ -64,7 +64,7 @@ PL_HD Loss make_loss(int type, double scale) {
     l.thr = scale;
     l.sq = scale * scale;
     l.inv_sq = 1.0 / l.sq;
-    l.max_loss = l.sq * log1p(1.0);
+    l.max_loss = l.sq * pl_log1p(1.0);
     l.mu = 0.5;
     return l;
 }
@@ -78,9 +78,9 @@ PL_HD double loss_value(const Loss &l, double r2) {
         return (r <= l.thr) ? r2 : l.thr * (2.0 * r - l.thr);
     }
     case LOSS_CAUCHY:
-        return l.sq * log1p(r2 * l.inv_sq);
+        return l.sq * pl_log1p(r2 * l.inv_sq);
     case LOSS_TRUNCATED_CAUCHY:
-        return (r2 > l.sq) ? l.max_loss : l.sq * log1p(r2 * l.inv_sq);
+        return (r2 > l.sq) ? l.max_loss : l.sq * pl_log1p(r2 * l.inv_sq);
     default:
         return r2;
     }

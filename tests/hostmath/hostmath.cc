@@ -581,8 +581,15 @@ double hm_lm_cube_switched(double x, int device_cube) {
 }
 
 // Serial evaluation of k_lm_cam's algorithm (lm_cam.hip): the same rows, the same per-entry sums in correspondence order.
-void hm_lm_cam(const double *const *pa, uint32_t n, double *params, const LMOptions *opt, CameraParams *cam_io, int cam_flags,
-               double point_scale, const uint8_t *mask, uint32_t *iterations, double *costs /* initial, final */) {
+// Returns 1, with nothing touched, when the flags select no parameter of the model (M = 0: the driver sends such a bundle to k_lm,
+// and lm_solve_k has no K = 6), 0 otherwise.
+int hm_lm_cam(const double *const *pa, uint32_t n, double *params, const LMOptions *opt, CameraParams *cam_io, int cam_flags,
+              double point_scale, const uint8_t *mask, uint32_t *iterations, double *costs /* initial, final, invalid steps */) {
+    {
+        int none[kCamMaxParams];
+        if (camera_refinement_idx(cam_io->model_id, cam_flags, none) == 0)
+            return 1;
+    }
     LMControl ctl;
     ctl.opt = *opt;
     ctl.loss = make_loss(opt->loss_type, opt->loss_scale);
@@ -650,13 +657,25 @@ void hm_lm_cam(const double *const *pa, uint32_t n, double *params, const LMOpti
     *cam_io = cam_cur;
     *iterations = ctl.iterations;
     costs[0] = ctl.initial_cost, costs[1] = ctl.cost;
+    costs[2] = (double)ctl.invalid_steps;
+    return 0;
+}
+// hm_lm_cam with the Nielsen update's cube in the device's form when device_cube != 0 (as hm_lm_ex): the serial model of k_lm_cam,
+// bit for bit; hm_lm_cube_args holds the cube's arguments afterwards
+int hm_lm_cam_ex(const double *const *pa, uint32_t n, double *params, const LMOptions *opt, CameraParams *cam_io, int cam_flags,
+                 double point_scale, const uint8_t *mask, int device_cube, uint32_t *iterations, double *costs) {
+    lm_cube_host_switch().device_form = device_cube != 0;
+    lm_cube_host_switch().calls = 0;
+    const int r = hm_lm_cam(pa, n, params, opt, cam_io, cam_flags, point_scale, mask, iterations, costs);
+    lm_cube_host_switch().device_form = 0;
+    return r;
 }
 
 // The shared-focal refiner as k_sfocal_lm runs it (sfocal.hip): every sum correspondence after correspondence.  prefilter_thr2 > 0:
 // refine_model of the estimator (relative_pose.cc:173-203) - the correspondences with Sampson error below it, nothing when <= 6.
 // Returns 1 when the refinement was skipped.
 int hm_sfocal_lm(const double *const *pa, uint32_t n, double *pose7, double *focal, const LMOptions *opt, double prefilter_thr2,
-                 const uint8_t *mask_in, uint32_t *iterations, double *costs /* initial, final */) {
+                 const uint8_t *mask_in, uint32_t *iterations, double *costs /* initial, final, invalid steps */) {
     std::vector<uint8_t> keep(n, 1);
     if (prefilter_thr2 > 0) {
         FocalModel m;
@@ -730,7 +749,17 @@ int hm_sfocal_lm(const double *const *pa, uint32_t n, double *pose7, double *foc
     *focal = cur[kSFocalFocalSlot];
     *iterations = ctl.iterations;
     costs[0] = ctl.initial_cost, costs[1] = ctl.cost;
+    costs[2] = (double)ctl.invalid_steps;
     return 0;
+}
+// hm_sfocal_lm with the device's cube when device_cube != 0 (as hm_lm_ex): the serial model of k_sfocal_lm, bit for bit
+int hm_sfocal_lm_ex(const double *const *pa, uint32_t n, double *pose7, double *focal, const LMOptions *opt, double prefilter_thr2,
+                    const uint8_t *mask_in, int device_cube, uint32_t *iterations, double *costs) {
+    lm_cube_host_switch().device_form = device_cube != 0;
+    lm_cube_host_switch().calls = 0;
+    const int r = hm_sfocal_lm(pa, n, pose7, focal, opt, prefilter_thr2, mask_in, iterations, costs);
+    lm_cube_host_switch().device_form = 0;
+    return r;
 }
 
 void hm_factorized_F(const double *params, double *F) { factorized_F(params, F); }
@@ -898,6 +927,36 @@ uint64_t hm_sincos_mismatches(uint64_t count, uint64_t seed, double *first_bad) 
     return bad;
 }
 
+// pl_log1p against the host's log1p: the number of arguments on which they differ in any bit.  A quarter of the arguments each:
+// u 2^e with e = -30 .. 29 (what r2 / scale^2 of a Cauchy loss can be), -u (down to -1), any bit pattern (NaN, inf, subnormals,
+// arguments below -1), and the neighbourhoods of the routine's branch points (sqrt(2) - 1, sqrt(2) / 2 - 1, 2^-29, 2^-54, 2^53)
+uint64_t hm_log1p_mismatches(uint64_t count, uint64_t seed, double *first_bad) {
+    uint64_t s = seed * 0x9e3779b97f4a7c15ull + 0x2545f4914f6cdd1dull, bad = 0;
+    auto rnd = [&]() {
+        s ^= s << 13, s ^= s >> 7, s ^= s << 17;
+        return s;
+    };
+    const double edges[6] = {0.41421356237309503, -0.29289321881345248, 0x1p-29, 0x1p-54, 0x1p53, -1.0};
+    for (uint64_t i = 0; i < count; ++i) {
+        const double u = (double)(rnd() >> 11) / 9007199254740992.0;
+        const uint64_t r = rnd();
+        double x;
+        switch (i % 4) {
+        case 0: x = std::ldexp(u, (int)(r % 60) - 30); break;
+        case 1: x = -u; break;
+        case 2: std::memcpy(&x, &r, 8); break;
+        default: x = edges[r % 6] * (1.0 + (2 * u - 1) * std::ldexp(1.0, -(int)((r >> 8) % 53))); break;
+        }
+        const double got = pl_log1p(x), want = std::log1p(x);
+        if (std::memcmp(&got, &want, 8) != 0 && !(got != got && want != want)) {
+            if (bad == 0 && first_bad)
+                *first_bad = x;
+            ++bad;
+        }
+    }
+    return bad;
+}
+
 // which: 0 acos (GEN_ACOS), 1 cos (GEN_COS), 2 sin (GEN_SIN): arguments on which pl_libm.h and the host's libm differ in any bit
 uint64_t hm_libm_mismatches(int which, uint64_t count, uint64_t seed, double *first_bad) {
     ArgStream g(GEN_ACOS + which, 0, seed);
@@ -1007,7 +1066,7 @@ struct HostFocalBackend {
             std::memset(&cam, 0, sizeof(cam));
             cam.model_id = CAM_SIMPLE_PINHOLE, cam.num_params = 3, cam.p[0] = m.f;
             uint32_t its;
-            double costs[2];
+            double costs[3];
             hm_lm_cam(pa, n, params, &lo, &cam, CAM_REFINE_FOCAL, 1.0, nullptr, &its, costs);
             for (int i = 0; i < 4; ++i)
                 m.q[i] = params[i];
@@ -1125,7 +1184,7 @@ struct HostSFocalBackend {
         lo.initial_lambda = 1e-3, lo.min_lambda = 1e-10, lo.max_lambda = 1e10, lo.lambda_factor = 10.0;
         for (FocalModel &m : refined) {
             uint32_t its;
-            double costs[2];
+            double costs[3];
             hm_sfocal_lm(pa, n, m.q, &m.f, &lo, 5 * thr2, nullptr, &its, costs); // (q and t are adjacent: 7 doubles)
         }
         return 0;

@@ -203,6 +203,13 @@ def glibc(which, x):
     return (out[: x.size], out[x.size:]) if which == "sincos" else out
 
 
+def log1p_mismatches(count, seed=1):
+    """pl_libm.h pl_log1p (the Cauchy losses' cost on the device) against the host's log1p: (arguments that differ, the first)"""
+    first = C.c_double(0.0)
+    lib().hm_log1p_mismatches.restype = C.c_uint64
+    return int(lib().hm_log1p_mismatches(C.c_uint64(count), C.c_uint64(seed), C.byref(first))), first.value
+
+
 def lm_cube(x):
     """pl_refine.h lm_cube_fma, the device's form of the Nielsen update's cube"""
     x = np.ascontiguousarray(x, dtype=np.float64)
@@ -275,19 +282,34 @@ def fund_params(F):
     return p
 
 
-def lm_cam(cols, params, opt: LMOptions, cam: CameraParams, cam_flags, point_scale=1.0, mask=None):
-    """k_lm_cam's algorithm serially: (pose parameters, camera parameters, iterations, (initial cost, cost))"""
+_last_invalid_steps = 0
+
+
+def invalid_steps():
+    """the steps the last lm_cam() / sfocal_lm() run rejected"""
+    return _last_invalid_steps
+
+
+def lm_cam(cols, params, opt: LMOptions, cam: CameraParams, cam_flags, point_scale=1.0, mask=None, device_cube=False):
+    """k_lm_cam's algorithm serially: (pose parameters, camera parameters, iterations, (initial cost, cost)).  device_cube: the
+    Nielsen update's cube as the device forms it (as lm()) - then a model of k_lm_cam bit for bit.  Flags that select no parameter
+    of the model raise: such a bundle is the pose-only one (lm("abs", ..., cam))."""
+    global _last_invalid_steps
     arrs, ptrs = _soa(cols)
     n = arrs[0].shape[0]
     p = np.zeros(16)
     p[: len(params)] = params
     c = CameraParams.from_buffer_copy(cam)
     it = C.c_uint32(0)
-    costs = np.zeros(2)
+    costs = np.zeros(3)
     m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
-    lib().hm_lm_cam(ptrs, C.c_uint32(n), _p(p), C.byref(opt), C.byref(c), C.c_int(cam_flags), C.c_double(point_scale),
-                    None if m is None else _p(m), C.byref(it), _p(costs))
-    return p, np.array(c.p[: c.num_params]), it.value, costs
+    lib().hm_lm_cam_ex.restype = C.c_int
+    err = lib().hm_lm_cam_ex(ptrs, C.c_uint32(n), _p(p), C.byref(opt), C.byref(c), C.c_int(cam_flags), C.c_double(point_scale),
+                             None if m is None else _p(m), C.c_int(int(bool(device_cube))), C.byref(it), _p(costs))
+    if err:
+        raise ValueError(f"lm_cam: flags {cam_flags} select no parameter of camera model {cam.model_id}")
+    _last_invalid_steps = int(costs[2])
+    return p, np.array(c.p[: c.num_params]), it.value, costs[:2]
 
 
 def factorized_F(params):
@@ -318,8 +340,10 @@ def relpose_6pt_shared_focal(b1, b2, stride=1):
     return poses[:n].copy(), focals[:n].copy()
 
 
-def sfocal_lm(x1, x2, pose, focal, opt, prefilter_thr2=0.0, mask=None):
-    """the shared-focal refiner as k_sfocal_lm runs it.  Returns (pose7, focal, iterations, (initial cost, cost), skipped)"""
+def sfocal_lm(x1, x2, pose, focal, opt, prefilter_thr2=0.0, mask=None, device_cube=False):
+    """the shared-focal refiner as k_sfocal_lm runs it (device_cube: as lm()).  Returns (pose7, focal, iterations, (initial cost,
+    cost), skipped)"""
+    global _last_invalid_steps
     x1 = np.ascontiguousarray(x1, dtype=np.float64)
     x2 = np.ascontiguousarray(x2, dtype=np.float64)
     n = x1.shape[0]
@@ -327,12 +351,13 @@ def sfocal_lm(x1, x2, pose, focal, opt, prefilter_thr2=0.0, mask=None):
     p = np.ascontiguousarray(pose, dtype=np.float64).copy()
     f = C.c_double(focal)
     its = C.c_uint32(0)
-    costs = np.zeros(2)
+    costs = np.zeros(3)
     m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
-    lib().hm_sfocal_lm.restype = C.c_int
-    skipped = lib().hm_sfocal_lm(ptrs, C.c_uint32(n), _p(p), C.byref(f), C.byref(opt), C.c_double(prefilter_thr2),
-                                 None if m is None else _p(m), C.byref(its), _p(costs))
-    return p, f.value, its.value, costs, bool(skipped)
+    lib().hm_sfocal_lm_ex.restype = C.c_int
+    skipped = lib().hm_sfocal_lm_ex(ptrs, C.c_uint32(n), _p(p), C.byref(f), C.byref(opt), C.c_double(prefilter_thr2),
+                                    None if m is None else _p(m), C.c_int(int(bool(device_cube))), C.byref(its), _p(costs))
+    _last_invalid_steps = int(costs[2])
+    return p, f.value, its.value, costs[:2], bool(skipped)
 
 
 def ransac_shared_focal(x1, x2, max_error=1.0, seed=0, max_iterations=100000, min_iterations=1000, dyn_mult=3.0,
