@@ -576,6 +576,48 @@ int pl_debug_radial1d_generate(pl_problem *p, const uint32_t *samples, size_t nu
 int pl_debug_generate(pl_problem *p, const uint32_t *samples, uint64_t seed, uint64_t pos_base, const uint32_t *positions, size_t num_iters,
                       uint32_t slots_per_iter, int real_focal_check, int route, double *models, uint32_t *num_models, uint32_t *nan_bits,
                       uint32_t *blk_tot, uint32_t *blk_nan, uint32_t *flags);
+/* Diagnostic: ONE stage of the two focal-length estimators on its own - the generator (k_focal_setup + k_focal_solve /
+ * k_sfocal_setup + k_sfocal_solve), the scorers (k_focal_score[_wg] / k_sfocal_score[_wg]) or the mask kernel - through the
+ * production launchers, with the arguments wired as the estimators' back ends wire them (models, counts and the workspace in device
+ * memory; the mirrors, the scores and the LM task records in pinned mapped memory).  Problems of kind 0 run the kernels of
+ * ransac_pnpf, problems of kind 2 those of ransac_shared_focal_relpose; every member of one call has the same kind.
+ * stage 0 generate, 1 score, 2 mask.  group 0: one member through the single-problem launcher (the score launcher's own rule picks the
+ * kernel: one workgroup per model up to 1024 slots, one wavefront per model - with num_models on kind 2, one workgroup per iteration -
+ * above); group 1: 1 .. 8 members as a device-resident table through the group launcher, whose grid is the largest member's;
+ * workgroup_per_model selects the group score kernel (0 on kind 2 requires num_models: the launcher's grid is one workgroup per
+ * iteration).  A member:
+ *   problem, idle   idle 1: wired with n = 0 and no iterations / slots / correspondences over real buffers - nothing may be written
+ *   count           generate: iterations (1 .. 2^20); score: slots (1 .. 2^20); mask: unused (the problem's n)
+ *   capacity        extent of the member's output buffers in the same unit (mask: bytes, >= n), >= count; what lies beyond the
+ *                   member's own extent must keep the prefill
+ *   generate        samples (count x 4 | 6 indices < n) or positions (count draws, relative to pos_base, with seed) - exactly one;
+ *                   max_focal (kind 0; < 0: no bound).  Outputs: out_models capacity x (10 | 60) x 8 doubles (q, t, f) and
+ *                   out_num_models capacity from device memory, out_host_models / out_host_num_models the pinned mirrors
+ *   score           models count x 8 doubles; num_models (optional gate: count / (10 | 60) entries, count a multiple of it); as_tasks
+ *                   1: the models packed into LMTask / SFocalLMTask records and handed over as lm_tasks instead of models (no
+ *                   refinement runs); thr2.  Outputs: out_counts, out_sums capacity each
+ *   mask            models: one model; thr2.  Outputs: out_mask (device), out_host_mask (pinned mirror), capacity bytes each
+ * Prefill before the launch: 0xff bytes in the counters (out_num_models, out_host_num_models, out_counts), 0x5a bytes - a finite
+ * double - everywhere else.
+ * PL_ERR_INVALID: a null argument, mixed or unsupported problem kinds, group 0 with more than one member, count 0 (unless idle) or
+ * above 2^20, capacity below count, samples together with positions or neither, a sample index >= n, positions on a problem smaller
+ * than a sample, a gate on a slot count that is no multiple of the models per iteration. */
+typedef struct pl_focal_stage_member {
+    pl_problem *problem;
+    int32_t idle, as_tasks;
+    uint32_t count, capacity;
+    const uint32_t *samples, *positions;
+    uint64_t seed, pos_base;
+    double max_focal, thr2;
+    const double *models;
+    const uint32_t *num_models;
+    double *out_models, *out_host_models;
+    uint32_t *out_num_models, *out_host_num_models;
+    uint32_t *out_counts;
+    double *out_sums;
+    uint8_t *out_mask, *out_host_mask;
+} pl_focal_stage_member;
+int pl_debug_focal_stage(int stage, int group, int workgroup_per_model, pl_focal_stage_member *members, size_t num_members);
 /* Diagnostic entry (no counterpart in the reference): `n` models - pl_camera_pose[n] for kinds 0/1, double[n][9]
  * column-major for kinds 2/3 - through the STREAMING scorer of the batched main loop, i.e. through the conservative
  * pre-filters (fp16/MFMA or fp32) in front of the exact fp64 evaluation, instead of the sequential scorer behind

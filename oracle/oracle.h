@@ -118,6 +118,28 @@ double orc_normalize_points(double *x1, double *x2, size_t n, double *T1, double
                             int normalize_centroid, int shared_scale);
 void orc_unproject(const orc_camera *cam, const double *xp, size_t n, double *out /* n x 2 */);
 
+/* ---- the two focal-length estimators stage by stage (model: pose7 and the focal length f of a SIMPLE_PINHOLE camera {f, 0, 0}) ----
+ * orc_score_image: compute_msac_score(Image, ...) - returns the MSAC score, *inlier_sum (optional) the inliers' squared residuals
+ * alone, r2 (optional, n) every correspondence's squared residual as the loop compared it (NaN behind the camera).
+ * orc_inliers_image: get_inliers(Image, ...); r2 (optional, n) in the mask's own form (a division where the score multiplies by a
+ * reciprocal).  orc_score_shared_focal / orc_inliers_shared_focal: the Sampson score and mask of F = K_inv (E K_inv), K_inv =
+ * diag(1, 1, f); r2 (optional, n) the Sampson values.  The ref_ forms (oracle/_ref) leave inlier_sum and r2 alone: the reference
+ * returns neither. */
+double orc_score_image(const double *pose7, double f, const double *x, const double *X, size_t n, double sq_thr, uint64_t *cnt,
+                       double *inlier_sum, double *r2);
+void orc_inliers_image(const double *pose7, double f, const double *x, const double *X, size_t n, double sq_thr, uint8_t *mask,
+                       double *r2);
+double orc_score_shared_focal(const double *pose7, double f, const double *x1, const double *x2, size_t n, double sq_thr,
+                              uint64_t *cnt, double *r2);
+void orc_inliers_shared_focal(const double *pose7, double f, const double *x1, const double *x2, size_t n, double sq_thr,
+                              uint8_t *mask, double *r2);
+/* generate_models of the focal estimators on caller-supplied samples: which 0 = absolute pose with unknown focal length (a: n x 2
+ * image points about the principal point, b: n x 3; samples B x 4; the estimator's filter with max_focal, < 0: no bound), 1 = shared
+ * focal relative pose (a, b: n x 2; samples B x 6; max_focal unused).  counts: B; models: room for B x (10 | 60) x 8 doubles (q, t,
+ * f), filled densely in emission order.  Returns the number of models, -1 for an index beyond n. */
+int64_t orc_generate_focal(int32_t which, const double *a, const double *b, size_t n, const uint64_t *samples, size_t B,
+                           double max_focal, uint32_t *counts, double *models);
+
 /* ---- refinement ---- */
 void orc_bundle_adjust(const double *x, const double *X, size_t n, const orc_camera *cam, double *pose7,
                        const orc_bundle_opt *opt, orc_bundle_stats *st);

@@ -469,6 +469,105 @@ void ref_refine_shared_focal_relpose(const double *x1, const double *x2, size_t 
     pose_out(pair.pose, pose7);
     *focal = pair.camera1.focal();
 }
+// ---- the two focal-length estimators stage by stage (oracle.h): compute_msac_score / get_inliers through an Image with the
+// estimator's camera (absolute_pose.cc:97-103), and the Sampson score / mask of F = K_inv * (E * K_inv) as score_model and
+// ransac_shared_focal_relpose form it (relative_pose.cc:165-170, ransac.cc:194-200).  inlier_sum and r2 are not the reference's to give.
+namespace {
+Image focal_image(const double *pose7, double f) {
+    Camera camera;
+    camera.model_id = CameraModelId::SIMPLE_PINHOLE;
+    camera.width = 0;
+    camera.height = 0;
+    camera.params = {f, 0.0, 0.0};
+    return Image(pose_in(pose7), camera);
+}
+Eigen::Matrix3d shared_focal_F(const double *pose7, double f) {
+    Eigen::Matrix3d K_inv;
+    K_inv << 1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, f;
+    Eigen::Matrix3d E;
+    essential_from_motion(pose_in(pose7), &E);
+    Eigen::Matrix3d F = K_inv * (E * K_inv);
+    return F;
+}
+} // namespace
+double ref_score_image(const double *pose7, double f, const double *x, const double *X, size_t n, double sq_thr, uint64_t *cnt,
+                       double *, double *) {
+    size_t c = 0;
+    const double s = compute_msac_score(focal_image(pose7, f), pts2(x, n), pts3(X, n), sq_thr, &c);
+    *cnt = c;
+    return s;
+}
+void ref_inliers_image(const double *pose7, double f, const double *x, const double *X, size_t n, double sq_thr, uint8_t *mask, double *) {
+    std::vector<char> m;
+    get_inliers(focal_image(pose7, f), pts2(x, n), pts3(X, n), sq_thr, &m);
+    mask_out(m, mask);
+}
+double ref_score_shared_focal(const double *pose7, double f, const double *x1, const double *x2, size_t n, double sq_thr, uint64_t *cnt,
+                              double *) {
+    size_t c = 0;
+    const double s = compute_sampson_msac_score(shared_focal_F(pose7, f), pts2(x1, n), pts2(x2, n), sq_thr, &c);
+    *cnt = c;
+    return s;
+}
+void ref_inliers_shared_focal(const double *pose7, double f, const double *x1, const double *x2, size_t n, double sq_thr, uint8_t *mask,
+                              double *) {
+    std::vector<char> m;
+    get_inliers(shared_focal_F(pose7, f), pts2(x1, n), pts2(x2, n), sq_thr, &m);
+    mask_out(m, mask);
+}
+// generate_models of the two estimators on caller-supplied samples instead of their own sampler's: the samples' points as the
+// estimators gather them (absolute_pose.cc:73-76, relative_pose.cc:157-160), the reference's solvers, the focal-length filter of
+// absolute_pose.cc:90-95 (refine_minimal_sample and filter_minimal_sample are off by default)
+int64_t ref_generate_focal(int32_t which, const double *a, const double *b, size_t n, const uint64_t *samples, size_t B, double max_focal,
+                           uint32_t *counts, double *models) {
+    if (which < 0 || which > 1)
+        return -1;
+    const size_t K = which == 0 ? 4 : 6;
+    for (size_t i = 0; i < B * K; ++i)
+        if (samples[i] >= n)
+            return -1;
+    const std::vector<Point2D> x1 = pts2(a, n), x2 = which == 0 ? std::vector<Point2D>() : pts2(b, n);
+    const std::vector<Point3D> X = which == 0 ? pts3(b, n) : std::vector<Point3D>();
+    int64_t total = 0;
+    for (size_t i = 0; i < B; ++i) {
+        const uint64_t *sample = samples + K * i;
+        counts[i] = 0;
+        if (which == 0) {
+            std::vector<Point2D> xs(4);
+            std::vector<Point3D> Xs(4);
+            for (size_t k = 0; k < 4; ++k) {
+                xs[k] = x1[sample[k]];
+                Xs[k] = X[sample[k]];
+            }
+            std::vector<CameraPose> poses;
+            std::vector<double> focals;
+            p35pf(xs, Xs, &poses, &focals);
+            for (size_t j = 0; j < poses.size(); ++j) {
+                if (focals[j] < 0)
+                    continue;
+                if (max_focal >= 0 && focals[j] > max_focal)
+                    continue;
+                pose_out(poses[j], models + 8 * total);
+                models[8 * total + 7] = focals[j];
+                ++total, ++counts[i];
+            }
+        } else {
+            std::vector<Eigen::Vector3d> x1s(6), x2s(6);
+            for (size_t k = 0; k < 6; ++k) {
+                x1s[k] = x1[sample[k]].homogeneous().normalized();
+                x2s[k] = x2[sample[k]].homogeneous().normalized();
+            }
+            ImagePairVector pairs;
+            relpose_6pt_shared_focal(x1s, x2s, &pairs);
+            for (size_t j = 0; j < pairs.size(); ++j) {
+                pose_out(pairs[j].pose, models + 8 * total);
+                models[8 * total + 7] = pairs[j].camera1.focal();
+                ++total, ++counts[i];
+            }
+        }
+    }
+    return total;
+}
 void ref_ransac_relpose(const double *x1, const double *x2, size_t n, const orc_robust_opt *opt, double *pose7,
                         uint8_t *inliers, orc_stats *st) {
     CameraPose best = pose_in(pose7);

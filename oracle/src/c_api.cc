@@ -336,6 +336,43 @@ void orc_inliers_homography(const double *H9, const double *x1, const double *x2
     inliers_homography(mat_in(H9), pts2(x1, n), pts2(x2, n), sq_thr, &m);
     mask_out(m, mask);
 }
+// the two focal-length estimators stage by stage (oracle.h)
+double orc_score_image(const double *pose7, double f, const double *x, const double *X, size_t n, double sq_thr, uint64_t *cnt,
+                       double *inlier_sum, double *r2) {
+    return focal_score_image(pose_in(pose7), f, pts2(x, n), pts3(X, n), sq_thr, cnt, inlier_sum, r2);
+}
+void orc_inliers_image(const double *pose7, double f, const double *x, const double *X, size_t n, double sq_thr, uint8_t *mask,
+                       double *r2) {
+    std::vector<char> m;
+    focal_inliers_image(pose_in(pose7), f, pts2(x, n), pts3(X, n), sq_thr, &m, r2);
+    mask_out(m, mask);
+}
+double orc_score_shared_focal(const double *pose7, double f, const double *x1, const double *x2, size_t n, double sq_thr,
+                              uint64_t *cnt, double *r2) {
+    return focal_score_shared(pose_in(pose7), f, pts2(x1, n), pts2(x2, n), sq_thr, cnt, r2);
+}
+void orc_inliers_shared_focal(const double *pose7, double f, const double *x1, const double *x2, size_t n, double sq_thr,
+                              uint8_t *mask, double *r2) {
+    std::vector<char> m;
+    focal_inliers_shared(pose_in(pose7), f, pts2(x1, n), pts2(x2, n), sq_thr, &m, r2);
+    mask_out(m, mask);
+}
+int64_t orc_generate_focal(int32_t which, const double *a, const double *b, size_t n, const uint64_t *samples, size_t B,
+                           double max_focal, uint32_t *counts, double *models) {
+    if (which < 0 || which > 1)
+        return -1;
+    const size_t K = which == 0 ? 4 : 6;
+    for (size_t i = 0; i < B * K; ++i)
+        if (samples[i] >= n)
+            return -1;
+    const std::vector<V2> a2 = pts2(a, n);
+    const std::vector<V2> b2 = which == 0 ? std::vector<V2>() : pts2(b, n);
+    const std::vector<V3> b3 = which == 0 ? pts3(b, n) : std::vector<V3>();
+    std::vector<double> out;
+    const size_t total = generate_focal_on_samples(which, a2, b2, b3, samples, B, max_focal, counts, &out);
+    std::memcpy(models, out.data(), sizeof(double) * out.size());
+    return static_cast<int64_t>(total);
+}
 double orc_normalize_points(double *x1, double *x2, size_t n, double *T1, double *T2, int normalize_scale,
                             int normalize_centroid, int shared_scale) {
     std::vector<V2> a = pts2(x1, n), b = pts2(x2, n);

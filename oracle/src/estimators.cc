@@ -54,8 +54,20 @@ struct AbsEstimator {
     void refine(Pose *p) const { bundle_adjust(x, X, p, lo_options(opt.max_error)); }
 };
 
-// utils.cc:66-100: MSAC score through a camera (here always the SIMPLE_PINHOLE camera of the focal estimator: f x + cx)
-double msac_reproj_image(const Image &im, const std::vector<V2> &x, const std::vector<V3> &X, double sq_thr, uint64_t *inliers) {
+// Camera::project of a 2-D point (camera_models.h:90-94) for the SIMPLE_PINHOLE camera of the focal estimators: the point is lifted to
+// (a, b, 1), NORMALISED, and projected as f x / z + c (camera_models.cc:716-720) - the bearing's length is divided in and out again,
+// which is not the identity in floating point
+inline void project_simple_pinhole(double f, double cx, double cy, double a, double b, double *u, double *v) {
+    const double nrm = std::sqrt(a * a + b * b + 1.0 * 1.0);
+    const double x0 = a / nrm, x1 = b / nrm, x2 = 1.0 / nrm;
+    *u = f * x0 / x2 + cx;
+    *v = f * x1 / x2 + cy;
+}
+// utils.cc:66-100: MSAC score through a camera (here always the SIMPLE_PINHOLE camera of the focal estimator)
+// inlier_sum (optional): the inliers' squared residuals alone, before the outliers are charged; r2 (optional): every
+// correspondence's squared residual as the loop compared it, NaN where the loop never formed one (behind the camera)
+double msac_reproj_image(const Image &im, const std::vector<V2> &x, const std::vector<V3> &X, double sq_thr, uint64_t *inliers,
+                         double *inlier_sum = nullptr, double *r2 = nullptr) {
     *inliers = 0;
     double score = 0.0;
     const M3 R = im.pose.R();
@@ -66,29 +78,43 @@ double msac_reproj_image(const Image &im, const std::vector<V2> &x, const std::v
         const double z0 = R.m[0][0] * X0 + R.m[0][1] * X1 + R.m[0][2] * X2 + t.x;
         const double z1 = R.m[1][0] * X0 + R.m[1][1] * X1 + R.m[1][2] * X2 + t.y;
         const double z2 = R.m[2][0] * X0 + R.m[2][1] * X1 + R.m[2][2] * X2 + t.z;
+        if (r2)
+            r2[k] = std::numeric_limits<double>::quiet_NaN();
         if (z2 <= 0.0)
             continue;
         const double inv_z2 = 1.0 / z2;
-        const double r0 = (f * (z0 * inv_z2) + cx) - x[k].x;
-        const double r1 = (f * (z1 * inv_z2) + cy) - x[k].y;
+        double u, v;
+        project_simple_pinhole(f, cx, cy, z0 * inv_z2, z1 * inv_z2, &u, &v);
+        const double r0 = u - x[k].x;
+        const double r1 = v - x[k].y;
         const double r_sq = r0 * r0 + r1 * r1;
+        if (r2)
+            r2[k] = r_sq;
         if (r_sq < sq_thr) {
             ++*inliers;
             score += r_sq;
         }
     }
+    if (inlier_sum)
+        *inlier_sum = score;
     score += static_cast<double>(x.size() - *inliers) * sq_thr;
     return score;
 }
-// utils.cc:385-399 (hnormalized: a division, not the reciprocal of the score above)
-void inliers_reproj_image(const Image &im, const std::vector<V2> &x, const std::vector<V3> &X, double sq_thr, std::vector<char> *mask) {
+// utils.cc:385-399 (hnormalized: a division, not the reciprocal of the score above); r2 (optional): every correspondence's squared
+// residual in this form
+void inliers_reproj_image(const Image &im, const std::vector<V2> &x, const std::vector<V3> &X, double sq_thr, std::vector<char> *mask,
+                          double *r2_out = nullptr) {
     mask->resize(x.size());
     const M3 R = im.pose.R();
     const double f = im.camera.params[0], cx = im.camera.params[1], cy = im.camera.params[2];
     for (size_t k = 0; k < x.size(); ++k) {
         const V3 Z = R * X[k] + im.pose.t;
-        const double r0 = (f * (Z.x / Z.z) + cx) - x[k].x, r1 = (f * (Z.y / Z.z) + cy) - x[k].y;
+        double u, v;
+        project_simple_pinhole(f, cx, cy, Z.x / Z.z, Z.y / Z.z, &u, &v);
+        const double r0 = u - x[k].x, r1 = v - x[k].y;
         const double r2 = r0 * r0 + r1 * r1;
+        if (r2_out)
+            r2_out[k] = r2;
         (*mask)[k] = (r2 < sq_thr && Z.z > 0.0);
     }
 }
@@ -117,6 +143,9 @@ struct FocalAbsEstimator {
     void generate(std::vector<Image> *models) {
         uint64_t s[4];
         sampler.next(s);
+        generate_from(s, models);
+    }
+    void generate_from(const uint64_t *s, std::vector<Image> *models) const {
         V2 xs[4];
         V3 Xs[4];
         for (int k = 0; k < 4; ++k) {
@@ -225,6 +254,9 @@ struct SharedFocalRelEstimator {
     void generate(std::vector<ImagePair> *models) {
         uint64_t s[6];
         sampler.next(s);
+        generate_from(s, models);
+    }
+    void generate_from(const uint64_t *s, std::vector<ImagePair> *models) const {
         V3 a[6], b[6];
         for (int k = 0; k < 6; ++k) {
             a[k] = bearing(x1[s[k]]);
@@ -612,6 +644,76 @@ RansacStats estimate_homography(const std::vector<V2> &x1, const std::vector<V2>
     *H = inverse(T2) * (*H) * T1;
     scale_to_unit_frobenius(*H);
     return st;
+}
+
+// ---- the two focal estimators' stages on their own (c_api.cc: orc_score_image ... orc_generate_focal) ----
+namespace {
+Image focal_image(const Pose &pose, double f) {
+    Image im;
+    im.pose = pose;
+    im.camera.model_id = CAM_SIMPLE_PINHOLE;
+    im.camera.params = {f, 0.0, 0.0};
+    return im;
+}
+ImagePair focal_pair(const Pose &pose, double f) {
+    ImagePair p;
+    p.pose = pose;
+    p.focal = f;
+    return p;
+}
+} // namespace
+double focal_score_image(const Pose &pose, double f, const std::vector<V2> &x, const std::vector<V3> &X, double sq_thr, uint64_t *inliers,
+                         double *inlier_sum, double *r2) {
+    return msac_reproj_image(focal_image(pose, f), x, X, sq_thr, inliers, inlier_sum, r2);
+}
+void focal_inliers_image(const Pose &pose, double f, const std::vector<V2> &x, const std::vector<V3> &X, double sq_thr,
+                         std::vector<char> *mask, double *r2) {
+    inliers_reproj_image(focal_image(pose, f), x, X, sq_thr, mask, r2);
+}
+double focal_score_shared(const Pose &pose, double f, const std::vector<V2> &x1, const std::vector<V2> &x2, double sq_thr,
+                          uint64_t *inliers, double *r2) {
+    return msac_sampson_F(shared_focal_fundamental(focal_pair(pose, f)), x1, x2, sq_thr, inliers, r2);
+}
+void focal_inliers_shared(const Pose &pose, double f, const std::vector<V2> &x1, const std::vector<V2> &x2, double sq_thr,
+                          std::vector<char> *mask, double *r2) {
+    inliers_sampson_F(shared_focal_fundamental(focal_pair(pose, f)), x1, x2, sq_thr, mask, r2);
+}
+// generate_models of FocalAbsEstimator (which 0: a2 image points, b3 3-D points; max_focal < 0: no bound) or SharedFocalRelEstimator
+// (which 1: a2, b2 the two images' points) on caller-supplied samples.  counts[i]: models of sample i; models: 8 doubles (q, t, f) per
+// model in emission order, sample after sample.  Returns the number of models.
+size_t generate_focal_on_samples(int which, const std::vector<V2> &a2, const std::vector<V2> &b2, const std::vector<V3> &b3,
+                                 const uint64_t *samples, size_t B, double max_focal, uint32_t *counts, std::vector<double> *models) {
+    AbsolutePoseOptions ao;
+    ao.min_fov = 0.0; // (the bound is the caller's)
+    RelativePoseOptions ro;
+    FocalAbsEstimator abs_est(ao, a2, b3);
+    abs_est.max_focal_length = max_focal;
+    SharedFocalRelEstimator rel_est(ro, a2, b2);
+    std::vector<Image> images;
+    std::vector<ImagePair> pairs;
+    models->clear();
+    size_t total = 0;
+    auto emit = [&](const Pose &p, double f) {
+        for (int i = 0; i < 4; ++i)
+            models->push_back(p.q[i]);
+        models->push_back(p.t.x), models->push_back(p.t.y), models->push_back(p.t.z);
+        models->push_back(f);
+    };
+    for (size_t i = 0; i < B; ++i) {
+        if (which == 0) {
+            abs_est.generate_from(samples + 4 * i, &images);
+            for (const Image &im : images)
+                emit(im.pose, im.camera.params[0]);
+            counts[i] = static_cast<uint32_t>(images.size());
+        } else {
+            rel_est.generate_from(samples + 6 * i, &pairs);
+            for (const ImagePair &p : pairs)
+                emit(p.pose, p.focal);
+            counts[i] = static_cast<uint32_t>(pairs.size());
+        }
+        total += counts[i];
+    }
+    return total;
 }
 
 } // namespace orc

@@ -57,6 +57,24 @@ size_t generate_models_on_samples(int kind, const std::vector<V2> &a2, const std
                                   const uint64_t *samples, size_t B, bool real_focal_check, uint32_t *counts,
                                   std::vector<double> *models, V3 *first, V3 *second);
 
+// The two focal-length estimators stage by stage (model: pose + focal length of a SIMPLE_PINHOLE camera {f, 0, 0} / of both views):
+//   focal_score_image    compute_msac_score(Image, ...) (utils.cc:66-98): returns the MSAC score; *inlier_sum the inliers' squared
+//                        residuals alone, r2 [n] (optional) each correspondence's squared residual (NaN behind the camera)
+//   focal_inliers_image  get_inliers(Image, ...) (utils.cc:385-399); r2 [n] (optional) in the mask's own form (a division)
+//   focal_score_shared / focal_inliers_shared   the Sampson score and mask of F = K_inv (E K_inv) (relative_pose.cc:164-171,
+//                        ransac.cc:194-200); r2 [n] (optional) the Sampson values
+//   generate_focal_on_samples   generate_models of the two estimators on caller-supplied samples: see estimators.cc
+double focal_score_image(const Pose &pose, double f, const std::vector<V2> &x, const std::vector<V3> &X, double sq_thr, uint64_t *inliers,
+                         double *inlier_sum, double *r2);
+void focal_inliers_image(const Pose &pose, double f, const std::vector<V2> &x, const std::vector<V3> &X, double sq_thr,
+                         std::vector<char> *mask, double *r2);
+double focal_score_shared(const Pose &pose, double f, const std::vector<V2> &x1, const std::vector<V2> &x2, double sq_thr,
+                          uint64_t *inliers, double *r2);
+void focal_inliers_shared(const Pose &pose, double f, const std::vector<V2> &x1, const std::vector<V2> &x2, double sq_thr,
+                          std::vector<char> *mask, double *r2);
+size_t generate_focal_on_samples(int which, const std::vector<V2> &a2, const std::vector<V2> &b2, const std::vector<V3> &b3,
+                                 const uint64_t *samples, size_t B, double max_focal, uint32_t *counts, std::vector<double> *models);
+
 RansacStats estimate_absolute_pose(const std::vector<V2> &p2d, const std::vector<V3> &p3d, AbsolutePoseOptions opt,
                                    Image *image, std::vector<char> *inliers);
 RansacStats estimate_relative_pose(const std::vector<V2> &x1, const std::vector<V2> &x2, const Camera &cam1,

@@ -76,12 +76,14 @@ double msac_sampson_pose(const Pose &pose, const std::vector<V2> &x1, const std:
 }
 
 double msac_sampson_F(const M3 &F, const std::vector<V2> &x1, const std::vector<V2> &x2, double sq_thr,
-                      uint64_t *inliers) {
+                      uint64_t *inliers, double *r2_out) {
     const Epi E(F);
     uint64_t cnt = 0;
     double score = 0.0;
     for (size_t k = 0; k < x1.size(); ++k) {
         const double r2 = E.sampson(x1[k], x2[k]);
+        if (r2_out)
+            r2_out[k] = r2;
         if (r2 < sq_thr) {
             ++cnt;
             score += r2;
@@ -152,12 +154,15 @@ int inliers_sampson_pose(const Pose &pose, const std::vector<V2> &x1, const std:
 }
 
 int inliers_sampson_F(const M3 &F, const std::vector<V2> &x1, const std::vector<V2> &x2, double sq_thr,
-                      std::vector<char> *mask) {
+                      std::vector<char> *mask, double *r2_out) {
     mask->resize(x1.size());
     const Epi E(F);
     int cnt = 0;
     for (size_t k = 0; k < x1.size(); ++k) {
-        const bool in = E.sampson(x1[k], x2[k]) < sq_thr;
+        const double r2 = E.sampson(x1[k], x2[k]);
+        if (r2_out)
+            r2_out[k] = r2;
+        const bool in = r2 < sq_thr;
         cnt += in;
         (*mask)[k] = in;
     }

@@ -17,8 +17,9 @@ double msac_reproj(const Pose &pose, const std::vector<V2> &x, const std::vector
 double msac_sampson_pose(const Pose &pose, const std::vector<V2> &x1, const std::vector<V2> &x2, double sq_thr,
                          uint64_t *inliers);
 // utils.cc:204-239
+// (r2: optional, the Sampson value of every correspondence as the loop compared it)
 double msac_sampson_F(const M3 &F, const std::vector<V2> &x1, const std::vector<V2> &x2, double sq_thr,
-                      uint64_t *inliers);
+                      uint64_t *inliers, double *r2 = nullptr);
 // utils.cc:300-329
 double msac_homography(const M3 &H, const std::vector<V2> &x1, const std::vector<V2> &x2, double sq_thr,
                        uint64_t *inliers);
@@ -31,7 +32,7 @@ int inliers_sampson_pose(const Pose &pose, const std::vector<V2> &x1, const std:
                          std::vector<char> *mask);
 // utils.cc:479-513
 int inliers_sampson_F(const M3 &F, const std::vector<V2> &x1, const std::vector<V2> &x2, double sq_thr,
-                      std::vector<char> *mask);
+                      std::vector<char> *mask, double *r2 = nullptr);
 // utils.cc:331-351
 void inliers_homography(const M3 &H, const std::vector<V2> &x1, const std::vector<V2> &x2, double sq_thr,
                         std::vector<char> *mask);

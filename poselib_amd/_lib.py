@@ -103,6 +103,14 @@ class DebugSamplerMember(C.Structure):  # pl_debug_sampler_member
                 ("build_used", u32), ("delta_guard", i32), ("ctl_clear", i32), ("pad", i32)]
 
 
+class FocalStageMember(C.Structure):  # pl_focal_stage_member
+    _fields_ = [("problem", C.c_void_p), ("idle", i32), ("as_tasks", i32), ("count", u32), ("capacity", u32), ("samples", C.c_void_p),
+                ("positions", C.c_void_p), ("seed", u64), ("pos_base", u64), ("max_focal", C.c_double), ("thr2", C.c_double),
+                ("models", C.c_void_p), ("num_models", C.c_void_p), ("out_models", C.c_void_p), ("out_host_models", C.c_void_p),
+                ("out_num_models", C.c_void_p), ("out_host_num_models", C.c_void_p), ("out_counts", C.c_void_p), ("out_sums", C.c_void_p),
+                ("out_mask", C.c_void_p), ("out_host_mask", C.c_void_p)]
+
+
 PL_F64, PL_F32 = 0, 1
 
 
@@ -236,6 +244,7 @@ def _declare(L):
         "pl_debug_group_slices": (cint, [cint, C.c_uint32, C.c_uint32, C.c_uint32]),
         "pl_debug_radial1d_generate": (cint, [vp, vp, sz, C.c_uint32, vp, vp, vp]),
         "pl_debug_generate": (cint, [vp, vp, u64, u64, vp, sz, C.c_uint32, cint, cint, vp, vp, vp, vp, vp, vp]),
+        "pl_debug_focal_stage": (cint, [cint, cint, cint, P(FocalStageMember), sz]),
         "pl_estimate_1D_radial_absolute_pose": (cint, [vp, vp, sz, opt, pose, vp, stats]),
         "pl_ransac_1D_radial_pnp": (cint, [vp, vp, sz, opt, pose, vp, stats]),
         "pl_p5lp_radial": (cint, [vp, vp, P(CameraPose), P(cint)]),
@@ -296,6 +305,7 @@ EXPORTED_SYMBOLS = [
     "pl_estimate_shared_focal_relative_pose", "pl_solve_focal_batch", "pl_p35pf", "pl_relpose_6pt_shared_focal", "pl_set_lm_mode",
     "pl_abi_version", "pl_problem_create_tangent", "pl_debug_inlier_mask", "pl_debug_tangent_chunk",
     "pl_p5lp_radial", "pl_debug_radial1d_chunk", "pl_debug_radial1d_generate", "pl_debug_group_slices", "pl_debug_generate",
+    "pl_debug_focal_stage",
     "pl_debug_score_shape", "pl_debug_score_stream_ex", "pl_debug_score_pruned", "pl_debug_score_survivors", "pl_debug_score_prune_gate",
     "pl_debug_score_bounded", "pl_debug_score_bounded_columns", "pl_debug_lm_route",
     "pl_estimate_absolute_pose_dev", "pl_estimate_relative_pose_dev", "pl_estimate_fundamental_dev", "pl_estimate_homography_dev",

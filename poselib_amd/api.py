@@ -1397,6 +1397,73 @@ def debug_generate(problem, samples=None, seed=0, pos_base=0, positions=None, sl
     return out
 
 
+FOCAL_STAGE_SAMPLE = {KIND_ABS: 4, KIND_FUND: 6}
+FOCAL_STAGE_MAX_MODELS = {KIND_ABS: 10, KIND_FUND: 60}
+
+
+def debug_focal_stage(stage, members, group=False, workgroup_per_model=False):
+    """Diagnostic (pl_debug_focal_stage): one stage - "generate", "score" or "mask" - of the focal-length estimators' kernels through
+    the production launchers: Problem(KIND_ABS) runs the pnpf kernels, Problem(KIND_FUND) the shared-focal ones.  `members`: a dict
+    (or, with group=True, a list of up to 8) with "problem" and, by stage,
+      generate  "samples" (B, K) or "positions" (B,) with "seed" / "pos_base"; "max_focal" (default -1: no bound)
+      score     "models" (S, 8) [q t f], "thr2"; optional "num_models" (S / max_models,) gate, "as_tasks"
+      mask      "model" (8,), "thr2"
+    and optionally "idle" (wired with no work over real buffers) and "capacity" (extent of the output buffers, default: the member's
+    own).  Returns one dict per member with the whole buffers, prefilled with 0xffffffff (counters) / 0x5a bytes (the rest):
+    models, num_models, host_models, host_num_models | counts, sums | mask, host_mask (uint8)."""
+    st = {"generate": 0, "score": 1, "mask": 2}[stage]
+    single = isinstance(members, dict)
+    ms = [members] if single else list(members)
+    rec = (L.FocalStageMember * max(len(ms), 1))()
+    keep, outs = [], []
+    for r, m in zip(rec, ms):
+        prob = m["problem"]
+        K, maxm = FOCAL_STAGE_SAMPLE.get(prob.kind, 4), FOCAL_STAGE_MAX_MODELS.get(prob.kind, 10)
+        r.problem = prob._h
+        r.idle = int(bool(m.get("idle", False)))
+        r.as_tasks = int(bool(m.get("as_tasks", False)))
+        r.seed, r.pos_base = int(m.get("seed", 0)), int(m.get("pos_base", 0))
+        r.max_focal, r.thr2 = float(m.get("max_focal", -1.0)), float(m.get("thr2", 0.0))
+        out = {}
+        if st == 0:
+            idx = None if m.get("samples") is None else np.ascontiguousarray(m["samples"], dtype=np.uint32).reshape(-1, K)
+            pos = None if m.get("positions") is None else np.ascontiguousarray(m["positions"], dtype=np.uint32).reshape(-1)
+            count = int(m["count"]) if "count" in m else idx.shape[0] if idx is not None else 0 if pos is None else pos.shape[0]
+            cap = int(m.get("capacity", max(count, 1)))
+            out = {"models": np.zeros((cap, maxm, 8)), "num_models": np.zeros(cap, dtype=np.uint32),
+                   "host_models": np.zeros((cap, maxm, 8)), "host_num_models": np.zeros(cap, dtype=np.uint32)}
+            r.samples = None if idx is None else _ptr(idx)
+            r.positions = None if pos is None else _ptr(pos)
+            r.out_models, r.out_num_models = _ptr(out["models"]), _ptr(out["num_models"])
+            r.out_host_models, r.out_host_num_models = _ptr(out["host_models"]), _ptr(out["host_num_models"])
+            keep += [idx, pos]
+        elif st == 1:
+            mod = None if m.get("models") is None else np.ascontiguousarray(m["models"], dtype=np.float64).reshape(-1, 8)
+            gate = None if m.get("num_models") is None else np.ascontiguousarray(m["num_models"], dtype=np.uint32).reshape(-1)
+            count = int(m["count"]) if "count" in m else 0 if mod is None else mod.shape[0]
+            cap = int(m.get("capacity", max(count, 1)))
+            out = {"counts": np.zeros(cap, dtype=np.uint32), "sums": np.zeros(cap)}
+            r.models = None if mod is None else _ptr(mod)
+            r.num_models = None if gate is None else _ptr(gate)
+            r.out_counts, r.out_sums = _ptr(out["counts"]), _ptr(out["sums"])
+            keep += [mod, gate]
+        else:
+            mod = None if m.get("model") is None else np.ascontiguousarray(m["model"], dtype=np.float64).reshape(8)
+            count = 0
+            cap = int(m.get("capacity", max(prob.n, 1)))
+            out = {"mask": np.zeros(cap, dtype=np.uint8), "host_mask": np.zeros(cap, dtype=np.uint8)}
+            r.models = None if mod is None else _ptr(mod)
+            r.out_mask, r.out_host_mask = _ptr(out["mask"]), _ptr(out["host_mask"])
+            keep.append(mod)
+        r.count = 0 if r.idle else count
+        r.capacity = cap
+        outs.append(out)
+    L.check(L.lib().pl_debug_focal_stage(C.c_int(st), C.c_int(int(bool(group))), C.c_int(int(bool(workgroup_per_model))), rec,
+                                         C.c_size_t(len(ms))))
+    del keep
+    return outs[0] if single else outs
+
+
 def inlier_mask(problem, model, max_error):
     """Diagnostic (pl_debug_inlier_mask): the inlier mask of one model on a resident problem."""
     mask = np.zeros(max(problem.n, 1), dtype=np.uint8)

@@ -3861,6 +3861,261 @@ int pl_debug_radial1d_generate(pl_problem *p, const uint32_t *samples, size_t nu
     return PL_OK;
 }
 
+// Diagnostic: one stage of the two focal-length estimators on its own (the header describes the arguments).  The argument blocks are
+// filled by the group policies' gen_args / score_args / lo_task - the functions driver_focal_group.inc wires its members with, which
+// set what DeviceFocalBackend / DeviceSFocalBackend set field by field - and go through the production launchers; nothing here
+// selects a kernel.  Where the back ends keep a buffer is where it lives here: models, counts per iteration, the solver workspace and
+// the mask in device memory; the mirrors, the scores and the task records in pinned mapped memory.
+extern "C++" { // (overloads and a template inside the C interface's block)
+namespace {
+constexpr unsigned char kStageFillCounter = 0xff, kStageFill = 0x5a;
+struct StageBuffers { // one member's buffers, released on every path
+    void *dev[4] = {nullptr, nullptr, nullptr, nullptr};   // generate: models, num_models, stage | score: models, num_models | mask: mask
+    void *host[4] = {nullptr, nullptr, nullptr, nullptr};  // generate: host_models, host_num_models, positions / samples | score: counts, sums, tasks | mask: host_mask
+    void *hdev[4] = {nullptr, nullptr, nullptr, nullptr};  // host[k] as the device addresses it
+    ~StageBuffers() {
+        for (void *q : dev)
+            if (q)
+                (void)hipFree(q);
+        for (void *q : host)
+            if (q)
+                (void)hipHostFree(q);
+    }
+    hipError_t device(int k, size_t bytes) { return hipMalloc(&dev[k], std::max<size_t>(bytes, 256)); }
+    hipError_t pinned(int k, size_t bytes) {
+        hipError_t e = hipHostMalloc(&host[k], std::max<size_t>(bytes, 256), hipHostMallocMapped);
+        return e != hipSuccess ? e : hipHostGetDevicePointer(&hdev[k], host[k], 0);
+    }
+};
+inline hipError_t stage_generate(const FocalGenArgs &g, hipStream_t s) { return launch_focal_generate(g, s); }
+inline hipError_t stage_generate(const SFocalGenArgs &g, hipStream_t s) { return launch_sfocal_generate(g, s); }
+inline hipError_t stage_score(const FocalScoreArgs &a, hipStream_t s) { return launch_focal_score(a, s); }
+inline hipError_t stage_score(const SFocalScoreArgs &a, hipStream_t s) { return launch_sfocal_score(a, s); }
+inline hipError_t stage_mask(PnpfGroupPolicy *, const FocalMaskArgs &a, hipStream_t s) {
+    return launch_focal_mask(a.a, a.n, a.model, a.thr2, a.mask, a.host_mask, s);
+}
+inline hipError_t stage_mask(SFocalGroupPolicy *, const FocalMaskArgs &a, hipStream_t s) {
+    return launch_sfocal_mask(a.a, a.n, a.model, a.thr2, a.mask, a.host_mask, s);
+}
+
+template <class P> int debug_focal_stage(Context *c, int stage, bool group, bool wg, pl_focal_stage_member *ms, uint32_t G) {
+    using GenArgs = typename P::GenArgs;
+    using ScoreArgs = typename P::ScoreArgs;
+    using Task = typename P::Task;
+    constexpr uint32_t K = P::Traits::kSample, M = P::Traits::kMaxModels;
+    std::vector<StageBuffers> bufs(G);
+    std::vector<FocalGroupItem> items(G);
+    std::vector<GenArgs> ga(G);
+    std::vector<ScoreArgs> sa(G);
+    std::vector<FocalMaskArgs> ma(G);
+    uint32_t extent_max = 0;
+    for (uint32_t k = 0; k < G; ++k) {
+        const pl_focal_stage_member &m = ms[k];
+        StageBuffers &b = bufs[k];
+        FocalGroupItem &g = items[k];
+        g.prob = *m.problem;
+        g.n = m.idle ? 0u : m.problem->n;
+        g.max_focal = m.max_focal;
+        g.thr2 = m.thr2;
+        g.lm_lo = lo_options(std::sqrt(std::max(m.thr2, 0.0)));
+        const uint32_t count = m.idle ? 0u : m.count, cap = m.capacity;
+        if (stage == 0) {
+            const size_t mod_bytes = sizeof(FocalModel) * (size_t)cap * M, nm_bytes = sizeof(uint32_t) * (size_t)cap;
+            HIP_TRY(b.device(0, mod_bytes));
+            HIP_TRY(b.device(1, nm_bytes));
+            HIP_TRY(b.device(2, P::stage_bytes(std::max(cap, 1u))));
+            HIP_TRY(b.pinned(0, mod_bytes));
+            HIP_TRY(b.pinned(1, nm_bytes));
+            HIP_TRY(b.pinned(2, sizeof(uint32_t) * (size_t)std::max(cap, 1u) * K));
+            HIP_TRY(hipMemsetAsync(b.dev[0], kStageFill, mod_bytes, c->stream));
+            HIP_TRY(hipMemsetAsync(b.dev[1], kStageFillCounter, nm_bytes, c->stream));
+            std::memset(b.host[0], kStageFill, mod_bytes);
+            std::memset(b.host[1], kStageFillCounter, nm_bytes);
+            // (the generator reads the positions / samples from the pinned block itself, as in the back ends)
+            if (count)
+                std::memcpy(b.host[2], m.samples ? m.samples : m.positions, sizeof(uint32_t) * (size_t)count * (m.samples ? K : 1));
+            GenArgs &a = ga[k];
+            P::gen_args(a, g);
+            a.n = g.n;
+            a.seed = m.seed;
+            a.pos_base = m.pos_base;
+            a.positions = static_cast<const uint32_t *>(b.hdev[2]);
+            a.samples = m.samples ? static_cast<const uint32_t *>(b.hdev[2]) : nullptr;
+            a.num_iters = count;
+            a.models = static_cast<FocalModel *>(b.dev[0]);
+            a.num_models = static_cast<uint32_t *>(b.dev[1]);
+            a.stage = static_cast<double *>(b.dev[2]);
+            a.explicit_in = nullptr;
+            a.host_models = static_cast<FocalModel *>(b.hdev[0]);
+            a.host_num_models = static_cast<uint32_t *>(b.hdev[1]);
+            extent_max = std::max(extent_max, count);
+        } else if (stage == 1) {
+            const size_t cnt_bytes = sizeof(uint32_t) * (size_t)cap, sum_bytes = sizeof(double) * (size_t)cap;
+            HIP_TRY(b.device(0, sizeof(FocalModel) * (size_t)std::max(count, 1u)));
+            HIP_TRY(b.device(1, sizeof(uint32_t) * (size_t)(count / M + 1)));
+            HIP_TRY(b.pinned(0, cnt_bytes));
+            HIP_TRY(b.pinned(1, sum_bytes));
+            HIP_TRY(b.pinned(2, sizeof(Task) * (size_t)std::max(count, 1u)));
+            std::memset(b.host[0], kStageFillCounter, cnt_bytes);
+            std::memset(b.host[1], kStageFill, sum_bytes);
+            const FocalModel *models = reinterpret_cast<const FocalModel *>(m.models);
+            if (count && !m.as_tasks)
+                HIP_TRY(hipMemcpyAsync(b.dev[0], models, sizeof(FocalModel) * (size_t)count, hipMemcpyHostToDevice, c->stream));
+            if (count && m.num_models)
+                HIP_TRY(hipMemcpyAsync(b.dev[1], m.num_models, sizeof(uint32_t) * (size_t)(count / M), hipMemcpyHostToDevice, c->stream));
+            Task *ht = static_cast<Task *>(b.host[2]);
+            for (uint32_t j = 0; m.as_tasks && j < count; ++j) // the record a local optimisation is enqueued with; no refinement runs
+                P::lo_task(ht[j], g, models[j], nullptr);
+            ScoreArgs &a = sa[k];
+            P::score_args(a, g, m.as_tasks ? static_cast<const Task *>(b.hdev[2]) : nullptr, static_cast<uint32_t *>(b.hdev[0]),
+                          static_cast<double *>(b.hdev[1]));
+            a.models = m.as_tasks ? nullptr : static_cast<const FocalModel *>(b.dev[0]);
+            a.num_models = m.num_models ? static_cast<const uint32_t *>(b.dev[1]) : nullptr;
+            a.num_slots = count;
+            extent_max = std::max(extent_max, count);
+        } else {
+            HIP_TRY(b.device(0, cap));
+            HIP_TRY(b.pinned(0, cap));
+            HIP_TRY(hipMemsetAsync(b.dev[0], kStageFill, cap, c->stream));
+            std::memset(b.host[0], kStageFill, cap);
+            FocalMaskArgs &a = ma[k];
+            std::memset(&a, 0, sizeof(a));
+            for (int d = 0; d < P::kNd; ++d)
+                a.a[d] = g.prob.ps.a[d];
+            a.n = g.n;
+            std::memcpy(&a.model, m.models, sizeof(FocalModel));
+            a.thr2 = m.thr2;
+            a.mask = static_cast<uint8_t *>(b.dev[0]);
+            a.host_mask = static_cast<uint8_t *>(b.hdev[0]);
+            extent_max = std::max(extent_max, g.n);
+        }
+    }
+    struct Table { // freed on every path
+        void *p = nullptr;
+        ~Table() {
+            if (p)
+                (void)hipFree(p);
+        }
+    } table;
+    auto upload = [&](const void *src, size_t bytes) -> hipError_t {
+        hipError_t e = hipMalloc(&table.p, bytes);
+        return e != hipSuccess ? e : hipMemcpyAsync(table.p, src, bytes, hipMemcpyHostToDevice, c->stream);
+    };
+    if (stage == 0) {
+        if (group) {
+            HIP_TRY(upload(ga.data(), sizeof(GenArgs) * G));
+            HIP_TRY(P::generate(static_cast<const GenArgs *>(table.p), G, extent_max, c->stream));
+        } else {
+            HIP_TRY(stage_generate(ga[0], c->stream));
+        }
+    } else if (stage == 1) {
+        if (group) {
+            HIP_TRY(upload(sa.data(), sizeof(ScoreArgs) * G));
+            HIP_TRY(P::score(static_cast<const ScoreArgs *>(table.p), G, extent_max, wg, c->stream));
+        } else {
+            HIP_TRY(stage_score(sa[0], c->stream));
+        }
+    } else {
+        if (group) {
+            HIP_TRY(upload(ma.data(), sizeof(FocalMaskArgs) * G));
+            HIP_TRY(P::mask(static_cast<const FocalMaskArgs *>(table.p), G, extent_max, c->stream));
+        } else {
+            HIP_TRY(stage_mask(static_cast<P *>(nullptr), ma[0], c->stream));
+        }
+    }
+    for (uint32_t k = 0; k < G; ++k) {
+        const pl_focal_stage_member &m = ms[k];
+        const uint32_t cap = m.capacity;
+        if (stage == 0) {
+            HIP_TRY(hipMemcpyAsync(m.out_models, bufs[k].dev[0], sizeof(FocalModel) * (size_t)cap * M, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipMemcpyAsync(m.out_num_models, bufs[k].dev[1], sizeof(uint32_t) * (size_t)cap, hipMemcpyDeviceToHost, c->stream));
+        } else if (stage == 2) {
+            HIP_TRY(hipMemcpyAsync(m.out_mask, bufs[k].dev[0], cap, hipMemcpyDeviceToHost, c->stream));
+        }
+    }
+    HIP_TRY(wait_stream(c));
+    for (uint32_t k = 0; k < G; ++k) { // what the kernels wrote into pinned memory themselves
+        const pl_focal_stage_member &m = ms[k];
+        const uint32_t cap = m.capacity;
+        if (stage == 0) {
+            std::memcpy(m.out_host_models, bufs[k].host[0], sizeof(FocalModel) * (size_t)cap * M);
+            std::memcpy(m.out_host_num_models, bufs[k].host[1], sizeof(uint32_t) * (size_t)cap);
+        } else if (stage == 1) {
+            std::memcpy(m.out_counts, bufs[k].host[0], sizeof(uint32_t) * (size_t)cap);
+            std::memcpy(m.out_sums, bufs[k].host[1], sizeof(double) * (size_t)cap);
+        } else {
+            std::memcpy(m.out_host_mask, bufs[k].host[0], cap);
+        }
+    }
+    return PL_OK;
+}
+} // namespace
+} // extern "C++"
+int pl_debug_focal_stage(int stage, int group, int workgroup_per_model, pl_focal_stage_member *members, size_t num_members) {
+    if (!members)
+        return fail(PL_ERR_INVALID, "null argument");
+    if (stage < 0 || stage > 2 || group < 0 || group > 1)
+        return fail(PL_ERR_INVALID, "stage: 0 generate, 1 score, 2 mask; group: 0 single launch, 1 group form");
+    if (num_members < 1 || num_members > 8 || (!group && num_members != 1))
+        return fail(PL_ERR_INVALID, "one member for the single launch, 1..8 for the group form");
+    for (size_t k = 0; k < num_members; ++k)
+        if (!members[k].problem)
+            return fail(PL_ERR_INVALID, "null argument");
+    const int kind = members[0].problem->kind;
+    if (kind != EST_ABS && kind != EST_FUND)
+        return fail(PL_ERR_INVALID, "the focal-length stages work on problems of kind 0 (absolute pose) or 2 (two views)");
+    const uint32_t K = kind == EST_ABS ? kFocalSample : kSFocalSample, M = kind == EST_ABS ? kFocalMaxModels : kSFocalMaxModels;
+    for (size_t k = 0; k < num_members; ++k) {
+        const pl_focal_stage_member &m = members[k];
+        if (m.problem->kind != kind)
+            return fail(PL_ERR_INVALID, "the members of one call have the same problem kind");
+        const bool outputs = stage == 0   ? m.out_models && m.out_num_models && m.out_host_models && m.out_host_num_models
+                             : stage == 1 ? m.out_counts && m.out_sums
+                                          : m.out_mask && m.out_host_mask;
+        if (!outputs)
+            return fail(PL_ERR_INVALID, "null argument");
+        if (stage == 2) {
+            if (!m.models)
+                return fail(PL_ERR_INVALID, "null argument");
+            if (m.capacity < m.problem->n || m.capacity == 0)
+                return fail(PL_ERR_INVALID, "capacity below the problem's size");
+            continue;
+        }
+        if (m.count > (1u << 20) || (!m.idle && m.count == 0) || m.capacity < m.count || m.capacity == 0)
+            return fail(PL_ERR_INVALID, "count must be 1..2^20 (0 for an idle member) and capacity at least count");
+        if (m.idle)
+            continue;
+        if (stage == 0) {
+            if ((m.samples != nullptr) == (m.positions != nullptr))
+                return fail(PL_ERR_INVALID, "give explicit samples or draw positions, not both");
+            if (m.samples) {
+                for (size_t i = 0; i < (size_t)K * m.count; ++i)
+                    if (m.samples[i] >= m.problem->n)
+                        return fail(PL_ERR_INVALID, "sample index beyond the problem's correspondences");
+            } else if (m.problem->n < K) {
+                return fail(PL_ERR_INVALID, "fewer correspondences than a minimal sample");
+            }
+        } else {
+            if (!m.models)
+                return fail(PL_ERR_INVALID, "null argument");
+            if (m.num_models && m.count % M != 0)
+                return fail(PL_ERR_INVALID, "a gated slot count is a multiple of the models per iteration");
+            if (group && !workgroup_per_model && kind == EST_FUND && !m.num_models)
+                return fail(PL_ERR_INVALID, "the shared-focal group scorer by iterations needs num_models");
+        }
+    }
+    Context *c;
+    int rc = get_context(&c);
+    if (rc != PL_OK)
+        return rc;
+    for (size_t k = 0; k < num_members; ++k)
+        if (members[k].problem->device != c->device)
+            return fail(PL_ERR_INVALID, "problem lives on another device than the calling thread's");
+    if (kind == EST_ABS)
+        return debug_focal_stage<PnpfGroupPolicy>(c, stage, group != 0, workgroup_per_model != 0, members, (uint32_t)num_members);
+    return debug_focal_stage<SFocalGroupPolicy>(c, stage, group != 0, workgroup_per_model != 0, members, (uint32_t)num_members);
+}
+
 // ---------------------------------------------------------------------------- front-ends (robust.cc)
 // the final bundle of a front-end over the inliers of the loop's model (the device mask ransac_core / run_focal left in c->mask)
 int front_final_refine(Context *c, pl_problem *p, const FrontEnd &fe, double *rec, CameraParams *cam_refined) {

@@ -23,26 +23,39 @@ struct FocalModel {
 };
 static_assert(sizeof(FocalModel) == 64, "8 doubles");
 
-// utils.cc:76-94 with SIMPLE_PINHOLE project (camera_models.cc: f x + cx, cx = cy = 0 here: + 0.0 changes no squared residual)
+// Camera::project of a 2-D point (misc/camera_models.h:90-94) with the SIMPLE_PINHOLE model (camera_models.cc:716-720): the point is
+// lifted to (a, b, 1), NORMALISED, and projected as f x / z + c.  Dividing the bearing's length in and out again is not the identity
+// in floating point, so every operation is kept, in the reference's order (cx = cy = 0 here: + 0.0 changes no squared residual).
+PL_HD void focal_project(double f, double a, double b, double &u, double &v) {
+    const double nrm = sqrt(a * a + b * b + 1.0 * 1.0);
+    const double x0 = a / nrm, x1 = b / nrm, x2 = 1.0 / nrm;
+    u = f * x0 / x2;
+    v = f * x1 / x2;
+}
+// utils.cc:76-94: the camera point times the reciprocal of its depth, then Camera::project
 PL_HD bool focal_reproj_inlier(const double *R, const double *t, double f, double x, double y, double X, double Y, double Z,
                                double thr2, double &r2) {
     const double z0 = R[0] * X + R[1] * Y + R[2] * Z + t[0];
     const double z1 = R[3] * X + R[4] * Y + R[5] * Z + t[1];
     const double z2 = R[6] * X + R[7] * Y + R[8] * Z + t[2];
     const double inv = 1.0 / z2;
-    const double e0 = f * (z0 * inv) - x;
-    const double e1 = f * (z1 * inv) - y;
+    double u, v;
+    focal_project(f, z0 * inv, z1 * inv, u, v);
+    const double e0 = u - x;
+    const double e1 = v - y;
     r2 = e0 * e0 + e1 * e1;
     return (z2 > 0.0) & (r2 < thr2);
 }
-// utils.cc:385-399: hnormalized() divides
+// utils.cc:385-399: hnormalized() divides, then Camera::project
 PL_HD bool focal_reproj_mask(const double *R, const double *t, double f, double x, double y, double X, double Y, double Z,
                              double thr2) {
     const double z0 = R[0] * X + R[1] * Y + R[2] * Z + t[0];
     const double z1 = R[3] * X + R[4] * Y + R[5] * Z + t[1];
     const double z2 = R[6] * X + R[7] * Y + R[8] * Z + t[2];
-    const double e0 = f * (z0 / z2) - x;
-    const double e1 = f * (z1 / z2) - y;
+    double u, v;
+    focal_project(f, z0 / z2, z1 / z2, u, v);
+    const double e0 = u - x;
+    const double e1 = v - y;
     const double r2 = e0 * e0 + e1 * e1;
     return (r2 < thr2) & (z2 > 0.0);
 }
@@ -407,8 +420,8 @@ struct FocalScoreArgs {
     const struct LMTask *lm_tasks; // optional: slot s = the pose and focal length k_lm_cam left in task s (instead of models)
     uint32_t num_slots;
     double thr2;
-    uint32_t *counts; // [num_slots]  (slots without a model: 0)
-    double *sums;     // [num_slots]
+    uint32_t *counts; // [num_slots]  a slot the num_models gate leaves empty: count 0 and sum 0.0, WRITTEN by both kernels (the pinned
+    double *sums;     // [num_slots]  block of the back ends never holds garbage, and no fill is dispatched in front of the launch)
 };
 
 struct FocalMaskArgs { // get_inliers of one member of a group (k_focal_mask_g)

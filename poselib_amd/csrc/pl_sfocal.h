@@ -176,8 +176,8 @@ struct SFocalScoreArgs {
     const SFocalLMTask *lm_tasks; // optional: slot s = the model k_sfocal_lm left in task s (a skipped task still holds its seed) instead of models
     uint32_t num_slots;
     double thr2;
-    uint32_t *counts; // [num_slots]
-    double *scores;   // [num_slots]
+    uint32_t *counts; // [num_slots]  a slot the num_models gate leaves empty is NOT written by either kernel (60 slots per iteration,
+    double *scores;   // [num_slots]  0.3 of them filled: the back ends read the filled slots only, driver_sfocal.inc)
 };
 // one refinement (refine_model, relative_pose.cc:173-203; with prefilter_thr2 == 0 and a mask: the front-end's final bundle)
 struct SFocalLMTask {

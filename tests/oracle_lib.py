@@ -322,6 +322,78 @@ def relpose_6pt_shared_focal(b1, b2):
     return poses[:n].copy(), focals[:n].copy()
 
 
+# ------------------------------------------------------------------ the focal-length estimators stage by stage
+FOCAL_K = {0: 4, 1: 6}
+FOCAL_MAX = {0: 10, 1: 60}
+
+
+def score_image(pose7, f, x, X, sq_thr):
+    """compute_msac_score(Image, ...) of the SIMPLE_PINHOLE camera {f, 0, 0}.  Returns (inlier sum, count, r2, msac): the sum of the
+    inliers' squared residuals WITHOUT the outliers' charge (what the device's scorer returns), the inlier count, every
+    correspondence's squared residual as the loop compared it (NaN behind the camera) and the full MSAC value.  Under
+    ref_lib.reference() the inlier sum and r2 are NaN: the reference returns neither."""
+    x, X, p = _f(x), _f(X), _f(pose7)
+    n = x.shape[0]
+    cnt, isum = u64(0), f64(np.nan)
+    r2 = np.full(max(n, 1), np.nan)
+    fn = lib().orc_score_image
+    fn.restype = f64
+    msac = fn(_p(p), f64(f), _p(x), _p(X), C.c_size_t(n), f64(sq_thr), C.byref(cnt), C.byref(isum), _p(r2))
+    return isum.value, cnt.value, r2[:n], msac
+
+
+def inliers_image(pose7, f, x, X, sq_thr):
+    """get_inliers(Image, ...).  Returns (mask, r2): r2 in the mask's own form (hnormalized divides)."""
+    x, X, p = _f(x), _f(X), _f(pose7)
+    n = x.shape[0]
+    mask = np.zeros(max(n, 1), dtype=np.uint8)
+    r2 = np.full(max(n, 1), np.nan)
+    lib().orc_inliers_image(_p(p), f64(f), _p(x), _p(X), C.c_size_t(n), f64(sq_thr), _p(mask), _p(r2))
+    return mask[:n].astype(bool), r2[:n]
+
+
+def score_shared_focal(pose7, f, x1, x2, sq_thr):
+    """compute_sampson_msac_score of F = K_inv (E K_inv), K_inv = diag(1, 1, f).  Returns (msac, count, r2): r2 the Sampson values."""
+    x1, x2, p = _f(x1), _f(x2), _f(pose7)
+    n = x1.shape[0]
+    cnt = u64(0)
+    r2 = np.full(max(n, 1), np.nan)
+    fn = lib().orc_score_shared_focal
+    fn.restype = f64
+    msac = fn(_p(p), f64(f), _p(x1), _p(x2), C.c_size_t(n), f64(sq_thr), C.byref(cnt), _p(r2))
+    return msac, cnt.value, r2[:n]
+
+
+def inliers_shared_focal(pose7, f, x1, x2, sq_thr):
+    """get_inliers(F, ...) of the same F.  Returns (mask, r2)."""
+    x1, x2, p = _f(x1), _f(x2), _f(pose7)
+    n = x1.shape[0]
+    mask = np.zeros(max(n, 1), dtype=np.uint8)
+    r2 = np.full(max(n, 1), np.nan)
+    lib().orc_inliers_shared_focal(_p(p), f64(f), _p(x1), _p(x2), C.c_size_t(n), f64(sq_thr), _p(mask), _p(r2))
+    return mask[:n].astype(bool), r2[:n]
+
+
+def generate_focal(which, a, b, samples, max_focal=-1.0):
+    """generate_models of the focal estimators on explicit samples (B, K): which 0 = absolute pose with unknown focal length (a (n, 2)
+    about the principal point, b (n, 3), the estimator's filter with max_focal, < 0: none), 1 = shared-focal relative pose (a, b
+    (n, 2)).  Returns (counts (B,), models (B, 10 | 60, 8) [q t f], zero beyond the count), the bearings normalised by the estimator."""
+    K, maxm = FOCAL_K[which], FOCAL_MAX[which]
+    a, b = _f(a), _f(b)
+    s = np.ascontiguousarray(samples, dtype=np.uint64).reshape(-1, K)
+    B = s.shape[0]
+    counts = np.zeros(max(B, 1), dtype=np.uint32)
+    dense = np.zeros((max(B, 1) * maxm, 8))
+    fn = lib().orc_generate_focal
+    fn.restype = C.c_int64
+    total = fn(i32(which), _p(a), _p(b), C.c_size_t(a.shape[0]), _p(s), C.c_size_t(B), f64(max_focal), _p(counts), _p(dense))
+    counts = counts[:B]
+    assert total == int(counts.sum()) and counts.max(initial=0) <= maxm, total
+    models = np.zeros((B, maxm, 8))
+    models[np.arange(maxm)[None, :] < counts[:, None]] = dense[:total]
+    return counts, models
+
+
 class libm_cubes:
     """Context: the six-point solver's cubes through std::pow(d, 3) like the reference's formulas (glibc: the correctly rounded cube
     except for ~8 of 10^4 arguments, one unit in the last place) instead of the oracle's default, the correctly rounded cube the
