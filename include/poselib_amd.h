@@ -360,7 +360,8 @@ int pl_debug_point_stats_group_dev(const pl_device_points *x1, const pl_device_p
  *     host (on the device, without a copy, by the _masked forms below).  Any n up to 2^31 - 1; the work buffers are 24 bytes per
  *     row beyond 8192 rows, none below.
  *   - Out of scope: models in device memory, a producer stream, scored resident problems (pl_problem_create_dev),
- *     scores for the focal-length, 1D-radial and pl_ransac_* entries, half-precision scores. */
+ *     scores for estimate_focal_length and the pl_ransac_* entries, half-precision scores.  (The shared-focal and 1D-radial
+ *     estimators take scores through their own _dev entry points, below.) */
 typedef struct {
     const void *data;   /* device address of the first row's score */
     int64_t stride;     /* ELEMENTS between consecutive rows' scores, >= 1: one column of a wider block is a valid source */
@@ -396,8 +397,9 @@ int pl_estimate_batch_dev_scored(pl_batch_item_dev *items, const pl_device_score
  *     no pinned host mask, no device-to-host copy and no scatter on the host.  The call returns after its streams have been
  *     waited for: the mask is complete and visible to any stream.
  *   - Out of scope: models or stats in device memory (the front-ends finish the model on the host), a producer stream or event,
- *     masks for resident problems (pl_problem_create_dev) and the pl_ransac_* entries, anything for kinds 4 and 5 and
- *     estimate_focal_length, whose refusals stay as they are. */
+ *     masks for resident problems (pl_problem_create_dev) and the pl_ransac_* entries, anything for kinds 4 and 5 of the batch
+ *     and the kind-numbered entry points and for estimate_focal_length, whose refusals stay as they are (single calls of the
+ *     shared-focal and 1D-radial estimators: their own _dev entry points, below). */
 typedef struct {
     uint8_t *data;      /* device address of row 0's flag */
     int64_t stride;     /* BYTES between consecutive rows' flags, >= 1: a bool / uint8 tensor, or one column of a wider byte block */
@@ -416,6 +418,41 @@ int pl_estimate_batch_dev_masked(pl_batch_item_dev *items, const pl_device_score
  * members up to it need one launch, larger ones merge passes through global memory. */
 int pl_debug_rank_scores(const pl_device_scores *scores, const size_t *n, size_t count, uint32_t *order, size_t *kept);
 int pl_debug_rank_tile(size_t max_n);
+/* ---- the two estimators of UNKNOWN cameras from device memory: shared focal length (two views of one uncalibrated camera) and
+ * 1D-radial absolute pose (unknown distortion).  One entry point each covers the plain, the scored and the device-mask form:
+ *   scores (may be NULL)  THE RULE of pl_device_scores: the call is the host entry point's on a[order], b[order], the mask speaks of
+ *                         the caller's rows, n_used = len(order) (n without scores).  The index-order sums in front of the loop -
+ *                         the mean distance from pp; n / sum |x_k| - are taken over the ranked rows in ranked order.
+ *   mask (may be NULL)    pl_device_mask's rule: all n bytes are written, dropped rows and a call whose host form writes no mask give
+ *                         0; `inliers` is then ignored, there is no pinned host mask and no scatter on the host.
+ *   inliers (host, may be NULL), stats, n_used (may be NULL)  as everywhere.
+ * The result - pose, focal length, mask and every field of the stats except `seconds` - is the host entry point's
+ * (pl_estimate_shared_focal_relative_pose, pl_estimate_1D_radial_absolute_pose) on the same values, bit for bit; float32 widens
+ * exactly.  What the host form answers without a launch is answered the same way before any launch: the option validation, null pp /
+ * pose / focal (PL_ERR_INVALID), 1D-radial with n < 5 (default stats, pose untouched; with scores or a device mask the device is
+ * asked first: n_used and the mask's zeros need it).  The descriptors get the points' checks without a device (PL_ERR_INVALID),
+ * then the memory's kind, device and extent.
+ *   - How: the rows become contiguous fp64 blocks on the device (read where they lie when they already are; the ranking's
+ *     permuting copy for a scored call); one single-workgroup launch adds the host's sum in the host's order and returns one small
+ *     record; shared focal then prepares the problem from those blocks, 1D radial writes its block of scaled pixels with the
+ *     ingest kernel - and from there the host forms' own code runs.  No point passes through the host.
+ *   - Out of scope: these two in pl_estimate_batch_dev (kinds 4 and 5 stay refused there), estimate_focal_length. */
+int pl_estimate_shared_focal_relative_pose_dev(const pl_device_points *x1, const pl_device_points *x2,
+                                               const pl_device_scores *scores /* may be NULL */, size_t n, const double *pp,
+                                               const pl_robust_options *opt, pl_camera_pose *pose, double *focal,
+                                               uint8_t *inliers /* host, may be NULL */,
+                                               const pl_device_mask *mask /* may be NULL; then inliers is ignored */,
+                                               pl_ransac_stats *stats, size_t *n_used /* may be NULL */);
+int pl_estimate_1D_radial_absolute_pose_dev(const pl_device_points *points2D, const pl_device_points *points3D,
+                                            const pl_device_scores *scores /* may be NULL */, size_t n, const pl_robust_options *opt,
+                                            pl_camera_pose *pose, uint8_t *inliers /* host, may be NULL */,
+                                            const pl_device_mask *mask /* may be NULL; then inliers is ignored */, pl_ransac_stats *stats,
+                                            size_t *n_used /* may be NULL */);
+/* Diagnostic: the two reductions alone.  x2 != NULL: the mean distance of both sets from (cx, cy), correspondence after
+ * correspondence, over sqrt(2) * n (shared focal); x2 == NULL: n / sum_k sqrt(0.0 + x_k^2 + y_k^2) of x1 in index order (1D
+ * radial; cx, cy unused).  out[0] = the scale, out[1] = max |coordinate * scale| (radial; a NaN propagates) or 0. */
+int pl_debug_point_stats_about_dev(const pl_device_points *x1, const pl_device_points *x2 /* NULL: radial */, size_t n, double cx,
+                                   double cy, double *out /* 2 */);
 /* What the calling thread's last pl_estimate_batch / pl_estimate_batch_devices / pl_estimate_batch_dev / pl_ransac_batch did with its items.  Items in
  * lock-step groups share one launch sequence (the advertised rate); `solo` items were outside the group path from the start
  * (options or sizes a group does not take - see pl_batch_item / pl_ransac_batch) and `fallback` items were handed back by their

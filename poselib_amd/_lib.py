@@ -220,6 +220,10 @@ def _declare(L):
         "pl_estimate_batch_dev_masked": (cint, [P(BatchItemDev), P(DeviceScores), P(DeviceMask), P(sz), sz, cint]),
         "pl_debug_rank_scores": (cint, [P(DeviceScores), P(sz), sz, vp, P(sz)]),
         "pl_debug_rank_tile": (cint, [sz]),
+        "pl_estimate_shared_focal_relative_pose_dev": (cint, [dpts, dpts, P(DeviceScores), sz, vp, opt, pose, P(dbl), vp, P(DeviceMask), stats,
+                                                               P(sz)]),
+        "pl_estimate_1D_radial_absolute_pose_dev": (cint, [dpts, dpts, P(DeviceScores), sz, opt, pose, vp, P(DeviceMask), stats, P(sz)]),
+        "pl_debug_point_stats_about_dev": (cint, [dpts, dpts, sz, dbl, dbl, vp]),
         "pl_last_batch_report": (None, [P(BatchReport)]),
         "pl_ransac_batch": (cint, [P(RansacItem), sz, cint, cint]),
         "pl_undistort_points": (cint, [cam, vp, sz, vp]),
@@ -313,6 +317,7 @@ EXPORTED_SYMBOLS = [
     "pl_debug_sampler_shape", "pl_debug_sample_positions", "pl_estimate_batch_dev", "pl_debug_point_stats_group_dev",
     "pl_estimate_dev_scored", "pl_estimate_batch_dev_scored", "pl_debug_rank_scores", "pl_debug_rank_tile",
     "pl_undistort_points_dev", "pl_undistort_points_batch_dev", "pl_estimate_dev_masked", "pl_estimate_batch_dev_masked",
-    # (pl_estimate_1D_radial_absolute_pose and pl_ransac_1D_radial_pnp carry the reference's capital D: declared above, exported by the
+    "pl_estimate_shared_focal_relative_pose_dev", "pl_debug_point_stats_about_dev",
+    # (pl_estimate_1D_radial_absolute_pose, its _dev form and pl_ransac_1D_radial_pnp carry the reference's capital D: declared above, exported by the
     # library, but outside the lower-case pattern tests/test_cabi_surface.py lists the header's symbols with)
 ]

@@ -1074,10 +1074,38 @@ def ransac_1D_radial_pnp(x, X, opt=None, initial_pose=None):
     return _ransac("pl_ransac_1D_radial_pnp", KIND_RAD1D, x, X, 3, opt, initial_pose)
 
 
-def estimate_1D_radial_absolute_pose(points2D, points3D, opt=None, initial_pose=None):
+def _uncalibrated_device_args(pts, scores, min_score, inliers_out):
+    """the optional arguments the two _dev entry points of unknown cameras share: (scores, mask, n_used) as ctypes arguments, the
+    objects that own their memory"""
+    sd, keep = _device_scores(scores, pts.n, min_score) if scores is not None else (None, None)
+    md, keep_mask = _device_mask(inliers_out, pts.n) if inliers_out is not None else (None, None)
+    used = C.c_size_t(0)
+    return (None if sd is None else C.byref(sd), None if md is None else C.byref(md), used), (sd, md, keep, keep_mask)
+
+
+def estimate_1D_radial_absolute_pose(points2D, points3D, opt=None, initial_pose=None, scores=None, min_score=None, inliers_out=None):
     """poselib.estimate_1D_radial_absolute_pose(points2D, points3D, opt, initial_pose) -> (CameraPose, info): absolute pose of a
-    camera with unknown radial distortion from pixels relative to the centre of distortion; the pose has t[2] = 0"""
-    return _ransac("pl_estimate_1D_radial_absolute_pose", KIND_RAD1D, points2D, points3D, 3, opt, initial_pose)
+    camera with unknown radial distortion from pixels relative to the centre of distortion; the pose has t[2] = 0.
+    Points on the GPU (float32 / float64, strided rows) are read where they lie; scores / min_score / inliers_out as
+    estimate_absolute_pose."""
+    on_device = _on_device(points2D) or _on_device(points3D)
+    _check_scores_args(on_device, scores, min_score)
+    _check_mask_args(on_device, inliers_out)
+    if scores is not None and not _on_device(scores):
+        return _scored_host(lambda a, b: estimate_1D_radial_absolute_pose(a, b, opt, initial_pose), points2D, points3D, scores, min_score)
+    if not on_device:
+        return _ransac("pl_estimate_1D_radial_absolute_pose", KIND_RAD1D, points2D, points3D, 3, opt, initial_pose)
+    pts = _Points(points2D, points3D, 2, 3)
+    o = _robust_options(opt, KIND_RAD1D, initial_pose is not None)
+    n = pts.n
+    inl = np.zeros(max(n, 1), dtype=np.uint8)
+    st = L.RansacStats()
+    pose = _cpose(initial_pose if initial_pose is not None else CameraPose())
+    (sd, md, used), keep = _uncalibrated_device_args(pts, scores, min_score, inliers_out)
+    L.check(L.lib().pl_estimate_1D_radial_absolute_pose_dev(pts.a, pts.b, sd, C.c_size_t(n), C.byref(o), C.byref(pose), _ptr(inl), md,
+                                                            C.byref(st), C.byref(used)))
+    del keep
+    return _pypose(pose), _info(st, inl[:n] if inliers_out is None else inliers_out, n if scores is None else int(used.value))
 
 
 def ransac_pnpf(x, X, opt=None):
@@ -1122,19 +1150,37 @@ def ransac_shared_focal_relpose(x1, x2, opt=None, initial_pair=None):
     return _shared_focal_pair(pose, focal.value, (0.0, 0.0)), _info(st, inl[:n])
 
 
-def estimate_shared_focal_relative_pose(points2D_1, points2D_2, pp, opt=None, initial_pair=None):
-    """robust.h:84-90 estimate_shared_focal_relative_pose: pixel coordinates, principal point pp.  Returns (ImagePair, info)."""
-    x1, x2 = _pts(points2D_1, 2), _pts(points2D_2, 2)
+def estimate_shared_focal_relative_pose(points2D_1, points2D_2, pp, opt=None, initial_pair=None, scores=None, min_score=None,
+                                        inliers_out=None):
+    """robust.h:84-90 estimate_shared_focal_relative_pose: pixel coordinates, principal point pp.  Returns (ImagePair, info).
+    Points on the GPU (float32 / float64, strided rows) are read where they lie; scores / min_score / inliers_out as
+    estimate_absolute_pose."""
+    on_device = _on_device(points2D_1) or _on_device(points2D_2)
+    _check_scores_args(on_device, scores, min_score)
+    _check_mask_args(on_device, inliers_out)
+    if scores is not None and not _on_device(scores):
+        return _scored_host(lambda a, b: estimate_shared_focal_relative_pose(a, b, pp, opt, initial_pair), points2D_1, points2D_2,
+                            scores, min_score)
+    pts = _Points(points2D_1, points2D_2, 2, 2)
     o = _robust_options(opt, KIND_REL, initial_pair is not None)
-    n = x1.shape[0]
+    n = pts.n
     inl = np.zeros(max(n, 1), dtype=np.uint8)
     st = L.RansacStats()
     pose = _cpose(initial_pair.pose if initial_pair is not None else CameraPose())
     focal = C.c_double(initial_pair.camera1.focal() if initial_pair is not None else 1.0)
     ppa = np.ascontiguousarray(pp, dtype=np.float64)
-    L.check(L.lib().pl_estimate_shared_focal_relative_pose(_ptr(x1), _ptr(x2), C.c_size_t(n), _ptr(ppa), C.byref(o), C.byref(pose),
-                                                           C.byref(focal), _ptr(inl), C.byref(st)))
-    return _shared_focal_pair(pose, focal.value, ppa), _info(st, inl[:n])
+    if ppa.shape != (2,):
+        raise ValueError("pp: expected two numbers")
+    if not pts.on_device:
+        L.check(L.lib().pl_estimate_shared_focal_relative_pose(pts.a, pts.b, C.c_size_t(n), _ptr(ppa), C.byref(o), C.byref(pose),
+                                                               C.byref(focal), _ptr(inl), C.byref(st)))
+        return _shared_focal_pair(pose, focal.value, ppa), _info(st, inl[:n])
+    (sd, md, used), keep = _uncalibrated_device_args(pts, scores, min_score, inliers_out)
+    L.check(L.lib().pl_estimate_shared_focal_relative_pose_dev(pts.a, pts.b, sd, C.c_size_t(n), _ptr(ppa), C.byref(o), C.byref(pose),
+                                                               C.byref(focal), _ptr(inl), md, C.byref(st), C.byref(used)))
+    del keep
+    return (_shared_focal_pair(pose, focal.value, ppa),
+            _info(st, inl[:n] if inliers_out is None else inliers_out, n if scores is None else int(used.value)))
 
 
 def refine_shared_focal_relpose(x1, x2, pair, bundle=None):
@@ -1721,6 +1767,23 @@ def point_stats_dev(x1, x2, centroid=True):
     L.check(L.lib().pl_debug_point_stats_dev(pts.a, pts.b, C.c_size_t(pts.n), int(bool(centroid)), _ptr(out)))
     return {"c1": out[0:2].copy(), "c2": out[2:4].copy(), "scale": float(out[4]), "absmax_normalised": float(out[5]),
             "absmax_first": float(out[6])}
+
+
+def point_stats_about_dev(x1, x2=None, centre=(0.0, 0.0)):
+    """Diagnostic (pl_debug_point_stats_about_dev): the reduction the device forms of the two estimators of unknown cameras read
+    back, for (N, 2) GPU tensors.  x2 given: the mean distance of both sets from `centre` over sqrt(2) (shared focal); x2 None:
+    n / sum |x_k| of x1 (1D radial).  Returns {"scale", "absmax"} (absmax: max |coordinate * scale|, radial only)."""
+    if not _on_device(x1) or (x2 is not None and not _on_device(x2)):
+        raise ValueError("point_stats_about_dev takes GPU tensors")
+    d1, n, keep1 = _device_points(x1, 2)
+    d2, n2, keep2 = _device_points(x2, 2) if x2 is not None else (None, n, None)
+    if n2 != n:
+        raise ValueError(f"the point sets differ in length ({n} and {n2})")
+    out = np.zeros(2)
+    L.check(L.lib().pl_debug_point_stats_about_dev(C.byref(d1), None if d2 is None else C.byref(d2), C.c_size_t(n), float(centre[0]),
+                                                   float(centre[1]), _ptr(out)))
+    del keep1, keep2
+    return {"scale": float(out[0]), "absmax": float(out[1])}
 
 
 def point_stats_group_dev(pairs, centroid=True):

@@ -4190,6 +4190,36 @@ int pl_estimate_absolute_pose(const double *points2D, const double *points3D, si
     return absolute_pose_run(c, fe, points2D, points3D, n, nullptr, opt, camera, pose, inliers, stats);
 }
 
+// The 1D-radial front-end behind its scale and the block of scaled pixels (the host form below and
+// pl_estimate_1D_radial_absolute_pose_dev): max_error and bundle.loss_scale follow the pixels, the loop, the gated bundle; the problem is
+// freed
+int radial1d_run(Context *c, pl_problem *p, double scale, const pl_robust_options *opt, pl_camera_pose *pose, uint8_t *inliers,
+                 pl_ransac_stats *st) {
+    pl_robust_options so = *opt;
+    so.max_error *= scale;
+    so.bundle.loss_scale *= scale;
+    double rec[kModelStride];
+    if (so.ransac.score_initial_model)
+        record_from_pose(pose, false, rec);
+    else
+        identity_record(EST_RAD1D, rec);
+    int rc = ransac_core(c, p, &so, rec, inliers, st);
+    if (rc == PL_OK && st->num_inliers > 5) {
+        CameraParams none;
+        std::memset(&none, 0, sizeof(none));
+        none.model_id = CAM_NULL;
+        double out[kModelStride];
+        rc = final_refine(c, p, rec, to_lm(so.bundle), none, 1.0, out, nullptr);
+        if (rc == PL_OK)
+            std::memcpy(rec, out, sizeof(out));
+    }
+    free_problem(p);
+    if (rc != PL_OK)
+        return rc;
+    pose_from_record(rec, pose);
+    return PL_OK;
+}
+
 // robust.cc:889-934: absolute pose of a 1D-radial camera from centred pixels.  The pixels are multiplied by n / sum |x_k| (summed in
 // index order) on the host as they are copied into the problem's block (one pass for the sum, the product in make_problem's copy;
 // the block is the resident-problem kind, uploaded once: its cost next to the pinned staging path has not been measured);
@@ -4217,33 +4247,11 @@ int pl_estimate_1D_radial_absolute_pose(const double *points2D, const double *po
     for (size_t k = 0; k < n; ++k)
         scale += std::sqrt(0.0 + points2D[2 * k] * points2D[2 * k] + points2D[2 * k + 1] * points2D[2 * k + 1]);
     scale = static_cast<double>(n) / scale;
-    pl_robust_options so = *opt;
-    so.max_error *= scale;
-    so.bundle.loss_scale *= scale;
     pl_problem p;
     rc = make_problem(c, EST_RAD1D, points2D, points3D, n, &p, scale); // (the pixels are multiplied as they are copied)
     if (rc != PL_OK)
         return rc;
-    double rec[kModelStride];
-    if (so.ransac.score_initial_model)
-        record_from_pose(pose, false, rec);
-    else
-        identity_record(EST_RAD1D, rec);
-    rc = ransac_core(c, &p, &so, rec, inliers, st);
-    if (rc == PL_OK && st->num_inliers > 5) {
-        CameraParams none;
-        std::memset(&none, 0, sizeof(none));
-        none.model_id = CAM_NULL;
-        double out[kModelStride];
-        rc = final_refine(c, &p, rec, to_lm(so.bundle), none, 1.0, out, nullptr);
-        if (rc == PL_OK)
-            std::memcpy(rec, out, sizeof(out));
-    }
-    free_problem(&p);
-    if (rc != PL_OK)
-        return rc;
-    pose_from_record(rec, pose);
-    return PL_OK;
+    return radial1d_run(c, &p, scale, opt, pose, inliers, st);
 }
 
 // relative pose, fundamental matrix, homography: validate, front_begin, the loop, the gated bundle, front_finish
@@ -4300,6 +4308,30 @@ int pl_estimate_relative_pose(const double *x1, const double *x2, size_t n, cons
     return estimate_two_view(tangent ? EST_RELT : EST_REL, x1, x2, n, camera1, camera2, opt, pose, inliers, stats ? stats : &local);
 }
 
+// The shared-focal front-end behind its normalisation (robust.cc:386-421; the host form below and
+// pl_estimate_shared_focal_relative_pose_dev, whose rows are already on the device: resident, x1 / x2 null)
+int shared_focal_run(Context *c, const double *x1, const double *x2, size_t n, const PrepareArgs &prep, double scale, bool resident,
+                     const pl_robust_options *opt, pl_camera_pose *pose, double *focal, uint8_t *inliers, pl_ransac_stats *st) {
+    pl_robust_options scaled = *opt;
+    scaled.max_error /= scale;
+    scaled.bundle.loss_scale /= scale;
+    double f = *focal;
+    if (opt->ransac.score_initial_model) // :392-397
+        f = f / scale;
+    pl_problem p;
+    int rc = make_problem_prepared(c, EST_FUND, x1, x2, n, prep, &p, resident, /*lm_only=*/true);
+    if (rc != PL_OK)
+        return rc;
+    rc = run_shared_focal(c, &p, &scaled, pose, &f, inliers, st);
+    if (rc == PL_OK && st->num_inliers > front_min_inliers(kFrontSharedFocal)) // :401-415: refine_shared_focal_relpose over the inliers (c->mask: the device mask)
+        rc = refine_shared_focal(c, &p, to_lm(scaled.bundle), c->mask.as<uint8_t>(), pose, &f, nullptr);
+    free_problem(&p);
+    if (rc != PL_OK)
+        return rc;
+    *focal = f * scale; // :417 (the caller's cameras: SIMPLE_PINHOLE {focal, pp[0], pp[1]}, :418-421)
+    return PL_OK;
+}
+
 int pl_estimate_shared_focal_relative_pose(const double *x1, const double *x2, size_t n, const double *pp, const pl_robust_options *opt,
                                            pl_camera_pose *pose, double *focal, uint8_t *inliers, pl_ransac_stats *stats) {
     if (!pp || !pose || !focal)
@@ -4316,24 +4348,7 @@ int pl_estimate_shared_focal_relative_pose(const double *x1, const double *x2, s
     // robust.cc:373-390
     PrepareArgs prep;
     const double scale = normalization_about(x1, x2, n, pp[0], pp[1], prep);
-    pl_robust_options scaled = *opt;
-    scaled.max_error /= scale;
-    scaled.bundle.loss_scale /= scale;
-    double f = *focal;
-    if (opt->ransac.score_initial_model) // :392-397
-        f = f / scale;
-    pl_problem p;
-    rc = make_problem_prepared(c, EST_FUND, x1, x2, n, prep, &p, false, /*lm_only=*/true);
-    if (rc != PL_OK)
-        return rc;
-    rc = run_shared_focal(c, &p, &scaled, pose, &f, inliers, st);
-    if (rc == PL_OK && st->num_inliers > front_min_inliers(kFrontSharedFocal)) // :401-415: refine_shared_focal_relpose over the inliers (c->mask: the device mask)
-        rc = refine_shared_focal(c, &p, to_lm(scaled.bundle), c->mask.as<uint8_t>(), pose, &f, nullptr);
-    free_problem(&p);
-    if (rc != PL_OK)
-        return rc;
-    *focal = f * scale; // :417 (the caller's cameras: SIMPLE_PINHOLE {focal, pp[0], pp[1]}, :418-421)
-    return PL_OK;
+    return shared_focal_run(c, x1, x2, n, prep, scale, /*resident=*/false, opt, pose, focal, inliers, st);
 }
 
 int pl_estimate_fundamental(const double *x1, const double *x2, size_t n, const pl_robust_options *opt, double *F,

@@ -202,7 +202,8 @@ int open_device_points(const pl_device_points *a, int cols_a, const pl_device_po
     return rc;
 }
 
-// the fp64 AoS blocks of both sets: c->raw_src_a / raw_src_b (k_prepare's input) - the caller's memory where it already is one
+// the fp64 AoS blocks of both sets: c->raw_src_a / raw_src_b (k_prepare's input) - the caller's memory where it already is one.
+// b == null (the diagnostic of the radial reduction): the first set alone
 int ingest_points(Context *c, const pl_device_points *a, const pl_device_points *b, size_t n) {
     c->raw_src_a = c->raw_src_b = nullptr;
     if (n == 0)
@@ -212,13 +213,13 @@ int ingest_points(Context *c, const pl_device_points *a, const pl_device_points 
         HIP_TRY(c->raw_a.ensure(sizeof(double) * a->cols * n));
         out_a = c->raw_a.as<double>();
     }
-    if (!reads_in_place(b)) {
+    if (b && !reads_in_place(b)) {
         HIP_TRY(c->raw_b.ensure(sizeof(double) * b->cols * n));
         out_b = c->raw_b.as<double>();
     }
-    HIP_TRY(launch_ingest(ingest_src(a), ingest_src(b), (uint32_t)n, out_a, out_b, c->stream));
+    HIP_TRY(launch_ingest(ingest_src(a), ingest_src(b ? b : a), (uint32_t)n, out_a, out_b, c->stream));
     c->raw_src_a = out_a ? out_a : static_cast<const double *>(a->data);
-    c->raw_src_b = out_b ? out_b : static_cast<const double *>(b->data);
+    c->raw_src_b = out_b ? out_b : b ? static_cast<const double *>(b->data) : nullptr;
     return PL_OK;
 }
 

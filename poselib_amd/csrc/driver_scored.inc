@@ -317,3 +317,245 @@ int pl_estimate_dev_masked(int kind, const pl_device_points *a, const pl_device_
         *n_used = it.n;
     return rc;
 }
+
+// ---------------------------------------------------------------------------- the two estimators of unknown cameras from device memory
+// pl_estimate_shared_focal_relative_pose_dev and pl_estimate_1D_radial_absolute_pose_dev: plain, scored and device-mask form of
+// each in one entry point.  What their host forms read of the caller's points in front of the loop is one reduction each
+// (normalization_about; n / sum |x_k|): k_point_stats makes it over the fp64 rows on the device - the ingested blocks, or the
+// permuted blocks a ranking left - in the host's order, one record comes back, and from there the host forms' own code runs
+// (shared_focal_run, radial1d_run).  No point passes through the host.
+namespace {
+
+// the checks that need no device, then - behind the context - those that ask the runtime; scores and mask may be null
+int uncal_check_plain(const pl_device_points *a, int cols_a, const pl_device_points *b, int cols_b, const pl_device_scores *scores,
+                      const pl_device_mask *mask, size_t n) {
+    int rc = check_points_plain(a, n, cols_a);
+    if (rc == PL_OK)
+        rc = check_points_plain(b, n, cols_b);
+    if (rc == PL_OK && scores)
+        rc = check_scores_plain(scores, n);
+    if (rc == PL_OK && mask)
+        rc = check_mask_plain(mask, n);
+    return rc;
+}
+int uncal_check_device(const Context *c, const pl_device_points *a, const pl_device_points *b, const pl_device_scores *scores,
+                       const pl_device_mask *mask, size_t n) {
+    int rc = check_points_device(c, a, n);
+    if (rc == PL_OK)
+        rc = check_points_device(c, b, n);
+    if (rc == PL_OK && scores)
+        rc = check_scores_device(c, scores, n);
+    if (rc == PL_OK && mask)
+        rc = check_mask_device(c, mask, n);
+    return rc;
+}
+
+// The rows a call runs on, as contiguous fp64 blocks behind c->raw_src_a / raw_src_b: with scores the kept rows in ranked order
+// (Ranking), otherwise all of them (ingest_points).  A device mask is zero-filled first, on the same stream; its destination -
+// through the ranking's permutation for a scored call - is `dest`.
+struct UncalRows {
+    std::vector<RankMember> m = std::vector<RankMember>(1);
+    Ranking ranking;
+    size_t used = 0;
+    MaskDest dest = {nullptr, 0, nullptr};
+    std::vector<uint8_t> ranked_mask; // a scored call's host mask over the kept rows
+    bool scored = false;
+
+    int stage(Context *c, const pl_device_points *a, const pl_device_points *b, const pl_device_scores *scores, const pl_device_mask *mask,
+              size_t n) {
+        scored = scores != nullptr;
+        if (mask && n) {
+            const MaskFillArgs fill = {mask->data, mask->stride, (uint32_t)n, 0};
+            const int rc = enqueue_mask_fill(c, &fill, 1);
+            if (rc != PL_OK)
+                return rc;
+            dest.data = mask->data, dest.stride = mask->stride;
+        }
+        if (!scores) {
+            used = n;
+            return ingest_points(c, a, b, n);
+        }
+        m[0].scores = scores, m[0].n = n, m[0].a = a, m[0].b = b;
+        if (n) {
+            const int rc = ranking.run(c, m, /*grouped=*/false);
+            if (rc != PL_OK)
+                return rc;
+        }
+        used = m[0].kept;
+        c->raw_src_a = m[0].out_a, c->raw_src_b = m[0].out_b;
+        if (dest.data)
+            dest.order = c->rank_order.as<uint32_t>() + m[0].order_at;
+        ranked_mask.assign(std::max<size_t>(used, 1), 0);
+        return PL_OK;
+    }
+    const MaskDest *mask_dest() const { return dest.data ? &dest : nullptr; }
+    // where the run writes its host mask: nowhere with a device mask, the caller's array, or - scored - the array scatter() reads
+    uint8_t *run_mask(uint8_t *inliers) { return dest.data || !inliers ? nullptr : scored ? ranked_mask.data() : inliers; }
+    void finish(Context *c, uint8_t *inliers, size_t *n_used) {
+        if (scored && inliers && !dest.data)
+            ranking.scatter(m[0], ranked_mask.data(), inliers);
+        if (n_used)
+            *n_used = used;
+        c->raw_src_a = c->raw_src_b = nullptr; // (the caller's memory is not read after the call)
+    }
+};
+struct MaskDestScope { // (a run that ends early leaves nothing set for the thread's next call)
+    explicit MaskDestScope(const MaskDest *d) { g_mask_dest = d; }
+    ~MaskDestScope() { g_mask_dest = nullptr; }
+};
+
+// k_point_stats in one of the two modes of unknown cameras over c->raw_src_a / raw_src_b (n > 0)
+int uncal_point_stats(Context *c, size_t n, int norm, double cx, double cy, PointStatsRecord *rec) {
+    PointStatsArgs args;
+    std::memset(&args, 0, sizeof(args));
+    args.norm = norm;
+    args.cx1 = args.cx2 = cx, args.cy1 = args.cy2 = cy;
+    return run_point_stats(c, n, args, rec);
+}
+
+} // namespace
+
+int pl_debug_point_stats_about_dev(const pl_device_points *x1, const pl_device_points *x2, size_t n, double cx, double cy, double *out) {
+    if (!out)
+        return fail(PL_ERR_INVALID, "output pointer is null");
+    int rc = check_points_plain(x1, n, 2);
+    if (rc == PL_OK && x2)
+        rc = check_points_plain(x2, n, 2);
+    Context *c = nullptr;
+    if (rc == PL_OK)
+        rc = get_context(&c);
+    if (rc == PL_OK)
+        rc = check_points_device(c, x1, n);
+    if (rc == PL_OK && x2)
+        rc = check_points_device(c, x2, n);
+    if (rc != PL_OK)
+        return rc;
+    out[0] = out[1] = 0.0;
+    if (n == 0)
+        return PL_OK;
+    rc = ingest_points(c, x1, x2, n);
+    PointStatsRecord rec;
+    if (rc == PL_OK)
+        rc = uncal_point_stats(c, n, x2 ? 2 : 3, cx, cy, &rec);
+    c->raw_src_a = c->raw_src_b = nullptr;
+    if (rc != PL_OK)
+        return rc;
+    out[0] = rec.scale, out[1] = rec.absmax;
+    return PL_OK;
+}
+
+int pl_estimate_shared_focal_relative_pose_dev(const pl_device_points *x1, const pl_device_points *x2, const pl_device_scores *scores,
+                                               size_t n, const double *pp, const pl_robust_options *opt, pl_camera_pose *pose, double *focal,
+                                               uint8_t *inliers, const pl_device_mask *mask, pl_ransac_stats *stats, size_t *n_used) {
+    if (n_used)
+        *n_used = 0;
+    if (!pp || !pose || !focal)
+        return fail(PL_ERR_INVALID, "null argument");
+    int rc = validate_options(opt);
+    if (rc == PL_OK)
+        rc = uncal_check_plain(x1, 2, x2, 2, scores, mask, n);
+    Context *c = nullptr;
+    if (rc == PL_OK)
+        rc = get_context(&c);
+    if (rc == PL_OK)
+        rc = uncal_check_device(c, x1, x2, scores, mask, n);
+    if (rc != PL_OK)
+        return rc;
+    pl_ransac_stats local;
+    pl_ransac_stats *st = stats ? stats : &local;
+    UncalRows rows;
+    rc = rows.stage(c, x1, x2, scores, mask, n);
+    if (rc != PL_OK)
+        return rc;
+    // normalization_about's sum, over the rows the run uses and in their order
+    double scale = 0.0;
+    if (rows.used) {
+        PointStatsRecord rec = {};
+        rc = uncal_point_stats(c, rows.used, 2, pp[0], pp[1], &rec);
+        scale = rec.scale;
+    } else {
+        scale = mean_distance_scale(0.0, 0); // (no rows: what the host's empty loop leaves)
+    }
+    if (rc == PL_OK) {
+        PrepareArgs prep;
+        prepare_about(pp[0], pp[1], scale, prep);
+        MaskDestScope scope(rows.mask_dest());
+        rc = shared_focal_run(c, nullptr, nullptr, rows.used, prep, scale, /*resident=*/true, opt, pose, focal, rows.run_mask(inliers), st);
+    }
+    rows.finish(c, rc == PL_OK ? inliers : nullptr, rc == PL_OK ? n_used : nullptr);
+    return rc;
+}
+
+int pl_estimate_1D_radial_absolute_pose_dev(const pl_device_points *points2D, const pl_device_points *points3D, const pl_device_scores *scores,
+                                            size_t n, const pl_robust_options *opt, pl_camera_pose *pose, uint8_t *inliers,
+                                            const pl_device_mask *mask, pl_ransac_stats *stats, size_t *n_used) {
+    if (n_used)
+        *n_used = 0;
+    int rc = validate_options(opt);
+    if (rc != PL_OK)
+        return rc;
+    if (!pose)
+        return fail(PL_ERR_INVALID, "points / pose pointer is null");
+    rc = uncal_check_plain(points2D, 2, points3D, 3, scores, mask, n);
+    if (rc != PL_OK)
+        return rc;
+    pl_ransac_stats local;
+    pl_ransac_stats *st = stats ? stats : &local;
+    if (n < 5 && !scores && !mask) { // (the host form: default stats, nothing is read - and here no device is asked for)
+        std::memset(st, 0, sizeof(*st));
+        return PL_OK;
+    }
+    Context *c = nullptr;
+    rc = get_context(&c);
+    if (rc == PL_OK)
+        rc = uncal_check_device(c, points2D, points3D, scores, mask, n);
+    if (rc != PL_OK)
+        return rc;
+    UncalRows rows;
+    rc = rows.stage(c, points2D, points3D, scores, mask, n);
+    if (rc != PL_OK)
+        return rc;
+    const size_t m = rows.used;
+    if (m < 5) { // too few rows (left): default stats, the pose untouched; a device mask keeps the zeros of its fill
+        std::memset(st, 0, sizeof(*st));
+        const hipError_t e = mask ? wait_stream(c) : hipSuccess;
+        rows.finish(c, inliers, n_used);
+        return e == hipSuccess ? PL_OK : fail(PL_ERR_HIP, "the fill of the device mask", e);
+    }
+    // n / sum |x_k| in index order and max |x * scale| of the block (make_problem's bound), then the block itself: the pixels times the
+    // scale, the 3-D points as they are
+    PointStatsRecord rec = {};
+    rc = uncal_point_stats(c, m, 3, 0.0, 0.0, &rec);
+    const double scale = rec.scale;
+    const int nd = point_doubles(EST_RAD1D);
+    hipError_t e = hipSuccess;
+    if (rc == PL_OK)
+        e = c->pts_arena.ensure(sizeof(double) * nd * m);
+    if (rc == PL_OK && e == hipSuccess) {
+        const pl_device_points a = ranked_points(c->raw_src_a, 2, m), b = ranked_points(c->raw_src_b, 3, m); // (contiguous fp64, whatever came in)
+        e = launch_ingest_soa(ingest_src(&a), ingest_src(&b), (uint32_t)m, 0, c->pts_arena.as<double>(), nullptr, c->stream, scale);
+    }
+    if (rc == PL_OK && e != hipSuccess)
+        rc = fail(PL_ERR_HIP, "the block of scaled pixels", e);
+    if (rc != PL_OK) {
+        rows.finish(c, nullptr, nullptr);
+        return rc;
+    }
+    pl_problem p;
+    p.kind = EST_RAD1D;
+    p.device = c->device;
+    p.n = (uint32_t)m;
+    p.d_pts = c->pts_arena.as<double>();
+    p.borrowed = true;
+    std::memset(&p.ps, 0, sizeof(p.ps));
+    p.ps.n = (uint32_t)m;
+    for (int d = 0; d < nd; ++d)
+        p.ps.a[d] = p.d_pts + (size_t)d * m;
+    p.ps.xy_absmax = std::nextafter((float)rec.absmax, std::numeric_limits<float>::infinity());
+    {
+        MaskDestScope scope(rows.mask_dest());
+        rc = radial1d_run(c, &p, scale, opt, pose, rows.run_mask(inliers), st);
+    }
+    rows.finish(c, rc == PL_OK ? inliers : nullptr, rc == PL_OK ? n_used : nullptr);
+    return rc;
+}

@@ -215,12 +215,16 @@ int run_shared_focal(Context *c, const pl_problem *p, const pl_robust_options *o
         pose->t[i] = best.t[i];
     *focal = best.f;
     // get_inliers(F, ...) (ransac.cc:194-200)
+    // (g_mask_dest, pl_estimate_shared_focal_relative_pose_dev with a device mask: the launch writes the caller's device memory
+    // itself - no pinned copy, `inliers` is ignored)
+    const MaskDest *dst = g_mask_dest;
     HIP_TRY(c->mask.ensure(std::max<uint32_t>(n, 1u)));
-    HIP_TRY(c->h_mask.ensure(std::max<uint32_t>(n, 1u)));
+    if (!dst)
+        HIP_TRY(c->h_mask.ensure(std::max<uint32_t>(n, 1u)));
     if (n) {
-        HIP_TRY(launch_sfocal_mask(p->ps.a, n, best, be.thr2, c->mask.as<uint8_t>(), c->h_mask.dev<uint8_t>(), c->stream));
+        HIP_TRY(launch_sfocal_mask(p->ps.a, n, best, be.thr2, c->mask.as<uint8_t>(), dst ? nullptr : c->h_mask.dev<uint8_t>(), c->stream, dst));
         HIP_TRY(hipStreamSynchronize(c->stream));
-        if (inliers)
+        if (inliers && !dst)
             std::memcpy(inliers, c->h_mask.p, n);
     }
     st->seconds = now_s() - t_start;
@@ -253,6 +257,17 @@ int refine_shared_focal(Context *c, const pl_problem *p, const LMOptions &opt, c
 
 // robust.cc:377-386: the image points relative to the principal point, then normalize_points(scale only, shared): the order-dependent
 // reduction (mean distance) summed here like the reference, the per-point part (subtract, divide) applied by k_prepare
+// the mean distance from the sum of 2 n distances.  One out-of-line function for the host form and the device form's call without
+// rows (n == 0: 0.0 / 0.0), so that both get the quotient - its NaN's sign bit included - from the same instruction
+__attribute__((noinline)) double mean_distance_scale(double sum, size_t n) { return sum / (std::sqrt(2) * n); }
+// (the per-point part, for a scale that is already known: the device form reads it back from k_point_stats)
+void prepare_about(double ppx, double ppy, double scale, PrepareArgs &pa) {
+    std::memset(&pa, 0, sizeof(pa));
+    pa.mode = 2;
+    pa.centred = 1;
+    pa.c1x = ppx, pa.c1y = ppy, pa.c2x = ppx, pa.c2y = ppy;
+    pa.scale = scale;
+}
 double normalization_about(const double *x1, const double *x2, size_t n, double ppx, double ppy, PrepareArgs &pa) {
     double scale = 0.0;
     for (size_t k = 0; k < n; ++k) {
@@ -260,11 +275,7 @@ double normalization_about(const double *x1, const double *x2, size_t n, double 
         scale += std::sqrt(a0 * a0 + a1 * a1);
         scale += std::sqrt(b0 * b0 + b1 * b1);
     }
-    scale /= std::sqrt(2) * n;
-    std::memset(&pa, 0, sizeof(pa));
-    pa.mode = 2;
-    pa.centred = 1;
-    pa.c1x = ppx, pa.c1y = ppy, pa.c2x = ppx, pa.c2y = ppy;
-    pa.scale = scale;
+    scale = mean_distance_scale(scale, n);
+    prepare_about(ppx, ppy, scale, pa);
     return scale;
 }

@@ -6,7 +6,9 @@
 //   k_ingest_soa    the same sources -> the SoA block of a resident problem, with make_problem's max |coordinate|
 //   k_point_stats   what the front-ends compute over the raw points on the host: the two ORDER-DEPENDENT reductions of the
 //                   homography / fundamental normalisation (utils.cc:584-644: centroid sums, then the mean distance), added
-//                   strictly in index order by one wavefront, and the order-free maxima behind the pre-filters' bound
+//                   strictly in index order by one wavefront, and the order-free maxima behind the pre-filters' bound; the same
+//                   adder for the two front-ends of unknown cameras: the mean distance from a GIVEN centre (shared focal,
+//                   normalization_about) and n / sum |x_k| of one point set (1D radial, with max |x * scale| of its block)
 //   k_ingest_ranked, k_ingest_ranked_g   k_ingest through a permutation: the rows an item's scores keep, in descending score (rank.hip)
 //   k_ingest_g, k_point_stats_g   the two for a lock-step group of problems (pl_estimate_batch_dev): the member is a grid
 //                   dimension, its arguments come from a device-visible table; the bodies are those of the single forms
@@ -95,15 +97,17 @@ __device__ __forceinline__ void ingest_ranked_body(const IngestRankedArgs &in) {
 __global__ __launch_bounds__(256) void k_ingest_ranked(IngestRankedArgs in) { ingest_ranked_body(in); }
 __global__ __launch_bounds__(256) void k_ingest_ranked_g(const IngestRankedArgs *tab) { ingest_ranked_body(tab[blockIdx.z]); }
 
-// ... straight into a resident problem's SoA block: a's columns, then b's, n doubles each (make_problem's layout and bound)
-__global__ __launch_bounds__(256) void k_ingest_soa(IngestSrc a, IngestSrc b, uint32_t n, int b_in_max, double *__restrict__ soa,
-                                                    unsigned long long *absmax_bits) {
+// ... straight into a resident problem's SoA block: a's columns, then b's, n doubles each (make_problem's layout and bound).
+// scale_a: factor of a's columns on their way in (the 1D-radial front-end; x * 1.0 == x for everybody else), the bound is taken
+// of the product, like make_problem's.  absmax_bits == null: the caller has the bound from elsewhere (k_point_stats, norm 3).
+__global__ __launch_bounds__(256) void k_ingest_soa(IngestSrc a, IngestSrc b, uint32_t n, int b_in_max, double scale_a,
+                                                    double *__restrict__ soa, unsigned long long *absmax_bits) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     double m = 0.0;
     if (i < n) {
         const size_t ra = (size_t)i * (size_t)a.row_stride, rb = (size_t)i * (size_t)b.row_stride;
         for (int d = 0; d < a.cols; ++d) {
-            const double v = ingest_load(a.data, a.f32, ra + d);
+            const double v = ingest_load(a.data, a.f32, ra + d) * scale_a;
             soa[(size_t)d * n + i] = v;
             take_abs(m, v);
         }
@@ -115,7 +119,7 @@ __global__ __launch_bounds__(256) void k_ingest_soa(IngestSrc a, IngestSrc b, ui
         }
     }
     const unsigned long long bits = wave_max_bits(m);
-    if ((threadIdx.x & 63) == 0 && bits)
+    if (absmax_bits && (threadIdx.x & 63) == 0 && bits)
         atomicMax(absmax_bits, bits);
 }
 
@@ -138,8 +142,32 @@ __device__ __forceinline__ void point_stats_body(const double *__restrict__ a_ra
     if (threadIdx.x < 5)
         s_norm[threadIdx.x] = 0.0;
     __syncthreads();
-    if (g.norm) { // (n, and with it every loop bound and barrier below, is the same for the whole workgroup)
-        if (g.centred) {
+    if (g.norm == 3) { // radial (one point set): sum += sqrt(0.0 + x * x + y * y) in index order, the record carries n / sum
+        double sum = 0.0;
+        for (uint32_t base = 0; base < n; base += kStatsChunk) {
+            const uint32_t i = base + threadIdx.x;
+            if (i < n) {
+                const double x = a_raw[2 * (size_t)i], y = a_raw[2 * (size_t)i + 1];
+                s_terms[threadIdx.x] = sqrt(0.0 + x * x + y * y);
+            }
+            __syncthreads();
+            if (adder) {
+                const int count = (int)(n - base < (uint32_t)kStatsChunk ? n - base : (uint32_t)kStatsChunk);
+#pragma unroll 8
+                for (int k = 0; k < count; ++k)
+                    sum += s_terms[k];
+            }
+            __syncthreads();
+        }
+        if (threadIdx.x == 0)
+            s_norm[4] = g.n_as_double / sum;
+    } else if (g.norm) { // (n, and with it every loop bound and barrier below, is the same for the whole workgroup)
+        const bool about = g.norm == 2; // about a given centre (shared focal): c1 = (cx1, cy1), c2 = (cx2, cy2) of the arguments
+        if (about) {
+            if (threadIdx.x == 0)
+                s_norm[0] = g.cx1, s_norm[1] = g.cy1, s_norm[2] = g.cx2, s_norm[3] = g.cy2;
+            __syncthreads();
+        } else if (g.centred) {
             double c1x = 0, c1y = 0, c2x = 0, c2y = 0;
             for (uint32_t base = 0; base < n; base += kStatsChunk) {
                 const uint32_t i = base + threadIdx.x;
@@ -175,7 +203,7 @@ __device__ __forceinline__ void point_stats_body(const double *__restrict__ a_ra
             if (i < n) {
                 double a0 = a_raw[2 * (size_t)i], a1 = a_raw[2 * (size_t)i + 1];
                 double b0 = b_raw[2 * (size_t)i], b1 = b_raw[2 * (size_t)i + 1];
-                if (g.centred)
+                if (g.centred || about)
                     a0 -= c1x, a1 -= c1y, b0 -= c2x, b1 -= c2y;
                 s_terms[2 * threadIdx.x] = sqrt(a0 * a0 + a1 * a1);
                 s_terms[2 * threadIdx.x + 1] = sqrt(b0 * b0 + b1 * b1);
@@ -194,7 +222,13 @@ __device__ __forceinline__ void point_stats_body(const double *__restrict__ a_ra
     }
     __syncthreads();
     double m = 0.0;
-    if (g.bound) {
+    if (g.norm == 3) { // max |x * scale|, max |y * scale| of the block make_problem would have written (NaN propagates)
+        const double scale = s_norm[4];
+        for (uint32_t i = threadIdx.x; i < n; i += 256) {
+            take_abs(m, a_raw[2 * (size_t)i] * scale);
+            take_abs(m, a_raw[2 * (size_t)i + 1] * scale);
+        }
+    } else if (g.bound) {
         double cx1 = g.cx1, cy1 = g.cy1, fx1 = g.fx1, fy1 = g.fy1, cx2 = g.cx2, cy2 = g.cy2, fx2 = g.fx2, fy2 = g.fy2;
         if (g.bound == 3) { // (x - centroid) / scale; the host subtracts 0.0 when the points are not centred
             cx1 = s_norm[0], cy1 = s_norm[1], cx2 = s_norm[2], cy2 = s_norm[3];
@@ -342,10 +376,10 @@ hipError_t launch_point_stats_g(const PointStatsGroupArgs *tab, uint32_t G, hipS
     return hipGetLastError();
 }
 hipError_t launch_ingest_soa(const IngestSrc &a, const IngestSrc &b, uint32_t n, int b_in_max, double *soa,
-                             unsigned long long *absmax_bits, hipStream_t stream) {
+                             unsigned long long *absmax_bits, hipStream_t stream, double scale_a) {
     if (n == 0)
         return hipSuccess;
-    k_ingest_soa<<<dim3((n + 255) / 256), dim3(256), 0, stream>>>(a, b, n, b_in_max, soa, absmax_bits);
+    k_ingest_soa<<<dim3((n + 255) / 256), dim3(256), 0, stream>>>(a, b, n, b_in_max, scale_a, soa, absmax_bits);
     return hipGetLastError();
 }
 hipError_t launch_point_stats(const double *a_raw, const double *b_raw, uint32_t n, const PointStatsArgs &args, PointStatsRecord *out,

@@ -235,11 +235,15 @@ struct IngestSrc {
 // -> the contiguous fp64 AoS blocks k_prepare / k_prepare_tangent take (n x a.cols, n x b.cols)
 hipError_t launch_ingest(const IngestSrc &a, const IngestSrc &b, uint32_t n, double *out_a, double *out_b, hipStream_t stream);
 // -> the SoA block of a resident problem (a.cols + b.cols arrays of n) and, like make_problem, max |a| - with max |b| when
-// b_in_max - as an atomic max of bit patterns on *absmax_bits (zeroed by the caller; a NaN propagates)
+// b_in_max - as an atomic max of bit patterns on *absmax_bits (zeroed by the caller; a NaN propagates; null: no maximum).
+// scale_a: a's columns are multiplied by it on their way in, the maximum is the products' (the 1D-radial front-end)
 hipError_t launch_ingest_soa(const IngestSrc &a, const IngestSrc &b, uint32_t n, int b_in_max, double *soa,
-                             unsigned long long *absmax_bits, hipStream_t stream);
+                             unsigned long long *absmax_bits, hipStream_t stream, double scale_a = 1.0);
 // What the front-ends compute over the raw points on the host, from the fp64 AoS blocks (N x 2 each) on the device:
-//   norm     the two order-dependent reductions of the homography / fundamental normalisation (utils.cc:584-644) in index order
+//   norm     1: the two order-dependent reductions of the homography / fundamental normalisation (utils.cc:584-644) in index order;
+//            2: the second of them about the GIVEN centres c1 = (cx1, cy1), c2 = (cx2, cy2) - no centroid pass (shared focal,
+//            normalization_about); 3: one point set (b_raw is not read): scale = n / sum_k sqrt(0.0 + x_k^2 + y_k^2) in index order
+//            and absmax = max |coordinate * scale|, NaN propagating (the 1D-radial front-end and make_problem's bound); no `bound`
 //   bound    0 none; 1 max |(a - c1) / f1| (absolute pose, linear camera); 2 the same over both sets with their cameras (relative
 //            pose, linear cameras); 3 max |(x - centroid) / scale| with the centroids and scale of `norm` (requires norm)
 struct PointStatsArgs {

@@ -201,8 +201,11 @@ hipError_t launch_sfocal_score(const SFocalScoreArgs &a, hipStream_t stream);
 size_t sfocal_stage_bytes(uint32_t num_iters);
 hipError_t launch_sfocal_solve(const double *in, uint32_t count, FocalModel *models, uint32_t *num_models, double *stage,
                                uint32_t stage_samples, hipStream_t stream);
+// host_mask (pinned, device-mapped; may be null): a second copy, written by the kernel itself; dst (may be null): the caller's
+// device copy in the same launch, strided and - for a scored item - through the ranking's permutation (launch_mask's form)
+struct MaskDest;
 hipError_t launch_sfocal_mask(const double *const *a, uint32_t n, const FocalModel &m, double thr2, uint8_t *mask, uint8_t *host_mask,
-                              hipStream_t stream);
+                              hipStream_t stream, const MaskDest *dst = nullptr);
 hipError_t launch_sfocal_lm(SFocalLMTask *tasks, uint32_t num_tasks, hipStream_t stream);
 #endif
 

@@ -359,7 +359,7 @@ __global__ __launch_bounds__(kSFocalScoreThreads) void k_sfocal_score_wg_g(const
 }
 
 __device__ __forceinline__ void sfocal_mask_body(const double *x1, const double *y1, const double *x2, const double *y2, uint32_t n, const FocalModel &m,
-                                                 double thr2, uint8_t *mask, uint8_t *host_mask, uint32_t i) {
+                                                 double thr2, uint8_t *mask, uint8_t *host_mask, uint32_t i, const MaskDest &dst) {
     if (i >= n)
         return;
     double F[9];
@@ -368,14 +368,19 @@ __device__ __forceinline__ void sfocal_mask_body(const double *x1, const double 
     mask[i] = v;
     if (host_mask)
         host_mask[i] = v;
+    if (dst.data) { // the caller's device copy (k_mask's form): one plain byte store per row, through the ranking's permutation for a scored item
+        const size_t row = dst.order ? dst.order[i] : i;
+        dst.data[row * (size_t)dst.stride] = v;
+    }
 }
 __global__ void k_sfocal_mask(const double *x1, const double *y1, const double *x2, const double *y2, uint32_t n, FocalModel m,
-                              double thr2, uint8_t *mask, uint8_t *host_mask) {
-    sfocal_mask_body(x1, y1, x2, y2, n, m, thr2, mask, host_mask, blockIdx.x * blockDim.x + threadIdx.x);
+                              double thr2, uint8_t *mask, uint8_t *host_mask, MaskDest dst) {
+    sfocal_mask_body(x1, y1, x2, y2, n, m, thr2, mask, host_mask, blockIdx.x * blockDim.x + threadIdx.x, dst);
 }
 __global__ void k_sfocal_mask_g(const FocalMaskArgs *__restrict__ as) {
     const FocalMaskArgs a = globalised(as[blockIdx.y]);
-    sfocal_mask_body(a.a[0], a.a[1], a.a[2], a.a[3], a.n, a.model, a.thr2, a.mask, a.host_mask, blockIdx.x * blockDim.x + threadIdx.x);
+    sfocal_mask_body(a.a[0], a.a[1], a.a[2], a.a[3], a.n, a.model, a.thr2, a.mask, a.host_mask, blockIdx.x * blockDim.x + threadIdx.x,
+                     MaskDest{nullptr, 0, nullptr});
 }
 
 constexpr int kSfLMThreads = 256;
@@ -698,10 +703,11 @@ hipError_t launch_sfocal_score(const SFocalScoreArgs &a, hipStream_t stream) {
     return hipGetLastError();
 }
 hipError_t launch_sfocal_mask(const double *const *a, uint32_t n, const FocalModel &m, double thr2, uint8_t *mask, uint8_t *host_mask,
-                              hipStream_t stream) {
+                              hipStream_t stream, const MaskDest *dst) {
     if (n == 0)
         return hipSuccess;
-    k_sfocal_mask<<<dim3((n + 255u) / 256u), dim3(256), 0, stream>>>(a[0], a[1], a[2], a[3], n, m, thr2, mask, host_mask);
+    const MaskDest none = {nullptr, 0, nullptr};
+    k_sfocal_mask<<<dim3((n + 255u) / 256u), dim3(256), 0, stream>>>(a[0], a[1], a[2], a[3], n, m, thr2, mask, host_mask, dst ? *dst : none);
     return hipGetLastError();
 }
 hipError_t launch_sfocal_lm(SFocalLMTask *tasks, uint32_t num_tasks, hipStream_t stream) {
