@@ -2896,9 +2896,9 @@ __device__ __forceinline__ void lm_start_params(int est, const LMTask &T, double
 template <int EST> constexpr bool kAbsLike = (EST == EST_ABS || EST == EST_RAD1D);
 
 template <int N> struct BlockReduce {
-    // Reduces N per-thread doubles (+ one counter) over the 1024-thread workgroup.  Result in out[0..N)
-    // and *count_out (valid for every thread after the call).  Fixed order: butterfly inside each
-    // wavefront, then wavefronts 0..15 in sequence.
+    // Reduces N per-thread doubles (+ one counter) over the kLMThreads-thread workgroup (PL_LM_THREADS = 512: 8 wavefronts).
+    // Result in out[0..N) and *count_out (valid for every thread after the call).  Fixed order: butterfly inside each
+    // wavefront, then wavefronts 0..7 in sequence.
     __device__ static void run(const double *v, uint32_t cnt, double (*scratch)[N + 1], double *out,
                                uint32_t *count_out) {
         const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;

@@ -172,6 +172,20 @@ def refine_inputs(n):
     return d, xs, scale, p0
 
 
+TREE_REFINEMENTS = [(n, run) for n in REFINE_N if n > 256 for run in sorted(REFINE_RUNS)]  # tree sums in the default LM mode
+
+
+def refine_on_device(P, n, run):
+    """a fixture refinement through Problem.refine of the product package P in the current LM mode:
+    (q and t as 7 numbers, iterations, the open problem, start pose, bundle options)"""
+    d, x, scale, p0 = refine_inputs(n)
+    loss, iters = REFINE_RUNS[run]
+    bundle = {"loss_type": loss, "loss_scale": MAX_ERROR * scale, "max_iterations": iters}
+    pr = P.Problem(P.KIND_RAD1D, x, d["p3d"])
+    pose, it = pr.refine(P.CameraPose(p0[:4], p0[4:]), bundle)
+    return np.r_[pose.q, pose.t], it, pr, p0, bundle
+
+
 # ------------------------------------------------------------------------------------------ estimator
 # name, n, outlier ratio, first data seed, options beyond max_error / ransac.seed, warm start
 EST_CASES = [

@@ -215,6 +215,23 @@ def refine_inputs(n, unproject=None):
     return P, MAX_ERROR * P["scale"], p0
 
 
+TREE_REFINEMENTS = [(n, run) for n in REFINE_N if n > 256 for run in sorted(REFINE_RUNS)]  # tree sums in the default LM mode
+
+
+def refine_on_device(P, n, run):
+    """a fixture refinement through TangentProblem.refine of the product package P: (q and t as 7 numbers, iterations)"""
+    d, x1, x2, c1, c2 = scene("OPENCV_FISHEYE", "RADIAL_FISHEYE", n, 0.0 if n <= 6 else 0.2, 120.0, 9200 + n)
+    scale, x1s, x2s, c1s, c2s = scaled_inputs(x1, x2, c1, c2)
+    p0 = GC.start_pose(d, np.random.RandomState(9300 + n), 0.003)
+    loss, iters = REFINE_RUNS[run]
+    pr = P.TangentProblem(x1s, x2s, c1s, c2s)
+    try:
+        pose, it = pr.refine(P.CameraPose(p0[:4], p0[4:]), {"loss_type": loss, "loss_scale": MAX_ERROR * scale, "max_iterations": iters})
+    finally:
+        pr.close()
+    return np.r_[pose.q, pose.t], it
+
+
 def record_refine():
     out = {}
     for n in REFINE_N:

@@ -49,6 +49,11 @@ TREE_NS = (SEQ + 1, STRIDE - 1, STRIDE, STRIDE + 1, 2 * STRIDE + 1, 1281)  # 128
 RING_NS = (RING - 1, RING, RING + 1)
 LM2_NS = {"hom": (2560, 2561, 3071, 3072), "fund": (2560,), "abs": (8192,)}
 N_SCENE = {"abs": 8192, "rel": 1281, "fund": 3072, "hom": 3072}
+# Rows beyond the staging limit: a task's correspondences go to LDS while 8 * ND * n bytes fit what the kernel's static LDS leaves
+# (about 2920 rows for k_lm<abs> and k_lm<hom>, 2907 for k_lm_ordered<abs>, 2086 for k_lm_ordered<hom>); beyond, every sweep
+# reads them from device memory
+UNSTAGED_NS = {"abs": 4096, "hom": 3072}
+UNSTAGED_RUNS = (("TRUNCATED", "rough"), ("CAUCHY", "gentle"), ("TRUNCATED_LE_ZACH", "far"), ("HUBER", "rough"))
 
 
 def lm2_slices(n):
@@ -382,6 +387,10 @@ def _masks(kind, route, n_small, n_large):
     return out
 
 
+def _unstaged(route):
+    return [Case(kind, route, n, loss, NIELSEN, LEVENBERG, 25, start) for kind, n in UNSTAGED_NS.items() for loss, start in UNSTAGED_RUNS]
+
+
 @functools.lru_cache(maxsize=None)
 def ordered_cases():
     """results that must equal the host model bit for bit: k_lm_ordered (route 1) at every size, k_lm (route 0) up to SEQ rows"""
@@ -396,6 +405,7 @@ def ordered_cases():
         out += _rejection_cases(kind, K_LM_ORDERED, RING_NS + TREE_NS)
         out += _stops_and_iterations(kind, K_LM_ORDERED, SEQ - 1, RING + 1)
         out += _masks(kind, K_LM_ORDERED, WAVE + 1, 2 * STRIDE + 1)
+    out += _unstaged(K_LM_ORDERED)
     return list(dict.fromkeys(out))
 
 
@@ -409,6 +419,7 @@ def tree_candidates():
         out += _rejection_cases(kind, K_LM, TREE_NS)
         out += _stops_and_iterations(kind, K_LM, STRIDE + 1, 2 * STRIDE + 1)
         out += _masks(kind, K_LM, STRIDE - 1, 2 * STRIDE + 1)
+    out += _unstaged(K_LM)
     return list(dict.fromkeys(out))
 
 
@@ -481,3 +492,63 @@ def refine_on_device(P, c, max_iterations=None):
     finally:
         pr.close()
     return flat(c.kind, got), it
+
+
+# ---- the tree routes' bits, pinned ---------------------------------------------------------------------------------------------------
+# tests/golden/lm_tree_bits_v1.json: what the device computed where its sums run in tree order (k_lm beyond SEQ rows) - the refined
+# model's bytes and the iteration count of every case of tree_cases() ("k_lm", keyed by case_id) and of the RAD1D and tangent-Sampson
+# refinements beyond SEQ rows in the default mode ("rad1d", "tangent", keyed "n/run").  The tolerance against the oracle says the
+# results are right; the fixture says they are the SAME after a change that is meant to leave every sum as it is.
+# Recorded by `PYTHONPATH=. python tests/lm_cases.py [path]` from the repository root on a machine with a device, with the kernels whose bits are to be held; a change
+# that means to alter a tree sum records it again and says so.
+TREE_BITS_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "lm_tree_bits_v1.json")
+
+
+def bits(model):
+    return np.ascontiguousarray(model, dtype=np.float64).tobytes().hex()
+
+
+@functools.lru_cache(maxsize=None)
+def tree_bits():
+    import json
+
+    return json.load(open(TREE_BITS_PATH))
+
+
+def assert_pinned(section, key, model, iterations):
+    """the device's result equals the fixture's entry; a missing entry fails"""
+    rec = tree_bits()[section].get(key)
+    assert rec is not None, f"{TREE_BITS_PATH} has no entry {section} / {key}: record the fixture again"
+    assert (bits(model), int(iterations)) == (rec["bits"], rec["iterations"]), (section, key, iterations, rec["iterations"])
+
+
+def _record(path):
+    import json
+    import sys
+
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import poselib_amd as P
+    from golden import make_golden_radial1d as rad1d
+    from golden import make_golden_tangent as tangent
+
+    out = {"k_lm": {}, "rad1d": {}, "tangent": {}}
+    for c in tree_cases():
+        prev = P.set_lm_mode(2 if c.kind == "fund" else 0)  # (fundamental matrices reach k_lm in mode 2 only)
+        assert P.lm_route(KIND_ID[c.kind], c.n, c.max_iterations) == (K_LM, 0), case_id(c)
+        got, it = refine_on_device(P, c)
+        P.set_lm_mode(prev)
+        out["k_lm"][case_id(c)] = {"bits": bits(got), "iterations": int(it)}
+    for section, module in (("rad1d", rad1d), ("tangent", tangent)):
+        for n, run in module.TREE_REFINEMENTS:
+            pose, it = module.refine_on_device(P, n, run)[:2]
+            out[section][f"{n}/{run}"] = {"bits": bits(pose), "iterations": int(it)}
+    with open(path, "w") as f:
+        json.dump(out, f, indent=0, sort_keys=True)
+        f.write("\n")
+    print("recorded", {k: len(v) for k, v in out.items()}, "->", path)
+
+
+if __name__ == "__main__":
+    import sys
+
+    _record(sys.argv[1] if len(sys.argv) > 1 else TREE_BITS_PATH)

@@ -80,7 +80,8 @@ def test_ordered_results_equal_the_host_model(gpu, kind, route):
 @pytest.mark.parametrize("kind", LC.KINDS)
 def test_tree_results_agree_with_the_oracle(gpu, kind):
     """k_lm beyond 256 rows (tree sums; the queue of correspondences with a non-zero weight under the truncated losses), in mode 2
-    and - poses and homographies - in mode 0: the oracle's iteration count, its model within 1e-9, the same bits twice"""
+    and - poses and homographies - in mode 0: the oracle's iteration count, its model within 1e-9, the same bits twice - and the
+    bits and the iteration count recorded in tests/golden/lm_tree_bits_v1.json (lm_cases.assert_pinned)"""
     cases = [c for c in LC.tree_cases() if c.kind == kind]
     assert len(cases) >= 40
     first = {}
@@ -95,6 +96,7 @@ def test_tree_results_agree_with_the_oracle(gpu, kind):
                 assert dist <= LC.TREE_TOL, (LC.case_id(c), dist)
                 again, it2 = LC.refine_on_device(gpu, c)  # (and the other mode runs the same kernel: the same bits again)
                 assert it2 == it and np.array_equal(again, got) and np.array_equal(first.setdefault(c, got), got), LC.case_id(c)
+                LC.assert_pinned("k_lm", LC.case_id(c), got, it)  # (the recorded bits: tests/golden/lm_tree_bits_v1.json)
                 if c.mask == "ones":
                     bare, bare_it = LC.refine_on_device(gpu, c._replace(mask=None))
                     assert bare_it == it and np.array_equal(bare, got), LC.case_id(c)

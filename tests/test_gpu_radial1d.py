@@ -10,6 +10,7 @@ import json
 import numpy as np
 import pytest
 
+import lm_cases as LC
 from golden import make_golden_radial1d as GR
 from poselib_amd import synth
 
@@ -170,21 +171,19 @@ def test_streaming_scorer_equals_the_sequential_scorer_with_and_without_the_filt
 def test_refinement_equals_the_reference(gpu, n, run):
     """Refiner<EST_RAD1D> (pl_refine_model with kind 5 = bundle_adjust_1D_radial): with the sums in the reference's order - k_lm up to
     256 correspondences, k_lm_ordered (pl_set_lm_mode(1)) beyond - pose bit for bit; in the default mode beyond 256 (tree sums)
-    identical iteration counts and the pose within 1e-6"""
-    d, x, scale, p0 = GR.refine_inputs(n)
+    identical iteration counts, the pose within 1e-6 and the bits recorded in tests/golden/lm_tree_bits_v1.json"""
     want = G["refine"][f"{n}/{run}"]
+    d, x, scale, p0 = GR.refine_inputs(n)
     assert GR.digest([x, d["p3d"], p0]) == want["input_sha256"], "the inputs changed: regenerate the fixture"
-    loss, iters = GR.REFINE_RUNS[run]
-    bundle = {"loss_type": loss, "loss_scale": GR.MAX_ERROR * scale, "max_iterations": iters}
-    pr = gpu.Problem(gpu.KIND_RAD1D, x, d["p3d"])
-    pose, it = pr.refine(gpu.CameraPose(p0[:4], p0[4:]), bundle)
+    got, it, pr, p0, bundle = GR.refine_on_device(gpu, n, run)
     ref = floats(want["pose"])
-    print(n, run, "default mode: iterations", it, want["iterations"], "max |pose difference|", float(np.abs(pose7(pose) - ref).max()))
+    print(n, run, "default mode: iterations", it, want["iterations"], "max |pose difference|", float(np.abs(got - ref).max()))
     assert it == want["iterations"]
     if n <= 256:
-        assert GR.reprs(pose7(pose)) == want["pose"]
+        assert GR.reprs(got) == want["pose"]
     else:
-        assert np.abs(pose7(pose) - ref).max() < 1e-6
+        assert np.abs(got - ref).max() < 1e-6
+        LC.assert_pinned("rad1d", f"{n}/{run}", got, it)
         before = gpu.set_lm_mode(1)
         try:
             pose, it = pr.refine(gpu.CameraPose(p0[:4], p0[4:]), bundle)
@@ -192,7 +191,8 @@ def test_refinement_equals_the_reference(gpu, n, run):
             gpu.set_lm_mode(before)
         assert it == want["iterations"]
         assert GR.reprs(pose7(pose)) == want["pose"]
-    assert pose.t[2] == 0.0
+        got = pose7(pose)
+    assert got[6] == 0.0
     pr.close()
 
 

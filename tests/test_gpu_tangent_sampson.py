@@ -10,6 +10,7 @@ import json
 import numpy as np
 import pytest
 
+import lm_cases as LC
 from golden import make_golden_tangent as GT
 from golden.make_golden import digest
 from poselib_amd import synth
@@ -165,22 +166,18 @@ LOSS = {"truncated": "TRUNCATED", "cauchy": "CAUCHY"}
 @pytest.mark.parametrize("run", sorted(GT.REFINE_RUNS))
 def test_refinement_equals_the_reference(gpu, n, run):
     """Refiner<EST_RELT> in k_lm on the device's own bearings and Jacobians: up to 256 correspondences the sums run in the reference's
-    order - pose bit for bit; beyond, identical iteration counts and the pose within 1e-6 (tests/test_gpu_radial_cameras.py)"""
-    d, x1, x2, c1, c2 = GT.scene("OPENCV_FISHEYE", "RADIAL_FISHEYE", n, 0.0 if n <= 6 else 0.2, 120.0, 9200 + n)
-    scale, x1s, x2s, c1s, c2s = GT.scaled_inputs(x1, x2, c1, c2)
-    p0 = GT.GC.start_pose(d, np.random.RandomState(9300 + n), 0.003)
+    order - pose bit for bit; beyond, identical iteration counts, the pose within 1e-6 (tests/test_gpu_radial_cameras.py) and the
+    bits recorded in tests/golden/lm_tree_bits_v1.json"""
     want = G["refine"][f"{n}/{run}"]
-    loss, iters = GT.REFINE_RUNS[run]
-    pr = gpu.TangentProblem(x1s, x2s, c1s, c2s)
-    pose, it = pr.refine(gpu.CameraPose(p0[:4], p0[4:]), {"loss_type": loss, "loss_scale": GT.MAX_ERROR * scale, "max_iterations": iters})
-    pr.close()
-    got, ref = np.r_[pose.q, pose.t], floats(want["pose"])
+    got, it = GT.refine_on_device(gpu, n, run)
+    ref = floats(want["pose"])
     print(n, run, "iterations", it, want["iterations"], "max |pose difference|", float(np.abs(got - ref).max()))
     assert it == want["iterations"]
     if n <= 256:
         assert GT.reprs(got) == want["pose"]
     else:
         assert np.abs(got - ref).max() < 1e-6
+        LC.assert_pinned("tangent", f"{n}/{run}", got, it)
 
 
 # ------------------------------------------------------------------------------------------ estimator
