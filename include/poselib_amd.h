@@ -436,7 +436,8 @@ int pl_debug_rank_tile(size_t max_n);
  *     permuting copy for a scored call); one single-workgroup launch adds the host's sum in the host's order and returns one small
  *     record; shared focal then prepares the problem from those blocks, 1D radial writes its block of scaled pixels with the
  *     ingest kernel - and from there the host forms' own code runs.  No point passes through the host.
- *   - Out of scope: these two in pl_estimate_batch_dev (kinds 4 and 5 stay refused there), estimate_focal_length. */
+ *   - Out of scope: these two in pl_estimate_batch_dev (kinds 4 and 5 stay refused there; batches of shared-focal pairs:
+ *     pl_estimate_shared_focal_relative_pose_batch_dev below), estimate_focal_length. */
 int pl_estimate_shared_focal_relative_pose_dev(const pl_device_points *x1, const pl_device_points *x2,
                                                const pl_device_scores *scores /* may be NULL */, size_t n, const double *pp,
                                                const pl_robust_options *opt, pl_camera_pose *pose, double *focal,
@@ -453,7 +454,52 @@ int pl_estimate_1D_radial_absolute_pose_dev(const pl_device_points *points2D, co
  * radial; cx, cy unused).  out[0] = the scale, out[1] = max |coordinate * scale| (radial; a NaN propagates) or 0. */
 int pl_debug_point_stats_about_dev(const pl_device_points *x1, const pl_device_points *x2 /* NULL: radial */, size_t n, double cx,
                                    double cy, double *out /* 2 */);
-/* What the calling thread's last pl_estimate_batch / pl_estimate_batch_devices / pl_estimate_batch_dev / pl_ransac_batch did with its items.  Items in
+/* ---- batches of shared-focal pairs from device memory: what a matcher's padded (pairs, N, 5) tensor holds, in one call.
+ * pl_estimate_batch_dev* and the kind-numbered _dev entries keep refusing kind 4; this entry point of its own serves it.
+ *   - Every item is pl_estimate_shared_focal_relative_pose_dev on the same arguments, bit for bit (and so the host call on the
+ *     same values as doubles): pose, focal length, the mask in the caller's row numbering, n_used and every field of the stats
+ *     except `seconds`.  A result does not depend on the item's group, on max_in_flight or on POSELIB_AMD_FOCAL_GROUP.
+ *   - scores / masks: NULL, or count entries belonging to items[i]; an entry whose data is NULL makes item i a plain item / an
+ *     item with its host `inliers` pointer (which is ignored when a device mask is given).  n_used: NULL, or count entries.
+ *   - All descriptors are checked before any launch, the checks that need no device first (PL_ERR_INVALID comes before
+ *     PL_ERR_NO_DEVICE), then the memory's kind, device and extent - the runtime is asked once per allocation and call.  A bad
+ *     item, or one with a null opt / pose / focal or options the single call rejects, fails alone with the status its single call
+ *     would give and the message "item k: cause"; its mask destination is not touched; the other items run; the call returns
+ *     the first failing item's status.  count == 0: PL_OK; items == NULL with count > 0: PL_ERR_INVALID.
+ *   - How: one zero-fill launch over all device masks first; all scored items ranked at once (one launch sequence, one
+ *     synchronisation); then the items the lock-step groups of pl_estimate_batch's kind 4 take - judged on n_used:
+ *     10 <= n_used <= 16384, no warm start, max_iterations > 0, min_iterations <= 4096, PROSAC included - advance in groups whose
+ *     first stage reads the rows where they lie: strided / fp32 members are copied into the group's block, one launch adds every
+ *     member's mean distance from its pp in index order, and the normalisation launch behind it takes each scale from the member's
+ *     record on the device - no point and no scale passes through the host in between.  A member's mask launch writes a device
+ *     mask itself, a scored member's through its ranking's permutation.  Everything else, and items a group hands back, runs through the
+ *     single _dev entry point (a scored one on its ranked blocks).  pl_last_batch_report: items, focal_grouped, solo, fallback
+ *     (grouped is 0).  Several calls may be in flight from different host threads.
+ *   - Out of scope: several devices, host and device items mixed in one call, a producer stream, models in device memory,
+ *     1D-radial batches and estimate_focal_length from device memory.
+ * Adding this record and entry point changes no existing record: PL_ABI_VERSION stays 5 (new symbols do not bump it). */
+typedef struct {
+    int32_t status;              /* out */
+    int32_t reserved;            /* 0 */
+    pl_device_points x1, x2;     /* N x 2 each */
+    size_t n;
+    double pp[2];
+    const pl_robust_options *opt;
+    pl_camera_pose *pose;        /* host, in/out as in the single call */
+    double *focal;               /* host, in/out as in the single call */
+    uint8_t *inliers;            /* host, n bytes, may be NULL */
+    pl_ransac_stats *stats;      /* may be NULL */
+} pl_shared_focal_item_dev;
+int pl_estimate_shared_focal_relative_pose_batch_dev(pl_shared_focal_item_dev *items,
+                                                     const pl_device_scores *scores /* may be NULL; an entry without data: a plain item */,
+                                                     const pl_device_mask *masks /* may be NULL; an entry without data: host mask */,
+                                                     size_t *n_used /* may be NULL */, size_t count, int max_in_flight);
+/* Diagnostic: the reduction in front of that call's groups alone - pl_debug_point_stats_about_dev (x2 != NULL) for count pairs at
+ * once through the grouped kernels, every member about its own centre (centres: count x 2).  out: count x 2, {scale, 0} per member. */
+int pl_debug_point_stats_about_group_dev(const pl_device_points *x1, const pl_device_points *x2, const size_t *n, const double *centres,
+                                         size_t count, double *out /* count x 2 */);
+/* What the calling thread's last pl_estimate_batch / pl_estimate_batch_devices / pl_estimate_batch_dev /
+ * pl_estimate_shared_focal_relative_pose_batch_dev / pl_ransac_batch did with its items.  Items in
  * lock-step groups share one launch sequence (the advertised rate); `solo` items were outside the group path from the start
  * (options or sizes a group does not take - see pl_batch_item / pl_ransac_batch) and `fallback` items were handed back by their
  * group: both kinds ran through the single-problem entry points, correct but at that path's rate - a batch that is mostly solo

@@ -11,7 +11,7 @@ from .api import (  # noqa: F401
     device_count, essential_matrix_5pt, estimate_absolute_pose, estimate_batch, last_batch_report, estimate_fundamental, estimate_homography,
     estimate_relative_pose, homography_4pt, p3p, p5p, ransac_fundamental, ransac_homography, ransac_pnp, ransac_pnpf,
     ransac_relpose, ransac_shared_focal_relpose, estimate_shared_focal_relative_pose, refine_shared_focal_relpose, ImagePair, p35pf, relpose_6pt_shared_focal, solve_focal_batch, relpose_5pt, relpose_7pt, set_device, set_lm_mode, solve_batch, undistort_points, undistort_points_batch,
-    check_device_points, score_order, rank_scores, rank_tile, point_stats_dev, point_stats_group_dev, point_stats_about_dev, score_pruned, score_survivors, score_bounded, score_prune_gate, lm_route, sampler_shape, sample_positions,
+    check_device_points, score_order, rank_scores, rank_tile, point_stats_dev, point_stats_group_dev, point_stats_about_dev, point_stats_about_group_dev, SharedFocalBatch, estimate_shared_focal_relative_pose_batch, score_pruned, score_survivors, score_bounded, score_prune_gate, lm_route, sampler_shape, sample_positions,
 )
 
 __version__ = "0.1.0"

@@ -141,6 +141,12 @@ class DeviceMask(C.Structure):  # pl_device_mask: one flag byte per row in DEVIC
     _fields_ = [("data", C.c_void_p), ("stride", C.c_int64)]
 
 
+class SharedFocalItemDev(C.Structure):  # pl_shared_focal_item_dev
+    _fields_ = [("status", i32), ("reserved", i32), ("x1", DevicePoints), ("x2", DevicePoints), ("n", C.c_size_t), ("pp", f64 * 2),
+                ("opt", C.POINTER(RobustOptions)), ("pose", C.POINTER(CameraPose)), ("focal", C.POINTER(f64)), ("inliers", C.c_void_p),
+                ("stats", C.POINTER(RansacStats))]
+
+
 class PoseLibAmdError(RuntimeError):
     pass
 
@@ -224,6 +230,8 @@ def _declare(L):
                                                                P(sz)]),
         "pl_estimate_1D_radial_absolute_pose_dev": (cint, [dpts, dpts, P(DeviceScores), sz, opt, pose, vp, P(DeviceMask), stats, P(sz)]),
         "pl_debug_point_stats_about_dev": (cint, [dpts, dpts, sz, dbl, dbl, vp]),
+        "pl_estimate_shared_focal_relative_pose_batch_dev": (cint, [P(SharedFocalItemDev), P(DeviceScores), P(DeviceMask), P(sz), sz, cint]),
+        "pl_debug_point_stats_about_group_dev": (cint, [dpts, dpts, P(sz), vp, sz, vp]),
         "pl_last_batch_report": (None, [P(BatchReport)]),
         "pl_ransac_batch": (cint, [P(RansacItem), sz, cint, cint]),
         "pl_undistort_points": (cint, [cam, vp, sz, vp]),
@@ -318,6 +326,7 @@ EXPORTED_SYMBOLS = [
     "pl_estimate_dev_scored", "pl_estimate_batch_dev_scored", "pl_debug_rank_scores", "pl_debug_rank_tile",
     "pl_undistort_points_dev", "pl_undistort_points_batch_dev", "pl_estimate_dev_masked", "pl_estimate_batch_dev_masked",
     "pl_estimate_shared_focal_relative_pose_dev", "pl_debug_point_stats_about_dev",
+    "pl_estimate_shared_focal_relative_pose_batch_dev", "pl_debug_point_stats_about_group_dev",
     # (pl_estimate_1D_radial_absolute_pose, its _dev form and pl_ransac_1D_radial_pnp carry the reference's capital D: declared above, exported by the
     # library, but outside the lower-case pattern tests/test_cabi_surface.py lists the header's symbols with)
 ]

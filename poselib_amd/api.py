@@ -571,7 +571,8 @@ class Batch:
 
     The point sets of a problem may be GPU tensors or __cuda_array_interface__ objects instead of arrays (the views of a matcher's
     padded (pairs, N, 4) tensor): the items then are pl_batch_item_dev records and `run()` is pl_estimate_batch_dev - nothing is
-    copied to the host.  A call is all-device or all-host; "shared_focal" and "radial1d" problems and `devices=` are host-only."""
+    copied to the host.  A call is all-device or all-host; "shared_focal" and "radial1d" problems and `devices=` are host-only
+    (shared-focal pairs on the GPU: SharedFocalBatch)."""
 
     def __init__(self, problems):
         kinds = {"abs": KIND_ABS, "rel": KIND_REL, "fund": KIND_FUND, "hom": KIND_HOM, "shared_focal": KIND_SHARED_FOCAL,
@@ -583,7 +584,8 @@ class Batch:
         if self.on_device:
             for pr in problems:
                 if pr[0] in ("shared_focal", "radial1d"):
-                    raise ValueError(f"a {pr[0]!r} problem is not served from device memory: pass host arrays")
+                    raise ValueError(f"a {pr[0]!r} problem is not served from device memory: pass host arrays" +
+                                     (" (pairs on the GPU: SharedFocalBatch)" if pr[0] == "shared_focal" else ""))
                 if _on_device(pr[1]) != _on_device(pr[2]):
                     raise ValueError("one point set is on the GPU and the other in host memory: pass both the same way")
         streams = {}
@@ -1181,6 +1183,88 @@ def estimate_shared_focal_relative_pose(points2D_1, points2D_2, pp, opt=None, in
     del keep
     return (_shared_focal_pair(pose, focal.value, ppa),
             _info(st, inl[:n] if inliers_out is None else inliers_out, n if scores is None else int(used.value)))
+
+
+class SharedFocalBatch:
+    """An array of pl_shared_focal_item_dev records (include/poselib_amd.h) marshalled once: `run()` is the C-ABI call
+    pl_estimate_shared_focal_relative_pose_batch_dev and nothing else, `results()` returns what
+    estimate_shared_focal_relative_pose returns per pair: [(ImagePair, info)].
+
+    pairs: (points2D_1, points2D_2, pp, opt) each, the point sets GPU tensors or __cuda_array_interface__ objects - the views of a
+    matcher's padded (pairs, N, 5) tensor; nothing is copied to the host.  opt may carry "scores" / "min_score" (one confidence
+    per row, on the GPU), "inliers_out" (a GPU array of n one-byte elements that receives the mask) and "initial_pair" (a warm
+    start: such a pair runs on its own).  Pairs in host memory: estimate_batch with "shared_focal" problems."""
+
+    def __init__(self, pairs):
+        cnt = len(pairs)
+        self.items = (L.SharedFocalItemDev * max(cnt, 1))()
+        self.scores = (L.DeviceScores * max(cnt, 1))()
+        self.masks = (L.DeviceMask * max(cnt, 1))()
+        self.n_used = (C.c_size_t * max(cnt, 1))()
+        self.scored = self.masked = False
+        self.keep = []
+        self.mask_out = []  # per pair: the caller's inliers_out= object or None
+        streams = {}
+        for i, (x1, x2, pp, opt) in enumerate(pairs):
+            on = (_on_device(x1), _on_device(x2))
+            if on == (False, False):
+                raise ValueError("SharedFocalBatch takes points on the GPU: pairs in host memory go through estimate_batch "
+                                 "(\"shared_focal\" problems)")
+            if on != (True, True):
+                raise ValueError("one point set is on the GPU and the other in host memory: pass both the same way")
+            opt = dict(opt or {})
+            init = opt.pop("initial_pair", None)
+            scores, min_score = opt.pop("scores", None), opt.pop("min_score", None)
+            inliers_out = opt.pop("inliers_out", None)
+            _check_scores_args(True, scores, min_score)
+            d1, n, keep1 = _device_points(x1, 2, streams)
+            d2, n2, keep2 = _device_points(x2, 2, streams)
+            if n2 != n:
+                raise ValueError(f"the point sets differ in length ({n} and {n2})")
+            ppa = np.ascontiguousarray(pp, dtype=np.float64)
+            if ppa.shape != (2,):
+                raise ValueError("pp: expected two numbers")
+            o = _robust_options(opt, KIND_REL, init is not None)
+            pose = _cpose(init.pose if init is not None else CameraPose())
+            focal = C.c_double(init.camera1.focal() if init is not None else 1.0)
+            inl = np.zeros(max(n, 1), dtype=np.uint8)
+            st = L.RansacStats()
+            keep_s = None
+            if scores is not None:
+                self.scores[i], keep_s = _device_scores(scores, n, min_score, streams)
+                self.scored = True
+            if inliers_out is not None:
+                self.masks[i], inliers_out = _device_mask(inliers_out, n, streams)
+                self.masked = True
+            it = self.items[i]
+            it.x1, it.x2, it.n = d1, d2, n
+            it.pp[0], it.pp[1] = float(ppa[0]), float(ppa[1])
+            it.opt, it.pose, it.focal = C.pointer(o), C.pointer(pose), C.pointer(focal)
+            it.inliers = _ptr(inl)
+            it.stats = C.pointer(st)
+            self.keep.append((o, pose, focal, ppa, inl, st, n, scores is not None, (keep1, keep2, keep_s)))
+            self.mask_out.append(inliers_out)
+        _sync_streams(streams)  # (once per device, not per tensor: the producers' work is complete before run())
+
+    def run(self, max_in_flight=8):
+        L.check(L.lib().pl_estimate_shared_focal_relative_pose_batch_dev(
+            self.items, self.scores if self.scored else None, self.masks if self.masked else None, self.n_used,
+            C.c_size_t(len(self.keep)), C.c_int(int(max_in_flight))))
+
+    def results(self):
+        out = []
+        for i, (o, pose, focal, ppa, inl, st, n, scored, _) in enumerate(self.keep):
+            info = _info(st, inl[:n] if self.mask_out[i] is None else self.mask_out[i], self.n_used[i] if scored else n)
+            out.append((_shared_focal_pair(pose, focal.value, ppa), info))
+        return out
+
+
+def estimate_shared_focal_relative_pose_batch(pairs, max_in_flight=8):
+    """estimate_shared_focal_relative_pose for many pairs in GPU memory in one call (SharedFocalBatch; include/poselib_amd.h
+    pl_estimate_shared_focal_relative_pose_batch_dev): [(ImagePair, info)] in the order of `pairs`."""
+    b = SharedFocalBatch(pairs)
+    b.run(max_in_flight)
+    return b.results()
 
 
 def refine_shared_focal_relpose(x1, x2, pair, bundle=None):
@@ -1800,6 +1884,25 @@ def point_stats_group_dev(pairs, centroid=True):
     L.check(L.lib().pl_debug_point_stats_group_dev(d1, d2, ns, C.c_size_t(cnt), int(bool(centroid)), _ptr(out)))
     return [{"c1": o[0:2].copy(), "c2": o[2:4].copy(), "scale": float(o[4]), "absmax_normalised": float(o[5]),
              "absmax_first": float(o[6])} for o in out[:cnt]]
+
+
+def point_stats_about_group_dev(pairs, centres):
+    """Diagnostic (pl_debug_point_stats_about_group_dev): point_stats_about_dev's shared-focal reduction for a list of (x1, x2)
+    pairs of device point sets at once, every pair about its own centre, through the grouped kernels of
+    pl_estimate_shared_focal_relative_pose_batch_dev - the list of scales."""
+    keep = [_Points(x1, x2, 2, 2) for x1, x2 in pairs]
+    if not all(p.on_device for p in keep):
+        raise ValueError("point_stats_about_group_dev takes device points")
+    cnt = len(keep)
+    cen = np.ascontiguousarray(centres, dtype=np.float64).reshape(-1, 2)
+    if cen.shape[0] != cnt:
+        raise ValueError(f"{cen.shape[0]} centres for {cnt} pairs")
+    d1 = (L.DevicePoints * max(cnt, 1))(*[p.keep[0] for p in keep])
+    d2 = (L.DevicePoints * max(cnt, 1))(*[p.keep[1] for p in keep])
+    ns = (C.c_size_t * max(cnt, 1))(*[p.n for p in keep])
+    out = np.zeros((max(cnt, 1), 2))
+    L.check(L.lib().pl_debug_point_stats_about_group_dev(d1, d2, ns, _ptr(cen), C.c_size_t(cnt), _ptr(out)))
+    return [float(o[0]) for o in out[:cnt]]
 
 
 def set_lm_mode(mode) -> int:

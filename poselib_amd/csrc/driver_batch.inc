@@ -5,6 +5,7 @@
 //   pl_estimate_batch              host-resident problems (the estimate_* front-ends) in lock-step groups
 //   pl_estimate_batch_devices      ... spread over several devices from one process
 //   pl_estimate_batch_dev          ... with the correspondences in the caller's device memory (pl_device_points per item)
+//   pl_estimate_shared_focal_relative_pose_batch_dev   the shared-focal estimator's items from device memory, in its lock-step groups
 //   pl_last_batch_report           where the items of the last call went
 // ---------------------------------------------------------------------------- batched front-end
 // A persistent pool of host threads (each owns a Context: HIP stream + scratch arena, created on first use and kept
@@ -169,9 +170,17 @@ int run_item_dev(const pl_batch_item_dev &it, const MaskDest *mdest) {
     }
 }
 int run_group_member_alone(GroupItem &g) { return g.ditem ? run_item_dev(*g.ditem, g.mdest) : run_item(*g.item); }
+// ... of pl_estimate_shared_focal_relative_pose_batch_dev: the single _dev entry point on the item's rows - a scored item's ranked
+// blocks as a plain item - with the mask through mdest (run_item_dev's way for kinds 0 - 3); h: the host-side copy of the item
+int run_shared_focal_item_dev(const pl_batch_item_dev &it, pl_batch_item &h, const MaskDest *mdest) {
+    return shared_focal_dev(&it.a, &it.b, nullptr, it.n, h.camera1->params + 1, h.opt, static_cast<pl_camera_pose *>(h.model),
+                            &h.camera1->params[0], h.inliers, nullptr, mdest, h.stats, nullptr);
+}
 // what pl_estimate_batch_dev hands to estimate_batch_on next to the host-side copies of its items (a == b == null)
 struct DeviceBatch {
     const pl_batch_item_dev *items;
+    const char *entry = "pl_estimate_batch_dev";
+    bool shared_focal = false; // pl_estimate_shared_focal_relative_pose_batch_dev: kind-4 items, which this route alone runs - in focal groups
     std::vector<int> decided;       // per item: PL_OK, or the status it got before anything ran (unsupported kind, rejected descriptor)
     std::vector<std::string> cause; // ... and why
     const MaskDest *masks = nullptr; // pl_estimate_batch_dev_masked: per item, where its inlier mask goes in the caller's device memory
@@ -245,7 +254,7 @@ void run_focal_group_job(std::vector<FocalGroupItem *> &items) {
             if (g->est == 0 && g->cam_saved) // (the camera is in / out: the group may have written the loop's focal length already)
                 for (int i = 0; i < g->item->camera1->num_params && i < 12; ++i)
                     g->item->camera1->params[i] = g->cam.p[i];
-            g->item->status = run_item(*g->item);
+            g->item->status = g->dev ? run_shared_focal_item_dev(g->dev->items[g->index], *g->item, g->dev->mask_of(g->index)) : run_item(*g->item);
             ++g_n_fallback;
             note_fallback_item();
             if (g->item->status != PL_OK)
@@ -424,7 +433,7 @@ int pl_ransac_batch(pl_ransac_item *items, size_t count, int max_in_flight, int 
 
 // pl_estimate_batch on one device (dev: the call is pl_estimate_batch_dev, `items` are the host-side copies of its items)
 static int estimate_batch_on(int device, pl_batch_item *items, size_t count, int max_in_flight, const DeviceBatch *dev = nullptr) {
-    const char *entry = dev ? "pl_estimate_batch_dev" : "pl_estimate_batch";
+    const char *entry = dev ? dev->entry : "pl_estimate_batch";
     int rc = device_usable(device); // fails loudly without a HIP device
     if (rc != PL_OK)
         return rc;
@@ -443,7 +452,7 @@ static int estimate_batch_on(int device, pl_batch_item *items, size_t count, int
         int est;
         if (!no_groups && group_eligible(items[i], dev != nullptr))
             by_kind[items[i].kind].push_back(i);
-        else if (!no_groups && !dev && (est = focal_group_estimator(items[i])) >= 0)
+        else if (!no_groups && (!dev || dev->shared_focal) && (est = focal_group_estimator(items[i], dev != nullptr)) >= 0)
             by_focal[est].push_back(i); // the two focal-length estimators: their own lock-step groups (driver_focal_group.inc)
         else
             solo.push_back(i);
@@ -551,6 +560,11 @@ static int estimate_batch_on(int device, pl_batch_item *items, size_t count, int
                 FocalGroupItem g;
                 g.item = &items[v[j]];
                 g.est = est;
+                if (dev) { // (est 1: the rows - ranked blocks for a scored item - and the mask's destination in device memory)
+                    g.src_a = &dev->items[v[j]].a, g.src_b = &dev->items[v[j]].b;
+                    g.mdest = dev->mask_of(v[j]);
+                    g.dev = dev, g.index = v[j];
+                }
                 if (est == 0 && g.item->camera1) { // snapshot before any worker touches the item (an error path restores from it)
                     g.cam = to_cam(g.item->camera1);
                     g.cam_saved = true;
@@ -571,7 +585,9 @@ static int estimate_batch_on(int device, pl_batch_item *items, size_t count, int
         jobs.emplace_back([items, i, dev] {
             if (dev && dev->decided[i] != PL_OK)
                 return;
-            items[i].status = dev ? run_item_dev(dev->items[i], dev->mask_of(i)) : run_item(items[i]);
+            items[i].status = !dev                ? run_item(items[i])
+                              : dev->shared_focal ? run_shared_focal_item_dev(dev->items[i], items[i], dev->mask_of(i))
+                                                  : run_item_dev(dev->items[i], dev->mask_of(i));
             if (items[i].status != PL_OK)
                 note_worker_error();
         });
@@ -705,8 +721,11 @@ int pl_estimate_batch_devices(pl_batch_item *items, size_t count, const int *dev
 // (masks: null, or count entries - pl_estimate_batch_dev_masked: an item whose entry has data gets its inlier mask there, in device
 // memory.  All such destinations are zero-filled by one launch in front of everything; the mask launch of the item's group, or of
 // its single run, then writes the flags itself - a scored item's through the permutation its ranking left on the device)
+// (shared_focal: the call is pl_estimate_shared_focal_relative_pose_batch_dev and `items` its records as kind-4 items - camera1:
+// SIMPLE_PINHOLE {focal, pp}, null where the record's focal pointer is.  This route alone takes kind 4, says of every item what its
+// single _dev call would, and lets estimate_batch_on form focal groups of items in device memory)
 static int estimate_batch_dev_impl(pl_batch_item_dev *items, const pl_device_scores *scores, size_t *n_used, size_t count,
-                                   int max_in_flight, const pl_device_mask *masks = nullptr) {
+                                   int max_in_flight, const pl_device_mask *masks = nullptr, bool shared_focal = false) {
     if (count == 0)
         return PL_OK;
     if (!items)
@@ -718,6 +737,9 @@ static int estimate_batch_dev_impl(pl_batch_item_dev *items, const pl_device_sco
             n_used[i] = 0;
     DeviceBatch dev;
     dev.items = items;
+    dev.shared_focal = shared_focal;
+    if (shared_focal)
+        dev.entry = "pl_estimate_shared_focal_relative_pose_batch_dev";
     dev.decided.assign(count, PL_OK);
     dev.cause.resize(count);
     auto decide = [&](size_t i, int rc) { // (rc came from fail(): g_err holds the cause)
@@ -727,18 +749,24 @@ static int estimate_batch_dev_impl(pl_batch_item_dev *items, const pl_device_sco
     auto first_decided = [&]() -> int {
         for (size_t i = 0; i < count; ++i)
             if (dev.decided[i] != PL_OK)
-                return fail(dev.decided[i], ("pl_estimate_batch_dev: item " + std::to_string(i) + ": " + dev.cause[i]).c_str());
+                return fail(dev.decided[i], (std::string(dev.entry) + ": item " + std::to_string(i) + ": " + dev.cause[i]).c_str());
         return PL_OK;
     };
     for (size_t i = 0; i < count; ++i) {
         pl_batch_item_dev &it = items[i];
         it.status = PL_OK;
-        if (it.kind < 0 || it.kind > 5) {
+        if (shared_focal) { // (what pl_estimate_shared_focal_relative_pose_dev says before it looks at the points)
+            const int rc0 = !it.model || !it.camera1 ? fail(PL_ERR_INVALID, "null argument") : validate_options(it.opt);
+            if (rc0 != PL_OK) {
+                decide(i, rc0);
+                continue;
+            }
+        } else if (it.kind < 0 || it.kind > 5) {
             decide(i, fail(PL_ERR_INVALID, "pl_batch_item_dev.kind must be 0..3"));
             continue;
-        }
-        if (it.kind == 4 || it.kind == EST_RAD1D) {
-            decide(i, fail(PL_ERR_UNSUPPORTED, it.kind == 4 ? "shared-focal relative pose (kind 4) is not served from device memory: use pl_estimate_batch"
+        } else if (it.kind == 4 || it.kind == EST_RAD1D) {
+            decide(i, fail(PL_ERR_UNSUPPORTED, it.kind == 4 ? "shared-focal relative pose (kind 4) is not served from device memory: use pl_estimate_batch, "
+                                                              "or pl_estimate_shared_focal_relative_pose_batch_dev"
                                                             : "1D-radial absolute pose (kind 5) is not served from device memory: use pl_estimate_batch"));
             continue;
         }
@@ -889,4 +917,36 @@ int pl_estimate_batch_dev_scored(pl_batch_item_dev *items, const pl_device_score
 int pl_estimate_batch_dev_masked(pl_batch_item_dev *items, const pl_device_scores *scores, const pl_device_mask *masks, size_t *n_used,
                                  size_t count, int max_in_flight) {
     return estimate_batch_dev_impl(items, scores, n_used, count, max_in_flight, masks);
+}
+
+int pl_estimate_shared_focal_relative_pose_batch_dev(pl_shared_focal_item_dev *items, const pl_device_scores *scores,
+                                                     const pl_device_mask *masks, size_t *n_used, size_t count, int max_in_flight) {
+    if (count == 0)
+        return PL_OK;
+    if (!items)
+        return fail(PL_ERR_INVALID, "items pointer is null");
+    // the records as kind-4 items: both cameras of the pair are one SIMPLE_PINHOLE {focal, pp}, in and out
+    std::vector<pl_batch_item_dev> its(count);
+    std::vector<pl_camera> cams(count);
+    for (size_t i = 0; i < count; ++i) {
+        const pl_shared_focal_item_dev &s = items[i];
+        pl_camera &cam = cams[i];
+        std::memset(&cam, 0, sizeof(cam));
+        cam.model_id = CAM_SIMPLE_PINHOLE;
+        cam.num_params = 3;
+        cam.params[0] = s.focal ? *s.focal : 1.0, cam.params[1] = s.pp[0], cam.params[2] = s.pp[1];
+        pl_batch_item_dev &it = its[i];
+        std::memset(&it, 0, sizeof(it));
+        it.kind = 4;
+        it.a = s.x1, it.b = s.x2, it.n = s.n;
+        it.opt = s.opt, it.camera1 = s.focal ? &cam : nullptr;
+        it.model = s.pose, it.inliers = s.inliers, it.stats = s.stats;
+    }
+    const int rc = estimate_batch_dev_impl(its.data(), scores, n_used, count, max_in_flight, masks, /*shared_focal=*/true);
+    for (size_t i = 0; i < count; ++i) {
+        items[i].status = its[i].status;
+        if (its[i].status == PL_OK)
+            *items[i].focal = cams[i].params[0];
+    }
+    return rc;
 }

@@ -7,6 +7,9 @@
 //
 //   stage A  front-end arithmetic per item on the host (front_begin, like the single-problem entry points), the raw
 //            correspondences of all members -> one pinned block -> one upload; k_prepare_g (un-projection / normalisation)
+//            (pl_estimate_shared_focal_relative_pose_batch_dev, members in the caller's device memory: no host pass and no upload of
+//            points - k_ingest_g, k_point_stats_g about the members' principal points, then k_prepare_g with the scale read from
+//            the member's record on the device; the host reads the records after the stage's one synchronisation)
 //   rounds   every member's loop (pl_focal.h FocalLoop - the code the single-problem path runs) is advanced to its next request;
 //            the requests of all members are evaluated together - a batch of iterations for the members that ask for one
 //            (k_*_setup_g + k_*_solve_g + k_*_score_g, blockIdx.y = member), the local optimisations of the others as ONE launch over
@@ -21,8 +24,18 @@
 constexpr uint32_t kFocalGroupMax = 64;  // members per launch sequence (pnpf: 8.8 KB of solver workspace per iteration and member)
 constexpr uint32_t kSFocalGroupMax = 32; // (shared focal: 60 model slots per iteration are mirrored in pinned memory, 3.8 KB per iteration)
 
+struct DeviceBatch; // (driver_batch.inc)
 struct FocalGroupItem {
     pl_batch_item *item = nullptr;
+    // pl_estimate_shared_focal_relative_pose_batch_dev (est 1): the member's rows in the caller's device memory - or, for a scored
+    // member, the contiguous fp64 blocks its ranking left - and, optionally, where its mask goes there.  dev / index: the call and
+    // the item's place in it (a member its group hands back runs through the single _dev entry point)
+    const pl_device_points *src_a = nullptr, *src_b = nullptr;
+    const MaskDest *mdest = nullptr;
+    const DeviceBatch *dev = nullptr;
+    size_t index = 0;
+    const double *raw_a = nullptr, *raw_b = nullptr; // ... the fp64 AoS blocks k_prepare_g reads (stage A)
+    const PointStatsRecord *d_rec = nullptr, *h_rec = nullptr; // ... the member's record of k_point_stats_g: device address, host address
     int est = 0; // 0: absolute pose with unknown focal length, 1: shared-focal relative pose
     uint32_t n = 0;
     bool fallback = false;
@@ -51,13 +64,14 @@ struct FocalGroupContext { // per host thread AND device, kept for later groups
     int device = -1;
     DevBuf pts, raw, args, models, num_models, stage, lm_scratch;
     HostBuf h_raw, h_args, h_pos, h_smp, h_out, h_rout, h_tasks, h_mask; // (h_smp: the PROSAC members' explicit samples of a round)
+    HostBuf h_dev_tab; // members in device memory: the tables of k_ingest_g / k_point_stats_g and the members' records
     void release() {
         for (DevBuf *b : {&pts, &raw, &args, &models, &num_models, &stage, &lm_scratch}) {
             if (b->p)
                 (void)hipFree(b->p);
             b->p = nullptr, b->cap = 0;
         }
-        for (HostBuf *b : {&h_raw, &h_args, &h_pos, &h_smp, &h_out, &h_rout, &h_tasks, &h_mask}) {
+        for (HostBuf *b : {&h_raw, &h_args, &h_pos, &h_smp, &h_out, &h_rout, &h_tasks, &h_mask, &h_dev_tab}) {
             if (b->p)
                 (void)hipHostFree(b->p);
             b->p = b->dp = nullptr, b->cap = 0;
@@ -66,9 +80,10 @@ struct FocalGroupContext { // per host thread AND device, kept for later groups
 };
 thread_local FocalGroupContext *g_focal_group_ctx = nullptr;
 
-// which focal estimator a batch item is, -1: none the group path covers
-int focal_group_estimator(const pl_batch_item &it) {
-    if (!it.opt || !it.model || !it.a || !it.b || !it.camera1)
+// which focal estimator a batch item is, -1: none the group path covers (dev: the host-side copy of an item whose points are in
+// device memory - a == b == null)
+int focal_group_estimator(const pl_batch_item &it, bool dev = false) {
+    if (!it.opt || !it.model || !it.camera1 || (!dev && (!it.a || !it.b)))
         return -1;
     const pl_robust_options &o = *it.opt;
     if (o.ransac.score_initial_model)
@@ -199,6 +214,15 @@ struct SFocalGroupPolicy {
     }
 };
 
+// the loop's options and its start from the front-end's scaled options
+void focal_group_loop_setup(FocalGroupItem &g) {
+    g.lo = focal_loop_options(g.fe.scaled, g.max_focal); // (no warm starts among the members: score_initial_model is 0)
+    g.thr2 = g.fe.scaled.max_error * g.fe.scaled.max_error;
+    g.lm_lo = lo_options(g.fe.scaled.max_error);
+    std::memset(&g.best, 0, sizeof(g.best)); // ransac.cc:61-66 / 185-190
+    g.best.q[0] = 1.0;
+    g.best.f = 1.0;
+}
 // stage A, host half: what pl_estimate_absolute_pose / pl_estimate_shared_focal_relative_pose compute before the loop
 void focal_group_prepare_item(FocalGroupItem &g) {
     pl_batch_item &it = *g.item;
@@ -218,13 +242,32 @@ void focal_group_prepare_item(FocalGroupItem &g) {
         fe.scaled.bundle.loss_scale /= fe.scale;
         g.max_focal = -1.0;
     }
-    g.lo = focal_loop_options(fe.scaled, g.max_focal); // (no warm starts among the members: score_initial_model is 0)
-    g.thr2 = fe.scaled.max_error * fe.scaled.max_error;
-    g.lm_lo = lo_options(fe.scaled.max_error);
-    std::memset(&g.best, 0, sizeof(g.best)); // ransac.cc:61-66 / 185-190
-    g.best.q[0] = 1.0;
-    g.best.f = 1.0;
+    focal_group_loop_setup(g);
 }
+// ... of a shared-focal member whose rows are in device memory: everything but the scale in front of stage A's launches (the
+// prepare entry takes the scale from the member's record on the device), the rest - focal_group_prepare_item's code, with the
+// reduction's result in place of normalization_about's - once the record is back
+void focal_group_begin_device_item(FocalGroupItem &g) {
+    pl_batch_item &it = *g.item;
+    g.n = (uint32_t)it.n;
+    g.st = it.stats ? it.stats : &g.local_st;
+    g.fe = FrontEnd();
+    g.fe.kind = kFrontSharedFocal;
+    g.fe.scaled = *it.opt;
+    const double *pp = it.camera1->params + 1;
+    prepare_about(pp[0], pp[1], 0.0, g.fe.prep);
+    g.max_focal = -1.0;
+}
+void focal_group_scale_from_device(FocalGroupItem &g) {
+    FrontEnd &fe = g.fe;
+    fe.scale = fe.prep.scale = g.h_rec->scale;
+    fe.scaled.max_error /= fe.scale;
+    fe.scaled.bundle.loss_scale /= fe.scale;
+    focal_group_loop_setup(g);
+}
+// k_ingest_g and k_point_stats_g (about the members' principal points) of a group of such members, enqueued on the context's
+// stream; sets the members' raw_a / raw_b / d_rec / h_rec (driver_scored.inc)
+int focal_group_stage_device(Context *c, FocalGroupContext &gc, FocalGroupItem *const *pit, uint32_t count);
 
 // ---- the tail of the two front-ends: the loop's result into the caller's records, the final bundle's task, its result ----
 void focal_group_loop_result(FocalGroupItem &g) {
@@ -311,13 +354,14 @@ template <class P> int run_focal_group(Context *c, FocalGroupItem *const *pit, u
     }
 
     // ---- stage A ----
+    const bool from_device = pit[0]->src_a != nullptr; // (a group is all-device or all-host)
     uint32_t max_n = 0;
     size_t raw_doubles = 0, pts_bytes = 0;
     std::vector<size_t> pts_off(count), raw_pts_off(count), mask_off(count);
     for (uint32_t i = 0; i < count; ++i) {
         FocalGroupItem &g = *pit[i];
         g.t_start = now_s();
-        focal_group_prepare_item(g);
+        from_device ? focal_group_begin_device_item(g) : focal_group_prepare_item(g);
         max_n = std::max(max_n, g.n);
         g.raw_a_off = raw_doubles;
         raw_doubles += 2 * (size_t)g.n;
@@ -340,10 +384,16 @@ template <class P> int run_focal_group(Context *c, FocalGroupItem *const *pit, u
     const size_t args_bytes = std::max({sizeof(PrepareGroupArgs) * prep_entries, sec_end, sizeof(FocalMaskArgs) * count});
     HIP_TRY(gc.pts.ensure(pts_bytes));
     HIP_TRY(gc.raw.ensure(sizeof(double) * raw_doubles));
-    HIP_TRY(gc.h_raw.ensure(sizeof(double) * raw_doubles));
+    if (!from_device)
+        HIP_TRY(gc.h_raw.ensure(sizeof(double) * raw_doubles));
     HIP_TRY(gc.args.ensure(args_bytes));
     HIP_TRY(gc.h_args.ensure(args_bytes));
     HIP_TRY(gc.h_mask.ensure(align_up(max_n) * count));
+    if (from_device) {
+        const int rc = focal_group_stage_device(c, gc, pit, count);
+        if (rc != PL_OK)
+            return rc;
+    }
     {
         double *h_raw = gc.h_raw.as<double>();
         PrepareGroupArgs *hp = gc.h_args.as<PrepareGroupArgs>();
@@ -352,8 +402,11 @@ template <class P> int run_focal_group(Context *c, FocalGroupItem *const *pit, u
         raw_cam.model_id = CAM_NULL; // pixels as they are
         for (uint32_t i = 0; i < count; ++i) {
             FocalGroupItem &g = *pit[i];
-            std::memcpy(h_raw + g.raw_a_off, g.item->a, sizeof(double) * 2 * g.n);
-            std::memcpy(h_raw + g.raw_b_off, g.item->b, sizeof(double) * P::kDb * g.n);
+            if (!from_device) {
+                std::memcpy(h_raw + g.raw_a_off, g.item->a, sizeof(double) * 2 * g.n);
+                std::memcpy(h_raw + g.raw_b_off, g.item->b, sizeof(double) * P::kDb * g.n);
+                g.raw_a = gc.raw.as<double>() + g.raw_a_off, g.raw_b = gc.raw.as<double>() + g.raw_b_off;
+            }
             auto problem_at = [&](pl_problem &p, size_t off) {
                 p.kind = P::kKind;
                 p.device = c->device;
@@ -367,13 +420,14 @@ template <class P> int run_focal_group(Context *c, FocalGroupItem *const *pit, u
                 p.ps.xy_absmax = std::numeric_limits<float>::infinity();
             };
             auto entry = [&](PrepareGroupArgs &e, const PrepareArgs &pa, const pl_problem &p) {
-                e.a_raw = gc.raw.as<double>() + g.raw_a_off;
-                e.b_raw = gc.raw.as<double>() + g.raw_b_off;
+                e.a_raw = g.raw_a;
+                e.b_raw = g.raw_b;
                 e.n = g.n;
                 e.pad = 0;
                 e.args = pa;
                 e.soa = p.d_pts;
                 e.absmax_bits = nullptr;
+                e.stats = g.d_rec; // (device members: the scale comes from the record the launch in front of this one writes)
             };
             problem_at(g.prob, pts_off[i]);
             entry(hp[i], g.fe.prep, g.prob);
@@ -383,11 +437,15 @@ template <class P> int run_focal_group(Context *c, FocalGroupItem *const *pit, u
             }
             g.d_mask = gc.pts.as<uint8_t>() + mask_off[i];
         }
-        HIP_TRY(hipMemcpyAsync(gc.raw.p, h_raw, sizeof(double) * raw_doubles, hipMemcpyHostToDevice, c->stream));
+        if (!from_device)
+            HIP_TRY(hipMemcpyAsync(gc.raw.p, h_raw, sizeof(double) * raw_doubles, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipMemcpyAsync(gc.args.p, hp, sizeof(PrepareGroupArgs) * prep_entries, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(launch_group_prepare(gc.args.as<PrepareGroupArgs>(), prep_entries, max_n, c->stream));
         // (the pinned table is rewritten below before the device has read it: wait - the first round's host work is short)
         HIP_TRY(wait_stream(c));
+        if (from_device) // the stage's one synchronisation is behind us: the scales, and what the host forms from them
+            for (uint32_t i = 0; i < count; ++i)
+                focal_group_scale_from_device(*pit[i]);
     }
 
     // ---- the loops ----
@@ -593,7 +651,10 @@ template <class P> int run_focal_group(Context *c, FocalGroupItem *const *pit, u
             ma.model = g.best;
             ma.thr2 = g.thr2;
             ma.mask = g.d_mask;
-            ma.host_mask = gc.h_mask.dev<uint8_t>() + mask_stride * i;
+            if (g.mdest) // the caller's device memory, written by the mask launch itself: no pinned mirror, nothing to copy out below
+                ma.dst = g.mdest->data, ma.dst_stride = g.mdest->stride, ma.dst_order = g.mdest->order;
+            else
+                ma.host_mask = gc.h_mask.dev<uint8_t>() + mask_stride * i;
         }
         HIP_TRY(hipMemcpyAsync(gc.args.p, hm, sizeof(FocalMaskArgs) * count, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(P::mask(gc.args.as<FocalMaskArgs>(), count, max_n, c->stream));
@@ -618,7 +679,7 @@ template <class P> int run_focal_group(Context *c, FocalGroupItem *const *pit, u
         const Task *ht = gc.h_tasks.as<Task>();
         for (uint32_t i = 0; i < count; ++i) {
             FocalGroupItem &g = *pit[i];
-            if (g.item->inliers && g.n)
+            if (g.item->inliers && g.n && !g.mdest)
                 std::memcpy(g.item->inliers, gc.h_mask.as<uint8_t>() + mask_stride * i, g.n);
             focal_group_finish_item(g, task_of[i] >= 0 ? &ht[task_of[i]] : nullptr);
             g.st->seconds = now_s() - g.t_start;

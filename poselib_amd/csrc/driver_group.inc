@@ -596,6 +596,7 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
             hp[i].b_raw = g.raw_b;
             hp[i].n = g.n;
             hp[i].pad = 0;
+            hp[i].stats = nullptr;
             hp[i].args = g.fe.prep;
             hp[i].soa = reinterpret_cast<double *>(slot(i, L.pts));
             // (the bound of max|x| comes from the host for the linear cameras; non-linear ones: k_prepare_g leaves it in the slot)
@@ -1049,6 +1050,7 @@ int run_group(Context *c, GroupItem *const *pit, uint32_t count, bool resident =
         h.args = prepare_unproject(raw_cam, nullptr);
         h.soa = reinterpret_cast<double *>(slot(i, L.pts2));
         h.absmax_bits = nullptr;
+        h.stats = nullptr;
     };
     // ---- stage D: final refinement of the best model, choice refined / incumbent, inlier mask (ransac_impl.h:190-198;
     // ransac.cc:55, 152, 259, 311) ----

@@ -444,9 +444,89 @@ int pl_debug_point_stats_about_dev(const pl_device_points *x1, const pl_device_p
     return PL_OK;
 }
 
-int pl_estimate_shared_focal_relative_pose_dev(const pl_device_points *x1, const pl_device_points *x2, const pl_device_scores *scores,
-                                               size_t n, const double *pp, const pl_robust_options *opt, pl_camera_pose *pose, double *focal,
-                                               uint8_t *inliers, const pl_device_mask *mask, pl_ransac_stats *stats, size_t *n_used) {
+namespace {
+
+// The members of one launch of the about-a-centre reduction (k_point_stats_g, norm 2) with the k_ingest_g launch in front of it:
+// the stage of pl_estimate_shared_focal_relative_pose_batch_dev's groups and the diagnostic entry below - one piece of code.
+struct AboutStatsMember {
+    const pl_device_points *a, *b; // N x 2 each, checked
+    size_t n;                      // 0: no work, no record
+    double cx, cy;
+    const double *raw_a = nullptr, *raw_b = nullptr; // (out) the fp64 AoS blocks: a slice of `raw`, or the caller's memory where it is one
+};
+// Enqueues both launches on the context's stream.  tab (pinned): [records | stats table | ingest table]; raw: room for the sets
+// that are not contiguous fp64.  h_rec / d_rec: the records, member after member, as the host and the device address them.
+int enqueue_about_stats_g(Context *c, HostBuf &tab, DevBuf &raw, AboutStatsMember *m, uint32_t count, PointStatsRecord **h_rec,
+                          PointStatsRecord **d_rec) {
+    size_t raw_doubles = 0;
+    for (uint32_t i = 0; i < count; ++i)
+        raw_doubles += (reads_in_place(m[i].a) ? 0 : 2 * m[i].n) + (reads_in_place(m[i].b) ? 0 : 2 * m[i].n);
+    HIP_TRY(raw.ensure(sizeof(double) * std::max<size_t>(raw_doubles, 1)));
+    const size_t table_bytes = (sizeof(IngestGroupArgs) + sizeof(PointStatsGroupArgs) + sizeof(PointStatsRecord)) * count;
+    HIP_TRY(tab.ensure(table_bytes));
+    PointStatsRecord *rec = tab.as<PointStatsRecord>();
+    PointStatsGroupArgs *hs = reinterpret_cast<PointStatsGroupArgs *>(rec + count);
+    IngestGroupArgs *hi = reinterpret_cast<IngestGroupArgs *>(hs + count);
+    *h_rec = rec;
+    *d_rec = tab.dev<PointStatsRecord>();
+    PointStatsGroupArgs *d_hs = reinterpret_cast<PointStatsGroupArgs *>(*d_rec + count);
+    IngestGroupArgs *d_hi = reinterpret_cast<IngestGroupArgs *>(d_hs + count);
+    std::memset(rec, 0, table_bytes);
+    size_t at = 0;
+    uint32_t ingest_n = 0;
+    for (uint32_t i = 0; i < count; ++i) {
+        AboutStatsMember &r = m[i];
+        if (r.n == 0)
+            continue;
+        double *oa = nullptr, *ob = nullptr;
+        if (!reads_in_place(r.a))
+            oa = raw.as<double>() + at, at += 2 * r.n;
+        if (!reads_in_place(r.b))
+            ob = raw.as<double>() + at, at += 2 * r.n;
+        if (oa || ob) {
+            hi[i].a = ingest_src(r.a), hi[i].b = ingest_src(r.b);
+            hi[i].n = (uint32_t)r.n;
+            hi[i].out_a = oa, hi[i].out_b = ob;
+            ingest_n = std::max(ingest_n, (uint32_t)r.n);
+        }
+        r.raw_a = oa ? oa : static_cast<const double *>(r.a->data);
+        r.raw_b = ob ? ob : static_cast<const double *>(r.b->data);
+        hs[i].a_raw = r.raw_a, hs[i].b_raw = r.raw_b;
+        hs[i].n = (uint32_t)r.n;
+        hs[i].out = *d_rec + i;
+        hs[i].args.norm = 2;
+        hs[i].args.cx1 = hs[i].args.cx2 = r.cx, hs[i].args.cy1 = hs[i].args.cy2 = r.cy;
+        point_stats_sizes(hs[i].args, r.n);
+    }
+    HIP_TRY(launch_ingest_g(d_hi, count, ingest_n, c->stream));
+    HIP_TRY(launch_point_stats_g(d_hs, count, c->stream));
+    return PL_OK;
+}
+
+int focal_group_stage_device(Context *c, FocalGroupContext &gc, FocalGroupItem *const *pit, uint32_t count) {
+    std::vector<AboutStatsMember> m(count);
+    for (uint32_t i = 0; i < count; ++i) {
+        const FocalGroupItem &g = *pit[i];
+        const double *pp = g.item->camera1->params + 1;
+        m[i].a = g.src_a, m[i].b = g.src_b, m[i].n = g.n, m[i].cx = pp[0], m[i].cy = pp[1];
+    }
+    PointStatsRecord *h_rec = nullptr, *d_rec = nullptr;
+    const int rc = enqueue_about_stats_g(c, gc.h_dev_tab, gc.raw, m.data(), count, &h_rec, &d_rec);
+    if (rc != PL_OK)
+        return rc;
+    for (uint32_t i = 0; i < count; ++i) {
+        FocalGroupItem &g = *pit[i];
+        g.raw_a = m[i].raw_a, g.raw_b = m[i].raw_b;
+        g.h_rec = h_rec + i, g.d_rec = d_rec + i;
+    }
+    return PL_OK;
+}
+
+// pl_estimate_shared_focal_relative_pose_dev.  ranked_dest: the call is a scored item of the batch form on the blocks its ranking
+// left (scores == mask == null) and its mask goes to the caller's device memory through the ranking's permutation
+int shared_focal_dev(const pl_device_points *x1, const pl_device_points *x2, const pl_device_scores *scores, size_t n, const double *pp,
+                     const pl_robust_options *opt, pl_camera_pose *pose, double *focal, uint8_t *inliers, const pl_device_mask *mask,
+                     const MaskDest *ranked_dest, pl_ransac_stats *stats, size_t *n_used) {
     if (n_used)
         *n_used = 0;
     if (!pp || !pose || !focal)
@@ -479,11 +559,58 @@ int pl_estimate_shared_focal_relative_pose_dev(const pl_device_points *x1, const
     if (rc == PL_OK) {
         PrepareArgs prep;
         prepare_about(pp[0], pp[1], scale, prep);
-        MaskDestScope scope(rows.mask_dest());
-        rc = shared_focal_run(c, nullptr, nullptr, rows.used, prep, scale, /*resident=*/true, opt, pose, focal, rows.run_mask(inliers), st);
+        MaskDestScope scope(ranked_dest ? ranked_dest : rows.mask_dest());
+        rc = shared_focal_run(c, nullptr, nullptr, rows.used, prep, scale, /*resident=*/true, opt, pose, focal,
+                              ranked_dest ? nullptr : rows.run_mask(inliers), st);
     }
     rows.finish(c, rc == PL_OK ? inliers : nullptr, rc == PL_OK ? n_used : nullptr);
     return rc;
+}
+
+} // namespace
+
+int pl_estimate_shared_focal_relative_pose_dev(const pl_device_points *x1, const pl_device_points *x2, const pl_device_scores *scores,
+                                               size_t n, const double *pp, const pl_robust_options *opt, pl_camera_pose *pose, double *focal,
+                                               uint8_t *inliers, const pl_device_mask *mask, pl_ransac_stats *stats, size_t *n_used) {
+    return shared_focal_dev(x1, x2, scores, n, pp, opt, pose, focal, inliers, mask, nullptr, stats, n_used);
+}
+
+int pl_debug_point_stats_about_group_dev(const pl_device_points *x1, const pl_device_points *x2, const size_t *n, const double *centres,
+                                         size_t count, double *out) {
+    if (!out || !x1 || !x2 || !n || !centres)
+        return fail(PL_ERR_INVALID, "a pointer is null");
+    if (count == 0)
+        return PL_OK;
+    if (count > 65535)
+        return fail(PL_ERR_INVALID, "too many members");
+    int rc = PL_OK;
+    for (size_t i = 0; i < count && rc == PL_OK; ++i) {
+        rc = check_points_plain(&x1[i], n[i], 2);
+        if (rc == PL_OK)
+            rc = check_points_plain(&x2[i], n[i], 2);
+    }
+    Context *c = nullptr;
+    if (rc == PL_OK)
+        rc = get_context(&c);
+    DeviceAllocationCache allocations;
+    for (size_t i = 0; i < count && rc == PL_OK; ++i) {
+        rc = allocations.check(c, &x1[i], n[i]);
+        if (rc == PL_OK)
+            rc = allocations.check(c, &x2[i], n[i]);
+    }
+    if (rc != PL_OK)
+        return rc;
+    std::vector<AboutStatsMember> m(count);
+    for (size_t i = 0; i < count; ++i)
+        m[i].a = &x1[i], m[i].b = &x2[i], m[i].n = n[i], m[i].cx = centres[2 * i], m[i].cy = centres[2 * i + 1];
+    PointStatsRecord *h_rec = nullptr, *d_rec = nullptr;
+    rc = enqueue_about_stats_g(c, c->h_pstats, c->raw_a, m.data(), (uint32_t)count, &h_rec, &d_rec);
+    if (rc != PL_OK)
+        return rc;
+    HIP_TRY(wait_stream(c));
+    for (size_t i = 0; i < count; ++i)
+        out[2 * i] = n[i] ? h_rec[i].scale : 0.0, out[2 * i + 1] = n[i] ? h_rec[i].absmax : 0.0;
+    return PL_OK;
 }
 
 int pl_estimate_1D_radial_absolute_pose_dev(const pl_device_points *points2D, const pl_device_points *points3D, const pl_device_scores *scores,

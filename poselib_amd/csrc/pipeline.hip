@@ -981,8 +981,9 @@ __global__ __launch_bounds__(256) void k_gather_shadow16_g(const GroupArgs *ga, 
 }
 
 // ------------------------------------------------------------------------------------ front-end pre-processing
+// scale: g.scale, or what a group member's record holds in its place (PrepareGroupArgs.stats)
 __device__ __forceinline__ void prepare_body(const double *__restrict__ a_raw, const double *__restrict__ b_raw,
-                                             uint32_t n, const PrepareArgs &g, double *__restrict__ soa,
+                                             uint32_t n, const PrepareArgs &g, double scale, double *__restrict__ soa,
                                              unsigned long long *absmax_bits) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     double m = 0.0;
@@ -991,7 +992,7 @@ __device__ __forceinline__ void prepare_body(const double *__restrict__ a_raw, c
         if (g.mode == 2) {
             if (g.centred)
                 a0 -= g.c1x, a1 -= g.c1y;
-            a0 /= g.scale, a1 /= g.scale;
+            a0 /= scale, a1 /= scale;
         } else {
             double u, v;
             camera_unproject(g.cam1, a0, a1, u, v);
@@ -1010,7 +1011,7 @@ __device__ __forceinline__ void prepare_body(const double *__restrict__ a_raw, c
             if (g.mode == 2) {
                 if (g.centred)
                     b0 -= g.c2x, b1 -= g.c2y;
-                b0 /= g.scale, b1 /= g.scale;
+                b0 /= scale, b1 /= scale;
             } else {
                 double u, v;
                 camera_unproject(g.cam2, b0, b1, u, v);
@@ -1033,7 +1034,7 @@ __device__ __forceinline__ void prepare_body(const double *__restrict__ a_raw, c
 __global__ __launch_bounds__(256) void k_prepare(const double *__restrict__ a_raw, const double *__restrict__ b_raw,
                                                  uint32_t n, PrepareArgs g, double *__restrict__ soa,
                                                  unsigned long long *absmax_bits) {
-    prepare_body(a_raw, b_raw, n, g, soa, absmax_bits);
+    prepare_body(a_raw, b_raw, n, g, g.scale, soa, absmax_bits);
 }
 // mode 3 (tangent Sampson, EST_RELT): robust.cc:256-265 + Camera::unproject_with_jac per image -> the problem's 18 arrays
 // d1[3] d2[3] M1[6] M2[6].  A kernel of its own: the Jacobian's registers stay out of k_prepare / k_prepare_g.
@@ -1062,7 +1063,7 @@ __global__ __launch_bounds__(256) void k_prepare_g(const PrepareGroupArgs *pa) {
         return;
     const PrepareGroupArgs g = globalised(in);
     // (in.args, not g.args: the cameras' parameter arrays are indexed at run time, a private copy of them would live in scratch)
-    prepare_body(g.a_raw, g.b_raw, g.n, in.args, g.soa, g.absmax_bits);
+    prepare_body(g.a_raw, g.b_raw, g.n, in.args, g.stats ? g.stats->scale : in.args.scale, g.soa, g.absmax_bits);
 }
 
 // Un-distortion as a stage of its own (BASELINE config 3: "OPENCV camera model" in front of the homography / 7-point

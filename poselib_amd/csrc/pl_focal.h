@@ -430,6 +430,10 @@ struct FocalMaskArgs { // get_inliers of one member of a group (k_focal_mask_g)
     FocalModel model;
     double thr2;
     uint8_t *mask, *host_mask; // device mask (the final bundle reads it) and its pinned mirror (optional)
+    // k_sfocal_mask_g: the caller's device copy (the members of pl_kernels.h's MaskDest; dst == null: none).  k_focal_mask_g reads none of it
+    uint8_t *dst;
+    int64_t dst_stride;
+    const uint32_t *dst_order;
 };
 
 #if defined(__HIPCC__)

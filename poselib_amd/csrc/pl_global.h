@@ -149,6 +149,7 @@ __device__ __forceinline__ PrepareGroupArgs globalised(PrepareGroupArgs p) {
     p.b_raw = as_global(p.b_raw);
     p.soa = as_global(p.soa);
     p.absmax_bits = as_global(p.absmax_bits);
+    p.stats = as_global(p.stats);
     return p;
 }
 

@@ -33,6 +33,8 @@ __device__ __forceinline__ FocalMaskArgs globalised(FocalMaskArgs a) {
         a.a[d] = as_global(a.a[d]);
     a.mask = as_global(a.mask);
     a.host_mask = as_global(a.host_mask);
+    a.dst = as_global(a.dst);
+    a.dst_order = as_global(a.dst_order);
     return a;
 }
 __device__ __forceinline__ SFocalGenArgs globalised(SFocalGenArgs g) {

@@ -538,6 +538,9 @@ struct PrepareGroupArgs {
     PrepareArgs args;
     double *soa;
     unsigned long long *absmax_bits;
+    // optional (null: args.scale as ever): the member's record of a k_point_stats_g launch in front of this one on the same stream -
+    // the kernel takes args.scale from stats->scale, so the host need not read the record back between the two launches
+    const PointStatsRecord *stats;
 };
 hipError_t launch_group_prepare(const PrepareGroupArgs *args, uint32_t G, uint32_t max_n, hipStream_t stream);
 // (pieces of launch_group_batch that live in pipeline.hip)

@@ -380,7 +380,7 @@ __global__ void k_sfocal_mask(const double *x1, const double *y1, const double *
 __global__ void k_sfocal_mask_g(const FocalMaskArgs *__restrict__ as) {
     const FocalMaskArgs a = globalised(as[blockIdx.y]);
     sfocal_mask_body(a.a[0], a.a[1], a.a[2], a.a[3], a.n, a.model, a.thr2, a.mask, a.host_mask, blockIdx.x * blockDim.x + threadIdx.x,
-                     MaskDest{nullptr, 0, nullptr});
+                     MaskDest{a.dst, a.dst_stride, a.dst_order});
 }
 
 constexpr int kSfLMThreads = 256;
